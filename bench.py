@@ -12,9 +12,20 @@ pass of the hot path over the batch: pplhip_set_inputs -> pplhip_run (32 layers)
 LLMEngine::Execute (reference src/engine/llm_engine.cc:171-236); each step emits 1024 tokens.
 value = 1024 * K / (max over ranks of the wall time of the K timed steps).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line.  Extra objects on the JSON line:
   roofline     -- the dominant kernel (decode attention): algorithmic KV bytes / HIP-event duration vs 8 TB/s
+                  (from the launch events of the timed steps themselves)
+With --full, also (each switchable off by its own --no-* / --*-steps 0 option):
+  breakdown_ms_per_step.gemm, roofline_gemm -- extra, untimed decode steps with every kernel class bracketed
+  ragged_batch -- decode steps at a samples_1024-shaped spread of context lengths
+  prefill_step_ms -- one 8192-token prefill step (TTFT proxy)
+  serving      -- the samples_1024-shaped load through tools/offline_inference (p50 TTFT)
+  online_i8i8  -- the same decode steps in the W8A8 mode, in a process of its own
   cpu_baseline -- the CPU restatement (oracle/, "port") timed on the host cores, on a bounded sample
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0): DIR/tokens.npy (the greedy token ids,
+float64), DIR/token_logprobs.npy (float32) and DIR/logits_sample.npy (float32 logits of a fixed, seeded sample of at most 256
+rows of the batch, LOGITS_SAMPLE_SEED).  Inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import importlib.util
@@ -108,13 +119,28 @@ def ragged_kv_lengths(B, seed=1234, cap=1024):
     return p + (rng.rand(B) * o).astype(np.int64)
 
 
+LOGITS_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, ctx, tok, logprobs, vocab):
+    """the last timed step's outputs as .npy files (float32 / float64, well under 64 MB in all)"""
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(tok)
+    logits = ctx.copy_logits(B)
+    n = min(B, 256, (48 << 20) // (4 * vocab))
+    rows = np.sort(np.random.RandomState(LOGITS_SAMPLE_SEED).choice(B, n, replace=False))
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(tok, dtype=np.float64))
+    np.save(os.path.join(out_dir, "token_logprobs.npy"), np.asarray(logprobs, dtype=np.float32))
+    np.save(os.path.join(out_dir, "logits_sample.npy"), np.ascontiguousarray(logits[rows], dtype=np.float32))
+
+
 def i8i8_leg(args):
     """the same decode steps in the reference's OTHER int8 mode, --quant-method online_i8i8 (W8A8: src/backends/cuda/resource_manager.cc:51-52)
     -- a secondary number beside the W8A16 headline BASELINE.json's configs name; its own process, after this one released the GPU"""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--act-quant", "8", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--kv-len", str(args.kv_len), "--kv-quant", str(args.kv_quant), "--cache-mode", str(args.cache_mode), "--no-cpu-baseline",
-           "--no-serving-leg", "--no-i8i8-leg", "--ragged-steps", "0", "--breakdown"]
+           "--no-serving-leg", "--no-i8i8-leg", "--ragged-steps", "0", "--breakdown", "--full"]
     try:
         out = subprocess.run(cmd, capture_output=True, timeout=600)
         lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -331,18 +357,23 @@ def main():
     ap.add_argument("--act-quant", type=int, default=0, choices=[0, 8],
                     help="8 = the reference's --quant-method online_i8i8 (W8A8); NOT the configuration of the headline metric")
     ap.add_argument("--layers", type=int, default=0, help="debug only: override the layer count (result is then INVALID)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (GEMM breakdown steps, ragged batch, prefill sample, serving, online_i8i8, CPU "
+                         "baseline); a plain run only times the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (tokens, their log-probabilities, a seeded sample of logits rows) as .npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-serving-leg", action="store_true", help="skip the samples_1024-shaped serving run (TTFT)")
     ap.add_argument("--no-paced-leg", action="store_true", help="serving leg: skip the second run at 64 requests/s")
     ap.add_argument("--breakdown", action="store_true",
                     help="also time the GEMM launches (events around every kernel class: costs the step ~3 %%; default: decode attention only)")
     ap.add_argument("--breakdown-steps", type=int, default=4,
-                    help="extra, untimed decode steps with every kernel class bracketed, for breakdown_ms_per_step.gemm (0: skip)")
+                    help="--full: extra, untimed decode steps with every kernel class bracketed, for breakdown_ms_per_step.gemm (0: skip)")
     ap.add_argument("--no-i8i8-leg", action="store_true",
                     help="skip the secondary run of the same decode step in the reference's other int8 mode (--quant-method online_i8i8)")
-    ap.add_argument("--ragged-steps", type=int, default=4, help="decode steps at a samples_1024-shaped ragged kv_len batch (0: skip)")
+    ap.add_argument("--ragged-steps", type=int, default=4, help="--full: decode steps at a samples_1024-shaped ragged kv_len batch (0: skip)")
     ap.add_argument("--tpb", type=int, default=0)
-    ap.add_argument("--prefill-sample", type=int, default=1, help="also time one 8192-token prefill step (TTFT proxy)")
+    ap.add_argument("--prefill-sample", type=int, default=1, help="--full: also time one 8192-token prefill step (TTFT proxy)")
     ap.add_argument("--cache-mode", type=int, default=0, choices=[0, 1],
                     help="0: contiguous KV ranges (default, as the metric is quoted), 1: paged KV with shuffled 16-token pages")
     ap.add_argument("--emulate-tp", type=int, default=0,
@@ -488,12 +519,14 @@ def run(args, guard, world, rank, local_rank):
         if dist is not None:
             dist.barrier()
 
+    last = {}
+
     def step(i, tok):
         st = P.make_step(tok, seq_starts, np.full(B, args.kv_len + i, dtype=np.int64), cache_idx, B, max_pages=max_pages,
                          req_list_changed=1 if i == 0 else 0)
         ctx.set_inputs(0, st)
         ctx.run(0)
-        out, _ = ctx.sample(B, top_k=1, req_list_changed=(i == 0))
+        out, last["logprobs"] = ctx.sample(B, top_k=1, req_list_changed=(i == 0))
         return out.astype(np.int64)
 
 
@@ -554,6 +587,8 @@ def run(args, guard, world, rank, local_rank):
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         rank_ms = [float(tmin.item()) / max(K, 1) * 1e3, float(t.item()) / max(K, 1) * 1e3]
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, tok, last["logprobs"], desc.vocab_size)
 
     n_attn, ms_attn = ctx.profile_get(P.PROF_ATTN_DECODE)
     n_gemm, ms_gemm = ctx.profile_get(P.PROF_GEMM)
@@ -582,10 +617,10 @@ def run(args, guard, world, rank, local_rank):
 
     # GEMM share of the step: 4 more decode steps, NOT part of the timed region, with every kernel class bracketed by events
     # (an event record is a barrier packet: bracketing inside the timed region would cost it ~3 %)
-    gemm_ms_per_step, gemm_note = None, None
+    gemm_ms_per_step, gemm_note = None, "GEMM not timed (--full: extra bracketed steps; --breakdown: inside the timed region)"
     if args.breakdown:
         gemm_ms_per_step, gemm_note = ms_gemm / K, "events around every kernel class inside the timed region (--breakdown)"
-    elif args.breakdown_steps > 0:
+    elif args.full and args.breakdown_steps > 0:
         ctx.profile_mode(1)
         ctx.profile_reset(0)
         for i in range(W + K, W + K + args.breakdown_steps):
@@ -599,7 +634,7 @@ def run(args, guard, world, rank, local_rank):
 
     # ragged leg: the same batch size at a samples_1024-shaped spread of context lengths (4 .. 1024 in ONE step)
     ragged = None
-    if rag_kv is not None:
+    if args.full and rag_kv is not None:
         r_idx = np.concatenate([[0], np.cumsum(rag_kv + args.ragged_steps + 1)[:-1]]).astype(np.int64)
         tok_r = rng.randint(3, desc.vocab_size, size=B).astype(np.int64)
 
@@ -628,7 +663,7 @@ def run(args, guard, world, rank, local_rank):
                   "attn_decode_frac_of_8TBps": round(bytes_r / (ms_r * 1e-3) / 8e12, 4) if ms_r > 0 else None,
                   "attn_avg_launch_ms": round(ms_r / max(n_r, 1), 4), "algorithmic_bytes_per_launch": int(bytes_r / max(n_r, 1))}
     extra = {}
-    if args.prefill_sample:
+    if args.full and args.prefill_sample:
         # TTFT proxy: one admission step of 16 x 512-token prompts (max_tokens_per_step 8192), cold cache slots
         nreq, plen = 16, 512
         if nreq * plen <= kv_tokens:
@@ -692,17 +727,17 @@ def run(args, guard, world, rank, local_rank):
         if args.emulate_tp > 1:
             res["INVALID"] = f"one rank's slice of a tp{args.emulate_tp} step without its peers (profiling only)"
         ctx.close()   # the serving leg sizes its own KV slab from the free memory
-        if world == 1 and not args.no_serving_leg and not args.layers and not args.emulate_tp:
+        if args.full and world == 1 and not args.no_serving_leg and not args.layers and not args.emulate_tp:
             try:
                 sv = serving_leg(mk, args)
             except Exception as e:
                 sv = {"error": repr(e)}
             res["serving"] = sv
             res["ttft_p50_ms"] = sv.get("ttft_p50_ms")
-        if (world == 1 and not args.no_i8i8_leg and not args.layers and not args.emulate_tp and args.act_quant == 0 and args.weight_quant == 8
+        if (args.full and world == 1 and not args.no_i8i8_leg and not args.layers and not args.emulate_tp and args.act_quant == 0 and args.weight_quant == 8
                 and args.model == "llama2-7b" and B == 1024):
             res["online_i8i8"] = i8i8_leg(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(mk, args.kv_len)
             except Exception as e:  # the baseline is reporting only; never hide the GPU result

@@ -10,7 +10,7 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility
 OBJS=$(cd $C && ls *.o | grep -v k_attn_decode.o | sed "s#^#$C/#")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/tpb/libpplhip.so $OBJS /tmp/tpb/k_attn_decode.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib || exit 1
 for rep in 1 2; do for t in 128 256 512; do
-  PPLHIP_LIB=/tmp/tpb/libpplhip.so PPLHIP_ATTN_TPB=$t python bench.py --steps 10 --warmup 3 --no-serving-leg --no-i8i8-leg --no-cpu-baseline --ragged-steps 6 > /tmp/b.json 2>/tmp/b.err
+  PPLHIP_LIB=/tmp/tpb/libpplhip.so PPLHIP_ATTN_TPB=$t python bench.py --full --steps 10 --warmup 3 --no-serving-leg --no-i8i8-leg --no-cpu-baseline --ragged-steps 6 > /tmp/b.json 2>/tmp/b.err
   python3 - $t >> $O <<'PY'
 import json, sys
 r = json.loads(open('/tmp/b.json').read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out; O=gpurun_out/decode_order_ab.log; : > $O
 timeout 600 python -m pytest tests/test_gpu_ops.py -x -q -k "attention_decode or attention_mixed" 2>&1 | tail -2 >> $O
 for rep in 1 2; do for o in 0 1; do
-  PPLHIP_DECODE_ORDER=$o python bench.py --steps 8 --warmup 3 --no-serving-leg --no-i8i8-leg --ragged-steps 8 > /tmp/b.json 2>/tmp/b.err
+  PPLHIP_DECODE_ORDER=$o python bench.py --full --steps 8 --warmup 3 --no-serving-leg --no-i8i8-leg --ragged-steps 8 > /tmp/b.json 2>/tmp/b.err
   python3 - $o >> $O <<'PY'
 import json, sys
 r = json.loads(open('/tmp/b.json').read().strip().splitlines()[-1])

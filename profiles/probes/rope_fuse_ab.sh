@@ -10,7 +10,7 @@ for rep in 1 2; do for f in 0 1; do
   PPLHIP_ROPE_FUSE=$f python profiles/small_batch_latency.py 1 2 4 8 16 32 64 128 2>&1 | grep "^batch" >> $O
 done; done
 for f in 0 1 0 1; do
-  PPLHIP_ROPE_FUSE=$f python bench.py --steps 12 --warmup 4 --no-serving-leg --no-i8i8-leg --no-cpu-baseline --ragged-steps 4 > /tmp/b.json 2>/tmp/b.err
+  PPLHIP_ROPE_FUSE=$f python bench.py --full --steps 12 --warmup 4 --no-serving-leg --no-i8i8-leg --no-cpu-baseline --ragged-steps 4 > /tmp/b.json 2>/tmp/b.err
   python3 - $f >> $O <<'PY'
 import json, sys
 r = json.loads(open('/tmp/b.json').read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ set -u
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-LEAN="--no-cpu-baseline --no-serving-leg --prefill-sample 0 --ragged-steps 0 --steps 32 --warmup 4"
+LEAN="--full --no-cpu-baseline --no-serving-leg --prefill-sample 0 --ragged-steps 0 --steps 32 --warmup 4"
 for cfg in "1 8 8" "1 0 0" "8 8 8"; do
   set -- $cfg
   tag=b$1_w$2_kv$3

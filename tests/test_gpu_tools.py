@@ -89,14 +89,14 @@ def test_offline_inference_samples_workload_and_prefix_benchmark():
 
 
 def test_reference_engine_and_generator_drive_the_hip_backend_unmodified():
-    """SURVEY.md 8(b) B1/B2 on the device: build/ref_backend_driver is the REFERENCE'S OWN llm_generator.cc + llm_engine.cc
-    (compiled in place from /root/reference/src by `make ref` in the build container, no line changed) over
+    """SURVEY.md 8(b) B1/B2 on the device: oracle/_ref/ref_backend_driver is the REFERENCE'S OWN llm_generator.cc + llm_engine.cc
+    (compiled in place from the reference's src/ by `make -C oracle ref` in build(), no line changed) over
     src/backends/hip_nn -- ppl::nn::Runtime / Tensor / Engine objects on top of libpplhip.  Same synthetic model, same four
     prompts as offline_inference --workload prompts4 (the repo's generator + engine): the generated tokens must be identical,
     at tensor-parallel size 1 and 2 (both ranks on device 0)."""
-    drv = os.path.join(PKG, "build", "ref_backend_driver")
+    drv = os.path.join(ROOT, "oracle", "_ref", "ref_backend_driver")
     if not os.path.exists(drv):
-        pytest.skip("build/ref_backend_driver is built only where the reference tree exists (make ref)")
+        pytest.skip("oracle/_ref/ref_backend_driver is built by build() only where the reference tree exists (oracle/Makefile ref)")
 
     def answers(out):
         return [[int(x) for x in l.split(":")[1].split()] for l in out.splitlines() if l.startswith("Answer tokens:")]
@@ -167,9 +167,9 @@ def test_reference_stack_and_this_tree_agree_on_random_scenarios(tmp_path, seed,
     src/backends/hip, same libpplhip: random prompts with shared prefixes, KV pressure, global and per-request stop tokens,
     early stopping on and off, per-request temperature, penalties, prefix cache -- every token of every request must be identical,
     and so must the set of rejected requests"""
-    drv = os.path.join(PKG, "build", "ref_backend_driver")
+    drv = os.path.join(ROOT, "oracle", "_ref", "ref_backend_driver")
     if not os.path.exists(drv):
-        pytest.skip("build/ref_backend_driver is built only where the reference tree exists (make ref)")
+        pytest.skip("oracle/_ref/ref_backend_driver is built by build() only where the reference tree exists (oracle/Makefile ref)")
     cfg = json.load(open(CFG))
     sc = _random_scenario(np.random.RandomState(seed), cfg["vocab_size"], prefix, penalty, stochastic)
     path = str(tmp_path / "scenario.json")

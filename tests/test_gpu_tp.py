@@ -311,7 +311,7 @@ def test_one_process_per_rank_over_ipc_handles():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PPLHIP_COMM="p2p", PPLHIP_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="1", PPLHIP_P2P_TIMEOUT_MS="30000")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--layers", "2",
-                          "--batch", "64", "--kv-len", "64", "--no-cpu-baseline", "--prefill-sample", "0"], env=env, timeout=900,
+                          "--batch", "64", "--kv-len", "64", "--no-cpu-baseline", "--prefill-sample", "0", "--full"], env=env, timeout=900,
                          capture_output=True)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     line = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -334,8 +334,8 @@ def test_bench_retries_on_another_path_when_the_warm_up_fails_on_the_direct_coll
     env.update(PPLHIP_COMM="p2p", PPLHIP_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="1", PPLHIP_P2P_TIMEOUT_MS="4000", PPLHIP_BENCH_FAIL_WARMUP_ONCE="1",
                PPLHIP_BENCH_FALLBACK_TO="p2p")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--layers", "2",
-                          "--batch", "64", "--kv-len", "64", "--no-cpu-baseline", "--prefill-sample", "0", "--ragged-steps", "0"], env=env, timeout=900,
-                         capture_output=True)
+                          "--batch", "64", "--kv-len", "64", "--no-cpu-baseline", "--prefill-sample", "0", "--ragged-steps", "0", "--full"], env=env,
+                         timeout=900, capture_output=True)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     line = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
     assert len(line) == 1, out.stdout.decode()[-2000:]
