@@ -54,8 +54,9 @@ typedef struct pplhip_model_desc {
     float norm_eps;          /* RMSNorm epsilon (graph attribute in the reference; 1e-5 for LLaMA-2) */
     float rope_theta;        /* 10000 for LLaMA-2 */
     int32_t max_position;    /* size of the host-built cos/sin table */
-    int32_t cache_quant_bit;   /* 0 (fp16 KV) or 8 (int8 KV)            src/generator/llm_generator.cc:131-136 */
-    int32_t cache_quant_group; /* 1 or 8 */
+    int32_t cache_quant_bit;   /* 0 (fp16 KV) or 8 (int8 / fp8 KV)      src/generator/llm_generator.cc:131-136 */
+    int32_t cache_quant_group; /* 1 with bit 0 (fp16); 8 with bit 8 (int8, one fp16 scale per 8 channels); head_dim (32, 64, 128)
+                                  with bit 8: fp8 e4m3fn, one power-of-two fp16 scale per head row (library 1.2; DESIGN.md numerics) */
     int32_t cache_layout;      /* 0..3                                  src/engine/llm_engine.cc:122-166 */
     int32_t cache_mode;        /* 0 contiguous ranges, 1 paged          src/generator/llm_generator.cc:486-560 */
     int32_t page_size;         /* tokens per page when cache_mode == 1 */

@@ -14,6 +14,8 @@
 //   int8 KV: bytes are biased to unsigned (x ^ 0x80), converted with v_cvt_f32_ubyteN and the -128 bias is
 //   folded out algebraically (sum(q) and sum(p*scale) corrections) -- the per-group fp16 scale multiplies the
 //   8-channel partial dot product, not each element.
+//   fp8 KV (KV_FP8): e4m3 bytes -> fp32 exactly (v_cvt_pk_f32_fp8); the row's power-of-two scale multiplies K's score and V's
+//   probability -- both exact in fp32, so the kernel computes attention over the exactly dequantised rows.
 // Numerics: fp32 everywhere, output rounded to fp16 once.  Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
 #include <hip/hip_ext.h>
@@ -78,7 +80,7 @@ static hipError_t launch_decode_t(hipStream_t s, const uint16_t* qkv, const KvAd
     return e;
 }
 
-hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit,
+hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                               const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                               int64_t max_pages, int64_t nb, int H, int Hkv, int D, int64_t max_kv_len, int split,
                               int threads, float* workspace, uint16_t* out, hipEvent_t t0, hipEvent_t t1) {
@@ -90,8 +92,8 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
     if (split < 1) split = 1;
     // grouped-query models: the MFMA kernel (k_attn_prefill.hip) reads each KV row once for the whole head group
     static const bool no_gqa = tune_set("PPLHIP_ATTN_NOGQA");
-    if (attn_decode_gqa_supported(quant_bit, H, Hkv, D) && !no_gqa) {
-        hipError_t e = launch_attn_decode_gqa(s, qkv, kv, quant_bit, seq_starts, start_pos, cache_indices, max_pages, nb, H,
+    if (attn_decode_gqa_supported(kv_fmt, H, Hkv, D) && !no_gqa) {
+        hipError_t e = launch_attn_decode_gqa(s, qkv, kv, kv_fmt, seq_starts, start_pos, cache_indices, max_pages, nb, H,
                                               Hkv, D, split, workspace, out, t0, t1);
         if (e != hipSuccess || split == 1) return e;
         const dim3 rg((unsigned)(nb * H)), rb(D < 64 ? 64 : D);
@@ -101,10 +103,11 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
         return hipGetLastError();
     }
 #define DEC_CASE(QB, DD)                                                                                            \
-    if (quant_bit == QB && D == DD)                                                                                 \
+    if (kv_fmt == QB && D == DD)                                                                                    \
         return launch_decode_t<QB, DD>(s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, nb, H, Hkv,     \
                                        split, threads, workspace, out, t0, t1);
     DEC_CASE(8, 128) DEC_CASE(0, 128) DEC_CASE(8, 64) DEC_CASE(0, 64) DEC_CASE(8, 32) DEC_CASE(0, 32)
+    DEC_CASE(KV_FP8, 128) DEC_CASE(KV_FP8, 64) DEC_CASE(KV_FP8, 32)
 #undef DEC_CASE
     return hipErrorInvalidValue;
 }

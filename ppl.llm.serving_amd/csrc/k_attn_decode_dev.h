@@ -8,11 +8,11 @@ namespace pplhip {
 
 template <int QBIT, int D>
 struct DecodeCfg {
-    static constexpr int ELT = QBIT == 8 ? 1 : 2;
+    static constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;   // int8 and fp8: one byte per channel
     static constexpr int CH = 16 / ELT;       // channels per lane
     static constexpr int LPT = D / CH;        // lanes per token row
     static constexpr int TPW = 64 / LPT;      // token rows per wave-load
-    static constexpr int NG = CH / 8;         // int8: quant groups per lane (group = 8 channels)
+    static constexpr int NG = CH / 8;         // int8: quant groups per lane (group = 8 channels); fp8: one scale per row
 };
 
 constexpr int DEC_UNROLL = 4;
@@ -72,7 +72,7 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
 
     const char* kbase = reinterpret_cast<const char*>(kv.cache) + ((int64_t)hk * kv.sH + ch0) * C::ELT;
     const char* vbase = kbase + kv.sKV * C::ELT;
-    const uint16_t* ksbase = kv.scale + (int64_t)hk * kv.ssH + ch0 / 8;
+    const uint16_t* ksbase = kv.scale + (int64_t)hk * kv.ssH + (QBIT == 8 ? ch0 / 8 : 0);
     const uint16_t* vsbase = ksbase + kv.ssKV;
     const int64_t row_bytes = kv.sN * C::ELT;
 
@@ -122,6 +122,9 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                     ksc[u] = ksbase[slot * kv.ssN];
                     vsc[u] = vsbase[slot * kv.ssN];
                 }
+            } else if constexpr (QBIT == KV_FP8) {  // the row's 2^e
+                ksc[u] = ksbase[slot * kv.ssN];
+                vsc[u] = vsbase[slot * kv.ssN];
             }
         }
         float s[DEC_UNROLL];
@@ -143,6 +146,11 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                     const float sc = h2f((uint16_t)(ksc[u] >> (16 * gi)));
                     d = fmaf(pd, sc, d);
                 }
+            } else if constexpr (QBIT == KV_FP8) {  // e4m3 -> fp32 exactly (v_cvt_pk_f32_fp8); the row's 2^e goes onto the score
+                float kf[16];
+                cvt_fp8x16_f32(kraw[u], kf);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) d = fmaf(q[i], kf[i], d);
             } else {
                 float kf[8];
                 unpack8(kraw[u], kf);
@@ -152,6 +160,7 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
             // reduce over the LPT lanes of the token row
 #pragma unroll
             for (int o = 1; o < LPT; o <<= 1) d += __shfl_xor(d, o, 64);
+            if constexpr (QBIT == KV_FP8) d *= h2f((uint16_t)ksc[u]);   // exact: a power of two
             s[u] = valid[u] ? d * sm_scale : -1e30f;
         }
         float mnew = m;
@@ -184,6 +193,12 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                         acc[gi * 8 + i] = fmaf(ps, vf, acc[gi * 8 + i]);
                     }
                 }
+            } else if constexpr (QBIT == KV_FP8) {  // V's 2^e folded into the probability (exact)
+                const float ps = p * h2f((uint16_t)vsc[u]);
+                float vf[16];
+                cvt_fp8x16_f32(vraw[u], vf);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = fmaf(ps, vf[i], acc[i]);
             } else {
                 float vf[8];
                 unpack8(vraw[u], vf);

@@ -22,6 +22,8 @@
 // Round 6: the two register buffers are consumed as ONE 32-key step (pair_step below) -- a SIMD issues about one instruction per 8.5 cycles
 // from this dependent VALU / LDS / MFMA mix however many waves it holds, so the kernel's time is its instruction count
 // (profiles/r06_gqa_experiments.md): -23 % VALU per key, +13 % bandwidth at config 4's shape.
+// fp8 KV (KV_FP8): K and V fragments come out of v_cvt_scalef32_pk_f16_fp8 with the row's power-of-two scale inside the conversion --
+// exact fp16 numbers, so K and V need no lo image (one MFMA per K piece half, one V image); P stays an exact hi + lo pair.
 // Grid (Hkv, requests, splits); workspace / reduce kernel shared with the multi-head kernel (k_attn_decode.hip).
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                                                                      const int64_t* __restrict__ cache_indices,
                                                                      int64_t max_pages, int H, int Hkv, int split,
                                                                      float* __restrict__ workspace, uint16_t* __restrict__ out) {
-    constexpr int ELT = QBIT == 8 ? 1 : 2;
+    constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;
     constexpr int CH = 16 / ELT;        // channels in one 16-byte piece
     constexpr int LPT = D / CH;         // pieces per row
     constexpr int PPL = LPT / 4;        // pieces per lane and 16-key sub-tile (K and V alike)
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
         const uint16_t* qrow = qkv + seq_starts[b] * rowstride + (int64_t)(hk * grp + (l15 < grp ? l15 : 0)) * D;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-            const int ch = QBIT == 8 ? 16 * (kq + 4 * (ks >> 1)) + 8 * (ks & 1) : 8 * (kq + 4 * ks);
+            const int ch = QBIT != KV_FP16 ? 16 * (kq + 4 * (ks >> 1)) + 8 * (ks & 1) : 8 * (kq + 4 * ks);
             const uint4 v = *reinterpret_cast<const uint4*>(qrow + ch);
             qf[ks] = __builtin_bit_cast(h8, l15 < grp ? v : make_uint4(0, 0, 0, 0));
         }
@@ -188,11 +190,13 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 kraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(kp + (uint32_t)(kk * rowb32 + pc * 16)));
                 if constexpr (QBIT == 8) ksc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ksp) + (uint32_t)((kk * srow32 + pc * 2) * 2)));
             }
+            if constexpr (QBIT == KV_FP8) ksc[p][0] = ksp[(uint32_t)(kk * srow32)];   // one scale per key row
 #pragma unroll
             for (int j = 0; j < PPL; ++j) {
                 const int vk = vkey_l[j] < last ? vkey_l[j] : last;
                 vraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(vp + (uint32_t)(vk * rowb32 + vpc_l[j] * 16)));
                 if constexpr (QBIT == 8) vsc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(vsp) + (uint32_t)((vk * srow32 + vpc_l[j] * 2) * 2)));
+                if constexpr (QBIT == KV_FP8) vsc[p][j] = vsp[(uint32_t)(vk * srow32)];
             }
         } else {  // pages smaller than (or not aligned to) a sub-tile: every row through the page table
             const int64_t kslot = kv_slot(kv, cache_indices, max_pages, b, kbc + kk);
@@ -202,12 +206,14 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 kraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(kbase + kslot * rowb + pc * 16));
                 if constexpr (QBIT == 8) ksc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(ksbase + kslot * srow + pc * 2));
             }
+            if constexpr (QBIT == KV_FP8) ksc[p][0] = ksbase[kslot * srow];
 #pragma unroll
             for (int j = 0; j < PPL; ++j) {
                 const int vk = vkey_l[j] < last ? vkey_l[j] : last;
                 const int64_t vslot = kv_slot(kv, cache_indices, max_pages, b, kbc + vk);
                 vraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(vbase + vslot * rowb + vpc_l[j] * 16));
                 if constexpr (QBIT == 8) vsc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(vsbase + vslot * srow + vpc_l[j] * 2));
+                if constexpr (QBIT == KV_FP8) vsc[p][j] = vsbase[vslot * srow];
             }
         }
     };
@@ -241,6 +247,11 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                     *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, q0 * splat8(sc[0]));
                     *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, q1 * splat8(sc[1]));
                 }
+            } else if constexpr (QBIT == KV_FP8) {  // exact fp16: the hi image alone
+                const float sc = h2f((uint16_t)vsc[P][j]);
+                uint16_t* dst = dstw + (ch0 >> 4) * GQ_VSUB + key * 16;
+                *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, cvt_fp8x8_f16(make_uint2(vraw[P][j].x, vraw[P][j].y), sc));
+                *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, cvt_fp8x8_f16(make_uint2(vraw[P][j].z, vraw[P][j].w), sc));
             } else {
                 *reinterpret_cast<uint4*>(dstw + (ch0 >> 4) * GQ_VSUB + key * 16 + (ch0 & 15)) = vraw[P][j];
             }
@@ -262,6 +273,11 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(lo1, qf[2 * j + 1], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi0, qf[2 * j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi1, qf[2 * j + 1], sacc, 0, 0, 0);
+            } else if constexpr (QBIT == KV_FP8) {
+                const float sc = h2f((uint16_t)ksc[P][0]);
+                const h8 k0 = cvt_fp8x8_f16(make_uint2(kraw[P][j].x, kraw[P][j].y), sc), k1 = cvt_fp8x8_f16(make_uint2(kraw[P][j].z, kraw[P][j].w), sc);
+                sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, qf[2 * j], sacc, 0, 0, 0);
+                sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, qf[2 * j + 1], sacc, 0, 0, 0);
             } else {
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, kraw[P][j]), qf[j], sacc, 0, 0, 0);
             }
@@ -405,20 +421,20 @@ static void gq_set_lds(const void* fn, int bytes) {
     if (done.insert({fn, dev}).second) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-bool attn_decode_gqa_supported(int quant_bit, int H, int Hkv, int D) {
+bool attn_decode_gqa_supported(int kv_fmt, int H, int Hkv, int D) {
     if (Hkv <= 0 || H % Hkv) return false;
     const int grp = H / Hkv;
     if (grp < 4 || grp > 16) return false;
-    if (quant_bit == 8) return D == 128 || D == 64;  // a row must hold >= four 16-byte pieces
-    return quant_bit == 0 && (D == 128 || D == 64 || D == 32);
+    if (kv_fmt == KV_I8G8 || kv_fmt == KV_FP8) return D == 128 || D == 64;  // a row must hold >= four 16-byte pieces
+    return kv_fmt == KV_FP16 && (D == 128 || D == 64 || D == 32);
 }
 
-hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit,
+hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                                   const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                                   int64_t max_pages, int64_t nb, int H, int Hkv, int D, int split, float* workspace,
                                   uint16_t* out, hipEvent_t t0, hipEvent_t t1) {
     if (nb == 0) return hipSuccess;
-    if (!attn_decode_gqa_supported(quant_bit, H, Hkv, D)) return hipErrorInvalidValue;
+    if (!attn_decode_gqa_supported(kv_fmt, H, Hkv, D)) return hipErrorInvalidValue;
     dim3 grid((unsigned)Hkv, (unsigned)nb, (unsigned)split);
     static const int small_min = getenv("PPLHIP_GQA_SMALL_BLOCK_MIN") ? atoi(getenv("PPLHIP_GQA_SMALL_BLOCK_MIN")) : GQ_SMALL_BLOCK_MIN;   // A/B runs
     const bool small = (int64_t)Hkv * nb * split >= small_min;
@@ -433,12 +449,12 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
                                start_pos, cache_indices, max_pages, H, Hkv, split, workspace, out);                              \
     } while (0)
 #define GQ_CASE(QB, DD)                                                                                          \
-    if (quant_bit == QB && D == DD) {                                                                            \
+    if (kv_fmt == QB && D == DD) {                                                                               \
         if (small) { if (kv.mode == 0) GQ_LAUNCH(QB, DD, 0, GQ_WAVES_SMALL); else GQ_LAUNCH(QB, DD, 1, GQ_WAVES_SMALL); } \
         else { if (kv.mode == 0) GQ_LAUNCH(QB, DD, 0, GQ_WAVES_BIG); else GQ_LAUNCH(QB, DD, 1, GQ_WAVES_BIG); }   \
         return hipGetLastError();                                                                                \
     }
-    GQ_CASE(8, 128) GQ_CASE(0, 128) GQ_CASE(8, 64) GQ_CASE(0, 64) GQ_CASE(0, 32)
+    GQ_CASE(8, 128) GQ_CASE(0, 128) GQ_CASE(8, 64) GQ_CASE(0, 64) GQ_CASE(0, 32) GQ_CASE(KV_FP8, 128) GQ_CASE(KV_FP8, 64)
 #undef GQ_CASE
 #undef GQ_LAUNCH
     return hipErrorInvalidValue;

@@ -14,7 +14,8 @@
 //   32 scores of ONE query row (col = lane&15), so the online softmax is lane-local plus two xor-shuffles and
 //   the probabilities are already in MFMA A-operand order for O += P . V (the k-slot permutation this implies
 //   is applied identically to the V^T reads).
-//   int8 KV is dequantised to fp16 while staging (one fp16 rounding of q*scale; DESIGN.md "numerics").
+//   int8 KV is dequantised to fp16 while staging (one fp16 rounding of q*scale; DESIGN.md "numerics"); fp8 KV likewise, with the
+//   row's power-of-two scale inside the conversion -- exact, no rounding.
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
 #include <type_traits>
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                                                                   const int64_t* __restrict__ cache_indices,
                                                                   int64_t max_pages, int64_t b0, int H, int Hkv,
                                                                   int nreq, int nqb, uint16_t* __restrict__ out) {
-    constexpr int ELT = QBIT == 8 ? 1 : 2;
+    constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;
     constexpr int CH = 16 / ELT;           // channels in one 16-byte piece
     constexpr int LPT = D / CH;            // pieces per row
     constexpr int KSTEPS = D / 32;
@@ -174,6 +175,10 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                             ksc[it][e] = *reinterpret_cast<const uint32_t*>(kst + (kk * srow32 + c * 2));
                             vsc[it][e] = *reinterpret_cast<const uint32_t*>(vst + (kk * srow32 + c * 2));
                         }
+                        if constexpr (QBIT == KV_FP8) {   // the row's 2^e
+                            ksc[it][e] = kst[kk * srow32];
+                            vsc[it][e] = vst[kk * srow32];
+                        }
                     }
                 } else {
                     const int k0i = (2 * kp) < last ? (2 * kp) : last, k1i = (2 * kp + 1) < last ? (2 * kp + 1) : last;
@@ -187,6 +192,10 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                         if constexpr (QBIT == 8) {
                             ksc[it][e] = *reinterpret_cast<const uint32_t*>(ksbase + slot * srow + c * 2);
                             vsc[it][e] = *reinterpret_cast<const uint32_t*>(vsbase + slot * srow + c * 2);
+                        }
+                        if constexpr (QBIT == KV_FP8) {
+                            ksc[it][e] = ksbase[slot * srow];
+                            vsc[it][e] = vsbase[slot * srow];
                         }
                     }
                 }
@@ -211,6 +220,12 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                         const h2 ksc2 = __builtin_bit_cast(h2, ksc[it][e]), vsc2 = __builtin_bit_cast(h2, vsc[it][e]);
                         kh[e][0] = k0 * ksc2[0]; kh[e][1] = k1 * ksc2[1];
                         vh[e][0] = v0 * vsc2[0]; vh[e][1] = v1 * vsc2[1];
+                    } else if constexpr (QBIT == KV_FP8) {   // e4m3 x 2^e: exact fp16
+                        const float ks = h2f((uint16_t)ksc[it][e]), vs = h2f((uint16_t)vsc[it][e]);
+                        kh[e][0] = cvt_fp8x8_f16(make_uint2(kraw[it][e].x, kraw[it][e].y), ks);
+                        kh[e][1] = cvt_fp8x8_f16(make_uint2(kraw[it][e].z, kraw[it][e].w), ks);
+                        vh[e][0] = cvt_fp8x8_f16(make_uint2(vraw[it][e].x, vraw[it][e].y), vs);
+                        vh[e][1] = cvt_fp8x8_f16(make_uint2(vraw[it][e].z, vraw[it][e].w), vs);
                     } else {
                         kh[e][0] = __builtin_bit_cast(h8, kraw[it][e]);
                         vh[e][0] = __builtin_bit_cast(h8, vraw[it][e]);
@@ -391,14 +406,14 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
     }
 }
 
-hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit,
+hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                                const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                                int64_t max_pages, int64_t b0, int64_t B, int H, int Hkv, int D, int64_t max_seq_len,
                                uint16_t* out, int64_t max_kv_len, float* ws, size_t ws_bytes, int64_t row0, int64_t nrows) {
     if (B <= b0 || max_seq_len <= 0) return hipSuccess;
     // head_dim 128: the 32-row kernel of k_attn_prefill32.hip (PPLHIP_PREFILL32=0 selects this file's 16-row kernel for A/B runs)
     static const int p32 = tune_int("PPLHIP_PREFILL32", 1);
-    if (p32 && D == 128 && (quant_bit == 0 || quant_bit == 8)) return launch_attn_prefill32(s, qkv, kv, quant_bit, seq_starts, start_pos, cache_indices, max_pages, b0, B, H, Hkv, D, max_seq_len, out, max_kv_len, ws, ws_bytes, row0, nrows);
+    if (p32 && D == 128 && (kv_fmt == KV_FP16 || kv_fmt == KV_I8G8 || kv_fmt == KV_FP8)) return launch_attn_prefill32(s, qkv, kv, kv_fmt, seq_starts, start_pos, cache_indices, max_pages, b0, B, H, Hkv, D, max_seq_len, out, max_kv_len, ws, ws_bytes, row0, nrows);
     // RG = 2 (256 query rows per block, Q fragments in LDS) halves the staging per MFMA but spills registers and measured
     // slower than RG = 1 once the softmax was trimmed (8192-token prompt: 1.86 ms vs 1.43 ms per layer); PPLHIP_PREFILL_RG=2 keeps
     // it reachable for experiments
@@ -411,12 +426,13 @@ hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr&
     hipLaunchKernelGGL((attn_prefill_kernel<QB, DD, MD, RGV>), grid, dim3(PF_THREADS), 0, s, qkv, kv, seq_starts, start_pos, \
                        cache_indices, max_pages, b0, H, Hkv, nreq, nqb, out)
 #define PF_CASE(QB, DD)                                                                                          \
-    if (quant_bit == QB && D == DD) {                                                                            \
+    if (kv_fmt == QB && D == DD) {                                                                               \
         if (kv.mode == 0) { if (rg == 2) PF_LAUNCH(QB, DD, 0, 2); else PF_LAUNCH(QB, DD, 0, 1); }                \
         else { if (rg == 2) PF_LAUNCH(QB, DD, 1, 2); else PF_LAUNCH(QB, DD, 1, 1); }                             \
         return hipGetLastError();                                                                                \
     }
     PF_CASE(8, 128) PF_CASE(0, 128) PF_CASE(8, 64) PF_CASE(0, 64) PF_CASE(8, 32) PF_CASE(0, 32)
+    PF_CASE(KV_FP8, 128) PF_CASE(KV_FP8, 64) PF_CASE(KV_FP8, 32)
 #undef PF_LAUNCH
 #undef PF_CASE
     return hipErrorInvalidValue;

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                                                                     float* __restrict__ ws, int64_t ws_row0) {
     constexpr int D = P3_D;
     constexpr int P3_BM = NW * 32, P3_THREADS = NW * 64;  // NW waves x 32 query rows share the staged K / V tiles
-    constexpr int ELT = QBIT == 8 ? 1 : 2;
+    constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;
     constexpr int CH = 16 / ELT;                 // channels in one 16-byte piece
     constexpr int LPT = D / CH;                  // pieces per row: 8 (int8) / 16 (fp16)
     constexpr int IPT = P3_BN * LPT / P3_THREADS;  // (key, piece) items per thread and matrix: 2 / 4 (4 waves), 1 / 2 (8 waves)
@@ -137,14 +137,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const int64_t sb_ = slot0 + key0_;                                                                                 \
             kp_ = kbase + sb_ * rowb + (kk_ * rowb32 + pc_ * 16);                                                              \
             vp_ = vbase + sb_ * rowb + (kk_ * rowb32 + pc_ * 16);                                                              \
-            ksp_ = ksbase + sb_ * srow + (kk_ * srow32 + pc_ * 2);                                                             \
-            vsp_ = vsbase + sb_ * srow + (kk_ * srow32 + pc_ * 2);                                                             \
+            ksp_ = ksbase + sb_ * srow + (kk_ * srow32 + (QBIT == 8 ? pc_ * 2 : 0));                                           \
+            vsp_ = vsbase + sb_ * srow + (kk_ * srow32 + (QBIT == 8 ? pc_ * 2 : 0));                                           \
         } else {                                                                                                               \
             const int64_t slot_ = kv_slot(kv, cache_indices, max_pages, b, key0_ + kk_);                                       \
             kp_ = kbase + slot_ * rowb + pc_ * 16;                                                                             \
             vp_ = vbase + slot_ * rowb + pc_ * 16;                                                                             \
-            ksp_ = ksbase + slot_ * srow + pc_ * 2;                                                                            \
-            vsp_ = vsbase + slot_ * srow + pc_ * 2;                                                                            \
+            ksp_ = ksbase + slot_ * srow + (QBIT == 8 ? pc_ * 2 : 0);                                                          \
+            vsp_ = vsbase + slot_ * srow + (QBIT == 8 ? pc_ * 2 : 0);                                                          \
         }                                                                                                                      \
         KR = *reinterpret_cast<const uint4*>(kp_);                                                                             \
         VR = *reinterpret_cast<const uint4*>(vp_);                                                                             \
@@ -152,6 +152,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             KC = *reinterpret_cast<const uint32_t*>(ksp_);                                                                     \
             VC = *reinterpret_cast<const uint32_t*>(vsp_);                                                                     \
         }                                                                                                                      \
+        if constexpr (QBIT == KV_FP8) { KC = *ksp_; VC = *vsp_; }  /* the row's 2^e */                                         \
     } while (0)
 #define P3_LOAD_TILE(TILE)                                                                                                     \
     do {                                                                                                                       \
@@ -174,6 +175,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const h8 v0 = cvt_i8x8_f16(make_uint2(VR.x, VR.y)), v1 = cvt_i8x8_f16(make_uint2(VR.z, VR.w));                     \
             const h2 ks2 = __builtin_bit_cast(h2, KC), vs2 = __builtin_bit_cast(h2, VC);                                       \
             const h8 kh0 = k0 * ks2[0], kh1 = k1 * ks2[1], vh0 = v0 * vs2[0], vh1 = v1 * vs2[1]; /* one rounding of q x scale */ \
+            *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh0);          \
+            *reinterpret_cast<uint4*>(&Kw[key * D + (((ch0 >> 3) + 1) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh1);    \
+            uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * P3_VSUB + (key & 15) * 16];                              \
+            *reinterpret_cast<uint4*>(vd) = __builtin_bit_cast(uint4, vh0);                                                    \
+            *reinterpret_cast<uint4*>(vd + 8) = __builtin_bit_cast(uint4, vh1);                                                \
+        } else if constexpr (QBIT == KV_FP8) {  /* e4m3 x 2^e: exact fp16, no rounding */                                      \
+            const float ks_ = h2f((uint16_t)KC), vs_ = h2f((uint16_t)VC);                                                      \
+            const h8 kh0 = cvt_fp8x8_f16(make_uint2(KR.x, KR.y), ks_), kh1 = cvt_fp8x8_f16(make_uint2(KR.z, KR.w), ks_);       \
+            const h8 vh0 = cvt_fp8x8_f16(make_uint2(VR.x, VR.y), vs_), vh1 = cvt_fp8x8_f16(make_uint2(VR.z, VR.w), vs_);       \
             *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh0);          \
             *reinterpret_cast<uint4*>(&Kw[key * D + (((ch0 >> 3) + 1) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh1);    \
             uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * P3_VSUB + (key & 15) * 16];                              \
@@ -372,11 +382,11 @@ __global__ void attn_prefill32_reduce_kernel(const float* __restrict__ ws, int n
 
 }  // namespace
 
-hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit, const int64_t* seq_starts,
+hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
                                  const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t b0, int64_t B,
                                  int H, int Hkv, int D, int64_t max_seq_len, uint16_t* out, int64_t max_kv_len, float* ws, size_t ws_bytes,
                                  int64_t row0, int64_t nrows) {
-    if (D != P3_D || (quant_bit != 0 && quant_bit != 8)) return hipErrorInvalidValue;
+    if (D != P3_D || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8)) return hipErrorInvalidValue;
     if (B <= b0 || max_seq_len <= 0) return hipSuccess;
     // Few new tokens behind long caches (a prefix-cache hit recomputes one page; a short follow-up turn): when the launch has too few
     // (query block, request, head) blocks to fill the chip, the keys of each are split over gridDim.y blocks whose partial rows are merged
@@ -395,7 +405,8 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
             dim3 grid((unsigned)blocks4, (unsigned)nsplit);
 #define P3_SPLIT(QB, MD) hipLaunchKernelGGL((attn_prefill32_kernel<QB, MD, 4, 0, 1>), grid, dim3(256), 0, s, qkv, kv, seq_starts, start_pos, \
                                             cache_indices, max_pages, b0, H, Hkv, nreq, (int)nqb4, out, ws, row0)
-            if (quant_bit == 8) { if (kv.mode == 0) P3_SPLIT(8, 0); else P3_SPLIT(8, 1); }
+            if (kv_fmt == KV_I8G8) { if (kv.mode == 0) P3_SPLIT(8, 0); else P3_SPLIT(8, 1); }
+            else if (kv_fmt == KV_FP8) { if (kv.mode == 0) P3_SPLIT(KV_FP8, 0); else P3_SPLIT(KV_FP8, 1); }
             else { if (kv.mode == 0) P3_SPLIT(0, 0); else P3_SPLIT(0, 1); }
 #undef P3_SPLIT
             hipError_t e = hipGetLastError();
@@ -420,10 +431,12 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
 #undef P3_ABL
 #endif
     if (nw == 8) {
-        if (quant_bit == 8) { if (kv.mode == 0) P3_LAUNCH(8, 0, 8); else P3_LAUNCH(8, 1, 8); }
+        if (kv_fmt == KV_I8G8) { if (kv.mode == 0) P3_LAUNCH(8, 0, 8); else P3_LAUNCH(8, 1, 8); }
+        else if (kv_fmt == KV_FP8) { if (kv.mode == 0) P3_LAUNCH(KV_FP8, 0, 8); else P3_LAUNCH(KV_FP8, 1, 8); }
         else { if (kv.mode == 0) P3_LAUNCH(0, 0, 8); else P3_LAUNCH(0, 1, 8); }
     } else {
-        if (quant_bit == 8) { if (kv.mode == 0) P3_LAUNCH(8, 0, 4); else P3_LAUNCH(8, 1, 4); }
+        if (kv_fmt == KV_I8G8) { if (kv.mode == 0) P3_LAUNCH(8, 0, 4); else P3_LAUNCH(8, 1, 4); }
+        else if (kv_fmt == KV_FP8) { if (kv.mode == 0) P3_LAUNCH(KV_FP8, 0, 4); else P3_LAUNCH(KV_FP8, 1, 4); }
         else { if (kv.mode == 0) P3_LAUNCH(0, 0, 4); else P3_LAUNCH(0, 1, 4); }
     }
 #undef P3_LAUNCH

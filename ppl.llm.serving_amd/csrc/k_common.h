@@ -86,6 +86,58 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
     return __builtin_bit_cast(uint4, h);
 }
 
+// KV cache formats.  The host derives one from (cache_quant_bit, cache_quant_group) once (pplhip.cc kv_format) and the launchers
+// take it in place of the quant bit; the two older formats keep their quant bits as values, so their kernel instantiations are unchanged.
+//   KV_FP16: fp16 rows, no scales.
+//   KV_I8G8: int8 rows, one fp16 scale per 8 channels.
+//   KV_FP8 : OCP e4m3fn rows, ONE fp16 scale per head row, a power of two 2^e with e in [-15, 8] (DESIGN.md "numerics"): every
+//            dequantised element q * 2^e is exactly an fp16 number, so the fp8 cache is the fp16 cache with every row replaced by Q(row).
+constexpr int KV_FP16 = 0, KV_I8G8 = 8, KV_FP8 = 1;
+
+// fp8 write: exponent e of a row's scale -- the smallest integer with 448 * 2^e >= amax, clamped to [-15, 8] (amax = 0: -15).
+// amax = m 2^k (m in [0.5, 1)): 448 = 0.875 2^9, so e = k - 9 when m <= 0.875, else k - 8.  amax is an fp16 value: an fp32 normal or 0.
+__device__ __forceinline__ int fp8_row_exp(float amax) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, amax);
+    const int k = (int)(u >> 23) - 126;
+    const int e = k - 9 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return u == 0 ? -15 : (e < -15 ? -15 : (e > 8 ? 8 : e));
+}
+// e4m3fn code of y (|y| <= 448), round to nearest even, fp8 subnormals included (integer rounding: no dependence on the
+// conversion instruction's rounding or clamp modes).  Normal range (|y| >= 2^-6): round the fp32 mantissa to 3 bits; below it the
+// value is m 2^-9 with m = rne(|y| 2^9) in 0 .. 8 -- and code 8 is 2^-6, the smallest normal, so m is the code as it stands.
+__device__ __forceinline__ uint32_t fp8_e4m3_rne(float y) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, y);
+    const uint32_t sign = (u >> 24) & 0x80u;
+    uint32_t a = u & 0x7fffffffu;
+    uint32_t code;
+    if (a >= 0x3c800000u) {                      // 2^-6
+        a += 0x7ffffu + ((a >> 20) & 1u);
+        code = (((a >> 23) - 120u) << 3) | ((a >> 20) & 7u);
+    } else {
+        code = (uint32_t)rintf(__builtin_bit_cast(float, a) * 512.0f);
+    }
+    return sign | code;
+}
+// 16 e4m3fn codes (a 16-byte piece) -> 16 fp32, exact (v_cvt_pk_f32_fp8)
+__device__ __forceinline__ void cvt_fp8x16_f32(const uint4& v, float* f) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        f[4 * i] = lo[0]; f[4 * i + 1] = lo[1]; f[4 * i + 2] = hi[0]; f[4 * i + 3] = hi[1];
+    }
+}
+// 4 e4m3fn codes (bytes of w) -> 4 fp16 times the power-of-two scale sc, by the hardware conversion with the scale inside (exact:
+// every q * 2^e of the format is an fp16 number)
+__device__ __forceinline__ h4 cvt_fp8x4_f16(uint32_t w, float sc) {
+    const h2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, sc, false), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, sc, true);
+    return h4{a[0], a[1], b[0], b[1]};
+}
+__device__ __forceinline__ h8 cvt_fp8x8_f16(uint2 v, float sc) {
+    const h4 a = cvt_fp8x4_f16(v.x, sc), b = cvt_fp8x4_f16(v.y, sc);
+    return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+
 // Decode attention reads every K/V row exactly once per step: non-temporal loads (compile-time switch PPLHIP_KV_NT) stream them
 // past the caches instead of through them -- measured +5..9 % (batch 1024 kv 512: 5.92 -> 6.23 TB/s, kv 1024: 6.24 -> 6.70 TB/s,
 // profiles/attn_microbench.py; MI355X_MICROARCH.md quotes 6.4 TB/s default policy vs 6.5-6.8 nt for a streaming read)

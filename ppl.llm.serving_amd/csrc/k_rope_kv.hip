@@ -1,10 +1,14 @@
 // K4 + K5 fused: rotary position embedding on q and k of the fused qkv rows, then write of k, v into the KV
-// slab -- with int8 group-8 quantisation when cache_quant_bit == 8.  HBM-bound; 1-4 workgroups per token.
+// slab -- with int8 group-8 quantisation (KV_I8G8) or fp8 e4m3 with one power-of-two scale per head row (KV_FP8).
+// HBM-bound; 1-4 workgroups per token.
 //
 // Work item = one (head, 8-channel block) of a token:
 //   q / k heads: channels [i0, i0+8) and their RoPE partners [i0+D/2, i0+D/2+8) (half-split pairing) -- two
 //                complete quantisation groups, so rotate + quantise + store needs no cross-lane traffic;
 //   v heads    : channels [i0, i0+8), copy / quantise only.
+// KV_FP8: a head row's scale needs max|x| over the whole row, i.e. over the D/16 (k) or D/8 (v) items of the head: those items sit
+//   on consecutive lanes of one wave, aligned to their count (the v items start at n_rope rounded up to D/8 for this format), and
+//   meet in a cross-lane max.
 // Position of row t of request b: start_pos[b] + (t - seq_starts[b]) (src/generator/llm_generator.cc:263-298);
 // slot of (b, pos): kv_slot() (k_common.h).  Oracle: ref_rope_kv_write (oracle/llama_ref.c).
 #include <stdlib.h>
@@ -39,6 +43,29 @@ __device__ __forceinline__ void store_group8(const KvAddr& kv, int kvsel, int he
     }
 }
 
+// KV_FP8: 8 channels of a head row whose scale exponent is e (fp8_row_exp of the row's max|x|): codes e4m3fn(x 2^-e), saturated to
+// +-240 at e = 8 so that q 2^e stays finite in fp16; the item of channel 0 stores the row's scale fp16(2^e)
+__device__ __forceinline__ void store_fp8_row8(const KvAddr& kv, int kvsel, int head, int64_t slot, int ch0, const float* x /*8*/,
+                                               int e) {
+    const int64_t base = (int64_t)kvsel * kv.sKV + (int64_t)head * kv.sH + slot * kv.sN + ch0;
+    const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);   // 2^-e, exact
+    const float lim = e == 8 ? 240.0f : 448.0f;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float y = __fmul_rn(x[i], inv);
+        const uint32_t b = fp8_e4m3_rne(fminf(fmaxf(y, -lim), lim));
+        if (i < 4) lo |= b << (8 * i); else hi |= b << (8 * (i - 4));
+    }
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(kv.cache) + base) = make_uint2(lo, hi);
+    if (ch0 == 0) kv.scale[(int64_t)kvsel * kv.ssKV + (int64_t)head * kv.ssH + slot * kv.ssN] = f2h(__builtin_bit_cast(float, (uint32_t)(127 + e) << 23));
+}
+// max over the n lanes (a power of two, aligned) of an item group
+__device__ __forceinline__ float group_max(float v, int n) {
+    for (int o = 1; o < n; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
 template <int QBIT>
 __global__ __launch_bounds__(256) void rope_kv_write_kernel(uint16_t* __restrict__ qkv, const float* __restrict__ cos_sin,
                                                             KvAddr kv, const int64_t* __restrict__ seq_starts,
@@ -69,11 +96,13 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(uint16_t* __restrict
     const int bph = half / 8;                  // rope work items per head
     const int n_rope = (H + Hkv) * bph;
     const int n_v = Hkv * (D / 8);
+    // first v item: fp8 aligns it to a v head's item count (the items in between do nothing)
+    const int v0 = QBIT == KV_FP8 ? (n_rope + D / 8 - 1) / (D / 8) * (D / 8) : n_rope;
     uint16_t* row = qkv + t * (int64_t)(H + 2 * Hkv) * D;
     const float* cs = cos_sin + pos * D;       // cos[0..half) then sin[0..half)
     // gridDim.y blocks share a token's work items (one item per thread at the LLaMA geometries: the step is a chain of dependent
     // latencies, not bandwidth -- 7B, 128 rows: 11.8 -> see DESIGN.md)
-    for (int w = blockIdx.y * 256 + threadIdx.x; w < n_rope + n_v; w += 256 * gridDim.y) {
+    for (int w = blockIdx.y * 256 + threadIdx.x; w < v0 + n_v; w += 256 * gridDim.y) {
         if (w < n_rope) {
             const int head = w / bph, i0 = (w - head * bph) * 8;
             uint16_t* x = row + (int64_t)head * D;
@@ -98,23 +127,36 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(uint16_t* __restrict
             if (head < H) {  // q: in place
                 *reinterpret_cast<uint4*>(x + i0) = pack8(ra);
                 *reinterpret_cast<uint4*>(x + i0 + half) = pack8(rb);
+            } else if constexpr (QBIT == KV_FP8) {  // k: to the cache (head is uniform over the item group)
+                float mx = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fmaxf(fabsf(ra[i]), fabsf(rb[i])));
+                const int e = fp8_row_exp(group_max(mx, bph));
+                store_fp8_row8(kv, 0, head - H, slot, i0, ra, e);
+                store_fp8_row8(kv, 0, head - H, slot, i0 + half, rb, e);
             } else {         // k: to the cache
                 store_group8<QBIT>(kv, 0, head - H, slot, i0, ra);
                 store_group8<QBIT>(kv, 0, head - H, slot, i0 + half, rb);
             }
-        } else {
-            const int wv = w - n_rope;
+        } else if (w >= v0) {
+            const int wv = w - v0;
             const int head = wv / (D / 8), i0 = (wv - head * (D / 8)) * 8;
             float v[8];
             if (sl.splits) slab_load8(sl, t - t0, (H + Hkv + head) * D + i0, v);
             else unpack8(*reinterpret_cast<const uint4*>(row + (int64_t)(H + Hkv + head) * D + i0), v);
-            store_group8<QBIT>(kv, 1, head, slot, i0, v);
+            if constexpr (QBIT == KV_FP8) {
+                float mx = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(v[i]));
+                store_fp8_row8(kv, 1, head, slot, i0, v, fp8_row_exp(group_max(mx, D / 8)));
+            } else {
+                store_group8<QBIT>(kv, 1, head, slot, i0, v);
+            }
         }
     }
 }
 
-hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_sin, const KvAddr& kv, int quant_bit,
-                                int quant_group, const int64_t* seq_starts, const int64_t* start_pos,
+hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_sin, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts, const int64_t* start_pos,
                                 const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0, int64_t T, int H,
                                 int Hkv, int D, const SplitSlabs* qkv_slabs) {
     if (T == 0) return hipSuccess;
@@ -123,7 +165,7 @@ hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_s
         sl = *qkv_slabs;
         if (sl.N != (H + 2 * Hkv) * D || sl.M != T) return hipErrorInvalidValue;
     }
-    if (D % 16 || (quant_bit == 8 && quant_group != 8) || (quant_bit != 0 && quant_bit != 8)) return hipErrorInvalidValue;
+    if (D % 16 || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8)) return hipErrorInvalidValue;
     const int items = (H + Hkv) * (D / 16) + Hkv * (D / 8);
     static const int forced_y = getenv("PPLHIP_ROPE_BLOCKS_PER_TOKEN") ? atoi(getenv("PPLHIP_ROPE_BLOCKS_PER_TOKEN")) : 0;
     int gy = (items + 255) / 256;            // one item per thread ...
@@ -131,7 +173,10 @@ hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_s
     if (T >= 4096 && gy > 2) gy = 2;         // ... unless the launch fills the chip many times over anyway
     if (forced_y > 0) gy = forced_y;
     const dim3 grid((unsigned)T, (unsigned)gy);
-    if (quant_bit == 8)
+    if (kv_fmt == KV_FP8)
+        hipLaunchKernelGGL(rope_kv_write_kernel<KV_FP8>, grid, dim3(256), 0, s, qkv, cos_sin, kv, seq_starts,
+                           start_pos, cache_indices, max_pages, B, t0, H, Hkv, D, sl);
+    else if (kv_fmt == KV_I8G8)
         hipLaunchKernelGGL(rope_kv_write_kernel<8>, grid, dim3(256), 0, s, qkv, cos_sin, kv, seq_starts,
                            start_pos, cache_indices, max_pages, B, t0, H, Hkv, D, sl);
     else

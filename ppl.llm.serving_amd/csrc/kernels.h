@@ -63,9 +63,10 @@ hipError_t launch_silu_mul(hipStream_t s, const uint16_t* gate_up, int64_t T, in
 // out[r] = x[seq_starts[r + 1] - 1] (last-token gather of K11 when the final norm already ran on every row: fused tensor-parallel norm)
 hipError_t launch_gather_last_rows(hipStream_t s, const uint16_t* x, const int64_t* seq_starts, int64_t B, int hidden, uint16_t* out);
 
+// The KV-cache kernels take the cache format kv_fmt (KV_FP16 / KV_I8G8 / KV_FP8, k_common.h).
 // ---- k_rope_kv.hip ----------------------------------------------------------------------------
-hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_sin, const KvAddr& kv, int quant_bit,
-                                int quant_group, const int64_t* seq_starts, const int64_t* start_pos,
+hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_sin, const KvAddr& kv, int kv_fmt,
+                                const int64_t* seq_starts, const int64_t* start_pos,
                                 const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0, int64_t T, int H,
                                 int Hkv, int D, const SplitSlabs* qkv_slabs = nullptr);  // token rows [t0, t0 + T) of the step's B requests;
                                                    // qkv_slabs: the rows come from unreduced split-K slabs of a [T, N] launch (slab row = token row - t0); rotated q -> qkv
@@ -74,14 +75,14 @@ hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_s
 // rows [0, nb) of the batch are single-token queries; q row of request b is qkv row seq_starts[b].
 // split > 1 uses `workspace` (fp32 [nb, H, split, D+2]).
 size_t attn_decode_workspace_bytes(int64_t nb, int H, int D, int split);
-hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit,
+hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                               const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                               int64_t max_pages, int64_t nb, int H, int Hkv, int D, int64_t max_kv_len, int split,
                               int threads, float* workspace, uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // ---- k_attn_prefill.hip -----------------------------------------------------------------------
 // requests [b0, B): causal attention of their new tokens over the cache [0, start_pos + seqlen).
-hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit,
+hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                                const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                                int64_t max_pages, int64_t b0, int64_t B, int H, int Hkv, int D, int64_t max_seq_len,
                                uint16_t* out, int64_t max_kv_len = 0, float* ws = nullptr, size_t ws_bytes = 0, int64_t row0 = 0,
@@ -89,7 +90,7 @@ hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr&
 
 // ---- k_attn_prefill32.hip ---------------------------------------------------------------------
 // the same operation for head_dim 128 on the 32-row wave tile (mfma_f32_32x32x16_f16, 64-key tiles, one barrier per tile)
-hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit, const int64_t* seq_starts,
+hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
                                  const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t b0, int64_t B,
                                  int H, int Hkv, int D, int64_t max_seq_len, uint16_t* out, int64_t max_kv_len = 0, float* ws = nullptr,
                                  size_t ws_bytes = 0, int64_t row0 = 0, int64_t nrows = 0);
@@ -97,8 +98,8 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
 // ---- k_attn_decode_gqa.hip --------------------------------------------------------------------
 // grouped-query decode (4 <= H/Hkv <= 16): MFMA kernel, one block per (request, KV head[, split]); same workspace layout
 // and reduce kernel as launch_attn_decode.  t0 / t1: optional start / stop events of the kernel's own dispatch packet.
-bool attn_decode_gqa_supported(int quant_bit, int H, int Hkv, int D);
-hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int quant_bit,
+bool attn_decode_gqa_supported(int kv_fmt, int H, int Hkv, int D);
+hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                                   const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                                   int64_t max_pages, int64_t nb, int H, int Hkv, int D, int split, float* workspace,
                                   uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
@@ -192,7 +193,8 @@ hipError_t launch_penalty(hipStream_t s, float* logits, const float* temperature
                           int vocab, int stride, int decoding_batches, uint16_t* count_map);
 
 // ---- synth.hip --------------------------------------------------------------------------------
-// kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm
+// kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm; and for the fp8 KV
+// slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales
 hipError_t launch_synth_fill(hipStream_t s, int kind, uint64_t seed, uint32_t tensor_id, uint32_t stream_id, float amp,
                              uint64_t n, void* out);
 

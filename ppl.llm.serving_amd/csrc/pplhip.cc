@@ -153,6 +153,7 @@ struct Rank {
 struct pplhip_ctx {
     pplhip_model_desc d;
     pplhip_opts o;
+    int kv_fmt = KV_FP16;  // KV cache format of (d.cache_quant_bit, d.cache_quant_group): kv_format(), derived once at init
     int tp = 1;
     bool tp_overlap = true;              // PPLHIP_TP_OVERLAP=0 keeps the collectives on the compute stream
     // PPLHIP_TP_OVERLAP_MIN_TOKENS.  Measured on one MI355X with identity collectives (bench.py --emulate-tp 2/4/8,
@@ -283,6 +284,16 @@ bool find_tensor(pplhip_ctx* c, Rank& R, const char* name, void** ptr, uint64_t*
     return false;
 }
 
+// KV cache format of a (cache_quant_bit, cache_quant_group) pair at head_dim D, -1 when the pair is not one of the three:
+// (0, 1) fp16, (8, 8) int8 group 8, (8, D) fp8 e4m3 with one power-of-two scale per head row (D = 32, 64, 128).  Everything behind
+// the sizes (make_kv_addr, pplhip_kv_block_bytes) works from the pair itself: 1 byte per element and D / group scales per row.
+static int kv_format(int quant_bit, int quant_group, int D) {
+    if (quant_bit == 0 && quant_group == 1) return KV_FP16;
+    if (quant_bit == 8 && quant_group == 8) return KV_I8G8;
+    if (quant_bit == 8 && quant_group == D && (D == 32 || D == 64 || D == 128)) return KV_FP8;
+    return -1;
+}
+
 KvAddr make_kv_addr(const pplhip_model_desc& d, int Hkv, int D, uint64_t tokens, void* cache, uint16_t* scale, int layer) {
     const int elt = d.cache_quant_bit == 8 ? 1 : 2;
     const int g = d.cache_quant_group > 0 ? d.cache_quant_group : 1;
@@ -320,7 +331,7 @@ void prof_end(Rank& R, ProfEvent* ev) {
 int decode_split(const pplhip_ctx* c, int64_t nb, int64_t max_kv_len) {
     const int mode = c->o.decoding_attn_split_k;
     if (mode == 0) return 1;
-    const bool gqa = attn_decode_gqa_supported(c->d.cache_quant_bit, c->H, c->Hkv, c->D);
+    const bool gqa = attn_decode_gqa_supported(c->kv_fmt, c->H, c->Hkv, c->D);
     const int64_t blocks = nb * (gqa ? c->Hkv : c->H);  // GQA kernel: one block per KV head
     int split = 1;
     // measured (profiles/attn_microbench.py): 512 workgroups already stream at 5.3 TB/s; split only below ~256.  (The grouped-query
@@ -545,7 +556,8 @@ static bool fuse_norm_active(const pplhip_ctx* c, const Rank& R);
 
 extern "C" {
 
-int pplhip_version(void) { return (1 << 16) | 1; }  // 1.1: pplhip_model_desc.act_quant_bit, comm_* and W8A8 operator entry points
+int pplhip_version(void) { return (1 << 16) | 2; }  // 1.1: pplhip_model_desc.act_quant_bit, comm_* and W8A8 operator entry points;
+                                                    // 1.2: fp8 e4m3 KV cache (cache_quant_bit 8, cache_quant_group = head_dim)
 
 int pplhip_device_count(void) {
     int n = 0;
@@ -636,13 +648,15 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
     if (d.num_heads % tp || d.num_kv_heads % tp || d.intermediate_dim % tp || d.vocab_size % tp) return bad("tp divisibility");
     if (d.num_heads % d.num_kv_heads) return bad("gqa");
     // src/generator/llm_generator.cc:114-144 (CheckParameters)
-    if (!((d.cache_quant_bit == 8 && d.cache_quant_group == 8) || (d.cache_quant_bit == 0 && d.cache_quant_group == 1))) return bad("cache quant");
+    // (plus the fp8 pair (8, head_dim) of this library: kv_format)
+    if (kv_format(d.cache_quant_bit, d.cache_quant_group, d.hidden_dim / d.num_heads) < 0) return bad("cache quant");
     if (d.cache_layout < 0 || d.cache_layout > 3 || d.cache_mode < 0 || d.cache_mode > 1) return bad("cache layout/mode");
     if (d.cache_mode == 1 && d.page_size <= 0) return bad("page_size");
     if (d.weight_quant_bit != 0 && d.weight_quant_bit != 8 && d.weight_quant_bit != 4) return bad("weight quant");
     if (d.act_quant_bit != 0 && !(d.act_quant_bit == 8 && d.weight_quant_bit == 8)) return bad("act quant (8 needs weight_quant_bit 8)");
     if (opts->max_running_batch <= 0 || opts->max_tokens_per_step <= 0 || d.max_position <= 0) return bad("limits");
     c->D = d.hidden_dim / d.num_heads;
+    c->kv_fmt = kv_format(d.cache_quant_bit, d.cache_quant_group, c->D);
     c->H = d.num_heads / tp;
     c->Hkv = d.num_kv_heads / tp;
     c->inter = d.intermediate_dim / tp;
@@ -1223,7 +1237,10 @@ int pplhip_kv_fill_synthetic(pplhip_ctx* c, int rank, uint64_t seed) {
     uint64_t kb, sb;
     pplhip_kv_block_bytes(c, &kb, &sb);
     const uint32_t st = 100u + (uint32_t)R.global_rank;
-    if (c->d.cache_quant_bit == 8) {
+    if (c->kv_fmt == KV_FP8) {   // finite e4m3 codes and power-of-two row scales
+        HIPCK(c, rank, launch_synth_fill(R.stream, 5, seed, 1, st, 0.f, R.kv_tokens * kb, R.kv_cache));
+        HIPCK(c, rank, launch_synth_fill(R.stream, 6, seed, 2, st, 0.f, R.kv_tokens * sb / 2, R.kv_scale));
+    } else if (c->kv_fmt == KV_I8G8) {
         HIPCK(c, rank, launch_synth_fill(R.stream, 1, seed, 1, st, 0.f, R.kv_tokens * kb, R.kv_cache));
         HIPCK(c, rank, launch_synth_fill(R.stream, 3, seed, 2, st, 0.02f, R.kv_tokens * sb / 2, R.kv_scale));
     } else {
@@ -1365,7 +1382,7 @@ static int layer_attention_part(pplhip_ctx* c, int rank, int l, const Chunk& k, 
         prof_end(R, &ev);
     }
     const KvAddr kv = make_kv_addr(d, Hkv, D, R.kv_tokens, R.kv_cache, R.kv_scale, l);
-    HIPCK(c, rank, launch_rope_kv_write(s, R.qkv, R.rope, kv, d.cache_quant_bit, d.cache_quant_group, R.d_seq, R.d_sp, R.d_ci,
+    HIPCK(c, rank, launch_rope_kv_write(s, R.qkv, R.rope, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci,
                                         R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &R.sl_qkv));
     R.sl_qkv = SplitSlabs{};
     // decode rows of the chunk: per-request arrays shifted to the chunk (q rows stay absolute through seq_starts);
@@ -1379,13 +1396,13 @@ static int layer_attention_part(pplhip_ctx* c, int rank, int l, const Chunk& k, 
             if (!R.prof_free.empty()) { p = R.prof_free.back(); R.prof_free.pop_back(); }
             else { hipEventCreate(&p.first); hipEventCreate(&p.second); }
             ev.cls = PPLHIP_PROF_ATTN_DECODE; ev.a = p.first; ev.b = p.second;
-            HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, d.cache_quant_bit, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
+            HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, c->kv_fmt, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
                                               R.max_pages, k.nd, H, Hkv, D, R.max_kv_len, split, threads, R.attn_ws,
                                               R.att + k.b0 * (int64_t)H * D, ev.a, ev.b));
             R.prof.push_back(ev);
         } else {
             prof_begin(c, R, PPLHIP_PROF_ATTN_DECODE, &ev);
-            HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, d.cache_quant_bit, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
+            HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, c->kv_fmt, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
                                               R.max_pages, k.nd, H, Hkv, D, R.max_kv_len, split, threads, R.attn_ws,
                                               R.att + k.b0 * (int64_t)H * D));
             prof_end(R, &ev);
@@ -1394,7 +1411,7 @@ static int layer_attention_part(pplhip_ctx* c, int rank, int l, const Chunk& k, 
     if (k.bn > k.nd) {
         prof_begin(c, R, PPLHIP_PROF_ATTN_PREFILL, &ev);
         // (decode requests own one token row each, so the prefill requests' rows are [t0 + nd, t0 + tn): the split-KV form for short suffixes)
-        HIPCK(c, rank, launch_attn_prefill(s, R.qkv, kv, d.cache_quant_bit, R.d_seq, R.d_sp, R.d_ci, R.max_pages, k.b0 + k.nd,
+        HIPCK(c, rank, launch_attn_prefill(s, R.qkv, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci, R.max_pages, k.b0 + k.nd,
                                            k.b0 + k.bn, H, Hkv, D, R.max_seq_len, R.att, R.max_kv_len, R.attn_ws, R.attn_ws_bytes,
                                            k.t0 + k.nd, k.tn - k.nd));
         prof_end(R, &ev);
@@ -2074,8 +2091,9 @@ static KvAddr view_addr(const pplhip_kv_view* v) {
 int pplhip_op_rope_kv_write(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
                             const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
                             int32_t num_heads) {
-    if (!kv) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_rope_kv_write((hipStream_t)stream, (uint16_t*)qkv, cos_sin, view_addr(kv), kv->quant_bit, kv->quant_group,
+    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
+    if (fmt < 0) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_rope_kv_write((hipStream_t)stream, (uint16_t*)qkv, cos_sin, view_addr(kv), fmt,
                                       seq_starts, start_pos, cache_indices, max_pages, B, 0, T, num_heads, kv->kv_heads, kv->head_dim));
 }
 
@@ -2084,7 +2102,8 @@ int pplhip_op_attention(void* stream, const void* qkv, const pplhip_kv_view* kv,
                         int64_t decoding_batches, int64_t max_seq_len, int64_t max_kv_len, int32_t num_heads, int32_t split_k,
                         void* workspace, uint64_t workspace_bytes, void* out) {
     (void)T;
-    if (!kv) return PPLHIP_INVALID_VALUE;
+    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
+    if (fmt < 0) return PPLHIP_INVALID_VALUE;
     const int64_t nb = std::min<int64_t>(std::max<int64_t>(decoding_batches, 0), B);
     int split = split_k < 1 ? 1 : split_k;
     if (split > 1 && attn_decode_workspace_bytes(nb, num_heads, kv->head_dim, split) > workspace_bytes) return PPLHIP_INVALID_VALUE;
@@ -2092,10 +2111,10 @@ int pplhip_op_attention(void* stream, const void* qkv, const pplhip_kv_view* kv,
     const KvAddr a = view_addr(kv);
     hipError_t e = hipSuccess;
     if (nb > 0)
-        e = launch_attn_decode(s, (const uint16_t*)qkv, a, kv->quant_bit, seq_starts, start_pos, cache_indices, max_pages, nb,
+        e = launch_attn_decode(s, (const uint16_t*)qkv, a, fmt, seq_starts, start_pos, cache_indices, max_pages, nb,
                                num_heads, kv->kv_heads, kv->head_dim, max_kv_len, split, 256, (float*)workspace, (uint16_t*)out);
     if (e == hipSuccess && B > nb)
-        e = launch_attn_prefill(s, (const uint16_t*)qkv, a, kv->quant_bit, seq_starts, start_pos, cache_indices, max_pages, nb, B,
+        e = launch_attn_prefill(s, (const uint16_t*)qkv, a, fmt, seq_starts, start_pos, cache_indices, max_pages, nb, B,
                                 num_heads, kv->kv_heads, kv->head_dim, max_seq_len, (uint16_t*)out, max_kv_len, (float*)workspace,
                                 (size_t)workspace_bytes, nb, T - nb);
     return op_rc(e);

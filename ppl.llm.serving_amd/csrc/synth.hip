@@ -28,6 +28,16 @@ __global__ __launch_bounds__(256) void synth_fill_kernel(int kind, uint64_t key,
     }
 }
 
+// KV_FP8 slab fill (pplhip_kv_fill_synthetic; no oracle counterpart): kind 5 e4m3 codes of magnitude < 2 (exponent field 0..7, never
+// NaN), kind 6 power-of-two fp16 row scales 2^-4 .. 2^-7
+__global__ __launch_bounds__(256) void synth_fill_fp8_kernel(int kind, uint64_t key, uint64_t n, void* out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t r = (uint32_t)(synth_val(key, i) >> 32);
+        if (kind == 5) ((uint8_t*)out)[i] = (uint8_t)(r & 0xbfu);
+        else ((uint16_t*)out)[i] = (uint16_t)((15 - 4 - (int)(r & 3u)) << 10);
+    }
+}
+
 hipError_t launch_synth_fill(hipStream_t s, int kind, uint64_t seed, uint32_t tensor_id, uint32_t stream_id, float amp,
                              uint64_t n, void* out) {
     if (n == 0) return hipSuccess;
@@ -40,7 +50,8 @@ hipError_t launch_synth_fill(hipStream_t s, int kind, uint64_t seed, uint32_t te
     const uint64_t key = mix(seed ^ ((uint64_t)tensor_id * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)stream_id * 0xD1B54A32D192ED03ull));
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, amp, n, out);
+    if (kind == 5 || kind == 6) hipLaunchKernelGGL(synth_fill_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, n, out);
+    else hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, amp, n, out);
     return hipGetLastError();
 }
 

@@ -69,8 +69,12 @@ RetCode LLMGenerator::CheckParameters() const {
     if (m.cache_layout < 0 || m.cache_layout > 3) { LOG(ERROR) << "only support cache_layout 0..3"; return RC_INVALID_VALUE; }
     const bool int8_kv = m.cache_quant_bit == 8 && m.cache_quant_group == 8;
     const bool fp16_kv = m.cache_quant_bit == 0 && m.cache_quant_group == 1;
-    if (!int8_kv && !fp16_kv) {
-        LOG(ERROR) << "only support (cache_quant_bit == 8 and cache_quant_group == 8) or (cache_quant_bit == 0 and cache_quant_group == 1)";
+    // this project's fp8 e4m3 KV cache: group = head_dim (one power-of-two scale per head row; the reference has no such pair)
+    const int head_dim = m.num_heads > 0 ? m.hidden_dim / m.num_heads : 0;
+    const bool fp8_kv = m.cache_quant_bit == 8 && m.cache_quant_group == head_dim && (head_dim == 32 || head_dim == 64 || head_dim == 128);
+    if (!int8_kv && !fp16_kv && !fp8_kv) {
+        LOG(ERROR) << "only support (cache_quant_bit == 8 and cache_quant_group == 8), (cache_quant_bit == 8 and cache_quant_group == "
+                      "head_dim) or (cache_quant_bit == 0 and cache_quant_group == 1)";
         return RC_INVALID_VALUE;
     }
     if (!m.dynamic_batching) { LOG(ERROR) << "only support dynamic_batching == true"; return RC_INVALID_VALUE; }

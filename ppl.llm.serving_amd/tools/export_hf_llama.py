@@ -131,10 +131,13 @@ def params_json(cfg, args):
     rope_theta = cfg.get("rope_theta")
     if rope_theta is None and isinstance(cfg.get("rope_parameters"), dict):
         rope_theta = cfg["rope_parameters"].get("rope_theta")
+    kv = getattr(args, "kv_cache", None) or ("int8" if args.cache_quant_bit == 8 else "fp16")
+    head_dim = cfg["hidden_size"] // cfg["num_attention_heads"]
+    kv_bit, kv_group = {"fp16": (0, 1), "int8": (8, 8), "fp8": (8, head_dim)}[kv]
     p = {"num_heads": cfg["num_attention_heads"], "num_kv_heads": cfg.get("num_key_value_heads", cfg["num_attention_heads"]),
          "num_layers": cfg["num_hidden_layers"], "hidden_dim": cfg["hidden_size"], "intermediate_dim": cfg["intermediate_size"],
-         "vocab_size": cfg["vocab_size"], "cache_quant_bit": args.cache_quant_bit,
-         "cache_quant_group": 8 if args.cache_quant_bit == 8 else 1, "cache_layout": args.cache_layout, "cache_mode": args.cache_mode,
+         "vocab_size": cfg["vocab_size"], "cache_quant_bit": kv_bit,
+         "cache_quant_group": kv_group, "cache_layout": args.cache_layout, "cache_mode": args.cache_mode,
          "dynamic_batching": True, "auto_causal": True, "norm_eps": cfg.get("rms_norm_eps", 1e-5),
          "rope_theta": float(rope_theta if rope_theta is not None else 10000.0),
          "max_position": cfg.get("max_position_embeddings", 4096),
@@ -152,6 +155,9 @@ def main(argv=None):
     ap.add_argument("--quant", choices=["none", "w8a16", "w4a16"], default="w8a16")
     ap.add_argument("--quant-group", type=int, default=128)
     ap.add_argument("--cache-quant-bit", type=int, choices=[0, 8], default=8)
+    ap.add_argument("--kv-cache", choices=["fp16", "int8", "fp8"], default=None,
+                    help="KV cache format; overrides --cache-quant-bit: fp16 (0, 1), int8 group 8 (8, 8), fp8 e4m3 with one scale per "
+                         "head row (8, head_dim)")
     ap.add_argument("--cache-layout", type=int, choices=[0, 1, 2, 3], default=3)
     ap.add_argument("--cache-mode", type=int, choices=[0, 1], default=0)
     ap.add_argument("--page-size", type=int, default=16)
