@@ -66,8 +66,19 @@ typedef struct pplhip_model_desc {
                                    src/backends/cuda/resource_manager.cc:51-52: per-token int8 activations in front of
                                    every layer linear, int8 x int8 -> int32 on the matrix cores.  In this mode an fp16
                                    [N,K] matrix handed to pplhip_rank_set_tensor for an int8 linear is quantised per
-                                   output row on the device ("online"). */
+                                   output row on the device ("online").
+                                   PPLHIP_ACT_QUANT_FP8 (with weight_quant_bit 8) = online_f8f8: the same places and
+                                   rows, quantised to OCP e4m3fn codes under one power-of-two scale per row (the rule of
+                                   the fp8 KV cache), e4m3 x e4m3 -> fp32 on the matrix cores; weights are quantised per
+                                   output row on the device from fp16 (DESIGN.md "numerics"). */
 } pplhip_model_desc;
+
+/* values of pplhip_model_desc.act_quant_bit besides 0: low byte the code width, bit 8 marks e4m3fn */
+#define PPLHIP_ACT_QUANT_I8 8      /* online_i8i8 */
+#define PPLHIP_ACT_QUANT_FP8 0x108 /* online_f8f8 */
+/* online_f8f8 arrived without a version bump (pplhip_version() stays 1.2): a client tells a library that has it by the symbol
+ * pplhip_op_linear_f8 (dlsym) or by pplhip_init accepting act_quant_bit PPLHIP_ACT_QUANT_FP8 (older 1.2 libraries return
+ * PPLHIP_INVALID_VALUE for it). */
 
 /* ---- context options: what CudaResourceManager::Init/InitTask take (resource_manager.cc:213-428) */
 typedef struct pplhip_opts {
@@ -342,6 +353,19 @@ PPLHIP_API int pplhip_op_rmsnorm_quant(void* stream, const void* x, const void* 
 PPLHIP_API int pplhip_op_quant_act(void* stream, const void* x, int64_t M, int32_t K, void* q, float* sx);
 PPLHIP_API int pplhip_op_quant_weight(void* stream, const void* w, int32_t N, int32_t K, void* q, void* scale);
 PPLHIP_API int pplhip_op_linear_i8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M,
+                                   int32_t N, int32_t K, void* y, int32_t out_fp32, int32_t swiglu);
+
+/* online_f8f8 (fp8 e4m3fn W8A8).  Every row -- a token's activations, a weight matrix's output row -- is quantised by the fp8 KV
+ * row rule: e = the smallest integer with 448 * 2^e >= max|x|, clamped to [-15, 8] (0 for an all-zero row: -15),
+ * q = e4m3fn_rne(x * 2^-e) saturated to +-448 (+-240 at e = 8).  Activations: q[M,K] codes, sx[M] = 2^e (fp32); weights:
+ * q[N,K] codes, scale[N] = fp16(2^e); y[m,n] = (sum_k xq * w in fp32) * sx[m] * scale[n], rounded to fp16 (or kept fp32);
+ * K % 16 == 0; swiglu as in pplhip_op_linear_swiglu.  pplhip_op_rmsnorm_quant_f8 = pplhip_op_quant_act_f8(pplhip_op_rmsnorm(...)),
+ * bit for bit. */
+PPLHIP_API int pplhip_op_rmsnorm_quant_f8(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t T,
+                                          int32_t hidden, void* residual_out, void* q, float* sx);
+PPLHIP_API int pplhip_op_quant_act_f8(void* stream, const void* x, int64_t M, int32_t K, void* q, float* sx);
+PPLHIP_API int pplhip_op_quant_weight_f8(void* stream, const void* w, int32_t N, int32_t K, void* q, void* scale);
+PPLHIP_API int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M,
                                    int32_t N, int32_t K, void* y, int32_t out_fp32, int32_t swiglu);
 
 PPLHIP_API int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out);

@@ -118,6 +118,13 @@ __device__ __forceinline__ uint32_t fp8_e4m3_rne(float y) {
     }
     return sign | code;
 }
+// 2^e as an fp32 (e in [-126, 127]), exact
+__device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float, (uint32_t)(127 + e) << 23); }
+// e4m3fn code of x in a row of scale exponent e: rne(x 2^-e), saturated to +-448, or +-240 at e = 8 so that q 2^e stays finite in fp16
+__device__ __forceinline__ uint32_t fp8_quant(float x, int e) {
+    const float lim = e == 8 ? 240.0f : 448.0f;
+    return fp8_e4m3_rne(fminf(fmaxf(__fmul_rn(x, pow2f(-e)), -lim), lim));
+}
 // 16 e4m3fn codes (a 16-byte piece) -> 16 fp32, exact (v_cvt_pk_f32_fp8)
 __device__ __forceinline__ void cvt_fp8x16_f32(const uint4& v, float* f) {
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};

@@ -37,7 +37,7 @@ hipError_t launch_gather_last_rows(hipStream_t s, const uint16_t* x, const int64
 // Each thread keeps up to MAXC chunks of its row in registers (hidden <= 256*8*MAXC); larger rows re-read.
 // NT threads per row: 256, or -- steps of a few hundred rows at most, where the launch is one block per CU or less and a row is a chain of
 // latencies (load, reduce, barrier, store) rather than bandwidth -- 512 / 1024 with one chunk per thread (launch_rmsnorm)
-template <int MAXC, int NT = 256>
+template <int MAXC, int NT = 256, bool F8 = false>
 __global__ __launch_bounds__(NT) void rmsnorm_kernel(const uint4* x /* may alias residual_out */, const uint4* __restrict__ skip,
                                                       const uint4* __restrict__ w, float eps, int chunks, int hidden,
                                                       const int64_t* __restrict__ gather, uint4* __restrict__ out,
@@ -118,6 +118,24 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(const uint4* x /* may alias
     amax = fmaxf(fmaxf(redq[0], redq[1]), fmaxf(redq[2], redq[3]));
 #pragma unroll
     for (int wv = 4; wv < NT / 64; ++wv) amax = fmaxf(amax, redq[wv]);
+    if constexpr (F8) {   // online_f8f8: the same rows as e4m3fn codes under 2^e (k_gemm_i8.hip, quant_act_f8_kernel)
+        const int e = fp8_row_exp(amax);
+        if (threadIdx.x == 0) sx[r] = pow2f(e);
+#pragma unroll
+        for (int i = 0; i < MAXC; ++i) {
+            const int c = threadIdx.x + i * NT;
+            if (c < chunks) {
+                uint32_t lo = 0, hi = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    lo |= fp8_quant(v[i][j], e) << (8 * j);
+                    hi |= fp8_quant(v[i][4 + j], e) << (8 * j);
+                }
+                *reinterpret_cast<uint2*>(qout + r * (int64_t)hidden + c * 8) = make_uint2(lo, hi);
+            }
+        }
+        return;
+    }
     const float qinv = amax > 0.f ? 127.0f / amax : 0.f;
     if (threadIdx.x == 0) sx[r] = amax / 127.0f;
 #pragma unroll
@@ -138,7 +156,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(const uint4* x /* may alias
 
 hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip, const uint16_t* w, float eps,
                           int64_t rows, int hidden, const int64_t* gather_seq_starts, uint16_t* out,
-                          uint16_t* residual_out, int8_t* qout, float* sx, const SplitSlabs* skip_slabs) {
+                          uint16_t* residual_out, int8_t* qout, float* sx, const SplitSlabs* skip_slabs, bool q_fp8) {
     if (rows == 0) return hipSuccess;
     const int chunks = hidden / 8;
     if (hidden % 8 || chunks > 256 * 8) return hipErrorInvalidValue;
@@ -148,9 +166,14 @@ hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip
         if (sl.N != hidden) return hipErrorInvalidValue;
     }
     dim3 g((unsigned)rows), b(256);
-#define RMS_LAUNCH(MC)                                                                                              \
-    hipLaunchKernelGGL(rmsnorm_kernel<MC>, g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,   \
-                       chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl)
+    if (q_fp8 && !qout) return hipErrorInvalidValue;
+#define RMS_LAUNCH(MC)                                                                                                              \
+    do {                                                                                                                            \
+        if (q_fp8) hipLaunchKernelGGL((rmsnorm_kernel<MC, 256, true>), g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, \
+                                      eps, chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);    \
+        else hipLaunchKernelGGL(rmsnorm_kernel<MC>, g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,          \
+                                chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);               \
+    } while (0)
     // few rows of a wide model (decode steps of 5..512 rows at hidden >= 4096): one chunk per thread on 512 / 1024 threads -- every load of
     // the row is in flight at once.  -1.9 % on config 4's per-rank step and -0.4..-1.7 % on 7B steps of 8-512 rows
     // (profiles/r04_rmsnorm_wide_ab.log).  The two forms sum a row's squares in different orders, so a token's norm -- and in the last bits
@@ -163,6 +186,13 @@ hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip
     // (profiles/r05_w4_gqa_margin.log).  PPLHIP_RMSNORM_WIDE_MAX_ROWS=0: the 256-thread form (A/B runs)
     static const int wide_rows = getenv("PPLHIP_RMSNORM_WIDE_MAX_ROWS") ? atoi(getenv("PPLHIP_RMSNORM_WIDE_MAX_ROWS")) : 512;
     if (rows > 4 && rows <= wide_rows && chunks >= 512 && chunks <= 1024 && chunks % 64 == 0) {
+        if (q_fp8) {
+            if (chunks <= 512) hipLaunchKernelGGL((rmsnorm_kernel<1, 512, true>), g, dim3(512), 0, s, (const uint4*)x, (const uint4*)skip,
+                                                  (const uint4*)w, eps, chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
+            else hipLaunchKernelGGL((rmsnorm_kernel<1, 1024, true>), g, dim3(1024), 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w,
+                                    eps, chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
+            return hipGetLastError();
+        }
         if (chunks <= 512) hipLaunchKernelGGL((rmsnorm_kernel<1, 512>), g, dim3(512), 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,
                                               chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
         else hipLaunchKernelGGL((rmsnorm_kernel<1, 1024>), g, dim3(1024), 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,

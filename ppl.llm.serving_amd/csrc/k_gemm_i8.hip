@@ -13,15 +13,26 @@
 // consumer form (gemm_i8_pc_kernel).
 // Skinny / generic kernel (any M, K % 16 == 0): one block per 16 weight rows, waves split K, weights straight from HBM
 // into the MFMA A operand, activations (L2 resident) into B; grid.y walks 32-row activation groups.
+//
+// online_f8f8 (fp8 e4m3fn W8A8) runs on the same kernels (template flag F8): per row, the fp8 KV row rule (k_common.h) gives
+// q = e4m3fn_rne(x 2^-e) with one power-of-two scale 2^e per token (sx, fp32) and per output row (scale, fp16)   quant_*_f8_kernel
+//   y[m,n] = fp16( (sum_k qx * qw) * 2^ex[m] * 2^ew[n] ),  fp32 sums of exact products on v_mfma_scale_f32_16x16x128_f8f6f4
+// A 128-deep K tile of 128-byte LDS rows feeds ONE fp8 MFMA per 16 x 16 tile where it feeds two int8 ones; ring, swizzle, tile
+// shapes and epilogues are shared.  No 256 x 256 form: fp8 steps of M >= 4096 run the 128 x 128 producer / consumer form.
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "k_gemm_dev.h"
 
 namespace pplhip {
 
 typedef int i4v __attribute__((ext_vector_type(4)));
+typedef int i8v __attribute__((ext_vector_type(8)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+// accumulator of a 16 x 16 tile: exact int32 sums (int8) or fp32 (fp8 -- exact as well for operands whose sums stay below 2^24)
+template <bool F8> using qacc_t = std::conditional_t<F8, f4v, i4v>;
 
 constexpr int I_BN = 128, I_BM = 128, I_BK = 128;
 
@@ -87,10 +98,92 @@ __global__ __launch_bounds__(256) void quant_weight_kernel(const uint16_t* __res
     for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
 }
 
+// online_f8f8: one block per row, the fp8 KV row rule (k_common.h fp8_row_exp / fp8_quant): e = the smallest integer with
+// 448 2^e >= max|x| (clamped to [-15, 8]), q = e4m3fn_rne(x 2^-e).  x [M, ldx] fp16 (K valid) -> q [M, ldq] codes (columns K..ldq-1
+// zero) + sx [M] = 2^e (fp32)
+__global__ __launch_bounds__(256) void quant_act_f8_kernel(const uint16_t* __restrict__ x, int K, int64_t ldx, uint8_t* __restrict__ q,
+                                                           int64_t ldq, float* __restrict__ sx) {
+    __shared__ float red[4];
+    const int64_t m = blockIdx.x;
+    const uint16_t* xr = x + m * ldx;
+    uint8_t* qr = q + m * ldq;
+    const int K8 = K >> 3;
+    float amax = 0.f;
+    for (int i = threadIdx.x; i < K8; i += 256) {
+        const h8 v = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(xr + i * 8));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j]));
+    }
+    for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(h2f(xr[k])));
+    const int e = fp8_row_exp(block_max_256(amax, red));
+    if (threadIdx.x == 0) sx[m] = pow2f(e);
+    for (int i = threadIdx.x; i < K8; i += 256) {
+        const h8 v = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(xr + i * 8));
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lo |= fp8_quant((float)v[j], e) << (8 * j);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hi |= fp8_quant((float)v[4 + j], e) << (8 * j);
+        *reinterpret_cast<uint2*>(qr + i * 8) = make_uint2(lo, hi);
+    }
+    for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) qr[k] = (uint8_t)fp8_quant(h2f(xr[k]), e);
+    for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
+}
+
+// one block per weight row, the same rule: w [N, K] fp16 -> q [N, ldq] e4m3fn codes (pad columns zero) + scale [N] = fp16(2^e)
+__global__ __launch_bounds__(256) void quant_weight_f8_kernel(const uint16_t* __restrict__ w, int K, uint8_t* __restrict__ q, int64_t ldq,
+                                                              uint16_t* __restrict__ scale) {
+    __shared__ float red[4];
+    const int64_t n = blockIdx.x;
+    const uint16_t* wr = w + n * K;
+    uint8_t* qr = q + n * ldq;
+    float amax = 0.f;
+    for (int k = threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(h2f(wr[k])));
+    const int e = fp8_row_exp(block_max_256(amax, red));
+    if (threadIdx.x == 0) scale[n] = f2h(pow2f(e));
+    for (int k = threadIdx.x; k < K; k += 256) qr[k] = (uint8_t)fp8_quant(h2f(wr[k]), e);
+    for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
+}
+
 template <int EPI>
 __device__ __forceinline__ void store4_i8(void* yv, int64_t ldy, int64_t m, int n, i4v acc, float sxm, h4 sh) {
     store4<EPI>(yv, ldy, m, n, ((float)acc[0] * sxm) * (float)sh[0], ((float)acc[1] * sxm) * (float)sh[1],
                 ((float)acc[2] * sxm) * (float)sh[2], ((float)acc[3] * sxm) * (float)sh[3]);
+}
+// fp8: sxm = 2^ex and sh = 2^ew, so both products are exact -- y = fp16(2^(ex + ew) * acc)
+template <int EPI>
+__device__ __forceinline__ void store4_i8(void* yv, int64_t ldy, int64_t m, int n, f4v acc, float sxm, h4 sh) {
+    store4<EPI>(yv, ldy, m, n, (acc[0] * sxm) * (float)sh[0], (acc[1] * sxm) * (float)sh[1], (acc[2] * sxm) * (float)sh[2],
+                (acc[3] * sxm) * (float)sh[3]);
+}
+
+// one 16 x 16 x 128 fp8 product on the scaled MFMA with unit E8M0 scales (127 = 2^0; the power-of-two scales go on in the epilogue).
+// lo / hi: the 16-byte k chunks the int8 form feeds its two 16x16x64 MFMAs with (chunks kq and 4 + kq of the 128-deep tile).  Both
+// operands carry the same k permutation, so the sum is the sum over the tile's 128 k.
+__device__ __forceinline__ f4v mma_f8(i4v alo, i4v ahi, i4v blo, i4v bhi, f4v c) {
+    const i8v a = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7), b = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
+}
+// consumer step of a 128-deep LDS tile pair ([row][128 B], g_swz chunks) for a 64 x 64 wave tile: weight rows wr0.., activation rows xr0..
+__device__ __forceinline__ void mma_tile_f8(const char* ws, const char* xs, int wr0, int xr0, int l15, int kq, f4v (&acc)[4][4]) {
+    i4v a[2][4], b[2][4];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = wr0 + i * 16 + l15;
+            a[ks][i] = *reinterpret_cast<const i4v*>(ws + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = xr0 + j * 16 + l15;
+            b[ks][j] = *reinterpret_cast<const i4v*>(xs + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = mma_f8(a[0][i], a[1][i], b[0][j], b[1][j], acc[i][j]);
 }
 
 template <int EPI>
@@ -184,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_kernel(const int8_t* __restric
 // Producer / consumer form of the tile kernel: 8 waves, waves 0..3 multiply (2 x 2 layout as above), waves 4..7 do nothing but wait
 // for their LDS-DMA pieces and refill the ring (the ~100-cycle issue cost of a piece then runs beside the MFMA stream instead of in
 // front of it: int8 moves 8 pieces per 32 MFMAs and wave, more than the fp16 kernel).  ST stages of 32 KiB, one barrier per tile.
-template <int EPI, int ST>
+template <int EPI, int ST, bool F8>
 __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restrict__ xq, const float* __restrict__ sx,
                                                          const int8_t* __restrict__ w, const uint16_t* __restrict__ scale, int64_t M,
                                                          int N, int K, void* __restrict__ yv, int64_t ldy, int n_tiles, int m_tiles) {
@@ -241,17 +334,21 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
     }
 
     const int wn = wave & 1, wm = wave >> 1;
-    i4v acc[4][4];
+    qacc_t<F8> acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = i4v{0, 0, 0, 0};
+        for (int j = 0; j < 4; ++j) acc[i][j] = qacc_t<F8>{0, 0, 0, 0};
     int st = 0;
     for (int t = 0; t < ktiles; ++t) {
         __syncthreads();
         const char* xs = smem_i8 + st * TILE;
         const char* ws = smem_i8 + ST * TILE + st * TILE;
         st = st == ST - 1 ? 0 : st + 1;
+        if constexpr (F8) {
+            mma_tile_f8(ws, xs, wn * 64, wm * 64, l15, kq, acc);
+            continue;
+        }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             i4v a[4], b[4];
@@ -293,7 +390,7 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
 constexpr int IW_BN = 384, IW_NC = 12, IW_NP = 4, IW_ST = 2;
 constexpr int IW_XB = I_BM * I_BK, IW_WB = IW_BN * I_BK;       // 16 KiB + 48 KiB per stage
 constexpr int IW_PP = (IW_XB + IW_WB) / 1024 / IW_NP;           // 16 one-KiB pieces per producer wave and tile (4 activation + 12 weight)
-template <int EPI>
+template <int EPI, bool F8>
 __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(const int8_t* __restrict__ xq, const float* __restrict__ sx,
                                                                              const int8_t* __restrict__ w, const uint16_t* __restrict__ scale,
                                                                              int64_t M, int N, int K, void* __restrict__ yv, int64_t ldy,
@@ -351,15 +448,19 @@ __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(cons
 
     const int l15 = lane & 15, kq = lane >> 4;
     const int wn = wave % 6, wm = wave / 6;
-    i4v acc[4][4];
+    qacc_t<F8> acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = i4v{0, 0, 0, 0};
+        for (int j = 0; j < 4; ++j) acc[i][j] = qacc_t<F8>{0, 0, 0, 0};
     for (int t = 0; t < ktiles; ++t) {
         __syncthreads();
         const char* xs = smem_i8 + (t & 1) * IW_XB;
         const char* ws = smem_i8 + IW_ST * IW_XB + (t & 1) * IW_WB;
+        if constexpr (F8) {
+            mma_tile_f8(ws, xs, wn * 64, wm * 64, l15, kq, acc);
+            continue;
+        }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             i4v a[4], b[4];
@@ -498,7 +599,8 @@ __global__ __launch_bounds__(512) void gemm_i8_256_kernel(const int8_t* __restri
 }
 
 // skinny / generic: block = NW waves = NW K slices of 16 weight rows; MT = 16-row activation tiles per block (grid.y walks M)
-template <int MT, int EPI, int NW>
+// fp8 (F8): one scaled 16x16x128 MFMA per two wave-loads (their 16-byte pieces as the lo / hi halves of both operands, mma_f8)
+template <int MT, int EPI, int NW, bool F8>
 __global__ __launch_bounds__(NW * 64) void gemv_i8_kernel(const int8_t* __restrict__ xq, const float* __restrict__ sx,
                                                           const int8_t* __restrict__ w, const uint16_t* __restrict__ scale, int64_t M, int N,
                                                           int K, void* __restrict__ yv, int64_t ldy) {
@@ -520,9 +622,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_i8_kernel(const int8_t* __restri
         if (m >= M) m = M - 1;
         xrow[mt] = xq + m * K;
     }
-    i4v acc[MT];
+    qacc_t<F8> acc[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] = i4v{0, 0, 0, 0};
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = qacc_t<F8>{0, 0, 0, 0};
     constexpr int U = 8;  // wave-loads of weights in flight (the block streams its rows once: bytes in flight = bandwidth)
     for (int st0 = s_begin; st0 < s_end; st0 += U) {
         i4v wr[U];
@@ -531,6 +633,20 @@ __global__ __launch_bounds__(NW * 64) void gemv_i8_kernel(const int8_t* __restri
             const int k = (st0 + u) * 64 + kq * 16;
             const bool ok = st0 + u < s_end && k < K;  // K % 16 == 0 (launcher)
             wr[u] = ok ? *reinterpret_cast<const i4v*>(wrow + k) : i4v{0, 0, 0, 0};
+        }
+        if constexpr (F8) {
+#pragma unroll
+            for (int u = 0; u < U; u += 2) {
+                const int k = (st0 + u) * 64 + kq * 16;
+                const bool ok0 = st0 + u < s_end && k < K, ok1 = st0 + u + 1 < s_end && k + 64 < K;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const i4v x0 = ok0 ? *reinterpret_cast<const i4v*>(xrow[mt] + k) : i4v{0, 0, 0, 0};
+                    const i4v x1 = ok1 ? *reinterpret_cast<const i4v*>(xrow[mt] + k + 64) : i4v{0, 0, 0, 0};
+                    acc[mt] = mma_f8(wr[u], wr[u + 1], x0, x1, acc[mt]);
+                }
+            }
+            continue;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -545,7 +661,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_i8_kernel(const int8_t* __restri
     }
     if (wave > 0) {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) *reinterpret_cast<i4v*>(red[wave - 1][mt][lane]) = acc[mt];
+        for (int mt = 0; mt < MT; ++mt) *reinterpret_cast<qacc_t<F8>*>(red[wave - 1][mt][lane]) = acc[mt];
     }
     __syncthreads();
     if (wave == 0) {
@@ -554,9 +670,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_i8_kernel(const int8_t* __restri
             const h4 sh = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(scale + nn));
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                i4v v = acc[mt];
+                qacc_t<F8> v = acc[mt];
 #pragma unroll
-                for (int ww = 0; ww < NW - 1; ++ww) v += *reinterpret_cast<const i4v*>(red[ww][mt][lane]);
+                for (int ww = 0; ww < NW - 1; ++ww) v += *reinterpret_cast<const qacc_t<F8>*>(red[ww][mt][lane]);
                 const int64_t m = mbase + mt * 16 + l15;
                 if (m >= M) continue;
                 store4_i8<EPI>(yv, ldy, m, nn, v, sx[m], sh);
@@ -579,8 +695,25 @@ hipError_t launch_quant_weight(hipStream_t s, const uint16_t* w, int N, int K, i
     return hipGetLastError();
 }
 
-hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M, int N,
-                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
+hipError_t launch_quant_act_f8(hipStream_t s, const uint16_t* x, int64_t M, int K, int64_t ldx, uint8_t* q, int64_t ldq, float* sx) {
+    if (M == 0) return hipSuccess;
+    if (K % 8 || ldx % 8 || ldq % 8 || ldq < K) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(quant_act_f8_kernel, dim3((unsigned)M), dim3(256), 0, s, x, K, ldx, q, ldq, sx);
+    return hipGetLastError();
+}
+
+hipError_t launch_quant_weight_f8(hipStream_t s, const uint16_t* w, int N, int K, uint8_t* q, int64_t ldq, uint16_t* scale) {
+    if (N == 0) return hipSuccess;
+    if (ldq < K) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(quant_weight_f8_kernel, dim3((unsigned)N), dim3(256), 0, s, w, K, q, ldq, scale);
+    return hipGetLastError();
+}
+
+// the int8 (F8 false) and fp8 (F8 true) launches share one dispatch table, except that fp8 has no 256 x 256 form (steps of M >= 4096
+// take the 128 x 128 producer / consumer form) and no 4-wave form (a forced PPLHIP_GEMM_I8_PC=0 runs the 2-stage producer / consumer form)
+template <bool F8>
+static hipError_t launch_linear_q8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M,
+                                   int N, int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
     if (M == 0) return hipSuccess;
     if (swiglu && out_fp32) return hipErrorInvalidValue;
     if (N % 4 || ldy % 4 || K % 16) return hipErrorInvalidValue;
@@ -593,9 +726,11 @@ hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, co
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (!attr_dev[dev & 63]) {
-            (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (!F8) {
+                (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            }
             attr_dev[dev & 63] = true;
         }
         dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles));
@@ -603,7 +738,7 @@ hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, co
         // w2 76.0 -> 51.4 us with a 4-stage ring, one block per CU; w13 116.6 -> 106.0 us with two stages, two blocks per CU; wqkv
         // 62.1 vs 63.6 us; M = 2048 layer 502 -> 459 us, M = 8192 equal).  PPLHIP_GEMM_I8_PC = 0 (4-wave kernel) / 2 / 3 / 4 forces a form.
         static const int min_m256 = tune_int("PPLHIP_GEMM_I8_256_MIN_M", 4096);  // measured: M = 4096 layer 888 us (1.87 POP/s) vs 1110, M = 2048 554 vs 459 us
-        if (M >= min_m256 && N >= 1024) {
+        if (!F8 && M >= min_m256 && N >= 1024) {
             const int nt2 = (N + 255) / 256, mt2 = (int)((M + 255) / 256);
             static const int st256 = tune_int("PPLHIP_GEMM_I8_256_ST", 4);
             const size_t lds2 = (size_t)(st256 == 3 ? 3 : 4) * 2 * 256 * 64;
@@ -636,57 +771,70 @@ hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, co
                 const size_t ldsw = (size_t)IW_ST * (IW_XB + IW_WB);
                 static bool attr_w[64] = {false};
                 if (!attr_w[dev & 63]) {
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
+                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_F16, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
+                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_F32, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
+                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_SWIGLU, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
                     attr_w[dev & 63] = true;
                 }
                 dim3 gw((unsigned)((ntw + 7) / 8 * 8 * mtw));
-#define LW(E) hipLaunchKernelGGL((gemm_i8_wide_kernel<E>), gw, dim3((IW_NC + IW_NP) * 64), ldsw, s, xq, sx, w, scale, M, N, K, y, ldy, ntw, mtw)
+#define LW(E) hipLaunchKernelGGL((gemm_i8_wide_kernel<E, F8>), gw, dim3((IW_NC + IW_NP) * 64), ldsw, s, xq, sx, w, scale, M, N, K, y, ldy, ntw, mtw)
                 if (epi == EPI_F32) LW(EPI_F32); else if (epi == EPI_F16) LW(EPI_F16); else LW(EPI_SWIGLU);
 #undef LW
                 return hipGetLastError();
             }
         }
         static const int forced_pc = tune_int("PPLHIP_GEMM_I8_PC", -1);
-        const int pc = forced_pc >= 0 ? forced_pc : ((int64_t)n_tiles * m_tiles <= 256 ? 4 : 2);
+        int pc = forced_pc >= 0 ? forced_pc : ((int64_t)n_tiles * m_tiles <= 256 ? 4 : 2);
+        if (F8 && pc != 3 && pc != 4) pc = 2;
         if (pc == 2 || pc == 3 || pc == 4) {
             const size_t lds_pc = (size_t)pc * 2 * I_BM * I_BK;
             static bool attr_pc[64] = {false};
             if (!attr_pc[dev & 63]) {
-#define PCA(E) do { (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 2 * I_BM * I_BK); \
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * I_BM * I_BK); \
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * I_BM * I_BK); } while (0)
+#define PCA(E) do { (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 3, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 2 * I_BM * I_BK); \
+                    (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 4, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * I_BM * I_BK); \
+                    (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 2, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * I_BM * I_BK); } while (0)
                 PCA(EPI_F16); PCA(EPI_F32); PCA(EPI_SWIGLU);
 #undef PCA
                 attr_pc[dev & 63] = true;
             }
-#define LPC(E) do { if (pc == 2) hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 2>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); \
-                    else if (pc == 3) hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 3>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); \
-                    else hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 4>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); } while (0)
+#define LPC(E) do { if (pc == 2) hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 2, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); \
+                    else if (pc == 3) hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 3, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); \
+                    else hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 4, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); } while (0)
             if (epi == EPI_F32) LPC(EPI_F32); else if (epi == EPI_F16) LPC(EPI_F16); else LPC(EPI_SWIGLU);
 #undef LPC
             return hipGetLastError();
         }
+        if constexpr (!F8) {
 #define LT(E) hipLaunchKernelGGL((gemm_i8_kernel<E>), grid, dim3(256), lds, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles)
-        if (epi == EPI_F32) LT(EPI_F32); else if (epi == EPI_F16) LT(EPI_F16); else LT(EPI_SWIGLU);
+            if (epi == EPI_F32) LT(EPI_F32); else if (epi == EPI_F16) LT(EPI_F16); else LT(EPI_SWIGLU);
 #undef LT
+        }
         return hipGetLastError();
     }
     const int nblk = (N + 15) / 16;
     if (M <= 16) {
         dim3 grid((unsigned)nblk, 1);
-#define LV(E) do { if (nblk <= 1024) hipLaunchKernelGGL((gemv_i8_kernel<1, E, 8>), grid, dim3(512), 0, s, xq, sx, w, scale, M, N, K, y, ldy); \
-                   else hipLaunchKernelGGL((gemv_i8_kernel<1, E, 4>), grid, dim3(256), 0, s, xq, sx, w, scale, M, N, K, y, ldy); } while (0)
+#define LV(E) do { if (nblk <= 1024) hipLaunchKernelGGL((gemv_i8_kernel<1, E, 8, F8>), grid, dim3(512), 0, s, xq, sx, w, scale, M, N, K, y, ldy); \
+                   else hipLaunchKernelGGL((gemv_i8_kernel<1, E, 4, F8>), grid, dim3(256), 0, s, xq, sx, w, scale, M, N, K, y, ldy); } while (0)
         if (epi == EPI_F32) LV(EPI_F32); else if (epi == EPI_F16) LV(EPI_F16); else LV(EPI_SWIGLU);
 #undef LV
         return hipGetLastError();
     }
     dim3 grid((unsigned)nblk, (unsigned)((M + 31) / 32));
-#define LV(E) hipLaunchKernelGGL((gemv_i8_kernel<2, E, 4>), grid, dim3(256), 0, s, xq, sx, w, scale, M, N, K, y, ldy)
+#define LV(E) hipLaunchKernelGGL((gemv_i8_kernel<2, E, 4, F8>), grid, dim3(256), 0, s, xq, sx, w, scale, M, N, K, y, ldy)
     if (epi == EPI_F32) LV(EPI_F32); else if (epi == EPI_F16) LV(EPI_F16); else LV(EPI_SWIGLU);
 #undef LV
     return hipGetLastError();
+}
+
+hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M, int N,
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
+    return launch_linear_q8<false>(s, xq, sx, w, scale, M, N, K, y, ldy, out_fp32, swiglu);
+}
+
+hipError_t launch_linear_f8(hipStream_t s, const uint8_t* xq, const float* sx, const uint8_t* w, const uint16_t* scale, int64_t M, int N,
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
+    return launch_linear_q8<true>(s, (const int8_t*)xq, sx, (const int8_t*)w, scale, M, N, K, y, ldy, out_fp32, swiglu);
 }
 
 }  // namespace pplhip

@@ -58,7 +58,8 @@ hipError_t launch_embedding(hipStream_t s, const int64_t* token_ids, const uint1
 hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip, const uint16_t* w, float eps,
                           int64_t rows, int hidden, const int64_t* gather_seq_starts, uint16_t* out,
                           uint16_t* residual_out, int8_t* qout = nullptr, float* sx = nullptr,
-                          const SplitSlabs* skip_slabs = nullptr);  // skip_slabs: the skip operand as unreduced split-K slabs
+                          const SplitSlabs* skip_slabs = nullptr,   // skip_slabs: the skip operand as unreduced split-K slabs
+                          bool q_fp8 = false);  // qout / sx: int8 rows and max|y| / 127 (online_i8i8), or e4m3fn rows and 2^e (online_f8f8)
 hipError_t launch_silu_mul(hipStream_t s, const uint16_t* gate_up, int64_t T, int inter, uint16_t* out);
 // out[r] = x[seq_starts[r + 1] - 1] (last-token gather of K11 when the final norm already ran on every row: fused tensor-parallel norm)
 hipError_t launch_gather_last_rows(hipStream_t s, const uint16_t* x, const int64_t* seq_starts, int64_t B, int hidden, uint16_t* out);
@@ -132,6 +133,14 @@ hipError_t launch_quant_act(hipStream_t s, const uint16_t* x, int64_t M, int K, 
 hipError_t launch_quant_weight(hipStream_t s, const uint16_t* w, int N, int K, int8_t* q, int64_t ldq, uint16_t* scale);
 // y[M,N] = fp16/fp32( (sum_k xq * w) * sx[m] * scale[n] ); K = row stride of xq and w (K % 16 == 0)
 hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M, int N,
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu);
+// online_f8f8 (fp8 e4m3fn W8A8): per-row codes under one power-of-two scale (the fp8 KV row rule, k_common.h fp8_row_exp / fp8_quant)
+// activations: q [M, ldq] (columns K..ldq-1 zeroed), sx [M] = 2^e (fp32)
+hipError_t launch_quant_act_f8(hipStream_t s, const uint16_t* x, int64_t M, int K, int64_t ldx, uint8_t* q, int64_t ldq, float* sx);
+// weights from an fp16 [N, K] matrix: q [N, ldq], scale [N] = fp16(2^e)
+hipError_t launch_quant_weight_f8(hipStream_t s, const uint16_t* w, int N, int K, uint8_t* q, int64_t ldq, uint16_t* scale);
+// y[M,N] = fp16/fp32( (sum_k xq * w) * sx[m] * scale[n] ), fp32 sums; K = row stride of xq and w (K % 16 == 0)
+hipError_t launch_linear_f8(hipStream_t s, const uint8_t* xq, const float* sx, const uint8_t* w, const uint16_t* scale, int64_t M, int N,
                             int K, void* y, int64_t ldy, bool out_fp32, bool swiglu);
 // dst row r = src row perm(r): r even -> r/2 (gate), r odd -> half + r/2 (up).  row_bytes % 4 == 0.
 hipError_t launch_interleave_rows(hipStream_t s, const void* src, void* dst, int rows, int64_t row_bytes);

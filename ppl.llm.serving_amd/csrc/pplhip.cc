@@ -24,6 +24,10 @@ using namespace pplhip;
 
 namespace {
 
+// activation format of the layer linears, from pplhip_model_desc.act_quant_bit (act_format, derived once at init):
+// fp16, int8 per token (online_i8i8), or e4m3fn per token under a power-of-two scale (online_f8f8)
+enum { ACT_FP16 = 0, ACT_I8 = 1, ACT_FP8 = 2 };
+
 struct Linear {
     int N = 0, K = 0, qbit = 0, group = 0;
     int Kp = 0;  // row stride on the device: K rounded up to the GEMM k-tile (64) with zero columns, so that a tensor-
@@ -154,6 +158,7 @@ struct pplhip_ctx {
     pplhip_model_desc d;
     pplhip_opts o;
     int kv_fmt = KV_FP16;  // KV cache format of (d.cache_quant_bit, d.cache_quant_group): kv_format(), derived once at init
+    int act_fmt = ACT_FP16;  // activation format of d.act_quant_bit: act_format(), derived once at init
     int tp = 1;
     bool tp_overlap = true;              // PPLHIP_TP_OVERLAP=0 keeps the collectives on the compute stream
     // PPLHIP_TP_OVERLAP_MIN_TOKENS.  Measured on one MI355X with identity collectives (bench.py --emulate-tp 2/4/8,
@@ -235,8 +240,17 @@ int fail(pplhip_ctx* c, int rank, int code, const std::string& msg) {
 static inline float h2f_host(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 static inline uint16_t f2h_host(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 
-// k-tile the padded row stride of w2 / the SwiGLU output is rounded to: 64 (fp16-activation tile GEMM), 128 (int8 x int8)
-static int k_tile(const pplhip_model_desc& d) { return d.act_quant_bit == 8 ? 128 : 64; }
+// ACT_* of an act_quant_bit value (-1: none); the quantised forms need weight_quant_bit 8
+static int act_format(int act_quant_bit, int weight_quant_bit) {
+    if (act_quant_bit == 0) return ACT_FP16;
+    if (weight_quant_bit != 8) return -1;
+    if (act_quant_bit == PPLHIP_ACT_QUANT_I8) return ACT_I8;
+    if (act_quant_bit == PPLHIP_ACT_QUANT_FP8) return ACT_FP8;
+    return -1;
+}
+
+// k-tile the padded row stride of w2 / the SwiGLU output is rounded to: 64 (fp16-activation tile GEMM), 128 (int8 / fp8 operands)
+static int k_tile(const pplhip_ctx* c) { return c->act_fmt != ACT_FP16 ? 128 : 64; }
 
 int dev_alloc(pplhip_ctx* c, int r, void** p, uint64_t bytes) {
     *p = nullptr;
@@ -249,7 +263,7 @@ int dev_alloc(pplhip_ctx* c, int r, void** p, uint64_t bytes) {
 
 int linear_alloc(pplhip_ctx* c, int r, Linear* l, int N, int K, int qbit, int group, bool pad_k = false) {
     l->N = N; l->K = K; l->qbit = qbit; l->group = group;
-    const int kt = k_tile(c->d);
+    const int kt = k_tile(c);
     l->Kp = (pad_k && qbit != 4) ? (K + kt - 1) / kt * kt : K;
     int rc = dev_alloc(c, r, &l->w, l->alloc_bytes());
     if (rc) return rc;
@@ -443,7 +457,7 @@ int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
     // own one-rank form ("solo": same arithmetic, no peers) turns them into the expected residual and normed rows; the real kernel, run on
     // the unreduced patterns, must then give the same bits in every row it gathered and in the residual rows it owns
     const int64_t frows = hd > 0 ? cnt / hd : 0;
-    if (ok && c->fuse_norm_want && c->d.act_quant_bit != 8 && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN && frows >= 1 &&
+    if (ok && c->fuse_norm_want && c->act_fmt == ACT_FP16 && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN && frows >= 1 &&
         c->ranks[0].gemm_ws_bytes >= (size_t)frows * hd * 4 + (size_t)hd * 2) {
         const int64_t fcnt = frows * hd;
         std::vector<uint16_t> want_x(fcnt), want_h(fcnt);
@@ -557,7 +571,8 @@ static bool fuse_norm_active(const pplhip_ctx* c, const Rank& R);
 extern "C" {
 
 int pplhip_version(void) { return (1 << 16) | 2; }  // 1.1: pplhip_model_desc.act_quant_bit, comm_* and W8A8 operator entry points;
-                                                    // 1.2: fp8 e4m3 KV cache (cache_quant_bit 8, cache_quant_group = head_dim)
+                                                    // 1.2: fp8 e4m3 KV cache (cache_quant_bit 8, cache_quant_group = head_dim),
+                                                    //      online_f8f8 (act_quant_bit PPLHIP_ACT_QUANT_FP8) and pplhip_op_*_f8
 
 int pplhip_device_count(void) {
     int n = 0;
@@ -653,10 +668,11 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
     if (d.cache_layout < 0 || d.cache_layout > 3 || d.cache_mode < 0 || d.cache_mode > 1) return bad("cache layout/mode");
     if (d.cache_mode == 1 && d.page_size <= 0) return bad("page_size");
     if (d.weight_quant_bit != 0 && d.weight_quant_bit != 8 && d.weight_quant_bit != 4) return bad("weight quant");
-    if (d.act_quant_bit != 0 && !(d.act_quant_bit == 8 && d.weight_quant_bit == 8)) return bad("act quant (8 needs weight_quant_bit 8)");
+    if (act_format(d.act_quant_bit, d.weight_quant_bit) < 0) return bad("act quant (8 / 0x108 need weight_quant_bit 8)");
     if (opts->max_running_batch <= 0 || opts->max_tokens_per_step <= 0 || d.max_position <= 0) return bad("limits");
     c->D = d.hidden_dim / d.num_heads;
     c->kv_fmt = kv_format(d.cache_quant_bit, d.cache_quant_group, c->D);
+    c->act_fmt = act_format(d.act_quant_bit, d.weight_quant_bit);
     c->H = d.num_heads / tp;
     c->Hkv = d.num_kv_heads / tp;
     c->inter = d.intermediate_dim / tp;
@@ -889,8 +905,8 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             ALLOC(R.hflags, 64);
             HIPCK(cp, r, hipMemset(R.hflags, 0, 64));
         }
-        const int inter_p = (d.weight_quant_bit != 4) ? (c->inter + k_tile(d) - 1) / k_tile(d) * k_tile(d) : c->inter;  // = layers[*].w2.Kp
-        if (d.act_quant_bit == 8) {  // online_i8i8: the int8 copy of whatever feeds the next linear + its per-token scales
+        const int inter_p = (d.weight_quant_bit != 4) ? (c->inter + k_tile(cp) - 1) / k_tile(cp) * k_tile(cp) : c->inter;  // = layers[*].w2.Kp
+        if (c->act_fmt != ACT_FP16) {  // online_i8i8 / f8f8: the 1-byte copy of whatever feeds the next linear + its per-token scales
             ALLOC(R.xq, (uint64_t)cap_T * std::max(std::max(hd, c->H * c->D), inter_p));
             ALLOC(R.sx, (uint64_t)cap_T * 4);
         }
@@ -994,8 +1010,8 @@ int pplhip_rank_set_tensor(pplhip_ctx* c, int rank, const char* name, const void
     Linear* lin = nullptr;
     if (!find_tensor(c, R, name, &p, &b, &lin)) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown tensor ") + name);
     const char* w13 = strstr(name, "feed_forward.w13.");
-    if (lin && lin->qbit == 8 && c->d.act_quant_bit == 8 && bytes == (uint64_t)lin->N * lin->K * 2) {
-        // online_i8i8 "online" half: an fp16 [N, K] matrix for an int8 linear is quantised per output row on the device
+    if (lin && lin->qbit == 8 && c->act_fmt != ACT_FP16 && bytes == (uint64_t)lin->N * lin->K * 2) {
+        // online_i8i8 / f8f8 "online" half: an fp16 [N, K] matrix for a 1-byte linear is quantised per output row on the device
         HIPCK(c, rank, hipSetDevice(R.device));
         void *tmp = nullptr, *tmp2 = nullptr;
         HIPCK(c, rank, hipMalloc(&tmp, bytes));
@@ -1006,7 +1022,9 @@ int pplhip_rank_set_tensor(pplhip_ctx* c, int rank, const char* name, const void
             if (e == hipSuccess) e = launch_interleave_rows(R.stream, tmp, tmp2, lin->N, (int64_t)lin->K * 2);
             src = (const uint16_t*)tmp2;
         }
-        if (e == hipSuccess) e = launch_quant_weight(R.stream, src, lin->N, lin->K, (int8_t*)lin->w, lin->Kp, lin->scale);
+        if (e == hipSuccess)
+            e = c->act_fmt == ACT_FP8 ? launch_quant_weight_f8(R.stream, src, lin->N, lin->K, (uint8_t*)lin->w, lin->Kp, lin->scale)
+                                      : launch_quant_weight(R.stream, src, lin->N, lin->K, (int8_t*)lin->w, lin->Kp, lin->scale);
         if (e == hipSuccess) e = hipStreamSynchronize(R.stream);
         hipFree(tmp);
         if (tmp2) hipFree(tmp2);
@@ -1014,6 +1032,14 @@ int pplhip_rank_set_tensor(pplhip_ctx* c, int rank, const char* name, const void
         return 0;
     }
     if (b != bytes) return fail(c, rank, PPLHIP_INVALID_VALUE, std::string("tensor ") + name + ": got " + std::to_string(bytes) + " bytes, want " + std::to_string(b));
+    if (c->act_fmt == ACT_FP8 && !lin && strstr(name, ".scale")) {
+        // online_f8f8 codes handed over as they are (N * K bytes + .scale): the row scales must be the powers of two 2^e, e in [-15, 8],
+        // that the row rule produces -- a scale of any other value has no exact fp16 product with the codes
+        const uint16_t* sc = (const uint16_t*)data;
+        for (uint64_t i = 0; i < bytes / 2; ++i)
+            if (sc[i] != 0x0200u && ((sc[i] & 0x83ffu) || sc[i] < 0x0400u || sc[i] > 0x5c00u))   // 2^-15 is the subnormal 0x0200
+                return fail(c, rank, PPLHIP_INVALID_VALUE, std::string("tensor ") + name + ": online_f8f8 scales must be powers of two 2^-15 .. 2^8");
+    }
     HIPCK(c, rank, hipSetDevice(R.device));
     if (w13) {
         // the container stores w13 as [gate rows | up rows]; on the device the rows are interleaved (gate_i, up_i) so
@@ -1080,6 +1106,15 @@ int pplhip_rank_init_synthetic(pplhip_ctx* c, int rank, uint64_t seed) {
     auto lin = [&](Linear& l, int layer, int wslot) -> hipError_t {
         hipError_t e;
         if (l.qbit == 0) return launch_synth_fill(s, 0, seed, tid(layer, wslot), st, AMP, (uint64_t)l.N * l.K, l.w);
+        if (c->act_fmt == ACT_FP8) {   // online_f8f8: the fp16 weights of an fp16 desc with this seed, quantised on the device (rows of K)
+            void* w16 = nullptr;
+            if ((e = hipMalloc(&w16, (uint64_t)l.N * l.K * 2)) != hipSuccess) return e;
+            e = launch_synth_fill(s, 0, seed, tid(layer, wslot), st, AMP, (uint64_t)l.N * l.K, w16);
+            if (e == hipSuccess) e = launch_quant_weight_f8(s, (const uint16_t*)w16, l.N, l.K, (uint8_t*)l.w, l.K, l.scale);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            hipFree(w16);
+            return e;
+        }
         if (l.qbit == 8) {
             if ((e = launch_synth_fill(s, 1, seed, tid(layer, wslot), st, 0.f, (uint64_t)l.N * l.K, l.w)) != hipSuccess) return e;
             return launch_synth_fill(s, 3, seed, tid(layer, wslot + 1), st, AMP / 127.0f, (uint64_t)l.N, l.scale);
@@ -1343,13 +1378,18 @@ struct Chunk {
     int64_t b0, bn, t0, tn, nd;
 };
 
-// one layer linear over a chunk: fp16 activations straight into the (weight-only quantised) GEMM, or -- online_i8i8 -- quantised
-// per token first and multiplied in int8.  x rows have stride l.Kp.
+// one layer linear over a chunk: fp16 activations straight into the (weight-only quantised) GEMM, or -- online_i8i8 / f8f8 -- quantised
+// per token first and multiplied in int8 / e4m3.  x rows have stride l.Kp.
 // pre_quantised: R.xq / R.sx already hold the rows (written by the RMSNorm in front of wqkv / w13).
 static int layer_linear(pplhip_ctx* c, int rank, const Linear& l, const uint16_t* x, int64_t M, void* y, int64_t ldy, bool swiglu,
                         bool pre_quantised = false, SplitSlabs* defer = nullptr) {
     Rank& R = c->ranks[rank];
-    if (c->d.act_quant_bit == 8) {
+    if (c->act_fmt == ACT_FP8) {
+        if (!pre_quantised) HIPCK(c, rank, launch_quant_act_f8(R.stream, x, M, l.Kp, l.Kp, (uint8_t*)R.xq, l.Kp, R.sx));
+        HIPCK(c, rank, launch_linear_f8(R.stream, (const uint8_t*)R.xq, R.sx, (const uint8_t*)l.w, l.scale, M, l.N, l.Kp, y, ldy, false, swiglu));
+        return 0;
+    }
+    if (c->act_fmt == ACT_I8) {
         if (!pre_quantised) HIPCK(c, rank, launch_quant_act(R.stream, x, M, l.Kp, l.Kp, R.xq, l.Kp, R.sx));
         HIPCK(c, rank, launch_linear_i8(R.stream, R.xq, R.sx, (const int8_t*)l.w, l.scale, M, l.N, l.Kp, y, ldy, false, swiglu));
         return 0;
@@ -1371,11 +1411,12 @@ static int layer_attention_part(pplhip_ctx* c, int rank, int l, const Chunk& k, 
     ProfEvent ev;
     uint16_t* h = R.h + k.t0 * hd;
     uint16_t* xn = R.xn + k.t0 * hd;
-    const bool a8 = d.act_quant_bit == 8;  // the norm writes the int8 operand of the next linear directly (no fp16 xn, no separate pass)
+    const bool a8 = c->act_fmt != ACT_FP16;  // the norm writes the 1-byte operand of the next linear directly (no fp16 xn, no separate pass)
     {
         if (!xn_ready)
             HIPCK(c, rank, launch_rmsnorm(s, h, pending ? pending + k.t0 * hd : nullptr, L.attn_norm, d.norm_eps, k.tn, hd, nullptr, xn,
-                                          pending ? h : nullptr, a8 ? R.xq : nullptr, a8 ? R.sx : nullptr, pending ? &R.sl_part2 : nullptr));
+                                          pending ? h : nullptr, a8 ? R.xq : nullptr, a8 ? R.sx : nullptr, pending ? &R.sl_part2 : nullptr,
+                                          c->act_fmt == ACT_FP8));
         R.sl_part2 = SplitSlabs{};
         prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
         { int rc = layer_linear(c, rank, L.wqkv, xn, k.tn, R.qkv + k.t0 * nqkv, L.wqkv.N, false, a8, &R.sl_qkv); if (rc) return rc; }
@@ -1436,10 +1477,10 @@ static int layer_ffn_part(pplhip_ctx* c, int rank, int l, const Chunk& k, bool x
     uint16_t* h = R.h + k.t0 * hd;
     uint16_t* xn = R.xn + k.t0 * hd;
     uint16_t* act = R.act + k.t0 * (int64_t)L.w2.Kp;
-    const bool a8 = d.act_quant_bit == 8;
+    const bool a8 = c->act_fmt != ACT_FP16;
     if (!xn_ready)
         HIPCK(c, rank, launch_rmsnorm(s, h, R.part + k.t0 * hd, L.ffn_norm, d.norm_eps, k.tn, hd, nullptr, xn, h, a8 ? R.xq : nullptr,
-                                      a8 ? R.sx : nullptr, &R.sl_part));
+                                      a8 ? R.sx : nullptr, &R.sl_part, c->act_fmt == ACT_FP8));
     R.sl_part = SplitSlabs{};
     prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
     { int rc = layer_linear(c, rank, L.w13, xn, k.tn, act, L.w2.Kp, /*swiglu=*/true, a8); if (rc) return rc; }
@@ -1453,7 +1494,7 @@ static int layer_ffn_part(pplhip_ctx* c, int rank, int l, const Chunk& k, bool x
 // the sequence-parallel residual stream is in force for this rank's steps (pplhip_ctx::fuse_norm_want)
 static bool fuse_norm_active(const pplhip_ctx* c, const Rank& R) {
     const int hd = c->d.hidden_dim;
-    return c->fuse_norm_want && c->tp_on && c->tp > 1 && c->d.act_quant_bit != 8 && !R.dump_dev && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN &&
+    return c->fuse_norm_want && c->tp_on && c->tp > 1 && c->act_fmt == ACT_FP16 && !R.dump_dev && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN &&
            (c->comm_mode == 2 || c->emulate_tp);
 }
 
@@ -1576,7 +1617,7 @@ static int run_launches(pplhip_ctx* c, int rank) {
     const bool identity_comm = comm && c->comm_mode != 2 && !R.comm;   // ranks emulated on one device (bench.py --emulate-tp)
     bool dual = false;
     if (c->dual_mode && R.stream2 && !ov && nb_decode == B && T == B && B >= c->dual_min_rows && B <= c->dual_max_rows && B >= 2 &&
-        (!comm || identity_comm || c->comm_mode == 2 || (R.comm && R.comm2 && !c->dual_auto)) && d.act_quant_bit != 8 && !R.dump_dev) {
+        (!comm || identity_comm || c->comm_mode == 2 || (R.comm && R.comm2 && !c->dual_auto)) && c->act_fmt == ACT_FP16 && !R.dump_dev) {
         hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(R.stream, &cst);
         if (cst == hipStreamCaptureStatusNone) {
@@ -1617,8 +1658,8 @@ static int run_launches(pplhip_ctx* c, int rank) {
 
     const bool fuse = fuse_norm_active(c, R);
     static const int defer_on = getenv("PPLHIP_DEFER_REDUCE") ? atoi(getenv("PPLHIP_DEFER_REDUCE")) : 1;
-    R.defer_reduce = defer_on && !comm && d.act_quant_bit != 8 && !R.dump_dev && (nck == 1 || dual);
-    R.defer_qkv = defer_on && d.act_quant_bit != 8 && !R.dump_dev && (nck == 1 || dual);   // (wo / w2 feed the all-reduce: their slabs are summed first)
+    R.defer_reduce = defer_on && !comm && c->act_fmt == ACT_FP16 && !R.dump_dev && (nck == 1 || dual);
+    R.defer_qkv = defer_on && c->act_fmt == ACT_FP16 && !R.dump_dev && (nck == 1 || dual);   // (wo / w2 feed the all-reduce: their slabs are summed first)
     R.keep_part2 = false;
     R.sl_qkv = R.sl_part = R.sl_part2 = SplitSlabs{};
     ProfEvent ev_run, ev;
@@ -1779,7 +1820,7 @@ int pplhip_comm_info(pplhip_ctx* c, int64_t rows, pplhip_comm_info_t* out) {
     const Rank& R = c->ranks[0];
     const bool two_chunks = c->tp_on && c->tp_overlap && rows >= c->tp_overlap_min_tokens && rows >= 2;
     const bool two_streams = !two_chunks && c->dual_mode && R.stream2 && rows >= c->dual_min_rows && rows <= c->dual_max_rows && rows >= 2 &&
-                             (!c->tp_on || c->comm_mode == 2 || !R.comm || (R.comm && R.comm2 && !c->dual_auto)) && c->d.act_quant_bit != 8;
+                             (!c->tp_on || c->comm_mode == 2 || !R.comm || (R.comm && R.comm2 && !c->dual_auto)) && c->act_fmt == ACT_FP16;
     out->schedule = two_chunks ? 2 : (two_streams ? 1 : 0);
     snprintf(out->notes, sizeof(out->notes), "%s", c->comm_notes.c_str());
     return 0;
@@ -2072,6 +2113,27 @@ int pplhip_op_quant_weight(void* stream, const void* w, int32_t N, int32_t K, vo
 int pplhip_op_linear_i8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M, int32_t N, int32_t K,
                         void* y, int32_t out_fp32, int32_t swiglu) {
     return op_rc(launch_linear_i8((hipStream_t)stream, (const int8_t*)xq, sx, (const int8_t*)w, (const uint16_t*)scale, M, N, K, y,
+                                  swiglu ? N / 2 : N, out_fp32 != 0, swiglu != 0));
+}
+
+int pplhip_op_rmsnorm_quant_f8(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t T, int32_t hidden,
+                               void* residual_out, void* q, float* sx) {
+    if (!q || !sx) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, T, hidden, nullptr,
+                                nullptr, (uint16_t*)residual_out, (int8_t*)q, sx, nullptr, true));
+}
+
+int pplhip_op_quant_act_f8(void* stream, const void* x, int64_t M, int32_t K, void* q, float* sx) {
+    return op_rc(launch_quant_act_f8((hipStream_t)stream, (const uint16_t*)x, M, K, K, (uint8_t*)q, K, sx));
+}
+
+int pplhip_op_quant_weight_f8(void* stream, const void* w, int32_t N, int32_t K, void* q, void* scale) {
+    return op_rc(launch_quant_weight_f8((hipStream_t)stream, (const uint16_t*)w, N, K, (uint8_t*)q, K, (uint16_t*)scale));
+}
+
+int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M, int32_t N, int32_t K,
+                        void* y, int32_t out_fp32, int32_t swiglu) {
+    return op_rc(launch_linear_f8((hipStream_t)stream, (const uint8_t*)xq, sx, (const uint8_t*)w, (const uint16_t*)scale, M, N, K, y,
                                   swiglu ? N / 2 : N, out_fp32 != 0, swiglu != 0));
 }
 

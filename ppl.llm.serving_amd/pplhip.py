@@ -37,6 +37,11 @@ class ModelDesc(C.Structure):
                 ("weight_quant_group", C.c_int32), ("act_quant_bit", C.c_int32)]
 
 
+# ModelDesc.act_quant_bit values besides 0 (include/pplhip.h)
+ACT_QUANT_I8 = 8        # online_i8i8
+ACT_QUANT_FP8 = 0x108   # online_f8f8
+
+
 class Opts(C.Structure):
     _fields_ = [("n_local_ranks", C.c_int32), ("world_size", C.c_int32), ("rank_base", C.c_int32),
                 ("device_ids", C.POINTER(C.c_int32)), ("nccl_unique_id", C.c_void_p),
@@ -87,7 +92,8 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic", "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
     "pplhip_sample", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
-    "pplhip_op_linear_i8", "pplhip_op_silu_mul", "pplhip_op_rope_kv_write",
+    "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
+    "pplhip_op_silu_mul", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
 ]
 
@@ -146,6 +152,10 @@ def lib():
         L.pplhip_op_quant_act.argtypes = [vp, vp, i64, i32, vp, vp]
         L.pplhip_op_quant_weight.argtypes = [vp, vp, i32, i32, vp, vp]
         L.pplhip_op_linear_i8.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, i32]
+        L.pplhip_op_rmsnorm_quant_f8.argtypes = [vp, vp, vp, vp, C.c_float, i64, i32, vp, vp, vp]
+        L.pplhip_op_quant_act_f8.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.pplhip_op_quant_weight_f8.argtypes = [vp, vp, i32, i32, vp, vp]
+        L.pplhip_op_linear_f8.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, i32]
         L.pplhip_op_silu_mul.argtypes = [vp, vp, i64, i32, vp]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,

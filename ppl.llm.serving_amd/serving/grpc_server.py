@@ -251,7 +251,7 @@ def add_flags(ap):
     ap.add_argument("--tokenizer-path", default="", help="sentencepiece model; without it only the token-in/token-out path is served")
     ap.add_argument("--tokenizer-type", default="sentencepiece")
     ap.add_argument("--model-type", default="llama")
-    ap.add_argument("--quant-method", default="none", help="none | online_i8i8 (tools/llm_server.cc:62)")
+    ap.add_argument("--quant-method", default="none", help="none | online_i8i8 (tools/llm_server.cc:62) | online_f8f8 (fp8 e4m3 W8A8, from fp16 slices)")
     ap.add_argument("--top-p", type=float, default=0.0)
     ap.add_argument("--top-k", type=int, default=1)
     ap.add_argument("--configure-decoding-attn-split-k", type=int, default=1, help="always-on(2)/heuristic(1)/off(0)")

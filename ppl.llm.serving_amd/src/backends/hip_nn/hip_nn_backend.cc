@@ -214,7 +214,13 @@ RetCode Backend::Init(const ModelConfig& mc, const ResourceConfig& rc, const Ext
     d.weight_quant_bit = ex.weight_quant_bit; d.weight_quant_group = ex.weight_quant_group;
     if (rc.engine_config.quant_method == "online_i8i8") {  // the reference's W8A8 mode (src/backends/cuda/resource_manager.cc:51-52)
         if (d.weight_quant_bit == 4) return ppl::common::RC_UNSUPPORTED;
-        d.weight_quant_bit = 8; d.act_quant_bit = 8;
+        d.weight_quant_bit = 8; d.act_quant_bit = PPLHIP_ACT_QUANT_I8;
+    } else if (rc.engine_config.quant_method == "online_f8f8") {  // fp8 e4m3fn W8A8 (DESIGN.md "numerics"): from fp16 slices only
+        if (d.weight_quant_bit != 0) {
+            LOG(ERROR) << "--quant-method online_f8f8 needs fp16 slices (params.json weight_quant_bit 0); these are W" << d.weight_quant_bit << "A16";
+            return ppl::common::RC_UNSUPPORTED;
+        }
+        d.weight_quant_bit = 8; d.act_quant_bit = PPLHIP_ACT_QUANT_FP8;
     } else if (rc.engine_config.quant_method != "none" && !rc.engine_config.quant_method.empty()) {
         return ppl::common::RC_UNSUPPORTED;
     }

@@ -31,7 +31,7 @@ typedef struct pplsrv_config {
                                       NULL or "": token-in/token-out only, a text request fails */
     const char* tokenizer_type;    /* --tokenizer-type, NULL = "sentencepiece" */
     const char* model_type;        /* --model-type, NULL = "llama" (LlamaTokenizer: BOS first) */
-    const char* quant_method;      /* --quant-method: NULL / "none" / "online_i8i8" */
+    const char* quant_method;      /* --quant-method: NULL / "none" / "online_i8i8" / "online_f8f8" */
     float top_p;                   /* --top-p, --top-k: the generator's defaults (GeneratorConfig; 0 / 0 = the tools' 0.0 and 1) */
     int32_t top_k;
     int32_t decoding_attn_split_k; /* --configure-decoding-attn-split-k + 1 (0 = the default, heuristic) */

@@ -32,7 +32,7 @@ inline void DefineCommonFlags(Args* a) {
     a->Def("--max-running-batch", "1024", "");
     a->Def("--max-tokens-per-step", "8192", "");
     a->Def("--max-cooldown-request", "2", "when gpu mem is full, wait for this number of tasks to complete");
-    a->Def("--quant-method", "none", "");
+    a->Def("--quant-method", "none", "none | online_i8i8 (int8 W8A8) | online_f8f8 (fp8 e4m3 W8A8; fp16 slices)");
     a->Def("--cublas-layout-hint", "default", "accepted for CLI compatibility; ignored by the hip backend");
     a->Def("--disable-decoding-shm-mha", "false", "accepted; ignored", true);
     a->Def("--disable-decoding-inf-mha", "false", "accepted; ignored", true);
