@@ -343,6 +343,16 @@ PPLHIP_API int pplhip_op_linear(void* stream, const void* x, const void* w, cons
 PPLHIP_API int pplhip_op_linear_swiglu(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit,
                                        int32_t group, int64_t M, int32_t N, int32_t K, void* y);
 
+/* pplhip_op_linear with the caller's row stride ldy (elements), split-K workspace ws / ws_bytes (device memory, may be NULL) and
+ * epilogue epi (0 fp16, 1 fp32, 2 fused SwiGLU: y[M, N/2]).  route (route_len bytes, may be NULL) receives the path taken as
+ * space-separated key=value tokens, the first naming the kernel template and its arguments, e.g.
+ * "kernel=gemm_dma_kernel<8,f16,4,6> splits=1 kchunk=4096 reduce=none order=super(8x12)"; a launch split along M gives two groups
+ * separated by " ; ".  dry_run != 0 decides the route and the status exactly as a launch would and makes no HIP call at all (no
+ * device needed).  For the tests: not part of the product boundary. */
+PPLHIP_API int pplhip_op_linear_ex(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group,
+                                   int64_t M, int32_t N, int32_t K, void* y, int64_t ldy, int32_t epi, void* ws, uint64_t ws_bytes,
+                                   int32_t dry_run, char* route, int32_t route_len);
+
 /* online_i8i8 (W8A8, src/backends/cuda/resource_manager.cc:51-52).  Per-token activation quantisation: q[M,K] int8,
  * sx[M] = max|x| / 127; per-output-row weight quantisation of an fp16 [N,K] matrix: q[N,K] int8, scale[N] fp16;
  * y[m,n] = (sum_k xq * w as int32) * sx[m] * scale[n], rounded to fp16 (or kept fp32); swiglu as in pplhip_op_linear_swiglu. */

@@ -14,6 +14,8 @@
 //   to all of them; MI355X_MICROARCH: block b -> XCD b % 8).
 // Numerics: fp32 accumulate; W8: y = scale[n] * sum (exact int8 -> fp16); W4: fp16(q * scale) per element
 // (one rounding).  Oracle: ref_linear_fwd (oracle/llama_ref.c).
+#include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -22,6 +24,17 @@
 #include "k_gemm_dev.h"
 
 namespace pplhip {
+
+void LinearRoute::add(const char* fmt, ...) {
+    if (!buf || cap <= 0 || len >= cap - 1) return;
+    if (len > 0) buf[len++] = ' ';
+    va_list ap;
+    va_start(ap, fmt);
+    const int n = vsnprintf(buf + len, (size_t)(cap - len), fmt, ap);
+    va_end(ap);
+    len = n < 0 ? len : (len + n < cap - 1 ? len + n : cap - 1);
+    buf[len] = 0;
+}
 
 template <int WQ, int EPI>
 __global__ __launch_bounds__(256) void gemm_kernel(const uint16_t* __restrict__ x, const void* __restrict__ wv,
@@ -611,12 +624,17 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const uint16_t* __restric
 
 template <int WQ, int EPI>
 static hipError_t launch_gemv(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int group, int64_t M,
-                              int N, int K, void* y, int64_t ldy) {
+                              int N, int K, void* y, int64_t ldy, LinearRoute* route) {
     dim3 grid((unsigned)((N + 15) / 16));
     const int mt = (int)((M + 15) / 16);
     static const int forced_nw = tune_int("PPLHIP_GEMV_WAVES", 0);
     // up to 1024 row tiles -> 8 K slices per tile so that every CU has enough waves streaming (profiles/gemm_microbench.py)
     const int nw = forced_nw ? forced_nw : ((N + 15) / 16 <= 1024 ? 8 : 4);
+    if (mt != 1 && mt != 2) return hipErrorInvalidValue;
+    if (route) {
+        route->add("kernel=gemv_kernel<%d,%d,%s,%d> splits=1 reduce=none order=plain", WQ, mt, epi_name(EPI), nw == 8 ? 8 : 4);
+        if (route->dry) return hipSuccess;
+    }
 #define GEMV_CASE(MT)                                                                                                    \
     if (mt == MT) {                                                                                                      \
         if (nw == 8) hipLaunchKernelGGL((gemv_kernel<WQ, MT, EPI, 8>), grid, dim3(512), 0, s, x, w, scale, M, N, K, group, y, ldy); \
@@ -660,7 +678,8 @@ hipError_t launch_splitk_reduce(hipStream_t s, const float* ws, int splits, int6
 }
 
 hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int wq_bit, int group,
-                         int64_t M, int N, int K, void* y, int64_t ldy, bool out_fp32, float* ws, size_t ws_bytes, bool swiglu, SplitSlabs* defer) {
+                         int64_t M, int N, int K, void* y, int64_t ldy, bool out_fp32, float* ws, size_t ws_bytes, bool swiglu, SplitSlabs* defer,
+                         LinearRoute* route) {
     if (defer) *defer = SplitSlabs{};
     if (M == 0) return hipSuccess;
     if (swiglu && out_fp32) return hipErrorInvalidValue;
@@ -677,10 +696,11 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
     if (msplit && M > 1024 && M < 3584 && (M & 1023) != 0 && (M & 1023) <= msplit) {
         const int64_t m_main = M & ~(int64_t)1023, m_rest = M - m_main;
         const size_t yelt = out_fp32 ? 4 : 2;
-        hipError_t e = launch_linear(s, x, w, scale, wq_bit, group, m_main, N, K, y, ldy, out_fp32, ws, ws_bytes, swiglu);
+        hipError_t e = launch_linear(s, x, w, scale, wq_bit, group, m_main, N, K, y, ldy, out_fp32, ws, ws_bytes, swiglu, nullptr, route);
         if (e != hipSuccess) return e;
+        if (route) route->add(";");
         return launch_linear(s, x + m_main * K, w, scale, wq_bit, group, m_rest, N, K, (char*)y + (size_t)m_main * ldy * yelt, ldy, out_fp32, ws,
-                             ws_bytes, swiglu);
+                             ws_bytes, swiglu, nullptr, route);
     }
     static const bool no_skinny = tune_set("PPLHIP_GEMM_NOSKINNY"), force_generic = tune_set("PPLHIP_GEMM_GENERIC");
     // the skinny kernel up to 3 rows; from 4 rows the half-height tile kernel (64 activation rows, split-K) is faster: 7B decode step at batch
@@ -688,16 +708,16 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
     static const int gemv_max_m = tune_int("PPLHIP_GEMV_MAX_M", 3);
     // up to 4 rows (PPLHIP_GEMV_STREAM_MAX_M): the streaming GEMV of k_gemv.hip -- whole 1-KiB row pieces per wave-load, no matrix unit
     if (M <= gemv_stream_max_m(wq_bit, group, N, K) && !no_skinny && !force_generic)
-        return launch_gemv_stream(s, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi);
+        return launch_gemv_stream(s, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, route);
     // (without a split-K workspace the half-height tiles would run as N / 128 unsplit blocks: the skinny kernel keeps its 16 rows there)
     // (int8 weights with K % 128 == 0: from 3 rows the half-height tiles with 16-row activation sub-tiles are faster than either GEMV)
     const int skinny_max = wq_bit == 8 && K % (G_BK * 2) == 0 && gemv_max_m > 2 && !tune_set("PPLHIP_GEMV_MAX_M") ? 2 : gemv_max_m;
     if (M <= (ws && ws_bytes ? skinny_max : 16) && M <= 16 && !no_skinny) {
 #define GEMV_DISPATCH(WQ)                                                                                      \
     if (wq_bit == WQ)                                                                                          \
-        return epi == EPI_F32 ? launch_gemv<WQ, EPI_F32>(s, x, w, scale, group, M, N, K, y, ldy)               \
-             : epi == EPI_F16 ? launch_gemv<WQ, EPI_F16>(s, x, w, scale, group, M, N, K, y, ldy)               \
-                              : launch_gemv<WQ, EPI_SWIGLU>(s, x, w, scale, group, M, N, K, y, ldy);
+        return epi == EPI_F32 ? launch_gemv<WQ, EPI_F32>(s, x, w, scale, group, M, N, K, y, ldy, route)        \
+             : epi == EPI_F16 ? launch_gemv<WQ, EPI_F16>(s, x, w, scale, group, M, N, K, y, ldy, route)        \
+                              : launch_gemv<WQ, EPI_SWIGLU>(s, x, w, scale, group, M, N, K, y, ldy, route);
         GEMV_DISPATCH(0) GEMV_DISPATCH(8) GEMV_DISPATCH(4)
 #undef GEMV_DISPATCH
     }
@@ -708,14 +728,14 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
     static const int pc_mode = getenv("PPLHIP_GEMM_PC") ? atoi(getenv("PPLHIP_GEMM_PC")) : 1;
     if (pc_mode && wq_bit == 4 && M > 128 && M <= 512 && !force_generic && (int64_t)((N + 63) / 64) * ((M + 127) / 128) >= 160 &&
         linear_w4_pc_supported(group, M, N, K, x, w, scale, y, ldy, epi))
-        return launch_linear_w4_pc(s, x, w, scale, M, N, K, y, ldy, epi);
+        return launch_linear_w4_pc(s, x, w, scale, M, N, K, y, ldy, epi, route);
     // W8A16 at 512 <= M < 4096 with N >= 8192 (wqkv / w13 of a decode step at batch ~1024): one 128 x 384 block per CU whose twelve
     // consumer waves share the activation tile (k_gemm_wide.hip) when its tiles fill the chip's rounds; PPLHIP_GEMM_WIDE=0: never
     static const int wide = tune_int("PPLHIP_GEMM_WIDE", 1);
     if (wide && wq_bit == 8 && K % G_BK == 0 && M >= 512 && (M < 4096 || wide == 2) && N >= 8192) {
         const int nc = wide == 2 ? 12 : linear_w8_wide_waves(M, N);  // (2: experiments -- every eligible shape, any M)
         // (round 4's hand-scheduled K loop for this block tile -- equal speed, both on the chip's power limit -- lives under profiles/probes/gemm_asm/ since round 6)
-        if (nc) return launch_linear_w8_wide(s, x, (const int8_t*)w, scale, M, N, K, y, ldy, epi, nc);
+        if (nc) return launch_linear_w8_wide(s, x, (const int8_t*)w, scale, M, N, K, y, ldy, epi, nc, route);
     }
     // (Round 6, measured and not adopted: 128 x 96 / 64 x 96 tiles whose four multiplying waves split each K tile by k-step on 32 x 32 x 16
     // MFMAs -- 232 / 256 blocks instead of 176 / 96 for the 7B / TP8 slice's w13 / wqkv, 22 KiB of fragment reads per K tile instead of 72.
@@ -749,6 +769,13 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
         if (gn > nl) gn = nl;
         const int nl_pad = (nl + gn - 1) / gn * gn;
         dim3 g256((unsigned)(8 * nl_pad * mt2));
+        static const int no_stage = tune_set("PPLHIP_GEMM_DIRECT_EPILOGUE") ? 1 : 0;  // A/B runs
+        const int staged = !no_stage && ldy % 8 == 0 && ((uintptr_t)y & 15) == 0 && (epi != EPI_SWIGLU || N % 16 == 0) ? 1 : 0;
+        if (route) {
+            route->add("kernel=gemm_w8_dma256_kernel<%s> splits=1 reduce=none order=super(%dx%d) epilogue=%s", epi_name(epi), gm, gn,
+                       staged ? "staged" : "direct");
+            if (route->dry) return hipSuccess;
+        }
         // (the attribute belongs to the function ON THE CURRENT DEVICE: one flag per device, or the other ranks of a single-process
         // tensor-parallel run would launch without it)
         static bool attr_dev[64] = {false};
@@ -761,8 +788,6 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
             (void)hipFuncSetAttribute((const void*)gemm_w8_dma256_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             attr_set = true;
         }
-        static const int no_stage = tune_set("PPLHIP_GEMM_DIRECT_EPILOGUE") ? 1 : 0;  // A/B runs
-        const int staged = !no_stage && ldy % 8 == 0 && ((uintptr_t)y & 15) == 0 && (epi != EPI_SWIGLU || N % 16 == 0) ? 1 : 0;
 #define L256(E) hipLaunchKernelGGL((gemm_w8_dma256_kernel<E>), g256, dim3(512), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm, staged)
         if (epi == EPI_F32) L256(EPI_F32); else if (epi == EPI_F16) L256(EPI_F16); else L256(EPI_SWIGLU);
 #undef L256
@@ -878,6 +903,14 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
             const int bm = M > 64 ? (int)((M + 15) / 16 * 16) : (half128 == 2 ? 64 : (M <= 16 ? 16 : (M <= 32 ? 32 : 64)));
             const int st = (bm <= 32 || bm > 64 || (int64_t)n_tiles * sp <= 256) ? 3 : 2;
             const size_t lds = (size_t)st * ((size_t)S_KS * bm * G_BK * 2 + S_WB);
+            if (route) {
+                route->add("kernel=gemm_w8_half128_kernel<%s,%d,%d> splits=%d kchunk=%d", epi_name(epi), st, bm, sp, kt_per128 * G_BK * S_KS);
+                if (sp == 1) route->add("reduce=none");
+                else if (defer && epi == EPI_F16 && N % 8 == 0 && sp <= 8) route->add("reduce=deferred");
+                else route->add("reduce=splitk_reduce_kernel<%s>", epi_name(epi));
+                route->add("order=plain");
+                if (route->dry) return hipSuccess;
+            }
             static bool attr_dev[64] = {false};
             int dev = 0;
             (void)hipGetDevice(&dev);
@@ -904,6 +937,22 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
         // W4 with K slabs of at most 32 tiles (16 quantisation groups): the scale area shrinks from 16 to 4 KiB and three blocks fit a CU
         static const int w4_sc16 = tune_int("PPLHIP_GEMM_W4_SC16", 1);
         const bool w4_small_sc = w4_sc16 && wq_bit == 4 && splits > 1 && kt_per <= 32 && wl == 1 && !half && stages == 2;
+        if (route) {
+            // (the choice of DMA_LAUNCH below)
+            if (wl == 6 && wq_bit == 8 && stages >= 3) route->add("kernel=gemm_dma_kernel<8,%s,%d,6>", epi_name(epi), stages);
+            else if (wl == 5) route->add("kernel=gemm_dma_kernel<%d,%s,%d,5>", wq_bit, epi_name(epi), stages);
+            else if (half) route->add("kernel=gemm_dma_kernel<%d,%s,%d,1,64>", wq_bit, epi_name(epi), stages);
+            else if (wq_bit == 4 && stages == 2 && w4_small_sc) route->add("kernel=gemm_dma_kernel<4,%s,2,1,128,16>", epi_name(epi));
+            else route->add("kernel=gemm_dma_kernel<%d,%s,%d,1>", wq_bit, epi_name(epi), stages);
+            route->add("splits=%d kchunk=%d", splits, kt_per * G_BK);
+            if (splits == 1) route->add("reduce=none");
+            else if (defer && epi == EPI_F16 && N % 8 == 0 && splits <= 8) route->add("reduce=deferred");
+            else route->add("reduce=splitk_reduce_kernel<%s>", epi_name(epi));
+            if ((map_mode & 0xff) == 1) route->add("order=xcd_m");
+            else if ((map_mode >> 16) & 0xff) route->add("order=super(%dx%d)", (map_mode >> 16) & 0xff, (map_mode >> 24) & 0xff);
+            else route->add("order=plain");
+            if (route->dry) return hipSuccess;
+        }
 #define DMA_LAUNCH(WQ, O32, ST)                                                                                     \
     do { if constexpr (WQ == 8 && ST >= 3) { if (wl == 6) { hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 6>), g2, dim3(768), 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); break; } } \
          if (wl == 5) hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 5>), g2, dim3(512), 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); \
@@ -924,6 +973,10 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
     }
 #define GEMM_CASE(WQ, O32)                                                                                          \
     if (wq_bit == WQ && epi == (int)O32) {                                                                          \
+        if (route) {                                                                                                \
+            route->add("kernel=gemm_kernel<%d,%s> splits=1 reduce=none order=plain", WQ, epi_name(epi));            \
+            if (route->dry) return hipSuccess;                                                                      \
+        }                                                                                                           \
         hipLaunchKernelGGL((gemm_kernel<WQ, O32>), grid, block, 0, s, x, w, scale, M, N, K, group, y, ldy, n_tiles, \
                            m_tiles);                                                                                \
         return hipGetLastError();                                                                                   \

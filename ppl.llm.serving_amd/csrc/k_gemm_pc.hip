@@ -381,8 +381,12 @@ bool linear_w4_pc_supported(int group, int64_t M, int N, int K, const void* x, c
 }
 
 hipError_t launch_linear_w4_pc(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int64_t M, int N, int K, void* y,
-                               int64_t ldy, int epi) {
+                               int64_t ldy, int epi, LinearRoute* route) {
     const int n_tiles = (N + PC_BN - 1) / PC_BN, m_tiles = (int)((M + PC_BM - 1) / PC_BM);
+    if (route) {
+        route->add("kernel=gemm_w4_pc_kernel<%s> splits=1 reduce=none order=plain", epi_name(epi));
+        if (route->dry) return hipSuccess;
+    }
     static bool attr_dev[64] = {false};
     int dev = 0;
     (void)hipGetDevice(&dev);

@@ -171,12 +171,16 @@ int linear_w8_wide_waves(int64_t M, int N) {
 
 // W8A16, K % 64 == 0, N % 4 == 0.  epi: EPI_F16 / EPI_F32 / EPI_SWIGLU; nc from linear_w8_wide_waves
 hipError_t launch_linear_w8_wide(hipStream_t s, const uint16_t* x, const int8_t* w, const uint16_t* scale, int64_t M, int N, int K, void* y,
-                                 int64_t ldy, int epi, int nc) {
+                                 int64_t ldy, int epi, int nc, LinearRoute* route) {
     if (nc != 12) return hipErrorInvalidValue;
     const int bn = 32 * nc;
     const int n_tiles = (N + bn - 1) / bn, m_tiles = (int)((M + WD_BM - 1) / WD_BM);
     constexpr int ST = 3;
     const size_t lds = (size_t)ST * (WD_XB + bn * G_BK);
+    if (route) {
+        route->add("kernel=gemm_w8_wide_kernel<%s,%d,%d> splits=1 reduce=none order=plain", epi_name(epi), ST, nc);
+        if (route->dry) return hipSuccess;
+    }
     static bool attr_dev[64] = {false};
     int dev = 0;
     (void)hipGetDevice(&dev);

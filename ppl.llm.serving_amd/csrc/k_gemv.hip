@@ -191,7 +191,7 @@ int gemv_stream_max_m(int wq_bit, int group, int N, int K) {
 }
 
 hipError_t launch_gemv_stream(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int wq_bit, int group, int64_t M, int N,
-                              int K, void* y, int64_t ldy, int epi) {
+                              int K, void* y, int64_t ldy, int epi, LinearRoute* route) {
     const int kl = wq_bit == 8 ? 16 : (wq_bit == 4 ? 32 : 8);
     const int pieces = (K / kl + 63) / 64;
     int nwk_log2 = 0;
@@ -208,6 +208,12 @@ hipError_t launch_gemv_stream(hipStream_t s, const uint16_t* x, const void* w, c
 #define GV_E(WQ, MM) do { if (epi == EPI_F32) GV_P(WQ, MM, EPI_F32); else if (epi == EPI_F16) GV_P(WQ, MM, EPI_F16); else GV_P(WQ, MM, EPI_SWIGLU); } while (0)
 #define GV_M(WQ) do { if (M == 1) GV_E(WQ, 1); else if (M == 2) GV_E(WQ, 2); else if (M == 3) GV_E(WQ, 3); else GV_E(WQ, 4); } while (0)
     if (M < 1 || M > 4 || npw > 3) return hipErrorInvalidValue;
+    if (wq_bit != 8 && wq_bit != 4 && wq_bit != 0) return hipErrorInvalidValue;
+    if (route) {
+        route->add("kernel=gemv_stream_kernel<%d,%d,%s,%d>", wq_bit, (int)M, epi_name(epi), nw);
+        route->add("splits=1 reduce=none order=plain nwk=%d nb=%d", nwk, nb);
+        if (route->dry) return hipSuccess;
+    }
     if (wq_bit == 8) GV_M(8); else if (wq_bit == 4) GV_M(4); else if (wq_bit == 0) GV_M(0); else return hipErrorInvalidValue;
 #undef GV_M
 #undef GV_E

@@ -2096,6 +2096,20 @@ int pplhip_op_linear_swiglu(void* stream, const void* x, const void* w, const vo
                                false, ws, ws_bytes, true));
 }
 
+// launch_linear with the caller's row stride, workspace and pointers, and the route it takes (kernels.h LinearRoute); dry_run: the route and
+// status only, no HIP call at all (works without a device)
+int pplhip_op_linear_ex(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M, int32_t N,
+                        int32_t K, void* y, int64_t ldy, int32_t epi, void* ws, uint64_t ws_bytes, int32_t dry_run, char* route, int32_t route_len) {
+    LinearRoute r;
+    r.buf = route_len > 0 ? route : nullptr;
+    r.cap = route_len;
+    r.dry = dry_run != 0;
+    if (r.buf) r.buf[0] = 0;
+    if (epi < 0 || epi > 2) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_linear((hipStream_t)stream, (const uint16_t*)x, w, (const uint16_t*)scale, wq_bit, group, M, N, K, y, ldy, epi == 1,
+                               (float*)ws, (size_t)ws_bytes, epi == 2, nullptr, &r));
+}
+
 int pplhip_op_rmsnorm_quant(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t T, int32_t hidden,
                             void* residual_out, void* q, float* sx) {
     return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, T, hidden, nullptr,

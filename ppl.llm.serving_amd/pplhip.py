@@ -91,7 +91,7 @@ SYMBOLS = [
     "pplhip_kv_block_bytes", "pplhip_kv_capacity", "pplhip_kv_alloc", "pplhip_kv_ptrs", "pplhip_kv_read",
     "pplhip_kv_write", "pplhip_kv_fill_synthetic", "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
     "pplhip_sample", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
-    "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
+    "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
     "pplhip_op_silu_mul", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
@@ -148,6 +148,7 @@ def lib():
         L.pplhip_op_rmsnorm.argtypes = [vp, vp, vp, vp, f32, i64, i32, vp, vp]
         L.pplhip_op_linear.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, i32]
         L.pplhip_op_linear_swiglu.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp]
+        L.pplhip_op_linear_ex.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, i64, i32, vp, u64, i32, C.c_char_p, i32]
         L.pplhip_op_rmsnorm_quant.argtypes = [vp, vp, vp, vp, C.c_float, i64, i32, vp, vp, vp]
         L.pplhip_op_quant_act.argtypes = [vp, vp, i64, i32, vp, vp]
         L.pplhip_op_quant_weight.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -163,6 +164,13 @@ def lib():
         L.pplhip_build_rope_table.argtypes = [vp, i32, i32, f32]
         _LIB = L
     return _LIB
+
+
+def linear_route(x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws=None, ws_bytes=0, dry_run=True, stream=None):
+    """pplhip_op_linear_ex: (status, route text).  Pointers are integers (device addresses; a dry run never dereferences them)."""
+    buf = C.create_string_buffer(1024)
+    rc = lib().pplhip_op_linear_ex(stream, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws, ws_bytes, int(dry_run), buf, 1024)
+    return rc, buf.value.decode()
 
 
 def make_desc(**kw):
