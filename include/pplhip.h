@@ -380,6 +380,23 @@ PPLHIP_API int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx
 
 PPLHIP_API int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out);
 
+/* the penalty kernel alone (launch_penalty), for the tests: every pointer is a device pointer; temperatures, rep, presence and
+ * frequency may be NULL.  count_map is the caller's: uint16 [slots, vocab], row batch_slots[b] belongs to batch row b.  Rows of
+ * `logits` are `stride` floats apart (stride >= vocab; columns [vocab, stride) are never touched).  Row b's counts are cleared when
+ * start_pos[b] == 0 or b >= decoding_batches; token ids must lie in [0, vocab) (pplhip_set_inputs validates them on the product path,
+ * nothing does here).  batch == 0 does nothing; an odd vocab is PPLHIP_INVALID_VALUE. */
+PPLHIP_API int pplhip_op_penalty(void* stream, float* logits, const float* temperatures, const float* rep, const float* presence,
+                                 const float* frequency, const int64_t* batch_slots, const int64_t* token_inputs,
+                                 const int64_t* seq_starts, const int64_t* start_pos, int32_t batch, int32_t vocab, int32_t stride,
+                                 int32_t decoding_batches, uint16_t* count_map);
+
+/* the sampling kernels alone, for the tests: top_k == 1 launches the greedy kernel (top_p, rnd, default_top_p unused), any other top_k
+ * the top-k / top-p kernel with the caller's random numbers rnd[batch] in [0, 1) (pplhip_sample draws them from rand()).  Device
+ * pointers; temperatures and top_p may be NULL; out_tok / out_logprob are device buffers of `batch` elements. */
+PPLHIP_API int pplhip_op_sample(void* stream, const float* logits, const float* temperatures, const float* top_p, const float* rnd,
+                                int32_t batch, int32_t vocab, int32_t stride, int32_t top_k, float default_top_p, int32_t* out_tok,
+                                float* out_logprob);
+
 /* description of a KV slab for the attention / cache-write operators */
 typedef struct pplhip_kv_view {
     void* cache;          /* fp16 or int8 */

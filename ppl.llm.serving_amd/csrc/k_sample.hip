@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void sample_topk_topp_kernel(const float* __re
         idx_cut = (int)ip;
     }
     // gather the k candidates, pad to a power of two, sort by (value descending, index ascending)
-    if (tid == 0) sel[3] = 0;
+    if (tid == 0) { sel[2] = 0; sel[3] = 0; }
     __syncthreads();
     for (int i = tid; i < vocab; i += 256) {
         const float x = row[i] * invt;
@@ -258,11 +258,17 @@ __global__ __launch_bounds__(256) void sample_topk_topp_kernel(const float* __re
         xv[j] = i < k ? cv[i] : -INFINITY;  // keep the candidate's x for the logprob
     }
     __syncthreads();
+    int with_mass = 0;
 #pragma unroll
     for (int j = 0; j < TOPK_MAX / 256; ++j) {
         const int i = tid + j * 256;
-        if (i < n2) cum[i] = i < k ? expf(xv[j] - mx) : 0.f;
+        if (i < n2) {
+            const float e = i < k ? expf(xv[j] - mx) : 0.f;
+            cum[i] = e;
+            with_mass += e > 0.f;
+        }
     }
+    if (with_mass) atomicAdd(&sel[2], with_mass);
     __syncthreads();
     for (int o = 1; o < n2; o <<= 1) {
         float add[TOPK_MAX / 256];
@@ -279,14 +285,18 @@ __global__ __launch_bounds__(256) void sample_topk_topp_kernel(const float* __re
         }
         __syncthreads();
     }
-    // keep = 1 + first i with cum[i] / tot >= tp (all k when none); tot = whole-row mass in pure top-p mode
-    const float tot = full ? se : cum[k - 1];
-    if (tid == 0) { sel[0] = k - 1; sel[1] = 0x7fffffff; }
+    // Candidates without mass (masked logits: -inf) sort last and are never the answer: the decisions below run over the km candidates that
+    // carry mass.  (Every entry of the scan is summed in a tree of its own, so the sums are not monotone to the last bit: a massless entry
+    // could exceed a target of rand ~ 1 that the last entry with mass just missed.)
+    const int km = sel[2] > 0 ? sel[2] : 1;
+    // keep = 1 + first i with cum[i] / tot >= tp (all km when none); tot = whole-row mass in pure top-p mode
+    const float tot = full ? se : cum[km - 1];
+    if (tid == 0) { sel[0] = km - 1; sel[1] = 0x7fffffff; }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < TOPK_MAX / 256; ++j) {
         const int i = tid + j * 256;
-        if (i < k && cum[i] / tot >= tp) atomicMin(&sel[0], i);
+        if (i < km && cum[i] / tot >= tp) atomicMin(&sel[0], i);
     }
     __syncthreads();
     const int keep = sel[0] + 1;

@@ -2155,6 +2155,25 @@ int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t int
     return op_rc(launch_silu_mul((hipStream_t)stream, (const uint16_t*)gate_up, T, inter, (uint16_t*)out));
 }
 
+// K12 / K13 alone, on the caller's buffers (the tests preload and read back the count map and pick vocab, stride and alignment)
+int pplhip_op_penalty(void* stream, float* logits, const float* temperatures, const float* rep, const float* presence,
+                      const float* frequency, const int64_t* batch_slots, const int64_t* token_inputs, const int64_t* seq_starts,
+                      const int64_t* start_pos, int32_t batch, int32_t vocab, int32_t stride, int32_t decoding_batches, uint16_t* count_map) {
+    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_penalty((hipStream_t)stream, logits, temperatures, rep, presence, frequency, batch_slots, token_inputs, seq_starts,
+                                start_pos, batch, vocab, stride, decoding_batches, count_map));
+}
+
+int pplhip_op_sample(void* stream, const float* logits, const float* temperatures, const float* top_p, const float* rnd, int32_t batch,
+                     int32_t vocab, int32_t stride, int32_t top_k, float default_top_p, int32_t* out_tok, float* out_logprob) {
+    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
+    if (top_k == 1)
+        return op_rc(launch_sample_greedy((hipStream_t)stream, logits, temperatures, batch, vocab, stride, out_tok, out_logprob));
+    if (!rnd && batch > 0) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_sample_topk_topp((hipStream_t)stream, logits, temperatures, top_p, rnd, batch, vocab, stride, top_k, default_top_p,
+                                         nullptr, out_tok, out_logprob));
+}
+
 static KvAddr view_addr(const pplhip_kv_view* v) {
     pplhip_model_desc d;
     memset(&d, 0, sizeof(d));

@@ -93,7 +93,7 @@ SYMBOLS = [
     "pplhip_sample", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
 ]
 
@@ -158,6 +158,8 @@ def lib():
         L.pplhip_op_quant_weight_f8.argtypes = [vp, vp, i32, i32, vp, vp]
         L.pplhip_op_linear_f8.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, i32]
         L.pplhip_op_silu_mul.argtypes = [vp, vp, i64, i32, vp]
+        L.pplhip_op_penalty.argtypes = [vp] * 10 + [i32, i32, i32, i32, vp]
+        L.pplhip_op_sample.argtypes = [vp] * 5 + [i32, i32, i32, i32, f32, vp, vp]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
