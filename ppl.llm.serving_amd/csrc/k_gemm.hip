@@ -199,6 +199,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const uint16_t* __restrict__ 
 }
 
 // stand-alone launch of the tile body (k_gemm_dev.h)
+struct DmaKernel { int wq, epi, stages, wl, bm, maxg; };  // template arguments of a launch (launch_linear)
 template <int WQ, int EPI, int G_ST, int WL, int BM = G_BM, int MAXG = W4_MAXG>
 __global__ __launch_bounds__(WL == 6 ? 768 : (WL == 5 ? 512 : 256)) void gemm_dma_kernel(const uint16_t* __restrict__ x, const void* __restrict__ wv,
                                                              const uint16_t* __restrict__ scale, int64_t M, int N, int K,
@@ -223,6 +224,7 @@ __global__ __launch_bounds__(WL == 6 ? 768 : (WL == 5 ? 512 : 256)) void gemm_dm
 constexpr int S_KS = 2;                                             // 64-deep sub-tiles per stage
 constexpr int S_WB = G_BN * G_BK * S_KS;                            // weight bytes per stage: 16 KiB
 template <int BM> constexpr int s_xb() { return S_KS * BM * G_BK * 2; }  // activation bytes per stage: 4 / 8 / 16 KiB
+struct Half128Kernel { int epi, st, bm; };                          // template arguments of a launch (launch_linear)
 
 template <int EPI, int ST, int BM>
 __global__ __launch_bounds__(256) void gemm_w8_half128_kernel(const uint16_t* __restrict__ x, const int8_t* __restrict__ w,
@@ -635,15 +637,12 @@ static hipError_t launch_gemv(hipStream_t s, const uint16_t* x, const void* w, c
         route->add("kernel=gemv_kernel<%d,%d,%s,%d> splits=1 reduce=none order=plain", WQ, mt, epi_name(EPI), nw == 8 ? 8 : 4);
         if (route->dry) return hipSuccess;
     }
-#define GEMV_CASE(MT)                                                                                                    \
-    if (mt == MT) {                                                                                                      \
-        if (nw == 8) hipLaunchKernelGGL((gemv_kernel<WQ, MT, EPI, 8>), grid, dim3(512), 0, s, x, w, scale, M, N, K, group, y, ldy); \
-        else hipLaunchKernelGGL((gemv_kernel<WQ, MT, EPI, 4>), grid, dim3(256), 0, s, x, w, scale, M, N, K, group, y, ldy);       \
-        return hipGetLastError();                                                                                        \
-    }
-    GEMV_CASE(1) GEMV_CASE(2)
-#undef GEMV_CASE
-    return hipErrorInvalidValue;
+    dispatch_int<1, 2>(mt, [&](auto MT) {
+        dispatch_int<8, 4>(nw, [&](auto NW) {
+            hipLaunchKernelGGL((gemv_kernel<WQ, MT, EPI, NW>), grid, dim3(NW * 64), 0, s, x, w, scale, M, N, K, group, y, ldy);
+        });
+    });
+    return hipGetLastError();
 }
 
 // split-K reduce: y[m][n] = (sum_z slab[z][m][n]) * scale[n]  (scale == NULL: 1)
@@ -671,9 +670,7 @@ hipError_t launch_splitk_reduce(hipStream_t s, const float* ws, int splits, int6
     const int64_t total = M * (N / 4);
     if (total == 0) return hipSuccess;
     const unsigned rb = (unsigned)std::min<int64_t>((total + 255) / 256, 2048);
-#define RED(E) hipLaunchKernelGGL(splitk_reduce_kernel<E>, dim3(rb), dim3(256), 0, s, ws, splits, M, N, scale, y, ldy)
-    if (epi == EPI_F32) RED(EPI_F32); else if (epi == EPI_F16) RED(EPI_F16); else RED(EPI_SWIGLU);
-#undef RED
+    dispatch_epi(epi, [&](auto E) { hipLaunchKernelGGL(splitk_reduce_kernel<E>, dim3(rb), dim3(256), 0, s, ws, splits, M, N, scale, y, ldy); });
     return hipGetLastError();
 }
 
@@ -713,13 +710,13 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
     // (int8 weights with K % 128 == 0: from 3 rows the half-height tiles with 16-row activation sub-tiles are faster than either GEMV)
     const int skinny_max = wq_bit == 8 && K % (G_BK * 2) == 0 && gemv_max_m > 2 && !tune_set("PPLHIP_GEMV_MAX_M") ? 2 : gemv_max_m;
     if (M <= (ws && ws_bytes ? skinny_max : 16) && M <= 16 && !no_skinny) {
-#define GEMV_DISPATCH(WQ)                                                                                      \
-    if (wq_bit == WQ)                                                                                          \
-        return epi == EPI_F32 ? launch_gemv<WQ, EPI_F32>(s, x, w, scale, group, M, N, K, y, ldy, route)        \
-             : epi == EPI_F16 ? launch_gemv<WQ, EPI_F16>(s, x, w, scale, group, M, N, K, y, ldy, route)        \
-                              : launch_gemv<WQ, EPI_SWIGLU>(s, x, w, scale, group, M, N, K, y, ldy, route);
-        GEMV_DISPATCH(0) GEMV_DISPATCH(8) GEMV_DISPATCH(4)
-#undef GEMV_DISPATCH
+        if (wq_bit == 0 || wq_bit == 8 || wq_bit == 4) {
+            hipError_t e = hipSuccess;
+            dispatch_int<0, 8, 4>(wq_bit, [&](auto WQ) {
+                dispatch_epi(epi, [&](auto E) { e = launch_gemv<WQ, E>(s, x, w, scale, group, M, N, K, y, ldy, route); });
+            });
+            return e;
+        }
     }
     // W4A16 at a few hundred rows (config 4: the 70B / TP8 slice at batch 256): 128 x 64 tiles, DMA waves beside MFMA waves whose fragment
     // registers roll (k_gemm_pc.hip, round 5) -- for the shapes whose 128 x 64 tiles fill most CUs WITHOUT K slabs (wo / w13 / w2 of that
@@ -776,21 +773,11 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
                        staged ? "staged" : "direct");
             if (route->dry) return hipSuccess;
         }
-        // (the attribute belongs to the function ON THE CURRENT DEVICE: one flag per device, or the other ranks of a single-process
-        // tensor-parallel run would launch without it)
-        static bool attr_dev[64] = {false};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        bool& attr_set = attr_dev[dev & 63];
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)gemm_w8_dma256_kernel<EPI_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)gemm_w8_dma256_kernel<EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)gemm_w8_dma256_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
-        }
-#define L256(E) hipLaunchKernelGGL((gemm_w8_dma256_kernel<E>), g256, dim3(512), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm, staged)
-        if (epi == EPI_F32) L256(EPI_F32); else if (epi == EPI_F16) L256(EPI_F16); else L256(EPI_SWIGLU);
-#undef L256
+        static LdsOptIn once;
+        if (once.first()) set_max_lds(lds, gemm_w8_dma256_kernel<EPI_F16>, gemm_w8_dma256_kernel<EPI_F32>, gemm_w8_dma256_kernel<EPI_SWIGLU>);
+        dispatch_epi(epi, [&](auto E) {
+            hipLaunchKernelGGL((gemm_w8_dma256_kernel<E>), g256, dim3(512), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm, staged);
+        });
         return hipGetLastError();
     }
     // W4: group 128 = two K tiles; one block keeps at most W4_MAXG groups of scales in LDS
@@ -902,33 +889,33 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
             // (above 64 rows in steps of 16: a 72-row step on a 128-row sub-tile would pay 128 rows of LDS traffic and MFMAs)
             const int bm = M > 64 ? (int)((M + 15) / 16 * 16) : (half128 == 2 ? 64 : (M <= 16 ? 16 : (M <= 32 ? 32 : 64)));
             const int st = (bm <= 32 || bm > 64 || (int64_t)n_tiles * sp <= 256) ? 3 : 2;
-            const size_t lds = (size_t)st * ((size_t)S_KS * bm * G_BK * 2 + S_WB);
+            const Half128Kernel hk{epi, st, bm};  // the template arguments: named in the route record and launched from the same struct
+            const size_t lds = (size_t)hk.st * ((size_t)S_KS * hk.bm * G_BK * 2 + S_WB);
             if (route) {
-                route->add("kernel=gemm_w8_half128_kernel<%s,%d,%d> splits=%d kchunk=%d", epi_name(epi), st, bm, sp, kt_per128 * G_BK * S_KS);
+                route->add("kernel=gemm_w8_half128_kernel<%s,%d,%d> splits=%d kchunk=%d", epi_name(hk.epi), hk.st, hk.bm, sp, kt_per128 * G_BK * S_KS);
                 if (sp == 1) route->add("reduce=none");
                 else if (defer && epi == EPI_F16 && N % 8 == 0 && sp <= 8) route->add("reduce=deferred");
                 else route->add("reduce=splitk_reduce_kernel<%s>", epi_name(epi));
                 route->add("order=plain");
                 if (route->dry) return hipSuccess;
             }
-            static bool attr_dev[64] = {false};
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            if (!attr_dev[dev & 63]) {
-#define H128_A(E, S, B) (void)hipFuncSetAttribute((const void*)gemm_w8_half128_kernel<E, S, B>, hipFuncAttributeMaxDynamicSharedMemorySize, S * (s_xb<B>() + S_WB))
-#define H128_AE(E) H128_A(E, 3, 16); H128_A(E, 3, 32); H128_A(E, 2, 64); H128_A(E, 3, 64); H128_A(E, 3, 80); H128_A(E, 3, 96); H128_A(E, 3, 112); H128_A(E, 3, 128)
-                H128_AE(EPI_F16); H128_AE(EPI_F32); H128_AE(EPI_SWIGLU);
-#undef H128_AE
-#undef H128_A
-                attr_dev[dev & 63] = true;
-            }
+            static LdsOptIn once;
+            if (once.first())
+                for_each_epi([](auto E) {
+                    auto opt_in = [&](auto ST, auto BM) { set_max_lds(ST * (s_xb<BM>() + S_WB), gemm_w8_half128_kernel<E, ST, BM>); };
+                    opt_in(int_c<3>{}, int_c<16>{}); opt_in(int_c<3>{}, int_c<32>{}); opt_in(int_c<2>{}, int_c<64>{}); opt_in(int_c<3>{}, int_c<64>{});
+                    opt_in(int_c<3>{}, int_c<80>{}); opt_in(int_c<3>{}, int_c<96>{}); opt_in(int_c<3>{}, int_c<112>{}); opt_in(int_c<3>{}, int_c<128>{});
+                });
             dim3 gh((unsigned)n_tiles, (unsigned)sp);
-#define H128_L(E, S, B) hipLaunchKernelGGL((gemm_w8_half128_kernel<E, S, B>), gh, dim3(256), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, n_tiles, kt_per128, ws)
-#define H128_E(E) do { if (bm == 16) H128_L(E, 3, 16); else if (bm == 32) H128_L(E, 3, 32); else if (bm == 80) H128_L(E, 3, 80); else if (bm == 96) H128_L(E, 3, 96); \
-                         else if (bm == 112) H128_L(E, 3, 112); else if (bm == 128) H128_L(E, 3, 128); else if (st == 3) H128_L(E, 3, 64); else H128_L(E, 2, 64); } while (0)
-            if (epi == EPI_F32) H128_E(EPI_F32); else if (epi == EPI_F16) H128_E(EPI_F16); else H128_E(EPI_SWIGLU);
-#undef H128_E
-#undef H128_L
+            dispatch_epi(hk.epi, [&](auto E) {
+                dispatch_int<16, 32, 80, 96, 112, 128, 64>(hk.bm, [&](auto BM) {
+                    auto go = [&](auto ST) {
+                        hipLaunchKernelGGL((gemm_w8_half128_kernel<E, ST, BM>), gh, dim3(256), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, n_tiles, kt_per128, ws);
+                    };
+                    if constexpr (BM == 64) { if (hk.st == 3) go(int_c<3>{}); else go(int_c<2>{}); }   // two stages: 64-row sub-tiles only
+                    else go(int_c<3>{});
+                });
+            });
             hipError_t e = hipGetLastError();
             if (e != hipSuccess || sp == 1) return e;
             if (defer && epi == EPI_F16 && N % 8 == 0 && sp <= 8) { *defer = SplitSlabs{ws, sp, scale, N, M}; return e; }  // the consumer reduces
@@ -937,13 +924,17 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
         // W4 with K slabs of at most 32 tiles (16 quantisation groups): the scale area shrinks from 16 to 4 KiB and three blocks fit a CU
         static const int w4_sc16 = tune_int("PPLHIP_GEMM_W4_SC16", 1);
         const bool w4_small_sc = w4_sc16 && wq_bit == 4 && splits > 1 && kt_per <= 32 && wl == 1 && !half && stages == 2;
+        // the ring kernel's template arguments, chosen once: the route record names them and the launch below instantiates from them
+        DmaKernel dk{wq_bit, epi, stages, 1, G_BM, W4_MAXG};
+        if (wl == 6 && wq_bit == 8 && stages >= 3) dk.wl = 6;
+        else if (wl == 5) dk.wl = 5;
+        else if (half) dk.bm = 64;
+        else if (wq_bit == 4 && stages == 2 && w4_small_sc) dk.maxg = 16;
         if (route) {
-            // (the choice of DMA_LAUNCH below)
-            if (wl == 6 && wq_bit == 8 && stages >= 3) route->add("kernel=gemm_dma_kernel<8,%s,%d,6>", epi_name(epi), stages);
-            else if (wl == 5) route->add("kernel=gemm_dma_kernel<%d,%s,%d,5>", wq_bit, epi_name(epi), stages);
-            else if (half) route->add("kernel=gemm_dma_kernel<%d,%s,%d,1,64>", wq_bit, epi_name(epi), stages);
-            else if (wq_bit == 4 && stages == 2 && w4_small_sc) route->add("kernel=gemm_dma_kernel<4,%s,2,1,128,16>", epi_name(epi));
-            else route->add("kernel=gemm_dma_kernel<%d,%s,%d,1>", wq_bit, epi_name(epi), stages);
+            char tail[16] = "";  // the defaulted arguments BM and MAXG appear only where they differ
+            if (dk.maxg != W4_MAXG) snprintf(tail, sizeof tail, ",%d,%d", dk.bm, dk.maxg);
+            else if (dk.bm != G_BM) snprintf(tail, sizeof tail, ",%d", dk.bm);
+            route->add("kernel=gemm_dma_kernel<%d,%s,%d,%d%s>", dk.wq, epi_name(dk.epi), dk.stages, dk.wl, tail);
             route->add("splits=%d kchunk=%d", splits, kt_per * G_BK);
             if (splits == 1) route->add("reduce=none");
             else if (defer && epi == EPI_F16 && N % 8 == 0 && splits <= 8) route->add("reduce=deferred");
@@ -953,38 +944,38 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
             else route->add("order=plain");
             if (route->dry) return hipSuccess;
         }
-#define DMA_LAUNCH(WQ, O32, ST)                                                                                     \
-    do { if constexpr (WQ == 8 && ST >= 3) { if (wl == 6) { hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 6>), g2, dim3(768), 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); break; } } \
-         if (wl == 5) hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 5>), g2, dim3(512), 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); \
-         else if (half) hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 1, 64>), g2, block, 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); \
-         else if (WQ == 4 && ST == 2 && w4_small_sc) hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 1, G_BM, 16>), g2, block, 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); \
-         else hipLaunchKernelGGL((gemm_dma_kernel<WQ, O32, ST, 1>), g2, block, 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws); } while (0)
-#define DMA_STAGES(WQ, O32)                                                                                         \
-    do { if (stages == 2) DMA_LAUNCH(WQ, O32, 2); else if (stages == 3) DMA_LAUNCH(WQ, O32, 3); else DMA_LAUNCH(WQ, O32, 4); } while (0)
-#define DMA_EPI(WQ) do { if (epi == EPI_F32) DMA_STAGES(WQ, EPI_F32); else if (epi == EPI_F16) DMA_STAGES(WQ, EPI_F16); else DMA_STAGES(WQ, EPI_SWIGLU); } while (0)
-        if (wq_bit == 8) DMA_EPI(8); else if (wq_bit == 4) DMA_EPI(4); else DMA_EPI(0);
-#undef DMA_EPI
-#undef DMA_STAGES
-#undef DMA_LAUNCH
+        dispatch_int<8, 4, 0>(dk.wq, [&](auto WQ) {
+            dispatch_epi(dk.epi, [&](auto E) {
+                dispatch_int<2, 3, 4>(dk.stages, [&](auto ST) {
+                    auto go = [&](auto kernel, unsigned threads) {
+                        hipLaunchKernelGGL(kernel, g2, dim3(threads), 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws);
+                    };
+                    if constexpr (WQ == 8 && ST >= 3) {
+                        if (dk.wl == 6) return go(gemm_dma_kernel<WQ, E, ST, 6>, 768);
+                    }
+                    if (dk.wl == 5) go(gemm_dma_kernel<WQ, E, ST, 5>, 512);
+                    else if (dk.bm == 64) go(gemm_dma_kernel<WQ, E, ST, 1, 64>, 256);
+                    else if (dk.maxg == 16) go(gemm_dma_kernel<WQ, E, ST, 1, G_BM, 16>, 256);
+                    else go(gemm_dma_kernel<WQ, E, ST, 1>, 256);
+                });
+            });
+        });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || splits == 1) return e;
         if (defer && epi == EPI_F16 && N % 8 == 0 && splits <= 8) { *defer = SplitSlabs{ws, splits, wq_bit == 8 ? scale : nullptr, N, M}; return e; }
         return launch_splitk_reduce(s, ws, splits, M, N, wq_bit == 8 ? scale : nullptr, y, ldy, epi);
     }
-#define GEMM_CASE(WQ, O32)                                                                                          \
-    if (wq_bit == WQ && epi == (int)O32) {                                                                          \
-        if (route) {                                                                                                \
-            route->add("kernel=gemm_kernel<%d,%s> splits=1 reduce=none order=plain", WQ, epi_name(epi));            \
-            if (route->dry) return hipSuccess;                                                                      \
-        }                                                                                                           \
-        hipLaunchKernelGGL((gemm_kernel<WQ, O32>), grid, block, 0, s, x, w, scale, M, N, K, group, y, ldy, n_tiles, \
-                           m_tiles);                                                                                \
-        return hipGetLastError();                                                                                   \
+    if (wq_bit != 0 && wq_bit != 8 && wq_bit != 4) return hipErrorInvalidValue;
+    if (route) {
+        route->add("kernel=gemm_kernel<%d,%s> splits=1 reduce=none order=plain", wq_bit, epi_name(epi));
+        if (route->dry) return hipSuccess;
     }
-    GEMM_CASE(0, EPI_F16) GEMM_CASE(0, EPI_F32) GEMM_CASE(0, EPI_SWIGLU) GEMM_CASE(8, EPI_F16) GEMM_CASE(8, EPI_F32) GEMM_CASE(8, EPI_SWIGLU)
-    GEMM_CASE(4, EPI_F16) GEMM_CASE(4, EPI_F32) GEMM_CASE(4, EPI_SWIGLU)
-#undef GEMM_CASE
-    return hipErrorInvalidValue;
+    dispatch_int<0, 8, 4>(wq_bit, [&](auto WQ) {
+        dispatch_epi(epi, [&](auto E) {
+            hipLaunchKernelGGL((gemm_kernel<WQ, E>), grid, block, 0, s, x, w, scale, M, N, K, group, y, ldy, n_tiles, m_tiles);
+        });
+    });
+    return hipGetLastError();
 }
 
 }  // namespace pplhip

@@ -5,12 +5,13 @@
 // Oracle: linear_fwd_a8 / ref_quant_act_rows / ref_quant_weight_rows (oracle/llama_ref.c) -- integer accumulation makes
 // the GEMM itself bit-exact against it; only the fp16 rounding of the two fp32 multiplies is left, done in the same order.
 //
-// Tile kernel (M > 32, K % 128 == 0): block tile 128 (n) x 128 (m) x 128 (k) int8, 4 waves as 2 x 2, each 64 x 64 =
-// 4 x 4 tiles of v_mfma_i32_16x16x64_i8 (weights = A operand, so a lane owns 4 consecutive n of one activation row).
-// Both operands go global -> LDS by DMA into [row][128 B] tiles whose 16-byte chunk index is XOR-swizzled with
-// (row >> 1) & 7 on the source address and on the fragment reads (same scheme as the fp16 activation tile of k_gemm_dev.h).
-// Two LDS stages (64 KiB -> two blocks per CU), one barrier per K tile; launches of <= 256 tiles use the 8-wave producer /
-// consumer form (gemm_i8_pc_kernel).
+// Tile kernel (M > 32, K % 128 == 0): block tile 128 (n) x 128 (m) x 128 (k) int8, 4 multiplying waves as 2 x 2, each 64 x 64 =
+// 4 x 4 tiles of v_mfma_i32_16x16x64_i8 (weights = A operand, so a lane owns 4 consecutive n of one activation row), and 4 producer
+// waves that only move the tiles (gemm_i8_pc_kernel).  Both operands go global -> LDS by DMA into [row][128 B] tiles whose 16-byte
+// chunk index is XOR-swizzled with (row >> 1) & 7 on the source address and on the fragment reads (same scheme as the fp16 activation
+// tile of k_gemm_dev.h).  A ring of 2 LDS stages (64 KiB -> two blocks per CU) or, for launches of <= 256 tiles, 4; one barrier per
+// K tile.  The 128 x 384 blocks (gemm_i8_wide_kernel) share its consumer step (mma_tile), block order (xcd_tile) and DMA source layout
+// (dma_src128); they and the 256 x 256 blocks (gemm_i8_256_kernel; int8, M >= 4096) share its epilogue (store_wave_tile).
 // Skinny / generic kernel (any M, K % 16 == 0): one block per 16 weight rows, waves split K, weights straight from HBM
 // into the MFMA A operand, activations (L2 resident) into B; grid.y walks 32-row activation groups.
 //
@@ -50,59 +51,14 @@ __device__ __forceinline__ int q8(float v) {
     return (int)v;
 }
 
-// one block per row; x [M, ldx] fp16 (K valid), q [M, ldq] int8 (columns K..ldq-1 zero), sx [M]
-__global__ __launch_bounds__(256) void quant_act_kernel(const uint16_t* __restrict__ x, int K, int64_t ldx, int8_t* __restrict__ q,
-                                                        int64_t ldq, float* __restrict__ sx) {
-    __shared__ float red[4];
-    const int64_t m = blockIdx.x;
-    const uint16_t* xr = x + m * ldx;
-    int8_t* qr = q + m * ldq;
-    const int K8 = K >> 3;
-    float amax = 0.f;
-    for (int i = threadIdx.x; i < K8; i += 256) {
-        const h8 v = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(xr + i * 8));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j]));
-    }
-    for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(h2f(xr[k])));
-    amax = block_max_256(amax, red);
-    const float inv = amax > 0.f ? 127.0f / amax : 0.f;
-    if (threadIdx.x == 0) sx[m] = amax / 127.0f;
-    for (int i = threadIdx.x; i < K8; i += 256) {
-        const h8 v = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(xr + i * 8));
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) lo |= (uint32_t)(q8((float)v[j] * inv) & 0xff) << (8 * j);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hi |= (uint32_t)(q8((float)v[4 + j] * inv) & 0xff) << (8 * j);
-        *reinterpret_cast<uint2*>(qr + i * 8) = make_uint2(lo, hi);
-    }
-    for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) qr[k] = (int8_t)q8(h2f(xr[k]) * inv);
-    for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
-}
-
-// one block per weight row; w [N, K] fp16 -> q [N, ldq] int8 (pad columns zero) + scale [N] fp16
-__global__ __launch_bounds__(256) void quant_weight_kernel(const uint16_t* __restrict__ w, int K, int8_t* __restrict__ q, int64_t ldq,
-                                                           uint16_t* __restrict__ scale) {
-    __shared__ float red[4];
-    const int64_t n = blockIdx.x;
-    const uint16_t* wr = w + n * K;
-    int8_t* qr = q + n * ldq;
-    float amax = 0.f;
-    for (int k = threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(h2f(wr[k])));
-    amax = block_max_256(amax, red);
-    const uint16_t sh = f2h(amax / 127.0f);
-    if (threadIdx.x == 0) scale[n] = sh;
-    const float s = h2f(sh) > 0.f ? h2f(sh) : 1.0f;
-    for (int k = threadIdx.x; k < K; k += 256) qr[k] = (int8_t)q8(h2f(wr[k]) / s);  // IEEE division (hipcc default: correctly rounded)
-    for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
-}
-
-// online_f8f8: one block per row, the fp8 KV row rule (k_common.h fp8_row_exp / fp8_quant): e = the smallest integer with
-// 448 2^e >= max|x| (clamped to [-15, 8]), q = e4m3fn_rne(x 2^-e).  x [M, ldx] fp16 (K valid) -> q [M, ldq] codes (columns K..ldq-1
-// zero) + sx [M] = 2^e (fp32)
-__global__ __launch_bounds__(256) void quant_act_f8_kernel(const uint16_t* __restrict__ x, int K, int64_t ldx, uint8_t* __restrict__ q,
-                                                           int64_t ldq, float* __restrict__ sx) {
+// The quantisers: one block per row.  int8 (F8 false): activations q = clamp(rint(x * (127 / max|x|))), sx = max|x| / 127; weights
+// scale = fp16(max|w| / 127), q = clamp(rint(w / scale)).  online_f8f8 (F8 true): the fp8 KV row rule (k_common.h fp8_row_exp /
+// fp8_quant) -- e = the smallest integer with 448 2^e >= max|x| (clamped to [-15, 8]), q = e4m3fn_rne(x 2^-e), sx = 2^e (fp32),
+// scale = fp16(2^e).  Only the per-element rule and the scale write differ between the two.
+// x [M, ldx] fp16 (K valid) -> q [M, ldq] codes (columns K..ldq-1 zero) + sx [M]
+template <bool F8>
+__device__ __forceinline__ void quant_act_row(const uint16_t* __restrict__ x, int K, int64_t ldx, uint8_t* __restrict__ q, int64_t ldq,
+                                              float* __restrict__ sx) {
     __shared__ float red[4];
     const int64_t m = blockIdx.x;
     const uint16_t* xr = x + m * ldx;
@@ -115,34 +71,57 @@ __global__ __launch_bounds__(256) void quant_act_f8_kernel(const uint16_t* __res
         for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j]));
     }
     for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(h2f(xr[k])));
-    const int e = fp8_row_exp(block_max_256(amax, red));
-    if (threadIdx.x == 0) sx[m] = pow2f(e);
+    amax = block_max_256(amax, red);
+    const int e = F8 ? fp8_row_exp(amax) : 0;
+    const float inv = amax > 0.f ? 127.0f / amax : 0.f;
+    if (threadIdx.x == 0) sx[m] = F8 ? pow2f(e) : amax / 127.0f;
+    auto code = [&](float v) -> uint32_t { return F8 ? fp8_quant(v, e) : (uint32_t)(q8(v * inv) & 0xff); };
     for (int i = threadIdx.x; i < K8; i += 256) {
         const h8 v = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(xr + i * 8));
         uint32_t lo = 0, hi = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) lo |= fp8_quant((float)v[j], e) << (8 * j);
+        for (int j = 0; j < 4; ++j) lo |= code((float)v[j]) << (8 * j);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) hi |= fp8_quant((float)v[4 + j], e) << (8 * j);
+        for (int j = 0; j < 4; ++j) hi |= code((float)v[4 + j]) << (8 * j);
         *reinterpret_cast<uint2*>(qr + i * 8) = make_uint2(lo, hi);
     }
-    for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) qr[k] = (uint8_t)fp8_quant(h2f(xr[k]), e);
+    for (int k = K8 * 8 + threadIdx.x; k < K; k += 256) qr[k] = (uint8_t)code(h2f(xr[k]));
     for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
 }
-
-// one block per weight row, the same rule: w [N, K] fp16 -> q [N, ldq] e4m3fn codes (pad columns zero) + scale [N] = fp16(2^e)
-__global__ __launch_bounds__(256) void quant_weight_f8_kernel(const uint16_t* __restrict__ w, int K, uint8_t* __restrict__ q, int64_t ldq,
-                                                              uint16_t* __restrict__ scale) {
+// w [N, K] fp16 -> q [N, ldq] codes (pad columns zero) + scale [N] fp16
+template <bool F8>
+__device__ __forceinline__ void quant_weight_row(const uint16_t* __restrict__ w, int K, uint8_t* __restrict__ q, int64_t ldq,
+                                                 uint16_t* __restrict__ scale) {
     __shared__ float red[4];
     const int64_t n = blockIdx.x;
     const uint16_t* wr = w + n * K;
     uint8_t* qr = q + n * ldq;
     float amax = 0.f;
     for (int k = threadIdx.x; k < K; k += 256) amax = fmaxf(amax, fabsf(h2f(wr[k])));
-    const int e = fp8_row_exp(block_max_256(amax, red));
-    if (threadIdx.x == 0) scale[n] = f2h(pow2f(e));
-    for (int k = threadIdx.x; k < K; k += 256) qr[k] = (uint8_t)fp8_quant(h2f(wr[k]), e);
+    amax = block_max_256(amax, red);
+    const int e = F8 ? fp8_row_exp(amax) : 0;
+    const uint16_t sh = F8 ? f2h(pow2f(e)) : f2h(amax / 127.0f);
+    if (threadIdx.x == 0) scale[n] = sh;
+    const float s = h2f(sh) > 0.f ? h2f(sh) : 1.0f;
+    for (int k = threadIdx.x; k < K; k += 256)  // int8: IEEE division (hipcc default: correctly rounded)
+        qr[k] = F8 ? (uint8_t)fp8_quant(h2f(wr[k]), e) : (uint8_t)q8(h2f(wr[k]) / s);
     for (int64_t k = K + threadIdx.x; k < ldq; k += 256) qr[k] = 0;
+}
+__global__ __launch_bounds__(256) void quant_act_kernel(const uint16_t* __restrict__ x, int K, int64_t ldx, int8_t* __restrict__ q,
+                                                        int64_t ldq, float* __restrict__ sx) {
+    quant_act_row<false>(x, K, ldx, reinterpret_cast<uint8_t*>(q), ldq, sx);
+}
+__global__ __launch_bounds__(256) void quant_act_f8_kernel(const uint16_t* __restrict__ x, int K, int64_t ldx, uint8_t* __restrict__ q,
+                                                           int64_t ldq, float* __restrict__ sx) {
+    quant_act_row<true>(x, K, ldx, q, ldq, sx);
+}
+__global__ __launch_bounds__(256) void quant_weight_kernel(const uint16_t* __restrict__ w, int K, int8_t* __restrict__ q, int64_t ldq,
+                                                           uint16_t* __restrict__ scale) {
+    quant_weight_row<false>(w, K, reinterpret_cast<uint8_t*>(q), ldq, scale);
+}
+__global__ __launch_bounds__(256) void quant_weight_f8_kernel(const uint16_t* __restrict__ w, int K, uint8_t* __restrict__ q, int64_t ldq,
+                                                              uint16_t* __restrict__ scale) {
+    quant_weight_row<true>(w, K, q, ldq, scale);
 }
 
 template <int EPI>
@@ -164,109 +143,53 @@ __device__ __forceinline__ f4v mma_f8(i4v alo, i4v ahi, i4v blo, i4v bhi, f4v c)
     const i8v a = __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7), b = __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
 }
-// consumer step of a 128-deep LDS tile pair ([row][128 B], g_swz chunks) for a 64 x 64 wave tile: weight rows wr0.., activation rows xr0..
-__device__ __forceinline__ void mma_tile_f8(const char* ws, const char* xs, int wr0, int xr0, int l15, int kq, f4v (&acc)[4][4]) {
-    i4v a[2][4], b[2][4];
+// Consumer step of a 128-deep LDS tile pair ([row][128 B], g_swz chunks) for a 64 x 64 wave tile, weight rows wr0.., activation rows
+// xr0..: the fragments of 16-byte chunk c = ks * 4 + kq (k-step ks), then int8 two rounds of 16 MFMAs, fp8 one round on both k-steps
+__device__ __forceinline__ void tile_frags(const char* ws, const char* xs, int wr0, int xr0, int l15, int c, i4v (&a)[4], i4v (&b)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = wr0 + i * 16 + l15;
+        a[i] = *reinterpret_cast<const i4v*>(ws + row * I_BK + g_swz(row, c) * 16);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = xr0 + j * 16 + l15;
+        b[j] = *reinterpret_cast<const i4v*>(xs + row * I_BK + g_swz(row, c) * 16);
+    }
+}
+__device__ __forceinline__ void mma_tile(const char* ws, const char* xs, int wr0, int xr0, int l15, int kq, i4v (&acc)[4][4]) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
+        i4v a[4], b[4];
+        tile_frags(ws, xs, wr0, xr0, l15, ks * 4 + kq, a, b);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = wr0 + i * 16 + l15;
-            a[ks][i] = *reinterpret_cast<const i4v*>(ws + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-        }
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = xr0 + j * 16 + l15;
-            b[ks][j] = *reinterpret_cast<const i4v*>(xs + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-        }
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
     }
+}
+__device__ __forceinline__ void mma_tile(const char* ws, const char* xs, int wr0, int xr0, int l15, int kq, f4v (&acc)[4][4]) {
+    i4v a[2][4], b[2][4];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) tile_frags(ws, xs, wr0, xr0, l15, ks * 4 + kq, a[ks], b[ks]);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = mma_f8(a[0][i], a[1][i], b[0][j], b[1][j], acc[i][j]);
 }
 
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_i8_kernel(const int8_t* __restrict__ xq, const float* __restrict__ sx,
-                                                         const int8_t* __restrict__ w, const uint16_t* __restrict__ scale, int64_t M,
-                                                         int N, int K, void* __restrict__ yv, int64_t ldy, int n_tiles, int m_tiles) {
-    extern __shared__ __attribute__((aligned(16))) char smem_i8[];  // 2 x (X 16 KiB + W 16 KiB)
-    constexpr int TILE = I_BM * I_BK;                               // bytes of one operand tile
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;  // the M tiles of one weight tile run on one XCD (block b -> XCD b % 8)
-    const int nt = xcd + 8 * (slot / m_tiles);
-    const int mt = slot % m_tiles;
-    if (nt >= n_tiles) return;
-    const int n0 = nt * I_BN;
-    const int64_t m0 = (int64_t)mt * I_BM;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kq = lane >> 4;
-    const int wn = wave & 1, wm = wave >> 1;
-
-    const int8_t* xsrc[4];
-    const int8_t* wsrc[4];
+// epilogue of a wave tile of 4 (n) x NJ (m) 16 x 16 tiles whose first output is y[m0][n0]
+template <int EPI, class ACC, int NJ>
+__device__ __forceinline__ void store_wave_tile(void* yv, int64_t ldy, const float* __restrict__ sx, const uint16_t* __restrict__ scale,
+                                                int64_t M, int N, int64_t m0, int n0, int l15, int kq, const ACC (&acc)[4][NJ]) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = j * 256 + tid, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
-        int64_t m = m0 + row;
-        if (m >= M) m = M - 1;
-        int n = n0 + row;
-        if (n >= N) n = N - 1;
-        xsrc[j] = xq + m * K + c * 16;
-        wsrc[j] = w + (int64_t)n * K + c * 16;
-    }
-    const uint32_t xdst = __builtin_amdgcn_readfirstlane(lds_addr(smem_i8) + wave * 1024);
-    const uint32_t wdst = xdst + 2 * TILE;
-    auto issue = [&](int stage, int k0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) glds16(xsrc[j] + k0, xdst + stage * TILE + j * 4096);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) glds16(wsrc[j] + k0, wdst + stage * TILE + j * 4096);
-    };
-
-    i4v acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = i4v{0, 0, 0, 0};
-
-    const int ktiles = K / I_BK;
-    issue(0, 0);
-    for (int t = 0; t < ktiles; ++t) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (t + 1 < ktiles) issue((t + 1) & 1, (t + 1) * I_BK);
-        const char* xs = smem_i8 + (t & 1) * TILE;
-        const char* ws = smem_i8 + 2 * TILE + (t & 1) * TILE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            i4v a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = wn * 64 + i * 16 + l15;
-                a[i] = *reinterpret_cast<const i4v*>(ws + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = wm * 64 + j * 16 + l15;
-                b[j] = *reinterpret_cast<const i4v*>(xs + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-    }
-
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t m = m0 + wm * 64 + j * 16 + l15;
+    for (int j = 0; j < NJ; ++j) {
+        const int64_t m = m0 + j * 16 + l15;
         if (m >= M) continue;
         const float sxm = sx[m];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + i * 16 + kq * 4;
+            const int n = n0 + i * 16 + kq * 4;
             if (n >= N) continue;
             const h4 sh = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(scale + n));
             store4_i8<EPI>(yv, ldy, m, n, acc[i][j], sxm, sh);
@@ -274,7 +197,28 @@ __global__ __launch_bounds__(256, 2) void gemm_i8_kernel(const int8_t* __restric
     }
 }
 
-// Producer / consumer form of the tile kernel: 8 waves, waves 0..3 multiply (2 x 2 layout as above), waves 4..7 do nothing but wait
+// block -> (weight tile nt, activation tile mt): the M tiles of one weight tile run on one XCD (block b -> XCD b % 8).  false: a block
+// of the padding that rounds the weight tiles up to 8
+__device__ __forceinline__ bool xcd_tile(int n_tiles, int m_tiles, int& nt, int& mt) {
+    const int id = blockIdx.x;
+    const int xcd = id & 7, slot = id >> 3;
+    nt = xcd + 8 * (slot / m_tiles);
+    mt = slot % m_tiles;
+    return nt < n_tiles;
+}
+
+// LDS-DMA source of lane position p (16-byte chunk p & 7 of tile row p >> 3) of a [rows][128 B] tile that starts at row row0 of the
+// matrix base [nrows][K]: rows past the matrix repeat its last row (never stored), the chunk is XOR-swizzled on the source side (the
+// DMA writes LDS linearly)
+template <class I>
+__device__ __forceinline__ const int8_t* dma_src128(const int8_t* base, I row0, I nrows, int K, int p) {
+    const int row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
+    I r = row0 + row;
+    if (r >= nrows) r = nrows - 1;
+    return base + (int64_t)r * K + c * 16;
+}
+
+// The tile kernel, a producer / consumer block of 8 waves: waves 0..3 multiply (2 x 2, each 64 x 64), waves 4..7 do nothing but wait
 // for their LDS-DMA pieces and refill the ring (the ~100-cycle issue cost of a piece then runs beside the MFMA stream instead of in
 // front of it: int8 moves 8 pieces per 32 MFMAs and wave, more than the fp16 kernel).  ST stages of 32 KiB, one barrier per tile.
 template <int EPI, int ST, bool F8>
@@ -283,11 +227,8 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
                                                          int N, int K, void* __restrict__ yv, int64_t ldy, int n_tiles, int m_tiles) {
     extern __shared__ __attribute__((aligned(16))) char smem_i8[];  // ST x (X 16 KiB) then ST x (W 16 KiB)
     constexpr int TILE = I_BM * I_BK;
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int nt = xcd + 8 * (slot / m_tiles);
-    const int mt = slot % m_tiles;
-    if (nt >= n_tiles) return;
+    int nt, mt;
+    if (!xcd_tile(n_tiles, m_tiles, nt, mt)) return;
     const int n0 = nt * I_BN;
     const int64_t m0 = (int64_t)mt * I_BM;
     const bool producer = threadIdx.x >= 256;
@@ -301,13 +242,8 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
         const int8_t* wsrc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int p = j * 256 + tid, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
-            int64_t m = m0 + row;
-            if (m >= M) m = M - 1;
-            int n = n0 + row;
-            if (n >= N) n = N - 1;
-            xsrc[j] = xq + m * K + c * 16;
-            wsrc[j] = w + (int64_t)n * K + c * 16;
+            xsrc[j] = dma_src128(xq, m0, M, K, j * 256 + tid);
+            wsrc[j] = dma_src128(w, n0, N, K, j * 256 + tid);
         }
         const uint32_t xdst = __builtin_amdgcn_readfirstlane(lds_addr(smem_i8) + wave * 1024);
         const uint32_t wdst = xdst + ST * TILE;
@@ -345,42 +281,9 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
         const char* xs = smem_i8 + st * TILE;
         const char* ws = smem_i8 + ST * TILE + st * TILE;
         st = st == ST - 1 ? 0 : st + 1;
-        if constexpr (F8) {
-            mma_tile_f8(ws, xs, wn * 64, wm * 64, l15, kq, acc);
-            continue;
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            i4v a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = wn * 64 + i * 16 + l15;
-                a[i] = *reinterpret_cast<const i4v*>(ws + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = wm * 64 + j * 16 + l15;
-                b[j] = *reinterpret_cast<const i4v*>(xs + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
+        mma_tile(ws, xs, wn * 64, wm * 64, l15, kq, acc);
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t m = m0 + wm * 64 + j * 16 + l15;
-        if (m >= M) continue;
-        const float sxm = sx[m];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + i * 16 + kq * 4;
-            if (n >= N) continue;
-            const h4 sh = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(scale + n));
-            store4_i8<EPI>(yv, ldy, m, n, acc[i][j], sxm, sh);
-        }
-    }
+    store_wave_tile<EPI>(yv, ldy, sx, scale, M, N, m0 + wm * 64, n0 + wn * 64, l15, kq, acc);
 }
 
 // 128 (m) x 384 (n) x 128 (k) block: the int8 form of gemm_w8_wide_kernel (k_gemm_wide.hip).  Twelve consumer waves as 6 (n) x 2 (m), wave
@@ -396,11 +299,8 @@ __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(cons
                                                                              int64_t M, int N, int K, void* __restrict__ yv, int64_t ldy,
                                                                              int n_tiles, int m_tiles) {
     extern __shared__ __attribute__((aligned(16))) char smem_i8[];  // IW_ST x (X 16 KiB) then IW_ST x (W 48 KiB)
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int nt = xcd + 8 * (slot / m_tiles);
-    const int mt = slot % m_tiles;
-    if (nt >= n_tiles) return;
+    int nt, mt;
+    if (!xcd_tile(n_tiles, m_tiles, nt, mt)) return;
     const int n0 = nt * IW_BN;
     const int64_t m0 = (int64_t)mt * I_BM;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -418,31 +318,19 @@ __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(cons
             const int P = pw + IW_NP * j;
             const bool isx = j < IW_XB / 1024 / IW_NP;
             const int Pl = isx ? P : P - IW_XB / 1024;
-            const int p = Pl * 64 + lane, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
-            if (isx) {
-                int64_t m = m0 + row;
-                if (m >= M) m = M - 1;
-                psrc[j] = xq + m * K + c * 16;
-                pdst[j] = __builtin_amdgcn_readfirstlane(xbase + Pl * 1024);
-            } else {
-                int n = n0 + row;
-                if (n >= N) n = N - 1;
-                psrc[j] = w + (int64_t)n * K + c * 16;
-                pdst[j] = __builtin_amdgcn_readfirstlane(wbase + Pl * 1024);
-            }
+            psrc[j] = isx ? dma_src128(xq, m0, M, K, Pl * 64 + lane) : dma_src128(w, n0, N, K, Pl * 64 + lane);
+            pdst[j] = __builtin_amdgcn_readfirstlane((isx ? xbase : wbase) + Pl * 1024);
         }
-#define IW_PRODUCE(KT, STG)                                                                                                  \
-    do {                                                                                                                     \
-        _Pragma("unroll") for (int j = 0; j < IW_PP; ++j)                                                                    \
-            glds16(psrc[j] + (int64_t)(KT) * I_BK, pdst[j] + (STG) * (j < IW_XB / 1024 / IW_NP ? IW_XB : IW_WB));            \
-    } while (0)
-        IW_PRODUCE(0, 0);
+        auto produce = [&](int kt, int stage) {
+#pragma unroll
+            for (int j = 0; j < IW_PP; ++j) glds16(psrc[j] + (int64_t)kt * I_BK, pdst[j] + stage * (j < IW_XB / 1024 / IW_NP ? IW_XB : IW_WB));
+        };
+        produce(0, 0);
         for (int t = 0; t < ktiles; ++t) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();  // tile t is published; the other stage (read during iteration t - 1) is free
-            if (t + 1 < ktiles) IW_PRODUCE(t + 1, (t + 1) & 1);
+            if (t + 1 < ktiles) produce(t + 1, (t + 1) & 1);
         }
-#undef IW_PRODUCE
         return;
     }
 
@@ -457,42 +345,9 @@ __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(cons
         __syncthreads();
         const char* xs = smem_i8 + (t & 1) * IW_XB;
         const char* ws = smem_i8 + IW_ST * IW_XB + (t & 1) * IW_WB;
-        if constexpr (F8) {
-            mma_tile_f8(ws, xs, wn * 64, wm * 64, l15, kq, acc);
-            continue;
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            i4v a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = wn * 64 + i * 16 + l15;
-                a[i] = *reinterpret_cast<const i4v*>(ws + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = wm * 64 + j * 16 + l15;
-                b[j] = *reinterpret_cast<const i4v*>(xs + row * I_BK + g_swz(row, ks * 4 + kq) * 16);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
+        mma_tile(ws, xs, wn * 64, wm * 64, l15, kq, acc);
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t m = m0 + wm * 64 + j * 16 + l15;
-        if (m >= M) continue;
-        const float sxm = sx[m];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + i * 16 + kq * 4;
-            if (n >= N) continue;
-            const h4 sh = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(scale + n));
-            store4_i8<EPI>(yv, ldy, m, n, acc[i][j], sxm, sh);
-        }
-    }
+    store_wave_tile<EPI>(yv, ldy, sx, scale, M, N, m0 + wm * 64, n0 + wn * 64, l15, kq, acc);
 }
 
 // Large M (steps that carry prefill): 256(n) x 256(m) x 64(k) tiles, 8 waves as 4 (n) x 2 (m), wave tile 64 x 128 = 4 x 8 MFMA tiles
@@ -583,19 +438,7 @@ __global__ __launch_bounds__(512) void gemm_i8_256_kernel(const int8_t* __restri
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int64_t m = m0 + wm * 128 + j * 16 + l15;
-        if (m >= M) continue;
-        const float sxm = sx[m];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + i * 16 + kq * 4;
-            if (n >= N) continue;
-            const h4 sh = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(scale + n));
-            store4_i8<EPI>(yv, ldy, m, n, acc[i][j], sxm, sh);
-        }
-    }
+    store_wave_tile<EPI>(yv, ldy, sx, scale, M, N, m0 + wm * 128, n0 + wn * 64, l15, kq, acc);
 }
 
 // skinny / generic: block = NW waves = NW K slices of 16 weight rows; MT = 16-row activation tiles per block (grid.y walks M)
@@ -710,7 +553,7 @@ hipError_t launch_quant_weight_f8(hipStream_t s, const uint16_t* w, int N, int K
 }
 
 // the int8 (F8 false) and fp8 (F8 true) launches share one dispatch table, except that fp8 has no 256 x 256 form (steps of M >= 4096
-// take the 128 x 128 producer / consumer form) and no 4-wave form (a forced PPLHIP_GEMM_I8_PC=0 runs the 2-stage producer / consumer form)
+// take the 128 x 128 producer / consumer form)
 template <bool F8>
 static hipError_t launch_linear_q8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M,
                                    int N, int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
@@ -721,35 +564,17 @@ static hipError_t launch_linear_q8(hipStream_t s, const int8_t* xq, const float*
     static const bool force_generic = tune_set("PPLHIP_GEMM_GENERIC");
     if (M > 32 && K % I_BK == 0 && !force_generic) {
         const int n_tiles = (N + I_BN - 1) / I_BN, m_tiles = (int)((M + I_BM - 1) / I_BM);
-        const size_t lds = 4 * (size_t)I_BM * I_BK;
-        static bool attr_dev[64] = {false};  // per device (see launch_linear)
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (!attr_dev[dev & 63]) {
-            if (!F8) {
-                (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute((const void*)gemm_i8_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            }
-            attr_dev[dev & 63] = true;
-        }
-        dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles));
-        // 8-wave producer / consumer blocks everywhere (measured at M = 1024 against the 4-wave kernel: wo 32.5 -> 28.6 us and
-        // w2 76.0 -> 51.4 us with a 4-stage ring, one block per CU; w13 116.6 -> 106.0 us with two stages, two blocks per CU; wqkv
-        // 62.1 vs 63.6 us; M = 2048 layer 502 -> 459 us, M = 8192 equal).  PPLHIP_GEMM_I8_PC = 0 (4-wave kernel) / 2 / 3 / 4 forces a form.
         static const int min_m256 = tune_int("PPLHIP_GEMM_I8_256_MIN_M", 4096);  // measured: M = 4096 layer 888 us (1.87 POP/s) vs 1110, M = 2048 554 vs 459 us
         if (!F8 && M >= min_m256 && N >= 1024) {
             const int nt2 = (N + 255) / 256, mt2 = (int)((M + 255) / 256);
-            static const int st256 = tune_int("PPLHIP_GEMM_I8_256_ST", 4);
-            const size_t lds2 = (size_t)(st256 == 3 ? 3 : 4) * 2 * 256 * 64;
-            static bool attr2[64] = {false};
-            if (!attr2[dev & 63]) {
-#define A2(E) do { (void)hipFuncSetAttribute((const void*)gemm_i8_256_kernel<E, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 2 * 256 * 64); \
-                   (void)hipFuncSetAttribute((const void*)gemm_i8_256_kernel<E, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 256 * 64); } while (0)
-                A2(EPI_F16); A2(EPI_F32); A2(EPI_SWIGLU);
-#undef A2
-                attr2[dev & 63] = true;
-            }
+            static const int st256 = tune_int("PPLHIP_GEMM_I8_256_ST", 4) == 3 ? 3 : 4;
+            const size_t lds2 = (size_t)st256 * 2 * 256 * 64;
+            static LdsOptIn once;  // (per device: see k_gemm_dev.h)
+            if (once.first())
+                for_each_epi([](auto E) {
+                    set_max_lds(3 * 2 * 256 * 64, gemm_i8_256_kernel<E, 3>);
+                    set_max_lds(4 * 2 * 256 * 64, gemm_i8_256_kernel<E, 4>);
+                });
             static const int forced_gm = tune_int("PPLHIP_GEMM256_GM", 0);
             static const int forced_gn = tune_int("PPLHIP_GEMM256_GN", 0);
             const int nl = (nt2 + 7) / 8;
@@ -758,72 +583,58 @@ static hipError_t launch_linear_q8(hipStream_t s, const int8_t* xq, const float*
             int gn = forced_gn > 0 ? forced_gn : 8;
             if (gn > nl) gn = nl;
             dim3 g2((unsigned)(8 * ((nl + gn - 1) / gn * gn) * mt2));
-#define L2(E) do { if (st256 == 3) hipLaunchKernelGGL((gemm_i8_256_kernel<E, 3>), g2, dim3(512), lds2, s, xq, sx, w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm); \
-                   else hipLaunchKernelGGL((gemm_i8_256_kernel<E, 4>), g2, dim3(512), lds2, s, xq, sx, w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm); } while (0)
-            if (epi == EPI_F32) L2(EPI_F32); else if (epi == EPI_F16) L2(EPI_F16); else L2(EPI_SWIGLU);
-#undef L2
+            dispatch_epi(epi, [&](auto E) {
+                dispatch_int<3, 4>(st256, [&](auto ST) {
+                    hipLaunchKernelGGL((gemm_i8_256_kernel<E, ST>), g2, dim3(512), lds2, s, xq, sx, w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm);
+                });
+            });
             return hipGetLastError();
         }
-        {   // 128 x 384 tiles when they fill rounds of 256 one-per-CU blocks (the rule of linear_w8_wide_waves, k_gemm_wide.hip)
-            static const int wide = tune_int("PPLHIP_GEMM_I8_WIDE", 1);
-            if (wide && M >= 512 && N >= 8192 && linear_w8_wide_waves(M, N) == 12) {
-                const int ntw = (N + IW_BN - 1) / IW_BN, mtw = (int)((M + I_BM - 1) / I_BM);
-                const size_t ldsw = (size_t)IW_ST * (IW_XB + IW_WB);
-                static bool attr_w[64] = {false};
-                if (!attr_w[dev & 63]) {
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_F16, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_F32, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_wide_kernel<EPI_SWIGLU, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                    attr_w[dev & 63] = true;
-                }
-                dim3 gw((unsigned)((ntw + 7) / 8 * 8 * mtw));
-#define LW(E) hipLaunchKernelGGL((gemm_i8_wide_kernel<E, F8>), gw, dim3((IW_NC + IW_NP) * 64), ldsw, s, xq, sx, w, scale, M, N, K, y, ldy, ntw, mtw)
-                if (epi == EPI_F32) LW(EPI_F32); else if (epi == EPI_F16) LW(EPI_F16); else LW(EPI_SWIGLU);
-#undef LW
-                return hipGetLastError();
-            }
+        // 128 x 384 tiles when they fill rounds of 256 one-per-CU blocks (the rule of linear_w8_wide_waves, k_gemm_wide.hip)
+        static const int wide = tune_int("PPLHIP_GEMM_I8_WIDE", 1);
+        if (wide && M >= 512 && N >= 8192 && linear_w8_wide_waves(M, N) == 12) {
+            const int ntw = (N + IW_BN - 1) / IW_BN;
+            const size_t ldsw = (size_t)IW_ST * (IW_XB + IW_WB);
+            static LdsOptIn once;
+            if (once.first()) set_max_lds(ldsw, gemm_i8_wide_kernel<EPI_F16, F8>, gemm_i8_wide_kernel<EPI_F32, F8>, gemm_i8_wide_kernel<EPI_SWIGLU, F8>);
+            dim3 gw((unsigned)((ntw + 7) / 8 * 8 * m_tiles));
+            dispatch_epi(epi, [&](auto E) {
+                hipLaunchKernelGGL((gemm_i8_wide_kernel<E, F8>), gw, dim3((IW_NC + IW_NP) * 64), ldsw, s, xq, sx, w, scale, M, N, K, y, ldy, ntw, m_tiles);
+            });
+            return hipGetLastError();
         }
+        // 8-wave producer / consumer blocks for everything else (measured at M = 1024 against the 4-wave kernel this file held until it
+        // had lost on every shape: wo 32.5 -> 28.6 us and w2 76.0 -> 51.4 us with a 4-stage ring, one block per CU; w13 116.6 -> 106.0 us
+        // with two stages, two blocks per CU; wqkv 62.1 vs 63.6 us; M = 2048 layer 502 -> 459 us, M = 8192 equal).  In a tuning build
+        // PPLHIP_GEMM_I8_PC = 3 / 4 forces that ring depth; any other value, 0 included, runs the two-stage form.
         static const int forced_pc = tune_int("PPLHIP_GEMM_I8_PC", -1);
         int pc = forced_pc >= 0 ? forced_pc : ((int64_t)n_tiles * m_tiles <= 256 ? 4 : 2);
-        if (F8 && pc != 3 && pc != 4) pc = 2;
-        if (pc == 2 || pc == 3 || pc == 4) {
-            const size_t lds_pc = (size_t)pc * 2 * I_BM * I_BK;
-            static bool attr_pc[64] = {false};
-            if (!attr_pc[dev & 63]) {
-#define PCA(E) do { (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 3, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 2 * I_BM * I_BK); \
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 4, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * I_BM * I_BK); \
-                    (void)hipFuncSetAttribute((const void*)gemm_i8_pc_kernel<E, 2, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * I_BM * I_BK); } while (0)
-                PCA(EPI_F16); PCA(EPI_F32); PCA(EPI_SWIGLU);
-#undef PCA
-                attr_pc[dev & 63] = true;
-            }
-#define LPC(E) do { if (pc == 2) hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 2, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); \
-                    else if (pc == 3) hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 3, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); \
-                    else hipLaunchKernelGGL((gemm_i8_pc_kernel<E, 4, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); } while (0)
-            if (epi == EPI_F32) LPC(EPI_F32); else if (epi == EPI_F16) LPC(EPI_F16); else LPC(EPI_SWIGLU);
-#undef LPC
-            return hipGetLastError();
-        }
-        if constexpr (!F8) {
-#define LT(E) hipLaunchKernelGGL((gemm_i8_kernel<E>), grid, dim3(256), lds, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles)
-            if (epi == EPI_F32) LT(EPI_F32); else if (epi == EPI_F16) LT(EPI_F16); else LT(EPI_SWIGLU);
-#undef LT
-        }
+        if (pc != 3 && pc != 4) pc = 2;
+        const size_t lds_pc = (size_t)pc * 2 * I_BM * I_BK;
+        static LdsOptIn once;
+        if (once.first())
+            for_each_epi([](auto E) {
+                set_max_lds(3 * 2 * I_BM * I_BK, gemm_i8_pc_kernel<E, 3, F8>);
+                set_max_lds(4 * 2 * I_BM * I_BK, gemm_i8_pc_kernel<E, 4, F8>);
+                set_max_lds(2 * 2 * I_BM * I_BK, gemm_i8_pc_kernel<E, 2, F8>);
+            });
+        dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles));
+        dispatch_epi(epi, [&](auto E) {
+            dispatch_int<2, 3, 4>(pc, [&](auto ST) {
+                hipLaunchKernelGGL((gemm_i8_pc_kernel<E, ST, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles);
+            });
+        });
         return hipGetLastError();
     }
+    // skinny / generic: one 16-row activation tile per block up to 16 rows (eight K slices while the row tiles are few), else two
     const int nblk = (N + 15) / 16;
-    if (M <= 16) {
-        dim3 grid((unsigned)nblk, 1);
-#define LV(E) do { if (nblk <= 1024) hipLaunchKernelGGL((gemv_i8_kernel<1, E, 8, F8>), grid, dim3(512), 0, s, xq, sx, w, scale, M, N, K, y, ldy); \
-                   else hipLaunchKernelGGL((gemv_i8_kernel<1, E, 4, F8>), grid, dim3(256), 0, s, xq, sx, w, scale, M, N, K, y, ldy); } while (0)
-        if (epi == EPI_F32) LV(EPI_F32); else if (epi == EPI_F16) LV(EPI_F16); else LV(EPI_SWIGLU);
-#undef LV
-        return hipGetLastError();
-    }
-    dim3 grid((unsigned)nblk, (unsigned)((M + 31) / 32));
-#define LV(E) hipLaunchKernelGGL((gemv_i8_kernel<2, E, 4, F8>), grid, dim3(256), 0, s, xq, sx, w, scale, M, N, K, y, ldy)
-    if (epi == EPI_F32) LV(EPI_F32); else if (epi == EPI_F16) LV(EPI_F16); else LV(EPI_SWIGLU);
-#undef LV
+    dim3 grid((unsigned)nblk, M <= 16 ? 1u : (unsigned)((M + 31) / 32));
+    dispatch_epi(epi, [&](auto E) {
+        auto go = [&](auto kernel, unsigned threads) { hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, s, xq, sx, w, scale, M, N, K, y, ldy); };
+        if (M > 16) go(gemv_i8_kernel<2, E, 4, F8>, 256);
+        else if (nblk <= 1024) go(gemv_i8_kernel<1, E, 8, F8>, 512);
+        else go(gemv_i8_kernel<1, E, 4, F8>, 256);
+    });
     return hipGetLastError();
 }
 

@@ -387,14 +387,8 @@ hipError_t launch_linear_w4_pc(hipStream_t s, const uint16_t* x, const void* w, 
         route->add("kernel=gemm_w4_pc_kernel<%s> splits=1 reduce=none order=plain", epi_name(epi));
         if (route->dry) return hipSuccess;
     }
-    static bool attr_dev[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_dev[dev & 63]) {
-        (void)hipFuncSetAttribute((const void*)gemm_w4_pc_kernel<EPI_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS);
-        (void)hipFuncSetAttribute((const void*)gemm_w4_pc_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS);
-        attr_dev[dev & 63] = true;
-    }
+    static LdsOptIn once;
+    if (once.first()) set_max_lds(PC_LDS, gemm_w4_pc_kernel<EPI_F16>, gemm_w4_pc_kernel<EPI_SWIGLU>);
     dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles)), block(512);
     const uint8_t* wq = reinterpret_cast<const uint8_t*>(w);
 #ifdef PC_ABLATE_BUILD

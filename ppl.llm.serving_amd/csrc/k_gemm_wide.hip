@@ -181,28 +181,24 @@ hipError_t launch_linear_w8_wide(hipStream_t s, const uint16_t* x, const int8_t*
         route->add("kernel=gemm_w8_wide_kernel<%s,%d,%d> splits=1 reduce=none order=plain", epi_name(epi), ST, nc);
         if (route->dry) return hipSuccess;
     }
-    static bool attr_dev[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_dev[dev & 63]) {
-#define WD_A(E, C) (void)hipFuncSetAttribute((const void*)gemm_w8_wide_kernel<E, ST, C>, hipFuncAttributeMaxDynamicSharedMemorySize, ST * (WD_XB + 32 * C * G_BK))
-        WD_A(EPI_F16, 12); WD_A(EPI_F32, 12); WD_A(EPI_SWIGLU, 12);
-#undef WD_A
-        attr_dev[dev & 63] = true;
-    }
+    static LdsOptIn once;
+    if (once.first()) set_max_lds(lds, gemm_w8_wide_kernel<EPI_F16, ST, 12>, gemm_w8_wide_kernel<EPI_F32, ST, 12>, gemm_w8_wide_kernel<EPI_SWIGLU, ST, 12>);
     dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles));
 #ifdef WD_ABLATE_BUILD  // diagnosis (wrong results): PPLHIP_GEMM_WIDE_ABLATE = 1 no refills, 2 no conversion, 4 one activation row, 8 no barriers
     static const int abl = getenv("PPLHIP_GEMM_WIDE_ABLATE") ? atoi(getenv("PPLHIP_GEMM_WIDE_ABLATE")) : 0;   // (an ablation build reads its switch itself: no TUNING=1 needed)
-#define WD_AB(A) if (abl == A) { (void)hipFuncSetAttribute((const void*)gemm_w8_wide_kernel<EPI_F16, ST, 12, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((gemm_w8_wide_kernel<EPI_F16, ST, 12, A>), grid, dim3((12 + WD_NP) * 64), lds, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles); return hipGetLastError(); }
-    WD_AB(1) WD_AB(2) WD_AB(3) WD_AB(4) WD_AB(6) WD_AB(7) WD_AB(8) WD_AB(15)
-#undef WD_AB
+    bool ablated = true;
+    dispatch_int<1, 2, 3, 4, 6, 7, 8, 15, 0>(abl, [&](auto A) {
+        if constexpr (A == 0) ablated = false;
+        else {
+            set_max_lds(lds, gemm_w8_wide_kernel<EPI_F16, ST, 12, A>);
+            hipLaunchKernelGGL((gemm_w8_wide_kernel<EPI_F16, ST, 12, A>), grid, dim3((12 + WD_NP) * 64), lds, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles);
+        }
+    });
+    if (ablated) return hipGetLastError();
 #endif
-#define WD_L(E, C) hipLaunchKernelGGL((gemm_w8_wide_kernel<E, ST, C>), grid, dim3((C + WD_NP) * 64), lds, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles)
-#define WD_E(C) do { if (epi == EPI_F32) WD_L(EPI_F32, C); else if (epi == EPI_F16) WD_L(EPI_F16, C); else WD_L(EPI_SWIGLU, C); } while (0)
-    WD_E(12);
-#undef WD_E
-#undef WD_L
+    dispatch_epi(epi, [&](auto E) {
+        hipLaunchKernelGGL((gemm_w8_wide_kernel<E, ST, 12>), grid, dim3((12 + WD_NP) * 64), lds, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles);
+    });
     return hipGetLastError();
 }
 

@@ -203,10 +203,6 @@ hipError_t launch_gemv_stream(hipStream_t s, const uint16_t* x, const void* w, c
     const int nb = waves16 >= 2048 ? 2 : 1;
     const int rows = (nw / nwk) * nb * GV_U;
     dim3 grid((unsigned)((N + rows - 1) / rows)), block(nw * 64);
-#define GV_L(WQ, MM, E, W) hipLaunchKernelGGL((gemv_stream_kernel<WQ, MM, E, W>), grid, block, 0, s, x, w, scale, N, K, group, y, ldy, nwk_log2, npw, nb)
-#define GV_P(WQ, MM, E) do { if (nw == 4) GV_L(WQ, MM, E, 4); else GV_L(WQ, MM, E, 8); } while (0)
-#define GV_E(WQ, MM) do { if (epi == EPI_F32) GV_P(WQ, MM, EPI_F32); else if (epi == EPI_F16) GV_P(WQ, MM, EPI_F16); else GV_P(WQ, MM, EPI_SWIGLU); } while (0)
-#define GV_M(WQ) do { if (M == 1) GV_E(WQ, 1); else if (M == 2) GV_E(WQ, 2); else if (M == 3) GV_E(WQ, 3); else GV_E(WQ, 4); } while (0)
     if (M < 1 || M > 4 || npw > 3) return hipErrorInvalidValue;
     if (wq_bit != 8 && wq_bit != 4 && wq_bit != 0) return hipErrorInvalidValue;
     if (route) {
@@ -214,11 +210,15 @@ hipError_t launch_gemv_stream(hipStream_t s, const uint16_t* x, const void* w, c
         route->add("splits=1 reduce=none order=plain nwk=%d nb=%d", nwk, nb);
         if (route->dry) return hipSuccess;
     }
-    if (wq_bit == 8) GV_M(8); else if (wq_bit == 4) GV_M(4); else if (wq_bit == 0) GV_M(0); else return hipErrorInvalidValue;
-#undef GV_M
-#undef GV_E
-#undef GV_P
-#undef GV_L
+    dispatch_int<8, 4, 0>(wq_bit, [&](auto WQ) {
+        dispatch_int<1, 2, 3, 4>((int)M, [&](auto MM) {
+            dispatch_epi(epi, [&](auto E) {
+                dispatch_int<4, 8>(nw, [&](auto NW) {
+                    hipLaunchKernelGGL((gemv_stream_kernel<WQ, MM, E, NW>), grid, block, 0, s, x, w, scale, N, K, group, y, ldy, nwk_log2, npw, nb);
+                });
+            });
+        });
+    });
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times pplhip_op_linear_i8 (online_i8i8 GEMM, quantiser not included) on the four linear shapes of a LLaMA-2-7B layer.
-usage: python profiles/gemm_i8_microbench.py [M]      (PPLHIP_GEMM_I8_VARIANT selects the tile-kernel variant)"""
+usage: python profiles/gemm_i8_microbench.py [M]      (a TUNING=1 build reads PPLHIP_GEMM_I8_PC = 2 / 3 / 4, the ring depth of the 128 x 128
+producer / consumer kernel, PPLHIP_GEMM_I8_WIDE = 0 and PPLHIP_GEMM_I8_256_MIN_M; the product build reads none of them)"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
