@@ -33,22 +33,23 @@ __global__ void attn_decode_kernel(const uint16_t* __restrict__ qkv, KvAddr kv, 
                               (int64_t)blockIdx.y, (int)blockIdx.z, (int)(blockDim.x >> 6), smem);
 }
 
-// split-K reduce: one wave per (request, head)
+// split reduce: one block per (row, head) of the workspace ([row][head][split][D + 2] floats), one thread per channel
 template <int D>
 __global__ void attn_decode_reduce_kernel(const float* __restrict__ workspace, int split, uint16_t* __restrict__ out) {
     const int64_t bh = blockIdx.x;
     const float* ws = workspace + bh * (int64_t)split * (D + 2);
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
-        float mm = -1e30f;
-        for (int s = 0; s < split; ++s) mm = fmaxf(mm, ws[s * (D + 2) + D]);
-        float ll = 0.f, o = 0.f;
-        for (int s = 0; s < split; ++s) {
-            const float a = __expf(ws[s * (D + 2) + D] - mm);
-            ll = fmaf(ws[s * (D + 2) + D + 1], a, ll);
-            o = fmaf(ws[s * (D + 2) + d], a, o);
-        }
-        out[bh * D + d] = f2h(o / ll);
+        const LseRow r = lse_merge(ws, split, D + 2, D, d);
+        out[bh * D + d] = f2h(r.o / r.l);
     }
+}
+
+hipError_t launch_attn_reduce(hipStream_t s, const float* ws, int nsplit, int64_t n_row_heads, int D, uint16_t* out) {
+    if (D != 128 && D != 64 && D != 32) return hipErrorInvalidValue;
+    dispatch_int<128, 64, 32>(D, [&](auto DD) {
+        hipLaunchKernelGGL((attn_decode_reduce_kernel<DD>), dim3((unsigned)n_row_heads), dim3(DD < 64 ? 64 : DD), 0, s, ws, nsplit, out);
+    });
+    return hipGetLastError();
 }
 
 size_t attn_decode_workspace_bytes(int64_t nb, int H, int D, int split) {
@@ -70,14 +71,9 @@ static hipError_t launch_decode_t(hipStream_t s, const uint16_t* qkv, const KvAd
     else
         hipLaunchKernelGGL((attn_decode_kernel<QBIT, D>), dim3(H, (unsigned)nb, split), dim3(threads), lds, s, qkv, kv,
                            seq_starts, start_pos, cache_indices, max_pages, H, Hkv, split, workspace, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (split > 1) {
-        hipLaunchKernelGGL((attn_decode_reduce_kernel<D>), dim3((unsigned)(nb * H)), dim3(D < 64 ? 64 : D), 0, s,
-                           workspace, split, out);
-        e = hipGetLastError();
-    }
-    return e;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || split == 1) return e;
+    return launch_attn_reduce(s, workspace, split, nb * H, D, out);
 }
 
 hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
@@ -90,26 +86,23 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
     if (threads < 64 || threads > 64 * DEC_MAX_WAVES || threads % 64) return hipErrorInvalidValue;
     if (threads < D) threads = D;  // the final merge uses one thread per channel
     if (split < 1) split = 1;
-    // grouped-query models: the MFMA kernel (k_attn_prefill.hip) reads each KV row once for the whole head group
+    // grouped-query models: the MFMA kernel (k_attn_decode_gqa.hip) reads each KV row once for the whole head group
     static const bool no_gqa = tune_set("PPLHIP_ATTN_NOGQA");
     if (attn_decode_gqa_supported(kv_fmt, H, Hkv, D) && !no_gqa) {
         hipError_t e = launch_attn_decode_gqa(s, qkv, kv, kv_fmt, seq_starts, start_pos, cache_indices, max_pages, nb, H,
                                               Hkv, D, split, workspace, out, t0, t1);
         if (e != hipSuccess || split == 1) return e;
-        const dim3 rg((unsigned)(nb * H)), rb(D < 64 ? 64 : D);
-        if (D == 128) hipLaunchKernelGGL((attn_decode_reduce_kernel<128>), rg, rb, 0, s, workspace, split, out);
-        else if (D == 64) hipLaunchKernelGGL((attn_decode_reduce_kernel<64>), rg, rb, 0, s, workspace, split, out);
-        else hipLaunchKernelGGL((attn_decode_reduce_kernel<32>), rg, rb, 0, s, workspace, split, out);
-        return hipGetLastError();
+        return launch_attn_reduce(s, workspace, split, nb * H, D, out);
     }
-#define DEC_CASE(QB, DD)                                                                                            \
-    if (kv_fmt == QB && D == DD)                                                                                    \
-        return launch_decode_t<QB, DD>(s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, nb, H, Hkv,     \
-                                       split, threads, workspace, out, t0, t1);
-    DEC_CASE(8, 128) DEC_CASE(0, 128) DEC_CASE(8, 64) DEC_CASE(0, 64) DEC_CASE(8, 32) DEC_CASE(0, 32)
-    DEC_CASE(KV_FP8, 128) DEC_CASE(KV_FP8, 64) DEC_CASE(KV_FP8, 32)
-#undef DEC_CASE
-    return hipErrorInvalidValue;
+    if ((kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8) || (D != 128 && D != 64 && D != 32)) return hipErrorInvalidValue;
+    hipError_t e = hipSuccess;
+    dispatch_int<KV_I8G8, KV_FP16, KV_FP8>(kv_fmt, [&](auto QB) {
+        dispatch_int<128, 64, 32>(D, [&](auto DD) {
+            e = launch_decode_t<QB, DD>(s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, nb, H, Hkv, split, threads, workspace,
+                                        out, t0, t1);
+        });
+    });
+    return e;
 }
 
 }  // namespace pplhip

@@ -2,18 +2,9 @@
 // wraps it into the kernel (the body is a header so that probes can run it inside other launches).  Design notes:
 // k_attn_decode.hip.
 #pragma once
-#include "kernels.h"
+#include "k_attn_dev.h"
 
 namespace pplhip {
-
-template <int QBIT, int D>
-struct DecodeCfg {
-    static constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;   // int8 and fp8: one byte per channel
-    static constexpr int CH = 16 / ELT;       // channels per lane
-    static constexpr int LPT = D / CH;        // lanes per token row
-    static constexpr int TPW = 64 / LPT;      // token rows per wave-load
-    static constexpr int NG = CH / 8;         // int8: quant groups per lane (group = 8 channels); fp8: one scale per row
-};
 
 constexpr int DEC_UNROLL = 4;
 constexpr int DEC_MAX_WAVES = 8;
@@ -24,7 +15,7 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                                                  const int64_t* __restrict__ start_pos, const int64_t* __restrict__ cache_indices,
                                                  int64_t max_pages, int H, int Hkv, int split, float* __restrict__ workspace,
                                                  uint16_t* __restrict__ out, int hq, int64_t b, int sp, int nw, float* smem) {
-    using C = DecodeCfg<QBIT, D>;
+    using C = AttnCfg<QBIT, D>;   // a lane holds one 16-byte piece of a row: CH channels
     constexpr int CH = C::CH, LPT = C::LPT, TPW = C::TPW;
     // smem: [nw][D + 2] floats, provided by the caller
 
@@ -70,11 +61,10 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
 #pragma unroll
     for (int gi = 0; gi < (C::NG > 0 ? C::NG : 1); ++gi) vcorr[gi] = 0.f;
 
-    const char* kbase = reinterpret_cast<const char*>(kv.cache) + ((int64_t)hk * kv.sH + ch0) * C::ELT;
-    const char* vbase = kbase + kv.sKV * C::ELT;
-    const uint16_t* ksbase = kv.scale + (int64_t)hk * kv.ssH + (QBIT == 8 ? ch0 / 8 : 0);
-    const uint16_t* vsbase = ksbase + kv.ssKV;
-    const int64_t row_bytes = kv.sN * C::ELT;
+    const KvHead kh = kv_head<QBIT>(kv, hk, ch0);
+    const char *const kbase = kh.kbase, *const vbase = kh.vbase;
+    const uint16_t *const ksbase = kh.ksbase, *const vsbase = kh.vsbase;
+    const int64_t row_bytes = kh.rowb;
 
     // Paged cache, power-of-two pages: the wave keeps 64 consecutive page ids of the request in ONE register (lane j: page pg0 + j) and
     // looks them up with ds_bpermute, instead of a dependent page-table load in front of every group of KV loads.  The window moves
@@ -116,15 +106,15 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
             vraw[u] = kv_stream_load(reinterpret_cast<const uint4*>(vbase + slot * row_bytes));
             if constexpr (QBIT == 8) {
                 if constexpr (C::NG == 2) {
-                    ksc[u] = kv_stream_load(reinterpret_cast<const uint32_t*>(ksbase + slot * kv.ssN));
-                    vsc[u] = kv_stream_load(reinterpret_cast<const uint32_t*>(vsbase + slot * kv.ssN));
+                    ksc[u] = kv_stream_load(reinterpret_cast<const uint32_t*>(ksbase + slot * kh.srow));
+                    vsc[u] = kv_stream_load(reinterpret_cast<const uint32_t*>(vsbase + slot * kh.srow));
                 } else {
-                    ksc[u] = ksbase[slot * kv.ssN];
-                    vsc[u] = vsbase[slot * kv.ssN];
+                    ksc[u] = ksbase[slot * kh.srow];
+                    vsc[u] = vsbase[slot * kh.srow];
                 }
             } else if constexpr (QBIT == KV_FP8) {  // the row's 2^e
-                ksc[u] = ksbase[slot * kv.ssN];
-                vsc[u] = vsbase[slot * kv.ssN];
+                ksc[u] = ksbase[slot * kh.srow];
+                vsc[u] = vsbase[slot * kh.srow];
             }
         }
         float s[DEC_UNROLL];
@@ -239,20 +229,13 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
     __syncthreads();
     if (threadIdx.x < D) {
         const int d = threadIdx.x;
-        float mm = -1e30f;
-        for (int w = 0; w < nw; ++w) mm = fmaxf(mm, smem[w * (D + 2) + D]);
-        float ll = 0.f, o = 0.f;
-        for (int w = 0; w < nw; ++w) {
-            const float a = __expf(smem[w * (D + 2) + D] - mm);
-            ll = fmaf(smem[w * (D + 2) + D + 1], a, ll);
-            o = fmaf(smem[w * (D + 2) + d], a, o);
-        }
+        const LseRow r = lse_merge(smem, nw, D + 2, D, d);
         if (split == 1) {
-            out[(b * H + hq) * (int64_t)D + d] = f2h(o / ll);
+            out[(b * H + hq) * (int64_t)D + d] = f2h(r.o / r.l);
         } else {
             float* ws = workspace + ((b * H + hq) * (int64_t)split + sp) * (D + 2);
-            ws[d] = o;
-            if (d == 0) { ws[D] = mm; ws[D + 1] = ll; }
+            ws[d] = r.o;
+            if (d == 0) { ws[D] = r.m; ws[D + 1] = r.l; }
         }
     }
 }

@@ -28,11 +28,8 @@
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
 #include <mutex>
-#include <set>
-#include <type_traits>
-#include <utility>
 #include <hip/hip_ext.h>
-#include "kernels.h"
+#include "k_attn_dev.h"
 
 namespace pplhip {
 
@@ -60,17 +57,6 @@ constexpr int GQ_WAVES_BIG = GQ_THREADS_N / 64, GQ_WAVES_SMALL = 4;
 #ifndef GQ_V_EXACT
 #define GQ_V_EXACT 1
 #endif
-constexpr int GQ_VSUB = 272;  // halfs per [16 keys][16 channels] V sub-tile in LDS: 256 + 16 of skew (bank spread of the writes)
-
-typedef short gq_s4 __attribute__((__vector_size__(4 * sizeof(short))));
-// transposing LDS read of a row-major [16 keys][16 channels] fp16 sub-tile: lane (channel l15, quarter kq) receives keys
-// kq*4 .. kq*4+3 of channel l15 (lane semantics pinned by profiles/probes/lds_tr_read_probe.hip)
-__device__ __forceinline__ uint2 gq_v_frag(const uint16_t* sub, int kq, int l15) {
-    const uint16_t* p = sub + (kq * 4 + (l15 >> 2)) * 16 + (l15 & 3) * 4;
-    const gq_s4 w = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gq_s4*)p);
-    return __builtin_bit_cast(uint2, w);
-}
-
 __device__ __forceinline__ h8 splat8(_Float16 v) { return h8{v, v, v, v, v, v, v, v}; }
 
 // exact product q * s of 8 small integers (fp16-exact) and an fp16 scale as hi + lo
@@ -83,7 +69,7 @@ __device__ __forceinline__ void two_product(h8 q, _Float16 s, h8& hi, h8& lo) {
 template <int QBIT, int D, int GQ_WAVES>
 constexpr int gq_lds_bytes() {
     constexpr int nimg = (QBIT == 8 && GQ_V_EXACT) ? 2 : 1;
-    constexpr int v_bytes = GQ_WAVES * 2 * nimg * (D / 16) * GQ_VSUB * 2, merge_bytes = GQ_WAVES * 16 * (D + 2) * 4;
+    constexpr int v_bytes = GQ_WAVES * 2 * nimg * (D / 16) * ATT_VSUB * 2, merge_bytes = GQ_WAVES * 16 * (D + 2) * 4;
     return v_bytes > merge_bytes ? v_bytes : merge_bytes;
 }
 
@@ -94,14 +80,13 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                                                                      const int64_t* __restrict__ cache_indices,
                                                                      int64_t max_pages, int H, int Hkv, int split,
                                                                      float* __restrict__ workspace, uint16_t* __restrict__ out) {
-    constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;
-    constexpr int CH = 16 / ELT;        // channels in one 16-byte piece
-    constexpr int LPT = D / CH;         // pieces per row
+    using C = AttnCfg<QBIT, D>;
+    constexpr int CH = C::CH, LPT = C::LPT;   // channels in one 16-byte piece, pieces per row
     constexpr int PPL = LPT / 4;        // pieces per lane and 16-key sub-tile (K and V alike)
     constexpr int KSTEPS = D / 32;
     constexpr int DT = D / 16;
     constexpr int NIMG = (QBIT == 8 && GQ_V_EXACT) ? 2 : 1;           // V images in LDS: hi (+ lo)
-    constexpr int VW = DT * GQ_VSUB;                  // halfs of one image of one wave's 16-key sub-tile
+    constexpr int VW = DT * ATT_VSUB;                  // halfs of one image of one wave's 16-key sub-tile
     static_assert(LPT % 4 == 0, "a row must hold a multiple of four 16-byte pieces");
     static_assert(GQ_NBUF == 2 || GQ_NBUF == 4, "a wave consumes its sub-tiles in pairs: register buffers (0, 1)[, (2, 3)]");
     extern __shared__ __attribute__((aligned(16))) char smem[];   // gq_lds_bytes<QBIT, D>(): per wave two sub-tiles' V image(s); the merge buffer overlays them
@@ -138,6 +123,9 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
     const float sm_scale = 1.0f / sqrtf((float)D);
 
     const int64_t slot0 = MODE == 0 ? cache_indices[b] : 0;
+    // (kv_head's own text, like the fp8 conversions below: this kernel is issue-bound and must keep its instruction stream -- through
+    // the helpers the fp16 and fp8 instantiations came out reordered, two of them one s_waitcnt / s_nop apart)
+    constexpr int ELT = C::ELT;
     const char* kbase = reinterpret_cast<const char*>(kv.cache) + (int64_t)hk * kv.sH * ELT;
     const char* vbase = kbase + kv.sKV * ELT;
     const uint16_t* ksbase = kv.scale + (int64_t)hk * kv.ssH;
@@ -230,30 +218,32 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
         constexpr int P = decltype(ptag)::value;
 #pragma unroll
         for (int j = 0; j < PPL; ++j) {
+            // (ATT_V_OFF's own text for a single 16-key sub-tile: its key >> 4 term, always 0 here, cost instructions)
             const int key = vkey_l[j], ch0 = vpc_l[j] * CH;
-            if constexpr (QBIT == 8) {
-                const h8 q0 = cvt_i8x8_f16(make_uint2(vraw[P][j].x, vraw[P][j].y)), q1 = cvt_i8x8_f16(make_uint2(vraw[P][j].z, vraw[P][j].w));
+            if constexpr (QBIT == 8 && GQ_V_EXACT) {   // exact hi + lo images: not dequant_piece, which rounds q * scale once
+                h8 q[2], hi0, lo0, hi1, lo1;
+                cvt_i8x16_f16(vraw[P][j], q);
                 const h2 sc = __builtin_bit_cast(h2, vsc[P][j]);
-                uint16_t* dst = dstw + (ch0 >> 4) * GQ_VSUB + key * 16;  // CH = 16: the piece is one whole sub-tile row
-                if constexpr (GQ_V_EXACT) {
-                    h8 hi0, lo0, hi1, lo1;
-                    two_product(q0, sc[0], hi0, lo0);
-                    two_product(q1, sc[1], hi1, lo1);
-                    *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, hi0);
-                    *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, hi1);
-                    *reinterpret_cast<uint4*>(dst + VW) = __builtin_bit_cast(uint4, lo0);
-                    *reinterpret_cast<uint4*>(dst + VW + 8) = __builtin_bit_cast(uint4, lo1);
-                } else {
-                    *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, q0 * splat8(sc[0]));
-                    *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, q1 * splat8(sc[1]));
-                }
-            } else if constexpr (QBIT == KV_FP8) {  // exact fp16: the hi image alone
+                uint16_t* dst = dstw + (ch0 >> 4) * ATT_VSUB + key * 16;
+                two_product(q[0], sc[0], hi0, lo0);
+                two_product(q[1], sc[1], hi1, lo1);
+                *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, hi0);
+                *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, hi1);
+                *reinterpret_cast<uint4*>(dst + VW) = __builtin_bit_cast(uint4, lo0);
+                *reinterpret_cast<uint4*>(dst + VW + 8) = __builtin_bit_cast(uint4, lo1);
+            } else if constexpr (QBIT == 8) {   // GQ_V_EXACT 0: the hi image alone, int8 x scale rounded once
+                h8 v[2];
+                dequant_piece<QBIT>(vraw[P][j], vsc[P][j], v);
+                uint16_t* dst = dstw + (ch0 >> 4) * ATT_VSUB + key * 16;
+                *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, v[0]);
+                *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, v[1]);
+            } else if constexpr (QBIT == KV_FP8) {   // exact fp16, the hi image alone (dequant_piece's own text: see kbase above)
                 const float sc = h2f((uint16_t)vsc[P][j]);
-                uint16_t* dst = dstw + (ch0 >> 4) * GQ_VSUB + key * 16;
+                uint16_t* dst = dstw + (ch0 >> 4) * ATT_VSUB + key * 16;
                 *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, cvt_fp8x8_f16(make_uint2(vraw[P][j].x, vraw[P][j].y), sc));
                 *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, cvt_fp8x8_f16(make_uint2(vraw[P][j].z, vraw[P][j].w), sc));
             } else {
-                *reinterpret_cast<uint4*>(dstw + (ch0 >> 4) * GQ_VSUB + key * 16 + (ch0 & 15)) = vraw[P][j];
+                *reinterpret_cast<uint4*>(dstw + (ch0 >> 4) * ATT_VSUB + key * 16 + (ch0 & 15)) = vraw[P][j];
             }
         }
     };
@@ -264,17 +254,17 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
 #pragma unroll
         for (int j = 0; j < PPL; ++j) {
             if constexpr (QBIT == 8) {
-                const h8 q0 = cvt_i8x8_f16(make_uint2(kraw[P][j].x, kraw[P][j].y)), q1 = cvt_i8x8_f16(make_uint2(kraw[P][j].z, kraw[P][j].w));
+                h8 q[2], hi0, lo0, hi1, lo1;   // exact hi + lo: not dequant_piece
+                cvt_i8x16_f16(kraw[P][j], q);
                 const h2 sc = __builtin_bit_cast(h2, ksc[P][j]);
-                h8 hi0, lo0, hi1, lo1;
-                two_product(q0, sc[0], hi0, lo0);
-                two_product(q1, sc[1], hi1, lo1);
+                two_product(q[0], sc[0], hi0, lo0);
+                two_product(q[1], sc[1], hi1, lo1);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(lo0, qf[2 * j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(lo1, qf[2 * j + 1], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi0, qf[2 * j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi1, qf[2 * j + 1], sacc, 0, 0, 0);
             } else if constexpr (QBIT == KV_FP8) {
-                const float sc = h2f((uint16_t)ksc[P][0]);
+                const float sc = h2f((uint16_t)ksc[P][0]);   // (dequant_piece's own text)
                 const h8 k0 = cvt_fp8x8_f16(make_uint2(kraw[P][j].x, kraw[P][j].y), sc), k1 = cvt_fp8x8_f16(make_uint2(kraw[P][j].z, kraw[P][j].w), sc);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, qf[2 * j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, qf[2 * j + 1], sacc, 0, 0, 0);
@@ -315,7 +305,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
             const float e0 = (k0 < tend) ? __expf(s0[r] - mnew) : 0.f;
             const float e1 = (k1 < tend) ? __expf(s1[r] - mnew) : 0.f;
             rs += e0 + e1;
-            const _Float16 h0 = to_h(e0), h1 = to_h(e1);
+            const _Float16 h0 = to_h(e0), h1 = to_h(e1);   // hi rounded to NEAREST: other arithmetic than the prefill kernels' p_hi_lo (truncation)
             p_hi[r] = h0; p_hi[4 + r] = h1;
             p_lo[r] = to_h(e0 - (float)h0);       // the part of p that fp16 dropped
             p_lo[4 + r] = to_h(e1 - (float)h1);
@@ -338,9 +328,9 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-            const uint2 a = gq_v_frag(vw + dt * GQ_VSUB, kq, l15), b = gq_v_frag(vw1 + dt * GQ_VSUB, kq, l15);  // keys kq*4 .. +4 of channel dt*16 + l15, both sub-tiles
+            const uint2 a = v_frag_tr(vw + dt * ATT_VSUB, 4 * kq, l15), b = v_frag_tr(vw1 + dt * ATT_VSUB, 4 * kq, l15);  // keys kq*4 .. +4 of channel dt*16 + l15, both sub-tiles
             if constexpr (QBIT == 8 && GQ_V_EXACT) {
-                const uint2 al = gq_v_frag(vw + VW + dt * GQ_VSUB, kq, l15), bl = gq_v_frag(vw1 + VW + dt * GQ_VSUB, kq, l15);
+                const uint2 al = v_frag_tr(vw + VW + dt * ATT_VSUB, 4 * kq, l15), bl = v_frag_tr(vw1 + VW + dt * ATT_VSUB, 4 * kq, l15);
                 const h8 vl = __builtin_bit_cast(h8, make_uint4(al.x, al.y, bl.x, bl.y));
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(p_lo, vl, o[dt], 0, 0, 0);
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(p_hi, vl, o[dt], 0, 0, 0);
@@ -388,38 +378,19 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
     __syncthreads();
     for (int idx = threadIdx.x; idx < grp * D; idx += GQ_WAVES * 64) {
         const int head = idx / D, d = idx - head * D;
-        float mm = -1e30f;
-        for (int w = 0; w < GQ_WAVES; ++w) mm = fmaxf(mm, mg[(w * 16 + head) * (D + 2) + D]);
-        float ll = 0.f, ov = 0.f;
-        for (int w = 0; w < GQ_WAVES; ++w) {
-            const float* row = mg + (w * 16 + head) * (D + 2);
-            const float a = __expf(row[D] - mm);
-            ll = fmaf(row[D + 1], a, ll);
-            ov = fmaf(row[d], a, ov);
-        }
+        const LseRow r = lse_merge(mg + head * (D + 2), GQ_WAVES, 16 * (D + 2), D, d);   // the waves' rows of this head
         const int hq = hk * grp + head;
         if (split == 1) {
-            out[(b * H + hq) * (int64_t)D + d] = f2h(ov / ll);
+            out[(b * H + hq) * (int64_t)D + d] = f2h(r.o / r.l);
         } else {
             float* ws = workspace + ((b * H + hq) * (int64_t)split + sp_i) * (D + 2);
-            ws[d] = ov;
-            if (d == 0) { ws[D] = mm; ws[D + 1] = ll; }
+            ws[d] = r.o;
+            if (d == 0) { ws[D] = r.m; ws[D + 1] = r.l; }
         }
     }
 }
 
 }  // namespace
-
-// more than 64 KiB of LDS per block (two sub-tiles' exact V images per wave): the attribute belongs to the function on the current device
-static void gq_set_lds(const void* fn, int bytes) {
-    if (bytes <= 65536) return;
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> done;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> g(mu);
-    if (done.insert({fn, dev}).second) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
 
 bool attn_decode_gqa_supported(int kv_fmt, int H, int Hkv, int D) {
     if (Hkv <= 0 || H % Hkv) return false;
@@ -438,26 +409,34 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
     dim3 grid((unsigned)Hkv, (unsigned)nb, (unsigned)split);
     static const int small_min = getenv("PPLHIP_GQA_SMALL_BLOCK_MIN") ? atoi(getenv("PPLHIP_GQA_SMALL_BLOCK_MIN")) : GQ_SMALL_BLOCK_MIN;   // A/B runs
     const bool small = (int64_t)Hkv * nb * split >= small_min;
-#define GQ_LAUNCH(QB, DD, MD, NW)                                                                                                 \
-    do {                                                                                                                          \
-        gq_set_lds((const void*)attn_decode_gqa_kernel<QB, DD, MD, NW>, gq_lds_bytes<QB, DD, NW>());                             \
-        if (t0 && t1)                                                                                                             \
-            hipExtLaunchKernelGGL((attn_decode_gqa_kernel<QB, DD, MD, NW>), grid, dim3(NW * 64), (gq_lds_bytes<QB, DD, NW>()), s, t0, t1, 0, qkv, kv, \
-                                  seq_starts, start_pos, cache_indices, max_pages, H, Hkv, split, workspace, out);               \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((attn_decode_gqa_kernel<QB, DD, MD, NW>), grid, dim3(NW * 64), (gq_lds_bytes<QB, DD, NW>()), s, qkv, kv, seq_starts, \
-                               start_pos, cache_indices, max_pages, H, Hkv, split, workspace, out);                              \
-    } while (0)
-#define GQ_CASE(QB, DD)                                                                                          \
-    if (kv_fmt == QB && D == DD) {                                                                               \
-        if (small) { if (kv.mode == 0) GQ_LAUNCH(QB, DD, 0, GQ_WAVES_SMALL); else GQ_LAUNCH(QB, DD, 1, GQ_WAVES_SMALL); } \
-        else { if (kv.mode == 0) GQ_LAUNCH(QB, DD, 0, GQ_WAVES_BIG); else GQ_LAUNCH(QB, DD, 1, GQ_WAVES_BIG); }   \
-        return hipGetLastError();                                                                                \
-    }
-    GQ_CASE(8, 128) GQ_CASE(0, 128) GQ_CASE(8, 64) GQ_CASE(0, 64) GQ_CASE(0, 32) GQ_CASE(KV_FP8, 128) GQ_CASE(KV_FP8, 64)
-#undef GQ_CASE
-#undef GQ_LAUNCH
-    return hipErrorInvalidValue;
+    hipError_t unbuilt = hipSuccess;   // a (format, head_dim) the supported set admits but no kernel is built for: an error, never a no-op
+    dispatch_int<KV_I8G8, KV_FP16, KV_FP8>(kv_fmt, [&](auto QB) {
+        dispatch_int<128, 64, 32>(D, [&](auto DD) {
+            if constexpr (QB == KV_FP16 || DD != 32) {
+                dispatch_int<0, 1>(kv.mode, [&](auto MD) {
+                    dispatch_int<GQ_WAVES_SMALL, GQ_WAVES_BIG>(small ? GQ_WAVES_SMALL : GQ_WAVES_BIG, [&](auto NW) {
+                        const auto kernel = attn_decode_gqa_kernel<QB, DD, MD, NW>;
+                        constexpr int lds = gq_lds_bytes<QB, DD, NW>();
+                        if constexpr (lds > 65536) {   // two sub-tiles' exact V images per wave; once per (instantiation, device)
+                            static std::mutex mu;      // (host threads may launch the same instantiation for the first time together)
+                            static LdsOptIn once;
+                            std::lock_guard<std::mutex> g(mu);
+                            if (once.first()) set_max_lds(lds, kernel);
+                        }
+                        if (t0 && t1)
+                            hipExtLaunchKernelGGL(kernel, grid, dim3(NW * 64), lds, s, t0, t1, 0, qkv, kv, seq_starts, start_pos, cache_indices,
+                                                  max_pages, H, Hkv, split, workspace, out);
+                        else
+                            hipLaunchKernelGGL(kernel, grid, dim3(NW * 64), lds, s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, H,
+                                               Hkv, split, workspace, out);
+                    });
+                });
+            } else {
+                unbuilt = hipErrorInvalidValue;   // int8 / fp8 with head_dim 32: a row holds fewer than four 16-byte pieces
+            }
+        });
+    });
+    return unbuilt != hipSuccess ? unbuilt : hipGetLastError();
 }
 
 }  // namespace pplhip

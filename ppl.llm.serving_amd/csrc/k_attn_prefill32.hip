@@ -15,7 +15,7 @@
 //   16-row kernel (DESIGN.md numerics).
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
-#include "kernels.h"
+#include "k_attn_dev.h"
 
 namespace pplhip {
 
@@ -27,21 +27,14 @@ constexpr int P3_BN = 64, P3_D = 128;
 // MODEL-level distance to the oracle where the margin is thinnest -- 32-layer 7B logits 1.14e-2 -> 1.35e-2 (1.03 -> 1.22 x the noise floor,
 // bar 1.3), config 5's cache-prefill step 1.05e-3 -> 1.17e-3 (1.5 x its floor); profiles/r05_parity_prefill_p_{exact,rounded}.jsonl -- the same
 // trade that the grouped-query decode kernel's rounded V turned out to be (k_attn_decode_gqa.hip).  Precision first: ~5 % of a cold TTFT.
-constexpr int P3_VSUB = 272;  // halfs per [16 keys][16 channels] V sub-tile: 256 + 16 of skew
-constexpr int P3_KS_HALFS = P3_BN * P3_D, P3_VS_HALFS = (P3_BN / 16) * (P3_D / 16) * P3_VSUB;
+constexpr int P3_KS_HALFS = P3_BN * P3_D, P3_VS_HALFS = (P3_BN / 16) * (P3_D / 16) * ATT_VSUB;
 typedef float f16v __attribute__((ext_vector_type(16)));
-typedef short p3_s4 __attribute__((__vector_size__(4 * sizeof(short))));
 
-__device__ __forceinline__ uint2 p3_v_frag(const uint16_t* sub, int r0, int l15) {
-    const uint16_t* p = sub + (r0 + (l15 >> 2)) * 16 + (l15 & 3) * 4;
-    const p3_s4 w = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) p3_s4*)p);
-    return __builtin_bit_cast(uint2, w);
-}
 __device__ __forceinline__ int crow(int i, int hi) { return (i & 3) + 8 * (i >> 2) + 4 * hi; }
 
 // SPLIT: the block handles the KV tiles of split blockIdx.y of gridDim.y only and writes unnormalised partial rows (O, m, l) to `ws`
 // ([token row - ws_row0][head][split][D + 2] floats, the layout of the decode kernels: the workspace holds the launch's own rows only,
-// whatever decode rows or earlier chunks precede them in the step); attn_prefill32_reduce_kernel merges them.  For short new
+// whatever decode rows or earlier chunks precede them in the step); launch_attn_reduce merges them.  For short new
 // suffixes behind a long cached prefix (a prefix-cache hit recomputes one page): a request is otherwise H blocks walking thousands of keys.
 template <int QBIT, int MODE, int NW, int ABL = 0, int SPLIT = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_prefill32_kernel(const uint16_t* __restrict__ qkv, KvAddr kv,
@@ -52,31 +45,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                                                                     float* __restrict__ ws, int64_t ws_row0) {
     constexpr int D = P3_D;
     constexpr int P3_BM = NW * 32, P3_THREADS = NW * 64;  // NW waves x 32 query rows share the staged K / V tiles
-    constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;
-    constexpr int CH = 16 / ELT;                 // channels in one 16-byte piece
-    constexpr int LPT = D / CH;                  // pieces per row: 8 (int8) / 16 (fp16)
+    using C = AttnCfg<QBIT, D>;
+    constexpr int CH = C::CH, LPT = C::LPT;      // channels in one 16-byte piece; pieces per row: 8 (int8, fp8) / 16 (fp16)
     constexpr int IPT = P3_BN * LPT / P3_THREADS;  // (key, piece) items per thread and matrix: 2 / 4 (4 waves), 1 / 2 (8 waves)
     constexpr int KSTEPS = D / 16;               // 8 k-steps of the 32x32x16 MFMA over the head dimension
     __shared__ __attribute__((aligned(16))) uint16_t smem[2 * (P3_KS_HALFS + P3_VS_HALFS)];
 
-    // 1-D grid, XCD-aware: consecutive workgroup ids go round-robin over the 8 XCDs (each with its own 4 MiB L2), so XCD x takes the
-    // H / 8 consecutive query heads x H/8 .. (same KV head under grouped-query attention) and walks them one after the other, each head's
-    // query blocks heaviest (last) first: what an XCD runs at any moment reads ONE head's K / V, which then lives in its L2
     int hq, qb, r;
-    {
-        const int L = blockIdx.x, per = nqb * nreq;
-        int rem;
-        if ((H & 7) == 0) {
-            const int j = L >> 3;
-            hq = (L & 7) * (H >> 3) + j / per;
-            rem = j % per;
-        } else {
-            hq = L / per;
-            rem = L % per;
-        }
-        qb = rem / nreq;
-        r = rem % nreq;
-    }
+    xcd_head_order(blockIdx.x, H, nqb, nreq, hq, qb, r);
     const int64_t b = b0 + r;
     const int hk = hq / (H / Hkv);
     const int64_t seqlen = seq_starts[b + 1] - seq_starts[b];
@@ -112,11 +88,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int64_t wlast = (wrow0 + 31 < seqlen - 1) ? wrow0 + 31 : seqlen - 1;
 
     const int64_t slot0 = MODE == 0 ? cache_indices[b] : 0;
-    const char* kbase = reinterpret_cast<const char*>(kv.cache) + (int64_t)hk * kv.sH * ELT;
-    const char* vbase = kbase + kv.sKV * ELT;
-    const uint16_t* ksbase = kv.scale + (int64_t)hk * kv.ssH;
-    const uint16_t* vsbase = ksbase + kv.ssKV;
-    const int64_t rowb = kv.sN * ELT, srow = kv.ssN;
+    const KvHead kh = kv_head<QBIT>(kv, hk);
+    const char *const kbase = kh.kbase, *const vbase = kh.vbase;
+    const uint16_t *const ksbase = kh.ksbase, *const vsbase = kh.vsbase;
+    const int64_t rowb = kh.rowb, srow = kh.srow;
     const int rowb32 = (int)rowb, srow32 = (int)srow;
 
     // ---- staging registers of one 64-key tile: item (key, piece) = divmod(tid + 256 it, LPT).  (Macros, not lambdas: register arrays
@@ -165,7 +140,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             P3_LOAD_ITEM(3, kr3, vr3, kc3, vc3);                                                                               \
         }                                                                                                                      \
     } while (0)
-    // dequantise one item -> stage.  K: fp16 [64 keys][128 channels], 16-byte chunks XOR-swizzled with (key & 15) (conflict-free b128
+    // dequantise one item -> stage (dequant_piece's and ATT_V_OFF's own text: through them nine of these kernels changed by 1-3
+    // instructions, some upwards).  K: fp16 [64 keys][128 channels], 16-byte chunks XOR-swizzled with (key & 15) (conflict-free b128
     // fragment reads); V: row-major [16 keys][16 channels] sub-tiles
 #define P3_STORE_ITEM(it, KR, VR, KC, VC)                                                                                       \
     do {                                                                                                                       \
@@ -177,7 +153,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const h8 kh0 = k0 * ks2[0], kh1 = k1 * ks2[1], vh0 = v0 * vs2[0], vh1 = v1 * vs2[1]; /* one rounding of q x scale */ \
             *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh0);          \
             *reinterpret_cast<uint4*>(&Kw[key * D + (((ch0 >> 3) + 1) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh1);    \
-            uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * P3_VSUB + (key & 15) * 16];                              \
+            uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * ATT_VSUB + (key & 15) * 16];                              \
             *reinterpret_cast<uint4*>(vd) = __builtin_bit_cast(uint4, vh0);                                                    \
             *reinterpret_cast<uint4*>(vd + 8) = __builtin_bit_cast(uint4, vh1);                                                \
         } else if constexpr (QBIT == KV_FP8) {  /* e4m3 x 2^e: exact fp16, no rounding */                                      \
@@ -186,12 +162,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const h8 vh0 = cvt_fp8x8_f16(make_uint2(VR.x, VR.y), vs_), vh1 = cvt_fp8x8_f16(make_uint2(VR.z, VR.w), vs_);       \
             *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh0);          \
             *reinterpret_cast<uint4*>(&Kw[key * D + (((ch0 >> 3) + 1) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh1);    \
-            uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * P3_VSUB + (key & 15) * 16];                              \
+            uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * ATT_VSUB + (key & 15) * 16];                              \
             *reinterpret_cast<uint4*>(vd) = __builtin_bit_cast(uint4, vh0);                                                    \
             *reinterpret_cast<uint4*>(vd + 8) = __builtin_bit_cast(uint4, vh1);                                                \
         } else {                                                                                                               \
             *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = KR;                                      \
-            *reinterpret_cast<uint4*>(&Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * P3_VSUB + (key & 15) * 16 + (ch0 & 15)]) = VR; \
+            *reinterpret_cast<uint4*>(&Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * ATT_VSUB + (key & 15) * 16 + (ch0 & 15)]) = VR; \
         }                                                                                                                      \
     } while (0)
 
@@ -297,27 +273,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                     for (int c = 0; c < 4; ++c) o[c][i] *= ar;
                 }
             }
-            // ---- O += P . V over four 16-key k-steps; P as an exact hi + lo pair (mask, subtract, v_cvt_pkrtz: two MFMAs per block) -----------
+            // ---- O += P . V over four 16-key k-steps; P as an exact hi + lo pair (p_hi_lo: two MFMAs per block) -----------
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                typedef __fp16 pk_h2 __attribute__((ext_vector_type(2)));
                 h8 pa, pl;
                 {
-                    uint32_t hw[4], lw[4];
+                    float p[8];
 #pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        const float p0 = sacc[s >> 1][8 * (s & 1) + 2 * q2], p1 = sacc[s >> 1][8 * (s & 1) + 2 * q2 + 1];
-                        const float h0 = __uint_as_float(__float_as_uint(p0) & 0xffffe000u), h1 = __uint_as_float(__float_as_uint(p1) & 0xffffe000u);
-                        hw[q2] = __builtin_bit_cast(uint32_t, (pk_h2)__builtin_amdgcn_cvt_pkrtz(h0, h1));
-                        lw[q2] = __builtin_bit_cast(uint32_t, (pk_h2)__builtin_amdgcn_cvt_pkrtz(p0 - h0, p1 - h1));
-                    }
-                    pa = __builtin_bit_cast(h8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
-                    pl = __builtin_bit_cast(h8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
+                    for (int i = 0; i < 8; ++i) p[i] = sacc[s >> 1][8 * (s & 1) + i];
+                    p_hi_lo(p, pa, pl);
                 }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const uint16_t* sub = Vs + (s * (D / 16) + 2 * c + chblk) * P3_VSUB;  // keys 16 s .. + 16, channels 32 c + 16 chblk .. + 16
-                    const uint2 v0 = p3_v_frag(sub, 4 * hi, l15), v1 = p3_v_frag(sub, 8 + 4 * hi, l15);
+                    const uint16_t* sub = Vs + (s * (D / 16) + 2 * c + chblk) * ATT_VSUB;  // keys 16 s .. + 16, channels 32 c + 16 chblk .. + 16
+                    const uint2 v0 = v_frag_tr(sub, 4 * hi, l15), v1 = v_frag_tr(sub, 8 + 4 * hi, l15);
                     const h8 bv = __builtin_bit_cast(h8, make_uint4(v0.x, v0.y, v1.x, v1.y));
                     if (!(ABL & 1)) o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, bv, o[c], 0, 0, 0);
                     o[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa, bv, o[c], 0, 0, 0);
@@ -357,23 +326,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
 }
 
-// merges the splits of token rows [row0, row0 + gridDim.x / H): one block per (row, head), one thread per channel
-__global__ void attn_prefill32_reduce_kernel(const float* __restrict__ ws, int nsplit, int64_t row0, int H, uint16_t* __restrict__ out) {
-    constexpr int D = P3_D;
-    const int64_t bh = row0 * H + blockIdx.x;  // absolute (row, head) of the output; the workspace is relative to row0
-    const float* w = ws + (int64_t)blockIdx.x * nsplit * (D + 2);
-    const int d = threadIdx.x;
-    float mm = -1e30f;
-    for (int sp = 0; sp < nsplit; ++sp) mm = fmaxf(mm, w[sp * (D + 2) + D]);
-    float ll = 0.f, o = 0.f;
-    for (int sp = 0; sp < nsplit; ++sp) {
-        const float a = __expf(w[sp * (D + 2) + D] - mm);
-        ll = fmaf(w[sp * (D + 2) + D + 1], a, ll);
-        o = fmaf(w[sp * (D + 2) + d], a, o);
-    }
-    out[bh * D + d] = f2h(o / ll);
-}
-
 #undef P3_LOAD_TILE
 #undef P3_LOAD_ITEM
 #undef P3_STORE_ITEM
@@ -388,6 +340,21 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
                                  int64_t row0, int64_t nrows) {
     if (D != P3_D || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8)) return hipErrorInvalidValue;
     if (B <= b0 || max_seq_len <= 0) return hipSuccess;
+    const int nreq = (int)(B - b0);
+    // one launch of nw waves per block (split form: 4 only) on `grid`: format and cache mode -> template arguments
+    auto launch = [&](dim3 grid, int nw, auto split_c, int nqb, float* part, int64_t part_row0) {
+        constexpr int SPLIT = decltype(split_c)::value;
+        dispatch_int<KV_I8G8, KV_FP8, KV_FP16>(kv_fmt, [&](auto QB) {
+            dispatch_int<0, 1>(kv.mode, [&](auto MD) {
+                dispatch_int<8, 4>(nw, [&](auto NW) {
+                    if constexpr (SPLIT == 0 || NW == 4)
+                        hipLaunchKernelGGL((attn_prefill32_kernel<QB, MD, NW, 0, SPLIT>), grid, dim3(NW * 64), 0, s, qkv, kv, seq_starts, start_pos,
+                                           cache_indices, max_pages, b0, H, Hkv, nreq, nqb, out, part, part_row0);
+                });
+            });
+        });
+        return hipGetLastError();
+    };
     // Few new tokens behind long caches (a prefix-cache hit recomputes one page; a short follow-up turn): when the launch has too few
     // (query block, request, head) blocks to fill the chip, the keys of each are split over gridDim.y blocks whose partial rows are merged
     // (flash-decoding form).  row0 / nrows: the token rows of these requests (contiguous in the step); ws: nrows x H x splits x (D + 2) floats.
@@ -401,18 +368,9 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
         if (split_env > 1) nsplit = split_env;
         while (nsplit > 1 && (size_t)nrows * H * nsplit * (P3_D + 2) * sizeof(float) > ws_bytes) --nsplit;
         if (nsplit > 1) {
-            const int nreq = (int)(B - b0);
-            dim3 grid((unsigned)blocks4, (unsigned)nsplit);
-#define P3_SPLIT(QB, MD) hipLaunchKernelGGL((attn_prefill32_kernel<QB, MD, 4, 0, 1>), grid, dim3(256), 0, s, qkv, kv, seq_starts, start_pos, \
-                                            cache_indices, max_pages, b0, H, Hkv, nreq, (int)nqb4, out, ws, row0)
-            if (kv_fmt == KV_I8G8) { if (kv.mode == 0) P3_SPLIT(8, 0); else P3_SPLIT(8, 1); }
-            else if (kv_fmt == KV_FP8) { if (kv.mode == 0) P3_SPLIT(KV_FP8, 0); else P3_SPLIT(KV_FP8, 1); }
-            else { if (kv.mode == 0) P3_SPLIT(0, 0); else P3_SPLIT(0, 1); }
-#undef P3_SPLIT
-            hipError_t e = hipGetLastError();
+            const hipError_t e = launch(dim3((unsigned)blocks4, (unsigned)nsplit), 4, int_c<1>{}, (int)nqb4, ws, row0);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(attn_prefill32_reduce_kernel, dim3((unsigned)(nrows * H)), dim3(P3_D), 0, s, ws, (int)nsplit, row0, H, out);
-            return hipGetLastError();
+            return launch_attn_reduce(s, ws, (int)nsplit, nrows * H, P3_D, out + row0 * H * P3_D);
         }
     }
     // 8 waves (256 query rows per block: each staged K / V tile serves twice the rows) once the sequences are long enough: 8192 new
@@ -420,27 +378,19 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
     static const int nw_env = tune_int("PPLHIP_P32_NW", 0);
     const int nw = nw_env ? nw_env : (max_seq_len >= 1024 ? 8 : 4);
     const int bm = nw * 32;
-    const int nqb = (int)((max_seq_len + bm - 1) / bm), nreq = (int)(B - b0);
+    const int nqb = (int)((max_seq_len + bm - 1) / bm);
     dim3 grid((unsigned)((int64_t)nqb * nreq * H));
-#define P3_LAUNCH(QB, MD, NW_) hipLaunchKernelGGL((attn_prefill32_kernel<QB, MD, NW_>), grid, dim3(NW_ * 64), 0, s, qkv, kv, seq_starts, start_pos, \
-                                                  cache_indices, max_pages, b0, H, Hkv, nreq, nqb, out, nullptr, 0)
 #ifdef P3_ABLATE_BUILD  // diagnosis build (profiles/r03_prefill_attention_ablation.md): wrong results, same instruction stream otherwise
     static const int abl = getenv("PPLHIP_P32_ABLATE") ? atoi(getenv("PPLHIP_P32_ABLATE")) : 0;   // (an ablation build reads its switch itself: no TUNING=1 needed)
-#define P3_ABL(A) if (abl == A && nw == 8) { hipLaunchKernelGGL((attn_prefill32_kernel<8, 0, 8, A>), grid, dim3(512), 0, s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, b0, H, Hkv, nreq, nqb, out, nullptr, 0); return hipGetLastError(); }
-    P3_ABL(1) P3_ABL(2) P3_ABL(3) P3_ABL(7)
-#undef P3_ABL
-#endif
-    if (nw == 8) {
-        if (kv_fmt == KV_I8G8) { if (kv.mode == 0) P3_LAUNCH(8, 0, 8); else P3_LAUNCH(8, 1, 8); }
-        else if (kv_fmt == KV_FP8) { if (kv.mode == 0) P3_LAUNCH(KV_FP8, 0, 8); else P3_LAUNCH(KV_FP8, 1, 8); }
-        else { if (kv.mode == 0) P3_LAUNCH(0, 0, 8); else P3_LAUNCH(0, 1, 8); }
-    } else {
-        if (kv_fmt == KV_I8G8) { if (kv.mode == 0) P3_LAUNCH(8, 0, 4); else P3_LAUNCH(8, 1, 4); }
-        else if (kv_fmt == KV_FP8) { if (kv.mode == 0) P3_LAUNCH(KV_FP8, 0, 4); else P3_LAUNCH(KV_FP8, 1, 4); }
-        else { if (kv.mode == 0) P3_LAUNCH(0, 0, 4); else P3_LAUNCH(0, 1, 4); }
+    if (nw == 8 && (abl == 1 || abl == 2 || abl == 3 || abl == 7)) {
+        dispatch_int<1, 2, 3, 7>(abl, [&](auto A) {
+            hipLaunchKernelGGL((attn_prefill32_kernel<8, 0, 8, A>), grid, dim3(512), 0, s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages,
+                               b0, H, Hkv, nreq, nqb, out, nullptr, 0);
+        });
+        return hipGetLastError();
     }
-#undef P3_LAUNCH
-    return hipGetLastError();
+#endif
+    return launch(grid, nw, int_c<0>{}, nqb, nullptr, 0);
 }
 
 }  // namespace pplhip

@@ -1,8 +1,8 @@
 // Device side of the tile GEMM (128 x 128 x 64, LDS-DMA ring): constants, epilogues, conversion helpers and the block body
 // gemm_dma_body; k_gemm.hip wraps it into the kernels and k_gemm_i8.hip shares the helpers.
 #pragma once
-#include <type_traits>
 #include "kernels.h"
+#include "k_launch.h"
 
 namespace pplhip {
 
@@ -29,40 +29,14 @@ __device__ __forceinline__ void store4(void* yv, int64_t ldy, int64_t m, int n, 
     }
 }
 
-// Host side of the launchers: a runtime choice -> template argument.  dispatch_int<A, B, C>(v, f) calls the generic lambda f with
-// std::integral_constant<int, V> for the V of the list that equals v (the last one when none does: the ladders' final `else`), so
-// only the listed values are instantiated; dispatch_epi does it for the three epilogues, for_each_epi visits all three.
-template <int V> using int_c = std::integral_constant<int, V>;
-template <int V0, int... Vs, class F>
-inline void dispatch_int(int v, F&& f) {
-    if constexpr (sizeof...(Vs) == 0) f(int_c<V0>{});
-    else if (v == V0) f(int_c<V0>{});
-    else dispatch_int<Vs...>(v, f);
-}
+// Host side of the launchers (dispatch_int, LdsOptIn: k_launch.h): dispatch_epi picks the template argument of the three epilogues,
+// for_each_epi visits all three.
 template <class F>
 inline void dispatch_epi(int epi, F&& f) {
     if (epi == EPI_F32) f(int_c<EPI_F32>{}); else if (epi == EPI_F16) f(int_c<EPI_F16>{}); else f(int_c<EPI_SWIGLU>{});
 }
 template <class F>
 inline void for_each_epi(F&& f) { f(int_c<EPI_F16>{}); f(int_c<EPI_F32>{}); f(int_c<EPI_SWIGLU>{}); }
-
-// Kernels that need more dynamic LDS than the default limit: `static LdsOptIn once; if (once.first()) set_max_lds(bytes, kernels...);`
-// first() is true once per device (the attribute belongs to the function ON THE CURRENT DEVICE: one flag per device, or the other ranks
-// of a single-process tensor-parallel run would launch without it)
-struct LdsOptIn {
-    bool done[64] = {false};
-    bool first() {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const bool f = !done[dev & 63];
-        done[dev & 63] = true;
-        return f;
-    }
-};
-template <class... Ks>
-inline void set_max_lds(size_t bytes, Ks... kernels) {
-    ((void)hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), ...);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // W8A16 fast path (K % 64 == 0): both operands go global -> LDS by DMA (global_load_lds_dwordx4: no staging VGPRs, no

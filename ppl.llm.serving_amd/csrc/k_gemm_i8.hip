@@ -569,7 +569,7 @@ static hipError_t launch_linear_q8(hipStream_t s, const int8_t* xq, const float*
             const int nt2 = (N + 255) / 256, mt2 = (int)((M + 255) / 256);
             static const int st256 = tune_int("PPLHIP_GEMM_I8_256_ST", 4) == 3 ? 3 : 4;
             const size_t lds2 = (size_t)st256 * 2 * 256 * 64;
-            static LdsOptIn once;  // (per device: see k_gemm_dev.h)
+            static LdsOptIn once;  // (per device: see k_launch.h)
             if (once.first())
                 for_each_epi([](auto E) {
                     set_max_lds(3 * 2 * 256 * 64, gemm_i8_256_kernel<E, 3>);

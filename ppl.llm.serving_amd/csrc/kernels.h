@@ -91,6 +91,9 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
                               const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                               int64_t max_pages, int64_t nb, int H, int Hkv, int D, int64_t max_kv_len, int split,
                               int threads, float* workspace, uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// merges the `nsplit` partial rows of each of n_row_heads (row, head) pairs of `ws` ([row][head][split][D + 2] floats) into out
+// ([row][head][D] fp16): the end of every split launch -- both decode kernels and the split-KV prefill
+hipError_t launch_attn_reduce(hipStream_t s, const float* ws, int nsplit, int64_t n_row_heads, int D, uint16_t* out);
 
 // ---- k_attn_prefill.hip -----------------------------------------------------------------------
 // requests [b0, B): causal attention of their new tokens over the cache [0, start_pos + seqlen).
@@ -109,7 +112,7 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
 
 // ---- k_attn_decode_gqa.hip --------------------------------------------------------------------
 // grouped-query decode (4 <= H/Hkv <= 16): MFMA kernel, one block per (request, KV head[, split]); same workspace layout
-// and reduce kernel as launch_attn_decode.  t0 / t1: optional start / stop events of the kernel's own dispatch packet.
+// and reduce (launch_attn_reduce, run by the caller) as launch_attn_decode.  t0 / t1: optional start / stop events of the kernel's own dispatch packet.
 bool attn_decode_gqa_supported(int kv_fmt, int H, int Hkv, int D);
 hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                                   const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,

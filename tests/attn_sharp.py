@@ -35,7 +35,7 @@ RISE_STEP, RISE_RAMP, RISE_MIN = 8.0, 2.0, 5.0   # F2 'rising': level step per 6
 # kernel parameters the needle positions must straddle (csrc)
 P3_BN = 64             # k_attn_prefill32.hip: keys per tile
 PF_BN = 128            # k_attn_prefill.hip: keys per tile
-PF_BM = 64             # k_attn_prefill.hip: query rows per block (16 x PF_NW)
+PF_BM = 64             # k_attn_prefill.hip: half the query rows of a block (16 x PF_NW = 128, itself in the edge set below)
 GQ_SUB, GQ_PAIR, GQ_STRIP = 16, 32, 128   # k_attn_decode_gqa.hip: sub-tile, pair step, split strip
 DEC_UNROLL = 4         # k_attn_decode_dev.h
 
@@ -61,7 +61,7 @@ def gqa_form(fmt, H, Hkv, D):
 
 
 def dec_key_step(fmt, D, threads=256):
-    """keys per wave step and per block step of the multi-head decode kernel (DecodeCfg)"""
+    """keys per wave step and per block step of the multi-head decode kernel (AttnCfg, k_attn_dev.h)"""
     lpt = D // (16 // (1 if fmt != "f16" else 2))
     tpw = 64 // lpt
     nw = max(threads, D) // 64
@@ -758,6 +758,7 @@ def teeth(case, want=None):
 # -------------------------------------------------------------------------------------------------------------------------------------
 LAYOUT_MODES = [(3, 1), (0, 0), (1, 1), (2, 0), (3, 0)]
 DEC_KV = [1, 2, 17, 64, 65, 700, 2049, 2049, 8192, 8192, 8192, 8192]        # decode kv lengths (the current token included)
+ODD_KV = [1, 2, 17, 64, 65, 300, 700, 700]                                  # ... of the specs on odd page sizes
 
 
 def f1_decode_specs():
@@ -786,6 +787,15 @@ def f1_decode_specs():
         specs.append(dict(name=f"gqa_small_{fmt}", fmt=fmt, H=16, Hkv=2, D=128 if fmt != "f16" else 64, seqlens=[1] * len(kv),
                           start_pos=[n - 1 for n in kv], nb=len(kv), layout=3, mode=1, page_size=16, split=2, seed=k))
         k += 1
+    # page sizes off the usual 16 / 64 (the addressing branches of the kernels): multi-head decode on pages of 2 (page ids no longer
+    # held in a lane register: page_shift < 2) and of 12 (page_shift -1: the division path), grouped-query decode on pages of 8 and 12
+    # (rows of a 16-key sub-tile no longer consecutive slots: every row through the page table)
+    for fmt in ("f16", "i8", "f8"):
+        for tag, H, Hkv, ps, split, kv in (("dec", 8, 8, 2, 1, ODD_KV), ("dec", 8, 8, 12, 3, ODD_KV),
+                                           ("gqa", 8, 1, 8, 2, ODD_KV + [1100]), ("gqa", 8, 2, 12, 1, ODD_KV)):
+            specs.append(dict(name=f"{tag}_{fmt}_{H}x{Hkv}x128_s{split}_l3m1p{ps}", fmt=fmt, H=H, Hkv=Hkv, D=128, seqlens=[1] * len(kv),
+                              start_pos=[n - 1 for n in kv], nb=len(kv), layout=3, mode=1, page_size=ps, split=split, seed=k))
+            k += 1
     return specs
 
 
@@ -799,6 +809,12 @@ def f1_prefill_specs():
             specs.append(dict(name=f"pf16_{fmt}_{H}x{Hkv}x{D}_l{layout}m{mode}", fmt=fmt, H=H, Hkv=Hkv, D=D, seqlens=[1, 1, 130, 64, 300],
                               start_pos=[40, 5, 0, 64, 1000], nb=2, layout=layout, mode=mode, page_size=16, seed=k))
             k += 1
+        # odd page sizes: 5 (the two keys of a staging item no longer share a page) and 12 (no shift addressing)
+        for ps in (5, 12):
+            specs.append(dict(name=f"pf16_{fmt}_8x2x64_l3m1p{ps}", fmt=fmt, H=8, Hkv=2, D=64, seqlens=[1, 1, 130, 64, 300],
+                              start_pos=[40, 5, 0, 64, 500], nb=2, layout=3, mode=1, page_size=ps, seed=k + 10 + ps))
+        specs.append(dict(name=f"p32_{fmt}_4x2x128_l3m1p12", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[1, 1, 130, 64, 300],
+                          start_pos=[40, 5, 0, 64, 500], nb=2, layout=3, mode=1, page_size=12, seed=k + 30))
         specs.append(dict(name=f"p32w4_{fmt}", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[300, 129, 5, 200], start_pos=[0, 900, 70, 3000],
                           nb=0, layout=3, mode=1, page_size=16, seed=k))
         specs.append(dict(name=f"p32w8_{fmt}", fmt=fmt, H=4, Hkv=1, D=128, seqlens=[1100, 37], start_pos=[0, 2000], nb=0, layout=3,

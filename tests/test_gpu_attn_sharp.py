@@ -45,13 +45,14 @@ def _f1(spec):
 
 @pytest.mark.parametrize("spec", A.f1_decode_specs(), ids=lambda s: s["name"])
 def test_f1_decode(spec):
-    """decode rows up to 8192 keys: splits 1 / 3 / 8 (2 in the small-block grouped-query form), every layout, pages of 16 and 64"""
+    """decode rows up to 8192 keys: splits 1 / 3 / 8 (2 in the small-block grouped-query form), every layout, pages of 16 and 64, and the
+    addressing branches behind pages of 2, 8 and 12"""
     _f1(spec)
 
 
 @pytest.mark.parametrize("spec", A.f1_prefill_specs(), ids=lambda s: s["name"])
 def test_f1_prefill(spec):
-    """prefill and cache-prefill rows: needles on the diagonal, probes one key past it, tile / page / split edges"""
+    """prefill and cache-prefill rows: needles on the diagonal, probes one key past it, tile / page / split edges, pages of 5 and 12"""
     _f1(spec)
 
 
