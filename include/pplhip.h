@@ -353,6 +353,44 @@ PPLHIP_API int pplhip_op_linear_ex(void* stream, const void* x, const void* w, c
                                    int64_t M, int32_t N, int32_t K, void* y, int64_t ldy, int32_t epi, void* ws, uint64_t ws_bytes,
                                    int32_t dry_run, char* route, int32_t route_len);
 
+/* The step schedule as a pure function (pplhip.cc plan_step: no HIP call, no environment read, no context, no device): what
+ * pplhip_run executes for a step of this shape under these settings, and what pplhip_comm_info reports.  For the tests: not part of
+ * the product boundary.  A chunk is requests [b0, b0 + bn) = token rows [t0, t0 + tn), its first nd requests decode rows. */
+typedef struct pplhip_chunk {
+    int64_t b0, bn, t0, tn, nd;
+} pplhip_chunk;
+typedef struct pplhip_plan_settings {   /* what pplhip_init derived from the descriptor, the options and the switches */
+    int32_t tp, tp_on;                  /* world size; collectives after wo / w2 and the logits gather are issued */
+    int32_t comm_mode;                  /* pplhip_comm_mode */
+    int32_t has_comm, has_comm2;        /* an RCCL communicator exists for channel 0 / channel 1 */
+    int32_t emulate_tp;                 /* PPLHIP_EMULATE_TP */
+    int32_t tp_overlap;                 /* PPLHIP_TP_OVERLAP */
+    int32_t dual_mode, dual_auto;       /* PPLHIP_DUAL_STREAM: on at all; by the automatic rule */
+    int32_t has_stream2;                /* the rank owns a second compute stream */
+    int64_t tp_overlap_min_tokens;      /* PPLHIP_TP_OVERLAP_MIN_TOKENS */
+    int64_t dual_min_rows, dual_max_rows;
+    int32_t fuse_norm_want, defer_on;   /* PPLHIP_TP_FUSE_NORM, PPLHIP_DEFER_REDUCE */
+    int32_t act_fmt;                    /* 0 fp16, 1 int8, 2 fp8 activations */
+    int32_t hidden_dim;
+    int32_t heads, kv_heads, head_dim;  /* per rank */
+    int32_t cache_quant_bit, cache_quant_group;
+    int32_t decoding_attn_split_k;      /* pplhip_opts */
+} pplhip_plan_settings;
+typedef struct pplhip_step_shape {
+    int64_t batch, num_tokens, decoding_batches, max_kv_len;   /* pplhip_step */
+    const int64_t* seq_starts;          /* host [batch + 1], or NULL: the rank holds no host copy (never read for a pure-decode step) */
+    int32_t capturing, dump;            /* the stream is capturing a graph; a residual dump is on */
+} pplhip_step_shape;
+typedef struct pplhip_step_plan {
+    int32_t schedule;                   /* as pplhip_comm_info_t.schedule: 0 one lane, 1 two lanes, 2 two chunks on the communication stream */
+    int32_t num_chunks;
+    pplhip_chunk chunk[2];
+    int32_t decode_split[2];            /* split-K of each chunk's decode attention */
+    int32_t fuse_norm, defer_reduce, defer_qkv;
+    int64_t lane1_ws_off;               /* floats: where lane 1's attention workspace starts */
+} pplhip_step_plan;
+PPLHIP_API int pplhip_op_step_plan(const pplhip_plan_settings* settings, const pplhip_step_shape* shape, pplhip_step_plan* out);
+
 /* online_i8i8 (W8A8, src/backends/cuda/resource_manager.cc:51-52).  Per-token activation quantisation: q[M,K] int8,
  * sx[M] = max|x| / 127; per-output-row weight quantisation of an fp16 [N,K] matrix: q[N,K] int8, scale[N] fp16;
  * y[m,n] = (sum_k xq * w as int32) * sx[m] * scale[n], rounded to fp16 (or kept fp32); swiglu as in pplhip_op_linear_swiglu. */

@@ -54,20 +54,42 @@ struct ProfEvent {
     hipEvent_t a, b;
 };
 
+// One collective channel of a rank: what two all-reduces need of their own to run side by side.  Channel 0 carries every collective
+// of a one-lane or two-chunk step, the self-test and the logits all-gather; channel 1 the second half-batch of a two-lane decode step.
+struct Channel {
+    int id = 0;                      // flag set of the direct collectives (k_comm.hip)
+    ncclComm_t comm = nullptr;       // RCCL communicator (a communicator serialises its streams, so each channel has one)
+    size_t x_scratch[2] = {0, 0};    // scratch double buffer: byte offsets inside the exchange region
+    uint32_t ar_count = 0;           // all-reduces issued (which scratch buffer is next)
+    uint32_t p2p_epoch = 0;          // epoch of the channel's flag words
+};
+
+// What the launches of one half-batch go out with.  run_launches builds a Lane per half on its stack for every step: lane 0 = the rank's
+// stream, workspaces and channel 0; lane 1 (two-lane decode only) = stream2, gemm_ws2, the attention workspace past the first half's
+// rows and channel 1.  Nothing in Rank is swapped while a step is issued, so an error return leaves nothing to restore.
+struct Lane {
+    hipStream_t stream = nullptr;
+    float* gemm_ws = nullptr;        // split-K partial slabs
+    float* attn_ws = nullptr;
+    size_t attn_ws_bytes = 0;
+    // split-K results left unreduced for the kernel that consumes them (kernels.h SplitSlabs): wqkv -> RoPE + KV write, wo -> FFN norm,
+    // w2 -> the next layer's attention norm (or the final norm)
+    SplitSlabs sl_qkv, sl_part, sl_part2;
+    Channel* ch = nullptr;
+};
+
 struct Rank {
     int device = 0;
     int global_rank = 0;
     hipStream_t stream = nullptr;
-    ncclComm_t comm = nullptr;
-    ncclComm_t comm2 = nullptr;         // the second half-batch's collectives of a two-stream decode step (a communicator serialises its streams)
-    hipStream_t comm_stream = nullptr;  // collectives of an overlapped step (pplhip_run)
-    // two-stream decode (run_launches, "dual"): the second half of a mid-size pure-decode step runs its layers on stream2, beside the first
-    // half on `stream`, with split-K / attention workspaces of its own; ev_fork / ev_join order the two around the step
+    Channel ch[2];                      // ch[1]: scratch pair when two-stream decode is on, communicator when it was asked for explicitly
+    hipStream_t comm_stream = nullptr;  // collectives of a two-chunk step (pplhip_run)
+    // two-lane decode (plan_step): the second half of a mid-size pure-decode step runs its layers on stream2, beside the first half on
+    // `stream`, with split-K / attention workspaces of its own (Lane); ev_fork / ev_join order the two around the step
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     float* gemm_ws2 = nullptr;
     bool dual_seen = false;
-    bool keep_part2 = false;            // this launch of w2 must write part2 (its consumer runs on the other stream): no deferred slabs
     hipEvent_t ev_compute[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr};
     const int64_t* h_seq = nullptr;     // host copy of this step's seq_starts (lives in the staging buffer)
     std::string err;
@@ -96,11 +118,6 @@ struct Rank {
     int64_t* pages_host = nullptr;  // pinned
     uint64_t pages_cap = 0;
     int64_t B = 0, T = 0, decoding_batches = 0, max_seq_len = 0, max_kv_len = 0, max_pages = 0;
-    // split-K results left unreduced for the kernel that consumes them (kernels.h SplitSlabs): wqkv -> RoPE + KV write, wo -> FFN norm,
-    // w2 -> the next layer's attention norm (or the final norm)
-    SplitSlabs sl_qkv, sl_part, sl_part2;
-    bool defer_reduce = false;   // this step: tensor-parallel size 1, weight-only quantisation, no residual dump
-    bool defer_qkv = false;      // ... wqkv's slabs alone also under tensor parallelism (RoPE + KV write consumes them on the rank itself)
 
     // activations
     uint16_t *h = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *part = nullptr, *part2 = nullptr, *gu = nullptr,
@@ -114,7 +131,7 @@ struct Rank {
     float* logits = nullptr;        // [B, V]
     float* attn_ws = nullptr;
     size_t attn_ws_bytes = 0;
-    float* gemm_ws = nullptr;  // split-K partial slabs
+    float* gemm_ws = nullptr;  // split-K partial slabs (gemm_ws2: as many bytes)
     size_t gemm_ws_bytes = 0;
 
     // sampler (local rank 0)
@@ -128,15 +145,9 @@ struct Rank {
     // exchange region of the direct collectives (k_comm.hip): fine-grained, peer-mapped; holds the flag words and the buffers
     // the collectives work in place on (part, part2) or push into (logits_gather)
     char* xbase = nullptr;
-    size_t xbytes = 0, x_part = 0, x_part2 = 0, x_scratch[2] = {0, 0}, x_local = 0;  // byte offsets inside the region
-    uint32_t ar_count = 0;              // all-reduces issued (scratch double buffer)
-    // channel 1 of the direct collectives (second half-batch of a two-stream decode step): flag set, scratch pair, counters of its own
-    size_t x_scratch2[2] = {0, 0};
-    uint32_t ar_count2 = 0, p2p_epoch2 = 0;
-    int channel = 0;                    // which of the two the launches being issued belong to
+    size_t xbytes = 0, x_part = 0, x_part2 = 0, x_local = 0;  // byte offsets inside the region (the scratch pairs: Channel)
     P2pPeers peers{};
     bool peer_ipc[P2P_MAX_RANKS] = {};  // peers.base[g] came from hipIpcOpenMemHandle (closed on destroy)
-    uint32_t p2p_epoch = 0;
     uint32_t* p2p_status = nullptr;     // pinned host word a kernel raises when one of its bounded spins timed out
     int32_t* d_flag = nullptr;          // one int for the cross-process agreement on the self-test
     // stream hand-offs of the two-chunk schedule through device-memory epochs (k_comm.hip handoff_*): words 0..1 = "chunk i's
@@ -168,6 +179,9 @@ struct pplhip_ctx {
     // all-reduce, chunks of >= 1024 rows keep the GEMM tiles full), not for pure decode steps of <= 1024 rows.
     int64_t tp_overlap_min_tokens = 2048;
     bool handoff_flags = true;  // PPLHIP_TP_HANDOFF=events: HIP events instead of device-memory epochs between the two streams
+    int tp_debug = 0;           // PPLHIP_TP_DEBUG (diagnosis): bit 0 = hand-off events are created anew instead of re-recorded inside a step,
+                                // bit 1 = chunks, but their collectives stay on the compute stream
+    bool defer_on = true;       // PPLHIP_DEFER_REDUCE=0: every split-K linear reduces its own slabs
     bool tp_on = false;     // the tensor-parallel step schedule (collectives after wo / w2, logits gather) is active
     // collectives: 2 = direct kernels over peer-mapped memory (k_comm.hip), 1 = RCCL, 0 = none.  PPLHIP_COMM=auto (default:
     // direct when the self-test passes on every rank, else RCCL) | p2p (direct or fail) | rccl
@@ -324,7 +338,7 @@ KvAddr make_kv_addr(const pplhip_model_desc& d, int Hkv, int D, uint64_t tokens,
     return a;
 }
 
-void prof_begin(pplhip_ctx* c, Rank& R, int cls, ProfEvent* ev) {
+void prof_begin(pplhip_ctx* c, Rank& R, const Lane& lane, int cls, ProfEvent* ev) {
     ev->cls = -1;
     if (!c->o.enable_profiling) return;
     // 2 = light: only the decode-attention launches (through hipExtLaunchKernel's start / stop events) and the whole run.  An event record is a barrier packet on the
@@ -334,19 +348,19 @@ void prof_begin(pplhip_ctx* c, Rank& R, int cls, ProfEvent* ev) {
     if (!R.prof_free.empty()) { p = R.prof_free.back(); R.prof_free.pop_back(); }
     else { hipEventCreate(&p.first); hipEventCreate(&p.second); }
     ev->cls = cls; ev->a = p.first; ev->b = p.second;
-    hipEventRecord(ev->a, R.stream);
+    hipEventRecord(ev->a, lane.stream);
 }
-void prof_end(Rank& R, ProfEvent* ev) {
+void prof_end(Rank& R, const Lane& lane, ProfEvent* ev) {
     if (ev->cls < 0) return;
-    hipEventRecord(ev->b, R.stream);
+    hipEventRecord(ev->b, lane.stream);
     R.prof.push_back(*ev);
 }
 
-int decode_split(const pplhip_ctx* c, int64_t nb, int64_t max_kv_len) {
-    const int mode = c->o.decoding_attn_split_k;
+int decode_split(const pplhip_plan_settings& s, int64_t nb, int64_t max_kv_len) {
+    const int mode = s.decoding_attn_split_k;
     if (mode == 0) return 1;
-    const bool gqa = attn_decode_gqa_supported(c->kv_fmt, c->H, c->Hkv, c->D);
-    const int64_t blocks = nb * (gqa ? c->Hkv : c->H);  // GQA kernel: one block per KV head
+    const bool gqa = attn_decode_gqa_supported(kv_format(s.cache_quant_bit, s.cache_quant_group, s.head_dim), s.heads, s.kv_heads, s.head_dim);
+    const int64_t blocks = nb * (gqa ? s.kv_heads : s.heads);  // GQA kernel: one block per KV head
     int split = 1;
     // measured (profiles/attn_microbench.py): 512 workgroups already stream at 5.3 TB/s; split only below ~256.  (The grouped-query
     // kernel at 256 blocks -- 70B / TP8, 256 requests x 1 KV head -- is faster unsplit: 37 us against 46 us with split 2, the reduce
@@ -408,11 +422,12 @@ int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
         }
         for (int r = 0; r < n; ++r) {
             Rank& R = c->ranks[r];
+            Channel& ch = R.ch[0];
             HIPCK(c, r, hipSetDevice(R.device));
-            HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, R.x_scratch[R.ar_count++ & 1], cnt, ++R.p2p_epoch,
+            HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], cnt, ++ch.p2p_epoch,
                                              ticks, R.p2p_status));
             HIPCK(c, r, launch_p2p_allgather(R.stream, R.peers, R.global_rank, tp, R.x_local, R.logits, grows, gcols * 4, (int64_t)gcols * 4 * tp,
-                                             ++R.p2p_epoch, ticks, R.p2p_status));
+                                             ++ch.p2p_epoch, ticks, R.p2p_status));
         }
         for (int r = 0; r < n && ok; ++r) {
             Rank& R = c->ranks[r];
@@ -464,17 +479,18 @@ int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
         for (int round = 0; round < 2 && ok; ++round) {
             for (int r = 0; r < n; ++r) {
                 Rank& R = c->ranks[r];
+                Channel& ch = R.ch[0];
                 HIPCK(c, r, hipSetDevice(R.device));
                 uint16_t* xref = (uint16_t*)R.gemm_ws, *href = xref + fcnt, *w = href + fcnt;
                 HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, fcnt, nullptr, 0, R.global_rank, round + 4));
-                HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, R.x_scratch[R.ar_count++ & 1], fcnt, ++R.p2p_epoch, ticks, R.p2p_status));
+                HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], fcnt, ++ch.p2p_epoch, ticks, R.p2p_status));
                 HIPCK(c, r, launch_p2p_pattern(R.stream, R.h, fcnt, nullptr, 0, 17, round + 4));    // the residual stream: the same on every rank
                 HIPCK(c, r, launch_p2p_pattern(R.stream, w, hd, nullptr, 0, 23, round + 4));
                 HIPCK(c, r, hipMemcpyAsync(href, R.h, (size_t)fcnt * 2, hipMemcpyDeviceToDevice, R.stream));
                 HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, 1, R.x_part, 0, frows, hd, href, w, c->d.norm_eps, xref, 0, ticks, R.p2p_status));
                 HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, fcnt, nullptr, 0, R.global_rank, round + 4));
-                HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, tp, R.x_part, R.x_scratch[R.ar_count++ & 1], frows, hd, R.h, w, c->d.norm_eps,
-                                                      R.xn, ++R.p2p_epoch, ticks, R.p2p_status));
+                HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], frows, hd, R.h, w, c->d.norm_eps,
+                                                      R.xn, ++ch.p2p_epoch, ticks, R.p2p_status));
             }
             for (int r = 0; r < n && ok; ++r) {
                 Rank& R = c->ranks[r];
@@ -503,7 +519,7 @@ int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
             HIPCK(c, r, hipMemcpy(R.d_flag, &v, 4, hipMemcpyHostToDevice));
         }
         NCCLCK(c, -1, ncclGroupStart());
-        for (int r = 0; r < n; ++r) NCCLCK(c, r, ncclAllReduce(c->ranks[r].d_flag, c->ranks[r].d_flag, 1, ncclInt32, ncclMin, c->ranks[r].comm, c->ranks[r].stream));
+        for (int r = 0; r < n; ++r) NCCLCK(c, r, ncclAllReduce(c->ranks[r].d_flag, c->ranks[r].d_flag, 1, ncclInt32, ncclMin, c->ranks[r].ch[0].comm, c->ranks[r].stream));
         NCCLCK(c, -1, ncclGroupEnd());
         for (int r = 0; r < n; ++r) {
             Rank& R = c->ranks[r];
@@ -564,9 +580,50 @@ int p2p_check(pplhip_ctx* c, int rank) {
     return 0;
 }
 
+// ---- the hand-off between a compute stream and the communication stream (two-chunk schedule), once: device-memory epochs
+// (k_comm.hip handoff_*, Rank::hflags) or, PPLHIP_TP_HANDOFF=events, HIP events
+
+// "the work issued on `from` so far is complete for slot i": the communication stream waits for that, runs `work` and marks slot i done.
+// identity: no collective exists (ranks emulated on one device) -- the wait kernel itself raises the done flag and nothing else is launched
+// fresh_events: PPLHIP_TP_DEBUG bit 0 asks for new events instead of re-recorded ones (the all-reduces; the logits all-gather never did)
+template <class Work>
+int comm_handoff(pplhip_ctx* c, int rank, hipStream_t from, int i, bool identity, bool fresh_events, Work&& work) {
+    Rank& R = c->ranks[rank];
+    if (c->handoff_flags) {
+        HIPCK(c, rank, launch_handoff_signal(from, R.hflags + i, ++R.h_ready_ep[i]));
+        HIPCK(c, rank, launch_handoff_wait(R.comm_stream, R.hflags + i, R.h_ready_ep[i], identity ? R.hflags + 2 + i : nullptr,
+                                           identity ? R.h_done_ep[i] + 1 : 0, c->p2p_timeout_ticks, R.p2p_status));
+        ++R.h_done_ep[i];
+        if (identity) return 0;
+        if (int rc = work(R.comm_stream)) return rc;
+        HIPCK(c, rank, launch_handoff_signal(R.comm_stream, R.hflags + 2 + i, R.h_done_ep[i]));
+        return 0;
+    }
+    if (fresh_events) {  // diagnosis: never re-record an event inside a step (the old ones are not destroyed)
+        hipEventCreateWithFlags(&R.ev_compute[i], hipEventDisableTiming);
+        hipEventCreateWithFlags(&R.ev_comm[i], hipEventDisableTiming);
+    }
+    HIPCK(c, rank, hipEventRecord(R.ev_compute[i], from));
+    HIPCK(c, rank, hipStreamWaitEvent(R.comm_stream, R.ev_compute[i], 0));
+    if (int rc = work(R.comm_stream)) return rc;
+    HIPCK(c, rank, hipEventRecord(R.ev_comm[i], R.comm_stream));
+    return 0;
+}
+
+// the compute stream `to` picks up slot i: what the communication stream did for it is complete
+int comm_pickup(pplhip_ctx* c, int rank, hipStream_t to, int i) {
+    Rank& R = c->ranks[rank];
+    if (c->handoff_flags)
+        HIPCK(c, rank, launch_handoff_wait(to, R.hflags + 2 + i, R.h_done_ep[i], nullptr, 0, c->p2p_timeout_ticks, R.p2p_status));
+    else
+        HIPCK(c, rank, hipStreamWaitEvent(to, R.ev_comm[i], 0));
+    return 0;
+}
+
 }  // namespace
 
-static bool fuse_norm_active(const pplhip_ctx* c, const Rank& R);
+static pplhip_plan_settings plan_settings(const pplhip_ctx* c, const Rank& R);
+static bool fuse_norm_active(const pplhip_plan_settings& s, bool dump);
 
 extern "C" {
 
@@ -610,8 +667,8 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.stream2) { hipStreamSynchronize(R.stream2); hipStreamDestroy(R.stream2); }
         if (R.ev_fork) hipEventDestroy(R.ev_fork);
         if (R.ev_join) hipEventDestroy(R.ev_join);
-        if (R.comm2) ncclCommDestroy(R.comm2);
-        if (R.comm) ncclCommDestroy(R.comm);
+        if (R.ch[1].comm) ncclCommDestroy(R.ch[1].comm);
+        if (R.ch[0].comm) ncclCommDestroy(R.ch[0].comm);
         if (R.comm_stream) hipStreamDestroy(R.comm_stream);
         for (int i = 0; i < 2; ++i) {
             if (R.ev_compute[i]) hipEventDestroy(R.ev_compute[i]);
@@ -737,6 +794,12 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
     }
     if (const char* e = getenv("PPLHIP_TP_OVERLAP")) c->tp_overlap = atoi(e) != 0;
     if (const char* e = getenv("PPLHIP_TP_HANDOFF")) c->handoff_flags = strcmp(e, "events") != 0;
+    {   // read once per process, like every diagnosis switch
+        static const int tp_debug = getenv("PPLHIP_TP_DEBUG") ? atoi(getenv("PPLHIP_TP_DEBUG")) : 0;
+        static const int defer_on = getenv("PPLHIP_DEFER_REDUCE") ? atoi(getenv("PPLHIP_DEFER_REDUCE")) : 1;
+        c->tp_debug = tp_debug;
+        c->defer_on = defer_on != 0;
+    }
     {   // Streams against hardware queues.  Kernels of this library WAIT for kernels on other streams of the same process (direct collectives
         // of ranks that share a device, the hand-off kernels of the two-chunk schedule, the halves of a two-stream step meeting in a
         // collective): the HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues per device (default 4), and a
@@ -788,20 +851,20 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             }
             NCCLCK(cp, -1, ncclGroupEnd());
         }
-        for (int r = 0; r < n; ++r) c->ranks[r].comm = comms[r];
+        for (int r = 0; r < n; ++r) c->ranks[r].ch[0].comm = comms[r];
         // a second communicator over the same ranks for the second stream of a two-stream decode step -- only when two-stream decode was
         // asked for explicitly (PPLHIP_DUAL_STREAM=1): the automatic mode runs on the direct collectives' second channel and never uses it
-        // (run_launches), and two RCCL communicators on one device have never run on two devices
+        // (plan_step), and two RCCL communicators on one device have never run on two devices
         if (c->dual_mode && !c->dual_auto) {
             std::vector<ncclComm_t> comms2(n, nullptr);
             ncclResult_t rc2 = ncclGroupStart();
             for (int r = 0; r < n && rc2 == ncclSuccess; ++r) rc2 = ncclCommSplit(comms[r], 0, opts->rank_base + r, &comms2[r], nullptr);
             const ncclResult_t rc3 = ncclGroupEnd();
             if (rc2 == ncclSuccess && rc3 == ncclSuccess) {
-                for (int r = 0; r < n; ++r) c->ranks[r].comm2 = comms2[r];
+                for (int r = 0; r < n; ++r) c->ranks[r].ch[1].comm = comms2[r];
             } else {
                 // ladder: without a second communicator a two-stream step can still run on the direct collectives (their second channel);
-                // on RCCL it falls back to one stream (run_launches checks R.comm2)
+                // on RCCL it falls back to one stream (plan_step checks has_comm2)
                 for (int r = 0; r < n; ++r) if (comms2[r]) (void)ncclCommAbort(comms2[r]);   // partially created group
                 comm_note(c.get(), std::string("second RCCL communicator unavailable (") + ncclGetErrorString(rc2 != ncclSuccess ? rc2 : rc3) +
                                        "): two-stream decode only on the direct collectives, else one stream");
@@ -820,6 +883,7 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
         Rank& R = c->ranks[r];
         R.device = devs[r];
         R.global_rank = opts->rank_base + r;
+        R.ch[1].id = 1;
         HIPCK(cp, r, hipSetDevice(R.device));
         HIPCK(cp, r, hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
         if (c->dual_mode) {
@@ -876,14 +940,9 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             R.x_part2 = R.x_part + up((size_t)cap_T * hd * 2);
             // a rank's reduced slice: <= half the buffer (n >= 2) -- as elements (plain all-reduce) or as whole rows (fused norm: ceil(T / 2) rows)
             const size_t slice_bytes = up(((size_t)cap_T / 2 + 1) * hd * 2 + 64);
-            R.x_scratch[0] = R.x_part2 + up((size_t)cap_T * hd * 2);
-            R.x_scratch[1] = R.x_scratch[0] + slice_bytes;
-            R.x_local = R.x_scratch[1] + slice_bytes;
-            if (c->dual_mode) {
-                R.x_scratch2[0] = R.x_local;
-                R.x_scratch2[1] = R.x_scratch2[0] + slice_bytes;
-                R.x_local = R.x_scratch2[1] + slice_bytes;
-            }
+            R.x_local = R.x_part2 + up((size_t)cap_T * hd * 2);
+            for (int ch = 0; ch < (c->dual_mode ? 2 : 1); ++ch)
+                for (int i = 0; i < 2; ++i) { R.ch[ch].x_scratch[i] = R.x_local; R.x_local += slice_bytes; }
             R.xbytes = R.x_local + up((size_t)cap_B * c->vocab_local * 4);
             // FINE-GRAINED device memory: the kind HIP defines as coherent between devices at system scope (what RCCL puts its
             // peer buffers in).  hipDeviceMallocUncached is NOT usable here: with several ranks on one MI355X a kernel reading
@@ -898,7 +957,7 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             R.part = (uint16_t*)(R.xbase + R.x_part);
             R.part2 = (uint16_t*)(R.xbase + R.x_part2);
             R.logits_local = (float*)(R.xbase + R.x_local);
-            if (R.comm) ALLOC(R.logits_gather, (uint64_t)cap_B * d.vocab_size * 4);  // RCCL all-gather target
+            if (R.ch[0].comm) ALLOC(R.logits_gather, (uint64_t)cap_B * d.vocab_size * 4);  // RCCL all-gather target
             HIPCK(cp, r, hipHostMalloc((void**)&R.p2p_status, 64, hipHostMallocMapped));
             *R.p2p_status = 0;
             ALLOC(R.d_flag, 64);
@@ -937,8 +996,7 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
     }
     // every rank of the group lives in this process: map the peers' regions now and try the direct collectives
     if (c->tp_on && c->comm_want != 1 && tp == n) {
-        int rc = p2p_connect_local(cp);
-        if (rc) return rc;
+        if (int rc = p2p_connect_local(cp)) return rc;
     }
     *out = c.release();
     return 0;
@@ -999,7 +1057,10 @@ int pplhip_comm_connect(pplhip_ctx* c, const void* all_handles) {
 }
 
 int pplhip_comm_mode(pplhip_ctx* c) { return c ? c->comm_mode : PPLHIP_INVALID_VALUE; }
-int pplhip_comm_fused_norm(pplhip_ctx* c) { return c && !c->ranks.empty() ? (fuse_norm_active(c, c->ranks[0]) ? 1 : 0) : PPLHIP_INVALID_VALUE; }
+int pplhip_comm_fused_norm(pplhip_ctx* c) {
+    if (!c || c->ranks.empty()) return PPLHIP_INVALID_VALUE;
+    return fuse_norm_active(plan_settings(c, c->ranks[0]), c->ranks[0].dump_dev != nullptr) ? 1 : 0;
+}
 
 /* ------------------------------------------------------------------------------------------------ weights */
 
@@ -1372,39 +1433,131 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
 }
 
 // A chunk of a step: requests [b0, b0 + bn) = token rows [t0, t0 + tn); the first nd requests of the chunk are
-// decode rows.  A step runs as ONE chunk, or -- tensor parallel, see pplhip_run -- as two that alternate between the
-// compute stream and the communication stream.
-struct Chunk {
-    int64_t b0, bn, t0, tn, nd;
-};
+// decode rows.  A step runs as ONE chunk or as two (plan_step).
+using Chunk = pplhip_chunk;
+using StepPlan = pplhip_step_plan;
+enum { SCHED_ONE_LANE = 0, SCHED_TWO_LANES = 1, SCHED_TWO_CHUNKS = 2 };   // pplhip_comm_info_t.schedule
+
+// what plan_step needs of the context and the rank, as they stand now (comm_mode changes when the ranks connect)
+static pplhip_plan_settings plan_settings(const pplhip_ctx* c, const Rank& R) {
+    pplhip_plan_settings s;
+    memset(&s, 0, sizeof(s));
+    s.tp = c->tp; s.tp_on = c->tp_on; s.comm_mode = c->comm_mode;
+    s.has_comm = R.ch[0].comm != nullptr; s.has_comm2 = R.ch[1].comm != nullptr;
+    s.emulate_tp = c->emulate_tp;
+    s.tp_overlap = c->tp_overlap; s.tp_overlap_min_tokens = c->tp_overlap_min_tokens;
+    s.dual_mode = c->dual_mode; s.dual_auto = c->dual_auto; s.has_stream2 = R.stream2 != nullptr;
+    s.dual_min_rows = c->dual_min_rows; s.dual_max_rows = c->dual_max_rows;
+    s.fuse_norm_want = c->fuse_norm_want; s.defer_on = c->defer_on;
+    s.act_fmt = c->act_fmt;
+    s.hidden_dim = c->d.hidden_dim; s.heads = c->H; s.kv_heads = c->Hkv; s.head_dim = c->D;
+    s.cache_quant_bit = c->d.cache_quant_bit; s.cache_quant_group = c->d.cache_quant_group;
+    s.decoding_attn_split_k = c->o.decoding_attn_split_k;
+    return s;
+}
+
+// the sequence-parallel residual stream is in force for this rank's steps (pplhip_ctx::fuse_norm_want)
+static bool fuse_norm_active(const pplhip_plan_settings& s, bool dump) {
+    const int hd = s.hidden_dim;
+    return s.fuse_norm_want && s.tp_on && s.tp > 1 && s.act_fmt == ACT_FP16 && !dump && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN &&
+           (s.comm_mode == 2 || s.emulate_tp);
+}
+
+// The schedule of one step: a pure function of the settings and the step's shape (no HIP call, no environment read), so that what a
+// step runs (run_launches), what pplhip_comm_info reports and what the tests check (pplhip_op_step_plan) are one decision.
+static StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape& sh) {
+    StepPlan p;
+    memset(&p, 0, sizeof(p));
+    const int64_t B = sh.batch, T = sh.num_tokens;
+    const int64_t nb_decode = std::min<int64_t>(std::max<int64_t>(sh.decoding_batches, 0), B);
+    const bool comm = s.tp_on, dump = sh.dump != 0;
+    p.schedule = SCHED_ONE_LANE;
+    p.chunk[0] = Chunk{0, B, 0, T, nb_decode};
+    // Tensor parallel: the step is cut at a request boundary into two chunks of about T/2 rows.  While the collective reduces
+    // the partial sums of one chunk on the communication stream, the compute stream runs the other chunk's block
+    // (attention part or FFN part), so the xGMI time hides under the matmuls instead of adding to them.
+    // Two-lane decode (PPLHIP_DUAL_STREAM=1): a pure-decode step of dual_min_rows..dual_max_rows rows is cut into two half-batches that run
+    // their layers on two streams, side by side.  At these sizes no kernel of the step fills the chip -- the linears are 20-256 tiles with
+    // short K loops, the attention launch a few hundred blocks -- so the halves' kernels interleave on the CUs instead of queueing behind each
+    // other's ramps and tails, and one half's HBM-bound attention runs beside the other's matrix work.  The halves share nothing but the
+    // weights and the KV slab: rows [t0, t0 + tn) of every activation buffer, a split-K workspace and an attention workspace each (Lane).
+    // Results are those of the same rows run as a step of their own.  Under tensor parallelism every half issues its all-reduces on its OWN
+    // stream and channel (direct collectives: a second flag set / scratch pair / epoch counter, k_comm.hip; RCCL: a second communicator over
+    // the same ranks) -- the all-reduce of one half runs beside the other half's matmuls with no hand-off kernels and no extra launches,
+    // which is what the chunked schedule pays +3.5 ms per 1024-row step for.  Not with int8 / fp8 activations (shared operand buffer),
+    // residual dumps or graph capture.
+    const bool identity_comm = comm && s.comm_mode != 2 && !s.has_comm;   // ranks emulated on one device (bench.py --emulate-tp)
+    if (comm && s.tp_overlap && sh.seq_starts && T >= s.tp_overlap_min_tokens && B >= 2) {
+        int64_t bm = 1, tm;
+        if (nb_decode == B) {   // pure decode: whole 128-row GEMM tiles in the first chunk (row i is request i: seq_starts is not read)
+            const int64_t r = (T / 2 + 127) / 128 * 128;
+            tm = bm = r < B ? r : B / 2;
+        } else {
+            while (bm < B - 1 && sh.seq_starts[bm] < T / 2) ++bm;  // first request boundary at or after row T/2
+            tm = sh.seq_starts[bm];
+        }
+        p.chunk[0] = Chunk{0, bm, 0, tm, std::min(nb_decode, bm)};
+        p.chunk[1] = Chunk{bm, B - bm, tm, T - tm, std::max<int64_t>(0, nb_decode - bm)};
+        p.schedule = SCHED_TWO_CHUNKS;
+    } else if (s.dual_mode && s.has_stream2 && nb_decode == B && T == B && B >= s.dual_min_rows && B <= s.dual_max_rows && B >= 2 &&
+               (!comm || identity_comm || s.comm_mode == 2 || (s.has_comm && s.has_comm2 && !s.dual_auto)) && s.act_fmt == ACT_FP16 && !dump &&
+               !sh.capturing) {
+        const int64_t bm = B >= 64 ? (B / 2 + 15) / 16 * 16 : B / 2;   // whole 16-row activation sub-tiles in the first half
+        p.chunk[0] = Chunk{0, bm, 0, bm, bm};
+        p.chunk[1] = Chunk{bm, B - bm, bm, B - bm, B - bm};
+        p.schedule = SCHED_TWO_LANES;
+        p.lane1_ws_off = bm * (int64_t)s.heads * 32 * (s.head_dim + 2);   // floats: past every row the first half can use
+    }
+    p.num_chunks = p.schedule == SCHED_ONE_LANE ? 1 : 2;
+    for (int i = 0; i < 2; ++i) p.decode_split[i] = i < p.num_chunks && p.chunk[i].nd > 0 ? decode_split(s, p.chunk[i].nd, sh.max_kv_len) : 1;
+    p.fuse_norm = fuse_norm_active(s, dump);
+    // split-K slabs stay unreduced for their consumer: at tensor-parallel size 1, weight-only quantisation, no residual dump, no chunks on the
+    // communication stream; wqkv's slabs alone also under tensor parallelism (RoPE + KV write consumes them on the rank itself, while wo / w2
+    // feed the all-reduce: their slabs are summed first)
+    p.defer_qkv = s.defer_on && s.act_fmt == ACT_FP16 && !dump && p.schedule != SCHED_TWO_CHUNKS;
+    p.defer_reduce = p.defer_qkv && !comm;
+    return p;
+}
+
+static Lane make_lane(Rank& R, int i, int64_t attn_ws_off) {
+    Lane ln;
+    ln.stream = i ? R.stream2 : R.stream;
+    ln.gemm_ws = i ? R.gemm_ws2 : R.gemm_ws;
+    ln.attn_ws = R.attn_ws + attn_ws_off;
+    ln.attn_ws_bytes = R.attn_ws_bytes - (size_t)attn_ws_off * 4;
+    ln.ch = &R.ch[i];
+    return ln;
+}
 
 // one layer linear over a chunk: fp16 activations straight into the (weight-only quantised) GEMM, or -- online_i8i8 / f8f8 -- quantised
 // per token first and multiplied in int8 / e4m3.  x rows have stride l.Kp.
 // pre_quantised: R.xq / R.sx already hold the rows (written by the RMSNorm in front of wqkv / w13).
-static int layer_linear(pplhip_ctx* c, int rank, const Linear& l, const uint16_t* x, int64_t M, void* y, int64_t ldy, bool swiglu,
+// defer: where the launch may leave its split-K slabs unreduced (the plan's defer flags decide; NULL: it reduces them itself)
+static int layer_linear(pplhip_ctx* c, int rank, Lane& lane, const Linear& l, const uint16_t* x, int64_t M, void* y, int64_t ldy, bool swiglu,
                         bool pre_quantised = false, SplitSlabs* defer = nullptr) {
     Rank& R = c->ranks[rank];
+    hipStream_t s = lane.stream;
     if (c->act_fmt == ACT_FP8) {
-        if (!pre_quantised) HIPCK(c, rank, launch_quant_act_f8(R.stream, x, M, l.Kp, l.Kp, (uint8_t*)R.xq, l.Kp, R.sx));
-        HIPCK(c, rank, launch_linear_f8(R.stream, (const uint8_t*)R.xq, R.sx, (const uint8_t*)l.w, l.scale, M, l.N, l.Kp, y, ldy, false, swiglu));
+        if (!pre_quantised) HIPCK(c, rank, launch_quant_act_f8(s, x, M, l.Kp, l.Kp, (uint8_t*)R.xq, l.Kp, R.sx));
+        HIPCK(c, rank, launch_linear_f8(s, (const uint8_t*)R.xq, R.sx, (const uint8_t*)l.w, l.scale, M, l.N, l.Kp, y, ldy, false, swiglu));
         return 0;
     }
     if (c->act_fmt == ACT_I8) {
-        if (!pre_quantised) HIPCK(c, rank, launch_quant_act(R.stream, x, M, l.Kp, l.Kp, R.xq, l.Kp, R.sx));
-        HIPCK(c, rank, launch_linear_i8(R.stream, R.xq, R.sx, (const int8_t*)l.w, l.scale, M, l.N, l.Kp, y, ldy, false, swiglu));
+        if (!pre_quantised) HIPCK(c, rank, launch_quant_act(s, x, M, l.Kp, l.Kp, R.xq, l.Kp, R.sx));
+        HIPCK(c, rank, launch_linear_i8(s, R.xq, R.sx, (const int8_t*)l.w, l.scale, M, l.N, l.Kp, y, ldy, false, swiglu));
         return 0;
     }
-    HIPCK(c, rank, launch_linear(R.stream, x, l.w, l.scale, l.qbit, l.group, M, l.N, l.Kp, y, ldy, false, R.gemm_ws, R.gemm_ws_bytes, swiglu,
-                                 (R.defer_reduce || (R.defer_qkv && defer == &R.sl_qkv)) ? defer : nullptr));
+    HIPCK(c, rank, launch_linear(s, x, l.w, l.scale, l.qbit, l.group, M, l.N, l.Kp, y, ldy, false, lane.gemm_ws, R.gemm_ws_bytes, swiglu, defer));
     return 0;
 }
 
 // attention block of layer l for one chunk: (Skip)RMSNorm -> wqkv -> RoPE + KV write -> attention -> wo (partial sums)
 // xn_ready: the fused collective of the previous half-layer already left this block's normalised input in R.xn (and the residual in R.h)
-static int layer_attention_part(pplhip_ctx* c, int rank, int l, const Chunk& k, const uint16_t* pending, int split, int threads, bool xn_ready = false) {
+static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepPlan& p, int l, const Chunk& k, const uint16_t* pending, int split,
+                                int threads, bool xn_ready = false) {
     Rank& R = c->ranks[rank];
     const pplhip_model_desc& d = c->d;
-    hipStream_t s = R.stream;
+    hipStream_t s = lane.stream;
     const int hd = d.hidden_dim, H = c->H, Hkv = c->Hkv, D = c->D;
     const int nqkv = (H + 2 * Hkv) * D;
     Layer& L = R.layers[l];
@@ -1412,65 +1565,60 @@ static int layer_attention_part(pplhip_ctx* c, int rank, int l, const Chunk& k, 
     uint16_t* h = R.h + k.t0 * hd;
     uint16_t* xn = R.xn + k.t0 * hd;
     const bool a8 = c->act_fmt != ACT_FP16;  // the norm writes the 1-byte operand of the next linear directly (no fp16 xn, no separate pass)
-    {
-        if (!xn_ready)
-            HIPCK(c, rank, launch_rmsnorm(s, h, pending ? pending + k.t0 * hd : nullptr, L.attn_norm, d.norm_eps, k.tn, hd, nullptr, xn,
-                                          pending ? h : nullptr, a8 ? R.xq : nullptr, a8 ? R.sx : nullptr, pending ? &R.sl_part2 : nullptr,
-                                          c->act_fmt == ACT_FP8));
-        R.sl_part2 = SplitSlabs{};
-        prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
-        { int rc = layer_linear(c, rank, L.wqkv, xn, k.tn, R.qkv + k.t0 * nqkv, L.wqkv.N, false, a8, &R.sl_qkv); if (rc) return rc; }
-        prof_end(R, &ev);
-    }
+    if (!xn_ready)
+        HIPCK(c, rank, launch_rmsnorm(s, h, pending ? pending + k.t0 * hd : nullptr, L.attn_norm, d.norm_eps, k.tn, hd, nullptr, xn,
+                                      pending ? h : nullptr, a8 ? R.xq : nullptr, a8 ? R.sx : nullptr, pending ? &lane.sl_part2 : nullptr,
+                                      c->act_fmt == ACT_FP8));
+    lane.sl_part2 = SplitSlabs{};
+    prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
+    if (int rc = layer_linear(c, rank, lane, L.wqkv, xn, k.tn, R.qkv + k.t0 * nqkv, L.wqkv.N, false, a8, p.defer_qkv ? &lane.sl_qkv : nullptr)) return rc;
+    prof_end(R, lane, &ev);
     const KvAddr kv = make_kv_addr(d, Hkv, D, R.kv_tokens, R.kv_cache, R.kv_scale, l);
     HIPCK(c, rank, launch_rope_kv_write(s, R.qkv, R.rope, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci,
-                                        R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &R.sl_qkv));
-    R.sl_qkv = SplitSlabs{};
+                                        R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &lane.sl_qkv));
+    lane.sl_qkv = SplitSlabs{};
     // decode rows of the chunk: per-request arrays shifted to the chunk (q rows stay absolute through seq_starts);
     // prefill requests: absolute request range
     const int64_t ci_stride = d.cache_mode == 1 ? R.max_pages : 1;
     if (k.nd > 0) {
-        if (c->o.enable_profiling == 2) {
-            // light profiling: the launch carries its own start / stop events (timestamps of the dispatch packet, no barrier
-            // packets on the stream; with split-K the reduce kernel is not included)
-            std::pair<hipEvent_t, hipEvent_t> p;
-            if (!R.prof_free.empty()) { p = R.prof_free.back(); R.prof_free.pop_back(); }
-            else { hipEventCreate(&p.first); hipEventCreate(&p.second); }
-            ev.cls = PPLHIP_PROF_ATTN_DECODE; ev.a = p.first; ev.b = p.second;
-            HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, c->kv_fmt, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
-                                              R.max_pages, k.nd, H, Hkv, D, R.max_kv_len, split, threads, R.attn_ws,
-                                              R.att + k.b0 * (int64_t)H * D, ev.a, ev.b));
-            R.prof.push_back(ev);
-        } else {
-            prof_begin(c, R, PPLHIP_PROF_ATTN_DECODE, &ev);
-            HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, c->kv_fmt, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
-                                              R.max_pages, k.nd, H, Hkv, D, R.max_kv_len, split, threads, R.attn_ws,
-                                              R.att + k.b0 * (int64_t)H * D));
-            prof_end(R, &ev);
+        // light profiling: the launch carries its own start / stop events (timestamps of the dispatch packet, no barrier
+        // packets on the stream; with split-K the reduce kernel is not included)
+        const bool light = c->o.enable_profiling == 2;
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_DECODE, &ev);   // (light: does nothing)
+        if (light) {
+            std::pair<hipEvent_t, hipEvent_t> pr;
+            if (!R.prof_free.empty()) { pr = R.prof_free.back(); R.prof_free.pop_back(); }
+            else { hipEventCreate(&pr.first); hipEventCreate(&pr.second); }
+            ev.cls = PPLHIP_PROF_ATTN_DECODE; ev.a = pr.first; ev.b = pr.second;
         }
+        HIPCK(c, rank, launch_attn_decode(s, R.qkv, kv, c->kv_fmt, R.d_seq + k.b0, R.d_sp + k.b0, R.d_ci + k.b0 * ci_stride,
+                                          R.max_pages, k.nd, H, Hkv, D, R.max_kv_len, split, threads, lane.attn_ws,
+                                          R.att + k.b0 * (int64_t)H * D, light ? ev.a : nullptr, light ? ev.b : nullptr));
+        if (light) R.prof.push_back(ev);
+        else prof_end(R, lane, &ev);
     }
     if (k.bn > k.nd) {
-        prof_begin(c, R, PPLHIP_PROF_ATTN_PREFILL, &ev);
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_PREFILL, &ev);
         // (decode requests own one token row each, so the prefill requests' rows are [t0 + nd, t0 + tn): the split-KV form for short suffixes)
         HIPCK(c, rank, launch_attn_prefill(s, R.qkv, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci, R.max_pages, k.b0 + k.nd,
-                                           k.b0 + k.bn, H, Hkv, D, R.max_seq_len, R.att, R.max_kv_len, R.attn_ws, R.attn_ws_bytes,
+                                           k.b0 + k.bn, H, Hkv, D, R.max_seq_len, R.att, R.max_kv_len, lane.attn_ws, lane.attn_ws_bytes,
                                            k.t0 + k.nd, k.tn - k.nd));
-        prof_end(R, &ev);
+        prof_end(R, lane, &ev);
     }
-    prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
-    {
-        int rc = layer_linear(c, rank, L.wo, R.att + k.t0 * (int64_t)H * D, k.tn, R.part + k.t0 * hd, hd, false, false, &R.sl_part);
-        if (rc) return rc;
-    }
-    prof_end(R, &ev);
+    prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
+    if (int rc = layer_linear(c, rank, lane, L.wo, R.att + k.t0 * (int64_t)H * D, k.tn, R.part + k.t0 * hd, hd, false, false,
+                              p.defer_reduce ? &lane.sl_part : nullptr))
+        return rc;
+    prof_end(R, lane, &ev);
     return 0;
 }
 
 // feed-forward block of layer l for one chunk: SkipRMSNorm -> w13 with fused SwiGLU (K3 + K10) -> w2 (partial sums)
-static int layer_ffn_part(pplhip_ctx* c, int rank, int l, const Chunk& k, bool xn_ready = false) {
+// keep_part2: this launch of w2 must write part2 (its consumer runs on the other lane's stream): no deferred slabs
+static int layer_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const StepPlan& p, int l, const Chunk& k, bool keep_part2, bool xn_ready = false) {
     Rank& R = c->ranks[rank];
     const pplhip_model_desc& d = c->d;
-    hipStream_t s = R.stream;
+    hipStream_t s = lane.stream;
     const int hd = d.hidden_dim;
     Layer& L = R.layers[l];
     ProfEvent ev;
@@ -1480,39 +1628,33 @@ static int layer_ffn_part(pplhip_ctx* c, int rank, int l, const Chunk& k, bool x
     const bool a8 = c->act_fmt != ACT_FP16;
     if (!xn_ready)
         HIPCK(c, rank, launch_rmsnorm(s, h, R.part + k.t0 * hd, L.ffn_norm, d.norm_eps, k.tn, hd, nullptr, xn, h, a8 ? R.xq : nullptr,
-                                      a8 ? R.sx : nullptr, &R.sl_part, c->act_fmt == ACT_FP8));
-    R.sl_part = SplitSlabs{};
-    prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
-    { int rc = layer_linear(c, rank, L.w13, xn, k.tn, act, L.w2.Kp, /*swiglu=*/true, a8); if (rc) return rc; }
-    prof_end(R, &ev);
-    prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
-    { int rc = layer_linear(c, rank, L.w2, act, k.tn, R.part2 + k.t0 * hd, hd, false, false, R.keep_part2 ? nullptr : &R.sl_part2); if (rc) return rc; }
-    prof_end(R, &ev);
+                                      a8 ? R.sx : nullptr, &lane.sl_part, c->act_fmt == ACT_FP8));
+    lane.sl_part = SplitSlabs{};
+    prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
+    if (int rc = layer_linear(c, rank, lane, L.w13, xn, k.tn, act, L.w2.Kp, /*swiglu=*/true, a8)) return rc;
+    prof_end(R, lane, &ev);
+    prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
+    if (int rc = layer_linear(c, rank, lane, L.w2, act, k.tn, R.part2 + k.t0 * hd, hd, false, false,
+                              p.defer_reduce && !keep_part2 ? &lane.sl_part2 : nullptr))
+        return rc;
+    prof_end(R, lane, &ev);
     return 0;
 }
 
-// the sequence-parallel residual stream is in force for this rank's steps (pplhip_ctx::fuse_norm_want)
-static bool fuse_norm_active(const pplhip_ctx* c, const Rank& R) {
-    const int hd = c->d.hidden_dim;
-    return c->fuse_norm_want && c->tp_on && c->tp > 1 && c->act_fmt == ACT_FP16 && !R.dump_dev && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN &&
-           (c->comm_mode == 2 || c->emulate_tp);
-}
-
-// all-reduce(sum) of the chunk's rows of `buf` ([T, hidden] fp16).  Overlapped mode: on the communication stream,
-// after the compute stream's work so far; the compute stream picks the result up through R.ev_comm[ci] later.
+// all-reduce(sum) of the chunk's rows of `buf` ([T, hidden] fp16) on the lane's channel.  Overlapped mode: on the communication stream,
+// after the lane's work so far; the compute stream picks the result up later (comm_pickup, slot ci).
 // norm_w != NULL (fuse_norm_active): the collective also folds the reduced rows into the residual stream and normalises them with norm_w --
 // afterwards R.xn holds rmsnorm(h + sum) * norm_w for every row of the chunk and R.h the new residual on the rows this rank owns.
-static int chunk_allreduce(pplhip_ctx* c, int rank, uint16_t* buf, const Chunk& k, int ci, bool overlapped, const uint16_t* norm_w = nullptr) {
+static int chunk_allreduce(pplhip_ctx* c, int rank, Lane& lane, uint16_t* buf, const Chunk& k, int ci, bool overlapped, const uint16_t* norm_w = nullptr) {
     Rank& R = c->ranks[rank];
+    Channel& ch = *lane.ch;
     const int hd = c->d.hidden_dim;
     uint16_t* p = buf + k.t0 * hd;
     auto reduce_on = [&](hipStream_t st) -> int {
         if (norm_w && c->comm_mode == 2) {
-            const bool ch1 = R.channel == 1;
-            HIPCK(c, rank, launch_p2p_allreduce_norm(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase),
-                                                     ch1 ? R.x_scratch2[R.ar_count2++ & 1] : R.x_scratch[R.ar_count++ & 1], k.tn, hd, R.h + k.t0 * hd, norm_w,
-                                                     c->d.norm_eps, R.xn + k.t0 * hd, ch1 ? ++R.p2p_epoch2 : ++R.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status,
-                                                     ch1 ? 1 : 0));
+            HIPCK(c, rank, launch_p2p_allreduce_norm(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase), ch.x_scratch[ch.ar_count++ & 1], k.tn,
+                                                     hd, R.h + k.t0 * hd, norm_w, c->d.norm_eps, R.xn + k.t0 * hd, ++ch.p2p_epoch, c->p2p_timeout_ticks,
+                                                     R.p2p_status, ch.id));
             return 0;
         }
         if (norm_w) {
@@ -1524,146 +1666,49 @@ static int chunk_allreduce(pplhip_ctx* c, int rank, uint16_t* buf, const Chunk& 
             if (nown > 0) HIPCK(c, rank, launch_rmsnorm(st, h, p + lo * hd, norm_w, c->d.norm_eps, nown, hd, nullptr, R.xn + (k.t0 + lo) * hd, h));
             return 0;
         }
-        if (c->comm_mode == 2) {
-            if (R.channel == 1)
-                HIPCK(c, rank, launch_p2p_allreduce(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase), R.x_scratch2[R.ar_count2++ & 1],
-                                                    k.tn * hd, ++R.p2p_epoch2, c->p2p_timeout_ticks, R.p2p_status, 1));
-            else
-                HIPCK(c, rank, launch_p2p_allreduce(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase), R.x_scratch[R.ar_count++ & 1],
-                                                    k.tn * hd, ++R.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status));
-        } else if (R.comm) {
-            NCCLCK(c, rank, ncclAllReduce(p, p, (size_t)k.tn * hd, ncclFloat16, ncclSum, R.channel == 1 ? R.comm2 : R.comm, st));
-        }
+        if (c->comm_mode == 2)
+            HIPCK(c, rank, launch_p2p_allreduce(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase), ch.x_scratch[ch.ar_count++ & 1], k.tn * hd,
+                                                ++ch.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status, ch.id));
+        else if (ch.comm)
+            NCCLCK(c, rank, ncclAllReduce(p, p, (size_t)k.tn * hd, ncclFloat16, ncclSum, ch.comm, st));
         return 0;
     };
-    static const int dbg = getenv("PPLHIP_TP_DEBUG") ? atoi(getenv("PPLHIP_TP_DEBUG")) : 0;
-    if (!overlapped || (dbg & 2)) return reduce_on(R.stream);
-    if (c->handoff_flags) {
-        // compute stream: "chunk ci's partial sums are complete"; communication stream: wait for that, reduce, "chunk ci is reduced"
-        HIPCK(c, rank, launch_handoff_signal(R.stream, R.hflags + ci, ++R.h_ready_ep[ci]));
-        const bool identity = c->comm_mode != 2 && !R.comm;  // ranks emulated on one device (bench.py --emulate-tp): nothing to reduce
-        HIPCK(c, rank, launch_handoff_wait(R.comm_stream, R.hflags + ci, R.h_ready_ep[ci], identity ? R.hflags + 2 + ci : nullptr,
-                                           identity ? R.h_done_ep[ci] + 1 : 0, c->p2p_timeout_ticks, R.p2p_status));
-        ++R.h_done_ep[ci];
-        if (!identity) {
-            if (int rc = reduce_on(R.comm_stream)) return rc;
-            HIPCK(c, rank, launch_handoff_signal(R.comm_stream, R.hflags + 2 + ci, R.h_done_ep[ci]));
-        }
-        return 0;
-    }
-    if (dbg & 1) {  // diagnosis: never re-record an event inside a step
-        hipEventCreateWithFlags(&R.ev_compute[ci], hipEventDisableTiming);
-        hipEventCreateWithFlags(&R.ev_comm[ci], hipEventDisableTiming);
-    }
-    HIPCK(c, rank, hipEventRecord(R.ev_compute[ci], R.stream));
-    HIPCK(c, rank, hipStreamWaitEvent(R.comm_stream, R.ev_compute[ci], 0));
-    if (int rc = reduce_on(R.comm_stream)) return rc;
-    HIPCK(c, rank, hipEventRecord(R.ev_comm[ci], R.comm_stream));
-    return 0;
+    if (!overlapped || (c->tp_debug & 2)) return reduce_on(lane.stream);
+    // (identity: ranks emulated on one device, bench.py --emulate-tp -- nothing to reduce)
+    return comm_handoff(c, rank, lane.stream, ci, c->comm_mode != 2 && !ch.comm, (c->tp_debug & 1) != 0, reduce_on);
 }
 
-// the compute stream picks up chunk ci's reduced rows
-static int wait_reduced(pplhip_ctx* c, int rank, int ci) {
-    Rank& R = c->ranks[rank];
-    if (c->handoff_flags)
-        HIPCK(c, rank, launch_handoff_wait(R.stream, R.hflags + 2 + ci, R.h_done_ep[ci], nullptr, 0, c->p2p_timeout_ticks, R.p2p_status));
-    else
-        HIPCK(c, rank, hipStreamWaitEvent(R.stream, R.ev_comm[ci], 0));
-    return 0;
-}
-
-// the launches of one step on the rank's stream(s)
-static int run_launches(pplhip_ctx* c, int rank) {
+// the launches of one step on the rank's stream(s): executes the plan, decides nothing
+static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& settings) {
     Rank& R = c->ranks[rank];
     const pplhip_model_desc& d = c->d;
     hipStream_t s = R.stream;
     const int64_t T = R.T, B = R.B;
     const int hd = d.hidden_dim;
-    const int64_t nb_decode = std::min<int64_t>(std::max<int64_t>(R.decoding_batches, 0), B);
     // (round 4: 128-thread blocks for many short requests looked 3-6 % faster in the operator micro-benchmark and measured 2 % SLOWER inside
     // the model step, interleaved A/B: 0.885 vs 0.868 ms per launch at batch 1024 / kv 520 -- not adopted)
     const int threads = c->o.decoding_attn_tpb == 512 ? 512 : 256;
     const bool comm = c->tp_on;
 
-    // Tensor parallel: the step is cut at a request boundary into two chunks of about T/2 rows.  While RCCL reduces
-    // the partial sums of one chunk on the communication stream, the compute stream runs the other chunk's block
-    // (attention part or FFN part), so the xGMI time hides under the matmuls instead of adding to them.
-    Chunk ck[2];
-    int nck = 1;
-    ck[0] = Chunk{0, B, 0, T, nb_decode};
-    if (comm && c->tp_overlap && R.h_seq && T >= c->tp_overlap_min_tokens && B >= 2) {
-        int64_t bm = 1;
-        while (bm < B - 1 && R.h_seq[bm] < T / 2) ++bm;  // first request boundary at or after row T/2
-        if (nb_decode == B) {                             // pure decode: whole 128-row GEMM tiles in the first chunk
-            const int64_t r = (T / 2 + 127) / 128 * 128;
-            bm = r < B ? r : B / 2;
-        }
-        const int64_t tm = R.h_seq[bm];
-        ck[0] = Chunk{0, bm, 0, tm, std::min(nb_decode, bm)};
-        ck[1] = Chunk{bm, B - bm, tm, T - tm, std::max<int64_t>(0, nb_decode - bm)};
-        nck = 2;
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    if (settings.dual_mode && settings.has_stream2) (void)hipStreamIsCapturing(s, &cst);   // (only a two-lane step depends on it)
+    const pplhip_step_shape shape{B, T, R.decoding_batches, R.max_kv_len, R.h_seq, cst != hipStreamCaptureStatusNone, R.dump_dev != nullptr};
+    const StepPlan p = plan_step(settings, shape);
+    const Chunk* ck = p.chunk;
+    const int nck = p.num_chunks;
+    const bool dual = p.schedule == SCHED_TWO_LANES, fuse = p.fuse_norm != 0;
+    const bool ov = p.schedule == SCHED_TWO_CHUNKS;                // collectives alternate with the other chunk's block ...
+    const bool on_comm = ov && !(c->tp_debug & 2);                 // ... on the communication stream (diagnosis: chunks, but collectives in stream)
+    if (dual && !R.dual_seen && verbose()) {
+        R.dual_seen = true;
+        fprintf(stderr, "[pplhip] rank %d: two-stream decode (rows %lld + %lld)\n", rank, (long long)ck[0].bn, (long long)ck[1].bn);
     }
-    const bool ov = nck == 2;
-    // Two-stream decode (PPLHIP_DUAL_STREAM=1): a pure-decode step of dual_min_rows..dual_max_rows rows is cut into two half-batches that run
-    // their layers on two streams, side by side.  At these sizes no kernel of the step fills the chip -- the linears are 20-256 tiles with
-    // short K loops, the attention launch a few hundred blocks -- so the halves' kernels interleave on the CUs instead of queueing behind each
-    // other's ramps and tails, and one half's HBM-bound attention runs beside the other's matrix work.  The halves share nothing but the
-    // weights and the KV slab: rows [t0, t0 + tn) of every activation buffer, a split-K workspace and an attention workspace each.  Results
-    // are those of the same rows run as a step of their own.  Under tensor parallelism every half issues its all-reduces on its OWN stream
-    // and channel (direct collectives: a second flag set / scratch pair / epoch counter, k_comm.hip; RCCL: a second communicator over the
-    // same ranks) -- the all-reduce of one half runs beside the other half's matmuls with no hand-off kernels and no extra launches, which
-    // is what the chunked schedule above pays +3.5 ms per 1024-row step for.  Not with int8 activations (shared operand buffer), residual
-    // dumps or graph capture.
-    const bool identity_comm = comm && c->comm_mode != 2 && !R.comm;   // ranks emulated on one device (bench.py --emulate-tp)
-    bool dual = false;
-    if (c->dual_mode && R.stream2 && !ov && nb_decode == B && T == B && B >= c->dual_min_rows && B <= c->dual_max_rows && B >= 2 &&
-        (!comm || identity_comm || c->comm_mode == 2 || (R.comm && R.comm2 && !c->dual_auto)) && c->act_fmt == ACT_FP16 && !R.dump_dev) {
-        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(R.stream, &cst);
-        if (cst == hipStreamCaptureStatusNone) {
-            const int64_t bm = B >= 64 ? (B / 2 + 15) / 16 * 16 : B / 2;   // whole 16-row activation sub-tiles in the first half
-            ck[0] = Chunk{0, bm, 0, bm, bm};
-            ck[1] = Chunk{bm, B - bm, bm, B - bm, B - bm};
-            nck = 2;
-            dual = true;
-            static const bool verbose_ = verbose();
-            if (verbose_ && !R.dual_seen) {
-                R.dual_seen = true;
-                fprintf(stderr, "[pplhip] rank %d: two-stream decode (rows %lld + %lld)\n", rank, (long long)bm, (long long)(B - bm));
-            }
-        }
-    }
-    // the second half's launches go out with its own stream, workspaces and deferred-slab state in the rank's working fields
-    struct HalfState { SplitSlabs sl_qkv, sl_part, sl_part2; } half2;
-    const int64_t aws_off = dual ? ck[1].b0 * (int64_t)c->H * 32 * (c->D + 2) : 0;   // floats: past every row the first half can use
-    auto enter2 = [&]() {
-        std::swap(R.stream, R.stream2); std::swap(R.gemm_ws, R.gemm_ws2);
-        R.attn_ws += aws_off; R.attn_ws_bytes -= (size_t)aws_off * 4;
-        R.channel = 1;
-        std::swap(R.sl_qkv, half2.sl_qkv); std::swap(R.sl_part, half2.sl_part); std::swap(R.sl_part2, half2.sl_part2);
-    };
-    auto leave2 = [&]() {
-        std::swap(R.stream, R.stream2); std::swap(R.gemm_ws, R.gemm_ws2);
-        R.attn_ws -= aws_off; R.attn_ws_bytes += (size_t)aws_off * 4;
-        R.channel = 0;
-        std::swap(R.sl_qkv, half2.sl_qkv); std::swap(R.sl_part, half2.sl_part); std::swap(R.sl_part2, half2.sl_part2);
-    };
-    struct Half2Guard {   // (an error return between enter2 and leave2 must not leave the rank on the second stream)
-        decltype(leave2)& l; bool in = false;
-        ~Half2Guard() { if (in) l(); }
-    } g2{leave2};
-    static const bool tpdbg2 = getenv("PPLHIP_TP_DEBUG") && (atoi(getenv("PPLHIP_TP_DEBUG")) & 2);  // diagnosis: chunks, but collectives in stream
-    int split[2] = {1, 1};
-    for (int i = 0; i < nck; ++i) split[i] = ck[i].nd > 0 ? decode_split(c, ck[i].nd, R.max_kv_len) : 1;
+    // chunk i goes out on lane i of a two-lane step, else on lane 0
+    Lane lane[2] = {make_lane(R, 0, 0), make_lane(R, 1, p.lane1_ws_off)};
+    auto lane_of = [&](int i) -> Lane& { return lane[dual ? i : 0]; };
 
-    const bool fuse = fuse_norm_active(c, R);
-    static const int defer_on = getenv("PPLHIP_DEFER_REDUCE") ? atoi(getenv("PPLHIP_DEFER_REDUCE")) : 1;
-    R.defer_reduce = defer_on && !comm && c->act_fmt == ACT_FP16 && !R.dump_dev && (nck == 1 || dual);
-    R.defer_qkv = defer_on && c->act_fmt == ACT_FP16 && !R.dump_dev && (nck == 1 || dual);   // (wo / w2 feed the all-reduce: their slabs are summed first)
-    R.keep_part2 = false;
-    R.sl_qkv = R.sl_part = R.sl_part2 = SplitSlabs{};
     ProfEvent ev_run, ev;
-    prof_begin(c, R, PPLHIP_PROF_RUN, &ev_run);
+    prof_begin(c, R, lane[0], PPLHIP_PROF_RUN, &ev_run);
     HIPCK(c, rank, launch_embedding(s, R.d_tok, R.embed, T, hd, R.h));
     const uint16_t* pending = nullptr;
     int rc;
@@ -1675,31 +1720,26 @@ static int run_launches(pplhip_ctx* c, int rank) {
     }
     for (int l = 0; l < d.num_layers; ++l) {
         // (the last layer's w2 writes part2 in both halves: the final norm gathers rows of both on the first stream)
-        R.keep_part2 = dual && l == d.num_layers - 1;
+        const bool keep_part2 = dual && l == d.num_layers - 1;
         for (int i = 0; i < nck; ++i) {
-            if (ov && l > 0 && !tpdbg2 && (rc = wait_reduced(c, rank, i))) return rc;  // part2 rows of chunk i are reduced
-            if (dual && i == 1) { enter2(); g2.in = true; }
-            if ((rc = layer_attention_part(c, rank, l, ck[i], pending, split[i], threads, fuse && l > 0))) return rc;
-            if (comm && (rc = chunk_allreduce(c, rank, R.part, ck[i], i, ov, fuse ? R.layers[l].ffn_norm : nullptr))) return rc;
-            if (g2.in) { leave2(); g2.in = false; }
+            if (on_comm && l > 0 && (rc = comm_pickup(c, rank, s, i))) return rc;  // part2 rows of chunk i are reduced
+            if ((rc = layer_attention_part(c, rank, lane_of(i), p, l, ck[i], pending, p.decode_split[i], threads, fuse && l > 0))) return rc;
+            if (comm && (rc = chunk_allreduce(c, rank, lane_of(i), R.part, ck[i], i, ov, fuse ? R.layers[l].ffn_norm : nullptr))) return rc;
         }
         for (int i = 0; i < nck; ++i) {
-            if (ov && !tpdbg2 && (rc = wait_reduced(c, rank, i))) return rc;            // part rows of chunk i are reduced
-            if (dual && i == 1) { enter2(); g2.in = true; }
-            if ((rc = layer_ffn_part(c, rank, l, ck[i], fuse))) return rc;
+            if (on_comm && (rc = comm_pickup(c, rank, s, i))) return rc;            // part rows of chunk i are reduced
+            if ((rc = layer_ffn_part(c, rank, lane_of(i), p, l, ck[i], keep_part2, fuse))) return rc;
             // (fused: the collective behind w2 normalises for the NEXT consumer -- the next layer's attention norm, or the final norm)
-            if (comm && (rc = chunk_allreduce(c, rank, R.part2, ck[i], i, ov, !fuse ? nullptr : (l + 1 < d.num_layers ? R.layers[l + 1].attn_norm : R.norm)))) return rc;
-            if (g2.in) { leave2(); g2.in = false; }
+            if (comm && (rc = chunk_allreduce(c, rank, lane_of(i), R.part2, ck[i], i, ov, !fuse ? nullptr : (l + 1 < d.num_layers ? R.layers[l + 1].attn_norm : R.norm)))) return rc;
         }
         pending = fuse ? nullptr : R.part2;
         if (R.dump_dev) {
-            if (ov && !tpdbg2) for (int i = 0; i < nck; ++i) if ((rc = wait_reduced(c, rank, i))) return rc;
+            if (on_comm) for (int i = 0; i < nck; ++i) if ((rc = comm_pickup(c, rank, s, i))) return rc;
             HIPCK(c, rank, hipMemcpyAsync(R.dump_dev + (size_t)(l + 1) * 2 * dump_n, R.h, dump_n * 2, hipMemcpyDeviceToDevice, s));
             HIPCK(c, rank, hipMemcpyAsync(R.dump_dev + ((size_t)(l + 1) * 2 + 1) * dump_n, R.part2, dump_n * 2, hipMemcpyDeviceToDevice, s));
         }
     }
-    if (ov && !tpdbg2) for (int i = 0; i < nck; ++i) if ((rc = wait_reduced(c, rank, i))) return rc;
-    R.keep_part2 = false;
+    if (on_comm) for (int i = 0; i < nck; ++i) if ((rc = comm_pickup(c, rank, s, i))) return rc;
     if (dual) {   // the first stream goes on behind the second half's last layer
         HIPCK(c, rank, hipEventRecord(R.ev_join, R.stream2));
         HIPCK(c, rank, hipStreamWaitEvent(s, R.ev_join, 0));
@@ -1713,50 +1753,40 @@ static int run_launches(pplhip_ctx* c, int rank) {
         if (T == B) hn = R.xn;
         else HIPCK(c, rank, launch_gather_last_rows(s, R.xn, R.d_seq, B, hd, R.hn));
     } else {
-        HIPCK(c, rank, launch_rmsnorm(s, R.h, pending, R.norm, d.norm_eps, B, hd, R.d_seq, R.hn, nullptr, nullptr, nullptr, pending ? &R.sl_part2 : nullptr));
+        HIPCK(c, rank, launch_rmsnorm(s, R.h, pending, R.norm, d.norm_eps, B, hd, R.d_seq, R.hn, nullptr, nullptr, nullptr, pending ? &lane[0].sl_part2 : nullptr));
     }
-    R.sl_part2 = SplitSlabs{};
-    prof_begin(c, R, PPLHIP_PROF_GEMM, &ev);
+    prof_begin(c, R, lane[0], PPLHIP_PROF_GEMM, &ev);
     if (!comm) {
         HIPCK(c, rank, launch_linear(s, hn, R.output.w, nullptr, 0, 0, B, R.output.N, hd, R.logits, d.vocab_size, true, R.gemm_ws, R.gemm_ws_bytes));
-        prof_end(R, &ev);
+        prof_end(R, lane[0], &ev);
     } else {
         const int vl = c->vocab_local;
         HIPCK(c, rank, launch_linear(s, hn, R.output.w, nullptr, 0, 0, B, vl, hd, R.logits_local, vl, true, R.gemm_ws, R.gemm_ws_bytes));
-        prof_end(R, &ev);
+        prof_end(R, lane[0], &ev);
         // every collective of this communicator is issued on ONE stream (the communication stream when overlapping)
-        hipStream_t cs = (ov && !tpdbg2) ? R.comm_stream : s;
-        if (ov && !tpdbg2) {
-            if (c->handoff_flags) {
-                HIPCK(c, rank, launch_handoff_signal(s, R.hflags + 0, ++R.h_ready_ep[0]));
-                HIPCK(c, rank, launch_handoff_wait(cs, R.hflags + 0, R.h_ready_ep[0], nullptr, 0, c->p2p_timeout_ticks, R.p2p_status));
-            } else {
-                HIPCK(c, rank, hipEventRecord(R.ev_compute[0], s));
-                HIPCK(c, rank, hipStreamWaitEvent(cs, R.ev_compute[0], 0));
+        Channel& ch = R.ch[0];
+        auto gather_on = [&](hipStream_t cs) -> int {
+            if (c->comm_mode == 2) {  // every rank pulls every shard straight into its [B, V] logits
+                HIPCK(c, rank, launch_p2p_allgather(cs, R.peers, R.global_rank, c->tp, R.x_local, R.logits, B, (int64_t)vl * 4,
+                                                    (int64_t)d.vocab_size * 4, ++ch.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status));
+            } else if (ch.comm) {
+                NCCLCK(c, rank, ncclAllGather(R.logits_local, R.logits_gather, (size_t)B * vl, ncclFloat32, ch.comm, cs));
+            } else {  // world size 1 without a communicator cannot happen (tp_on implies one of the two)
+                return fail(c, rank, PPLHIP_OTHER_ERROR, "tensor-parallel step without collectives");
             }
-        }
-        if (c->comm_mode == 2) {  // every rank pulls every shard straight into its [B, V] logits
-            HIPCK(c, rank, launch_p2p_allgather(cs, R.peers, R.global_rank, c->tp, R.x_local, R.logits, B, (int64_t)vl * 4,
-                                                (int64_t)d.vocab_size * 4, ++R.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status));
-        } else if (R.comm) {
-            NCCLCK(c, rank, ncclAllGather(R.logits_local, R.logits_gather, (size_t)B * vl, ncclFloat32, R.comm, cs));
-        } else {  // world size 1 without a communicator cannot happen (tp_on implies one of the two)
-            return fail(c, rank, PPLHIP_OTHER_ERROR, "tensor-parallel step without collectives");
-        }
-        if (ov && !tpdbg2) {
-            if (c->handoff_flags) {
-                HIPCK(c, rank, launch_handoff_signal(cs, R.hflags + 2, ++R.h_done_ep[0]));
-                if ((rc = wait_reduced(c, rank, 0))) return rc;
-            } else {
-                HIPCK(c, rank, hipEventRecord(R.ev_comm[0], cs));
-                HIPCK(c, rank, hipStreamWaitEvent(s, R.ev_comm[0], 0));
-            }
+            return 0;
+        };
+        if (!on_comm) {
+            if ((rc = gather_on(s))) return rc;
+        } else {
+            if ((rc = comm_handoff(c, rank, s, 0, false, false, gather_on))) return rc;
+            if ((rc = comm_pickup(c, rank, s, 0))) return rc;
         }
         for (int r = 0; r < c->tp && c->comm_mode != 2; ++r)
             HIPCK(c, rank, hipMemcpy2DAsync(R.logits + (size_t)r * vl, (size_t)d.vocab_size * 4, R.logits_gather + (size_t)r * B * vl,
                                             (size_t)vl * 4, (size_t)vl * 4, B, hipMemcpyDeviceToDevice, s));
     }
-    prof_end(R, &ev_run);
+    prof_end(R, lane[0], &ev_run);
     return 0;
 }
 
@@ -1769,13 +1799,13 @@ static int run_launches(pplhip_ctx* c, int rank) {
 // (PPLHIP_DECODE_GRAPH=1).  Round 4, with the step at 2.3 ms: batch 1 / 2 2.33 / 2.53 -> 2.28 / 2.48 ms replayed, nothing from batch 4 up;
 // still opt-in (a paged cache changes the page-table width, hence the captured shape, every page_size steps).
 // Never under tensor parallelism (collectives on a second stream) or profiling.
-static int run_decode_graph(pplhip_ctx* c, int rank, bool* done) {
+static int run_decode_graph(pplhip_ctx* c, int rank, const pplhip_plan_settings& settings, bool* done) {
     Rank& R = c->ranks[rank];
     *done = false;
     const int64_t B = R.B;
     const int64_t nb_decode = std::min<int64_t>(std::max<int64_t>(R.decoding_batches, 0), B);
     if (!c->graph_on || c->tp_on || c->o.enable_profiling || R.T != B || nb_decode != B || B > c->graph_max_batch) return 0;
-    const uint64_t key = (uint64_t)B | ((uint64_t)decode_split(c, B, R.max_kv_len) << 24) | ((uint64_t)R.max_pages << 32);
+    const uint64_t key = (uint64_t)B | ((uint64_t)decode_split(settings, B, R.max_kv_len) << 24) | ((uint64_t)R.max_pages << 32);
     auto it = R.graphs.find(key);
     if (it == R.graphs.end()) {  // first sight: run eagerly (one-time function attributes, lazily loaded code objects)
         if (R.graphs.size() >= 32) {  // drop the least recently used shape
@@ -1791,7 +1821,7 @@ static int run_decode_graph(pplhip_ctx* c, int rank, bool* done) {
     if (!it->second.exec) {
         hipGraph_t g = nullptr;
         HIPCK(c, rank, hipStreamBeginCapture(R.stream, hipStreamCaptureModeThreadLocal));
-        const int rc = run_launches(c, rank);
+        const int rc = run_launches(c, rank, settings);
         const hipError_t e = hipStreamEndCapture(R.stream, &g);
         if (rc) { if (g) hipGraphDestroy(g); return rc; }
         if (e != hipSuccess || !g) { (void)hipGetLastError(); c->graph_on = false; return 0; }  // capture unsupported here: eager from now on
@@ -1813,15 +1843,13 @@ int pplhip_comm_info(pplhip_ctx* c, int64_t rows, pplhip_comm_info_t* out) {
     memset(out, 0, sizeof(*out));
     out->mode = c->comm_mode;
     out->selftest = c->selftest;
-    out->has_rccl = !c->ranks.empty() && c->ranks[0].comm != nullptr;
+    out->has_rccl = !c->ranks.empty() && c->ranks[0].ch[0].comm != nullptr;
     out->dual_min_rows = c->dual_mode ? c->dual_min_rows : 0;
     out->dual_max_rows = c->dual_mode ? c->dual_max_rows : 0;
-    // the schedule run_launches picks for a pure-decode step of `rows` rows (int8 activations, residual dumps and graph capture aside)
-    const Rank& R = c->ranks[0];
-    const bool two_chunks = c->tp_on && c->tp_overlap && rows >= c->tp_overlap_min_tokens && rows >= 2;
-    const bool two_streams = !two_chunks && c->dual_mode && R.stream2 && rows >= c->dual_min_rows && rows <= c->dual_max_rows && rows >= 2 &&
-                             (!c->tp_on || c->comm_mode == 2 || !R.comm || (R.comm && R.comm2 && !c->dual_auto)) && c->act_fmt == ACT_FP16;
-    out->schedule = two_chunks ? 2 : (two_streams ? 1 : 0);
+    // the schedule plan_step picks for a pure-decode step of `rows` rows (one token per request; no residual dump, no graph capture)
+    static const int64_t held[1] = {0};   // "the rank holds a host copy of seq_starts": a pure-decode plan never reads it
+    const pplhip_step_shape shape{rows, rows, rows, 0, held, 0, 0};
+    out->schedule = plan_step(plan_settings(c, c->ranks[0]), shape).schedule;
     snprintf(out->notes, sizeof(out->notes), "%s", c->comm_notes.c_str());
     return 0;
 }
@@ -1835,8 +1863,9 @@ int pplhip_comm_allreduce_us(pplhip_ctx* c, int rank, int64_t rows, int32_t iter
     Rank& R = c->ranks[rank];
     *us = -1.f;
     if (!c->tp_on || rows > R.cap_T) return PPLHIP_INVALID_VALUE;
-    if (path == 1 && !R.comm) return 0;              // no RCCL communicator: nothing to compare with
-    if (path == 0 && c->comm_mode != 2 && !R.comm) return 0;
+    ncclComm_t rccl = R.ch[0].comm;
+    if (path == 1 && !rccl) return 0;                // no RCCL communicator: nothing to compare with
+    if (path == 0 && c->comm_mode != 2 && !rccl) return 0;
     HIPCK(c, rank, hipSetDevice(R.device));
     struct Ev {   // destroyed on every return path
         hipEvent_t e = nullptr;
@@ -1847,10 +1876,12 @@ int pplhip_comm_allreduce_us(pplhip_ctx* c, int rank, int64_t rows, int32_t iter
     hipEvent_t e0 = ev0.e, e1 = ev1.e;
     const int hd = c->d.hidden_dim;
     const Chunk k{0, rows, 0, rows, rows};
+    Lane lane = make_lane(R, 0, 0);
+    const uint16_t* norm_w = fuse_norm_active(plan_settings(c, R), R.dump_dev != nullptr) ? R.norm : nullptr;
     for (int it = -2; it < iters; ++it) {            // two warm-up rounds
         if (it == 0) HIPCK(c, rank, hipEventRecord(e0, R.stream));
-        if (path == 1) NCCLCK(c, rank, ncclAllReduce(R.part, R.part, (size_t)rows * hd, ncclFloat16, ncclSum, R.comm, R.stream));
-        else if (int rc = chunk_allreduce(c, rank, R.part, k, 0, false, fuse_norm_active(c, R) ? R.norm : nullptr)) return rc;   // what a step issues
+        if (path == 1) NCCLCK(c, rank, ncclAllReduce(R.part, R.part, (size_t)rows * hd, ncclFloat16, ncclSum, rccl, R.stream));
+        else if (int rc = chunk_allreduce(c, rank, lane, R.part, k, 0, false, norm_w)) return rc;   // what a step issues
     }
     HIPCK(c, rank, hipEventRecord(e1, R.stream));
     HIPCK(c, rank, hipStreamSynchronize(R.stream));
@@ -1869,8 +1900,9 @@ int pplhip_run(pplhip_ctx* c, int rank, int cache_prefill) {
     HIPCK(c, rank, hipSetDevice(R.device));
     if (R.B == 0) return 0;
     bool done = false;
-    if (int rc = run_decode_graph(c, rank, &done)) return rc;
-    return done ? 0 : run_launches(c, rank);
+    const pplhip_plan_settings settings = plan_settings(c, R);   // once per step
+    if (int rc = run_decode_graph(c, rank, settings, &done)) return rc;
+    return done ? 0 : run_launches(c, rank, settings);
 }
 
 // Diagnosis entry point (tests bisect a logits difference per layer with it): pplhip_run with the residual stream captured after
@@ -1885,7 +1917,7 @@ int pplhip_debug_run_dump(pplhip_ctx* c, int rank, float* hidden_dump_host) {
     const int L = c->d.num_layers;
     const size_t n = (size_t)R.T * c->d.hidden_dim;
     HIPCK(c, rank, hipMalloc((void**)&R.dump_dev, (size_t)(L + 1) * 2 * n * 2));
-    int rc = run_launches(c, rank);
+    int rc = run_launches(c, rank, plan_settings(c, R));
     std::vector<uint16_t> host((size_t)(L + 1) * 2 * n);
     hipError_t e = hipStreamSynchronize(R.stream);
     if (e == hipSuccess) e = hipMemcpy(host.data(), R.dump_dev, host.size() * 2, hipMemcpyDeviceToHost);
@@ -2149,6 +2181,12 @@ int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx, const voi
                         void* y, int32_t out_fp32, int32_t swiglu) {
     return op_rc(launch_linear_f8((hipStream_t)stream, (const uint8_t*)xq, sx, (const uint8_t*)w, (const uint16_t*)scale, M, N, K, y,
                                   swiglu ? N / 2 : N, out_fp32 != 0, swiglu != 0));
+}
+
+int pplhip_op_step_plan(const pplhip_plan_settings* settings, const pplhip_step_shape* shape, pplhip_step_plan* out) {
+    if (!settings || !shape || !out || shape->batch < 0 || shape->num_tokens < 0) return PPLHIP_INVALID_VALUE;
+    *out = plan_step(*settings, *shape);
+    return 0;
 }
 
 int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out) {

@@ -83,6 +83,32 @@ class CommInfo(C.Structure):
                 ("dual_min_rows", C.c_int64), ("dual_max_rows", C.c_int64), ("notes", C.c_char * 512)]
 
 
+# pplhip_op_step_plan (test support): the step schedule as a pure function
+SCHED_ONE_LANE, SCHED_TWO_LANES, SCHED_TWO_CHUNKS = 0, 1, 2   # CommInfo.schedule / StepPlan.schedule
+
+
+class Chunk(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("b0", "bn", "t0", "tn", "nd")]
+
+
+class PlanSettings(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tp", "tp_on", "comm_mode", "has_comm", "has_comm2", "emulate_tp", "tp_overlap", "dual_mode",
+                                          "dual_auto", "has_stream2")] + \
+               [(n, C.c_int64) for n in ("tp_overlap_min_tokens", "dual_min_rows", "dual_max_rows")] + \
+               [(n, C.c_int32) for n in ("fuse_norm_want", "defer_on", "act_fmt", "hidden_dim", "heads", "kv_heads", "head_dim",
+                                          "cache_quant_bit", "cache_quant_group", "decoding_attn_split_k")]
+
+
+class StepShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("num_tokens", C.c_int64), ("decoding_batches", C.c_int64), ("max_kv_len", C.c_int64),
+                ("seq_starts", C.c_void_p), ("capturing", C.c_int32), ("dump", C.c_int32)]
+
+
+class StepPlan(C.Structure):
+    _fields_ = [("schedule", C.c_int32), ("num_chunks", C.c_int32), ("chunk", Chunk * 2), ("decode_split", C.c_int32 * 2),
+                ("fuse_norm", C.c_int32), ("defer_reduce", C.c_int32), ("defer_qkv", C.c_int32), ("lane1_ws_off", C.c_int64)]
+
+
 # every symbol include/pplhip.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "pplhip_version", "pplhip_device_count", "pplhip_get_unique_id", "pplhip_init", "pplhip_destroy",
@@ -91,7 +117,7 @@ SYMBOLS = [
     "pplhip_kv_block_bytes", "pplhip_kv_capacity", "pplhip_kv_alloc", "pplhip_kv_ptrs", "pplhip_kv_read",
     "pplhip_kv_write", "pplhip_kv_fill_synthetic", "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
     "pplhip_sample", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
-    "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
+    "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
     "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
@@ -149,6 +175,10 @@ def lib():
         L.pplhip_op_linear.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, i32]
         L.pplhip_op_linear_swiglu.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp]
         L.pplhip_op_linear_ex.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, i64, i32, vp, u64, i32, C.c_char_p, i32]
+        # (PPLHIP_LIB may name a 1.2 build from before this entry point: bench.py and the profiles/ scripts must still load it for A/B runs;
+        # tests/test_abi.py holds the product's own library to the export)
+        if hasattr(L, "pplhip_op_step_plan"):
+            L.pplhip_op_step_plan.argtypes = [C.POINTER(PlanSettings), C.POINTER(StepShape), C.POINTER(StepPlan)]
         L.pplhip_op_rmsnorm_quant.argtypes = [vp, vp, vp, vp, C.c_float, i64, i32, vp, vp, vp]
         L.pplhip_op_quant_act.argtypes = [vp, vp, i64, i32, vp, vp]
         L.pplhip_op_quant_weight.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -173,6 +203,21 @@ def linear_route(x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws=None, ws_b
     buf = C.create_string_buffer(1024)
     rc = lib().pplhip_op_linear_ex(stream, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws, ws_bytes, int(dry_run), buf, 1024)
     return rc, buf.value.decode()
+
+
+def step_plan(settings, batch, num_tokens, decoding_batches, seq_starts=None, max_kv_len=0, capturing=False, dump=False):
+    """pplhip_op_step_plan (no device): the plan of a step as a dict.  settings: PlanSettings field -> value (the rest 0);
+    seq_starts: the host copy, None when the rank holds none."""
+    st = PlanSettings(**settings)
+    ss = None if seq_starts is None else np.ascontiguousarray(seq_starts, dtype=np.int64)
+    sh = StepShape(batch, num_tokens, decoding_batches, max_kv_len, None if ss is None else ss.ctypes.data, int(capturing), int(dump))
+    out = StepPlan()
+    rc = lib().pplhip_op_step_plan(C.byref(st), C.byref(sh), C.byref(out))
+    if rc:
+        raise PplHipError(f"pplhip_op_step_plan -> {STATUS.get(rc, rc)}")
+    return {"schedule": out.schedule, "chunks": [tuple(getattr(out.chunk[i], n) for n in ("b0", "bn", "t0", "tn", "nd")) for i in range(out.num_chunks)],
+            "decode_split": [out.decode_split[i] for i in range(out.num_chunks)], "fuse_norm": bool(out.fuse_norm),
+            "defer_reduce": bool(out.defer_reduce), "defer_qkv": bool(out.defer_qkv), "lane1_ws_off": out.lane1_ws_off}
 
 
 def make_desc(**kw):

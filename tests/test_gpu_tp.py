@@ -158,6 +158,8 @@ def test_tensor_parallel_group_on_one_device(monkeypatch, tp, mode, overlap):
     rng = np.random.RandomState(tp)
     prompts = [rng.randint(3, 2048, size=n) for n in (40, 3, 129, 1, 16, 77)]
     check(f"tp{tp}_tiny_mode{mode}_ov{int(overlap)}", generate(g, prompts, 4), k=1.5)   # observed (r02) <= 0.98e-3, int8 KV
+    # what the context reports for the decode steps it just ran (one plan behind the step and the report)
+    assert g.ctx.comm_info(len(prompts))["schedule"] == m.COMM_SCHEDULES[m.SCHED_TWO_CHUNKS if overlap else m.SCHED_ONE_LANE]
     g.close()
 
 
@@ -178,6 +180,7 @@ def test_tensor_parallel_two_stream_decode(monkeypatch, tp, mode):
     rng = np.random.RandomState(tp)
     prompts = [rng.randint(3, 2048, size=n) for n in (40, 3, 29, 1, 16, 77, 5, 9, 2, 33, 12)]
     check(f"tp{tp}_tiny_mode{mode}_two_stream", generate(g, prompts, 5), k=1.5)
+    assert g.ctx.comm_info(len(prompts))["schedule"] == m.COMM_SCHEDULES[m.SCHED_TWO_LANES]
     g.close()
 
 
