@@ -54,9 +54,14 @@ typedef struct pplhip_model_desc {
     float norm_eps;          /* RMSNorm epsilon (graph attribute in the reference; 1e-5 for LLaMA-2) */
     float rope_theta;        /* 10000 for LLaMA-2 */
     int32_t max_position;    /* size of the host-built cos/sin table */
-    int32_t cache_quant_bit;   /* 0 (fp16 KV) or 8 (int8 / fp8 KV)      src/generator/llm_generator.cc:131-136 */
+    int32_t cache_quant_bit;   /* 0 (fp16 KV), 8 (int8 / fp8 KV) or 4 (int4 KV)   src/generator/llm_generator.cc:131-136 */
     int32_t cache_quant_group; /* 1 with bit 0 (fp16); 8 with bit 8 (int8, one fp16 scale per 8 channels); head_dim (32, 64, 128)
-                                  with bit 8: fp8 e4m3fn, one power-of-two fp16 scale per head row (library 1.2; DESIGN.md numerics) */
+                                  with bit 8: fp8 e4m3fn, one power-of-two fp16 scale per head row (library 1.2; DESIGN.md numerics);
+                                  32 with bit 4: int4 (nibble = q + 8, two channels per byte, low nibble first), one fp16 scale of 8
+                                  significant bits per 32 channels, head_dim 32, 64 or 128: a head row is head_dim / 2 bytes and
+                                  head_dim / 32 scales.  The pair arrived without a version bump (pplhip_version() stays 1.2): a
+                                  client tells a library that has it by pplhip_init accepting it (older 1.2 libraries return
+                                  PPLHIP_INVALID_VALUE) */
     int32_t cache_layout;      /* 0..3                                  src/engine/llm_engine.cc:122-166 */
     int32_t cache_mode;        /* 0 contiguous ranges, 1 paged          src/generator/llm_generator.cc:486-560 */
     int32_t page_size;         /* tokens per page when cache_mode == 1 */
@@ -438,7 +443,7 @@ PPLHIP_API int pplhip_op_sample(void* stream, const float* logits, const float* 
 /* description of a KV slab for the attention / cache-write operators */
 typedef struct pplhip_kv_view {
     void* cache;          /* fp16 or int8 */
-    void* scale;          /* fp16, NULL when quant_bit == 0 */
+    void* scale;          /* fp16, NULL when quant_bit == 0 (quant_bit / quant_group: the pairs of pplhip_model_desc, (4, 32) included) */
     int64_t max_tokens;   /* N */
     int32_t num_layers;   /* L */
     int32_t kv_heads;     /* h (per rank) */

@@ -16,6 +16,16 @@
 //   8-channel partial dot product, not each element.
 //   fp8 KV (KV_FP8): e4m3 bytes -> fp32 exactly (v_cvt_pk_f32_fp8); the row's power-of-two scale multiplies K's score and V's
 //   probability -- both exact in fp32, so the kernel computes attention over the exactly dequantised rows.
+//   int4 KV (KV_I4G32): a lane's 16-byte piece is one quant group of 32 channels (q and acc of 32 floats; 16 / 32 / 64 rows per wave-load at
+//   head_dim 128 / 64 / 32).  The nibbles of a word are masked into bytes (even and odd channels) and converted with v_cvt_f32_ubyteN; the
+//   + 8 is folded out like int8's 128 (8 sum(q) per group for the score, 8 sum(p s) for V); the group's scale multiplies the lane's
+//   partial dot product and the probability.  (A whole piece per lane rather than an 8-byte half: one scale and one correction per lane, and
+//   16-byte loads -- 128 bytes per lane in flight -- as in every other format.  The price is registers: q, acc, four K / V pieces and their
+//   addresses fill the 128 VGPRs of four waves per SIMD; empty asm statements (k_attn_decode_dev.h) keep the scheduler from converting all
+//   four keys' nibbles ahead of their use (~250 VGPRs otherwise), 11-16 dwords still go to scratch.  Build variants with room for 168 and 243
+//   VGPRs (three and two waves per SIMD, no or less scratch) were slower at 7B, batch 1024: 805 and 822 us against 779 us per launch
+//   (measured before the nibbles' byte form was pinned, which took the launch to 638 us).
+//   The kernel is bound by its instruction count, not by HBM: DESIGN.md "numerics", profiles/kv_i4_step.jsonl.)
 // Numerics: fp32 everywhere, output rounded to fp16 once.  Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
 #include <hip/hip_ext.h>
@@ -94,9 +104,9 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
         if (e != hipSuccess || split == 1) return e;
         return launch_attn_reduce(s, workspace, split, nb * H, D, out);
     }
-    if ((kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8) || (D != 128 && D != 64 && D != 32)) return hipErrorInvalidValue;
+    if ((kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8 && kv_fmt != KV_I4G32) || (D != 128 && D != 64 && D != 32)) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
-    dispatch_int<KV_I8G8, KV_FP16, KV_FP8>(kv_fmt, [&](auto QB) {
+    dispatch_int<KV_I8G8, KV_FP16, KV_FP8, KV_I4G32>(kv_fmt, [&](auto QB) {
         dispatch_int<128, 64, 32>(D, [&](auto DD) {
             e = launch_decode_t<QB, DD>(s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, nb, H, Hkv, split, threads, workspace,
                                         out, t0, t1);

@@ -35,7 +35,10 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
     // q fragment (unscaled fp16 -> fp32); the softmax scale is applied to the score
     const uint16_t* qrow = qkv + seq_starts[b] * (int64_t)(H + 2 * Hkv) * D + (int64_t)hq * D + ch0;
     float q[CH];
-    if constexpr (CH == 16) {
+    if constexpr (CH == 32) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) unpack8(*reinterpret_cast<const uint4*>(qrow + 8 * i), q + 8 * i);
+    } else if constexpr (CH == 16) {
         unpack8(*reinterpret_cast<const uint4*>(qrow), q);
         unpack8(*reinterpret_cast<const uint4*>(qrow + 8), q + 8);
     } else {
@@ -51,13 +54,19 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
             qsum[gi] = s * 128.0f;
         }
     }
+    if constexpr (QBIT == KV_I4G32) {   // the lane's piece is one group: 8 sum(q) takes the + 8 of the nibbles out of the score
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) s += q[i];
+        qsum[0] = s * 8.0f;
+    }
     const float sm_scale = 1.0f / sqrtf((float)D);
 
     float m = -1e30f, l = 0.f;
     float acc[CH];
 #pragma unroll
     for (int i = 0; i < CH; ++i) acc[i] = 0.f;
-    float vcorr[C::NG > 0 ? C::NG : 1];  // int8: sum of p*scale per group (x128 bias correction)
+    float vcorr[C::NG > 0 ? C::NG : 1];  // int8: sum of p*scale per group (x128 bias correction); int4: [0] alone, the piece's group (x8)
 #pragma unroll
     for (int gi = 0; gi < (C::NG > 0 ? C::NG : 1); ++gi) vcorr[gi] = 0.f;
 
@@ -112,7 +121,7 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                     ksc[u] = ksbase[slot * kh.srow];
                     vsc[u] = vsbase[slot * kh.srow];
                 }
-            } else if constexpr (QBIT == KV_FP8) {  // the row's 2^e
+            } else if constexpr (QBIT == KV_FP8 || QBIT == KV_I4G32) {  // the row's 2^e; int4: the scale of the lane's piece
                 ksc[u] = ksbase[slot * kh.srow];
                 vsc[u] = vsbase[slot * kh.srow];
             }
@@ -136,6 +145,23 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                     const float sc = h2f((uint16_t)(ksc[u] >> (16 * gi)));
                     d = fmaf(pd, sc, d);
                 }
+            } else if constexpr (QBIT == KV_I4G32) {  // nibbles as bytes (even / odd channels of a word) -> v_cvt_f32_ubyteN; the scale on the group's sum
+                uint32_t w[4] = {kraw[u].x, kraw[u].y, kraw[u].z, kraw[u].w};
+                // one key's 32 conversions at a time: the empty asm ties this key's words to the previous key's score, else the scheduler
+                // converts all four keys' nibbles ahead of the first fma and the kernel needs ~250 VGPRs
+                if (u > 0) asm("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "v"(s[u - 1]));
+                float pd = -qsum[0];
+#pragma unroll
+                for (int wi = 0; wi < 4; ++wi) {
+                    uint32_t ev = w[wi] & 0x0f0f0f0fu, od = (w[wi] >> 4) & 0x0f0f0f0fu;
+                    asm("" : "+v"(ev), "+v"(od));   // keep the byte form: folded into (w >> 4 k) & 15 every nibble costs a v_bfe_u32 in front of v_cvt_f32_ubyte0
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        pd = fmaf(q[8 * wi + 2 * i], (float)((ev >> (8 * i)) & 0xffu), pd);
+                        pd = fmaf(q[8 * wi + 2 * i + 1], (float)((od >> (8 * i)) & 0xffu), pd);
+                    }
+                }
+                d = pd * h2f((uint16_t)ksc[u]);
             } else if constexpr (QBIT == KV_FP8) {  // e4m3 -> fp32 exactly (v_cvt_pk_f32_fp8); the row's 2^e goes onto the score
                 float kf[16];
                 cvt_fp8x16_f32(kraw[u], kf);
@@ -165,6 +191,7 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
 #pragma unroll
             for (int gi = 0; gi < C::NG; ++gi) vcorr[gi] *= alpha;
         }
+        if constexpr (QBIT == KV_I4G32) vcorr[0] *= alpha;
 #pragma unroll
         for (int u = 0; u < DEC_UNROLL; ++u) {
             const float p = valid[u] ? __expf(s[u] - m) : 0.f;
@@ -181,6 +208,21 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
                         const uint32_t word = w[(gi * 8 + i) >> 2];
                         const float vf = (float)((word >> (8 * (i & 3))) & 0xffu);
                         acc[gi * 8 + i] = fmaf(ps, vf, acc[gi * 8 + i]);
+                    }
+                }
+            } else if constexpr (QBIT == KV_I4G32) {  // the group's scale on the probability; the + 8 comes out at the end
+                uint32_t w[4] = {vraw[u].x, vraw[u].y, vraw[u].z, vraw[u].w};
+                const float ps = p * h2f((uint16_t)vsc[u]);
+                asm("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "v"(ps));   // (as for K: V's conversions wait for their probability)
+                vcorr[0] += ps;
+#pragma unroll
+                for (int wi = 0; wi < 4; ++wi) {
+                    uint32_t ev = w[wi] & 0x0f0f0f0fu, od = (w[wi] >> 4) & 0x0f0f0f0fu;
+                    asm("" : "+v"(ev), "+v"(od));
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        acc[8 * wi + 2 * i] = fmaf(ps, (float)((ev >> (8 * i)) & 0xffu), acc[8 * wi + 2 * i]);
+                        acc[8 * wi + 2 * i + 1] = fmaf(ps, (float)((od >> (8 * i)) & 0xffu), acc[8 * wi + 2 * i + 1]);
                     }
                 }
             } else if constexpr (QBIT == KV_FP8) {  // V's 2^e folded into the probability (exact)
@@ -202,6 +244,11 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
         for (int gi = 0; gi < C::NG; ++gi)
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[gi * 8 + i] = fmaf(-128.0f, vcorr[gi], acc[gi * 8 + i]);
+    }
+
+    if constexpr (QBIT == KV_I4G32) {
+#pragma unroll
+        for (int i = 0; i < CH; ++i) acc[i] = fmaf(-8.0f, vcorr[0], acc[i]);
     }
 
     // merge the TPW token groups of the wave (lanes with equal channel block c)

@@ -24,6 +24,9 @@
 // (profiles/r06_gqa_experiments.md): -23 % VALU per key, +13 % bandwidth at config 4's shape.
 // fp8 KV (KV_FP8): K and V fragments come out of v_cvt_scalef32_pk_f16_fp8 with the row's power-of-two scale inside the conversion --
 // exact fp16 numbers, so K and V need no lo image (one MFMA per K piece half, one V image); P stays an exact hi + lo pair.
+// int4 KV (KV_I4G32, head_dim 128: a row is four 16-byte pieces, one per quarter kq): a piece and its group scale become 32 exact fp16
+// numbers (nibble - 8 times the 8-bit scale, one packed multiply) -- four K fragments for four MFMAs against the Q fragments of the same
+// channels, and two 16-channel V sub-tiles of ONE image; no lo image, P stays an exact hi + lo pair.
 // Grid (Hkv, requests, splits); workspace / reduce kernel shared with the multi-head kernel (k_attn_decode.hip).
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
@@ -111,7 +114,8 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
         const uint16_t* qrow = qkv + seq_starts[b] * rowstride + (int64_t)(hk * grp + (l15 < grp ? l15 : 0)) * D;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-            const int ch = QBIT != KV_FP16 ? 16 * (kq + 4 * (ks >> 1)) + 8 * (ks & 1) : 8 * (kq + 4 * ks);
+            const int ch = QBIT == KV_I4G32 ? 32 * kq + 8 * ks   // int4: piece kq -> channels 32 kq + 8 ks
+                                            : (QBIT != KV_FP16 ? 16 * (kq + 4 * (ks >> 1)) + 8 * (ks & 1) : 8 * (kq + 4 * ks));
             const uint4 v = *reinterpret_cast<const uint4*>(qrow + ch);
             qf[ks] = __builtin_bit_cast(h8, l15 < grp ? v : make_uint4(0, 0, 0, 0));
         }
@@ -177,6 +181,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 const int pc = kq + 4 * j;
                 kraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(kp + (uint32_t)(kk * rowb32 + pc * 16)));
                 if constexpr (QBIT == 8) ksc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(ksp) + (uint32_t)((kk * srow32 + pc * 2) * 2)));
+                if constexpr (QBIT == KV_I4G32) ksc[p][j] = ksp[(uint32_t)(kk * srow32 + pc)];   // one scale per piece
             }
             if constexpr (QBIT == KV_FP8) ksc[p][0] = ksp[(uint32_t)(kk * srow32)];   // one scale per key row
 #pragma unroll
@@ -185,6 +190,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 vraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(vp + (uint32_t)(vk * rowb32 + vpc_l[j] * 16)));
                 if constexpr (QBIT == 8) vsc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(vsp) + (uint32_t)((vk * srow32 + vpc_l[j] * 2) * 2)));
                 if constexpr (QBIT == KV_FP8) vsc[p][j] = vsp[(uint32_t)(vk * srow32)];
+                if constexpr (QBIT == KV_I4G32) vsc[p][j] = vsp[(uint32_t)(vk * srow32 + vpc_l[j])];
             }
         } else {  // pages smaller than (or not aligned to) a sub-tile: every row through the page table
             const int64_t kslot = kv_slot(kv, cache_indices, max_pages, b, kbc + kk);
@@ -193,6 +199,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 const int pc = kq + 4 * j;
                 kraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(kbase + kslot * rowb + pc * 16));
                 if constexpr (QBIT == 8) ksc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(ksbase + kslot * srow + pc * 2));
+                if constexpr (QBIT == KV_I4G32) ksc[p][j] = ksbase[kslot * srow + pc];
             }
             if constexpr (QBIT == KV_FP8) ksc[p][0] = ksbase[kslot * srow];
 #pragma unroll
@@ -202,6 +209,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 vraw[p][j] = kv_stream_load(reinterpret_cast<const uint4*>(vbase + vslot * rowb + vpc_l[j] * 16));
                 if constexpr (QBIT == 8) vsc[p][j] = kv_stream_load(reinterpret_cast<const uint32_t*>(vsbase + vslot * srow + vpc_l[j] * 2));
                 if constexpr (QBIT == KV_FP8) vsc[p][j] = vsbase[vslot * srow];
+                if constexpr (QBIT == KV_I4G32) vsc[p][j] = vsbase[vslot * srow + vpc_l[j]];
             }
         }
     };
@@ -242,6 +250,14 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 uint16_t* dst = dstw + (ch0 >> 4) * ATT_VSUB + key * 16;
                 *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, cvt_fp8x8_f16(make_uint2(vraw[P][j].x, vraw[P][j].y), sc));
                 *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, cvt_fp8x8_f16(make_uint2(vraw[P][j].z, vraw[P][j].w), sc));
+            } else if constexpr (QBIT == KV_I4G32) {   // exact fp16, the hi image alone: the piece's 32 channels fill two sub-tiles
+                h8 v[4];
+                dequant_piece<QBIT>(vraw[P][j], vsc[P][j], v);
+                uint16_t* dst = dstw + (ch0 >> 4) * ATT_VSUB + key * 16;
+                *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, v[0]);
+                *reinterpret_cast<uint4*>(dst + 8) = __builtin_bit_cast(uint4, v[1]);
+                *reinterpret_cast<uint4*>(dst + ATT_VSUB) = __builtin_bit_cast(uint4, v[2]);
+                *reinterpret_cast<uint4*>(dst + ATT_VSUB + 8) = __builtin_bit_cast(uint4, v[3]);
             } else {
                 *reinterpret_cast<uint4*>(dstw + (ch0 >> 4) * ATT_VSUB + key * 16 + (ch0 & 15)) = vraw[P][j];
             }
@@ -268,6 +284,11 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void attn_decode_gqa_kernel(const ui
                 const h8 k0 = cvt_fp8x8_f16(make_uint2(kraw[P][j].x, kraw[P][j].y), sc), k1 = cvt_fp8x8_f16(make_uint2(kraw[P][j].z, kraw[P][j].w), sc);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, qf[2 * j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, qf[2 * j + 1], sacc, 0, 0, 0);
+            } else if constexpr (QBIT == KV_I4G32) {   // one MFMA per 8-channel fragment of the piece
+                h8 k[4];
+                dequant_piece<QBIT>(kraw[P][j], ksc[P][j], k);
+#pragma unroll
+                for (int f = 0; f < 4; ++f) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(k[f], qf[4 * j + f], sacc, 0, 0, 0);
             } else {
                 sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, kraw[P][j]), qf[j], sacc, 0, 0, 0);
             }
@@ -397,6 +418,7 @@ bool attn_decode_gqa_supported(int kv_fmt, int H, int Hkv, int D) {
     const int grp = H / Hkv;
     if (grp < 4 || grp > 16) return false;
     if (kv_fmt == KV_I8G8 || kv_fmt == KV_FP8) return D == 128 || D == 64;  // a row must hold >= four 16-byte pieces
+    if (kv_fmt == KV_I4G32) return D == 128;   // (64 bytes; head_dim 64 and 32 run on the multi-head kernel)
     return kv_fmt == KV_FP16 && (D == 128 || D == 64 || D == 32);
 }
 
@@ -410,9 +432,9 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
     static const int small_min = getenv("PPLHIP_GQA_SMALL_BLOCK_MIN") ? atoi(getenv("PPLHIP_GQA_SMALL_BLOCK_MIN")) : GQ_SMALL_BLOCK_MIN;   // A/B runs
     const bool small = (int64_t)Hkv * nb * split >= small_min;
     hipError_t unbuilt = hipSuccess;   // a (format, head_dim) the supported set admits but no kernel is built for: an error, never a no-op
-    dispatch_int<KV_I8G8, KV_FP16, KV_FP8>(kv_fmt, [&](auto QB) {
+    dispatch_int<KV_I8G8, KV_FP16, KV_FP8, KV_I4G32>(kv_fmt, [&](auto QB) {
         dispatch_int<128, 64, 32>(D, [&](auto DD) {
-            if constexpr (QB == KV_FP16 || DD != 32) {
+            if constexpr (QB == KV_I4G32 ? DD == 128 : (QB == KV_FP16 || DD != 32)) {
                 dispatch_int<0, 1>(kv.mode, [&](auto MD) {
                     dispatch_int<GQ_WAVES_SMALL, GQ_WAVES_BIG>(small ? GQ_WAVES_SMALL : GQ_WAVES_BIG, [&](auto NW) {
                         const auto kernel = attn_decode_gqa_kernel<QB, DD, MD, NW>;
@@ -432,7 +454,7 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
                     });
                 });
             } else {
-                unbuilt = hipErrorInvalidValue;   // int8 / fp8 with head_dim 32: a row holds fewer than four 16-byte pieces
+                unbuilt = hipErrorInvalidValue;   // int8 / fp8 with head_dim 32, int4 below 128: a row holds fewer than four 16-byte pieces
             }
         });
     });

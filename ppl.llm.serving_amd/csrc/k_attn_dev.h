@@ -6,21 +6,22 @@
 //   kv_head        used by the multi-head decode and both prefill kernels; the grouped-query kernel spells its own four pointers
 //   ATT_V_OFF      used by the 16-row prefill; the 32-row prefill (P3_STORE_ITEM) and the grouped-query kernel (stage_v) spell theirs
 //   dequant_piece  used by the 16-row prefill's store_tile (fp8; int8 there and P3_STORE_ITEM keep their own conversion) and by the
-//                  grouped-query stage_v's rounded int8 form (GQ_V_EXACT = 0); that kernel's fp8 V and fp8 scores keep their own
+//                  grouped-query stage_v's rounded int8 form (GQ_V_EXACT = 0); that kernel's fp8 V and fp8 scores keep their own;
+//                  the int4 form (KV_I4G32) is used by the 16-row prefill and the grouped-query kernel (V and scores)
 #pragma once
 #include "kernels.h"
 #include "k_launch.h"
 
 namespace pplhip {
 
-// a KV row of D channels in format QBIT (KV_FP16 / KV_I8G8 / KV_FP8) as 16-byte pieces
+// a KV row of D channels in format QBIT (KV_FP16 / KV_I8G8 / KV_FP8 / KV_I4G32) as 16-byte pieces
 template <int QBIT, int D>
 struct AttnCfg {
-    static constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;   // bytes per channel (int8 and fp8: one)
-    static constexpr int CH = 16 / ELT;       // channels per piece
+    static constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;   // bytes per slab element (int8 and fp8: a channel; int4: two channels)
+    static constexpr int CH = QBIT == KV_I4G32 ? 32 : 16 / ELT;   // channels per piece (int4: a piece is one quant group)
     static constexpr int LPT = D / CH;        // pieces per row (multi-head decode: lanes per token row)
     static constexpr int TPW = 64 / LPT;      // multi-head decode: token rows per wave-load
-    static constexpr int NG = CH / 8;         // int8: quant groups per piece (group = 8 channels); fp8: one scale per row
+    static constexpr int NG = CH / 8;         // int8: quant groups per piece (group = 8 channels); fp8: one scale per row; int4: unused
 };
 
 // K / V rows and scales of KV head hk from channel ch0 on; row (slot) r is at kbase + r * rowb bytes, its scales at ksbase + r * srow halfs
@@ -33,9 +34,9 @@ template <int QBIT>
 __device__ __forceinline__ KvHead kv_head(const KvAddr& kv, int hk, int ch0 = 0) {
     constexpr int ELT = QBIT != KV_FP16 ? 1 : 2;
     KvHead h;
-    h.kbase = reinterpret_cast<const char*>(kv.cache) + ((int64_t)hk * kv.sH + ch0) * ELT;
+    h.kbase = reinterpret_cast<const char*>(kv.cache) + ((int64_t)hk * kv.sH + (QBIT == KV_I4G32 ? ch0 / 2 : ch0)) * ELT;
     h.vbase = h.kbase + kv.sKV * ELT;
-    h.ksbase = kv.scale + (int64_t)hk * kv.ssH + (QBIT == KV_I8G8 ? ch0 / 8 : 0);
+    h.ksbase = kv.scale + (int64_t)hk * kv.ssH + (QBIT == KV_I8G8 ? ch0 / 8 : (QBIT == KV_I4G32 ? ch0 / 32 : 0));
     h.vsbase = h.ksbase + kv.ssKV;
     h.rowb = kv.sN * ELT;
     h.srow = kv.ssN;
@@ -85,7 +86,7 @@ __device__ __forceinline__ void cvt_i8x16_f16(uint4 raw, h8* q) {
 }
 // A 16-byte piece and its scale word -> CH / 8 groups of 8 fp16.  int8: times the group's fp16 scale in packed fp16 (sc = the piece's two
 // scales; one rounding of q * scale, as the oracle's dequantisation); fp8: the row's power-of-two scale inside the conversion -- exact,
-// no rounding; fp16: the piece itself.
+// no rounding; fp16: the piece itself; int4: the piece is one group of 32 channels -> four groups of 8 fp16 times its scale, exact.
 template <int QBIT>
 __device__ __forceinline__ void dequant_piece(uint4 raw, uint32_t sc, h8* out) {
     if constexpr (QBIT == KV_I8G8) {
@@ -97,6 +98,12 @@ __device__ __forceinline__ void dequant_piece(uint4 raw, uint32_t sc, h8* out) {
         const float s = h2f((uint16_t)sc);
         out[0] = cvt_fp8x8_f16(make_uint2(raw.x, raw.y), s);
         out[1] = cvt_fp8x8_f16(make_uint2(raw.z, raw.w), s);
+    } else if constexpr (QBIT == KV_I4G32) {
+        const _Float16 s = __builtin_bit_cast(_Float16, (uint16_t)sc);
+        out[0] = cvt_i4x8_f16(raw.x, s);
+        out[1] = cvt_i4x8_f16(raw.y, s);
+        out[2] = cvt_i4x8_f16(raw.z, s);
+        out[3] = cvt_i4x8_f16(raw.w, s);
     } else {
         out[0] = __builtin_bit_cast(h8, raw);
     }

@@ -16,7 +16,8 @@
 //   the probabilities are already in MFMA A-operand order for O += P . V (the k-slot permutation this implies
 //   is applied identically to the V^T reads).
 //   int8 KV is dequantised to fp16 while staging (one fp16 rounding of q*scale; DESIGN.md "numerics"); fp8 KV likewise, with the
-//   row's power-of-two scale inside the conversion -- exact, no rounding.
+//   row's power-of-two scale inside the conversion -- exact, no rounding; int4 KV (KV_I4G32): a piece is one group of 32 channels, nibble - 8
+//   times its 8-bit scale in packed fp16 -- exact as well; the piece fills four K chunks and two 16-channel V sub-tiles.
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
 #include "k_attn_dev.h"
@@ -131,6 +132,10 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                             ksc[it][e] = kst[kk * srow32];
                             vsc[it][e] = vst[kk * srow32];
                         }
+                        if constexpr (QBIT == KV_I4G32) {   // the piece's scale
+                            ksc[it][e] = kst[kk * srow32 + c];
+                            vsc[it][e] = vst[kk * srow32 + c];
+                        }
                     }
                 } else {
                     const int k0i = (2 * kp) < last ? (2 * kp) : last, k1i = (2 * kp + 1) < last ? (2 * kp + 1) : last;
@@ -148,6 +153,10 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                         if constexpr (QBIT == KV_FP8) {
                             ksc[it][e] = ksbase[slot * srow];
                             vsc[it][e] = vsbase[slot * srow];
+                        }
+                        if constexpr (QBIT == KV_I4G32) {
+                            ksc[it][e] = ksbase[slot * srow + c];
+                            vsc[it][e] = vsbase[slot * srow + c];
                         }
                     }
                 }
@@ -171,7 +180,7 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                         const h2 ksc2 = __builtin_bit_cast(h2, ksc[it][e]), vsc2 = __builtin_bit_cast(h2, vsc[it][e]);
                         kf[e][0] = k0 * ksc2[0]; kf[e][1] = k1 * ksc2[1];
                         vf[e][0] = v0 * vsc2[0]; vf[e][1] = v1 * vsc2[1];
-                    } else if constexpr (QBIT == KV_FP8) {
+                    } else if constexpr (QBIT == KV_FP8 || QBIT == KV_I4G32) {
                         dequant_piece<QBIT>(kraw[it][e], ksc[it][e], kf[e]);
                         dequant_piece<QBIT>(vraw[it][e], vsc[it][e], vf[e]);
                     } else {   // (no scales: nothing was loaded into ksc / vsc)
@@ -323,13 +332,13 @@ hipError_t launch_attn_prefill(hipStream_t s, const uint16_t* qkv, const KvAddr&
                                int64_t max_pages, int64_t b0, int64_t B, int H, int Hkv, int D, int64_t max_seq_len,
                                uint16_t* out, int64_t max_kv_len, float* ws, size_t ws_bytes, int64_t row0, int64_t nrows) {
     if (B <= b0 || max_seq_len <= 0) return hipSuccess;
-    if (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8) return hipErrorInvalidValue;
+    if (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8 && kv_fmt != KV_I4G32) return hipErrorInvalidValue;
     // head_dim 128: the 32-row kernel of k_attn_prefill32.hip
     if (D == 128) return launch_attn_prefill32(s, qkv, kv, kv_fmt, seq_starts, start_pos, cache_indices, max_pages, b0, B, H, Hkv, D, max_seq_len, out, max_kv_len, ws, ws_bytes, row0, nrows);
     if (D != 64 && D != 32) return hipErrorInvalidValue;
     const int nqb = (int)((max_seq_len + PF_BM - 1) / PF_BM), nreq = (int)(B - b0);
     dim3 grid((unsigned)((int64_t)nqb * nreq * H));
-    dispatch_int<KV_I8G8, KV_FP16, KV_FP8>(kv_fmt, [&](auto QB) {
+    dispatch_int<KV_I8G8, KV_FP16, KV_FP8, KV_I4G32>(kv_fmt, [&](auto QB) {
         dispatch_int<64, 32>(D, [&](auto DD) {
             dispatch_int<0, 1>(kv.mode, [&](auto MD) {
                 hipLaunchKernelGGL((attn_prefill_kernel<QB, DD, MD>), grid, dim3(PF_THREADS), 0, s, qkv, kv, seq_starts, start_pos, cache_indices,

@@ -13,6 +13,9 @@
 //   is read with the same key permutation (two transposing LDS reads of 4 keys each).
 //   P enters as an exact hi + lo pair of fp16 numbers (two MFMAs), K / V dequantised int8 x scale rounded to fp16 once, as in the
 //   16-row kernel (DESIGN.md numerics).
+//   int4 KV (KV_I4G32): a staging item is an 8-byte HALF piece (16 channels: two K chunks, one V sub-tile), so the items per thread and
+//   their stores are those of the int8 form at every block size (a whole piece per item would leave half of an 8-wave block without one);
+//   nibble - 8 times the group's 8-bit scale in packed fp16, exact.
 // Oracle: ref_attention (oracle/llama_ref.c).
 #include <stdlib.h>
 #include "k_attn_dev.h"
@@ -46,7 +49,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     constexpr int D = P3_D;
     constexpr int P3_BM = NW * 32, P3_THREADS = NW * 64;  // NW waves x 32 query rows share the staged K / V tiles
     using C = AttnCfg<QBIT, D>;
-    constexpr int CH = C::CH, LPT = C::LPT;      // channels in one 16-byte piece; pieces per row: 8 (int8, fp8) / 16 (fp16)
+    // channels in one staging item (a 16-byte piece; int4: an 8-byte half piece); items per row: 8 (int8, fp8, int4) / 16 (fp16)
+    constexpr int CH = QBIT == KV_I4G32 ? 16 : C::CH, LPT = QBIT == KV_I4G32 ? 8 : C::LPT;
+    constexpr int PCB = QBIT == KV_I4G32 ? 8 : 16;   // bytes of an item
     constexpr int IPT = P3_BN * LPT / P3_THREADS;  // (key, piece) items per thread and matrix: 2 / 4 (4 waves), 1 / 2 (8 waves)
     constexpr int KSTEPS = D / 16;               // 8 k-steps of the 32x32x16 MFMA over the head dimension
     __shared__ __attribute__((aligned(16))) uint16_t smem[2 * (P3_KS_HALFS + P3_VS_HALFS)];
@@ -103,6 +108,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #define P3_ITEM_PC(it) ((int)(threadIdx.x + (it) * P3_THREADS) % LPT)
     // rows past kv_end re-read the last valid row (beyond every row's causal horizon); contiguous slots: one scalar tile base plus
     // 32-bit lane offsets
+#define P3_SC_OFF(pc) (QBIT == 8 ? (pc) * 2 : (QBIT == KV_I4G32 ? (pc) / 2 : 0))   /* halfs from the row's first scale to the item's */
 #define P3_LOAD_ITEM(it, KR, VR, KC, VC)                                                                                        \
     do {                                                                                                                       \
         const int kk_ = P3_ITEM_KEY(it) < last_ ? P3_ITEM_KEY(it) : last_, pc_ = P3_ITEM_PC(it);                               \
@@ -110,19 +116,25 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         const uint16_t *ksp_, *vsp_;                                                                                           \
         if constexpr (MODE == 0) {                                                                                             \
             const int64_t sb_ = slot0 + key0_;                                                                                 \
-            kp_ = kbase + sb_ * rowb + (kk_ * rowb32 + pc_ * 16);                                                              \
-            vp_ = vbase + sb_ * rowb + (kk_ * rowb32 + pc_ * 16);                                                              \
-            ksp_ = ksbase + sb_ * srow + (kk_ * srow32 + (QBIT == 8 ? pc_ * 2 : 0));                                           \
-            vsp_ = vsbase + sb_ * srow + (kk_ * srow32 + (QBIT == 8 ? pc_ * 2 : 0));                                           \
+            kp_ = kbase + sb_ * rowb + (kk_ * rowb32 + pc_ * PCB);                                                             \
+            vp_ = vbase + sb_ * rowb + (kk_ * rowb32 + pc_ * PCB);                                                             \
+            ksp_ = ksbase + sb_ * srow + (kk_ * srow32 + P3_SC_OFF(pc_));                                           \
+            vsp_ = vsbase + sb_ * srow + (kk_ * srow32 + P3_SC_OFF(pc_));                                           \
         } else {                                                                                                               \
             const int64_t slot_ = kv_slot(kv, cache_indices, max_pages, b, key0_ + kk_);                                       \
-            kp_ = kbase + slot_ * rowb + pc_ * 16;                                                                             \
-            vp_ = vbase + slot_ * rowb + pc_ * 16;                                                                             \
-            ksp_ = ksbase + slot_ * srow + (QBIT == 8 ? pc_ * 2 : 0);                                                          \
-            vsp_ = vsbase + slot_ * srow + (QBIT == 8 ? pc_ * 2 : 0);                                                          \
+            kp_ = kbase + slot_ * rowb + pc_ * PCB;                                                                            \
+            vp_ = vbase + slot_ * rowb + pc_ * PCB;                                                                            \
+            ksp_ = ksbase + slot_ * srow + P3_SC_OFF(pc_);                                                          \
+            vsp_ = vsbase + slot_ * srow + P3_SC_OFF(pc_);                                                          \
         }                                                                                                                      \
-        KR = *reinterpret_cast<const uint4*>(kp_);                                                                             \
-        VR = *reinterpret_cast<const uint4*>(vp_);                                                                             \
+        if constexpr (QBIT == KV_I4G32) {                                                                                      \
+            const uint2 k2_ = *reinterpret_cast<const uint2*>(kp_), v2_ = *reinterpret_cast<const uint2*>(vp_);                \
+            KR.x = k2_.x; KR.y = k2_.y; VR.x = v2_.x; VR.y = v2_.y;                                                            \
+            KC = *ksp_; VC = *vsp_;  /* the group's scale */                                                                   \
+        } else {                                                                                                               \
+            KR = *reinterpret_cast<const uint4*>(kp_);                                                                         \
+            VR = *reinterpret_cast<const uint4*>(vp_);                                                                         \
+        }                                                                                                                      \
         if constexpr (QBIT == 8) {                                                                                             \
             KC = *reinterpret_cast<const uint32_t*>(ksp_);                                                                     \
             VC = *reinterpret_cast<const uint32_t*>(vsp_);                                                                     \
@@ -160,6 +172,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const float ks_ = h2f((uint16_t)KC), vs_ = h2f((uint16_t)VC);                                                      \
             const h8 kh0 = cvt_fp8x8_f16(make_uint2(KR.x, KR.y), ks_), kh1 = cvt_fp8x8_f16(make_uint2(KR.z, KR.w), ks_);       \
             const h8 vh0 = cvt_fp8x8_f16(make_uint2(VR.x, VR.y), vs_), vh1 = cvt_fp8x8_f16(make_uint2(VR.z, VR.w), vs_);       \
+            *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh0);          \
+            *reinterpret_cast<uint4*>(&Kw[key * D + (((ch0 >> 3) + 1) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh1);    \
+            uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * ATT_VSUB + (key & 15) * 16];                              \
+            *reinterpret_cast<uint4*>(vd) = __builtin_bit_cast(uint4, vh0);                                                    \
+            *reinterpret_cast<uint4*>(vd + 8) = __builtin_bit_cast(uint4, vh1);                                                \
+        } else if constexpr (QBIT == KV_I4G32) {  /* (nibble - 8) x the group's 8-bit scale: exact fp16, no rounding */         \
+            const _Float16 ks_ = __builtin_bit_cast(_Float16, (uint16_t)KC), vs_ = __builtin_bit_cast(_Float16, (uint16_t)VC); \
+            const h8 kh0 = cvt_i4x8_f16(KR.x, ks_), kh1 = cvt_i4x8_f16(KR.y, ks_);                                             \
+            const h8 vh0 = cvt_i4x8_f16(VR.x, vs_), vh1 = cvt_i4x8_f16(VR.y, vs_);                                             \
             *reinterpret_cast<uint4*>(&Kw[key * D + ((ch0 >> 3) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh0);          \
             *reinterpret_cast<uint4*>(&Kw[key * D + (((ch0 >> 3) + 1) ^ (key & 15)) * 8]) = __builtin_bit_cast(uint4, kh1);    \
             uint16_t* vd = &Vw[((key >> 4) * (D / 16) + (ch0 >> 4)) * ATT_VSUB + (key & 15) * 16];                              \
@@ -326,6 +347,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
 }
 
+#undef P3_SC_OFF
 #undef P3_LOAD_TILE
 #undef P3_LOAD_ITEM
 #undef P3_STORE_ITEM
@@ -338,13 +360,13 @@ hipError_t launch_attn_prefill32(hipStream_t s, const uint16_t* qkv, const KvAdd
                                  const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t b0, int64_t B,
                                  int H, int Hkv, int D, int64_t max_seq_len, uint16_t* out, int64_t max_kv_len, float* ws, size_t ws_bytes,
                                  int64_t row0, int64_t nrows) {
-    if (D != P3_D || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8)) return hipErrorInvalidValue;
+    if (D != P3_D || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8 && kv_fmt != KV_I4G32)) return hipErrorInvalidValue;
     if (B <= b0 || max_seq_len <= 0) return hipSuccess;
     const int nreq = (int)(B - b0);
     // one launch of nw waves per block (split form: 4 only) on `grid`: format and cache mode -> template arguments
     auto launch = [&](dim3 grid, int nw, auto split_c, int nqb, float* part, int64_t part_row0) {
         constexpr int SPLIT = decltype(split_c)::value;
-        dispatch_int<KV_I8G8, KV_FP8, KV_FP16>(kv_fmt, [&](auto QB) {
+        dispatch_int<KV_I8G8, KV_FP8, KV_FP16, KV_I4G32>(kv_fmt, [&](auto QB) {
             dispatch_int<0, 1>(kv.mode, [&](auto MD) {
                 dispatch_int<8, 4>(nw, [&](auto NW) {
                     if constexpr (SPLIT == 0 || NW == 4)

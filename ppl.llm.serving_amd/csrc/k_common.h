@@ -92,7 +92,11 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 //   KV_I8G8: int8 rows, one fp16 scale per 8 channels.
 //   KV_FP8 : OCP e4m3fn rows, ONE fp16 scale per head row, a power of two 2^e with e in [-15, 8] (DESIGN.md "numerics"): every
 //            dequantised element q * 2^e is exactly an fp16 number, so the fp8 cache is the fp16 cache with every row replaced by Q(row).
-constexpr int KV_FP16 = 0, KV_I8G8 = 8, KV_FP8 = 1;
+//   KV_I4G32: int4 rows, one fp16 scale per 32 channels (a group is one 16-byte piece), D = 32, 64, 128.  Channel 2j of a group is the low
+//            nibble of byte j, channel 2j + 1 the high one; a nibble is q + 8 with q in [-7, 7] (the W4A16 convention of k_gemm_dev.h), so
+//            0 is never written.  The scale has 8 significant bits (kv_i4_scale): q * s is exactly an fp16 number, and the int4 cache is the
+//            fp16 cache with every written group replaced by Q(group) = q * s (DESIGN.md "numerics").
+constexpr int KV_FP16 = 0, KV_I8G8 = 8, KV_FP8 = 1, KV_I4G32 = 4;
 
 // fp8 write: exponent e of a row's scale -- the smallest integer with 448 * 2^e >= amax, clamped to [-15, 8] (amax = 0: -15).
 // amax = m 2^k (m in [0.5, 1)): 448 = 0.875 2^9, so e = k - 9 when m <= 0.875, else k - 8.  amax is an fp16 value: an fp32 normal or 0.
@@ -144,6 +148,41 @@ __device__ __forceinline__ h8 cvt_fp8x8_f16(uint2 v, float sc) {
     const h4 a = cvt_fp8x4_f16(v.x, sc), b = cvt_fp8x4_f16(v.y, sc);
     return h8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
+
+// int4 write: scale of a group whose max|x| is amax (an fp16 value) -- amax / 7 (one correctly rounded division) rounded UP to 8
+// significant bits, clamped to [2^-14, 9344]: exactly an fp16 number whose low three mantissa bits are zero, 7 s <= 65408 is finite and
+// every q s (|q| <= 7) is a normal fp16 number or 0
+__device__ __forceinline__ float kv_i4_scale(float amax) {
+    uint32_t u = __builtin_bit_cast(uint32_t, __fdiv_rn(amax, 7.0f));
+    u = (u + 0xffffu) & ~0xffffu;
+    return fminf(fmaxf(__builtin_bit_cast(float, u), 6.103515625e-05f), 9344.0f);
+}
+// nibble (q + 8, in 1..15) of x under the reciprocal inv = 1 / s (one correctly rounded division per group: the int8 writer's rule)
+__device__ __forceinline__ uint32_t kv_i4_quant(float x, float inv) {
+    const float q = fminf(fmaxf(rintf(__fmul_rn(x, inv)), -7.f), 7.f);
+    return (uint32_t)((int)q + 8);
+}
+// 8 channels' nibbles -> one 32-bit word, channel i at bits 4 i
+__device__ __forceinline__ uint32_t kv_i4_pack8(const float* x, float inv) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w |= kv_i4_quant(x[i], inv) << (4 * i);
+    return w;
+}
+// the 8 nibbles of a word -> 8 fp16 q = nibble - 8 in channel order, exact: the nibbles become the bytes n0 .. n3 | n4 .. n7 (v_perm),
+// each goes under the fp16 exponent 0x64 (= 1024 + n), minus 1032
+__device__ __forceinline__ h8 cvt_i4x8_f16(uint32_t w) {
+    const uint32_t lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;   // even / odd channels
+    const uint32_t b0 = __builtin_amdgcn_perm(hi, lo, 0x05010400u), b1 = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
+    const h2 bias = {(_Float16)1032.0f, (_Float16)1032.0f};
+    const h2 a = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, b0, 0x04010400u)) - bias;
+    const h2 b = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, b0, 0x04030402u)) - bias;
+    const h2 c = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, b1, 0x04010400u)) - bias;
+    const h2 d = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, b1, 0x04030402u)) - bias;
+    return h8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+// ... times the group's scale in packed fp16: exact (a 3-bit by 8-bit product), no rounding
+__device__ __forceinline__ h8 cvt_i4x8_f16(uint32_t w, _Float16 s) { return cvt_i4x8_f16(w) * s; }
 
 // Decode attention reads every K/V row exactly once per step: non-temporal loads (compile-time switch PPLHIP_KV_NT) stream them
 // past the caches instead of through them -- measured +5..9 % (batch 1024 kv 512: 5.92 -> 6.23 TB/s, kv 1024: 6.24 -> 6.70 TB/s,

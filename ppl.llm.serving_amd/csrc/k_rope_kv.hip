@@ -1,5 +1,6 @@
 // K4 + K5 fused: rotary position embedding on q and k of the fused qkv rows, then write of k, v into the KV
-// slab -- with int8 group-8 quantisation (KV_I8G8) or fp8 e4m3 with one power-of-two scale per head row (KV_FP8).
+// slab -- with int8 group-8 quantisation (KV_I8G8), fp8 e4m3 with one power-of-two scale per head row (KV_FP8) or int4 with one fp16
+// scale per 32 channels (KV_I4G32).
 // HBM-bound; 1-4 workgroups per token.
 //
 // Work item = one (head, 8-channel block) of a token:
@@ -9,6 +10,9 @@
 // KV_FP8: a head row's scale needs max|x| over the whole row, i.e. over the D/16 (k) or D/8 (v) items of the head: those items sit
 //   on consecutive lanes of one wave, aligned to their count (the v items start at n_rope rounded up to D/8 for this format), and
 //   meet in a cross-lane max.
+// KV_I4G32: a group of 32 channels is the 4 aligned items that hold it (k: the first halves i0 .. of four items form one group, their
+//   partner halves i0 + D/2 .. another; head_dim 32: the head's 2 items with both halves; v: 4 items, the v items start at n_rope
+//   rounded up to 4); they meet in a cross-lane max, each stores its 4 bytes of codes and the first one the group's scale.
 // Position of row t of request b: start_pos[b] + (t - seq_starts[b]) (src/generator/llm_generator.cc:263-298);
 // slot of (b, pos): kv_slot() (k_common.h).  Oracle: ref_rope_kv_write (oracle/llama_ref.c).
 #include <stdlib.h>
@@ -60,6 +64,15 @@ __device__ __forceinline__ void store_fp8_row8(const KvAddr& kv, int kvsel, int 
     *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(kv.cache) + base) = make_uint2(lo, hi);
     if (ch0 == 0) kv.scale[(int64_t)kvsel * kv.ssKV + (int64_t)head * kv.ssH + slot * kv.ssN] = f2h(__builtin_bit_cast(float, (uint32_t)(127 + e) << 23));
 }
+// KV_I4G32: 8 channels of a group whose max|x| is amax: nibbles q + 8, q = clamp(rint(x / s), +-7), s = kv_i4_scale(amax); the item of the
+// group's first channel stores s
+__device__ __forceinline__ void store_i4_group8(const KvAddr& kv, int kvsel, int head, int64_t slot, int ch0, const float* x /*8*/, float amax) {
+    const float sf = kv_i4_scale(amax);
+    const float inv = __fdiv_rn(1.0f, sf);   // one correctly rounded reciprocal per group
+    const int64_t base = (int64_t)kvsel * kv.sKV + (int64_t)head * kv.sH + slot * kv.sN + ch0 / 2;   // a row of D / 2 one-byte elements
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(kv.cache) + base) = kv_i4_pack8(x, inv);
+    if ((ch0 & 31) == 0) kv.scale[(int64_t)kvsel * kv.ssKV + (int64_t)head * kv.ssH + slot * kv.ssN + ch0 / 32] = f2h(sf);
+}
 // max over the n lanes (a power of two, aligned) of an item group
 __device__ __forceinline__ float group_max(float v, int n) {
     for (int o = 1; o < n; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -97,7 +110,8 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(uint16_t* __restrict
     const int n_rope = (H + Hkv) * bph;
     const int n_v = Hkv * (D / 8);
     // first v item: fp8 aligns it to a v head's item count (the items in between do nothing)
-    const int v0 = QBIT == KV_FP8 ? (n_rope + D / 8 - 1) / (D / 8) * (D / 8) : n_rope;
+    // (int4: to a group's 4 items)
+    const int v0 = QBIT == KV_FP8 ? (n_rope + D / 8 - 1) / (D / 8) * (D / 8) : (QBIT == KV_I4G32 ? (n_rope + 3) / 4 * 4 : n_rope);
     uint16_t* row = qkv + t * (int64_t)(H + 2 * Hkv) * D;
     const float* cs = cos_sin + pos * D;       // cos[0..half) then sin[0..half)
     // gridDim.y blocks share a token's work items (one item per thread at the LLaMA geometries: the step is a chain of dependent
@@ -134,6 +148,14 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(uint16_t* __restrict
                 const int e = fp8_row_exp(group_max(mx, bph));
                 store_fp8_row8(kv, 0, head - H, slot, i0, ra, e);
                 store_fp8_row8(kv, 0, head - H, slot, i0 + half, rb, e);
+            } else if constexpr (QBIT == KV_I4G32) {  // k: to the cache (head is uniform over the 4 (head_dim 32: 2) items of a group)
+                float ma = 0.f, mb = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { ma = fmaxf(ma, fabsf(ra[i])); mb = fmaxf(mb, fabsf(rb[i])); }
+                if (D == 32) ma = mb = group_max(fmaxf(ma, mb), 2);   // one group: both halves of both items
+                else { ma = group_max(ma, 4); mb = group_max(mb, 4); }
+                store_i4_group8(kv, 0, head - H, slot, i0, ra, ma);
+                store_i4_group8(kv, 0, head - H, slot, i0 + half, rb, mb);
             } else {         // k: to the cache
                 store_group8<QBIT>(kv, 0, head - H, slot, i0, ra);
                 store_group8<QBIT>(kv, 0, head - H, slot, i0 + half, rb);
@@ -149,6 +171,11 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(uint16_t* __restrict
 #pragma unroll
                 for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(v[i]));
                 store_fp8_row8(kv, 1, head, slot, i0, v, fp8_row_exp(group_max(mx, D / 8)));
+            } else if constexpr (QBIT == KV_I4G32) {
+                float mx = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(v[i]));
+                store_i4_group8(kv, 1, head, slot, i0, v, group_max(mx, 4));
             } else {
                 store_group8<QBIT>(kv, 1, head, slot, i0, v);
             }
@@ -165,7 +192,8 @@ hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_s
         sl = *qkv_slabs;
         if (sl.N != (H + 2 * Hkv) * D || sl.M != T) return hipErrorInvalidValue;
     }
-    if (D % 16 || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8)) return hipErrorInvalidValue;
+    if (D % 16 || (kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8 && kv_fmt != KV_I4G32)) return hipErrorInvalidValue;
+    if (kv_fmt == KV_I4G32 && D != 32 && D != 64 && D != 128) return hipErrorInvalidValue;
     const int items = (H + Hkv) * (D / 16) + Hkv * (D / 8);
     static const int forced_y = getenv("PPLHIP_ROPE_BLOCKS_PER_TOKEN") ? atoi(getenv("PPLHIP_ROPE_BLOCKS_PER_TOKEN")) : 0;
     int gy = (items + 255) / 256;            // one item per thread ...
@@ -173,7 +201,10 @@ hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_s
     if (T >= 4096 && gy > 2) gy = 2;         // ... unless the launch fills the chip many times over anyway
     if (forced_y > 0) gy = forced_y;
     const dim3 grid((unsigned)T, (unsigned)gy);
-    if (kv_fmt == KV_FP8)
+    if (kv_fmt == KV_I4G32)
+        hipLaunchKernelGGL(rope_kv_write_kernel<KV_I4G32>, grid, dim3(256), 0, s, qkv, cos_sin, kv, seq_starts,
+                           start_pos, cache_indices, max_pages, B, t0, H, Hkv, D, sl);
+    else if (kv_fmt == KV_FP8)
         hipLaunchKernelGGL(rope_kv_write_kernel<KV_FP8>, grid, dim3(256), 0, s, qkv, cos_sin, kv, seq_starts,
                            start_pos, cache_indices, max_pages, B, t0, H, Hkv, D, sl);
     else if (kv_fmt == KV_I8G8)

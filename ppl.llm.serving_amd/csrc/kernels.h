@@ -75,7 +75,7 @@ hipError_t launch_silu_mul(hipStream_t s, const uint16_t* gate_up, int64_t T, in
 // out[r] = x[seq_starts[r + 1] - 1] (last-token gather of K11 when the final norm already ran on every row: fused tensor-parallel norm)
 hipError_t launch_gather_last_rows(hipStream_t s, const uint16_t* x, const int64_t* seq_starts, int64_t B, int hidden, uint16_t* out);
 
-// The KV-cache kernels take the cache format kv_fmt (KV_FP16 / KV_I8G8 / KV_FP8, k_common.h).
+// The KV-cache kernels take the cache format kv_fmt (KV_FP16 / KV_I8G8 / KV_FP8 / KV_I4G32, k_common.h).
 // ---- k_rope_kv.hip ----------------------------------------------------------------------------
 hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_sin, const KvAddr& kv, int kv_fmt,
                                 const int64_t* seq_starts, const int64_t* start_pos,
@@ -218,7 +218,7 @@ hipError_t launch_penalty(hipStream_t s, float* logits, const float* temperature
 
 // ---- synth.hip --------------------------------------------------------------------------------
 // kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm; and for the fp8 KV
-// slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales
+// slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales; for the int4 KV slab: 7 nibble pairs 1..15, 8 scales of its rule
 hipError_t launch_synth_fill(hipStream_t s, int kind, uint64_t seed, uint32_t tensor_id, uint32_t stream_id, float amp,
                              uint64_t n, void* out);
 

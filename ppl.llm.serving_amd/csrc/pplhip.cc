@@ -312,20 +312,25 @@ bool find_tensor(pplhip_ctx* c, Rank& R, const char* name, void** ptr, uint64_t*
     return false;
 }
 
-// KV cache format of a (cache_quant_bit, cache_quant_group) pair at head_dim D, -1 when the pair is not one of the three:
-// (0, 1) fp16, (8, 8) int8 group 8, (8, D) fp8 e4m3 with one power-of-two scale per head row (D = 32, 64, 128).  Everything behind
-// the sizes (make_kv_addr, pplhip_kv_block_bytes) works from the pair itself: 1 byte per element and D / group scales per row.
+// KV cache format of a (cache_quant_bit, cache_quant_group) pair at head_dim D, -1 when the pair is not one of the four:
+// (0, 1) fp16, (8, 8) int8 group 8, (8, D) fp8 e4m3 with one power-of-two scale per head row, (4, 32) int4 with one fp16 scale per 32
+// channels (the last two at D = 32, 64, 128).  Everything behind the sizes (make_kv_addr, pplhip_kv_block_bytes) works from the pair
+// itself: kv_row_bytes() bytes of codes and D / group scales per row.
 static int kv_format(int quant_bit, int quant_group, int D) {
     if (quant_bit == 0 && quant_group == 1) return KV_FP16;
     if (quant_bit == 8 && quant_group == 8) return KV_I8G8;
     if (quant_bit == 8 && quant_group == D && (D == 32 || D == 64 || D == 128)) return KV_FP8;
+    if (quant_bit == 4 && quant_group == 32 && (D == 32 || D == 64 || D == 128)) return KV_I4G32;
     return -1;
 }
+// bytes of one head row of D channels in the slab: fp16 2 D, int8 / fp8 D, int4 D / 2 (two channels per byte)
+static int64_t kv_row_bytes(int quant_bit, int D) { return quant_bit == 4 ? D / 2 : (quant_bit == 8 ? D : 2 * D); }
 
 KvAddr make_kv_addr(const pplhip_model_desc& d, int Hkv, int D, uint64_t tokens, void* cache, uint16_t* scale, int layer) {
-    const int elt = d.cache_quant_bit == 8 ? 1 : 2;
+    const int elt = d.cache_quant_bit == 0 ? 2 : 1;
     const int g = d.cache_quant_group > 0 ? d.cache_quant_group : 1;
-    const KvStrides cs = kv_strides(d.cache_layout, (int64_t)tokens, d.num_layers, Hkv, D);
+    // (int4: the slab is addressed like the int8 slab with a row of D / 2 one-byte elements)
+    const KvStrides cs = kv_strides(d.cache_layout, (int64_t)tokens, d.num_layers, Hkv, kv_row_bytes(d.cache_quant_bit, D) / elt);
     const KvStrides ss = kv_strides(d.cache_layout, (int64_t)tokens, d.num_layers, Hkv, D / g);
     KvAddr a;
     a.cache = (char*)cache + (int64_t)layer * cs.sL * elt;
@@ -630,6 +635,8 @@ extern "C" {
 int pplhip_version(void) { return (1 << 16) | 2; }  // 1.1: pplhip_model_desc.act_quant_bit, comm_* and W8A8 operator entry points;
                                                     // 1.2: fp8 e4m3 KV cache (cache_quant_bit 8, cache_quant_group = head_dim),
                                                     //      online_f8f8 (act_quant_bit PPLHIP_ACT_QUANT_FP8) and pplhip_op_*_f8
+                                                    //      (later additions keep 1.2 and are detected by pplhip_init accepting them:
+                                                    //      the int4 KV cache, cache_quant_bit 4 / cache_quant_group 32)
 
 int pplhip_device_count(void) {
     int n = 0;
@@ -720,7 +727,7 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
     if (d.num_heads % tp || d.num_kv_heads % tp || d.intermediate_dim % tp || d.vocab_size % tp) return bad("tp divisibility");
     if (d.num_heads % d.num_kv_heads) return bad("gqa");
     // src/generator/llm_generator.cc:114-144 (CheckParameters)
-    // (plus the fp8 pair (8, head_dim) of this library: kv_format)
+    // (plus the fp8 pair (8, head_dim) and the int4 pair (4, 32) of this library: kv_format)
     if (kv_format(d.cache_quant_bit, d.cache_quant_group, d.hidden_dim / d.num_heads) < 0) return bad("cache quant");
     if (d.cache_layout < 0 || d.cache_layout > 3 || d.cache_mode < 0 || d.cache_mode > 1) return bad("cache layout/mode");
     if (d.cache_mode == 1 && d.page_size <= 0) return bad("page_size");
@@ -1249,8 +1256,7 @@ int pplhip_rank_tie_output(pplhip_ctx* c, int rank, int64_t shift, uint64_t seed
 int pplhip_kv_block_bytes(pplhip_ctx* c, uint64_t* cache_bytes, uint64_t* scale_bytes) {
     if (!c) return PPLHIP_INVALID_VALUE;
     // src/backends/cuda/resource_manager.cc:381-387
-    const uint64_t elt = c->d.cache_quant_bit == 8 ? 1 : 2;
-    const uint64_t kb = (uint64_t)c->d.num_layers * 2 * c->Hkv * c->D * elt;
+    const uint64_t kb = (uint64_t)c->d.num_layers * 2 * c->Hkv * (uint64_t)kv_row_bytes(c->d.cache_quant_bit, c->D);
     const uint64_t sb = c->d.cache_quant_bit > 0 ? (uint64_t)c->d.num_layers * 2 * c->Hkv * (c->D / c->d.cache_quant_group) * 2 : 0;
     if (cache_bytes) *cache_bytes = kb;
     if (scale_bytes) *scale_bytes = sb;
@@ -1336,6 +1342,9 @@ int pplhip_kv_fill_synthetic(pplhip_ctx* c, int rank, uint64_t seed) {
     if (c->kv_fmt == KV_FP8) {   // finite e4m3 codes and power-of-two row scales
         HIPCK(c, rank, launch_synth_fill(R.stream, 5, seed, 1, st, 0.f, R.kv_tokens * kb, R.kv_cache));
         HIPCK(c, rank, launch_synth_fill(R.stream, 6, seed, 2, st, 0.f, R.kv_tokens * sb / 2, R.kv_scale));
+    } else if (c->kv_fmt == KV_I4G32) {   // nibbles 1..15 and scales of the format's rule
+        HIPCK(c, rank, launch_synth_fill(R.stream, 7, seed, 1, st, 0.f, R.kv_tokens * kb, R.kv_cache));
+        HIPCK(c, rank, launch_synth_fill(R.stream, 8, seed, 2, st, 0.f, R.kv_tokens * sb / 2, R.kv_scale));
     } else if (c->kv_fmt == KV_I8G8) {
         HIPCK(c, rank, launch_synth_fill(R.stream, 1, seed, 1, st, 0.f, R.kv_tokens * kb, R.kv_cache));
         HIPCK(c, rank, launch_synth_fill(R.stream, 3, seed, 2, st, 0.02f, R.kv_tokens * sb / 2, R.kv_scale));

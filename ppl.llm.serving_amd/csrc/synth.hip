@@ -38,6 +38,16 @@ __global__ __launch_bounds__(256) void synth_fill_fp8_kernel(int kind, uint64_t 
     }
 }
 
+// KV_I4G32 slab fill: kind 7 bytes of two nibbles 1 .. 15 each (0 is never written by the format), kind 8 fp16 group scales of the
+// format's rule -- 8 significant bits (the low three mantissa bits zero), 2^-7 .. just under 2^-3
+__global__ __launch_bounds__(256) void synth_fill_i4_kernel(int kind, uint64_t key, uint64_t n, void* out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t r = (uint32_t)(synth_val(key, i) >> 32);
+        if (kind == 7) ((uint8_t*)out)[i] = (uint8_t)((1u + (r & 0xffffu) % 15u) | ((1u + (r >> 16) % 15u) << 4));
+        else ((uint16_t*)out)[i] = (uint16_t)(((15 - 4 - (int)(r & 3u)) << 10) | (((r >> 2) & 0x7fu) << 3));
+    }
+}
+
 hipError_t launch_synth_fill(hipStream_t s, int kind, uint64_t seed, uint32_t tensor_id, uint32_t stream_id, float amp,
                              uint64_t n, void* out) {
     if (n == 0) return hipSuccess;
@@ -50,7 +60,8 @@ hipError_t launch_synth_fill(hipStream_t s, int kind, uint64_t seed, uint32_t te
     const uint64_t key = mix(seed ^ ((uint64_t)tensor_id * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)stream_id * 0xD1B54A32D192ED03ull));
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    if (kind == 5 || kind == 6) hipLaunchKernelGGL(synth_fill_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, n, out);
+    if (kind == 7 || kind == 8) hipLaunchKernelGGL(synth_fill_i4_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, n, out);
+    else if (kind == 5 || kind == 6) hipLaunchKernelGGL(synth_fill_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, n, out);
     else hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, kind, key, amp, n, out);
     return hipGetLastError();
 }

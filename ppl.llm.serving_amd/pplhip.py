@@ -367,6 +367,7 @@ class Context:
         n = self.kv_tokens * (sb if which else kb)
         if n == 0:
             return None
+        # quantised slabs as bytes: int8 and fp8 one per channel, int4 (cache_quant_bit 4) two channels per byte, low nibble first
         dt = np.float16 if which == 1 or self.desc.cache_quant_bit == 0 else np.int8
         out = np.empty(n // np.dtype(dt).itemsize, dtype=dt)
         self._ck(lib().pplhip_kv_read(self.h, rank, which, 0, out.ctypes.data, n), rank, "kv_read")

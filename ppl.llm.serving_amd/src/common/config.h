@@ -74,8 +74,8 @@ struct ModelConfig final {
     int32_t num_kv_heads = 0;          // optional key, defaults to num_heads
     int32_t vocab_size = 0;
     // ---- KV cache format (required keys; llm_engine.cc:118-169 gives the four layouts) ----------------------------
-    int32_t cache_quant_bit = 0;       // 0 (fp16) or 8 (int8)
-    int32_t cache_quant_group = 0;     // 8 with int8, 1 with fp16
+    int32_t cache_quant_bit = 0;       // 0 (fp16), 8 (int8 / fp8) or 4 (int4)
+    int32_t cache_quant_group = 0;     // 1 with fp16; with bit 8: 8 (int8) or head_dim (fp8 e4m3, one scale per head row); 32 with bit 4
     int32_t cache_layout = 0;          // 0..3
     int32_t cache_mode = 0;            // 0 contiguous ranges, 1 pages
     int32_t page_size = 0;             // required when cache_mode == 1

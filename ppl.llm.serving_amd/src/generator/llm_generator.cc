@@ -72,9 +72,12 @@ RetCode LLMGenerator::CheckParameters() const {
     // this project's fp8 e4m3 KV cache: group = head_dim (one power-of-two scale per head row; the reference has no such pair)
     const int head_dim = m.num_heads > 0 ? m.hidden_dim / m.num_heads : 0;
     const bool fp8_kv = m.cache_quant_bit == 8 && m.cache_quant_group == head_dim && (head_dim == 32 || head_dim == 64 || head_dim == 128);
-    if (!int8_kv && !fp16_kv && !fp8_kv) {
+    // this project's int4 KV cache: one fp16 scale per 32 channels (the reference has no such pair either)
+    const bool int4_kv = m.cache_quant_bit == 4 && m.cache_quant_group == 32 && (head_dim == 32 || head_dim == 64 || head_dim == 128);
+    if (!int8_kv && !fp16_kv && !fp8_kv && !int4_kv) {
         LOG(ERROR) << "only support (cache_quant_bit == 8 and cache_quant_group == 8), (cache_quant_bit == 8 and cache_quant_group == "
-                      "head_dim) or (cache_quant_bit == 0 and cache_quant_group == 1)";
+                      "head_dim), (cache_quant_bit == 4 and cache_quant_group == 32, head_dim 32 / 64 / 128) or (cache_quant_bit == 0 and "
+                      "cache_quant_group == 1)";
         return RC_INVALID_VALUE;
     }
     if (!m.dynamic_batching) { LOG(ERROR) << "only support dynamic_batching == true"; return RC_INVALID_VALUE; }

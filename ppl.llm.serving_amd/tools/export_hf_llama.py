@@ -133,7 +133,7 @@ def params_json(cfg, args):
         rope_theta = cfg["rope_parameters"].get("rope_theta")
     kv = getattr(args, "kv_cache", None) or ("int8" if args.cache_quant_bit == 8 else "fp16")
     head_dim = cfg["hidden_size"] // cfg["num_attention_heads"]
-    kv_bit, kv_group = {"fp16": (0, 1), "int8": (8, 8), "fp8": (8, head_dim)}[kv]
+    kv_bit, kv_group = {"fp16": (0, 1), "int8": (8, 8), "fp8": (8, head_dim), "int4": (4, 32)}[kv]
     p = {"num_heads": cfg["num_attention_heads"], "num_kv_heads": cfg.get("num_key_value_heads", cfg["num_attention_heads"]),
          "num_layers": cfg["num_hidden_layers"], "hidden_dim": cfg["hidden_size"], "intermediate_dim": cfg["intermediate_size"],
          "vocab_size": cfg["vocab_size"], "cache_quant_bit": kv_bit,
@@ -155,9 +155,9 @@ def main(argv=None):
     ap.add_argument("--quant", choices=["none", "w8a16", "w4a16"], default="w8a16")
     ap.add_argument("--quant-group", type=int, default=128)
     ap.add_argument("--cache-quant-bit", type=int, choices=[0, 8], default=8)
-    ap.add_argument("--kv-cache", choices=["fp16", "int8", "fp8"], default=None,
+    ap.add_argument("--kv-cache", choices=["fp16", "int8", "fp8", "int4"], default=None,
                     help="KV cache format; overrides --cache-quant-bit: fp16 (0, 1), int8 group 8 (8, 8), fp8 e4m3 with one scale per "
-                         "head row (8, head_dim)")
+                         "head row (8, head_dim), int4 with one fp16 scale per 32 channels (4, 32)")
     ap.add_argument("--cache-layout", type=int, choices=[0, 1, 2, 3], default=3)
     ap.add_argument("--cache-mode", type=int, choices=[0, 1], default=0)
     ap.add_argument("--page-size", type=int, default=16)
