@@ -257,6 +257,38 @@ PPLHIP_API int pplhip_kv_write(pplhip_ctx* ctx, int rank, int which, uint64_t of
 PPLHIP_API int pplhip_kv_fill_synthetic(pplhip_ctx* ctx, int rank, uint64_t seed);
 
 /* ================================================================================================
+ * multi-LoRA: per-request adapters on attention.wqkv, attention.wo and feed_forward.w2 (no counterpart in the reference; library
+ * extension, DESIGN.md "numerics").  An adapter gives a target linear y0 = linear(x) the factors A fp16 [r, K], B fp16 [N, r] and one fp32
+ * scale (lora_alpha / r); rows of a request that uses it become y = fp16(fp32(y0) + scale * fp16(x A^T) B^T), fp32 sums.  The update works
+ * on the fp16 input and output of the linear, so it is the same over fp16, W8A16 and W4A16 base weights and over every KV format.
+ * Arrived without a version bump (pplhip_version() stays 1.2): a client tells a library that has it by the symbol pplhip_lora_commit
+ * (dlsym).  Every pplhip_lora_* entry point and pplhip_set_adapters return PPLHIP_UNSUPPORTED when world_size > 1 (tensor parallelism) or
+ * act_quant_bit != 0 (online_i8i8 / online_f8f8: the norm writes only the 1-byte operand, there is no fp16 x).  gate / up (w13) targets are
+ * refused by name: the fused SwiGLU epilogue never materialises gate and up.
+ * Sequence: pplhip_lora_load (or set_tensor x n + commit) once per slot; then per step pplhip_set_inputs, pplhip_set_adapters, pplhip_run.
+ * ============================================================================================== */
+#define PPLHIP_LORA_MAX_SLOTS 64
+#define PPLHIP_LORA_MAX_RANK 128
+
+/* uploads one factor of adapter `slot` (0 .. PPLHIP_LORA_MAX_SLOTS - 1) with rank r (1 .. PPLHIP_LORA_MAX_RANK; zero-padded to a multiple
+ * of 16 on the device).  name: layers.{l}.attention.wqkv.lora_a (fp16 [r, hidden]) / .lora_b (fp16 [N, r], rows in the container's wqkv
+ * order), and the same under attention.wo and feed_forward.w2 (lora_a [r, intermediate_dim]).  A name under feed_forward.w13 returns
+ * PPLHIP_UNSUPPORTED.  A committed slot must be unloaded first (PPLHIP_INVALID_VALUE). */
+PPLHIP_API int pplhip_lora_set_tensor(pplhip_ctx* ctx, int rank, int slot, const char* name, const void* data, uint64_t bytes, int32_t r);
+/* makes the slot usable: every (layer, target) must have both factors (of one rank) or neither, at least one pair present. */
+PPLHIP_API int pplhip_lora_commit(pplhip_ctx* ctx, int rank, int slot, float scale);
+/* reads `<dir>/lora.pplhip` -- the weight container's format with the names above and a one-element fp32 tensor lora.scale -- and commits. */
+PPLHIP_API int pplhip_lora_load(pplhip_ctx* ctx, int rank, int slot, const char* dir);
+/* synchronises the rank's stream, then frees the slot (committed or half loaded).  A staged adapter assignment is dropped with it: the
+ * next pplhip_run wants a new pplhip_set_inputs (+ pplhip_set_adapters). */
+PPLHIP_API int pplhip_lora_unload(pplhip_ctx* ctx, int rank, int slot);
+/* the adapter of every request of the staged step: slots host [batch], -1 = none.  After pplhip_set_inputs (which clears the assignment:
+ * callers that never call this get the step they always got) and before pplhip_run.  With every entry -1 the step issues exactly the
+ * launches of a step without adapters.  A step with an assigned row runs on one lane, reduces its split-K linears at once and is never
+ * captured into or replayed from a decode graph. */
+PPLHIP_API int pplhip_set_adapters(pplhip_ctx* ctx, int rank, const int32_t* slots, int64_t batch);
+
+/* ================================================================================================
  * the step -- replaces SetInputTask / RunModelTask (src/engine/llm_engine.cc:29-116)
  * ============================================================================================== */
 
@@ -293,7 +325,7 @@ PPLHIP_API int pplhip_penalty(pplhip_ctx* ctx, float* logits_device, const pplhi
 
 /* kernel classes that are timed with HIP events when opts.enable_profiling != 0 */
 enum { PPLHIP_PROF_ATTN_DECODE = 0, PPLHIP_PROF_ATTN_PREFILL = 1, PPLHIP_PROF_GEMM = 2,
-       PPLHIP_PROF_RUN = 3, PPLHIP_PROF_COUNT = 4 };
+       PPLHIP_PROF_RUN = 3, PPLHIP_PROF_LORA = 4 /* the two adapter kernels of a target linear */, PPLHIP_PROF_COUNT = 5 };
 
 /* clears the event log of this rank. */
 PPLHIP_API int pplhip_profile_reset(pplhip_ctx* ctx, int rank);
@@ -385,6 +417,8 @@ typedef struct pplhip_step_shape {
     int64_t batch, num_tokens, decoding_batches, max_kv_len;   /* pplhip_step */
     const int64_t* seq_starts;          /* host [batch + 1], or NULL: the rank holds no host copy (never read for a pure-decode step) */
     int32_t capturing, dump;            /* the stream is capturing a graph; a residual dump is on */
+    int32_t lora;                       /* some row of the step carries an adapter (pplhip_set_adapters): every linear's output must exist
+                                           in memory, so no slabs stay unreduced and the step runs on one lane.  0: the plan of every step so far */
 } pplhip_step_shape;
 typedef struct pplhip_step_plan {
     int32_t schedule;                   /* as pplhip_comm_info_t.schedule: 0 one lane, 1 two lanes, 2 two chunks on the communication stream */
@@ -420,6 +454,17 @@ PPLHIP_API int pplhip_op_quant_act_f8(void* stream, const void* x, int64_t M, in
 PPLHIP_API int pplhip_op_quant_weight_f8(void* stream, const void* w, int32_t N, int32_t K, void* q, void* scale);
 PPLHIP_API int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M,
                                    int32_t N, int32_t K, void* y, int32_t out_fp32, int32_t swiglu);
+
+/* the two multi-LoRA kernels alone (csrc/k_lora.hip) on the caller's stream: rows m of y [T, ldy] with slot s = row_slots[m] >= 0 become
+ * fp16(fp32(y[m, n]) + scales[s] * sum_j fp32(t[m, j]) B_s[n, j]), t[m, j] = fp16(sum_k x[m, k] A_s[j, k]); rows with -1 are neither read
+ * nor written.  x [T, ldx], y: device fp16; row_slots: HOST [T]; A, B: HOST arrays [n_slots] of device pointers (NULL: slot not loaded),
+ * A_s fp16 [rp, K], B_s fp16 [N, rp] with rp = ranks[s] rounded up to a multiple of 16 and the rows / columns past ranks[s] zero (what
+ * pplhip_lora_set_tensor makes of a factor); ranks, scales: HOST [n_slots].  ws: device scratch for the tile list, the slot table and t,
+ * 8192 + (T / 16 + n_slots + 1) * 4352 bytes always suffice.  K % 32 == 0, N % 16 == 0, ldx % 8 == 0, n_slots <= PPLHIP_LORA_MAX_SLOTS,
+ * ranks 1 .. PPLHIP_LORA_MAX_RANK, every named slot loaded: else PPLHIP_INVALID_VALUE before any HIP call.  For the tests. */
+PPLHIP_API int pplhip_op_lora(void* stream, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t T, int32_t N, int32_t K,
+                              const int32_t* row_slots, int32_t n_slots, const void* const* A, const void* const* B, const int32_t* ranks,
+                              const float* scales, void* ws, uint64_t ws_bytes);
 
 PPLHIP_API int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out);
 

@@ -160,6 +160,27 @@ hipError_t launch_linear_f8(hipStream_t s, const uint8_t* xq, const float* sx, c
 // dst row r = src row perm(r): r even -> r/2 (gate), r odd -> half + r/2 (up).  row_bytes % 4 == 0.
 hipError_t launch_interleave_rows(hipStream_t s, const void* src, void* dst, int rows, int64_t row_bytes);
 
+// ---- k_lora.hip: multi-LoRA, the low-rank update of a layer linear on the rows whose request carries an adapter --------------------
+constexpr int LORA_MAX_SLOTS = 64, LORA_MAX_RANK = 128;   // PPLHIP_LORA_MAX_SLOTS / PPLHIP_LORA_MAX_RANK
+// up to 16 token rows that share adapter slot `slot`; row[i] = -1 marks padding.  Built on the host (pplhip.cc lora_build_tiles).
+struct LoraTile {
+    int32_t slot;
+    int32_t n;          // rows in use (the first n of row[])
+    int32_t row[16];
+};
+// one slot's factors for ONE target linear: a [rp, K] and b [N, rp] fp16 with the rank zero-padded to rp (a multiple of 16);
+// a == NULL: the adapter leaves this linear alone
+struct LoraSlot {
+    const uint16_t* a;
+    const uint16_t* b;
+    int32_t rp;
+    float scale;
+};
+// t[tile][16][LORA_MAX_RANK] = fp16(x rows . a^T), then y rows += scale * t . b^T in place (fp16(fp32(y) + scale * sum)); slots: device
+// LoraSlot [LORA_MAX_SLOTS]; t: device scratch of ntiles * 16 * LORA_MAX_RANK fp16.  K % 32 == 0, N % 16 == 0, ldx % 8 == 0, x 16-byte aligned
+hipError_t launch_lora(hipStream_t s, const LoraTile* tiles, int ntiles, const LoraSlot* slots, const uint16_t* x, int64_t ldx, uint16_t* y,
+                       int64_t ldy, int N, int K, uint16_t* t);
+
 // ---- k_comm.hip ------------------------------------------------------------------------------
 // direct (all-links) tensor-parallel collectives over peer-mapped exchange regions; see the file header.
 constexpr int P2P_MAX_RANKS = 8;

@@ -1,6 +1,7 @@
 // libpplhip.so -- the C ABI of include/pplhip.h: per-rank runtime (streams, weights, KV slab, step inputs,
 // activations), the decoder forward as a sequence of hand-written gfx950 kernels, RCCL collectives for tensor
-// parallelism and the sampler.  This file replaces what the reference reaches through ppl.nn
+// parallelism, the sampler and per-request LoRA adapters (slots loaded at run time, a tile list per
+// step: "multi-LoRA" below).  This file replaces what the reference reaches through ppl.nn
 // (Engine/Runtime/Tensor, src/backends/cuda/resource_manager.cc:43-211) and ppl.llm.kernel.cuda.
 #include "../../include/pplhip.h"
 
@@ -47,6 +48,19 @@ struct Layer {
     uint16_t* attn_norm = nullptr;
     uint16_t* ffn_norm = nullptr;
     Linear wqkv, wo, w13, w2;
+};
+
+// One adapter slot of a rank: per (layer, target) the two factors on the device, zero-padded to rank rp (a multiple of 16) and, for w2's
+// A, to the padded row stride Kp of the activation it multiplies.  Targets: 0 attention.wqkv, 1 attention.wo, 2 feed_forward.w2.
+enum { LORA_WQKV = 0, LORA_WO = 1, LORA_W2 = 2, LORA_TARGETS = 3 };
+struct LoraFactor {
+    uint16_t *a = nullptr, *b = nullptr;
+    int ra = 0, rb = 0;   // ranks the two arrived with
+};
+struct LoraAdapter {
+    bool committed = false;
+    float scale = 0.f;
+    std::vector<LoraFactor> f;   // [layer][target]; empty: nothing loaded
 };
 
 struct ProfEvent {
@@ -154,6 +168,20 @@ struct Rank {
     // partial sums are complete" (compute -> communication stream), 2..3 = "chunk i is reduced" (communication -> compute)
     uint32_t* hflags = nullptr;
     uint32_t h_ready_ep[2] = {0, 0}, h_done_ep[2] = {0, 0};
+
+    // multi-LoRA (k_lora.hip): adapters by slot, allocated when a slot is loaded
+    LoraAdapter lora[LORA_MAX_SLOTS];
+    int lora_committed = 0;                 // slots in use
+    std::vector<LoraSlot> lora_tab_host;    // [layer][target][slot]: what the kernels read, mirrored on the device (lora_tab)
+    LoraSlot* lora_tab = nullptr;
+    LoraTile* lora_tiles = nullptr;         // the staged step's tile list (device) and its pinned staging copy
+    LoraTile* lora_tiles_host = nullptr;
+    hipEvent_t lora_ev = nullptr;           // the copy out of lora_tiles_host is done
+    int64_t lora_tile_cap = 0;
+    uint16_t* lora_t = nullptr;             // shrink output [lora_tile_cap][16][LORA_MAX_RANK] fp16
+    int lora_ntiles = 0;                    // > 0: the staged step has rows on adapters (pplhip_set_adapters; pplhip_set_inputs clears it)
+    std::vector<uint8_t> lora_touch;        // [layer][target]: some adapter of the staged assignment changes this linear
+    bool lora_stale = false;                // a slot was unloaded under a staged assignment: pplhip_run wants new inputs first
 
     // diagnosis (pplhip_debug_run_dump): residual stream h and the pending row-parallel FFN output after every layer
     uint16_t* dump_dev = nullptr;  // [L+1][2][T, hidden] fp16 (slot 0 = h, slot 1 = pending), allocated for one run
@@ -685,6 +713,12 @@ void pplhip_destroy(pplhip_ctx* c) {
         for (auto& e : R.prof) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
         for (auto& p : R.prof_free) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
         for (void* p : R.allocs) hipFree(p);
+        for (auto& ad : R.lora) for (auto& f : ad.f) { if (f.a) hipFree(f.a); if (f.b) hipFree(f.b); }
+        if (R.lora_tab) hipFree(R.lora_tab);
+        if (R.lora_tiles) hipFree(R.lora_tiles);
+        if (R.lora_tiles_host) hipHostFree(R.lora_tiles_host);
+        if (R.lora_t) hipFree(R.lora_t);
+        if (R.lora_ev) hipEventDestroy(R.lora_ev);
         for (int g = 0; g < P2P_MAX_RANKS; ++g)
             if (R.peer_ipc[g] && R.peers.base[g]) hipIpcCloseMemHandle(R.peers.base[g]);
         if (R.xbase) hipFree(R.xbase);
@@ -1360,6 +1394,8 @@ int pplhip_kv_fill_synthetic(pplhip_ctx* c, int rank, uint64_t seed) {
 int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
     if (!c || rank < 0 || rank >= (int)c->ranks.size() || !st) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[rank];
+    R.lora_ntiles = 0;   // the adapter assignment belongs to one step (pplhip_set_adapters)
+    R.lora_stale = false;
     const int64_t B = st->batch, T = st->num_tokens;
     if (B < 0 || T < 0 || B > R.cap_B || T > R.cap_T)
         return fail(c, rank, PPLHIP_INVALID_VALUE, "step exceeds max_running_batch / max_tokens_per_step");
@@ -1441,6 +1477,284 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
     return 0;
 }
 
+
+// ---- multi-LoRA ------------------------------------------------------------------------------------------------------------------------
+// Tile list of a row -> slot map (-1: no adapter): every assigned row in exactly one tile, a tile's rows share one slot, unassigned rows in
+// none.  Slots in ascending order, rows of a slot in ascending order, 16 to a tile, the last tile of a slot padded with -1.
+static void lora_build_tiles(const int32_t* row_slots, int64_t T, std::vector<LoraTile>& out) {
+    int64_t cnt[LORA_MAX_SLOTS] = {0}, first[LORA_MAX_SLOTS];
+    for (int64_t m = 0; m < T; ++m) if (row_slots[m] >= 0) ++cnt[row_slots[m]];
+    int64_t nt = 0;
+    for (int s = 0; s < LORA_MAX_SLOTS; ++s) { first[s] = nt; nt += (cnt[s] + 15) / 16; }
+    LoraTile blank;
+    blank.slot = 0; blank.n = 0;
+    for (int i = 0; i < 16; ++i) blank.row[i] = -1;
+    out.assign((size_t)nt, blank);
+    int64_t pos[LORA_MAX_SLOTS] = {0};
+    for (int64_t m = 0; m < T; ++m) {
+        const int s = row_slots[m];
+        if (s < 0) continue;
+        LoraTile& tl = out[(size_t)(first[s] + pos[s] / 16)];
+        tl.slot = s;
+        tl.row[tl.n++] = (int32_t)m;
+        ++pos[s];
+    }
+}
+
+// what every adapter entry point refuses: tensor parallelism and quantised activations (include/pplhip.h)
+static int lora_guard(pplhip_ctx* c, int rank) {
+    if (!c || rank < 0 || rank >= (int)c->ranks.size()) return PPLHIP_INVALID_VALUE;
+    if (c->tp > 1) return fail(c, rank, PPLHIP_UNSUPPORTED, "LoRA adapters under tensor parallelism (world_size > 1) are not supported");
+    if (c->act_fmt != ACT_FP16) return fail(c, rank, PPLHIP_UNSUPPORTED, "LoRA adapters need fp16 activations (act_quant_bit 0): online_i8i8 / online_f8f8 keep no fp16 input of the linears");
+    return 0;
+}
+
+// the device buffers every adapter step shares, allocated when the first factor arrives
+static int lora_ensure_buffers(pplhip_ctx* c, int rank) {
+    Rank& R = c->ranks[rank];
+    if (R.lora_tab) return 0;
+    const size_t ntab = (size_t)c->d.num_layers * LORA_TARGETS * LORA_MAX_SLOTS;
+    const int64_t cap = R.cap_T / 16 + LORA_MAX_SLOTS + 1;
+    void *tab = nullptr, *tiles = nullptr, *t = nullptr, *host = nullptr;
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipMalloc(&tab, ntab * sizeof(LoraSlot));
+    if (e == hipSuccess) e = hipMemset(tab, 0, ntab * sizeof(LoraSlot));
+    if (e == hipSuccess) e = hipMalloc(&tiles, (size_t)cap * sizeof(LoraTile));
+    if (e == hipSuccess) e = hipMalloc(&t, (size_t)cap * 16 * LORA_MAX_RANK * 2);
+    if (e == hipSuccess) e = hipHostMalloc(&host, (size_t)cap * sizeof(LoraTile), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (tab) hipFree(tab);
+        if (tiles) hipFree(tiles);
+        if (t) hipFree(t);
+        if (host) hipHostFree(host);
+        (void)hipGetLastError();
+        return fail(c, rank, PPLHIP_OUT_OF_MEMORY, std::string("adapter buffers: ") + hipGetErrorString(e));
+    }
+    R.lora_tab = (LoraSlot*)tab; R.lora_tiles = (LoraTile*)tiles; R.lora_t = (uint16_t*)t; R.lora_tiles_host = (LoraTile*)host;
+    R.lora_ev = ev; R.lora_tile_cap = cap;
+    R.lora_tab_host.assign(ntab, LoraSlot{nullptr, nullptr, 0, 0.f});
+    R.lora_touch.assign((size_t)c->d.num_layers * LORA_TARGETS, 0);
+    return 0;
+}
+
+static void lora_free_slot(Rank& R, int slot) {
+    LoraAdapter& ad = R.lora[slot];
+    for (auto& f : ad.f) { if (f.a) hipFree(f.a); if (f.b) hipFree(f.b); }
+    ad.f.clear();
+    if (ad.committed) --R.lora_committed;
+    ad.committed = false;
+    ad.scale = 0.f;
+}
+
+// the slot's column of the kernels' table, on the host mirror and the device (the stream is idle: nothing reads the table meanwhile)
+static int lora_publish_slot(pplhip_ctx* c, int rank, int slot) {
+    Rank& R = c->ranks[rank];
+    const LoraAdapter& ad = R.lora[slot];
+    const size_t n = (size_t)c->d.num_layers * LORA_TARGETS;
+    for (size_t i = 0; i < n; ++i) {
+        LoraSlot e{nullptr, nullptr, 0, 0.f};
+        if (ad.committed && ad.f[i].a) e = LoraSlot{ad.f[i].a, ad.f[i].b, (ad.f[i].ra + 15) / 16 * 16, ad.scale};
+        R.lora_tab_host[i * LORA_MAX_SLOTS + slot] = e;
+    }
+    HIPCK(c, rank, hipMemcpy(R.lora_tab, R.lora_tab_host.data(), R.lora_tab_host.size() * sizeof(LoraSlot), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int pplhip_lora_set_tensor(pplhip_ctx* c, int rank, int slot, const char* name, const void* data, uint64_t bytes, int32_t r) {
+    if (int rc = lora_guard(c, rank)) return rc;
+    if (!name || !data) return PPLHIP_INVALID_VALUE;
+    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
+    if (r < 1 || r > LORA_MAX_RANK) return fail(c, rank, PPLHIP_INVALID_VALUE, std::string(name) + ": rank " + std::to_string(r) + " outside 1 .. " + std::to_string(LORA_MAX_RANK));
+    Rank& R = c->ranks[rank];
+    int l = -1;
+    char rest[128];
+    if (sscanf(name, "layers.%d.%127s", &l, rest) != 2 || l < 0 || l >= c->d.num_layers) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown adapter tensor ") + name);
+    if (!strncmp(rest, "feed_forward.w13.", 17))
+        return fail(c, rank, PPLHIP_UNSUPPORTED, std::string(name) + ": adapters on feed_forward.w13 (gate / up) are not supported, the fused SwiGLU epilogue never materialises them");
+    Layer& L = R.layers[l];
+    struct { const char* n; Linear* lin; } tab[LORA_TARGETS] = {{"attention.wqkv.", &L.wqkv}, {"attention.wo.", &L.wo}, {"feed_forward.w2.", &L.w2}};
+    int target = -1, is_b = -1;
+    for (int i = 0; i < LORA_TARGETS; ++i) {
+        const size_t nl = strlen(tab[i].n);
+        if (strncmp(rest, tab[i].n, nl)) continue;
+        if (!strcmp(rest + nl, "lora_a")) { target = i; is_b = 0; }
+        if (!strcmp(rest + nl, "lora_b")) { target = i; is_b = 1; }
+    }
+    if (target < 0) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown adapter tensor ") + name);
+    const Linear& lin = *tab[target].lin;
+    if (lin.Kp % 32 || lin.N % 16) return fail(c, rank, PPLHIP_UNSUPPORTED, std::string(name) + ": the adapter kernels need K % 32 == 0 and N % 16 == 0");
+    const uint64_t want = is_b ? (uint64_t)lin.N * r * 2 : (uint64_t)r * lin.K * 2;
+    if (bytes != want) return fail(c, rank, PPLHIP_INVALID_VALUE, std::string("tensor ") + name + ": got " + std::to_string(bytes) + " bytes, want " + std::to_string(want));
+    LoraAdapter& ad = R.lora[slot];
+    if (ad.committed) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " is committed: unload it first");
+    HIPCK(c, rank, hipSetDevice(R.device));
+    if (int rc = lora_ensure_buffers(c, rank)) return rc;
+    if (ad.f.empty()) ad.f.resize((size_t)c->d.num_layers * LORA_TARGETS);
+    LoraFactor& f = ad.f[(size_t)l * LORA_TARGETS + target];
+    const int rp = (r + 15) / 16 * 16;
+    // zero-padded on the device: A [rp, Kp] (rows past r and columns past K zero), B [N, rp] (columns past r zero)
+    const size_t pitch = is_b ? (size_t)rp * 2 : (size_t)lin.Kp * 2, rows = is_b ? (size_t)lin.N : (size_t)rp;
+    const size_t src_pitch = is_b ? (size_t)r * 2 : (size_t)lin.K * 2, src_rows = is_b ? (size_t)lin.N : (size_t)r;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, pitch * rows);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, rank, PPLHIP_OUT_OF_MEMORY, std::string("tensor ") + name + ": " + hipGetErrorString(e)); }
+    e = hipMemset(p, 0, pitch * rows);
+    if (e == hipSuccess) e = hipMemcpy2D(p, pitch, data, src_pitch, src_pitch, src_rows, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(p); return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, std::string("tensor ") + name + ": " + hipGetErrorString(e)); }
+    uint16_t*& dst = is_b ? f.b : f.a;
+    if (dst) hipFree(dst);
+    dst = (uint16_t*)p;
+    (is_b ? f.rb : f.ra) = r;
+    return 0;
+}
+
+int pplhip_lora_commit(pplhip_ctx* c, int rank, int slot, float scale) {
+    if (int rc = lora_guard(c, rank)) return rc;
+    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
+    Rank& R = c->ranks[rank];
+    LoraAdapter& ad = R.lora[slot];
+    if (ad.committed) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " is committed already");
+    if (!std::isfinite(scale)) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter scale is not finite");
+    int pairs = 0;
+    for (size_t i = 0; i < ad.f.size(); ++i) {
+        const LoraFactor& f = ad.f[i];
+        if (!f.a && !f.b) continue;
+        const std::string where = "layer " + std::to_string(i / LORA_TARGETS) + " target " + std::to_string(i % LORA_TARGETS);
+        if (!f.a || !f.b) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + ": " + where + " has one factor of two");
+        if (f.ra != f.rb) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + ": " + where + " has factors of ranks " + std::to_string(f.ra) + " and " + std::to_string(f.rb));
+        ++pairs;
+    }
+    if (!pairs) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " holds no factors");
+    HIPCK(c, rank, hipSetDevice(R.device));
+    HIPCK(c, rank, hipStreamSynchronize(R.stream));
+    ad.committed = true;
+    ad.scale = scale;
+    ++R.lora_committed;
+    const int rc = lora_publish_slot(c, rank, slot);
+    if (rc) {   // the device table did not take it: not committed, and the host mirror names none of its factors
+        ad.committed = false;
+        --R.lora_committed;
+        for (size_t i = 0; i < ad.f.size(); ++i) R.lora_tab_host[i * LORA_MAX_SLOTS + slot] = LoraSlot{nullptr, nullptr, 0, 0.f};
+    }
+    return rc;
+}
+
+int pplhip_lora_unload(pplhip_ctx* c, int rank, int slot) {
+    if (int rc = lora_guard(c, rank)) return rc;
+    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
+    Rank& R = c->ranks[rank];
+    if (R.lora[slot].f.empty()) return fail(c, rank, PPLHIP_NOT_FOUND, "adapter slot " + std::to_string(slot) + " is not loaded");
+    HIPCK(c, rank, hipSetDevice(R.device));
+    HIPCK(c, rank, hipStreamSynchronize(R.stream));
+    const bool was = R.lora[slot].committed;
+    lora_free_slot(R, slot);
+    if (R.lora_ntiles > 0) { R.lora_ntiles = 0; R.lora_stale = true; }
+    return was ? lora_publish_slot(c, rank, slot) : 0;
+}
+
+// container: pplhip_rank_load's, with the adapter names and lora.scale (fp32 [1]); the rank of a factor follows from its size
+int pplhip_lora_load(pplhip_ctx* c, int rank, int slot, const char* dir) {
+    if (int rc = lora_guard(c, rank)) return rc;
+    if (!dir) return PPLHIP_INVALID_VALUE;
+    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
+    Rank& R = c->ranks[rank];
+    if (!R.lora[slot].f.empty()) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " is in use: unload it first");
+    const std::string path = std::string(dir) + "/lora.pplhip";
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return fail(c, rank, PPLHIP_NOT_FOUND, "cannot open " + path);
+    char magic[8];
+    uint32_t count = 0;
+    int rc = 0;
+    bool have_scale = false;
+    float scale = 0.f;
+    std::vector<char> buf;
+    uint64_t max_bytes = 4;
+    for (const Layer& L : R.layers)
+        for (const Linear* lin : {&L.wqkv, &L.wo, &L.w2}) max_bytes = std::max<uint64_t>(max_bytes, (uint64_t)LORA_MAX_RANK * std::max(lin->N, lin->K) * 2);
+    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "PPLHIPW1", 8) || fread(&count, 4, 1, f) != 1) {
+        fclose(f);
+        return fail(c, rank, PPLHIP_INVALID_VALUE, "bad header in " + path);
+    }
+    for (uint32_t i = 0; i < count && !rc; ++i) {
+        uint32_t nl = 0; uint64_t nb = 0;
+        char name[256];
+        if (fread(&nl, 4, 1, f) != 1 || nl >= sizeof(name) || fread(name, 1, nl, f) != nl || fread(&nb, 8, 1, f) != 1) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, "truncated container " + path); break; }
+        name[nl] = 0;
+        const long pos = ftell(f);
+        fseek(f, (64 - pos % 64) % 64, SEEK_CUR);
+        // (no factor is larger than LORA_MAX_RANK rows or columns of the widest target linear: a corrupt size is refused, not allocated)
+        if (nb > max_bytes) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, std::string("tensor ") + name + " in " + path + ": " + std::to_string(nb) + " bytes is larger than any adapter tensor"); break; }
+        buf.resize(nb);
+        if (fread(buf.data(), 1, nb, f) != nb) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, "truncated container " + path); break; }
+        if (!strcmp(name, "lora.scale")) {
+            if (nb != 4) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, "lora.scale must be one fp32"); break; }
+            memcpy(&scale, buf.data(), 4);
+            have_scale = true;
+            continue;
+        }
+        // rank from the size: lora_a is [r, K], lora_b [N, r] of the target linear
+        int l = -1;
+        char rest[128];
+        int64_t unit = 0;
+        if (sscanf(name, "layers.%d.%127s", &l, rest) == 2 && l >= 0 && l < c->d.num_layers) {
+            const Layer& L = R.layers[l];
+            const bool b = strstr(rest, ".lora_b") != nullptr;
+            if (!strncmp(rest, "attention.wqkv.", 15)) unit = b ? L.wqkv.N : L.wqkv.K;
+            else if (!strncmp(rest, "attention.wo.", 13)) unit = b ? L.wo.N : L.wo.K;
+            else if (!strncmp(rest, "feed_forward.w2.", 16)) unit = b ? L.w2.N : L.w2.K;
+        }
+        const int64_t r = unit > 0 && nb % (uint64_t)(unit * 2) == 0 ? (int64_t)(nb / (uint64_t)(unit * 2)) : 1;   // (a wrong size or name: set_tensor says which)
+        rc = pplhip_lora_set_tensor(c, rank, slot, name, buf.data(), nb, (int32_t)std::min<int64_t>(r, INT32_MAX));
+    }
+    fclose(f);
+    if (!rc && !have_scale) rc = fail(c, rank, PPLHIP_INVALID_VALUE, path + " has no lora.scale");
+    if (!rc) rc = pplhip_lora_commit(c, rank, slot, scale);
+    if (rc && !R.lora[slot].f.empty()) {   // nothing half loaded stays behind
+        const std::string msg = R.err;
+        lora_free_slot(R, slot);
+        R.err = msg;
+    }
+    return rc;
+}
+
+int pplhip_set_adapters(pplhip_ctx* c, int rank, const int32_t* slots, int64_t batch) {
+    if (int rc = lora_guard(c, rank)) return rc;
+    Rank& R = c->ranks[rank];
+    if (!slots || batch != R.B) return fail(c, rank, PPLHIP_INVALID_VALUE, "pplhip_set_adapters: one slot per request of the staged step");
+    R.lora_ntiles = 0;
+    R.lora_stale = false;
+    bool any = false;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int s = slots[b];
+        if (s == -1) continue;
+        if (s < 0 || s >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "request " + std::to_string(b) + ": adapter slot " + std::to_string(s) + " out of range");
+        if (!R.lora[s].committed) return fail(c, rank, PPLHIP_INVALID_VALUE, "request " + std::to_string(b) + ": adapter slot " + std::to_string(s) + " is not loaded");
+        any = true;
+    }
+    if (!any) return 0;   // exactly the step without adapters
+    if (!R.h_seq) return fail(c, rank, PPLHIP_INVALID_VALUE, "pplhip_set_adapters before pplhip_set_inputs");
+    std::vector<int32_t> row_slots((size_t)R.T, -1);
+    for (int64_t b = 0; b < batch; ++b)
+        for (int64_t m = R.h_seq[b]; m < R.h_seq[b + 1]; ++m) row_slots[(size_t)m] = slots[b];   // (seq_starts validated by pplhip_set_inputs)
+    std::vector<LoraTile> tiles;
+    lora_build_tiles(row_slots.data(), R.T, tiles);
+    if ((int64_t)tiles.size() > R.lora_tile_cap) return fail(c, rank, PPLHIP_OTHER_ERROR, "adapter tile list exceeds its buffer");
+    std::fill(R.lora_touch.begin(), R.lora_touch.end(), 0);
+    for (int64_t b = 0; b < batch; ++b) {
+        if (slots[b] < 0) continue;
+        const LoraAdapter& ad = R.lora[slots[b]];
+        for (size_t i = 0; i < ad.f.size(); ++i) if (ad.f[i].a) R.lora_touch[i] = 1;
+    }
+    HIPCK(c, rank, hipSetDevice(R.device));
+    HIPCK(c, rank, hipEventSynchronize(R.lora_ev));   // the copy that last read the staging buffer is done
+    memcpy(R.lora_tiles_host, tiles.data(), tiles.size() * sizeof(LoraTile));
+    HIPCK(c, rank, hipMemcpyAsync(R.lora_tiles, R.lora_tiles_host, tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice, R.stream));
+    HIPCK(c, rank, hipEventRecord(R.lora_ev, R.stream));
+    R.lora_ntiles = (int)tiles.size();
+    return 0;
+}
+
 // A chunk of a step: requests [b0, b0 + bn) = token rows [t0, t0 + tn); the first nd requests of the chunk are
 // decode rows.  A step runs as ONE chunk or as two (plan_step).
 using Chunk = pplhip_chunk;
@@ -1496,7 +1810,8 @@ static StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape
     // which is what the chunked schedule pays +3.5 ms per 1024-row step for.  Not with int8 / fp8 activations (shared operand buffer),
     // residual dumps or graph capture.
     const bool identity_comm = comm && s.comm_mode != 2 && !s.has_comm;   // ranks emulated on one device (bench.py --emulate-tp)
-    if (comm && s.tp_overlap && sh.seq_starts && T >= s.tp_overlap_min_tokens && B >= 2) {
+    const bool lanes_ok = !sh.lora;   // a step with adapter rows: one lane, one chunk (the tile list names rows of the whole step)
+    if (lanes_ok && comm && s.tp_overlap && sh.seq_starts && T >= s.tp_overlap_min_tokens && B >= 2) {
         int64_t bm = 1, tm;
         if (nb_decode == B) {   // pure decode: whole 128-row GEMM tiles in the first chunk (row i is request i: seq_starts is not read)
             const int64_t r = (T / 2 + 127) / 128 * 128;
@@ -1508,7 +1823,7 @@ static StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape
         p.chunk[0] = Chunk{0, bm, 0, tm, std::min(nb_decode, bm)};
         p.chunk[1] = Chunk{bm, B - bm, tm, T - tm, std::max<int64_t>(0, nb_decode - bm)};
         p.schedule = SCHED_TWO_CHUNKS;
-    } else if (s.dual_mode && s.has_stream2 && nb_decode == B && T == B && B >= s.dual_min_rows && B <= s.dual_max_rows && B >= 2 &&
+    } else if (lanes_ok && s.dual_mode && s.has_stream2 && nb_decode == B && T == B && B >= s.dual_min_rows && B <= s.dual_max_rows && B >= 2 &&
                (!comm || identity_comm || s.comm_mode == 2 || (s.has_comm && s.has_comm2 && !s.dual_auto)) && s.act_fmt == ACT_FP16 && !dump &&
                !sh.capturing) {
         const int64_t bm = B >= 64 ? (B / 2 + 15) / 16 * 16 : B / 2;   // whole 16-row activation sub-tiles in the first half
@@ -1523,7 +1838,7 @@ static StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape
     // split-K slabs stay unreduced for their consumer: at tensor-parallel size 1, weight-only quantisation, no residual dump, no chunks on the
     // communication stream; wqkv's slabs alone also under tensor parallelism (RoPE + KV write consumes them on the rank itself, while wo / w2
     // feed the all-reduce: their slabs are summed first)
-    p.defer_qkv = s.defer_on && s.act_fmt == ACT_FP16 && !dump && p.schedule != SCHED_TWO_CHUNKS;
+    p.defer_qkv = s.defer_on && s.act_fmt == ACT_FP16 && !dump && p.schedule != SCHED_TWO_CHUNKS && !sh.lora;
     p.defer_reduce = p.defer_qkv && !comm;
     return p;
 }
@@ -1560,6 +1875,19 @@ static int layer_linear(pplhip_ctx* c, int rank, Lane& lane, const Linear& l, co
     return 0;
 }
 
+// the low-rank update of one target linear of layer l on the step's adapter rows (k_lora.hip), right behind the linear that wrote y.  The
+// tile list names absolute token rows: x and y are the whole step's matrices (a step with adapter rows is one chunk on one lane)
+static int layer_lora(pplhip_ctx* c, int rank, Lane& lane, int l, int target, const uint16_t* x, int64_t ldx, uint16_t* y, int N, int K) {
+    Rank& R = c->ranks[rank];
+    if (R.lora_ntiles <= 0 || !R.lora_touch[(size_t)l * LORA_TARGETS + target]) return 0;
+    ProfEvent ev;
+    prof_begin(c, R, lane, PPLHIP_PROF_LORA, &ev);
+    HIPCK(c, rank, launch_lora(lane.stream, R.lora_tiles, R.lora_ntiles, R.lora_tab + ((size_t)l * LORA_TARGETS + target) * LORA_MAX_SLOTS, x, ldx,
+                               y, N, N, K, R.lora_t));
+    prof_end(R, lane, &ev);
+    return 0;
+}
+
 // attention block of layer l for one chunk: (Skip)RMSNorm -> wqkv -> RoPE + KV write -> attention -> wo (partial sums)
 // xn_ready: the fused collective of the previous half-layer already left this block's normalised input in R.xn (and the residual in R.h)
 static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepPlan& p, int l, const Chunk& k, const uint16_t* pending, int split,
@@ -1582,6 +1910,7 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
     prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
     if (int rc = layer_linear(c, rank, lane, L.wqkv, xn, k.tn, R.qkv + k.t0 * nqkv, L.wqkv.N, false, a8, p.defer_qkv ? &lane.sl_qkv : nullptr)) return rc;
     prof_end(R, lane, &ev);
+    if (int rc = layer_lora(c, rank, lane, l, LORA_WQKV, R.xn, hd, R.qkv, nqkv, hd)) return rc;
     const KvAddr kv = make_kv_addr(d, Hkv, D, R.kv_tokens, R.kv_cache, R.kv_scale, l);
     HIPCK(c, rank, launch_rope_kv_write(s, R.qkv, R.rope, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci,
                                         R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &lane.sl_qkv));
@@ -1619,7 +1948,7 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
                               p.defer_reduce ? &lane.sl_part : nullptr))
         return rc;
     prof_end(R, lane, &ev);
-    return 0;
+    return layer_lora(c, rank, lane, l, LORA_WO, R.att, (int64_t)H * D, R.part, hd, H * D);
 }
 
 // feed-forward block of layer l for one chunk: SkipRMSNorm -> w13 with fused SwiGLU (K3 + K10) -> w2 (partial sums)
@@ -1647,7 +1976,7 @@ static int layer_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const StepPlan& p
                               p.defer_reduce && !keep_part2 ? &lane.sl_part2 : nullptr))
         return rc;
     prof_end(R, lane, &ev);
-    return 0;
+    return layer_lora(c, rank, lane, l, LORA_W2, R.act, L.w2.Kp, R.part2, hd, L.w2.Kp);
 }
 
 // all-reduce(sum) of the chunk's rows of `buf` ([T, hidden] fp16) on the lane's channel.  Overlapped mode: on the communication stream,
@@ -1701,7 +2030,8 @@ static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& set
 
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     if (settings.dual_mode && settings.has_stream2) (void)hipStreamIsCapturing(s, &cst);   // (only a two-lane step depends on it)
-    const pplhip_step_shape shape{B, T, R.decoding_batches, R.max_kv_len, R.h_seq, cst != hipStreamCaptureStatusNone, R.dump_dev != nullptr};
+    const pplhip_step_shape shape{B, T, R.decoding_batches, R.max_kv_len, R.h_seq, cst != hipStreamCaptureStatusNone, R.dump_dev != nullptr,
+                                  R.lora_ntiles > 0};
     const StepPlan p = plan_step(settings, shape);
     const Chunk* ck = p.chunk;
     const int nck = p.num_chunks;
@@ -1814,6 +2144,7 @@ static int run_decode_graph(pplhip_ctx* c, int rank, const pplhip_plan_settings&
     const int64_t B = R.B;
     const int64_t nb_decode = std::min<int64_t>(std::max<int64_t>(R.decoding_batches, 0), B);
     if (!c->graph_on || c->tp_on || c->o.enable_profiling || R.T != B || nb_decode != B || B > c->graph_max_batch) return 0;
+    if (R.lora_ntiles > 0) return 0;   // the tile list is this step's own: neither captured nor replayed
     const uint64_t key = (uint64_t)B | ((uint64_t)decode_split(settings, B, R.max_kv_len) << 24) | ((uint64_t)R.max_pages << 32);
     auto it = R.graphs.find(key);
     if (it == R.graphs.end()) {  // first sight: run eagerly (one-time function attributes, lazily loaded code objects)
@@ -1857,7 +2188,7 @@ int pplhip_comm_info(pplhip_ctx* c, int64_t rows, pplhip_comm_info_t* out) {
     out->dual_max_rows = c->dual_mode ? c->dual_max_rows : 0;
     // the schedule plan_step picks for a pure-decode step of `rows` rows (one token per request; no residual dump, no graph capture)
     static const int64_t held[1] = {0};   // "the rank holds a host copy of seq_starts": a pure-decode plan never reads it
-    const pplhip_step_shape shape{rows, rows, rows, 0, held, 0, 0};
+    const pplhip_step_shape shape{rows, rows, rows, 0, held, 0, 0, 0};
     out->schedule = plan_step(plan_settings(c, c->ranks[0]), shape).schedule;
     snprintf(out->notes, sizeof(out->notes), "%s", c->comm_notes.c_str());
     return 0;
@@ -1908,6 +2239,7 @@ int pplhip_run(pplhip_ctx* c, int rank, int cache_prefill) {
     if (!R.kv_cache) return fail(c, rank, PPLHIP_INVALID_VALUE, "kv slab not allocated");
     HIPCK(c, rank, hipSetDevice(R.device));
     if (R.B == 0) return 0;
+    if (R.lora_stale) return fail(c, rank, PPLHIP_INVALID_VALUE, "an adapter slot was unloaded after the step's adapters were set: set the inputs again");
     bool done = false;
     const pplhip_plan_settings settings = plan_settings(c, R);   // once per step
     if (int rc = run_decode_graph(c, rank, settings, &done)) return rc;
@@ -2196,6 +2528,47 @@ int pplhip_op_step_plan(const pplhip_plan_settings* settings, const pplhip_step_
     if (!settings || !shape || !out || shape->batch < 0 || shape->num_tokens < 0) return PPLHIP_INVALID_VALUE;
     *out = plan_step(*settings, *shape);
     return 0;
+}
+
+int pplhip_op_lora(void* stream, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t T, int32_t N, int32_t K, const int32_t* row_slots,
+                   int32_t n_slots, const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, void* ws,
+                   uint64_t ws_bytes) {
+    // everything the kernels trust is checked here, before any HIP call
+    if (T < 0 || T > INT32_MAX || N <= 0 || K <= 0 || K % 32 || N % 16 || ldx < K || ldx % 8 || ldy < N) return PPLHIP_INVALID_VALUE;
+    if (n_slots < 0 || n_slots > LORA_MAX_SLOTS || (T > 0 && !row_slots) || (n_slots > 0 && (!A || !B || !ranks || !scales))) return PPLHIP_INVALID_VALUE;
+    if (((uintptr_t)x & 15) || ((uintptr_t)y & 1)) return PPLHIP_INVALID_VALUE;
+    LoraSlot tab[LORA_MAX_SLOTS];
+    for (int s = 0; s < LORA_MAX_SLOTS; ++s) tab[s] = LoraSlot{nullptr, nullptr, 0, 0.f};
+    for (int s = 0; s < n_slots; ++s) {
+        if (!A[s] && !B[s]) continue;
+        if (!A[s] || !B[s] || ranks[s] < 1 || ranks[s] > LORA_MAX_RANK || ((uintptr_t)A[s] & 15) || ((uintptr_t)B[s] & 15)) return PPLHIP_INVALID_VALUE;
+        tab[s] = LoraSlot{(const uint16_t*)A[s], (const uint16_t*)B[s], (ranks[s] + 15) / 16 * 16, scales[s]};
+    }
+    bool any = false;
+    for (int64_t m = 0; m < T; ++m) {
+        const int s = row_slots[m];
+        if (s == -1) continue;
+        if (s < 0 || s >= n_slots || !tab[s].a) return PPLHIP_INVALID_VALUE;   // out of range, or not loaded
+        any = true;
+    }
+    if (!any) return 0;
+    if (!x || !y || !ws) return PPLHIP_INVALID_VALUE;
+    std::vector<LoraTile> tiles;
+    lora_build_tiles(row_slots, T, tiles);
+    // workspace: slot table | tile list | t, each on a 256-byte boundary
+    const uint64_t tab_bytes = sizeof(tab), tile_bytes = (tiles.size() * sizeof(LoraTile) + 255) / 256 * 256;
+    const uint64_t pre = (256 - ((uintptr_t)ws & 255)) & 255;
+    const uint64_t need = pre + tab_bytes + tile_bytes + (uint64_t)tiles.size() * 16 * LORA_MAX_RANK * 2;
+    if (ws_bytes < need) return PPLHIP_INVALID_VALUE;
+    char* base = (char*)ws + pre;
+    hipStream_t s = (hipStream_t)stream;
+    // (pageable sources: each copy has left the host buffer when the call returns)
+    hipError_t e = hipMemcpyAsync(base, tab, tab_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + tab_bytes, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_lora(s, (const LoraTile*)(base + tab_bytes), (int)tiles.size(), (const LoraSlot*)base, (const uint16_t*)x, ldx, (uint16_t*)y, ldy, N, K,
+                        (uint16_t*)(base + tab_bytes + tile_bytes));
+    return op_rc(e);
 }
 
 int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out) {

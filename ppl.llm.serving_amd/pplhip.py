@@ -21,7 +21,7 @@ _LIB = None
 STATUS = {0: "SUCCESS", -1: "OTHER_ERROR", -2: "INVALID_VALUE", -3: "OUT_OF_MEMORY", -4: "DEVICE_RUNTIME_ERROR",
           -5: "DEVICE_MEMORY_ERROR", -6: "NOT_FOUND", -7: "UNSUPPORTED"}
 
-PROF_ATTN_DECODE, PROF_ATTN_PREFILL, PROF_GEMM, PROF_RUN = 0, 1, 2, 3
+PROF_ATTN_DECODE, PROF_ATTN_PREFILL, PROF_GEMM, PROF_RUN, PROF_LORA = 0, 1, 2, 3, 4
 
 
 class PplHipError(RuntimeError):
@@ -101,7 +101,7 @@ class PlanSettings(C.Structure):
 
 class StepShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_tokens", C.c_int64), ("decoding_batches", C.c_int64), ("max_kv_len", C.c_int64),
-                ("seq_starts", C.c_void_p), ("capturing", C.c_int32), ("dump", C.c_int32)]
+                ("seq_starts", C.c_void_p), ("capturing", C.c_int32), ("dump", C.c_int32), ("lora", C.c_int32)]
 
 
 class StepPlan(C.Structure):
@@ -115,7 +115,9 @@ SYMBOLS = [
     "pplhip_comm_export", "pplhip_comm_connect", "pplhip_comm_mode", "pplhip_comm_fused_norm", "pplhip_comm_info", "pplhip_comm_allreduce_us",
     "pplhip_last_error", "pplhip_rank_load", "pplhip_rank_set_tensor", "pplhip_rank_init_synthetic", "pplhip_rank_tie_output",
     "pplhip_kv_block_bytes", "pplhip_kv_capacity", "pplhip_kv_alloc", "pplhip_kv_ptrs", "pplhip_kv_read",
-    "pplhip_kv_write", "pplhip_kv_fill_synthetic", "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
+    "pplhip_kv_write", "pplhip_kv_fill_synthetic",
+    "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
+    "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
     "pplhip_sample", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
@@ -159,6 +161,14 @@ def lib():
         L.pplhip_kv_write.argtypes = [vp, C.c_int, C.c_int, u64, vp, u64]
         L.pplhip_kv_fill_synthetic.argtypes = [vp, C.c_int, u64]
         L.pplhip_set_inputs.argtypes = [vp, C.c_int, C.POINTER(Step)]
+        # (as pplhip_op_step_plan: PPLHIP_LIB may name a build from before multi-LoRA)
+        if hasattr(L, "pplhip_lora_commit"):
+            L.pplhip_lora_set_tensor.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, vp, u64, i32]
+            L.pplhip_lora_commit.argtypes = [vp, C.c_int, C.c_int, f32]
+            L.pplhip_lora_load.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
+            L.pplhip_lora_unload.argtypes = [vp, C.c_int, C.c_int]
+            L.pplhip_set_adapters.argtypes = [vp, C.c_int, vp, i64]
+            L.pplhip_op_lora.argtypes = [vp, vp, i64, vp, i64, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp, u64]
         L.pplhip_run.argtypes = [vp, C.c_int, C.c_int]
         L.pplhip_debug_run_dump.argtypes = [vp, C.c_int, vp]
         L.pplhip_logits.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(i64)]
@@ -205,12 +215,12 @@ def linear_route(x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws=None, ws_b
     return rc, buf.value.decode()
 
 
-def step_plan(settings, batch, num_tokens, decoding_batches, seq_starts=None, max_kv_len=0, capturing=False, dump=False):
+def step_plan(settings, batch, num_tokens, decoding_batches, seq_starts=None, max_kv_len=0, capturing=False, dump=False, lora=False):
     """pplhip_op_step_plan (no device): the plan of a step as a dict.  settings: PlanSettings field -> value (the rest 0);
     seq_starts: the host copy, None when the rank holds none."""
     st = PlanSettings(**settings)
     ss = None if seq_starts is None else np.ascontiguousarray(seq_starts, dtype=np.int64)
-    sh = StepShape(batch, num_tokens, decoding_batches, max_kv_len, None if ss is None else ss.ctypes.data, int(capturing), int(dump))
+    sh = StepShape(batch, num_tokens, decoding_batches, max_kv_len, None if ss is None else ss.ctypes.data, int(capturing), int(dump), int(lora))
     out = StepPlan()
     rc = lib().pplhip_op_step_plan(C.byref(st), C.byref(sh), C.byref(out))
     if rc:
@@ -218,6 +228,34 @@ def step_plan(settings, batch, num_tokens, decoding_batches, seq_starts=None, ma
     return {"schedule": out.schedule, "chunks": [tuple(getattr(out.chunk[i], n) for n in ("b0", "bn", "t0", "tn", "nd")) for i in range(out.num_chunks)],
             "decode_split": [out.decode_split[i] for i in range(out.num_chunks)], "fuse_norm": bool(out.fuse_norm),
             "defer_reduce": bool(out.defer_reduce), "defer_qkv": bool(out.defer_qkv), "lane1_ws_off": out.lane1_ws_off}
+
+
+LORA_MAX_SLOTS, LORA_MAX_RANK = 64, 128
+LORA_TARGETS = ("attention.wqkv", "attention.wo", "feed_forward.w2")
+
+
+def lora_ws_bytes(T, n_slots=LORA_MAX_SLOTS):
+    """a workspace size that always suffices for pplhip_op_lora (include/pplhip.h)"""
+    return 8192 + (T // 16 + n_slots + 1) * 4352
+
+
+def op_lora(x, ldx, y, ldy, T, N, K, row_slots, A, B, ranks, scales, ws, ws_bytes, stream=None):
+    """pplhip_op_lora -> status.  x, y, ws and the entries of A / B are device addresses (integers, None for a slot that is not loaded);
+    row_slots [T], ranks and scales [len(A)] are host arrays.  The refusals are decided before any device call."""
+    n = len(A)
+    rs = np.ascontiguousarray(row_slots, dtype=np.int32)
+    pa = (C.c_void_p * max(n, 1))(*[a or None for a in A])
+    pb = (C.c_void_p * max(n, 1))(*[b or None for b in B])
+    rk = np.ascontiguousarray(ranks, dtype=np.int32)
+    sc = np.ascontiguousarray(scales, dtype=np.float32)
+    return lib().pplhip_op_lora(stream, x, ldx, y, ldy, T, N, K, rs.ctypes.data, n, pa, pb, rk.ctypes.data, sc.ctypes.data, ws, ws_bytes)
+
+
+def write_lora_container(path, tensors, scale):
+    """lora.pplhip: the weight container with the adapter's factors ({name: fp16 array}) and lora.scale (fp32 [1])"""
+    t = {k: np.ascontiguousarray(v, dtype=np.float16) for k, v in tensors.items()}
+    t["lora.scale"] = np.array([scale], dtype=np.float32)
+    write_container(path, t)
 
 
 def make_desc(**kw):
@@ -383,6 +421,34 @@ class Context:
     # step
     def set_inputs(self, rank, step):
         self._ck(lib().pplhip_set_inputs(self.h, rank, C.byref(step)), rank, "set_inputs")
+
+    # multi-LoRA
+    def lora_set_tensor(self, rank, slot, name, arr, r=None):
+        """one factor: lora_a [r, K] or lora_b [N, r] (fp16)"""
+        arr = np.ascontiguousarray(arr, dtype=np.float16)
+        if r is None:
+            r = arr.shape[1] if name.endswith("lora_b") else arr.shape[0]
+        self._ck(lib().pplhip_lora_set_tensor(self.h, rank, slot, name.encode(), arr.ctypes.data, arr.nbytes, r), rank, f"lora_set_tensor({name})")
+
+    def lora_commit(self, rank, slot, scale):
+        self._ck(lib().pplhip_lora_commit(self.h, rank, slot, scale), rank, "lora_commit")
+
+    def lora_set(self, rank, slot, tensors, scale):
+        """every factor of {name: array}, then commit"""
+        for name, arr in tensors.items():
+            self.lora_set_tensor(rank, slot, name, arr)
+        self.lora_commit(rank, slot, scale)
+
+    def lora_load(self, rank, slot, adapter_dir):
+        self._ck(lib().pplhip_lora_load(self.h, rank, slot, adapter_dir.encode()), rank, "lora_load")
+
+    def lora_unload(self, rank, slot):
+        self._ck(lib().pplhip_lora_unload(self.h, rank, slot), rank, "lora_unload")
+
+    def set_adapters(self, rank, slots):
+        """after set_inputs, before run: the adapter slot of every request of the step (-1: none)"""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        self._ck(lib().pplhip_set_adapters(self.h, rank, s.ctypes.data, len(s)), rank, "set_adapters")
 
     def run(self, rank, cache_prefill=0):
         self._ck(lib().pplhip_run(self.h, rank, cache_prefill), rank, "run")

@@ -26,7 +26,10 @@ RetCode HipRuntime::SetInputs(const StepInputs& in) {
     st.start_pos = in.start_pos;
     st.cache_indices = in.cache_indices;
     st.req_list_changed = in.req_list_changed ? 1 : 0;
-    return FromPplHipStatus(pplhip_set_inputs(ctx_, rank_, &st));
+    const int rc = pplhip_set_inputs(ctx_, rank_, &st);
+    // (pplhip_set_inputs cleared the previous step's assignment: a step without adapters is the step it always was)
+    if (rc || !in.lora_slots) return FromPplHipStatus(rc);
+    return FromPplHipStatus(pplhip_set_adapters(ctx_, rank_, in.lora_slots, in.batch));
 }
 
 RetCode HipRuntime::Run(bool is_prefix_cache_hit) {
@@ -221,7 +224,46 @@ RetCode HipResourceManager::Init(const ModelConfig& mc, const ResourceConfig& rc
     return post_processor->InitPostProcessorMem(rc.max_running_batch, mc.vocab_size, rc.enable_penalty);
 }
 
+static RetCode LoadAdapterRank(uint32_t id, pplhip_ctx* ctx, int slot, const std::string& dir) {
+    const int st = pplhip_lora_load(ctx, (int)id, slot, dir.c_str());
+    if (st) LOG(ERROR) << "load adapter [" << dir << "] into slot [" << slot << "] on rank [" << id << "] failed: " << pplhip_last_error(ctx, (int)id);
+    return FromPplHipStatus(st);
+}
+
+static RetCode UnloadAdapterRank(uint32_t id, pplhip_ctx* ctx, int slot) {
+    return FromPplHipStatus(pplhip_lora_unload(ctx, (int)id, slot));
+}
+
+RetCode HipResourceManager::LoadAdapter(int slot, const std::string& dir) {
+    if (!ctx || slot < 0 || slot >= AdapterRegistry::kMaxSlots) return RC_INVALID_VALUE;
+    std::lock_guard<std::mutex> device(adapters.DeviceMutex());   // (check, load and publish are one critical section: two loads of a slot do not race)
+    if (adapters.IsLoaded(slot)) {
+        LOG(ERROR) << "adapter slot [" << slot << "] is in use: unload it first";
+        return RC_INVALID_VALUE;
+    }
+    const RetCode rc = utils::ParallelExecute(LoadAdapterRank, &device_worker_pool_, ctx, slot, dir);
+    if (rc != RC_SUCCESS) {
+        utils::ParallelExecute(UnloadAdapterRank, &device_worker_pool_, ctx, slot);   // (ranks that did load it)
+        return rc;
+    }
+    adapters.Publish(slot);
+    return RC_SUCCESS;
+}
+
+RetCode HipResourceManager::UnloadAdapter(int slot) {
+    if (!ctx) return RC_INVALID_VALUE;
+    const int r = adapters.Retire(slot);
+    if (r < 0) return RC_NOT_FOUND;
+    if (r == 0) {
+        LOG(ERROR) << "adapter slot [" << slot << "] is named by a pending or running request";
+        return RC_INVALID_VALUE;
+    }
+    std::lock_guard<std::mutex> device(adapters.DeviceMutex());
+    return utils::ParallelExecute(UnloadAdapterRank, &device_worker_pool_, ctx, slot);
+}
+
 void HipResourceManager::FillResource(Resource* resource) {
+    resource->adapters = &adapters;
     resource->tensor_parallel_size = tensor_parallel_size;
     resource->kv_cache_max_tokens = kv_cache_max_tokens;
     resource->items = items;

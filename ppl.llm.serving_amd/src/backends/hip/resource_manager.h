@@ -52,6 +52,10 @@ struct HipResourceManager final {
     ppl::common::RetCode Init(const ModelConfig& model_config, const ResourceConfig& resource_config);
     // fills a Resource the way tools/offline_inference.cc:367-373 does
     void FillResource(Resource* resource);
+    // LoRA adapters (include/pplhip.h "multi-LoRA"): loads `<dir>/lora.pplhip` into `slot` on every rank's worker and gives the slot a
+    // fresh uid; unloads a slot unless a pending or running request names it (RC_INVALID_VALUE).  Callable while the generator runs.
+    ppl::common::RetCode LoadAdapter(int slot, const std::string& dir);
+    ppl::common::RetCode UnloadAdapter(int slot);
 
     ppl::common::StaticThreadPool device_worker_pool_;
     std::vector<ResourceItem> items;
@@ -60,6 +64,7 @@ struct HipResourceManager final {
     uint64_t kv_cache_max_tokens = 0;
     uint32_t tensor_parallel_size = 0;
     pplhip_ctx* ctx = nullptr;
+    AdapterRegistry adapters;
 };
 
 }}}  // namespace ppl::llm::hip

@@ -145,7 +145,19 @@ int pplsrv_create(const pplsrv_config* cfg, pplsrv** out) {
     return 0;
 }
 
-int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n) {
+int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n) { return pplsrv_submit_lora(s, reqs, nullptr, n); }
+
+int pplsrv_load_adapter(pplsrv* s, int32_t slot, const char* dir) {
+    if (!s || !dir) return -(int)ppl::common::RC_INVALID_VALUE;
+    return -(int)s->resource_manager.LoadAdapter(slot, dir);
+}
+
+int pplsrv_unload_adapter(pplsrv* s, int32_t slot) {
+    if (!s) return -(int)ppl::common::RC_INVALID_VALUE;
+    return -(int)s->resource_manager.UnloadAdapter(slot);
+}
+
+int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -159,6 +171,7 @@ int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n) {
         r->frequency_penalty = q.frequency_penalty;
         r->generation_length = q.generation_length;
         r->early_stopping = q.early_stopping != 0;
+        r->lora_slot = slots ? slots[i] : -1;
         if (!q.tokens && q.prompt) {
             // text request (grpc_server.cc:218-252): LLMGenerator::Process tokenises it and adds the EOS id to its stop tokens
             if (!s->resource.tokenizer) {

@@ -68,6 +68,14 @@ typedef struct pplsrv_response {
 
 PPLSRV_API int pplsrv_create(const pplsrv_config* cfg, pplsrv** out);      /* 0 on success, a negated RetCode otherwise */
 PPLSRV_API int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n);
+/* LoRA adapters (include/pplhip.h "multi-LoRA"; pplsrv_request keeps its layout, so a request's adapter travels beside it).
+ * pplsrv_load_adapter reads <dir>/lora.pplhip into slot 0 .. 63 on every rank; pplsrv_unload_adapter refuses a slot that a pending or
+ * running request names; pplsrv_submit_lora is pplsrv_submit with slots[i] the adapter of reqs[i] (-1 = none; slots NULL = none at all).
+ * A request that names a slot nothing is loaded in fails (PPLSRV_FAILED).  K/V pages computed under an adapter are shared through the
+ * prefix cache only among requests on the same load of that adapter. */
+PPLSRV_API int pplsrv_load_adapter(pplsrv* s, int32_t slot, const char* dir);
+PPLSRV_API int pplsrv_unload_adapter(pplsrv* s, int32_t slot);
+PPLSRV_API int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, int32_t n);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

@@ -29,6 +29,7 @@ struct Request final {
     bool is_token_in_out = false;
     std::shared_ptr<std::vector<int>> token_ids;
     std::shared_ptr<std::unordered_set<int>> stop_tokens;
+    int32_t lora_slot = -1;  // LoRA adapter slot of this request (HipResourceManager::LoadAdapter), -1 = the base model
 };
 
 enum class FinishFlag { NOT_FINISHED, LENGTH, EOS_TOKEN, STOP_SEQUENCE };

@@ -8,6 +8,7 @@
 
 #include <vector>
 
+#include "adapter_registry.h"
 #include "ppl/common/retcode.h"
 #include "ppl/common/threadpool.h"
 
@@ -41,6 +42,7 @@ struct StepInputs {
     const int64_t* start_pos = nullptr;
     const int64_t* cache_indices = nullptr;  // mode 0: [B]; mode 1: [B, max_pages], only read when req_list_changed
     bool req_list_changed = true;
+    const int32_t* lora_slots = nullptr;     // [B] adapter slot per request, -1 = none; NULL when no request of the step has one
 };
 
 // the runtime handle of one tensor-parallel rank (ppl::nn::Runtime + its bound tensors in the reference)
@@ -72,6 +74,7 @@ struct Resource final {
     PostProcessor* post_processor = nullptr;
     ppl::common::StaticThreadPool* device_worker_pool_ = nullptr;
     const Tokenizer* tokenizer = nullptr;
+    AdapterRegistry* adapters = nullptr;     // LoRA adapter slots of the backend; NULL: the backend serves none
 };
 
 }}  // namespace ppl::llm

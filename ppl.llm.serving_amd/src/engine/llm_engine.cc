@@ -1,5 +1,7 @@
 #include "llm_engine.h"
 
+#include <mutex>
+
 #include "../utils/utils.h"
 #include "ppl/common/log.h"
 
@@ -12,6 +14,7 @@ LLMEngine::LLMEngine(const Resource& resource, const ModelConfig& model_config, 
     , device_worker_pool_(resource.device_worker_pool_)
     , kv_cache_max_tokens_(resource.kv_cache_max_tokens)
     , post_processor_(resource.post_processor)
+    , adapters_(resource.adapters)
     , model_config_(model_config)
     , enable_penalty_(enable_penalty)
     , top_k_(top_k)
@@ -69,6 +72,11 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
     // (src/engine/llm_engine.cc:63-71)
     step.cache_indices = model_config_.cache_mode == 0 ? in.cache_indices.data() : in.page_list.data();
     step.req_list_changed = req_list_changed;
+    for (int32_t s : in.lora_slots)
+        if (s >= 0) step.lora_slots = in.lora_slots.data();
+    // (a backend with adapters loads and unloads them on the same device workers: one or the other)
+    std::unique_lock<std::mutex> device_lock;
+    if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
 
     {
         utils::TimingGuard timing(&step_counter_->current.set_input_cost);

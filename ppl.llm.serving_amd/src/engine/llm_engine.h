@@ -33,6 +33,7 @@ struct ModelInput {
     std::vector<float> presence_penalty_list;
     std::vector<float> frequency_penalty_list;
     std::vector<int64_t> batch_slots;
+    std::vector<int32_t> lora_slots;  // adapter slot per request (Request::lora_slot), -1 = none
 };
 
 struct ModelOutput {
@@ -62,6 +63,7 @@ private:
     std::vector<Runtime*> runtimes_;
     uint64_t kv_cache_max_tokens_;
     PostProcessor* post_processor_;
+    AdapterRegistry* adapters_;
     ModelConfig model_config_;
     bool enable_penalty_;
     int32_t top_k_;

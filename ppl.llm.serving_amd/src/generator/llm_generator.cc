@@ -42,6 +42,7 @@ struct LLMGenerator::Admission {
 LLMGenerator::LLMGenerator(const Resource& resource, const GeneratorConfig& generator_config, const ModelConfig& model_config,
                            Connection* conn)
     : tokenizer_(resource.tokenizer)
+    , adapters_(resource.adapters)
     , generator_config_(generator_config)
     , model_config_(model_config)
     , conn_(conn)
@@ -130,8 +131,14 @@ void LLMGenerator::Process(const std::shared_ptr<Request>& req) {
     ++worker_profiler_->req_counter.encode_cnt;
     worker_profiler_->req_counter.encode_cost += encode_cost;
 
+    uint64_t lora_uid = 0;
+    if (req->lora_slot != -1 && !(adapters_ && adapters_->Acquire(req->lora_slot, &lora_uid))) {
+        conn_->NotifyFailure(req->id, RC_INVALID_VALUE, "adapter slot [" + std::to_string(req->lora_slot) + "] is not loaded");
+        return;
+    }
     auto* lreq = new LlmRequest();
     lreq->orig = req;
+    lreq->lora_uid = lora_uid;
     lreq->enqueue_ts = std::chrono::high_resolution_clock::now();
     if (sched_.PushRequest(lreq)) req_signal_.NotifyOne();
 }
@@ -210,7 +217,8 @@ bool LLMGenerator::ReserveKv(const LlmRequest& req, Admission* adm, int32_t* coo
         const std::vector<int>& tokens = *req.orig->token_ids;
         const int64_t P = model_config_.page_size;
         // 1. longest chain of cached full pages: h_i = HashCombine(h_{i-1}, page i tokens)
-        uint64_t prev_hash = 0, start = 0;
+        // (the chain of a request on an adapter starts from the adapter's uid: its K/V are not the base model's, nor another adapter's)
+        uint64_t prev_hash = req.lora_uid, start = 0;
         for (; start + P <= tokens.size(); start += P) {
             const uint64_t h = utils::HashCombine(prev_hash, tokens.data() + start, (int32_t)P);
             const int64_t page_id = prefix_cache_mgr_.Find(h);
@@ -296,11 +304,13 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     const Request& r = *req.orig;
     if (adm.rest_iters <= 0 || adm.first_fill_len == -1) {
         conn_->NotifyFailure(r.id, RC_INVALID_VALUE, adm.errmsg);
+        if (adapters_) adapters_->Release(r.lora_slot);
         return true;
     }
     const int mode = model_config_.cache_mode;
     if ((mode == 0 && adm.cache_index == INT64_MAX) || (mode == 1 && adm.page_list.empty())) {
         LOG(ERROR) << "catch invalid cache_index or page list";
+        if (adapters_) adapters_->Release(r.lora_slot);
         return false;
     }
     TidData& t = tid_data_map_.emplace(r.id, TidData()).first->second;
@@ -317,6 +327,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     t.stop_tokens = r.stop_tokens;
     t.is_token_in_out = r.is_token_in_out;
     t.slot_index = adm.slot_index;
+    t.lora_slot = r.lora_slot;
     if (mode == 0) {
         t.cache_index = (uint64_t)adm.cache_index;
     } else {
@@ -345,6 +356,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     in->presence_penalty_list.push_back(t.presence_penalty);
     in->frequency_penalty_list.push_back(t.frequency_penalty);
     in->batch_slots.push_back(t.slot_index);
+    in->lora_slots.push_back(t.lora_slot);
     if (mode == 0) in->cache_indices.push_back(adm.cache_index);
     else in->max_pages = std::max<int64_t>((int64_t)t.page_list.size(), in->max_pages);
     return true;
@@ -394,6 +406,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
         in->presence_penalty_list[keep] = in->presence_penalty_list[i];
         in->frequency_penalty_list[keep] = in->frequency_penalty_list[i];
         in->batch_slots[keep] = in->batch_slots[i];
+        in->lora_slots[keep] = in->lora_slots[i];
         ++keep;
     }
     tid_list_.resize(keep);
@@ -406,6 +419,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
     in->presence_penalty_list.resize(keep);
     in->frequency_penalty_list.resize(keep);
     in->batch_slots.resize(keep);
+    in->lora_slots.resize(keep);
     LOG(DEBUG) << "Rest tasks: " << keep;
 }
 
@@ -436,6 +450,7 @@ void LLMGenerator::DeleteTasks(ModelInput* in) {
             page_mgr_.Free(t.page_list.data(), (int64_t)t.page_list.size());
         }
         if (generator_config_.enable_penalty) batch_slots_mgr_.Free((uint64_t)in->batch_slots[row], 1);
+        if (adapters_) adapters_->Release(t.lora_slot);
         // (the reference adds to a by-value pointer here and so counts nothing -- SURVEY.md Q2; counted properly)
         worker_profiler_->req_counter.output_tokens_per_req += (uint64_t)t.gen_tokens_cnt;
         tid_data_map_.erase(it);
@@ -450,6 +465,7 @@ void LLMGenerator::ReleaseResource() {
         if (model_config_.cache_mode == 0) idx_mgr_.Free(t->cache_index, (uint64_t)t->total_len - 1);
         else page_mgr_.Free(t->page_list.data(), (int64_t)t->page_list.size());
         if (generator_config_.enable_penalty) batch_slots_mgr_.Free((uint64_t)t->slot_index, 1);
+        if (adapters_) adapters_->Release(t->lora_slot);
     }
     prefix_cache_mgr_.Reset();
     tid_list_.clear();

@@ -67,11 +67,13 @@ struct TidData final {
     int32_t gen_tokens_cnt = 0;
     std::vector<uint64_t> hash_list;  // hashes of this request's full prompt pages (cached + newly inserted)
     int64_t cache_hit_count = 0;
+    int32_t lora_slot = -1;  // holds a reference in the adapter registry until the request leaves
 };
 
 struct LlmRequest final : public ppl::common::MPSCQueue::Node {
     std::shared_ptr<Request> orig;
     std::chrono::time_point<std::chrono::high_resolution_clock> enqueue_ts;
+    uint64_t lora_uid = 0;  // uid of the adapter in orig->lora_slot when the request was queued (0: none): seed of its page-hash chain
 };
 
 // test hook: receives every ModelInput right before Execute
@@ -110,6 +112,7 @@ private:
 
 private:
     const Tokenizer* tokenizer_;
+    AdapterRegistry* adapters_;
     GeneratorConfig generator_config_;
     ModelConfig model_config_;
     Connection* conn_;

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <iostream>
 #include <random>
+#include <sstream>
 #include <thread>
 
 #include "tool_common.h"
@@ -29,6 +30,8 @@ int main(int argc, char** argv) {
     a.Def("--max-seq-len", "1024", "samples1024: prompt + answer length cap (seqlen of the benchmark config)");
     a.Def("--request-rate", "0", "samples1024: Poisson arrivals at this many requests per second (0: all submitted at once), as "
                                  "client_qps_measure's --request_rate");
+    a.Def("--lora-dirs", "", "LoRA adapters to load: a,b,... (each holds lora.pplhip, tools/export_peft_lora.py); the slot is the position");
+    a.Def("--lora-map", "", "adapter slot of every request, -1 = none: 0,-1,1,... cycled over the requests (needs --lora-dirs)");
     if (!a.Parse(argc, argv)) return -1;
     if (a.Bool("--help")) { a.PrintHelp(); return 0; }
 
@@ -109,6 +112,31 @@ int main(int argc, char** argv) {
     } else {
         std::cerr << "unknown --workload " << workload << "\n";
         return -1;
+    }
+
+    // ---- LoRA adapters: slot = position in --lora-dirs; --lora-map cycled over the requests ---------------------
+    {
+        std::vector<std::string> dirs;
+        std::stringstream ds(a.Str("--lora-dirs"));
+        for (std::string d; std::getline(ds, d, ',');)
+            if (!d.empty()) dirs.push_back(d);
+        for (size_t s = 0; s < dirs.size(); ++s) {
+            st = resource_manager.LoadAdapter((int)s, dirs[s]);
+            if (st != RC_SUCCESS) {
+                std::cerr << "load adapter " << dirs[s] << " failed: " << GetRetCodeStr(st) << "\n";
+                return -1;
+            }
+        }
+        std::vector<int> map;
+        std::stringstream ms(a.Str("--lora-map"));
+        for (std::string v; std::getline(ms, v, ',');)
+            if (!v.empty()) map.push_back(atoi(v.c_str()));
+        for (int s : map)
+            if (s < -1 || s >= (int)dirs.size()) {
+                std::cerr << "--lora-map names slot " << s << ", --lora-dirs loads " << dirs.size() << "\n";
+                return -1;
+            }
+        for (size_t i = 0; i < requests.size() && !map.empty(); ++i) requests[i]->lora_slot = map[i % map.size()];
     }
 
     tools::LocalConnection conn;
