@@ -315,6 +315,25 @@ PPLHIP_API int pplhip_sync(pplhip_ctx* ctx, int rank);
 PPLHIP_API int pplhip_sample(pplhip_ctx* ctx, const float* logits_device, const pplhip_sample_args* args,
                              int32_t* output_host, float* logprob_host);
 
+/* The per-request sampler (DESIGN.md "numerics", per-request sampler row): row b is answered with ITS temperature, top_k, top_p and the
+ * random number u(seeds[b], draws[b]) (Philox4x32-10, made on the device); top_k[b] == 1 is greedy, <= 0 pure top-p, > 1024 clamped.
+ * draws[b] = the number of tokens the request has produced so far.  Every array is staged and uploaded on every call (there is no
+ * req_list_changed rule), one synchronisation like pplhip_sample, no rand(): the two entry points may be mixed.  Acts on local rank 0's
+ * logits at any tensor-parallel degree.  NULL top_k / top_p / seeds / draws or batch outside [0, max_running_batch]:
+ * PPLHIP_INVALID_VALUE before any device call.
+ * Arrived without a version bump (pplhip_version() stays 1.2): a client tells a library that has it by the symbol pplhip_sample_rows
+ * (dlsym). */
+typedef struct pplhip_sample_rows_args {
+    const float* temperatures;   /* host [B] or NULL (NULL when the penalty kernel already divided by them) */
+    const int32_t* top_k;        /* host [B] */
+    const float* top_p;          /* host [B] */
+    const uint64_t* seeds;       /* host [B] */
+    const uint64_t* draws;       /* host [B] */
+    int32_t batch, vocab_size, batch_stride;
+} pplhip_sample_rows_args;
+PPLHIP_API int pplhip_sample_rows(pplhip_ctx* ctx, const float* logits_device, const pplhip_sample_rows_args* args,
+                                  int32_t* output_host, float* logprob_host);
+
 /* in-place penalty on the logits of the last run, using the step's device-resident token_inputs /
  * seq_starts / start_pos (llm_engine.cc:204-216). */
 PPLHIP_API int pplhip_penalty(pplhip_ctx* ctx, float* logits_device, const pplhip_penalty_args* args);
@@ -484,6 +503,16 @@ PPLHIP_API int pplhip_op_penalty(void* stream, float* logits, const float* tempe
 PPLHIP_API int pplhip_op_sample(void* stream, const float* logits, const float* temperatures, const float* top_p, const float* rnd,
                                 int32_t batch, int32_t vocab, int32_t stride, int32_t top_k, float default_top_p, int32_t* out_tok,
                                 float* out_logprob);
+
+/* the per-request sampling kernels alone (csrc/k_sample_rows.hip), for the tests: every pointer is a DEVICE pointer, arrays of `batch`
+ * elements indexed by the batch row.  temperatures may be NULL.  rnd != NULL replaces the generator with the caller's numbers in [0, 1)
+ * (seeds / draws may then be NULL).  The greedy / sampling row list is made on the host from a read-back of top_k, so the call
+ * synchronises `stream` before it launches: one launch for the rows with top_k == 1, one for the others, none for an empty kind. */
+PPLHIP_API int pplhip_op_sample_rows(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
+                                     const uint64_t* seeds, const uint64_t* draws, const float* rnd, int32_t batch, int32_t vocab,
+                                     int32_t stride, int32_t* out_tok, float* out_logprob);
+/* out_u[b] = u(seeds[b], draws[b]), the generator alone (device pointers) */
+PPLHIP_API int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u);
 
 /* description of a KV slab for the attention / cache-write operators */
 typedef struct pplhip_kv_view {

@@ -237,6 +237,15 @@ hipError_t launch_penalty(hipStream_t s, float* logits, const float* temperature
                           const int64_t* token_inputs, const int64_t* seq_starts, const int64_t* start_pos, int batch,
                           int vocab, int stride, int decoding_batches, uint16_t* count_map);
 
+// ---- k_sample_rows.hip: the per-request sampler ---------------------------------------------------
+// rows: device list of batch rows, the n_greedy rows with top_k == 1 first, then the n_sampling others; every other array is indexed by
+// the batch row.  temperatures may be NULL; rnd != NULL replaces u(seeds, draws).  One launch per non-empty kind.
+hipError_t launch_sample_rows(hipStream_t s, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
+                              const uint64_t* seeds, const uint64_t* draws, const float* rnd, const int32_t* rows, int n_greedy,
+                              int n_sampling, int vocab, int stride, int32_t* out_tok, float* out_logprob);
+// out_u[b] = u(seeds[b], draws[b]): Philox4x32-10, word 0, 24 bits
+hipError_t launch_sample_uniform(hipStream_t s, const uint64_t* seeds, const uint64_t* draws, int batch, float* out_u);
+
 // ---- synth.hip --------------------------------------------------------------------------------
 // kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm; and for the fp8 KV
 // slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales; for the int4 KV slab: 7 nibble pairs 1..15, 8 scales of its rule

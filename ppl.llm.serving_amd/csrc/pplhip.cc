@@ -92,6 +92,10 @@ struct Lane {
     Channel* ch = nullptr;
 };
 
+// pplhip_sample_rows stages one step's per-row arrays in one pinned block that goes up in one copy: for capacity cap_B,
+// seeds u64 [cap_B] | draws u64 [cap_B] | temperatures f32 [cap_B] | top_p f32 [cap_B] | top_k i32 [cap_B] | row list i32 [cap_B]
+constexpr int64_t SROWS_BYTES = 8 + 8 + 4 + 4 + 4 + 4;
+
 struct Rank {
     int device = 0;
     int global_rank = 0;
@@ -155,6 +159,7 @@ struct Rank {
     int64_t* d_slots = nullptr;
     float *d_rep = nullptr, *d_pres = nullptr, *d_freq = nullptr, *d_ptemp = nullptr;
     float* h_rand = nullptr;  // pinned
+    char *h_srows = nullptr, *d_srows = nullptr;  // pplhip_sample_rows: pinned staging and its device image, SROWS_BYTES per batch row
 
     // exchange region of the direct collectives (k_comm.hip): fine-grained, peer-mapped; holds the flag words and the buffers
     // the collectives work in place on (part, part2) or push into (logits_gather)
@@ -732,6 +737,7 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.pages_host) hipHostFree(R.pages_host);
         if (R.pages_dev) hipFree(R.pages_dev);
         if (R.h_rand) hipHostFree(R.h_rand);
+        if (R.h_srows) hipHostFree(R.h_srows);
         if (R.stream) hipStreamDestroy(R.stream);
     }
     delete c;
@@ -1025,6 +1031,8 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             ALLOC(R.d_temp, cap_B * 4); ALLOC(R.d_topp, cap_B * 4); ALLOC(R.d_rand, cap_B * 4);
             ALLOC(R.d_lp, cap_B * 4); ALLOC(R.d_tokout, cap_B * 4);
             HIPCK(cp, r, hipHostMalloc((void**)&R.h_rand, cap_B * 4, hipHostMallocDefault));
+            ALLOC(R.d_srows, cap_B * SROWS_BYTES);
+            HIPCK(cp, r, hipHostMalloc((void**)&R.h_srows, cap_B * SROWS_BYTES, hipHostMallocDefault));
             if (opts->enable_penalty) {
                 ALLOC(R.count_map, (uint64_t)cap_B * d.vocab_size * 2);
                 ALLOC(R.d_slots, cap_B * 8);
@@ -2360,6 +2368,54 @@ int pplhip_sample(pplhip_ctx* c, const float* logits_device, const pplhip_sample
     return p2p_check(c, 0);
 }
 
+// greedy rows (top_k == 1) first, then the others, each kind in batch order; returns the number of greedy rows
+static int sample_row_list(const int32_t* top_k, int B, int32_t* rows) {
+    int ng = 0;
+    for (int i = 0; i < B; ++i)
+        if (top_k[i] == 1) rows[ng++] = i;
+    int n = ng;
+    for (int i = 0; i < B; ++i)
+        if (top_k[i] != 1) rows[n++] = i;
+    return ng;
+}
+
+int pplhip_sample_rows(pplhip_ctx* c, const float* logits_device, const pplhip_sample_rows_args* a, int32_t* output_host,
+                       float* logprob_host) {
+    if (!c || !a || !logits_device || !output_host || !logprob_host) return PPLHIP_INVALID_VALUE;
+    if (!a->top_k || !a->top_p || !a->seeds || !a->draws) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    const int B = a->batch;
+    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
+    if (a->vocab_size <= 0 || a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
+    if (B == 0) return 0;
+    // every array, every call, one copy: the block keeps its capacity layout, so the copy is cap_B rows long only when B is
+    const int64_t cap = R.cap_B;
+    char* h = R.h_srows;
+    uint64_t* h_seed = (uint64_t*)h;
+    uint64_t* h_draw = (uint64_t*)(h + 8 * cap);
+    float* h_temp = (float*)(h + 16 * cap);
+    float* h_topp = (float*)(h + 20 * cap);
+    int32_t* h_topk = (int32_t*)(h + 24 * cap);
+    int32_t* h_rows = (int32_t*)(h + 28 * cap);
+    memcpy(h_seed, a->seeds, (size_t)B * 8);
+    memcpy(h_draw, a->draws, (size_t)B * 8);
+    if (a->temperatures) memcpy(h_temp, a->temperatures, (size_t)B * 4);
+    memcpy(h_topp, a->top_p, (size_t)B * 4);
+    memcpy(h_topk, a->top_k, (size_t)B * 4);
+    const int ng = sample_row_list(a->top_k, B, h_rows);
+    HIPCK(c, 0, hipSetDevice(R.device));
+    hipStream_t s = R.stream;
+    HIPCK(c, 0, hipMemcpyAsync(R.d_srows, h, (size_t)(28 * cap + 4 * (int64_t)B), hipMemcpyHostToDevice, s));
+    const char* d = R.d_srows;
+    HIPCK(c, 0, launch_sample_rows(s, logits_device, a->temperatures ? (const float*)(d + 16 * cap) : nullptr, (const int32_t*)(d + 24 * cap),
+                                   (const float*)(d + 20 * cap), (const uint64_t*)d, (const uint64_t*)(d + 8 * cap), nullptr,
+                                   (const int32_t*)(d + 28 * cap), ng, B - ng, a->vocab_size, a->batch_stride, R.d_tokout, R.d_lp));
+    HIPCK(c, 0, hipMemcpyAsync(output_host, R.d_tokout, B * 4, hipMemcpyDeviceToHost, s));
+    HIPCK(c, 0, hipMemcpyAsync(logprob_host, R.d_lp, B * 4, hipMemcpyDeviceToHost, s));
+    HIPCK(c, 0, hipStreamSynchronize(s));  // the one synchronisation, as in pplhip_sample
+    return p2p_check(c, 0);
+}
+
 int pplhip_penalty(pplhip_ctx* c, float* logits_device, const pplhip_penalty_args* a) {
     if (!c || !a || !logits_device) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[0];
@@ -2592,6 +2648,35 @@ int pplhip_op_sample(void* stream, const float* logits, const float* temperature
     if (!rnd && batch > 0) return PPLHIP_INVALID_VALUE;
     return op_rc(launch_sample_topk_topp((hipStream_t)stream, logits, temperatures, top_p, rnd, batch, vocab, stride, top_k, default_top_p,
                                          nullptr, out_tok, out_logprob));
+}
+
+// the per-request sampler alone.  The row list is made here: top_k is read back, compacted on the host and sent up again into stream-ordered
+// scratch (two synchronisations of `stream` in front of the launches) -- test support, the product entry point has the arrays on the host already
+int pplhip_op_sample_rows(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
+                          const uint64_t* seeds, const uint64_t* draws, const float* rnd, int32_t batch, int32_t vocab, int32_t stride,
+                          int32_t* out_tok, float* out_logprob) {
+    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
+    if (batch == 0) return 0;
+    if (!logits || !top_k || !top_p || !out_tok || !out_logprob || (!rnd && (!seeds || !draws))) return PPLHIP_INVALID_VALUE;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> k(batch), rows(batch);
+    hipError_t e = hipMemcpyAsync(k.data(), top_k, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    const int ng = sample_row_list(k.data(), batch, rows.data());
+    int32_t* d_rows = nullptr;
+    if ((e = hipMallocAsync((void**)&d_rows, (size_t)batch * 4, s)) != hipSuccess) return op_rc(e);
+    e = hipMemcpyAsync(d_rows, rows.data(), (size_t)batch * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call; the stream was idle anyway
+    if (e == hipSuccess)
+        e = launch_sample_rows(s, logits, temperatures, top_k, top_p, seeds, draws, rnd, d_rows, ng, batch - ng, vocab, stride, out_tok, out_logprob);
+    const hipError_t e2 = hipFreeAsync(d_rows, s);
+    return op_rc(e != hipSuccess ? e : e2);
+}
+
+int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u) {
+    if (batch < 0 || (batch > 0 && (!seeds || !draws || !out_u))) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_sample_uniform((hipStream_t)stream, seeds, draws, batch, out_u));
 }
 
 static KvAddr view_addr(const pplhip_kv_view* v) {

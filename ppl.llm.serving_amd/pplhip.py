@@ -62,6 +62,11 @@ class SampleArgs(C.Structure):
                 ("default_top_p", C.c_float), ("req_list_changed", C.c_int32), ("enable_penalty", C.c_int32)]
 
 
+class SampleRowsArgs(C.Structure):
+    _fields_ = [("temperatures", C.c_void_p), ("top_k", C.c_void_p), ("top_p", C.c_void_p), ("seeds", C.c_void_p), ("draws", C.c_void_p),
+                ("batch", C.c_int32), ("vocab_size", C.c_int32), ("batch_stride", C.c_int32)]
+
+
 class PenaltyArgs(C.Structure):
     _fields_ = [("temperatures", C.c_void_p), ("repetition_penalties", C.c_void_p), ("presence_penalties", C.c_void_p),
                 ("frequency_penalties", C.c_void_p), ("batch_slots", C.c_void_p), ("batch", C.c_int32),
@@ -118,10 +123,10 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
-    "pplhip_sample", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
+    "pplhip_sample", "pplhip_sample_rows", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
 ]
 
@@ -200,6 +205,10 @@ def lib():
         L.pplhip_op_silu_mul.argtypes = [vp, vp, i64, i32, vp]
         L.pplhip_op_penalty.argtypes = [vp] * 10 + [i32, i32, i32, i32, vp]
         L.pplhip_op_sample.argtypes = [vp] * 5 + [i32, i32, i32, i32, f32, vp, vp]
+        if hasattr(L, "pplhip_sample_rows"):
+            L.pplhip_sample_rows.argtypes = [vp, vp, C.POINTER(SampleRowsArgs), vp, vp]
+            L.pplhip_op_sample_rows.argtypes = [vp] * 8 + [i32, i32, i32, vp, vp]
+            L.pplhip_op_sample_uniform.argtypes = [vp, vp, vp, i32, vp]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
@@ -488,6 +497,26 @@ class Context:
         if logits_ptr is None:
             logits_ptr = self.logits_ptr(0)[0]
         self._ck(lib().pplhip_sample(self.h, logits_ptr, C.byref(a), tok.ctypes.data, lp.ctypes.data), 0, "sample")
+        return tok, lp
+
+    def sample_rows(self, top_k, top_p, seeds, draws, temperatures=None, logits_ptr=None):
+        """the per-request sampler on the logits of the last run: every argument one value per batch row"""
+        a = SampleRowsArgs()
+        k = np.ascontiguousarray(top_k, dtype=np.int32)
+        p = np.ascontiguousarray(top_p, dtype=np.float32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        dr = np.ascontiguousarray(draws, dtype=np.uint64)
+        t = None if temperatures is None else np.ascontiguousarray(temperatures, dtype=np.float32)
+        batch = len(k)
+        assert len(p) == len(sd) == len(dr) == batch and (t is None or len(t) == batch)
+        a.top_k, a.top_p, a.seeds, a.draws = k.ctypes.data, p.ctypes.data, sd.ctypes.data, dr.ctypes.data
+        a.temperatures = None if t is None else t.ctypes.data
+        a.batch, a.vocab_size, a.batch_stride = batch, self.desc.vocab_size, self.desc.vocab_size
+        tok = np.empty(batch, dtype=np.int32)
+        lp = np.empty(batch, dtype=np.float32)
+        if logits_ptr is None:
+            logits_ptr = self.logits_ptr(0)[0]
+        self._ck(lib().pplhip_sample_rows(self.h, logits_ptr, C.byref(a), tok.ctypes.data, lp.ctypes.data), 0, "sample_rows")
         return tok, lp
 
     def penalty(self, temperatures, repetition, presence, frequency, batch_slots, req_list_changed=True):

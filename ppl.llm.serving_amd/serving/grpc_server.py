@@ -62,6 +62,8 @@ def load_lib():
     L = C.CDLL(LIB_PATH)
     L.pplsrv_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
     L.pplsrv_submit.argtypes = [C.c_void_p, C.POINTER(CRequest), C.c_int32]
+    L.pplsrv_create_ex.argtypes = [C.POINTER(Config), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.pplsrv_submit_ex.argtypes = [C.c_void_p, C.POINTER(CRequest), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int32]
     L.pplsrv_poll.argtypes = [C.c_void_p, C.POINTER(CResponse), C.c_int32, C.c_int32]
     L.pplsrv_poll_text.argtypes = [C.c_void_p, C.POINTER(CResponse), C.c_int32, C.c_int32, C.c_char_p, C.c_int64]
     L.pplsrv_cancel.argtypes = [C.c_void_p, C.c_uint64]
@@ -141,6 +143,7 @@ class Serving:
             return
         q = asyncio.Queue()
         creqs = (CRequest * n)()
+        seeds = (C.c_uint64 * n)()             # choosing_parameters.seed beside the request (0: none); used with --per-request-sampling
         keep = []
         failed = []
         with self.lock:
@@ -155,6 +158,7 @@ class Serving:
             kw = parse_request(pb)
             c = creqs[len(mapped)]
             c.id = base + i
+            seeds[len(mapped)] = pb.choosing_parameters.seed if pb.choosing_parameters.do_sample else 0
             if text:
                 raw = pb.prompt.encode("utf-8")
                 keep.append(raw)
@@ -171,7 +175,7 @@ class Serving:
             for mid, orig, text in mapped:
                 self.routes[mid] = (q, orig, text)
         if mapped:
-            rc = self.lib.pplsrv_submit(self.h, creqs, len(mapped))
+            rc = self.lib.pplsrv_submit_ex(self.h, creqs, None, seeds, len(mapped))
             if rc != 0:
                 failed += [orig for _, orig, _ in mapped]
                 with self.lock:
@@ -269,6 +273,11 @@ def add_flags(ap):
     ap.add_argument("--synthetic-weights", action="store_true")
     ap.add_argument("--synthetic-seed", type=int, default=1234)
     ap.add_argument("--kv-cache-max-tokens", type=int, default=0)
+    ap.add_argument("--per-request-sampling", action="store_true",
+                    help="every request sampled with its own top_k / top_p / temperature and choosing_parameters.seed (off: as the reference, "
+                         "the first row's top_k for the batch and an unseeded rand())")
+    ap.add_argument("--sampling-seed", type=int, default=0,
+                    help="with --per-request-sampling: the n-th request without a seed gets splitmix64(this + n); 0: from std::random_device")
     ap.add_argument("--host", default="127.0.0.1")            # tools/llm_server.cc:84-85
     ap.add_argument("--port", type=int, default=10086)
 
@@ -276,9 +285,9 @@ def add_flags(ap):
 async def serve(a, ready=None):
     lib = load_lib()
     h = C.c_void_p()
-    rc = lib.pplsrv_create(C.byref(make_config(a)), C.byref(h))
+    rc = lib.pplsrv_create_ex(C.byref(make_config(a)), int(a.per_request_sampling), a.sampling_seed, C.byref(h))
     if rc != 0:
-        raise RuntimeError(f"pplsrv_create failed: RetCode {-rc}")
+        raise RuntimeError(f"pplsrv_create_ex failed: RetCode {-rc}")
     srv = Serving(lib, h, bool(a.tokenizer_path))
     srv.start(asyncio.get_running_loop())
     server = grpc.aio.server(options=[("grpc.max_receive_message_length", 64 << 20), ("grpc.max_send_message_length", 64 << 20)])

@@ -69,6 +69,25 @@ RetCode HipPostProcessor::SampleTopKTopP(const float* logits_device, const float
     return FromPplHipStatus(st);
 }
 
+RetCode HipPostProcessor::SampleRows(const float* logits_device, const float* temperatures_host, const int32_t* top_k_host,
+                                     const float* top_p_host, const uint64_t* seeds_host, const uint64_t* draws_host, int32_t batch,
+                                     int32_t vocab_size, int32_t batch_stride, int32_t* output_host, float* logprob_host) {
+    if (batch == 0) return RC_SUCCESS;
+    pplhip_sample_rows_args a;
+    memset(&a, 0, sizeof(a));
+    a.temperatures = temperatures_host;
+    a.top_k = top_k_host;
+    a.top_p = top_p_host;
+    a.seeds = seeds_host;
+    a.draws = draws_host;
+    a.batch = batch;
+    a.vocab_size = vocab_size;
+    a.batch_stride = batch_stride;
+    const int st = pplhip_sample_rows(ctx_, logits_device, &a, output_host, logprob_host);
+    if (st) LOG(ERROR) << "per-request sampling failed: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
 RetCode HipPostProcessor::ApplyPenalty(const float* temperatures_host, const float* repetition_penalties_host,
                                        const float* presence_penalties_host, const float* frequency_penalties_host,
                                        const int64_t* batch_slots_host, const int64_t*, const int64_t*, const int64_t*,

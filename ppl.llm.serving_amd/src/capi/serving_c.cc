@@ -93,7 +93,9 @@ struct pplsrv {
 
 extern "C" {
 
-int pplsrv_create(const pplsrv_config* cfg, pplsrv** out) {
+int pplsrv_create(const pplsrv_config* cfg, pplsrv** out) { return pplsrv_create_ex(cfg, 0, 0, out); }
+
+int pplsrv_create_ex(const pplsrv_config* cfg, int32_t per_request_sampling, uint64_t sampling_seed, pplsrv** out) {
     if (!cfg || !out || !cfg->model_param_path) return -(int)ppl::common::RC_INVALID_VALUE;
     ResourceConfig rc;
     GeneratorConfig gc;
@@ -116,6 +118,8 @@ int pplsrv_create(const pplsrv_config* cfg, pplsrv** out) {
     gc.top_p = cfg->top_p;
     gc.top_k = cfg->top_k > 0 ? cfg->top_k : 1;
     gc.enable_penalty = rc.enable_penalty;
+    gc.per_request_sampling = per_request_sampling != 0;
+    gc.sampling_seed = sampling_seed;
     gc.max_running_batch = rc.max_running_batch;
     gc.max_tokens_per_step = rc.max_tokens_per_step;
     gc.max_input_tokens_per_request = cfg->max_input_tokens_per_request > 0 ? cfg->max_input_tokens_per_request : 4096;
@@ -158,6 +162,10 @@ int pplsrv_unload_adapter(pplsrv* s, int32_t slot) {
 }
 
 int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, int32_t n) {
+    return pplsrv_submit_ex(s, reqs, slots, nullptr, n);
+}
+
+int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -172,6 +180,7 @@ int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slo
         r->generation_length = q.generation_length;
         r->early_stopping = q.early_stopping != 0;
         r->lora_slot = slots ? slots[i] : -1;
+        r->seed = seeds ? seeds[i] : 0;
         if (!q.tokens && q.prompt) {
             // text request (grpc_server.cc:218-252): LLMGenerator::Process tokenises it and adds the EOS id to its stop tokens
             if (!s->resource.tokenizer) {

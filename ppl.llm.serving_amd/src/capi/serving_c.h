@@ -76,6 +76,13 @@ PPLSRV_API int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n);
 PPLSRV_API int pplsrv_load_adapter(pplsrv* s, int32_t slot, const char* dir);
 PPLSRV_API int pplsrv_unload_adapter(pplsrv* s, int32_t slot);
 PPLSRV_API int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, int32_t n);
+/* The per-request sampler (both structs keep their layout, so its switch and a request's seed travel beside them).  pplsrv_create_ex is
+ * pplsrv_create with GeneratorConfig::per_request_sampling and ::sampling_seed (0: a seed from std::random_device); with the switch on
+ * every request is sampled with its own top_k / top_p / temperature and a random sequence of its own.  pplsrv_submit_ex is
+ * pplsrv_submit_lora with seeds[i] the sampling seed of reqs[i] (0 = none: the generator gives it the next one of sampling_seed's
+ * sequence); slots NULL = no adapters, seeds NULL = no seeds. */
+PPLSRV_API int pplsrv_create_ex(const pplsrv_config* cfg, int32_t per_request_sampling, uint64_t sampling_seed, pplsrv** out);
+PPLSRV_API int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, int32_t n);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

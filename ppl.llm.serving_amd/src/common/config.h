@@ -48,6 +48,11 @@ struct GeneratorConfig final {
     float top_p = 0.0f;                          // --top-p
     int32_t top_k = 1;                           // --top-k
     bool enable_penalty = false;                 // --enable-penalty
+    // every request sampled with its own top_k / top_p / temperature and a random number of its own (seed, tokens produced so far);
+    // off: the reference's call (the first row's top_k for the batch, rand()), SURVEY.md Q3
+    bool per_request_sampling = false;           // --per-request-sampling
+    // the n-th request that brings no seed (n from 1) gets splitmix64(sampling_seed + n); 0: drawn from std::random_device at construction
+    uint64_t sampling_seed = 0;                  // --sampling-seed
     // ---- admission limits ----------------------------------------------------------------------------------------
     int32_t max_running_batch = 0;               // --max-running-batch
     int32_t max_input_tokens_per_request = 0;    // --max-input-tokens-per-request  (longer prompts are rejected)

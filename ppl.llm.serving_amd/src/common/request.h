@@ -30,6 +30,7 @@ struct Request final {
     std::shared_ptr<std::vector<int>> token_ids;
     std::shared_ptr<std::unordered_set<int>> stop_tokens;
     int32_t lora_slot = -1;  // LoRA adapter slot of this request (HipResourceManager::LoadAdapter), -1 = the base model
+    uint64_t seed = 0;       // sampling seed (GeneratorConfig::per_request_sampling), 0 = none: the generator gives the request one
 };
 
 enum class FinishFlag { NOT_FINISHED, LENGTH, EOS_TOKEN, STOP_SEQUENCE };

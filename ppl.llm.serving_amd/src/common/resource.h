@@ -29,6 +29,16 @@ public:
                                               const int64_t* batch_slots_host, const int64_t* token_inputs,
                                               const int64_t* seqstarts, const int64_t* start_pos, int32_t batch,
                                               int32_t vocab_size, bool req_list_changed, float* logits) = 0;
+    // The per-request sampler (GeneratorConfig::per_request_sampling): row b is answered with ITS temperature, top_k, top_p and the random
+    // number of (seeds[b], draws[b]); every array is consumed on every call (no req_list_changed).  temperatures_host NULL: the penalty
+    // step already divided by them.  Blocking, like SampleTopKTopP.  batch == 0 touches nothing and only tells whether the backend can do
+    // it (LLMEngine::Init asks so); a backend that cannot keeps this default.
+    virtual ppl::common::RetCode SampleRows(const float* /*logits_device*/, const float* /*temperatures_host*/, const int32_t* /*top_k_host*/,
+                                            const float* /*top_p_host*/, const uint64_t* /*seeds_host*/, const uint64_t* /*draws_host*/,
+                                            int32_t /*batch*/, int32_t /*vocab_size*/, int32_t /*batch_stride*/, int32_t* /*output_host*/,
+                                            float* /*logprob_host*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
 };
 
 // one step of one rank: the 11-input contract of src/engine/llm_engine.h:124-138 (attn_mask is never written by the

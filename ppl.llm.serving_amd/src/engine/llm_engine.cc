@@ -9,7 +9,8 @@ using namespace ppl::common;
 
 namespace ppl { namespace llm {
 
-LLMEngine::LLMEngine(const Resource& resource, const ModelConfig& model_config, bool enable_penalty, int32_t top_k, float top_p)
+LLMEngine::LLMEngine(const Resource& resource, const ModelConfig& model_config, bool enable_penalty, int32_t top_k, float top_p,
+                     bool per_request_sampling)
     : tensor_parallel_size_(resource.tensor_parallel_size)
     , device_worker_pool_(resource.device_worker_pool_)
     , kv_cache_max_tokens_(resource.kv_cache_max_tokens)
@@ -18,7 +19,8 @@ LLMEngine::LLMEngine(const Resource& resource, const ModelConfig& model_config, 
     , model_config_(model_config)
     , enable_penalty_(enable_penalty)
     , top_k_(top_k)
-    , top_p_(top_p) {
+    , top_p_(top_p)
+    , per_request_sampling_(per_request_sampling) {
     for (uint32_t i = 0; i < tensor_parallel_size_; ++i) runtimes_.push_back(resource.items[i].runtime);
 }
 
@@ -36,6 +38,12 @@ RetCode LLMEngine::Init(WorkerPerStepCounter* step_counter) {
             LOG(ERROR) << "resource item without runtime";
             return RC_INVALID_VALUE;
         }
+    }
+    if (per_request_sampling_ &&
+        (!post_processor_ || post_processor_->SampleRows(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, model_config_.vocab_size,
+                                                         model_config_.vocab_size, nullptr, nullptr) != RC_SUCCESS)) {
+        LOG(ERROR) << "per_request_sampling is on, but the backend's post processor has no per-request sampler (SampleRows)";
+        return RC_UNSUPPORTED;
     }
     return RC_SUCCESS;
 }
@@ -116,14 +124,21 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
                 return RC_OTHER_ERROR;
             }
         }
-        // only top_k_list[0] reaches the kernel (src/engine/llm_engine.cc:219)
-        const int32_t default_top_k = in.top_k_list.empty() ? top_k_ : in.top_k_list[0];
-        rc = post_processor_->SampleTopKTopP(logits, in.temperatures.data(), in.top_k_list.data(), in.top_p_list.data(),
-                                             running_batch, model_config_.vocab_size, (int32_t)stride, default_top_k, top_p_,
-                                             req_list_changed, out->output_token.data(), out->logprobs.data(),
-                                             enable_penalty_);
+        if (per_request_sampling_) {
+            // every row its own parameters and random number (the penalty step has applied the temperatures already)
+            rc = post_processor_->SampleRows(logits, enable_penalty_ ? nullptr : in.temperatures.data(), in.top_k_list.data(),
+                                             in.top_p_list.data(), in.seed_list.data(), in.draw_list.data(), running_batch,
+                                             model_config_.vocab_size, (int32_t)stride, out->output_token.data(), out->logprobs.data());
+        } else {
+            // only top_k_list[0] reaches the kernel (src/engine/llm_engine.cc:219)
+            const int32_t default_top_k = in.top_k_list.empty() ? top_k_ : in.top_k_list[0];
+            rc = post_processor_->SampleTopKTopP(logits, in.temperatures.data(), in.top_k_list.data(), in.top_p_list.data(),
+                                                 running_batch, model_config_.vocab_size, (int32_t)stride, default_top_k, top_p_,
+                                                 req_list_changed, out->output_token.data(), out->logprobs.data(),
+                                                 enable_penalty_);
+        }
         if (rc != RC_SUCCESS) {
-            *error_msg = "SampleTopKTopP failed: " + std::string(GetRetCodeStr(rc));
+            *error_msg = std::string(per_request_sampling_ ? "SampleRows" : "SampleTopKTopP") + " failed: " + std::string(GetRetCodeStr(rc));
             LOG(ERROR) << *error_msg;
             return RC_OTHER_ERROR;
         }

@@ -28,6 +28,8 @@ struct ModelInput {
     std::vector<float> temperatures;
     std::vector<float> top_p_list;
     std::vector<int32_t> top_k_list;
+    std::vector<uint64_t> seed_list;  // sampling seed per request (per_request_sampling)
+    std::vector<uint64_t> draw_list;  // tokens the request has produced so far: 0 on the step that ends its prefill
 
     std::vector<float> repetition_penalty_list;
     std::vector<float> presence_penalty_list;
@@ -51,7 +53,8 @@ struct ModelOutput {
 
 class LLMEngine final {
 public:
-    LLMEngine(const Resource& resource, const ModelConfig& model_config, bool enable_penalty, int32_t top_k, float top_p);
+    LLMEngine(const Resource& resource, const ModelConfig& model_config, bool enable_penalty, int32_t top_k, float top_p,
+              bool per_request_sampling = false);
 
     ppl::common::RetCode Init(WorkerPerStepCounter* step_counter);
     ppl::common::RetCode Execute(const ModelInput& model_input, bool req_list_changed, bool is_prefix_cache_hit,
@@ -68,6 +71,7 @@ private:
     bool enable_penalty_;
     int32_t top_k_;
     float top_p_;
+    bool per_request_sampling_;
     WorkerPerStepCounter* step_counter_ = nullptr;
 };
 

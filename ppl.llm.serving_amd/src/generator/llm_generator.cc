@@ -1,5 +1,6 @@
 #include "llm_generator.h"
 
+#include <random>
 #include <math.h>
 #include <string.h>
 
@@ -47,7 +48,12 @@ LLMGenerator::LLMGenerator(const Resource& resource, const GeneratorConfig& gene
     , model_config_(model_config)
     , conn_(conn)
     , kv_cache_max_tokens_(resource.kv_cache_max_tokens)
-    , llm_engine_(resource, model_config, generator_config.enable_penalty, generator_config.top_k, generator_config.top_p) {
+    , llm_engine_(resource, model_config, generator_config.enable_penalty, generator_config.top_k, generator_config.top_p,
+                  generator_config.per_request_sampling) {
+    if (generator_config_.per_request_sampling && generator_config_.sampling_seed == 0) {
+        std::random_device rd;
+        generator_config_.sampling_seed = ((uint64_t)rd() << 32) | rd();
+    }
     idx_mgr_.Init(kv_cache_max_tokens_);
     batch_slots_mgr_.Init(generator_config.max_running_batch);
     page_mgr_.Init(kv_cache_max_tokens_, model_config_.page_size);
@@ -299,6 +305,14 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
     return true;
 }
 
+// seed of a request that brings none: one step of the splitmix64 generator (Vigna) from state x
+static uint64_t SplitMix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // reference ParseRequest, llm_generator.cc:193-261
 bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, ModelInput* in) {
     const Request& r = *req.orig;
@@ -328,6 +342,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     t.is_token_in_out = r.is_token_in_out;
     t.slot_index = adm.slot_index;
     t.lora_slot = r.lora_slot;
+    t.seed = r.seed ? r.seed : SplitMix64(generator_config_.sampling_seed + ++unseeded_requests_);
     if (mode == 0) {
         t.cache_index = (uint64_t)adm.cache_index;
     } else {
@@ -352,6 +367,8 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     in->temperatures.push_back(t.temperature);
     in->top_p_list.push_back(t.top_p);
     in->top_k_list.push_back(t.top_k);
+    in->seed_list.push_back(t.seed);
+    in->draw_list.push_back(0);
     in->repetition_penalty_list.push_back(t.repetition_penalty);
     in->presence_penalty_list.push_back(t.presence_penalty);
     in->frequency_penalty_list.push_back(t.frequency_penalty);
@@ -402,6 +419,8 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
         in->temperatures[keep] = in->temperatures[i];
         in->top_p_list[keep] = in->top_p_list[i];
         in->top_k_list[keep] = in->top_k_list[i];
+        in->seed_list[keep] = in->seed_list[i];
+        in->draw_list[keep] = in->draw_list[i];
         in->repetition_penalty_list[keep] = in->repetition_penalty_list[i];
         in->presence_penalty_list[keep] = in->presence_penalty_list[i];
         in->frequency_penalty_list[keep] = in->frequency_penalty_list[i];
@@ -415,6 +434,8 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
     in->temperatures.resize(keep);
     in->top_p_list.resize(keep);
     in->top_k_list.resize(keep);
+    in->seed_list.resize(keep);
+    in->draw_list.resize(keep);
     in->repetition_penalty_list.resize(keep);
     in->presence_penalty_list.resize(keep);
     in->frequency_penalty_list.resize(keep);
@@ -576,6 +597,7 @@ void LLMGenerator::Generate() {
             for (int row = 0; row < running_batch; ++row) {
                 TidData* t = tid_list_[row];
                 ++t->gen_tokens_cnt;
+                ++in.draw_list[row];
                 const int tok = out.output_token[row];
                 const int64_t fed = (int64_t)t->next_tokens->size();
                 t->next_tokens = std::make_shared<std::vector<int>>(1, tok);

@@ -68,6 +68,7 @@ struct TidData final {
     std::vector<uint64_t> hash_list;  // hashes of this request's full prompt pages (cached + newly inserted)
     int64_t cache_hit_count = 0;
     int32_t lora_slot = -1;  // holds a reference in the adapter registry until the request leaves
+    uint64_t seed = 0;       // sampling seed: the request's own, or the generator's next one
 };
 
 struct LlmRequest final : public ppl::common::MPSCQueue::Node {
@@ -124,6 +125,7 @@ private:
     std::vector<TidData*> tid_list_;
     std::map<uint64_t, TidData> tid_data_map_;
     bool req_list_changed_ = true;
+    uint64_t unseeded_requests_ = 0;  // requests parsed without a seed of their own so far (the n of splitmix64(sampling_seed + n))
     ppl::common::TypedMPSCQueue<FinishedTaskInfo> finished_tasks_;
 
     utils::IndexManager idx_mgr_;

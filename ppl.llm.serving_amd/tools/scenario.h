@@ -4,7 +4,8 @@
 //                  "enable_penalty", "stop_tokens": [..]},
 //    "kv_cache_max_tokens": N,
 //    "requests": [{"id", "tokens": [..], "generation_length", "temperature", "top_p", "top_k", "repetition_penalty",
-//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..]}]}
+//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed"}]}
+// "seed" (this tree's Request only: the sampling seed of --per-request-sampling, 0 or absent = none) is ignored for a request type without it.
 // Templates: Request / GeneratorConfig are this tree's or the reference's types (same member names by construction).
 #pragma once
 #include <fstream>
@@ -41,6 +42,11 @@ void ScenarioGeneratorConfig(const utils::JsonValue& doc, GeneratorConfigT* gc) 
 }
 
 template <typename RequestT>
+auto SetSeed(RequestT* q, uint64_t seed, int) -> decltype(q->seed = seed, void()) { q->seed = seed; }
+template <typename RequestT>
+void SetSeed(RequestT*, uint64_t, long) {}
+
+template <typename RequestT>
 std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& doc, int vocab_size) {
     std::vector<std::shared_ptr<RequestT>> out;
     for (const auto& r : doc.Find("requests")->arr) {
@@ -52,6 +58,7 @@ std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& 
         q->presence_penalty = (float)r.GetNum("presence_penalty", 0.0);
         q->frequency_penalty = (float)r.GetNum("frequency_penalty", 0.0);
         q->early_stopping = r.GetBool("early_stopping", true);
+        SetSeed(q.get(), (uint64_t)r.GetInt("seed", 0), 0);
         q->token_ids = std::make_shared<std::vector<int>>();
         if (const utils::JsonValue* t = r.Find("tokens"))
             for (const auto& v : t->arr) q->token_ids->push_back((int)(v.AsInt() % vocab_size));

@@ -60,6 +60,8 @@ inline void DefineCommonFlags(Args* a) {
     a->Def("--synthetic-decisive-head", "0", "with --synthetic-weights: lm_head row v = embedding row v - N, i.e. token t is answered by t + N with a wide margin (answers of two runs can then be compared token for token); 0: off");
     a->Def("--kv-cache-max-tokens", "0", "pin the KV slab size in tokens (0: max-tokens-scale x free memory)");
     a->Def("--seed", "1234", "workload seed");
+    a->Def("--per-request-sampling", "false", "sample every request with its own top_k / top_p / temperature and its own seeded random sequence (off: the first row's top_k for the whole batch and rand(), as the reference)", true);
+    a->Def("--sampling-seed", "0", "with --per-request-sampling: the n-th request without a seed of its own gets splitmix64(this + n); 0: taken from std::random_device");
 }
 
 inline bool FillConfigs(const Args& a, ppl::llm::ResourceConfig* rc, ppl::llm::GeneratorConfig* gc, ppl::llm::ModelConfig* mc) {
@@ -88,6 +90,8 @@ inline bool FillConfigs(const Args& a, ppl::llm::ResourceConfig* rc, ppl::llm::G
     gc->top_p = (float)a.Num("--top-p");
     gc->top_k = a.Int("--top-k");
     gc->enable_penalty = a.Bool("--enable-penalty");
+    gc->per_request_sampling = a.Bool("--per-request-sampling");
+    gc->sampling_seed = (uint64_t)a.I64("--sampling-seed");
     gc->max_running_batch = a.Int("--max-running-batch");
     gc->max_input_tokens_per_request = a.Int("--max-input-tokens-per-request");
     gc->max_output_tokens_per_request = a.Int("--max-output-tokens-per-request");
