@@ -532,6 +532,43 @@ PPLHIP_API int pplhip_op_rope_kv_write(void* stream, void* qkv, const float* cos
                                        const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
                                        int32_t num_heads);
 
+/* ---- the row kernels between the GEMMs with everything their launchers take.  For the tests: not part of the product boundary. ----
+ * A split-K linear may leave its result as unreduced fp32 slabs for the kernel that consumes it:
+ * y[m][n] = fp16((sum_{z < splits}, z = 0, 1, ... slab_ws[(z * slab_M + m) * N + n]) * slab_scale[n]) (slab_scale fp16 [N], NULL: 1).
+ * A slab description is (slab_ws, slab_splits, slab_scale, slab_M); slab_splits == 0: none; 1 .. 8; anything else, a NULL or misaligned
+ * (16 bytes) slab_ws / slab_scale or N % 8 != 0 is PPLHIP_INVALID_VALUE before any HIP call. */
+
+/* The kernel form a (Skip)RMSNorm launch of (rows, hidden) takes, as text in buf (len bytes): "rmsnorm_kernel<MAXC,NT>", with ",i8" /
+ * ",f8" appended for the quantising epilogues (quant 0 none, 1 int8, 2 fp8; int8 is the runtime branch of the same instantiation as
+ * none).  wide_max_rows: the largest row count that takes the 512 / 1024-thread forms (the product: PPLHIP_RMSNORM_WIDE_MAX_ROWS,
+ * default 512).  Returns the status a launch would (hidden % 8 != 0 or more than 2048 chunks of 8: PPLHIP_INVALID_VALUE; rows == 0:
+ * success, empty text).  The launcher calls the same function; no HIP call, no device needed. */
+PPLHIP_API int pplhip_op_rmsnorm_form(int64_t rows, int32_t hidden, int32_t quant, int32_t wide_max_rows, char* buf, int32_t len);
+
+/* launch_rmsnorm whole: out[r] = rmsnorm(x[src(r)] + skip[src(r)]) * w with src(r) = gather_seq_starts[r + 1] - 1 (device int64, NULL:
+ * src(r) = r); skip from `skip` or, when slab_splits > 0, from the slab description (slab row = src(r), N = hidden); residual_out[r]
+ * (may be NULL) = fp16(x + skip).  q != NULL: instead of out, the int8 (q_fp8 != 0: e4m3fn) rows q [rows, hidden] and sx [rows]. */
+PPLHIP_API int pplhip_op_rmsnorm_ex(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t rows, int32_t hidden,
+                                    const int64_t* gather_seq_starts, void* out, void* residual_out, void* q, float* sx, int32_t q_fp8,
+                                    const float* slab_ws, int32_t slab_splits, const void* slab_scale, int64_t slab_M);
+
+/* out[r] = x[seq_starts[r + 1] - 1], r < B: the last-token gather alone (hidden % 8 == 0) */
+PPLHIP_API int pplhip_op_gather_last_rows(void* stream, const void* x, const int64_t* seq_starts, int64_t B, int32_t hidden, void* out);
+
+/* pplhip_op_rope_kv_write on token rows [t0, t0 + T) of the step's B requests; slab_splits > 0: the rows come from the slab description
+ * of a [T, (H + 2 Hkv) D] launch (slab row = token row - t0, slab_M == T) instead of qkv, which then only receives the rotated q. */
+PPLHIP_API int pplhip_op_rope_kv_write_ex(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
+                                          const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0,
+                                          int64_t T, int32_t num_heads, const float* slab_ws, int32_t slab_splits, const void* slab_scale,
+                                          int64_t slab_M);
+
+/* pplhip_op_linear_ex (fp16 epilogue) called the way the runtime calls wqkv / wo / w2: a split-K route may leave its slabs unreduced in
+ * ws.  *splits receives the slab count (0: y was written as usual), *slab_scale the scale pointer of the slab description (slab_M = M);
+ * the route text then holds "reduce=deferred".  dry_run: route and status only, no HIP call; *splits stays 0 (read splits= in the route). */
+PPLHIP_API int pplhip_op_linear_defer(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group,
+                                      int64_t M, int32_t N, int32_t K, void* y, int64_t ldy, void* ws, uint64_t ws_bytes, int32_t dry_run,
+                                      int32_t* splits, const void** slab_scale, char* route, int32_t route_len);
+
 /* attention over the cache for rows [row_begin, row_end) of the batch: decode rows (seqlen 1) go to
  * the decode kernel, others to the prefill kernel.  out[T, H*D] fp16. */
 PPLHIP_API int pplhip_op_attention(void* stream, const void* qkv, const pplhip_kv_view* kv,

@@ -154,55 +154,62 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(const uint4* x /* may alias
     }
 }
 
-hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip, const uint16_t* w, float eps,
-                          int64_t rows, int hidden, const int64_t* gather_seq_starts, uint16_t* out,
-                          uint16_t* residual_out, int8_t* qout, float* sx, const SplitSlabs* skip_slabs, bool q_fp8) {
+// The form a launch takes, decided by (rows, hidden) alone: the record of pplhip_op_rmsnorm_form and the launch below come from this one
+// function (as Half128Kernel / DmaKernel in k_gemm.hip).  No HIP call.
+//
+// few rows of a wide model (decode steps of 5..512 rows at hidden >= 4096): one chunk per thread on 512 / 1024 threads -- every load of
+// the row is in flight at once.  -1.9 % on config 4's per-rank step and -0.4..-1.7 % on 7B steps of 8-512 rows
+// (profiles/r04_rmsnorm_wide_ab.log).  The two forms sum a row's squares in different orders, so a token's norm -- and in the last bits
+// its logits -- depend on the step's row count class (<= 4, 5..512, > 512; the 512-row halves of a two-stream step): the same kind of
+// dependence as the GEMM tile choice by M, inside the specification's noise floor, guarded by the greedy-token tests
+// (tests/test_gpu_config5_tokens.py, test_gpu_model.py).  Up to 4 rows stay on the 256-thread form only because a block of 1024
+// threads per row buys nothing there.  Round 4 kept the wide form opt-in: its summation order moved the 70B / TP8 W4A16 parity case
+// over its fixed cap -- a case that the grouped-query decode kernel's rounded V had already brought to 0.90 of that cap; with V exact
+// again (k_attn_decode_gqa.hip, round 5) the case sits at 0.89e-3 = 1.27 x the oracle's noise floor WITH this form
+// (profiles/r05_w4_gqa_margin.log).
+hipError_t rmsnorm_form(int64_t rows, int hidden, int wide_max_rows, RmsnormForm* f) {
+    *f = RmsnormForm{};
     if (rows == 0) return hipSuccess;
     const int chunks = hidden / 8;
     if (hidden % 8 || chunks > 256 * 8) return hipErrorInvalidValue;
+    if (rows > 4 && rows <= wide_max_rows && chunks >= 512 && chunks <= 1024 && chunks % 64 == 0) *f = RmsnormForm{1, chunks <= 512 ? 512 : 1024};
+    else *f = RmsnormForm{chunks <= 256 ? 1 : (chunks <= 512 ? 2 : (chunks <= 1024 ? 4 : 8)), 256};
+    return hipSuccess;
+}
+
+// PPLHIP_RMSNORM_WIDE_MAX_ROWS=0: the 256-thread form (A/B runs); read once
+int rmsnorm_wide_max_rows() {
+    static const int wide_rows = getenv("PPLHIP_RMSNORM_WIDE_MAX_ROWS") ? atoi(getenv("PPLHIP_RMSNORM_WIDE_MAX_ROWS")) : 512;
+    return wide_rows;
+}
+
+hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip, const uint16_t* w, float eps,
+                          int64_t rows, int hidden, const int64_t* gather_seq_starts, uint16_t* out,
+                          uint16_t* residual_out, int8_t* qout, float* sx, const SplitSlabs* skip_slabs, bool q_fp8) {
+    RmsnormForm f;
+    const hipError_t fe = rmsnorm_form(rows, hidden, rmsnorm_wide_max_rows(), &f);
+    if (fe != hipSuccess || rows == 0) return fe;
+    const int chunks = hidden / 8;
     SplitSlabs sl;
     if (skip_slabs && skip_slabs->splits > 0) {
         sl = *skip_slabs;
         if (sl.N != hidden) return hipErrorInvalidValue;
     }
-    dim3 g((unsigned)rows), b(256);
     if (q_fp8 && !qout) return hipErrorInvalidValue;
-#define RMS_LAUNCH(MC)                                                                                                              \
+    const dim3 g((unsigned)rows), b((unsigned)f.nt);
+#define RMS_LAUNCH(MC, NT)                                                                                                          \
     do {                                                                                                                            \
-        if (q_fp8) hipLaunchKernelGGL((rmsnorm_kernel<MC, 256, true>), g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, \
+        if (q_fp8) hipLaunchKernelGGL((rmsnorm_kernel<MC, NT, true>), g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, \
                                       eps, chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);    \
-        else hipLaunchKernelGGL(rmsnorm_kernel<MC>, g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,          \
+        else hipLaunchKernelGGL((rmsnorm_kernel<MC, NT>), g, b, 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,    \
                                 chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);               \
     } while (0)
-    // few rows of a wide model (decode steps of 5..512 rows at hidden >= 4096): one chunk per thread on 512 / 1024 threads -- every load of
-    // the row is in flight at once.  -1.9 % on config 4's per-rank step and -0.4..-1.7 % on 7B steps of 8-512 rows
-    // (profiles/r04_rmsnorm_wide_ab.log).  The two forms sum a row's squares in different orders, so a token's norm -- and in the last bits
-    // its logits -- depend on the step's row count class (<= 4, 5..512, > 512; the 512-row halves of a two-stream step): the same kind of
-    // dependence as the GEMM tile choice by M, inside the specification's noise floor, guarded by the greedy-token tests
-    // (tests/test_gpu_config5_tokens.py, test_gpu_model.py).  Up to 4 rows stay on the 256-thread form only because a block of 1024
-    // threads per row buys nothing there.  Round 4 kept the wide form opt-in: its summation order moved the 70B / TP8 W4A16 parity case
-    // over its fixed cap -- a case that the grouped-query decode kernel's rounded V had already brought to 0.90 of that cap; with V exact
-    // again (k_attn_decode_gqa.hip, round 5) the case sits at 0.89e-3 = 1.27 x the oracle's noise floor WITH this form
-    // (profiles/r05_w4_gqa_margin.log).  PPLHIP_RMSNORM_WIDE_MAX_ROWS=0: the 256-thread form (A/B runs)
-    static const int wide_rows = getenv("PPLHIP_RMSNORM_WIDE_MAX_ROWS") ? atoi(getenv("PPLHIP_RMSNORM_WIDE_MAX_ROWS")) : 512;
-    if (rows > 4 && rows <= wide_rows && chunks >= 512 && chunks <= 1024 && chunks % 64 == 0) {
-        if (q_fp8) {
-            if (chunks <= 512) hipLaunchKernelGGL((rmsnorm_kernel<1, 512, true>), g, dim3(512), 0, s, (const uint4*)x, (const uint4*)skip,
-                                                  (const uint4*)w, eps, chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
-            else hipLaunchKernelGGL((rmsnorm_kernel<1, 1024, true>), g, dim3(1024), 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w,
-                                    eps, chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
-            return hipGetLastError();
-        }
-        if (chunks <= 512) hipLaunchKernelGGL((rmsnorm_kernel<1, 512>), g, dim3(512), 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,
-                                              chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
-        else hipLaunchKernelGGL((rmsnorm_kernel<1, 1024>), g, dim3(1024), 0, s, (const uint4*)x, (const uint4*)skip, (const uint4*)w, eps,
-                                chunks, hidden, gather_seq_starts, (uint4*)out, (uint4*)residual_out, qout, sx, sl);
-        return hipGetLastError();
-    }
-    if (chunks <= 256) RMS_LAUNCH(1);
-    else if (chunks <= 512) RMS_LAUNCH(2);
-    else if (chunks <= 1024) RMS_LAUNCH(4);
-    else RMS_LAUNCH(8);
+    if (f.nt == 512) RMS_LAUNCH(1, 512);
+    else if (f.nt == 1024) RMS_LAUNCH(1, 1024);
+    else if (f.maxc == 1) RMS_LAUNCH(1, 256);
+    else if (f.maxc == 2) RMS_LAUNCH(2, 256);
+    else if (f.maxc == 4) RMS_LAUNCH(4, 256);
+    else RMS_LAUNCH(8, 256);
 #undef RMS_LAUNCH
     return hipGetLastError();
 }

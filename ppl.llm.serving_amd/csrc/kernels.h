@@ -71,6 +71,13 @@ hipError_t launch_rmsnorm(hipStream_t s, const uint16_t* x, const uint16_t* skip
                           uint16_t* residual_out, int8_t* qout = nullptr, float* sx = nullptr,
                           const SplitSlabs* skip_slabs = nullptr,   // skip_slabs: the skip operand as unreduced split-K slabs
                           bool q_fp8 = false);  // qout / sx: int8 rows and max|y| / 127 (online_i8i8), or e4m3fn rows and 2^e (online_f8f8)
+// the instantiation rmsnorm_kernel<maxc, nt> a launch of (rows, hidden) takes and the status it returns (rows == 0: success, no launch,
+// maxc 0): a pure function, no HIP call.  wide_max_rows: rmsnorm_wide_max_rows() in the product (PPLHIP_RMSNORM_WIDE_MAX_ROWS, read once)
+struct RmsnormForm {
+    int maxc = 0, nt = 0;
+};
+hipError_t rmsnorm_form(int64_t rows, int hidden, int wide_max_rows, RmsnormForm* f);
+int rmsnorm_wide_max_rows();
 hipError_t launch_silu_mul(hipStream_t s, const uint16_t* gate_up, int64_t T, int inter, uint16_t* out);
 // out[r] = x[seq_starts[r + 1] - 1] (last-token gather of K11 when the final norm already ran on every row: fused tensor-parallel norm)
 hipError_t launch_gather_last_rows(hipStream_t s, const uint16_t* x, const int64_t* seq_starts, int64_t B, int hidden, uint16_t* out);

@@ -2697,6 +2697,70 @@ int pplhip_op_rope_kv_write(void* stream, void* qkv, const float* cos_sin, const
                                       seq_starts, start_pos, cache_indices, max_pages, B, 0, T, num_heads, kv->kv_heads, kv->head_dim));
 }
 
+// ---- the row kernels with everything their launchers take (for the tests: not part of the product boundary) ----
+// slab description -> SplitSlabs of a [slab_M, N] launch; false: not a description a producer can leave
+static bool op_slabs(const float* ws, int32_t splits, const void* scale, int64_t M, int N, SplitSlabs* sl) {
+    *sl = SplitSlabs{};
+    if (splits == 0) return true;
+    if (splits < 0 || splits > 8 || !ws || M <= 0 || N <= 0 || N % 8 || ((uintptr_t)ws & 15) || ((uintptr_t)scale & 15)) return false;
+    *sl = SplitSlabs{ws, splits, (const uint16_t*)scale, N, M};
+    return true;
+}
+
+int pplhip_op_rmsnorm_form(int64_t rows, int32_t hidden, int32_t quant, int32_t wide_max_rows, char* buf, int32_t len) {
+    if (buf && len > 0) buf[0] = 0;
+    if (rows < 0 || quant < 0 || quant > 2) return PPLHIP_INVALID_VALUE;
+    RmsnormForm f;
+    const hipError_t e = rmsnorm_form(rows, hidden, wide_max_rows, &f);
+    if (e == hipSuccess && f.nt && buf && len > 0)
+        snprintf(buf, (size_t)len, "rmsnorm_kernel<%d,%d%s>", f.maxc, f.nt, quant == 2 ? ",f8" : (quant == 1 ? ",i8" : ""));
+    return op_rc(e);
+}
+
+int pplhip_op_rmsnorm_ex(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t rows, int32_t hidden,
+                         const int64_t* gather_seq_starts, void* out, void* residual_out, void* q, float* sx, int32_t q_fp8,
+                         const float* slab_ws, int32_t slab_splits, const void* slab_scale, int64_t slab_M) {
+    SplitSlabs sl;
+    if (rows < 0 || !op_slabs(slab_ws, slab_splits, slab_scale, slab_M, hidden, &sl)) return PPLHIP_INVALID_VALUE;
+    if (rows > 0 && (!x || !w || (q ? !sx : !out))) return PPLHIP_INVALID_VALUE;
+    if (sl.splits && !gather_seq_starts && rows > slab_M) return PPLHIP_INVALID_VALUE;   // (gathered rows: the caller's seq_starts stay below slab_M)
+    return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, rows, hidden,
+                                gather_seq_starts, (uint16_t*)out, (uint16_t*)residual_out, (int8_t*)q, sx, &sl, q_fp8 != 0));
+}
+
+int pplhip_op_gather_last_rows(void* stream, const void* x, const int64_t* seq_starts, int64_t B, int32_t hidden, void* out) {
+    if (B < 0 || (B > 0 && (!x || !seq_starts || !out))) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_gather_last_rows((hipStream_t)stream, (const uint16_t*)x, seq_starts, B, hidden, (uint16_t*)out));
+}
+
+int pplhip_op_rope_kv_write_ex(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
+                               const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0, int64_t T,
+                               int32_t num_heads, const float* slab_ws, int32_t slab_splits, const void* slab_scale, int64_t slab_M) {
+    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
+    if (fmt < 0 || t0 < 0 || T < 0 || B < 0) return PPLHIP_INVALID_VALUE;
+    SplitSlabs sl;
+    if (!op_slabs(slab_ws, slab_splits, slab_scale, slab_M, (num_heads + 2 * kv->kv_heads) * kv->head_dim, &sl)) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_rope_kv_write((hipStream_t)stream, (uint16_t*)qkv, cos_sin, view_addr(kv), fmt, seq_starts, start_pos, cache_indices,
+                                      max_pages, B, t0, T, num_heads, kv->kv_heads, kv->head_dim, &sl));
+}
+
+// launch_linear (fp16 epilogue) with a non-null `defer`, as layer_linear calls it for wqkv / wo / w2: a split-K route leaves its slabs in ws
+int pplhip_op_linear_defer(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M, int32_t N,
+                           int32_t K, void* y, int64_t ldy, void* ws, uint64_t ws_bytes, int32_t dry_run, int32_t* splits,
+                           const void** slab_scale, char* route, int32_t route_len) {
+    LinearRoute r;
+    r.buf = route_len > 0 ? route : nullptr;
+    r.cap = route_len;
+    r.dry = dry_run != 0;
+    if (r.buf) r.buf[0] = 0;
+    SplitSlabs sl;
+    const hipError_t e = launch_linear((hipStream_t)stream, (const uint16_t*)x, w, (const uint16_t*)scale, wq_bit, group, M, N, K, y, ldy, false,
+                                       (float*)ws, (size_t)ws_bytes, false, &sl, &r);
+    if (splits) *splits = sl.splits;
+    if (slab_scale) *slab_scale = sl.scale;
+    return op_rc(e);
+}
+
 int pplhip_op_attention(void* stream, const void* qkv, const pplhip_kv_view* kv, const int64_t* seq_starts,
                         const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
                         int64_t decoding_batches, int64_t max_seq_len, int64_t max_kv_len, int32_t num_heads, int32_t split_k,

@@ -128,6 +128,7 @@ SYMBOLS = [
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
     "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
+    "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
 
 
@@ -213,6 +214,14 @@ def lib():
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
         L.pplhip_build_rope_table.argtypes = [vp, i32, i32, f32]
+        # (the row-kernel test entries: PPLHIP_LIB may name a build from before them, as above)
+        if hasattr(L, "pplhip_op_rmsnorm_form"):
+            L.pplhip_op_rmsnorm_form.argtypes = [i64, i32, i32, i32, C.c_char_p, i32]
+            L.pplhip_op_rmsnorm_ex.argtypes = [vp, vp, vp, vp, f32, i64, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, i64]
+            L.pplhip_op_gather_last_rows.argtypes = [vp, vp, vp, i64, i32, vp]
+            L.pplhip_op_rope_kv_write_ex.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i32, vp, i32, vp, i64]
+            L.pplhip_op_linear_defer.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, i64, vp, u64, i32, C.POINTER(i32), C.POINTER(vp),
+                                                 C.c_char_p, i32]
         _LIB = L
     return _LIB
 
@@ -222,6 +231,22 @@ def linear_route(x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws=None, ws_b
     buf = C.create_string_buffer(1024)
     rc = lib().pplhip_op_linear_ex(stream, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws, ws_bytes, int(dry_run), buf, 1024)
     return rc, buf.value.decode()
+
+
+def rmsnorm_form(rows, hidden, quant=0, wide_max_rows=512):
+    """pplhip_op_rmsnorm_form (no device): (status, form text)"""
+    buf = C.create_string_buffer(64)
+    rc = lib().pplhip_op_rmsnorm_form(rows, hidden, quant, wide_max_rows, buf, 64)
+    return rc, buf.value.decode()
+
+
+def linear_defer(x, w, scale, wq_bit, group, M, N, K, y, ldy, ws=None, ws_bytes=0, dry_run=True, stream=None):
+    """pplhip_op_linear_defer: (status, route text, splits, slab scale address or None).  Pointers are integers, as in linear_route."""
+    buf = C.create_string_buffer(1024)
+    sp, sc = C.c_int32(0), C.c_void_p(None)
+    rc = lib().pplhip_op_linear_defer(stream, x, w, scale, wq_bit, group, M, N, K, y, ldy, ws, ws_bytes, int(dry_run), C.byref(sp), C.byref(sc),
+                                      buf, 1024)
+    return rc, buf.value.decode(), sp.value, sc.value
 
 
 def step_plan(settings, batch, num_tokens, decoding_batches, seq_starts=None, max_kv_len=0, capturing=False, dump=False, lora=False):

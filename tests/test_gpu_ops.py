@@ -61,6 +61,9 @@ def test_embedding_bit_exact():
 @pytest.mark.parametrize("hidden", [128, 4096, 8192, 5120])
 @pytest.mark.parametrize("skip", [False, True])
 def test_rmsnorm(hidden, skip):
+    """Against the oracle with a relative tolerance, at 37 rows: hidden 128 takes rmsnorm_kernel<1,256>, 4096 <1,512>, 5120 and 8192
+    <1,1024>.  The forms <2,256>, <4,256> and <8,256> (steps of up to 4 or more than 512 rows, chunk counts that are no multiple of 64,
+    hidden > 8192), every form on inputs where a dropped chunk shows, and the gather / slab operands: tests/test_gpu_row_ops.py."""
     m = load_pplhip()
     rng = np.random.RandomState(hidden)
     T = 37
