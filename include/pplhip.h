@@ -334,6 +334,29 @@ typedef struct pplhip_sample_rows_args {
 PPLHIP_API int pplhip_sample_rows(pplhip_ctx* ctx, const float* logits_device, const pplhip_sample_rows_args* args,
                                   int32_t* output_host, float* logprob_host);
 
+/* Top-N logprobs (DESIGN.md "numerics", top-N logprobs row): for every batch row b with n = num_logprobs[b] > 0 the first n tokens of the
+ * ranking "x = logit * (1 / temperature) descending, ties by ascending token index" and logprob = x - logsumexp(x) over the whole
+ * vocabulary, the number the samplers report for their token.  Entry 0 is the row's greedy token.  Entries j >= vocab_size are token -1,
+ * logprob -inf.  The logits are the ones the step's sampler sees: call it after pplhip_penalty when the penalty is on, with temperatures
+ * NULL then.
+ * The results are compact: the j-th asking row, in ascending batch row, owns tokens_out[j * 20 .. j * 20 + n) and the same of
+ * logprobs_out; *rows_out is the number of asking rows.  The two pointers are library-owned pinned memory.
+ * ASYNCHRONOUS: one upload, one launch and one download are queued on local rank 0's stream and the call returns.  The contents are valid
+ * after the next synchronisation of that stream (pplhip_sample, pplhip_sample_rows or pplhip_sync) and until the next pplhip_top_logprobs;
+ * a step that asks calls this in front of its sampler and still has one synchronisation.  Two calls need such a synchronisation between
+ * them.  No asking row: no device call at all, *rows_out = 0.  Acts on local rank 0's logits at any tensor-parallel degree.
+ * NULL num_logprobs, an entry outside [0, PPLHIP_TOP_LOGPROBS_MAX], batch outside [0, max_running_batch] or batch_stride < vocab_size:
+ * PPLHIP_INVALID_VALUE before any device call.
+ * Arrived without a version bump: a client tells a library that has it by the symbol pplhip_top_logprobs (dlsym). */
+#define PPLHIP_TOP_LOGPROBS_MAX 20
+typedef struct pplhip_top_logprobs_args {
+    const float* temperatures;   /* host [B] or NULL, the convention of pplhip_sample_rows_args */
+    const int32_t* num_logprobs; /* host [B], 0 .. PPLHIP_TOP_LOGPROBS_MAX */
+    int32_t batch, vocab_size, batch_stride;
+} pplhip_top_logprobs_args;
+PPLHIP_API int pplhip_top_logprobs(pplhip_ctx* ctx, const float* logits_device, const pplhip_top_logprobs_args* args,
+                                   const int32_t** tokens_out, const float** logprobs_out, int32_t* rows_out);
+
 /* in-place penalty on the logits of the last run, using the step's device-resident token_inputs /
  * seq_starts / start_pos (llm_engine.cc:204-216). */
 PPLHIP_API int pplhip_penalty(pplhip_ctx* ctx, float* logits_device, const pplhip_penalty_args* args);
@@ -511,6 +534,12 @@ PPLHIP_API int pplhip_op_sample(void* stream, const float* logits, const float* 
 PPLHIP_API int pplhip_op_sample_rows(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
                                      const uint64_t* seeds, const uint64_t* draws, const float* rnd, int32_t batch, int32_t vocab,
                                      int32_t stride, int32_t* out_tok, float* out_logprob);
+/* the top-N logprobs kernel alone (csrc/k_logprobs.hip), for the tests: DEVICE pointers.  temperatures may be NULL; num_logprobs [batch] in
+ * 0 .. PPLHIP_TOP_LOGPROBS_MAX (anything else: PPLHIP_INVALID_VALUE, nothing launched).  out_tok / out_logprob are [asked, 20], `asked` the
+ * number of rows with num_logprobs > 0, in ascending batch row; row j's slots behind its n are not written.  The row list is made on the
+ * host from a read-back of num_logprobs, so the call synchronises `stream` before it launches; no asking row: no launch. */
+PPLHIP_API int pplhip_op_top_logprobs(void* stream, const float* logits, const float* temperatures, const int32_t* num_logprobs,
+                                      int32_t batch, int32_t vocab, int32_t stride, int32_t* out_tok, float* out_logprob);
 /* out_u[b] = u(seeds[b], draws[b]), the generator alone (device pointers) */
 PPLHIP_API int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u);
 

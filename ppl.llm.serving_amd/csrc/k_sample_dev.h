@@ -2,7 +2,8 @@
 // tree (DESIGN.md "sampler").  k_sample.hip instantiates them with a launch's uniform arguments (K13: sample_greedy_kernel,
 // sample_topk_topp_kernel), k_sample_rows.hip with every row's own arguments through a row list.  A row function sees the row's pointer,
 // the row's temperature (already defaulted: row_temperature), its k / p / random number and the two places its answer goes; for equal
-// arguments it gives equal token and logprob bits from either file.
+// arguments it gives equal token and logprob bits from either file.  A third row function, top_logprobs_row (k_logprobs.hip), reports the
+// first n tokens of the same ranking with the same full-vocabulary logprob; it decides nothing and shares radix_pass with the top-k rule.
 #pragma once
 #include "kernels.h"
 
@@ -305,6 +306,127 @@ __device__ __forceinline__ void sample_topk_topp_row(const float* __restrict__ r
             *out_tok = ci[pick];
             *out_lp = xv[j] - (mx + logf(se));
         }
+}
+
+// top-N logprobs (DESIGN.md "numerics", top-N logprobs row): the first n entries of the ranking "x = logits / temperature descending, ties
+// by ascending index" (am_better's order) with logprob x - logsumexp(x) over the WHOLE vocabulary, the number both samplers report for
+// their token.  Entries j >= vocab are padded (token -1, logprob -inf); the slots behind n are not written.
+// Work per row (one block of TL_THREADS = ST_THREADS threads, the width radix_pass is written for): maximum and mass in the greedy row's
+// style (16-byte loads, four in flight per thread, when `vec`), the four radix rounds for the key of rank n (+ the index rounds only when
+// equal keys straddle the cut), one gather of <= 20 candidates into LDS, a 32-entry bitonic sort by shuffles in wave 0, one thread per
+// entry for the answer.  -0 ranks as +0 (the float comparison of am_better calls them equal): rank_key folds the two before order_key.
+constexpr int TL_THREADS = ST_THREADS, TL_WAVES = TL_THREADS / 64;
+static_assert(TL_THREADS == 256, "radix_pass and block_scan_incl are written for 256 threads");
+
+__device__ __forceinline__ uint32_t rank_key(float x) {
+    return order_key(x == 0.f ? 0.f : x);
+}
+
+__device__ __forceinline__ void top_logprobs_row(const float* __restrict__ row, bool vec, float t, int n, int vocab,
+                                                 int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
+    __shared__ float sf[TL_WAVES];
+    __shared__ int wsum[4], sel[4], hist[256];
+    __shared__ float cv[32];
+    __shared__ int ci[32];
+    const int tid = threadIdx.x;
+    const float invt = 1.0f / t;
+    const int k = n < vocab ? n : vocab;
+    const int nv = vec ? vocab >> 2 : 0;   // float4 chunks; the tail (and unaligned rows) element by element
+    const float4 none = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+
+    float mx = -INFINITY;
+    for (int c0 = tid; c0 < nv; c0 += 4 * TL_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 + u * TL_THREADS;
+            v[u] = c < nv ? reinterpret_cast<const float4*>(row)[c] : none;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) mx = fmaxf(mx, fmaxf(fmaxf(v[u].x * invt, v[u].y * invt), fmaxf(v[u].z * invt, v[u].w * invt)));
+    }
+    for (int i = nv * 4 + tid; i < vocab; i += TL_THREADS) mx = fmaxf(mx, row[i] * invt);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) sf[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sf[0], sf[1]), fmaxf(sf[2], sf[3]));
+    __syncthreads();
+    // the mass: per thread its chunks in order, (x + y) + (z + w) inside a chunk, then its tail elements; then a tree over the block
+    float se = 0.f;
+    for (int c0 = tid; c0 < nv; c0 += 4 * TL_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 + u * TL_THREADS;
+            v[u] = c < nv ? reinterpret_cast<const float4*>(row)[c] : none;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            se += (__expf(v[u].x * invt - mx) + __expf(v[u].y * invt - mx)) + (__expf(v[u].z * invt - mx) + __expf(v[u].w * invt - mx));
+    }
+    for (int i = nv * 4 + tid; i < vocab; i += TL_THREADS) se += __expf(row[i] * invt - mx);
+    se = wave_sum(se);
+    if ((tid & 63) == 0) sf[tid >> 6] = se;
+    __syncthreads();
+    se = (sf[0] + sf[1]) + (sf[2] + sf[3]);   // with the wave's six steps: log2(TL_THREADS) tree steps
+    const float lse = mx + logf(se);
+
+    // the key of rank k, most significant byte first
+    uint32_t prefix = 0, mask = 0;
+    int need = k, n_eq = 0;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        const int bin = radix_pass<true>(vocab, shift,
+            [&](int i, uint32_t& kk) { kk = rank_key(row[i] * invt); return (kk & mask) == prefix; }, need, &n_eq, hist, wsum, sel);
+        prefix |= (uint32_t)bin << shift;
+        mask |= 255u << shift;
+    }
+    // `need` of the `n_eq` elements whose key equals the cut are entries: the ones with the lowest indices
+    int idx_cut = 0x7fffffff;
+    if (need < n_eq) {
+        uint32_t ip = 0, im = 0;
+        int dummy = 0;
+#pragma unroll 1
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            const int bin = radix_pass<false>(vocab, shift,
+                [&](int i, uint32_t& kk) { kk = (uint32_t)i; return rank_key(row[i] * invt) == prefix && ((uint32_t)i & im) == ip; },
+                need, &dummy, hist, wsum, sel);
+            ip |= (uint32_t)bin << shift;
+            im |= 255u << shift;
+        }
+        idx_cut = (int)ip;
+    }
+    // gather the k entries (any order), pad to 32, sort by (x descending, index ascending)
+    if (tid < 32) { cv[tid] = -INFINITY; ci[tid] = 0x7fffffff; }
+    if (tid == 0) sel[3] = 0;
+    __syncthreads();
+    for (int i = tid; i < vocab; i += TL_THREADS) {
+        const float x = row[i] * invt;
+        const uint32_t kk = rank_key(x);
+        if (kk > prefix || (kk == prefix && i <= idx_cut)) {
+            const int slot = atomicAdd(&sel[3], 1);
+            if (slot < 32) { cv[slot] = x; ci[slot] = i; }
+        }
+    }
+    __syncthreads();
+    if (tid < 64) {   // wave 0; lanes 32..63 sort a copy of their own, which nobody reads
+        ArgMax a{cv[tid & 31], ci[tid & 31]};
+#pragma unroll
+        for (int size = 2; size <= 32; size <<= 1)
+#pragma unroll
+            for (int str = size >> 1; str > 0; str >>= 1) {
+                ArgMax b;
+                b.v = __shfl_xor(a.v, str, 64);
+                b.i = __shfl_xor(a.i, str, 64);
+                const bool a_first = a.v > b.v || (a.v == b.v && a.i < b.i);   // a ranks before b
+                const bool want_first = ((tid & str) == 0) == ((tid & size) == 0);  // this lane keeps the better of the pair
+                a = (a_first == want_first) ? a : b;
+            }
+        if (tid < n) {
+            out_tok[tid] = tid < k ? a.i : -1;
+            out_lp[tid] = tid < k ? a.v - lse : -INFINITY;
+        }
+    }
 }
 
 }  // namespace pplhip

@@ -253,6 +253,13 @@ hipError_t launch_sample_rows(hipStream_t s, const float* logits, const float* t
 // out_u[b] = u(seeds[b], draws[b]): Philox4x32-10, word 0, 24 bits
 hipError_t launch_sample_uniform(hipStream_t s, const uint64_t* seeds, const uint64_t* draws, int batch, float* out_u);
 
+// ---- k_logprobs.hip: top-N logprobs ---------------------------------------------------------------
+// rows: device list of the n_rows batch rows with num_logprobs[b] in 1 .. 20, ascending; num_logprobs and temperatures (may be NULL) are
+// indexed by the batch row, out_tok / out_logprob [n_rows, 20] by the place in the list.  No rows: no launch.
+constexpr int TOP_LOGPROBS_MAX = 20;   // slots per asked row (PPLHIP_TOP_LOGPROBS_MAX)
+hipError_t launch_top_logprobs(hipStream_t s, const float* logits, const float* temperatures, const int32_t* num_logprobs,
+                               const int32_t* rows, int n_rows, int vocab, int stride, int32_t* out_tok, float* out_logprob);
+
 // ---- synth.hip --------------------------------------------------------------------------------
 // kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm; and for the fp8 KV
 // slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales; for the int4 KV slab: 7 nibble pairs 1..15, 8 scales of its rule

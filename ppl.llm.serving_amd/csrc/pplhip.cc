@@ -95,6 +95,12 @@ struct Lane {
 // pplhip_sample_rows stages one step's per-row arrays in one pinned block that goes up in one copy: for capacity cap_B,
 // seeds u64 [cap_B] | draws u64 [cap_B] | temperatures f32 [cap_B] | top_p f32 [cap_B] | top_k i32 [cap_B] | row list i32 [cap_B]
 constexpr int64_t SROWS_BYTES = 8 + 8 + 4 + 4 + 4 + 4;
+// pplhip_top_logprobs has a pinned block of its own (the step's sampler call restages h_srows while this one's copy may still be in
+// flight): temperatures f32 [cap_B] | num_logprobs i32 [cap_B] | row list i32 [cap_B] going up, and one block coming down, for `asked`
+// rows tokens i32 [asked, 20] | logprobs f32 [asked, 20]
+constexpr int64_t TLP_IN_BYTES = 4 + 4 + 4;
+constexpr int64_t TLP_OUT_BYTES = (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
+static_assert(PPLHIP_TOP_LOGPROBS_MAX == TOP_LOGPROBS_MAX, "header and kernel disagree");
 
 struct Rank {
     int device = 0;
@@ -160,6 +166,8 @@ struct Rank {
     float *d_rep = nullptr, *d_pres = nullptr, *d_freq = nullptr, *d_ptemp = nullptr;
     float* h_rand = nullptr;  // pinned
     char *h_srows = nullptr, *d_srows = nullptr;  // pplhip_sample_rows: pinned staging and its device image, SROWS_BYTES per batch row
+    char *h_tlp_in = nullptr, *d_tlp_in = nullptr;    // pplhip_top_logprobs: TLP_IN_BYTES per batch row going up ...
+    char *h_tlp_out = nullptr, *d_tlp_out = nullptr;  // ... TLP_OUT_BYTES per batch row coming down
 
     // exchange region of the direct collectives (k_comm.hip): fine-grained, peer-mapped; holds the flag words and the buffers
     // the collectives work in place on (part, part2) or push into (logits_gather)
@@ -738,6 +746,8 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.pages_dev) hipFree(R.pages_dev);
         if (R.h_rand) hipHostFree(R.h_rand);
         if (R.h_srows) hipHostFree(R.h_srows);
+        if (R.h_tlp_in) hipHostFree(R.h_tlp_in);
+        if (R.h_tlp_out) hipHostFree(R.h_tlp_out);
         if (R.stream) hipStreamDestroy(R.stream);
     }
     delete c;
@@ -1033,6 +1043,10 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             HIPCK(cp, r, hipHostMalloc((void**)&R.h_rand, cap_B * 4, hipHostMallocDefault));
             ALLOC(R.d_srows, cap_B * SROWS_BYTES);
             HIPCK(cp, r, hipHostMalloc((void**)&R.h_srows, cap_B * SROWS_BYTES, hipHostMallocDefault));
+            ALLOC(R.d_tlp_in, cap_B * TLP_IN_BYTES);
+            HIPCK(cp, r, hipHostMalloc((void**)&R.h_tlp_in, cap_B * TLP_IN_BYTES, hipHostMallocDefault));
+            ALLOC(R.d_tlp_out, cap_B * TLP_OUT_BYTES);
+            HIPCK(cp, r, hipHostMalloc((void**)&R.h_tlp_out, cap_B * TLP_OUT_BYTES, hipHostMallocDefault));
             if (opts->enable_penalty) {
                 ALLOC(R.count_map, (uint64_t)cap_B * d.vocab_size * 2);
                 ALLOC(R.d_slots, cap_B * 8);
@@ -2416,6 +2430,47 @@ int pplhip_sample_rows(pplhip_ctx* c, const float* logits_device, const pplhip_s
     return p2p_check(c, 0);
 }
 
+// the rows with num_logprobs[b] in 1 .. 20, ascending; returns their number, or -1 for an entry outside [0, 20]
+static int top_logprobs_row_list(const int32_t* num_logprobs, int B, int32_t* rows) {
+    int n = 0;
+    for (int i = 0; i < B; ++i) {
+        if (num_logprobs[i] < 0 || num_logprobs[i] > PPLHIP_TOP_LOGPROBS_MAX) return -1;
+        if (num_logprobs[i] > 0) rows[n++] = i;
+    }
+    return n;
+}
+
+int pplhip_top_logprobs(pplhip_ctx* c, const float* logits_device, const pplhip_top_logprobs_args* a, const int32_t** tokens_out,
+                        const float** logprobs_out, int32_t* rows_out) {
+    if (!c || !a || !logits_device || !tokens_out || !logprobs_out || !rows_out || !a->num_logprobs) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    const int B = a->batch;
+    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
+    if (a->vocab_size <= 0 || a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
+    const int64_t cap = R.cap_B;
+    char* h = R.h_tlp_in;
+    // (the list is built in place: a refused call has launched nothing, and nothing of an earlier call still reads this block once the
+    // stream was synchronised, which the contract asks for between two calls)
+    const int asked = top_logprobs_row_list(a->num_logprobs, B, (int32_t*)(h + 8 * cap));
+    if (asked < 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "num_logprobs outside [0, PPLHIP_TOP_LOGPROBS_MAX]");
+    *tokens_out = (const int32_t*)R.h_tlp_out;
+    *logprobs_out = (const float*)(R.h_tlp_out + (int64_t)asked * 4 * PPLHIP_TOP_LOGPROBS_MAX);
+    *rows_out = asked;
+    if (asked == 0) return 0;   // nobody asked: no HIP call
+    if (a->temperatures) memcpy(h, a->temperatures, (size_t)B * 4);
+    memcpy(h + 4 * cap, a->num_logprobs, (size_t)B * 4);
+    HIPCK(c, 0, hipSetDevice(R.device));
+    hipStream_t s = R.stream;
+    HIPCK(c, 0, hipMemcpyAsync(R.d_tlp_in, h, (size_t)(8 * cap + 4 * (int64_t)asked), hipMemcpyHostToDevice, s));
+    const char* d = R.d_tlp_in;
+    int32_t* d_tok = (int32_t*)R.d_tlp_out;
+    float* d_lp = (float*)(R.d_tlp_out + (int64_t)asked * 4 * PPLHIP_TOP_LOGPROBS_MAX);
+    HIPCK(c, 0, launch_top_logprobs(s, logits_device, a->temperatures ? (const float*)d : nullptr, (const int32_t*)(d + 4 * cap),
+                                    (const int32_t*)(d + 8 * cap), asked, a->vocab_size, a->batch_stride, d_tok, d_lp));
+    HIPCK(c, 0, hipMemcpyAsync(R.h_tlp_out, R.d_tlp_out, (size_t)asked * TLP_OUT_BYTES, hipMemcpyDeviceToHost, s));
+    return 0;   // asynchronous: the step's sampler call (or pplhip_sync) is the synchronisation
+}
+
 int pplhip_penalty(pplhip_ctx* c, float* logits_device, const pplhip_penalty_args* a) {
     if (!c || !a || !logits_device) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[0];
@@ -2670,6 +2725,29 @@ int pplhip_op_sample_rows(void* stream, const float* logits, const float* temper
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call; the stream was idle anyway
     if (e == hipSuccess)
         e = launch_sample_rows(s, logits, temperatures, top_k, top_p, seeds, draws, rnd, d_rows, ng, batch - ng, vocab, stride, out_tok, out_logprob);
+    const hipError_t e2 = hipFreeAsync(d_rows, s);
+    return op_rc(e != hipSuccess ? e : e2);
+}
+
+// top_logprobs_kernel alone.  The row list is made here from a read-back of num_logprobs, as pplhip_op_sample_rows makes its own
+int pplhip_op_top_logprobs(void* stream, const float* logits, const float* temperatures, const int32_t* num_logprobs, int32_t batch,
+                           int32_t vocab, int32_t stride, int32_t* out_tok, float* out_logprob) {
+    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
+    if (batch == 0) return 0;
+    if (!logits || !num_logprobs || !out_tok || !out_logprob) return PPLHIP_INVALID_VALUE;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> n(batch), rows(batch);
+    hipError_t e = hipMemcpyAsync(n.data(), num_logprobs, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    const int asked = top_logprobs_row_list(n.data(), batch, rows.data());
+    if (asked < 0) return PPLHIP_INVALID_VALUE;
+    if (asked == 0) return 0;
+    int32_t* d_rows = nullptr;
+    if ((e = hipMallocAsync((void**)&d_rows, (size_t)asked * 4, s)) != hipSuccess) return op_rc(e);
+    e = hipMemcpyAsync(d_rows, rows.data(), (size_t)asked * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call
+    if (e == hipSuccess) e = launch_top_logprobs(s, logits, temperatures, num_logprobs, d_rows, asked, vocab, stride, out_tok, out_logprob);
     const hipError_t e2 = hipFreeAsync(d_rows, s);
     return op_rc(e != hipSuccess ? e : e2);
 }

@@ -67,6 +67,14 @@ class SampleRowsArgs(C.Structure):
                 ("batch", C.c_int32), ("vocab_size", C.c_int32), ("batch_stride", C.c_int32)]
 
 
+TOP_LOGPROBS_MAX = 20   # PPLHIP_TOP_LOGPROBS_MAX
+
+
+class TopLogprobsArgs(C.Structure):
+    _fields_ = [("temperatures", C.c_void_p), ("num_logprobs", C.c_void_p), ("batch", C.c_int32), ("vocab_size", C.c_int32),
+                ("batch_stride", C.c_int32)]
+
+
 class PenaltyArgs(C.Structure):
     _fields_ = [("temperatures", C.c_void_p), ("repetition_penalties", C.c_void_p), ("presence_penalties", C.c_void_p),
                 ("frequency_penalties", C.c_void_p), ("batch_slots", C.c_void_p), ("batch", C.c_int32),
@@ -123,10 +131,10 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
-    "pplhip_sample", "pplhip_sample_rows", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
+    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -210,6 +218,9 @@ def lib():
             L.pplhip_sample_rows.argtypes = [vp, vp, C.POINTER(SampleRowsArgs), vp, vp]
             L.pplhip_op_sample_rows.argtypes = [vp] * 8 + [i32, i32, i32, vp, vp]
             L.pplhip_op_sample_uniform.argtypes = [vp, vp, vp, i32, vp]
+        if hasattr(L, "pplhip_top_logprobs"):
+            L.pplhip_top_logprobs.argtypes = [vp, vp, C.POINTER(TopLogprobsArgs), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
+            L.pplhip_op_top_logprobs.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
@@ -543,6 +554,32 @@ class Context:
             logits_ptr = self.logits_ptr(0)[0]
         self._ck(lib().pplhip_sample_rows(self.h, logits_ptr, C.byref(a), tok.ctypes.data, lp.ctypes.data), 0, "sample_rows")
         return tok, lp
+
+    def top_logprobs(self, num_logprobs, temperatures=None, logits_ptr=None):
+        """queues the top-N logprobs of the last run's logits for the rows with num_logprobs > 0 and returns a function that reads them:
+        call it after the step's sampler call (or sync()) and before the next top_logprobs; it gives (tokens, logprobs), each
+        [asked, TOP_LOGPROBS_MAX] copied out of the library's pinned block, row j = the j-th asking batch row."""
+        a = TopLogprobsArgs()
+        n = np.ascontiguousarray(num_logprobs, dtype=np.int32)
+        t = None if temperatures is None else np.ascontiguousarray(temperatures, dtype=np.float32)
+        assert t is None or len(t) == len(n)
+        a.num_logprobs = n.ctypes.data
+        a.temperatures = None if t is None else t.ctypes.data
+        a.batch, a.vocab_size, a.batch_stride = len(n), self.desc.vocab_size, self.desc.vocab_size
+        if logits_ptr is None:
+            logits_ptr = self.logits_ptr(0)[0]
+        p_tok, p_lp, rows = C.c_void_p(), C.c_void_p(), C.c_int32(-1)
+        self._ck(lib().pplhip_top_logprobs(self.h, logits_ptr, C.byref(a), C.byref(p_tok), C.byref(p_lp), C.byref(rows)), 0, "top_logprobs")
+        asked = rows.value
+
+        def read():
+            if asked == 0:
+                return np.empty((0, TOP_LOGPROBS_MAX), dtype=np.int32), np.empty((0, TOP_LOGPROBS_MAX), dtype=np.float32)
+            tok = np.ctypeslib.as_array(C.cast(p_tok, C.POINTER(C.c_int32)), shape=(asked, TOP_LOGPROBS_MAX)).copy()
+            lp = np.ctypeslib.as_array(C.cast(p_lp, C.POINTER(C.c_float)), shape=(asked, TOP_LOGPROBS_MAX)).copy()
+            return tok, lp
+        read.rows = asked
+        return read
 
     def penalty(self, temperatures, repetition, presence, frequency, batch_slots, req_list_changed=True):
         a = PenaltyArgs()

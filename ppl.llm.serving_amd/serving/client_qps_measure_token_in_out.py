@@ -39,12 +39,14 @@ def synthetic_requests(n, vocab, max_seq_len, seed):
     return out
 
 
-async def one_request(stub, rid, tokens, gen_len, early_stopping, rec):
+async def one_request(stub, rid, tokens, gen_len, early_stopping, rec, top_logprobs=0):
     req = P.BatchedRequest()
     r = req.req.add()
     r.id = rid
     r.tokens.ids.extend(tokens)
     r.choosing_parameters.do_sample = False
+    if top_logprobs:
+        r.choosing_parameters.top_logprobs = top_logprobs
     r.stopping_parameters.max_new_tokens = gen_len
     r.stopping_parameters.ignore_eos_token = not early_stopping
     t0 = time.perf_counter()
@@ -80,7 +82,7 @@ async def run(a):
         tasks = []
         t_begin = time.perf_counter()
         for i, (tok, gl) in enumerate(reqs):
-            tasks.append(asyncio.create_task(one_request(stub, i, tok, gl, a.early_stopping, rec)))
+            tasks.append(asyncio.create_task(one_request(stub, i, tok, gl, a.early_stopping, rec, a.top_logprobs)))
             if rate != float("inf"):
                 await asyncio.sleep(rng.exponential(1.0 / rate))
             elif i % 64 == 63:
@@ -113,6 +115,7 @@ def main(argv=None):
     ap.add_argument("--vocab-size", type=int, default=32000)
     ap.add_argument("--max-seq-len", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--top-logprobs", type=int, default=0, help="ask for N ranked alternatives with every token (0 .. 20; only forwarded)")
     a = ap.parse_args(argv)
     return asyncio.run(run(a))
 

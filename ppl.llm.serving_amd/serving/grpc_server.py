@@ -51,6 +51,13 @@ class CRequest(C.Structure):
                 ("prompt", C.c_char_p), ("n_prompt", C.c_int32)]
 
 
+TOP_LOGPROBS_MAX = 20   # PPLSRV_TOP_LOGPROBS_MAX
+
+
+class CTopLogprobs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("tokens", C.c_int32 * TOP_LOGPROBS_MAX), ("logprobs", C.c_float * TOP_LOGPROBS_MAX)]
+
+
 class CResponse(C.Structure):
     _fields_ = [("id", C.c_uint64), ("token", C.c_int32), ("logprob", C.c_float), ("status", C.c_int32),
                 ("finish_reason", C.c_int32), ("is_special", C.c_int32), ("text_len", C.c_int32), ("text_off", C.c_int64)]
@@ -66,6 +73,9 @@ def load_lib():
     L.pplsrv_submit_ex.argtypes = [C.c_void_p, C.POINTER(CRequest), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int32]
     L.pplsrv_poll.argtypes = [C.c_void_p, C.POINTER(CResponse), C.c_int32, C.c_int32]
     L.pplsrv_poll_text.argtypes = [C.c_void_p, C.POINTER(CResponse), C.c_int32, C.c_int32, C.c_char_p, C.c_int64]
+    L.pplsrv_submit_logprobs.argtypes = [C.c_void_p, C.POINTER(CRequest), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                         C.c_int32]
+    L.pplsrv_poll_logprobs.argtypes = [C.c_void_p, C.POINTER(CResponse), C.c_int32, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(CTopLogprobs)]
     L.pplsrv_cancel.argtypes = [C.c_void_p, C.c_uint64]
     L.pplsrv_kv_cache_max_tokens.argtypes = [C.c_void_p]
     L.pplsrv_kv_cache_max_tokens.restype = C.c_uint64
@@ -108,8 +118,9 @@ class Serving:
         buf = (CResponse * 4096)()
         tcap = 1 << 20
         tbuf = C.create_string_buffer(tcap)
+        tops = (CTopLogprobs * 4096)()
         while not self.stop:
-            n = self.lib.pplsrv_poll_text(self.h, buf, 4096, 50, tbuf, tcap)
+            n = self.lib.pplsrv_poll_logprobs(self.h, buf, 4096, 50, tbuf, tcap, tops)
             if n <= 0:
                 continue
             per_call = {}
@@ -126,7 +137,8 @@ class Serving:
                     piece = (C.string_at(C.addressof(tbuf) + r.text_off, r.text_len).decode("utf-8", errors="replace")
                              if (text and r.text_off >= 0) else "")
                     per_call.setdefault(id(q), (q, []))[1].append((orig_id, r.token, r.logprob, r.status, r.finish_reason,
-                                                                   r.is_special, text, piece))
+                                                                   r.is_special, text, piece,
+                                                                   (tops[i].tokens[:tops[i].n], tops[i].logprobs[:tops[i].n]) if tops[i].n else None))
             for q, items in per_call.values():
                 self.loop.call_soon_threadsafe(q.put_nowait, items)
 
@@ -144,6 +156,7 @@ class Serving:
         q = asyncio.Queue()
         creqs = (CRequest * n)()
         seeds = (C.c_uint64 * n)()             # choosing_parameters.seed beside the request (0: none); used with --per-request-sampling
+        nlp = (C.c_int32 * n)()                # choosing_parameters.top_logprobs beside the request (0: none; the generator clamps to 20)
         keep = []
         failed = []
         with self.lock:
@@ -159,6 +172,7 @@ class Serving:
             c = creqs[len(mapped)]
             c.id = base + i
             seeds[len(mapped)] = pb.choosing_parameters.seed if pb.choosing_parameters.do_sample else 0
+            nlp[len(mapped)] = min(int(pb.choosing_parameters.top_logprobs), TOP_LOGPROBS_MAX)
             if text:
                 raw = pb.prompt.encode("utf-8")
                 keep.append(raw)
@@ -175,7 +189,7 @@ class Serving:
             for mid, orig, text in mapped:
                 self.routes[mid] = (q, orig, text)
         if mapped:
-            rc = self.lib.pplsrv_submit_ex(self.h, creqs, None, seeds, len(mapped))
+            rc = self.lib.pplsrv_submit_logprobs(self.h, creqs, None, seeds, nlp, len(mapped))
             if rc != 0:
                 failed += [orig for _, orig, _ in mapped]
                 with self.lock:
@@ -193,7 +207,7 @@ class Serving:
             while pending > 0:
                 items = await q.get()
                 out = P.BatchedResponse()
-                for orig_id, token, logprob, status, reason, special, text, piece in items:
+                for orig_id, token, logprob, status, reason, special, text, piece, top in items:
                     r = out.rsp.add()
                     r.status, r.id = status, orig_id
                     if status == P.FAILED:
@@ -204,6 +218,9 @@ class Serving:
                     else:
                         r.tokens.ids.append(token & 0xFFFFFFFF)
                     r.detail.logprobs, r.detail.is_special, r.detail.finish_reason = logprob, bool(special), reason
+                    if top:
+                        r.detail.top_tokens.extend(t & 0xFFFFFFFF for t in top[0])
+                        r.detail.top_logprobs.extend(top[1])
                     if status == P.FINISHED:
                         pending -= 1
                 yield out

@@ -28,7 +28,9 @@ def _build():
         ("temperature", 1, F.TYPE_FLOAT, OPT, None), ("top_k", 2, F.TYPE_UINT32, OPT, None), ("top_p", 3, F.TYPE_FLOAT, OPT, None),
         ("typical_p", 4, F.TYPE_FLOAT, OPT, None), ("do_sample", 5, F.TYPE_BOOL, OPT, None), ("seed", 6, F.TYPE_UINT64, OPT, None),
         ("repetition_penalty", 7, F.TYPE_FLOAT, OPT, None), ("presence_penalty", 8, F.TYPE_FLOAT, OPT, None),
-        ("frequency_penalty", 9, F.TYPE_FLOAT, OPT, None), ("watermark", 10, F.TYPE_BOOL, OPT, None)])
+        ("frequency_penalty", 9, F.TYPE_FLOAT, OPT, None), ("watermark", 10, F.TYPE_BOOL, OPT, None),
+        # past the reference's numbers (its clients skip the field; unset it adds no byte): ranked alternatives per generated token, 0 .. 20
+        ("top_logprobs", 16, F.TYPE_UINT32, OPT, None)])
     _msg(fd, "StoppingCriteriaParameters", [
         ("max_new_tokens", 1, F.TYPE_UINT32, OPT, None), ("stop_tokens", 2, F.TYPE_MESSAGE, OPT, "Tokens"),
         ("ignore_eos_token", 3, F.TYPE_BOOL, OPT, None)])
@@ -45,7 +47,9 @@ def _build():
             ev = e.value.add()
             ev.name, ev.number = v, i
     _msg(fd, "Detail", [("logprobs", 1, F.TYPE_FLOAT, OPT, None), ("is_special", 2, F.TYPE_BOOL, OPT, None),
-                        ("finish_reason", 3, F.TYPE_ENUM, OPT, "FinishReason")])
+                        ("finish_reason", 3, F.TYPE_ENUM, OPT, "FinishReason"),
+                        # past the reference's numbers, as above: the alternatives, best first, and their logprobs
+                        ("top_tokens", 16, F.TYPE_UINT32, REP, None), ("top_logprobs", 17, F.TYPE_FLOAT, REP, None)])
     _msg(fd, "Response", [("status", 1, F.TYPE_ENUM, OPT, "Status"), ("id", 2, F.TYPE_UINT64, OPT, None),
                           ("generated", 3, F.TYPE_STRING, OPT, None), ("tokens", 4, F.TYPE_MESSAGE, OPT, "Tokens"),
                           ("detail", 5, F.TYPE_MESSAGE, OPT, "Detail")])

@@ -88,6 +88,23 @@ RetCode HipPostProcessor::SampleRows(const float* logits_device, const float* te
     return FromPplHipStatus(st);
 }
 
+static_assert(PostProcessor::kTopLogprobsMax == PPLHIP_TOP_LOGPROBS_MAX, "interface and library disagree");
+
+RetCode HipPostProcessor::TopLogprobs(const float* logits_device, const float* temperatures_host, const int32_t* num_logprobs_host,
+                                      int32_t batch, int32_t vocab_size, int32_t batch_stride, const int32_t** tokens, const float** logprobs,
+                                      int32_t* rows) {
+    pplhip_top_logprobs_args a;
+    memset(&a, 0, sizeof(a));
+    a.temperatures = temperatures_host;
+    a.num_logprobs = num_logprobs_host;
+    a.batch = batch;
+    a.vocab_size = vocab_size;
+    a.batch_stride = batch_stride;
+    const int st = pplhip_top_logprobs(ctx_, logits_device, &a, tokens, logprobs, rows);
+    if (st) LOG(ERROR) << "top logprobs failed: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
 RetCode HipPostProcessor::ApplyPenalty(const float* temperatures_host, const float* repetition_penalties_host,
                                        const float* presence_penalties_host, const float* frequency_penalties_host,
                                        const int64_t* batch_slots_host, const int64_t*, const int64_t*, const int64_t*,

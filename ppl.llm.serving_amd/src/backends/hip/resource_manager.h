@@ -43,6 +43,9 @@ public:
     ppl::common::RetCode SampleRows(const float* logits_device, const float* temperatures_host, const int32_t* top_k_host,
                                     const float* top_p_host, const uint64_t* seeds_host, const uint64_t* draws_host, int32_t batch,
                                     int32_t vocab_size, int32_t batch_stride, int32_t* output_host, float* logprob_host) override;
+    ppl::common::RetCode TopLogprobs(const float* logits_device, const float* temperatures_host, const int32_t* num_logprobs_host,
+                                     int32_t batch, int32_t vocab_size, int32_t batch_stride, const int32_t** tokens, const float** logprobs,
+                                     int32_t* rows) override;
 
 private:
     pplhip_ctx* ctx_;

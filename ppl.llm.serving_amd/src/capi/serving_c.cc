@@ -1,5 +1,6 @@
 #include "capi/serving_c.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <condition_variable>
@@ -37,6 +38,10 @@ public:
             o.text_off = -1;
             q_.push_back(o);
             text_.push_back(r.generated);
+            pplsrv_top_logprobs t{};
+            t.n = (int32_t)std::min<size_t>(r.top_tokens.size(), PPLSRV_TOP_LOGPROBS_MAX);
+            for (int32_t j = 0; j < t.n; ++j) { t.tokens[j] = r.top_tokens[j]; t.logprobs[j] = r.top_logprobs[j]; }
+            top_.push_back(t);
         }
         cv_.notify_all();
     }
@@ -48,9 +53,10 @@ public:
         o.text_off = -1;
         q_.push_back(o);
         text_.emplace_back();
+        top_.emplace_back();
         cv_.notify_all();
     }
-    int Poll(pplsrv_response* out, int max, int timeout_ms, char* text_buf, int64_t text_cap) {
+    int Poll(pplsrv_response* out, int max, int timeout_ms, char* text_buf, int64_t text_cap, pplsrv_top_logprobs* tops) {
         std::unique_lock<std::mutex> lk(mu_);
         if (q_.empty() && timeout_ms > 0) cv_.wait_for(lk, std::chrono::milliseconds(timeout_ms), [&] { return !q_.empty(); });
         int n = 0;
@@ -66,9 +72,11 @@ public:
                 out[n].text_len = (int32_t)t.size();
                 used += (int64_t)t.size();
             }
+            if (tops) tops[n] = top_.front();
             ++n;
             q_.pop_front();
             text_.pop_front();
+            top_.pop_front();
         }
         return n;
     }
@@ -78,6 +86,7 @@ private:
     std::condition_variable cv_;
     std::deque<pplsrv_response> q_;
     std::deque<std::string> text_;  // Response::generated of q_[i]
+    std::deque<pplsrv_top_logprobs> top_;  // Response::top_tokens / top_logprobs of q_[i]
 };
 
 }  // namespace
@@ -166,6 +175,11 @@ int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slo
 }
 
 int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, int32_t n) {
+    return pplsrv_submit_logprobs(s, reqs, slots, seeds, nullptr, n);
+}
+
+int pplsrv_submit_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
+                           int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -181,6 +195,7 @@ int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots
         r->early_stopping = q.early_stopping != 0;
         r->lora_slot = slots ? slots[i] : -1;
         r->seed = seeds ? seeds[i] : 0;
+        r->num_logprobs = num_logprobs ? num_logprobs[i] : 0;
         if (!q.tokens && q.prompt) {
             // text request (grpc_server.cc:218-252): LLMGenerator::Process tokenises it and adds the EOS id to its stop tokens
             if (!s->resource.tokenizer) {
@@ -200,12 +215,18 @@ int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots
 
 int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms) {
     if (!s || !out || max <= 0) return 0;
-    return s->conn.Poll(out, max, timeout_ms, nullptr, 0);
+    return s->conn.Poll(out, max, timeout_ms, nullptr, 0, nullptr);
 }
 
 int pplsrv_poll_text(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms, char* text_buf, int64_t text_buf_bytes) {
     if (!s || !out || max <= 0) return 0;
-    return s->conn.Poll(out, max, timeout_ms, text_buf, text_buf ? text_buf_bytes : 0);
+    return s->conn.Poll(out, max, timeout_ms, text_buf, text_buf ? text_buf_bytes : 0, nullptr);
+}
+
+int pplsrv_poll_logprobs(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms, char* text_buf, int64_t text_buf_bytes,
+                         pplsrv_top_logprobs* tops) {
+    if (!s || !out || max <= 0) return 0;
+    return s->conn.Poll(out, max, timeout_ms, text_buf, text_buf ? text_buf_bytes : 0, tops);
 }
 
 int pplsrv_cancel(pplsrv* s, uint64_t id) {

@@ -83,6 +83,21 @@ PPLSRV_API int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const i
  * sequence); slots NULL = no adapters, seeds NULL = no seeds. */
 PPLSRV_API int pplsrv_create_ex(const pplsrv_config* cfg, int32_t per_request_sampling, uint64_t sampling_seed, pplsrv** out);
 PPLSRV_API int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, int32_t n);
+/* Top-N logprobs (both structs keep their layout, so a request's count and a response's lists travel beside them).
+ * pplsrv_submit_logprobs is pplsrv_submit_ex with num_logprobs[i] the number of ranked alternatives reqs[i] wants with every generated
+ * token (Request::num_logprobs: above PPLSRV_TOP_LOGPROBS_MAX counts as that, negative as 0; num_logprobs NULL = nobody asks).
+ * pplsrv_poll_logprobs is pplsrv_poll_text (text_buf may be NULL) with tops[i] the lists of out[i]: n entries, best first, entry 0 the
+ * greedy token; n = 0 when the request did not ask. */
+#define PPLSRV_TOP_LOGPROBS_MAX 20
+typedef struct pplsrv_top_logprobs {
+    int32_t n;
+    int32_t tokens[PPLSRV_TOP_LOGPROBS_MAX];
+    float logprobs[PPLSRV_TOP_LOGPROBS_MAX];
+} pplsrv_top_logprobs;
+PPLSRV_API int pplsrv_submit_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                      const int32_t* num_logprobs, int32_t n);
+PPLSRV_API int pplsrv_poll_logprobs(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms, char* text_buf, int64_t text_buf_bytes,
+                                    pplsrv_top_logprobs* tops);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

@@ -31,6 +31,7 @@ struct Request final {
     std::shared_ptr<std::unordered_set<int>> stop_tokens;
     int32_t lora_slot = -1;  // LoRA adapter slot of this request (HipResourceManager::LoadAdapter), -1 = the base model
     uint64_t seed = 0;       // sampling seed (GeneratorConfig::per_request_sampling), 0 = none: the generator gives the request one
+    int32_t num_logprobs = 0;  // ranked alternatives per generated token (Response::top_tokens); above 20: 20, negative: 0
 };
 
 enum class FinishFlag { NOT_FINISHED, LENGTH, EOS_TOKEN, STOP_SEQUENCE };
@@ -42,6 +43,10 @@ struct Response final {
     FinishFlag finish_flag = FinishFlag::NOT_FINISHED;
     float logprob = 0.f;
     bool is_special = false;
+    // the first Request::num_logprobs tokens of the step's ranking and their logprobs (DESIGN.md "numerics", top-N logprobs): empty when
+    // the request did not ask, else min(num_logprobs, vocab_size) entries; entry 0 is the greedy token
+    std::vector<int32_t> top_tokens;
+    std::vector<float> top_logprobs;
 };
 
 struct GeneratorReqCounter final {

@@ -39,6 +39,18 @@ public:
                                             float* /*logprob_host*/) {
         return ppl::common::RC_UNSUPPORTED;
     }
+    // Top-N logprobs of the rows with num_logprobs_host[b] > 0 (0 .. kTopLogprobsMax), on the logits the step's sampler is about to see.
+    // NOT blocking: *tokens / *logprobs point at backend-owned host memory, [*rows, kTopLogprobsMax] each, row j = the j-th asking batch
+    // row, valid once the step's sampler call (SampleTopKTopP / SampleRows) has returned and until the next TopLogprobs.  Entries behind
+    // a row's n are undefined; entries behind the vocabulary are token -1.  The engine calls it only on steps in which a row asks.  A
+    // backend that cannot keeps this default, and the requests that ask are failed.
+    static constexpr int32_t kTopLogprobsMax = 20;
+    virtual ppl::common::RetCode TopLogprobs(const float* /*logits_device*/, const float* /*temperatures_host*/,
+                                             const int32_t* /*num_logprobs_host*/, int32_t /*batch*/, int32_t /*vocab_size*/,
+                                             int32_t /*batch_stride*/, const int32_t** /*tokens*/, const float** /*logprobs*/,
+                                             int32_t* /*rows*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
 };
 
 // one step of one rank: the 11-input contract of src/engine/llm_engine.h:124-138 (attn_mask is never written by the

@@ -124,6 +124,24 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
                 return RC_OTHER_ERROR;
             }
         }
+        // top-N logprobs: queued in front of the sampler, whose synchronisation makes the results readable; nothing on a step nobody asks in
+        const int32_t* top_tok = nullptr;
+        const float* top_lp = nullptr;
+        int32_t top_rows = 0;
+        bool asks = false;
+        for (int32_t n : in.num_logprobs_list) asks = asks || n > 0;
+        if (asks) {
+            rc = post_processor_->TopLogprobs(logits, enable_penalty_ ? nullptr : in.temperatures.data(), in.num_logprobs_list.data(),
+                                              running_batch, model_config_.vocab_size, (int32_t)stride, &top_tok, &top_lp, &top_rows);
+            if (rc == RC_UNSUPPORTED) {
+                out->top_unsupported = true;
+                top_rows = 0;
+            } else if (rc != RC_SUCCESS) {
+                *error_msg = "TopLogprobs failed: " + std::string(GetRetCodeStr(rc));
+                LOG(ERROR) << *error_msg;
+                return RC_OTHER_ERROR;
+            }
+        }
         if (per_request_sampling_) {
             // every row its own parameters and random number (the penalty step has applied the temperatures already)
             rc = post_processor_->SampleRows(logits, enable_penalty_ ? nullptr : in.temperatures.data(), in.top_k_list.data(),
@@ -141,6 +159,12 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
             *error_msg = std::string(per_request_sampling_ ? "SampleRows" : "SampleTopKTopP") + " failed: " + std::string(GetRetCodeStr(rc));
             LOG(ERROR) << *error_msg;
             return RC_OTHER_ERROR;
+        }
+        if (top_rows > 0) {
+            const size_t cnt = (size_t)top_rows * PostProcessor::kTopLogprobsMax;
+            out->top_tokens.assign(top_tok, top_tok + cnt);
+            out->top_logprobs.assign(top_lp, top_lp + cnt);
+            out->top_rows = top_rows;
         }
     }
     step_counter_->global.choose_token_cost += step_counter_->current.choose_token_cost;

@@ -36,14 +36,24 @@ struct ModelInput {
     std::vector<float> frequency_penalty_list;
     std::vector<int64_t> batch_slots;
     std::vector<int32_t> lora_slots;  // adapter slot per request (Request::lora_slot), -1 = none
+    std::vector<int32_t> num_logprobs_list;  // top-N logprobs per request (Request::num_logprobs, clamped to 0 .. 20)
 };
 
 struct ModelOutput {
     std::vector<int32_t> output_token;
     std::vector<float> logprobs;
+    // top-N logprobs, compact: [top_rows, PostProcessor::kTopLogprobsMax] each, row j = the j-th batch row with num_logprobs_list > 0
+    std::vector<int32_t> top_tokens;
+    std::vector<float> top_logprobs;
+    int32_t top_rows = 0;
+    bool top_unsupported = false;  // a row asked and the backend has no TopLogprobs: the generator fails those requests
     void Clear() {
         output_token.clear();
         logprobs.clear();
+        top_tokens.clear();
+        top_logprobs.clear();
+        top_rows = 0;
+        top_unsupported = false;
     }
     void Resize(int32_t n) {
         output_token.resize(n);

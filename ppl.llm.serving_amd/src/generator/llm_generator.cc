@@ -343,6 +343,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     t.slot_index = adm.slot_index;
     t.lora_slot = r.lora_slot;
     t.seed = r.seed ? r.seed : SplitMix64(generator_config_.sampling_seed + ++unseeded_requests_);
+    t.num_logprobs = std::min(std::max(r.num_logprobs, 0), PostProcessor::kTopLogprobsMax);
     if (mode == 0) {
         t.cache_index = (uint64_t)adm.cache_index;
     } else {
@@ -374,6 +375,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     in->frequency_penalty_list.push_back(t.frequency_penalty);
     in->batch_slots.push_back(t.slot_index);
     in->lora_slots.push_back(t.lora_slot);
+    in->num_logprobs_list.push_back(t.num_logprobs);
     if (mode == 0) in->cache_indices.push_back(adm.cache_index);
     else in->max_pages = std::max<int64_t>((int64_t)t.page_list.size(), in->max_pages);
     return true;
@@ -426,6 +428,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
         in->frequency_penalty_list[keep] = in->frequency_penalty_list[i];
         in->batch_slots[keep] = in->batch_slots[i];
         in->lora_slots[keep] = in->lora_slots[i];
+        in->num_logprobs_list[keep] = in->num_logprobs_list[i];
         ++keep;
     }
     tid_list_.resize(keep);
@@ -441,6 +444,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
     in->frequency_penalty_list.resize(keep);
     in->batch_slots.resize(keep);
     in->lora_slots.resize(keep);
+    in->num_logprobs_list.resize(keep);
     LOG(DEBUG) << "Rest tasks: " << keep;
 }
 
@@ -509,6 +513,8 @@ void LLMGenerator::SendTokens(const std::vector<TidGenToken>& tokens) {
         r.finish_flag = g.finish_flag;
         r.logprob = g.logprob;
         r.is_special = g.is_special;
+        r.top_tokens = g.top_tokens;
+        r.top_logprobs = g.top_logprobs;
         if (!g.is_token_in_out && tokenizer_) {
             int tok = g.token;
             tokenizer_->Decode(&tok, 1, &r.generated);
@@ -594,6 +600,7 @@ void LLMGenerator::Generate() {
             decoder_thread_pool_.Wait();  // the previous step's responses are out
             auto tokens = std::make_shared<std::vector<TidGenToken>>();
             tokens->reserve(running_batch);
+            int32_t top_row = 0;  // the place of the next asking row in the compact top-N results
             for (int row = 0; row < running_batch; ++row) {
                 TidData* t = tid_list_[row];
                 ++t->gen_tokens_cnt;
@@ -613,14 +620,30 @@ void LLMGenerator::Generate() {
                 FinishFlag flag = FinishFlag::NOT_FINISHED;
                 const bool hit_stop = t->early_stopping &&
                     (generator_config_.stop_tokens.count(tok) || (t->stop_tokens && t->stop_tokens->count(tok)));
-                if (t->rest_iters <= 0 || hit_stop) {
+                // a request that asks for top-N logprobs on a backend without them fails alone: it leaves like a finished one, unanswered
+                const bool no_top = t->num_logprobs > 0 && out.top_unsupported;
+                if (t->rest_iters <= 0 || hit_stop || no_top) {
                     flag = t->rest_iters <= 0 ? FinishFlag::LENGTH : FinishFlag::EOS_TOKEN;
                     if (cool_down > 0) --cool_down;
                     finished_tasks_.Push(FinishedTaskInfo(t->tid, FinishedTaskInfo::FROM_WORKER));
                     req_list_changed_ = true;
                 }
+                if (no_top) {
+                    conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "num_logprobs: the backend's post processor has no TopLogprobs");
+                    continue;
+                }
                 tokens->push_back(TidGenToken{t->tid, tok, out.logprobs[row], flag, (uint64_t)t->steps, t->is_token_in_out,
-                                              generator_config_.special_tokens.count(tok) > 0});
+                                              generator_config_.special_tokens.count(tok) > 0, {}, {}});
+                if (t->num_logprobs > 0 && top_row < out.top_rows) {
+                    // the row's first n slots; the ones behind the vocabulary (token -1) are padding
+                    const int32_t* tt = out.top_tokens.data() + (size_t)top_row * PostProcessor::kTopLogprobsMax;
+                    const float* tl = out.top_logprobs.data() + (size_t)top_row * PostProcessor::kTopLogprobsMax;
+                    int32_t n = 0;
+                    while (n < t->num_logprobs && tt[n] >= 0) ++n;
+                    tokens->back().top_tokens.assign(tt, tt + n);
+                    tokens->back().top_logprobs.assign(tl, tl + n);
+                    ++top_row;
+                }
             }
             // detokenise + send overlaps the next step (llm_generator.cc:738-745)
             decoder_thread_pool_.RunAsync([this, tokens](uint32_t, uint32_t) { SendTokens(*tokens); });

@@ -35,6 +35,8 @@ struct TidGenToken final {
     uint64_t steps;
     bool is_token_in_out;
     bool is_special;
+    std::vector<int32_t> top_tokens;  // Response::top_tokens / top_logprobs
+    std::vector<float> top_logprobs;
 };
 
 struct FinishedTaskInfo final {
@@ -69,6 +71,7 @@ struct TidData final {
     int64_t cache_hit_count = 0;
     int32_t lora_slot = -1;  // holds a reference in the adapter registry until the request leaves
     uint64_t seed = 0;       // sampling seed: the request's own, or the generator's next one
+    int32_t num_logprobs = 0;  // Request::num_logprobs, clamped to 0 .. PostProcessor::kTopLogprobsMax
 };
 
 struct LlmRequest final : public ppl::common::MPSCQueue::Node {

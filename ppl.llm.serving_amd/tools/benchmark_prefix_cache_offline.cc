@@ -76,6 +76,7 @@ int main(int argc, char** argv) {
         for (int b = 0; b < batch; ++b) {
             auto r = std::make_shared<Request>((uint64_t)(run * batch + b), "", 1.0f, (uint32_t)gen_len);
             r->early_stopping = false;
+            r->num_logprobs = a.Int("--num-logprobs");
             r->token_ids = std::make_shared<std::vector<int>>(*prompts[b]);
             reqs.push_back(r);
         }

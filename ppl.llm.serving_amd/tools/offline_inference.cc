@@ -114,6 +114,9 @@ int main(int argc, char** argv) {
         return -1;
     }
 
+    if (workload != "scenario")
+        for (auto& r : requests) r->num_logprobs = a.Int("--num-logprobs");
+
     // ---- LoRA adapters: slot = position in --lora-dirs; --lora-map cycled over the requests ---------------------
     {
         std::vector<std::string> dirs;
@@ -179,17 +182,32 @@ int main(int argc, char** argv) {
             std::cout << "\nAnswer tokens:";
             for (int t : conn.records()[r->id].tokens) std::cout << " " << t;
             std::cout << "\n";
+            if (r->num_logprobs > 0) {   // per answer token: its alternatives, best first, as token:logprob
+                std::cout << "Answer top logprobs:";
+                const auto& rec = conn.records()[r->id];
+                for (size_t i = 0; i < rec.top_tokens.size(); ++i) {
+                    std::cout << (i ? " |" : "");
+                    for (size_t j = 0; j < rec.top_tokens[i].size(); ++j) std::cout << " " << rec.top_tokens[i][j] << ":" << rec.top_logprobs[i][j];
+                }
+                std::cout << "\n";
+            }
         }
         std::cout << "generation time: " << generate_us / 1e3 << "ms" << std::endl;
     } else if (workload == "scenario") {
         std::map<uint64_t, std::vector<int>> tokens;
+        std::map<uint64_t, std::vector<std::vector<int32_t>>> top_tokens;
+        std::map<uint64_t, std::vector<std::vector<float>>> top_logprobs;
         std::vector<uint64_t> failed;
         for (auto& r : requests) {
             auto& rec = conn.records()[r->id];
             if (rec.failed) failed.push_back(r->id);
             else tokens[r->id] = rec.tokens;
+            if (!rec.failed && r->num_logprobs > 0) {
+                top_tokens[r->id] = rec.top_tokens;
+                top_logprobs[r->id] = rec.top_logprobs;
+            }
         }
-        scenario::PrintScenarioResult(tokens, failed);
+        scenario::PrintScenarioResult(tokens, failed, top_tokens, top_logprobs);
     } else {
         std::vector<double> ttft, tpot;
         uint64_t out_tokens = 0, in_tokens = 0, failed = 0;

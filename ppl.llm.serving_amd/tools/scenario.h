@@ -4,8 +4,9 @@
 //                  "enable_penalty", "stop_tokens": [..]},
 //    "kv_cache_max_tokens": N,
 //    "requests": [{"id", "tokens": [..], "generation_length", "temperature", "top_p", "top_k", "repetition_penalty",
-//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed"}]}
+//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed", "num_logprobs"}]}
 // "seed" (this tree's Request only: the sampling seed of --per-request-sampling, 0 or absent = none) is ignored for a request type without it.
+// "num_logprobs" (this tree's Request only: ranked alternatives per generated token, 0 .. 20, 0 or absent = none) likewise.
 // Templates: Request / GeneratorConfig are this tree's or the reference's types (same member names by construction).
 #pragma once
 #include <fstream>
@@ -47,6 +48,11 @@ template <typename RequestT>
 void SetSeed(RequestT*, uint64_t, long) {}
 
 template <typename RequestT>
+auto SetNumLogprobs(RequestT* q, int32_t n, int) -> decltype(q->num_logprobs = n, void()) { q->num_logprobs = n; }
+template <typename RequestT>
+void SetNumLogprobs(RequestT*, int32_t, long) {}
+
+template <typename RequestT>
 std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& doc, int vocab_size) {
     std::vector<std::shared_ptr<RequestT>> out;
     for (const auto& r : doc.Find("requests")->arr) {
@@ -59,6 +65,7 @@ std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& 
         q->frequency_penalty = (float)r.GetNum("frequency_penalty", 0.0);
         q->early_stopping = r.GetBool("early_stopping", true);
         SetSeed(q.get(), (uint64_t)r.GetInt("seed", 0), 0);
+        SetNumLogprobs(q.get(), (int32_t)r.GetInt("num_logprobs", 0), 0);
         q->token_ids = std::make_shared<std::vector<int>>();
         if (const utils::JsonValue* t = r.Find("tokens"))
             for (const auto& v : t->arr) q->token_ids->push_back((int)(v.AsInt() % vocab_size));
@@ -70,9 +77,8 @@ std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& 
     return out;
 }
 
-// {"tokens": {"id": [..]}, "failed": [ids]}
 template <typename TokMap, typename FailedVec>
-void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed) {
+void PrintScenarioBody(const TokMap& tokens, const FailedVec& failed) {
     std::cout << "{\"tokens\":{";
     bool first = true;
     for (const auto& kv : tokens) {
@@ -83,7 +89,48 @@ void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed) {
     }
     std::cout << "},\"failed\":[";
     for (size_t i = 0; i < failed.size(); ++i) std::cout << (i ? "," : "") << failed[i];
-    std::cout << "]}" << std::endl;
+    std::cout << "]";
+}
+
+// {"tokens": {"id": [..]}, "failed": [ids]}
+template <typename TokMap, typename FailedVec>
+void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed) {
+    PrintScenarioBody(tokens, failed);
+    std::cout << "}" << std::endl;
+}
+
+// the same, plus "top_tokens" / "top_logprobs": {"id": [[..] per generated token]} of the requests that asked (TopMap: id -> per-token
+// lists); without such a request the line is PrintScenarioResult's
+template <typename TokMap, typename FailedVec, typename TopTokMap, typename TopLpMap>
+void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed, const TopTokMap& top_tokens, const TopLpMap& top_logprobs) {
+    PrintScenarioBody(tokens, failed);
+    auto lists = [](const char* key, const auto& m) {
+        std::cout << ",\"" << key << "\":{";
+        bool first = true;
+        for (const auto& kv : m) {
+            std::cout << (first ? "" : ",") << "\"" << kv.first << "\":[";
+            for (size_t i = 0; i < kv.second.size(); ++i) {
+                std::cout << (i ? "," : "") << "[";
+                for (size_t j = 0; j < kv.second[i].size(); ++j) {
+                    if (j) std::cout << ",";
+                    // (JSON has no infinity: a masked entry's logprob goes out as the lowest float)
+                    if (kv.second[i][j] < -3.0e38) std::cout << "-3.4028235e38";
+                    else std::cout << kv.second[i][j];
+                }
+                std::cout << "]";
+            }
+            std::cout << "]";
+            first = false;
+        }
+        std::cout << "}";
+    };
+    if (!top_tokens.empty()) {
+        const auto prec = std::cout.precision(9);
+        lists("top_tokens", top_tokens);
+        lists("top_logprobs", top_logprobs);
+        std::cout.precision(prec);
+    }
+    std::cout << "}" << std::endl;
 }
 
 }}}  // namespace ppl::llm::scenario

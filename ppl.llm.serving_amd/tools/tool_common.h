@@ -61,6 +61,7 @@ inline void DefineCommonFlags(Args* a) {
     a->Def("--kv-cache-max-tokens", "0", "pin the KV slab size in tokens (0: max-tokens-scale x free memory)");
     a->Def("--seed", "1234", "workload seed");
     a->Def("--per-request-sampling", "false", "sample every request with its own top_k / top_p / temperature and its own seeded random sequence (off: the first row's top_k for the whole batch and rand(), as the reference)", true);
+    a->Def("--num-logprobs", "0", "ranked alternatives per generated token (top-N logprobs, 0 .. 20) asked for by every request of a generated workload");
     a->Def("--sampling-seed", "0", "with --per-request-sampling: the n-th request without a seed of its own gets splitmix64(this + n); 0: taken from std::random_device");
 }
 
@@ -122,6 +123,8 @@ class LocalConnection final : public ppl::llm::Connection {
 public:
     struct Rec {
         std::vector<int> tokens;
+        std::vector<std::vector<int32_t>> top_tokens;   // per generated token: Response::top_tokens / top_logprobs (empty: not asked)
+        std::vector<std::vector<float>> top_logprobs;
         std::string text;
         Clock::time_point submit, first, last;
         bool finished = false, failed = false;
@@ -139,6 +142,8 @@ public:
             Rec& rec = recs_[r.id];
             if (rec.tokens.empty()) rec.first = now;
             rec.tokens.push_back(r.token);
+            rec.top_tokens.push_back(r.top_tokens);
+            rec.top_logprobs.push_back(r.top_logprobs);
             rec.text += r.generated;   // text requests: the detokenised piece(s) of this response
             rec.last = now;
             if (r.finish_flag != ppl::llm::FinishFlag::NOT_FINISHED) {
