@@ -357,6 +357,46 @@ typedef struct pplhip_top_logprobs_args {
 PPLHIP_API int pplhip_top_logprobs(pplhip_ctx* ctx, const float* logits_device, const pplhip_top_logprobs_args* args,
                                    const int32_t** tokens_out, const float** logprobs_out, int32_t* rows_out);
 
+/* Logit rules (DESIGN.md "numerics", logit rules row): what a request may produce.  A batch slot (the batch_slots of pplhip_penalty_args)
+ * holds one rule, fixed while its request lives: up to PPLHIP_LOGIT_BIAS_MAX pairs (token, bias value; -inf bans the token), an optional
+ * mask of allowed tokens (token v is bit v & 31 of word v >> 5; bits at or behind vocab_size mean nothing) and up to
+ * PPLHIP_LOGIT_STOP_MAX stop tokens that a row can have suppressed.  The edit of a row with flags f, in place, x the logit as written:
+ *   y = -inf              if (f & 1) and allowed_bits is given and v's bit is clear
+ *     = -inf              else if (f & 2) and v is in stop_tokens
+ *     = fp32(x + bias)    else if (f & 1) and v is in bias_tokens
+ *     = x, bit for bit    otherwise;  f == 0: the row is not touched.
+ * All pointers of pplhip_logit_rule are HOST memory and are read before pplhip_logit_rule_set returns.
+ * pplhip_logit_rule_set validates (PPLHIP_INVALID_VALUE with the reason in pplhip_last_error, nothing changed: slot outside
+ * [0, max_running_batch), a count above its maximum or negative, a token outside [0, vocab_size), a bias value that is NaN or +inf, a
+ * token with two bias entries, and a rule that leaves no token alive: allowed (or all) minus banned minus stop_tokens is empty -- pass the
+ * stops only for a request that will have them suppressed), stages the record in pinned memory and queues its copy to the slot on local
+ * rank 0's stream, in front of every later pplhip_logit_edit; any number of calls may follow one another without a synchronisation.
+ * The table (max_running_batch records) is allocated on the first call, so a context that never sets a rule allocates nothing.
+ * A slot's record stays until the next pplhip_logit_rule_set of that slot; it is read only by rows that ask with that slot.
+ * pplhip_logit_edit: batch_slots and flags are host [batch]; one upload and one launch over the rows with flags != 0 are queued on local
+ * rank 0's stream, with no synchronisation of the device work; all flags 0 is no device call at all.  Call it in front of pplhip_penalty:
+ * a bias is in raw-logit units, and the penalty, pplhip_top_logprobs and the samplers then all see the edited row.  A flag above 3, a slot
+ * outside the table or without a rule in a row that asks, vocab_size other than the model's, batch outside [0, max_running_batch] or
+ * batch_stride < vocab_size: PPLHIP_INVALID_VALUE before any device call.  Acts on local rank 0's logits at any tensor-parallel degree.
+ * Arrived without a version bump: a client tells a library that has it by the symbol pplhip_logit_edit (dlsym). */
+#define PPLHIP_LOGIT_BIAS_MAX 512
+#define PPLHIP_LOGIT_STOP_MAX 64
+typedef struct pplhip_logit_rule {
+    const int32_t* bias_tokens;   /* [n_bias], unique */
+    const float* bias_values;     /* [n_bias], finite or -inf */
+    int32_t n_bias;
+    const uint32_t* allowed_bits; /* NULL (every token allowed) or ceil(vocab_size / 32) words */
+    const int32_t* stop_tokens;   /* [n_stop] */
+    int32_t n_stop;
+} pplhip_logit_rule;
+typedef struct pplhip_logit_edit_args {
+    const int64_t* batch_slots;   /* host [B] */
+    const uint32_t* flags;        /* host [B]: bit 0 apply mask and bias, bit 1 suppress the stops */
+    int32_t batch, vocab_size, batch_stride;
+} pplhip_logit_edit_args;
+PPLHIP_API int pplhip_logit_rule_set(pplhip_ctx* ctx, int32_t slot, const pplhip_logit_rule* rule);
+PPLHIP_API int pplhip_logit_edit(pplhip_ctx* ctx, float* logits_device, const pplhip_logit_edit_args* args);
+
 /* in-place penalty on the logits of the last run, using the step's device-resident token_inputs /
  * seq_starts / start_pos (llm_engine.cc:204-216). */
 PPLHIP_API int pplhip_penalty(pplhip_ctx* ctx, float* logits_device, const pplhip_penalty_args* args);
@@ -540,6 +580,16 @@ PPLHIP_API int pplhip_op_sample_rows(void* stream, const float* logits, const fl
  * host from a read-back of num_logprobs, so the call synchronises `stream` before it launches; no asking row: no launch. */
 PPLHIP_API int pplhip_op_top_logprobs(void* stream, const float* logits, const float* temperatures, const int32_t* num_logprobs,
                                       int32_t batch, int32_t vocab, int32_t stride, int32_t* out_tok, float* out_logprob);
+/* the logit rules kernel alone (csrc/k_logit_rules.hip), for the tests: caller-owned DEVICE memory only.  flags / slots are [batch], indexed
+ * by the batch row; the table is five arrays indexed by slot: head [slots, 4] = {n_bias, n_stop, has_mask, 0}, bias_tokens / bias_values
+ * [slots, PPLHIP_LOGIT_BIAS_MAX], stop_tokens [slots, PPLHIP_LOGIT_STOP_MAX], mask [slots, ceil(vocab / 32)].  Nothing is validated
+ * but the shape (batch < 0, vocab <= 0, stride < vocab, a NULL array: PPLHIP_INVALID_VALUE, nothing launched): the kernel skips a token
+ * outside [0, vocab) and clamps the counts.  rows NULL: the list of the rows with flags != 0 is made on the host from a read-back of
+ * flags, so the call synchronises `stream` before it launches.  rows != NULL: a device list of n_rows asking rows, launched as it is
+ * with no host round trip (the product's path; the timing script's).  No asking row: no launch. */
+PPLHIP_API int pplhip_op_logit_edit(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const uint32_t* flags,
+                                    const int32_t* slots, const int32_t* head, const int32_t* bias_tokens, const float* bias_values,
+                                    const int32_t* stop_tokens, const uint32_t* mask, const int32_t* rows, int32_t n_rows);
 /* out_u[b] = u(seeds[b], draws[b]), the generator alone (device pointers) */
 PPLHIP_API int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u);
 

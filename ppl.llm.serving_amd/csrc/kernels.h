@@ -260,6 +260,25 @@ constexpr int TOP_LOGPROBS_MAX = 20;   // slots per asked row (PPLHIP_TOP_LOGPRO
 hipError_t launch_top_logprobs(hipStream_t s, const float* logits, const float* temperatures, const int32_t* num_logprobs,
                                const int32_t* rows, int n_rows, int vocab, int stride, int32_t* out_tok, float* out_logprob);
 
+// ---- k_logit_rules.hip: per-request logit rules ------------------------------------------------------
+// The rule table, one record per batch slot, as five device arrays with their own strides (in elements) from one slot to the next:
+// head [slot] = {n_bias, n_stop, has_mask, 0}; bias_tok / bias_val [slot, <= 512]; stops [slot, <= 64]; mask [slot, ceil(V / 32)] with
+// token v at bit v & 31 of word v >> 5.
+constexpr int LOGIT_BIAS_MAX = 512;   // PPLHIP_LOGIT_BIAS_MAX
+constexpr int LOGIT_STOP_MAX = 64;    // PPLHIP_LOGIT_STOP_MAX
+struct LogitRuleTable {
+    const int32_t* head;
+    const int32_t* bias_tok;
+    const float* bias_val;
+    const int32_t* stops;
+    const uint32_t* mask;
+    int64_t head_stride, bias_stride, stop_stride, mask_stride;
+};
+// rows: device list of the n_rows batch rows with flags[b] != 0; slots and flags (bit 0: mask and bias, bit 1: suppress the stops) are
+// indexed by the batch row.  Edits logits[b * stride + 0 .. vocab) of the listed rows in place.  No rows: no launch.
+hipError_t launch_logit_edit(hipStream_t s, float* logits, int stride, int vocab, const int32_t* rows, int n_rows, const int32_t* slots,
+                             const uint32_t* flags, const LogitRuleTable& table);
+
 // ---- synth.hip --------------------------------------------------------------------------------
 // kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm; and for the fp8 KV
 // slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales; for the int4 KV slab: 7 nibble pairs 1..15, 8 scales of its rule

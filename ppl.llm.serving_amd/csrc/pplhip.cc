@@ -101,6 +101,14 @@ constexpr int64_t SROWS_BYTES = 8 + 8 + 4 + 4 + 4 + 4;
 constexpr int64_t TLP_IN_BYTES = 4 + 4 + 4;
 constexpr int64_t TLP_OUT_BYTES = (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
 static_assert(PPLHIP_TOP_LOGPROBS_MAX == TOP_LOGPROBS_MAX, "header and kernel disagree");
+// logit rules: a slot's record in the device table and in the pinned staging ring is
+// head i32 [4] = {n_bias, n_stop, has_mask, 0} | bias tokens i32 [512] | bias values f32 [512] | stops i32 [64] | mask u32 [words, padded to 4]
+// so one copy carries a rule.  pplhip_logit_edit stages slots i32 [cap_B] | flags u32 [cap_B] | row list i32 [cap_B] in a block of its own.
+static_assert(PPLHIP_LOGIT_BIAS_MAX == LOGIT_BIAS_MAX && PPLHIP_LOGIT_STOP_MAX == LOGIT_STOP_MAX, "header and kernel disagree");
+constexpr int64_t LR_HEAD = 16, LR_BIAS_TOK = LR_HEAD, LR_BIAS_VAL = LR_BIAS_TOK + 4 * LOGIT_BIAS_MAX,
+                  LR_STOPS = LR_BIAS_VAL + 4 * LOGIT_BIAS_MAX, LR_MASK = LR_STOPS + 4 * LOGIT_STOP_MAX;
+constexpr int LR_RING = 4;   // staging records; a record is reused once the event behind its copy has passed
+constexpr int64_t LRE_BYTES = 4 + 4 + 4;
 
 struct Rank {
     int device = 0;
@@ -168,6 +176,15 @@ struct Rank {
     char *h_srows = nullptr, *d_srows = nullptr;  // pplhip_sample_rows: pinned staging and its device image, SROWS_BYTES per batch row
     char *h_tlp_in = nullptr, *d_tlp_in = nullptr;    // pplhip_top_logprobs: TLP_IN_BYTES per batch row going up ...
     char *h_tlp_out = nullptr, *d_tlp_out = nullptr;  // ... TLP_OUT_BYTES per batch row coming down
+    // logit rules, all allocated by the first pplhip_logit_rule_set: the device table (cap_B records of lr_rec bytes), the pinned
+    // staging ring with one event per record, which slots hold a rule, and pplhip_logit_edit's staging block with the event of its copy
+    char *lr_table = nullptr, *lr_stage = nullptr;
+    int64_t lr_rec = 0;
+    hipEvent_t lr_ev[LR_RING] = {};
+    int lr_next = 0;
+    std::vector<uint8_t> lr_has;
+    char *h_lre = nullptr, *d_lre = nullptr;
+    hipEvent_t lre_ev = nullptr;
 
     // exchange region of the direct collectives (k_comm.hip): fine-grained, peer-mapped; holds the flag words and the buffers
     // the collectives work in place on (part, part2) or push into (logits_gather)
@@ -748,6 +765,10 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.h_srows) hipHostFree(R.h_srows);
         if (R.h_tlp_in) hipHostFree(R.h_tlp_in);
         if (R.h_tlp_out) hipHostFree(R.h_tlp_out);
+        if (R.lr_stage) hipHostFree(R.lr_stage);
+        if (R.h_lre) hipHostFree(R.h_lre);
+        for (hipEvent_t e : R.lr_ev) if (e) hipEventDestroy(e);
+        if (R.lre_ev) hipEventDestroy(R.lre_ev);
         if (R.stream) hipStreamDestroy(R.stream);
     }
     delete c;
@@ -2471,6 +2492,119 @@ int pplhip_top_logprobs(pplhip_ctx* c, const float* logits_device, const pplhip_
     return 0;   // asynchronous: the step's sampler call (or pplhip_sync) is the synchronisation
 }
 
+// the first rule of a context: the table, the staging ring and the edit's staging block
+static int logit_rules_alloc(pplhip_ctx* c) {
+    Rank& R = c->ranks[0];
+    const int64_t words = ((int64_t)c->d.vocab_size + 31) / 32;
+    const int64_t rec = LR_MASK + (words + 3) / 4 * 16;
+    int rc;
+    char *table = nullptr, *d_lre = nullptr;
+    if ((rc = dev_alloc(c, 0, (void**)&table, (uint64_t)R.cap_B * rec))) return rc;
+    if ((rc = dev_alloc(c, 0, (void**)&d_lre, (uint64_t)R.cap_B * LRE_BYTES))) return rc;
+    if (!R.lr_stage) HIPCK(c, 0, hipHostMalloc((void**)&R.lr_stage, (size_t)(LR_RING * rec), hipHostMallocDefault));
+    if (!R.h_lre) HIPCK(c, 0, hipHostMalloc((void**)&R.h_lre, (size_t)(R.cap_B * LRE_BYTES), hipHostMallocDefault));
+    for (int i = 0; i < LR_RING; ++i)
+        if (!R.lr_ev[i]) HIPCK(c, 0, hipEventCreateWithFlags(&R.lr_ev[i], hipEventDisableTiming));
+    if (!R.lre_ev) HIPCK(c, 0, hipEventCreateWithFlags(&R.lre_ev, hipEventDisableTiming));
+    R.lr_has.assign((size_t)R.cap_B, 0);
+    R.d_lre = d_lre;
+    R.lr_rec = rec;
+    R.lr_table = table;   // last: the table counts as there only when everything is
+    return 0;
+}
+
+int pplhip_logit_rule_set(pplhip_ctx* c, int32_t slot, const pplhip_logit_rule* r) {
+    if (!c || !r) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    const int V = c->d.vocab_size;
+    const int64_t words = ((int64_t)V + 31) / 32;
+    if (slot < 0 || slot >= R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: slot outside [0, max_running_batch)");
+    if (r->n_bias < 0 || r->n_bias > PPLHIP_LOGIT_BIAS_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: n_bias outside [0, PPLHIP_LOGIT_BIAS_MAX]");
+    if (r->n_stop < 0 || r->n_stop > PPLHIP_LOGIT_STOP_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: n_stop outside [0, PPLHIP_LOGIT_STOP_MAX]");
+    if ((r->n_bias > 0 && (!r->bias_tokens || !r->bias_values)) || (r->n_stop > 0 && !r->stop_tokens))
+        return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: a count without its array");
+    // dead[v]: the token cannot be produced; seen[v]: it has a bias entry
+    std::vector<uint8_t> dead((size_t)V, 0), seen((size_t)V, 0);
+    for (int i = 0; i < r->n_bias; ++i) {
+        const int32_t t = r->bias_tokens[i];
+        const float v = r->bias_values[i];
+        if (t < 0 || t >= V) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: bias_tokens[" + std::to_string(i) + "] outside [0, vocab_size)");
+        if (v != v || v == INFINITY) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: bias_values[" + std::to_string(i) + "] is NaN or +inf");
+        if (seen[t]) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: bias_tokens[" + std::to_string(i) + "] has an entry already");
+        seen[t] = 1;
+        if (v == -INFINITY) dead[t] = 1;
+    }
+    for (int i = 0; i < r->n_stop; ++i) {
+        const int32_t t = r->stop_tokens[i];
+        if (t < 0 || t >= V) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: stop_tokens[" + std::to_string(i) + "] outside [0, vocab_size)");
+        dead[t] = 1;
+    }
+    bool alive = false;
+    for (int v = 0; v < V && !alive; ++v)
+        alive = !dead[v] && (!r->allowed_bits || ((r->allowed_bits[v >> 5] >> (v & 31)) & 1u));
+    if (!alive) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: allowed_bits minus the banned and stop tokens leaves no token");
+    HIPCK(c, 0, hipSetDevice(R.device));
+    if (!R.lr_table)
+        if (int rc = logit_rules_alloc(c)) return rc;
+    const int k = R.lr_next;
+    HIPCK(c, 0, hipEventSynchronize(R.lr_ev[k]));   // the copy that last used this staging record (a fresh event has passed)
+    char* h = R.lr_stage + (int64_t)k * R.lr_rec;
+    int32_t* head = (int32_t*)h;
+    head[0] = r->n_bias; head[1] = r->n_stop; head[2] = r->allowed_bits ? 1 : 0; head[3] = 0;
+    if (r->n_bias) {
+        memcpy(h + LR_BIAS_TOK, r->bias_tokens, (size_t)r->n_bias * 4);
+        memcpy(h + LR_BIAS_VAL, r->bias_values, (size_t)r->n_bias * 4);
+    }
+    if (r->n_stop) memcpy(h + LR_STOPS, r->stop_tokens, (size_t)r->n_stop * 4);
+    if (r->allowed_bits) memcpy(h + LR_MASK, r->allowed_bits, (size_t)words * 4);
+    // (the parts behind the counts, and the mask of a rule without one, go up as the ring holds them: the kernel reads none of it)
+    HIPCK(c, 0, hipMemcpyAsync(R.lr_table + (int64_t)slot * R.lr_rec, h, (size_t)R.lr_rec, hipMemcpyHostToDevice, R.stream));
+    HIPCK(c, 0, hipEventRecord(R.lr_ev[k], R.stream));
+    R.lr_next = (k + 1) % LR_RING;
+    R.lr_has[slot] = 1;
+    return 0;
+}
+
+int pplhip_logit_edit(pplhip_ctx* c, float* logits_device, const pplhip_logit_edit_args* a) {
+    if (!c || !a || !logits_device || !a->batch_slots || !a->flags) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    const int B = a->batch;
+    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
+    if (a->vocab_size != c->d.vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit edit: vocab_size is not the model's");
+    if (a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
+    int asked = 0;
+    for (int i = 0; i < B; ++i) {
+        if (a->flags[i] > 3u) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit edit: flags above 3");
+        if (!a->flags[i]) continue;
+        const int64_t slot = a->batch_slots[i];
+        if (slot < 0 || slot >= R.cap_B || !R.lr_table || !R.lr_has[slot])
+            return fail(c, 0, PPLHIP_INVALID_VALUE, "logit edit: row " + std::to_string(i) + " asks with a slot that holds no rule");
+        ++asked;
+    }
+    if (asked == 0) return 0;   // nobody asks: no HIP call
+    HIPCK(c, 0, hipSetDevice(R.device));
+    HIPCK(c, 0, hipEventSynchronize(R.lre_ev));   // the previous call's upload has left the staging block
+    const int64_t cap = R.cap_B;
+    int32_t* h_slots = (int32_t*)R.h_lre;
+    uint32_t* h_flags = (uint32_t*)(R.h_lre + 4 * cap);
+    int32_t* h_rows = (int32_t*)(R.h_lre + 8 * cap);
+    int n = 0;
+    for (int i = 0; i < B; ++i) {
+        h_slots[i] = a->flags[i] ? (int32_t)a->batch_slots[i] : 0;
+        h_flags[i] = a->flags[i];
+        if (a->flags[i]) h_rows[n++] = i;
+    }
+    hipStream_t s = R.stream;
+    HIPCK(c, 0, hipMemcpyAsync(R.d_lre, R.h_lre, (size_t)(8 * cap + 4 * (int64_t)asked), hipMemcpyHostToDevice, s));
+    HIPCK(c, 0, hipEventRecord(R.lre_ev, s));
+    const int64_t rw = R.lr_rec / 4;
+    const LogitRuleTable tb{(const int32_t*)R.lr_table, (const int32_t*)(R.lr_table + LR_BIAS_TOK), (const float*)(R.lr_table + LR_BIAS_VAL),
+                            (const int32_t*)(R.lr_table + LR_STOPS), (const uint32_t*)(R.lr_table + LR_MASK), rw, rw, rw, rw};
+    HIPCK(c, 0, launch_logit_edit(s, logits_device, a->batch_stride, a->vocab_size, (const int32_t*)(R.d_lre + 8 * cap), asked,
+                                  (const int32_t*)R.d_lre, (const uint32_t*)(R.d_lre + 4 * cap), tb));
+    return 0;   // asynchronous: in stream order in front of the step's penalty, top-N logprobs and sampler
+}
+
 int pplhip_penalty(pplhip_ctx* c, float* logits_device, const pplhip_penalty_args* a) {
     if (!c || !a || !logits_device) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[0];
@@ -2748,6 +2882,33 @@ int pplhip_op_top_logprobs(void* stream, const float* logits, const float* tempe
     e = hipMemcpyAsync(d_rows, rows.data(), (size_t)asked * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call
     if (e == hipSuccess) e = launch_top_logprobs(s, logits, temperatures, num_logprobs, d_rows, asked, vocab, stride, out_tok, out_logprob);
+    const hipError_t e2 = hipFreeAsync(d_rows, s);
+    return op_rc(e != hipSuccess ? e : e2);
+}
+
+// logit_edit_kernel alone on caller-owned memory; without `rows` the list is made here from a read-back of flags
+int pplhip_op_logit_edit(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const uint32_t* flags, const int32_t* slots,
+                         const int32_t* head, const int32_t* bias_tokens, const float* bias_values, const int32_t* stop_tokens,
+                         const uint32_t* mask, const int32_t* rows, int32_t n_rows) {
+    if (batch < 0 || vocab <= 0 || stride < vocab || n_rows < 0 || n_rows > batch) return PPLHIP_INVALID_VALUE;
+    if (batch == 0) return 0;
+    if (!logits || !flags || !slots || !head || !bias_tokens || !bias_values || !stop_tokens || !mask) return PPLHIP_INVALID_VALUE;
+    hipStream_t s = (hipStream_t)stream;
+    const LogitRuleTable tb{head, bias_tokens, bias_values, stop_tokens, mask, 4, LOGIT_BIAS_MAX, LOGIT_STOP_MAX, ((int64_t)vocab + 31) / 32};
+    if (rows) return op_rc(launch_logit_edit(s, logits, stride, vocab, rows, n_rows, slots, flags, tb));
+    std::vector<uint32_t> f(batch);
+    std::vector<int32_t> list;
+    hipError_t e = hipMemcpyAsync(f.data(), flags, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    for (int i = 0; i < batch; ++i)
+        if (f[i]) list.push_back(i);
+    if (list.empty()) return 0;
+    int32_t* d_rows = nullptr;
+    if ((e = hipMallocAsync((void**)&d_rows, list.size() * 4, s)) != hipSuccess) return op_rc(e);
+    e = hipMemcpyAsync(d_rows, list.data(), list.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `list` is pageable and dies with this call
+    if (e == hipSuccess) e = launch_logit_edit(s, logits, stride, vocab, d_rows, (int)list.size(), slots, flags, tb);
     const hipError_t e2 = hipFreeAsync(d_rows, s);
     return op_rc(e != hipSuccess ? e : e2);
 }

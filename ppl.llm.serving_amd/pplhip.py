@@ -75,6 +75,20 @@ class TopLogprobsArgs(C.Structure):
                 ("batch_stride", C.c_int32)]
 
 
+LOGIT_BIAS_MAX = 512   # PPLHIP_LOGIT_BIAS_MAX
+LOGIT_STOP_MAX = 64    # PPLHIP_LOGIT_STOP_MAX
+
+
+class LogitRule(C.Structure):
+    _fields_ = [("bias_tokens", C.c_void_p), ("bias_values", C.c_void_p), ("n_bias", C.c_int32), ("allowed_bits", C.c_void_p),
+                ("stop_tokens", C.c_void_p), ("n_stop", C.c_int32)]
+
+
+class LogitEditArgs(C.Structure):
+    _fields_ = [("batch_slots", C.c_void_p), ("flags", C.c_void_p), ("batch", C.c_int32), ("vocab_size", C.c_int32),
+                ("batch_stride", C.c_int32)]
+
+
 class PenaltyArgs(C.Structure):
     _fields_ = [("temperatures", C.c_void_p), ("repetition_penalties", C.c_void_p), ("presence_penalties", C.c_void_p),
                 ("frequency_penalties", C.c_void_p), ("batch_slots", C.c_void_p), ("batch", C.c_int32),
@@ -131,10 +145,10 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
-    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
+    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_logit_edit", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -221,6 +235,10 @@ def lib():
         if hasattr(L, "pplhip_top_logprobs"):
             L.pplhip_top_logprobs.argtypes = [vp, vp, C.POINTER(TopLogprobsArgs), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
             L.pplhip_op_top_logprobs.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+        if hasattr(L, "pplhip_logit_edit"):
+            L.pplhip_logit_rule_set.argtypes = [vp, i32, C.POINTER(LogitRule)]
+            L.pplhip_logit_edit.argtypes = [vp, vp, C.POINTER(LogitEditArgs)]
+            L.pplhip_op_logit_edit.argtypes = [vp, vp, i32, i32, i32] + [vp] * 8 + [i32]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
@@ -580,6 +598,37 @@ class Context:
             return tok, lp
         read.rows = asked
         return read
+
+    def logit_rule_set(self, slot, bias=(), allowed_bits=None, stops=(), check=True):
+        """one slot's rule: bias = pairs (token, value), allowed_bits = None or uint32 [ceil(V / 32)], stops = tokens.  Returns the status
+        (raises on failure unless check is False)."""
+        r = LogitRule()
+        bt = np.ascontiguousarray([t for t, _ in bias], dtype=np.int32)
+        bv = np.ascontiguousarray([v for _, v in bias], dtype=np.float32)
+        st = np.ascontiguousarray(list(stops), dtype=np.int32)
+        ab = None if allowed_bits is None else np.ascontiguousarray(allowed_bits, dtype=np.uint32)
+        r.bias_tokens, r.bias_values, r.n_bias = bt.ctypes.data, bv.ctypes.data, len(bt)
+        r.allowed_bits = None if ab is None else ab.ctypes.data
+        r.stop_tokens, r.n_stop = st.ctypes.data, len(st)
+        rc = lib().pplhip_logit_rule_set(self.h, int(slot), C.byref(r))
+        if check:
+            self._ck(rc, 0, "logit_rule_set")
+        return rc
+
+    def logit_edit(self, batch_slots, flags, logits_ptr=None, check=True):
+        """queues the in-place edit of the last run's logits (rank 0) for the rows with flags != 0; asynchronous."""
+        a = LogitEditArgs()
+        sl = np.ascontiguousarray(batch_slots, dtype=np.int64)
+        fl = np.ascontiguousarray(flags, dtype=np.uint32)
+        assert len(sl) == len(fl)
+        a.batch_slots, a.flags = sl.ctypes.data, fl.ctypes.data
+        a.batch, a.vocab_size, a.batch_stride = len(fl), self.desc.vocab_size, self.desc.vocab_size
+        if logits_ptr is None:
+            logits_ptr = self.logits_ptr(0)[0]
+        rc = lib().pplhip_logit_edit(self.h, logits_ptr, C.byref(a))
+        if check:
+            self._ck(rc, 0, "logit_edit")
+        return rc
 
     def penalty(self, temperatures, repetition, presence, frequency, batch_slots, req_list_changed=True):
         a = PenaltyArgs()

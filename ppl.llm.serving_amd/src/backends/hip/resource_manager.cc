@@ -105,6 +105,39 @@ RetCode HipPostProcessor::TopLogprobs(const float* logits_device, const float* t
     return FromPplHipStatus(st);
 }
 
+static_assert(PostProcessor::kLogitBiasMax == PPLHIP_LOGIT_BIAS_MAX && PostProcessor::kLogitStopMax == PPLHIP_LOGIT_STOP_MAX,
+              "interface and library disagree");
+
+RetCode HipPostProcessor::SetLogitRule(int64_t slot, const LogitRule& rule) {
+    pplhip_logit_rule r;
+    memset(&r, 0, sizeof(r));
+    r.bias_tokens = rule.bias_tokens.data();
+    r.bias_values = rule.bias_values.data();
+    r.n_bias = (int32_t)rule.bias_tokens.size();
+    r.allowed_bits = rule.has_mask ? rule.allowed_bits.data() : nullptr;
+    r.stop_tokens = rule.stop_tokens.data();
+    r.n_stop = (int32_t)rule.stop_tokens.size();
+    if (slot < 0 || slot > INT32_MAX) return RC_INVALID_VALUE;
+    const int st = pplhip_logit_rule_set(ctx_, (int32_t)slot, &r);
+    if (st) LOG(ERROR) << "logit rule of slot " << slot << " refused: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
+RetCode HipPostProcessor::EditLogits(float* logits_device, const int64_t* batch_slots_host, const uint32_t* flags_host, int32_t batch,
+                                     int32_t vocab_size, int32_t batch_stride) {
+    if (batch == 0) return RC_SUCCESS;   // the generator's question whether logit rules are served
+    pplhip_logit_edit_args a;
+    memset(&a, 0, sizeof(a));
+    a.batch_slots = batch_slots_host;
+    a.flags = flags_host;
+    a.batch = batch;
+    a.vocab_size = vocab_size;
+    a.batch_stride = batch_stride;
+    const int st = pplhip_logit_edit(ctx_, logits_device, &a);
+    if (st) LOG(ERROR) << "logit edit failed: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
 RetCode HipPostProcessor::ApplyPenalty(const float* temperatures_host, const float* repetition_penalties_host,
                                        const float* presence_penalties_host, const float* frequency_penalties_host,
                                        const int64_t* batch_slots_host, const int64_t*, const int64_t*, const int64_t*,

@@ -46,6 +46,9 @@ public:
     ppl::common::RetCode TopLogprobs(const float* logits_device, const float* temperatures_host, const int32_t* num_logprobs_host,
                                      int32_t batch, int32_t vocab_size, int32_t batch_stride, const int32_t** tokens, const float** logprobs,
                                      int32_t* rows) override;
+    ppl::common::RetCode SetLogitRule(int64_t slot, const LogitRule& rule) override;
+    ppl::common::RetCode EditLogits(float* logits_device, const int64_t* batch_slots_host, const uint32_t* flags_host, int32_t batch,
+                                    int32_t vocab_size, int32_t batch_stride) override;
 
 private:
     pplhip_ctx* ctx_;

@@ -180,6 +180,11 @@ int pplsrv_submit_ex(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots
 
 int pplsrv_submit_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
                            int32_t n) {
+    return pplsrv_submit_rules(s, reqs, slots, seeds, num_logprobs, nullptr, n);
+}
+
+int pplsrv_submit_rules(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
+                        const pplsrv_rule* const* rules, int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -196,6 +201,14 @@ int pplsrv_submit_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t*
         r->lora_slot = slots ? slots[i] : -1;
         r->seed = seeds ? seeds[i] : 0;
         r->num_logprobs = num_logprobs ? num_logprobs[i] : 0;
+        if (rules && rules[i]) {
+            const pplsrv_rule& u = *rules[i];
+            for (int32_t j = 0; j < u.n_bias; ++j) r->logit_bias.emplace_back(u.bias_tokens[j], u.bias_values[j]);
+            if (u.has_allowed)
+                r->allowed_tokens = std::make_shared<std::vector<int32_t>>(u.allowed_tokens, u.allowed_tokens + (u.n_allowed > 0 ? u.n_allowed : 0));
+            if (u.n_banned > 0) r->banned_tokens.assign(u.banned_tokens, u.banned_tokens + u.n_banned);
+            r->min_new_tokens = u.min_new_tokens;
+        }
         if (!q.tokens && q.prompt) {
             // text request (grpc_server.cc:218-252): LLMGenerator::Process tokenises it and adds the EOS id to its stop tokens
             if (!s->resource.tokenizer) {

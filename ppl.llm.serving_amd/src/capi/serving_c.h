@@ -98,6 +98,24 @@ PPLSRV_API int pplsrv_submit_logprobs(pplsrv* s, const pplsrv_request* reqs, con
                                       const int32_t* num_logprobs, int32_t n);
 PPLSRV_API int pplsrv_poll_logprobs(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms, char* text_buf, int64_t text_buf_bytes,
                                     pplsrv_top_logprobs* tops);
+/* Logit rules (pplsrv_request keeps its layout, so a request's rule travels beside it).  pplsrv_submit_rules is pplsrv_submit_logprobs with
+ * rules[i] the rule of reqs[i]: Request::logit_bias (pairs bias_tokens[j], bias_values[j]; -inf bans), ::allowed_tokens (has_allowed != 0:
+ * the only tokens the request may produce, n_allowed of them), ::banned_tokens and ::min_new_tokens.  rules NULL or rules[i] NULL: no rule.
+ * The arrays are read before the call returns.  A rule is validated when its request is admitted; an invalid one fails that request alone
+ * (PPLSRV_FAILED), as does any rule on a backend without logit rules. */
+typedef struct pplsrv_rule {
+    const int32_t* bias_tokens;
+    const float* bias_values;
+    int32_t n_bias;
+    const int32_t* allowed_tokens;
+    int32_t n_allowed;
+    int32_t has_allowed;
+    const int32_t* banned_tokens;
+    int32_t n_banned;
+    int32_t min_new_tokens;
+} pplsrv_rule;
+PPLSRV_API int pplsrv_submit_rules(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                   const int32_t* num_logprobs, const pplsrv_rule* const* rules, int32_t n);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

@@ -6,6 +6,7 @@
 #include <memory>
 #include <string>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "ppl/common/retcode.h"
@@ -32,6 +33,12 @@ struct Request final {
     int32_t lora_slot = -1;  // LoRA adapter slot of this request (HipResourceManager::LoadAdapter), -1 = the base model
     uint64_t seed = 0;       // sampling seed (GeneratorConfig::per_request_sampling), 0 = none: the generator gives the request one
     int32_t num_logprobs = 0;  // ranked alternatives per generated token (Response::top_tokens); above 20: 20, negative: 0
+    // logit rules (DESIGN.md "numerics", logit rules row; validated when the request is admitted, logit_rule.h):
+    std::vector<std::pair<int32_t, float>> logit_bias;   // (token, value added to its raw logit); -inf bans the token
+    std::shared_ptr<std::vector<int32_t>> allowed_tokens;  // the only tokens the request may produce; null: all
+    std::vector<int32_t> banned_tokens;                  // tokens it never produces (single-token bad words)
+    int32_t min_new_tokens = 0;                          // its stop tokens cannot be produced before this many tokens are out
+    bool HasLogitRule() const { return !logit_bias.empty() || allowed_tokens || !banned_tokens.empty() || min_new_tokens > 0; }
 };
 
 enum class FinishFlag { NOT_FINISHED, LENGTH, EOS_TOKEN, STOP_SEQUENCE };

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "adapter_registry.h"
+#include "logit_rule.h"
 #include "ppl/common/retcode.h"
 #include "ppl/common/threadpool.h"
 
@@ -49,6 +50,21 @@ public:
                                              const int32_t* /*num_logprobs_host*/, int32_t /*batch*/, int32_t /*vocab_size*/,
                                              int32_t /*batch_stride*/, const int32_t** /*tokens*/, const float** /*logprobs*/,
                                              int32_t* /*rows*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
+    // Logit rules (DESIGN.md "numerics", logit rules row).  SetLogitRule hands the backend the merged, validated rule of the request that
+    // owns batch slot `slot` (logit_rule.h: BuildLogitRule), once, before the request's first step; NOT blocking, ordered in front of
+    // every later EditLogits.  EditLogits edits the rows with flags_host[b] != 0 in place with the rule of batch_slots_host[b] (bit 0:
+    // mask and bias, bit 1: suppress the rule's stops); NOT blocking; the engine calls it in front of ApplyPenalty and only on steps in
+    // which a flag is set.  batch == 0 touches nothing and only tells whether the backend can do it (the generator asks so when a
+    // request with a rule is admitted); a backend that cannot keeps these defaults, and the requests that ask are failed.
+    static constexpr int32_t kLogitBiasMax = 512;
+    static constexpr int32_t kLogitStopMax = 64;
+    virtual ppl::common::RetCode SetLogitRule(int64_t /*slot*/, const LogitRule& /*rule*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
+    virtual ppl::common::RetCode EditLogits(float* /*logits_device*/, const int64_t* /*batch_slots_host*/, const uint32_t* /*flags_host*/,
+                                            int32_t /*batch*/, int32_t /*vocab_size*/, int32_t /*batch_stride*/) {
         return ppl::common::RC_UNSUPPORTED;
     }
 };

@@ -113,6 +113,19 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
         Runtime* rt0 = runtimes_[0];  // sampling happens on rank 0's logits only (src/engine/llm_engine.cc:200)
         int64_t stride = 0;
         float* logits = rt0->GetLogits(&stride);
+        // logit rules: in place and first, so a bias is in raw-logit units and the penalty, the top-N logprobs and the sampler all see
+        // the edited rows; nothing on a step without a flag
+        bool edits = false;
+        for (uint32_t f : in.logit_flags) edits = edits || f != 0;
+        if (edits) {
+            rc = post_processor_->EditLogits(logits, in.batch_slots.data(), in.logit_flags.data(), running_batch, model_config_.vocab_size,
+                                             (int32_t)stride);
+            if (rc != RC_SUCCESS) {
+                *error_msg = "EditLogits failed: " + std::string(GetRetCodeStr(rc));
+                LOG(ERROR) << *error_msg;
+                return RC_OTHER_ERROR;
+            }
+        }
         if (enable_penalty_) {
             rc = post_processor_->ApplyPenalty(in.temperatures.data(), in.repetition_penalty_list.data(), nullptr, nullptr,
                                                in.batch_slots.data(), rt0->GetTokenInputsDevice(), rt0->GetSeqStartsDevice(),

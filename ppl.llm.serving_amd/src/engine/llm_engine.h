@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -37,6 +38,9 @@ struct ModelInput {
     std::vector<int64_t> batch_slots;
     std::vector<int32_t> lora_slots;  // adapter slot per request (Request::lora_slot), -1 = none
     std::vector<int32_t> num_logprobs_list;  // top-N logprobs per request (Request::num_logprobs, clamped to 0 .. 20)
+    // logit rules per request: 0 = the request has none; bit 0 = apply the mask and bias of the rule in its batch slot, bit 1 = suppress
+    // the rule's stop tokens (set while the request has produced fewer than min_new_tokens tokens)
+    std::vector<uint32_t> logit_flags;
 };
 
 struct ModelOutput {
@@ -69,6 +73,16 @@ public:
     ppl::common::RetCode Init(WorkerPerStepCounter* step_counter);
     ppl::common::RetCode Execute(const ModelInput& model_input, bool req_list_changed, bool is_prefix_cache_hit,
                                  ModelOutput* model_output, std::string* error_msg);
+    // logit rules: whether the backend's post processor has them (PostProcessor::EditLogits with batch 0), and the upload of one slot's rule
+    bool HasLogitRules() const {
+        return post_processor_ && post_processor_->EditLogits(nullptr, nullptr, nullptr, 0, model_config_.vocab_size,
+                                                              model_config_.vocab_size) == ppl::common::RC_SUCCESS;
+    }
+    ppl::common::RetCode SetLogitRule(int64_t slot, const LogitRule& rule) {
+        std::unique_lock<std::mutex> device_lock;  // as Execute: adapters load and unload on the same device
+        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
+        return post_processor_->SetLogitRule(slot, rule);
+    }
 
 private:
     uint32_t tensor_parallel_size_;

@@ -27,8 +27,13 @@ struct LLMGenerator::Admission {
     int32_t running_batch = 0;
     int32_t prefill_batch = 0;
     std::string errmsg;
+    RetCode errcode = RC_INVALID_VALUE;
+    bool has_rule = false;  // the request carries a logit rule: `rule` is its validated, merged form
+    LogitRule rule;
 
     void ResetForRequest(int prompt_len) {
+        errcode = RC_INVALID_VALUE;
+        has_rule = false;
         cache_index = INT64_MAX;
         page_list.clear();
         slot_index = INT64_MAX;
@@ -268,7 +273,7 @@ bool LLMGenerator::ReserveKv(const LlmRequest& req, Admission* adm, int32_t* coo
         const int64_t pages = ((int64_t)total_len + model_config_.page_size - 1) / model_config_.page_size;
         if (page_mgr_.Alloc(pages, &adm->page_list) != RC_SUCCESS) return false;
     }
-    if (generator_config_.enable_penalty) {
+    if (generator_config_.enable_penalty || adm->has_rule) {  // the count map row and the rule record live in the request's batch slot
         adm->slot_index = batch_slots_mgr_.Alloc(1);
         if (adm->slot_index == INT64_MAX) {
             LOG(ERROR) << "alloc batch slot error, available [" << batch_slots_mgr_.GetAvailableBlockNum() << "]";
@@ -299,6 +304,26 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
         adm->errmsg = "id [" + std::to_string(req.orig->id) + "] generation length <= 0";
         return true;
     }
+    if (req.orig->HasLogitRule()) {  // validated once, here; an invalid rule fails its request alone (StartRequest)
+        const Request& r = *req.orig;
+        bool ok = llm_engine_.HasLogitRules();
+        if (!ok) {
+            adm->errmsg = "logit rules: the backend's post processor has no EditLogits";
+            adm->errcode = RC_UNSUPPORTED;
+        } else {
+            std::vector<int> stops(generator_config_.stop_tokens.begin(), generator_config_.stop_tokens.end());
+            if (r.stop_tokens) stops.insert(stops.end(), r.stop_tokens->begin(), r.stop_tokens->end());
+            ok = BuildLogitRule(r.logit_bias, r.allowed_tokens.get(), r.banned_tokens, r.min_new_tokens, stops, model_config_.vocab_size,
+                                &adm->rule, &adm->errmsg);
+        }
+        if (!ok) {
+            adm->errmsg = "id [" + std::to_string(r.id) + "] " + adm->errmsg;
+            LOG(ERROR) << adm->errmsg;
+            adm->first_fill_len = -1;
+            return true;
+        }
+        adm->has_rule = true;
+    }
     if (!ReserveKv(req, adm, cool_down, is_prefix_cache_hit)) return false;
     ++adm->running_batch;
     ++adm->prefill_batch;
@@ -317,7 +342,7 @@ static uint64_t SplitMix64(uint64_t x) {
 bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, ModelInput* in) {
     const Request& r = *req.orig;
     if (adm.rest_iters <= 0 || adm.first_fill_len == -1) {
-        conn_->NotifyFailure(r.id, RC_INVALID_VALUE, adm.errmsg);
+        conn_->NotifyFailure(r.id, adm.errcode, adm.errmsg);
         if (adapters_) adapters_->Release(r.lora_slot);
         return true;
     }
@@ -344,6 +369,20 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     t.lora_slot = r.lora_slot;
     t.seed = r.seed ? r.seed : SplitMix64(generator_config_.sampling_seed + ++unseeded_requests_);
     t.num_logprobs = std::min(std::max(r.num_logprobs, 0), PostProcessor::kTopLogprobsMax);
+    // the logit rule goes up once, now that the request has its slot and before its first step.  A slot's record is never cleared: it is
+    // read only while its owner's flags are set, and the next owner with a rule overwrites it
+    uint32_t logit_flags = 0;
+    if (adm.has_rule) {
+        t.min_new_tokens = r.min_new_tokens;
+        const RetCode rule_rc = llm_engine_.SetLogitRule(t.slot_index, adm.rule);
+        if (rule_rc != RC_SUCCESS) {
+            LOG(ERROR) << "id [" << r.id << "] SetLogitRule failed: " << GetRetCodeStr(rule_rc);
+            t.rule_failed = true;
+        } else {
+            if (!adm.rule.bias_tokens.empty() || adm.rule.has_mask) logit_flags |= 1u;
+            if (!adm.rule.stop_tokens.empty()) logit_flags |= 2u;
+        }
+    }
     if (mode == 0) {
         t.cache_index = (uint64_t)adm.cache_index;
     } else {
@@ -376,6 +415,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     in->batch_slots.push_back(t.slot_index);
     in->lora_slots.push_back(t.lora_slot);
     in->num_logprobs_list.push_back(t.num_logprobs);
+    in->logit_flags.push_back(logit_flags);
     if (mode == 0) in->cache_indices.push_back(adm.cache_index);
     else in->max_pages = std::max<int64_t>((int64_t)t.page_list.size(), in->max_pages);
     return true;
@@ -429,6 +469,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
         in->batch_slots[keep] = in->batch_slots[i];
         in->lora_slots[keep] = in->lora_slots[i];
         in->num_logprobs_list[keep] = in->num_logprobs_list[i];
+        in->logit_flags[keep] = in->logit_flags[i];
         ++keep;
     }
     tid_list_.resize(keep);
@@ -445,6 +486,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
     in->batch_slots.resize(keep);
     in->lora_slots.resize(keep);
     in->num_logprobs_list.resize(keep);
+    in->logit_flags.resize(keep);
     LOG(DEBUG) << "Rest tasks: " << keep;
 }
 
@@ -474,7 +516,7 @@ void LLMGenerator::DeleteTasks(ModelInput* in) {
         } else {
             page_mgr_.Free(t.page_list.data(), (int64_t)t.page_list.size());
         }
-        if (generator_config_.enable_penalty) batch_slots_mgr_.Free((uint64_t)in->batch_slots[row], 1);
+        if (t.slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t.slot_index, 1);
         if (adapters_) adapters_->Release(t.lora_slot);
         // (the reference adds to a by-value pointer here and so counts nothing -- SURVEY.md Q2; counted properly)
         worker_profiler_->req_counter.output_tokens_per_req += (uint64_t)t.gen_tokens_cnt;
@@ -489,7 +531,7 @@ void LLMGenerator::ReleaseResource() {
     for (TidData* t : tid_list_) {
         if (model_config_.cache_mode == 0) idx_mgr_.Free(t->cache_index, (uint64_t)t->total_len - 1);
         else page_mgr_.Free(t->page_list.data(), (int64_t)t->page_list.size());
-        if (generator_config_.enable_penalty) batch_slots_mgr_.Free((uint64_t)t->slot_index, 1);
+        if (t->slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t->slot_index, 1);
         if (adapters_) adapters_->Release(t->lora_slot);
     }
     prefix_cache_mgr_.Reset();
@@ -605,6 +647,7 @@ void LLMGenerator::Generate() {
                 TidData* t = tid_list_[row];
                 ++t->gen_tokens_cnt;
                 ++in.draw_list[row];
+                if (t->gen_tokens_cnt >= t->min_new_tokens) in.logit_flags[row] &= ~2u;  // the stops are free from the next step on
                 const int tok = out.output_token[row];
                 const int64_t fed = (int64_t)t->next_tokens->size();
                 t->next_tokens = std::make_shared<std::vector<int>>(1, tok);
@@ -621,7 +664,7 @@ void LLMGenerator::Generate() {
                 const bool hit_stop = t->early_stopping &&
                     (generator_config_.stop_tokens.count(tok) || (t->stop_tokens && t->stop_tokens->count(tok)));
                 // a request that asks for top-N logprobs on a backend without them fails alone: it leaves like a finished one, unanswered
-                const bool no_top = t->num_logprobs > 0 && out.top_unsupported;
+                const bool no_top = (t->num_logprobs > 0 && out.top_unsupported) || t->rule_failed;
                 if (t->rest_iters <= 0 || hit_stop || no_top) {
                     flag = t->rest_iters <= 0 ? FinishFlag::LENGTH : FinishFlag::EOS_TOKEN;
                     if (cool_down > 0) --cool_down;
@@ -629,7 +672,8 @@ void LLMGenerator::Generate() {
                     req_list_changed_ = true;
                 }
                 if (no_top) {
-                    conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "num_logprobs: the backend's post processor has no TopLogprobs");
+                    if (t->rule_failed) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "logit rules: the backend could not take the request's rule");
+                    else conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "num_logprobs: the backend's post processor has no TopLogprobs");
                     continue;
                 }
                 tokens->push_back(TidGenToken{t->tid, tok, out.logprobs[row], flag, (uint64_t)t->steps, t->is_token_in_out,

@@ -64,7 +64,7 @@ struct TidData final {
     int64_t start_pos = 0;
     uint64_t cache_index = 0;
     std::vector<int64_t> page_list;
-    int64_t slot_index = 0;
+    int64_t slot_index = 0;  // batch slot: the penalty count map row and the logit rule record; INT64_MAX: the request holds none
     int32_t steps = 0;
     int32_t gen_tokens_cnt = 0;
     std::vector<uint64_t> hash_list;  // hashes of this request's full prompt pages (cached + newly inserted)
@@ -72,6 +72,8 @@ struct TidData final {
     int32_t lora_slot = -1;  // holds a reference in the adapter registry until the request leaves
     uint64_t seed = 0;       // sampling seed: the request's own, or the generator's next one
     int32_t num_logprobs = 0;  // Request::num_logprobs, clamped to 0 .. PostProcessor::kTopLogprobsMax
+    int32_t min_new_tokens = 0;  // Request::min_new_tokens: bit 1 of the row's logit flags until this many tokens are out
+    bool rule_failed = false;    // the upload of its logit rule failed: the request is failed on its first step
 };
 
 struct LlmRequest final : public ppl::common::MPSCQueue::Node {

@@ -4,11 +4,16 @@
 //                  "enable_penalty", "stop_tokens": [..]},
 //    "kv_cache_max_tokens": N,
 //    "requests": [{"id", "tokens": [..], "generation_length", "temperature", "top_p", "top_k", "repetition_penalty",
-//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed", "num_logprobs"}]}
+//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed", "num_logprobs",
+//                  "logit_bias": [[token, value], ..], "allowed_tokens": [..], "banned_tokens": [..], "min_new_tokens"}]}
 // "seed" (this tree's Request only: the sampling seed of --per-request-sampling, 0 or absent = none) is ignored for a request type without it.
 // "num_logprobs" (this tree's Request only: ranked alternatives per generated token, 0 .. 20, 0 or absent = none) likewise.
+// "logit_bias" / "allowed_tokens" / "banned_tokens" / "min_new_tokens" (this tree's Request only: its logit rule; a value may be the string
+// "-inf"; token ids are taken as written, an id outside the vocabulary fails the request) likewise.
 // Templates: Request / GeneratorConfig are this tree's or the reference's types (same member names by construction).
 #pragma once
+#include <math.h>
+
 #include <fstream>
 #include <iostream>
 #include <memory>
@@ -53,6 +58,25 @@ template <typename RequestT>
 void SetNumLogprobs(RequestT*, int32_t, long) {}
 
 template <typename RequestT>
+auto SetLogitRule(RequestT* q, const utils::JsonValue& r, int) -> decltype(q->min_new_tokens = 0, void()) {
+    if (const utils::JsonValue* lb = r.Find("logit_bias"))
+        for (const auto& p : lb->arr) {
+            if (p.arr.size() != 2) { q->logit_bias.emplace_back(-1, 0.f); continue; }   // malformed: a pair the generator refuses
+            const float v = p.arr[1].type == utils::JsonValue::STRING && p.arr[1].str == "-inf" ? -INFINITY : (float)p.arr[1].num;
+            q->logit_bias.emplace_back((int32_t)p.arr[0].AsInt(), v);
+        }
+    if (const utils::JsonValue* al = r.Find("allowed_tokens")) {
+        q->allowed_tokens = std::make_shared<std::vector<int32_t>>();
+        for (const auto& v : al->arr) q->allowed_tokens->push_back((int32_t)v.AsInt());
+    }
+    if (const utils::JsonValue* bn = r.Find("banned_tokens"))
+        for (const auto& v : bn->arr) q->banned_tokens.push_back((int32_t)v.AsInt());
+    q->min_new_tokens = (int32_t)r.GetInt("min_new_tokens", 0);
+}
+template <typename RequestT>
+void SetLogitRule(RequestT*, const utils::JsonValue&, long) {}
+
+template <typename RequestT>
 std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& doc, int vocab_size) {
     std::vector<std::shared_ptr<RequestT>> out;
     for (const auto& r : doc.Find("requests")->arr) {
@@ -66,6 +90,7 @@ std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& 
         q->early_stopping = r.GetBool("early_stopping", true);
         SetSeed(q.get(), (uint64_t)r.GetInt("seed", 0), 0);
         SetNumLogprobs(q.get(), (int32_t)r.GetInt("num_logprobs", 0), 0);
+        SetLogitRule(q.get(), r, 0);
         q->token_ids = std::make_shared<std::vector<int>>();
         if (const utils::JsonValue* t = r.Find("tokens"))
             for (const auto& v : t->arr) q->token_ids->push_back((int)(v.AsInt() % vocab_size));
