@@ -299,6 +299,41 @@ PPLHIP_API int pplhip_set_inputs(pplhip_ctx* ctx, int rank, const pplhip_step* s
  * cache_prefill = ENGINE_CONF_CACHE_PREFILL (llm_engine.cc:114). */
 PPLHIP_API int pplhip_run(pplhip_ctx* ctx, int rank, int cache_prefill);
 
+/* Prompt logprobs (DESIGN.md "numerics", prompt logprobs row; no counterpart in the reference): a request of the staged step can have every
+ * one of its own prompt tokens scored.  Request b with ask[b] >= 0 and token rows s .. e-1 of the step (s = seq_starts[b], e =
+ * seq_starts[b + 1]) yields the e - s - 1 positions r = s .. e-2: position r is row r's distribution scored against token_inputs[r + 1],
+ *   logprob = x[t] - max - log(sum exp(x - max)),   rank = #{v : x[v] > x[t]} + #{v < t : x[v] == x[t]}   (rank 0: the greedy token),
+ * x the row's RAW fp32 logits over the whole vocabulary.  The request's last row predicts its first generated token and is not a position;
+ * a request of one row (a decode row among them) yields none.  ask[b] = n in 1 .. PPLHIP_TOP_LOGPROBS_MAX also gives the first n entries
+ * of every position's ranking (x descending, ties to the lower token id; entries behind the vocabulary are token -1, logprob -inf), entry
+ * 0 the greedy token; where the target is among them its logprob equals that entry's bit for bit.
+ * THE DISTRIBUTION IS THE MODEL'S OWN: no temperature, no penalty, no logit rule touches it.  pplhip_top_logprobs is the opposite: it
+ * reports the row the step's sampler sees, after all of them.
+ * pplhip_set_prompt_logprobs: ask is host [batch], -1 (off) .. 20.  After pplhip_set_inputs (which clears the ask: callers that never call
+ * this get the step they always got) and before pplhip_run, like pplhip_set_adapters.  With no position asked the step issues exactly the
+ * launches of a step without it and nothing is allocated; the buffers (device and pinned) are allocated by the first call that asks.
+ * pplhip_run then scores the asked rows in front of its own last-token gather, in chunks of at most max_running_batch rows through the
+ * buffers the step's own lm_head uses next (final norm of the rows, lm_head, one workgroup per position), and queues ONE download into
+ * pinned memory; the step's logits are bit for bit those of the step without the ask.
+ * PPLHIP_INVALID_VALUE before any device call: ask NULL, batch other than the staged step's, an entry outside [-1, 20].
+ * PPLHIP_UNSUPPORTED when world_size > 1: the lm_head is vocabulary-sharded under tensor parallelism and the reduction over the vocabulary
+ * would have to cross the shards; that is a later change.
+ * pplhip_prompt_logprobs fills `out` for the rank's LAST pplhip_run: the pointers are library-owned pinned memory, valid after the next
+ * synchronisation of the rank's stream (the step's sampler call, pplhip_copy_logits or pplhip_sync) and until the next pplhip_run;
+ * positions = 0 when that run had no ask.  Position i is packed row rows[i] (ascending) of the step.
+ * Arrived without a version bump (pplhip_version() stays 1.2): a client tells a library that has it by the symbol
+ * pplhip_set_prompt_logprobs (dlsym). */
+typedef struct pplhip_prompt_logprobs_out {
+    int64_t positions;
+    const int32_t* rows;         /* [positions] packed row of the step, ascending; scored against token_inputs[rows[i] + 1] */
+    const float* logprobs;       /* [positions] */
+    const int32_t* ranks;        /* [positions] */
+    const int32_t* top_tokens;   /* [positions, PPLHIP_TOP_LOGPROBS_MAX]: the first n slots of a position whose request asked n >= 1, */
+    const float* top_logprobs;   /* the rest (and every slot of an n = 0 position) unspecified */
+} pplhip_prompt_logprobs_out;
+PPLHIP_API int pplhip_set_prompt_logprobs(pplhip_ctx* ctx, int rank, const int32_t* ask, int64_t batch);
+PPLHIP_API int pplhip_prompt_logprobs(pplhip_ctx* ctx, int rank, pplhip_prompt_logprobs_out* out);
+
 /* device pointer + row stride (floats) of `logits fp32[B, vocab]` of the last run (llm_engine.cc:207-222). */
 PPLHIP_API int pplhip_logits(pplhip_ctx* ctx, int rank, float** logits_device, int64_t* stride);
 
@@ -590,6 +625,15 @@ PPLHIP_API int pplhip_op_top_logprobs(void* stream, const float* logits, const f
 PPLHIP_API int pplhip_op_logit_edit(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const uint32_t* flags,
                                     const int32_t* slots, const int32_t* head, const int32_t* bias_tokens, const float* bias_values,
                                     const int32_t* stop_tokens, const uint32_t* mask, const int32_t* rows, int32_t n_rows);
+/* the prompt logprobs kernel alone (csrc/k_prompt_logprobs.hip), for the tests: DEVICE pointers.  Position j < n_rows reads logits row j
+ * ([n_rows, stride] raw fp32, stride >= vocab) and is scored against targets[rows[j] + 1] (targets: int64 [n_targets], the layout of a
+ * step's token_inputs; rows: int32 [n_rows]); n_top [n_rows] in 0 .. PPLHIP_TOP_LOGPROBS_MAX.  out_logprob / out_rank [n_rows]; out_top_tok
+ * / out_top_logprob [n_rows, 20], row j's first n_top[j] slots written, may be NULL when every n_top is 0.  rows and n_top are read back and
+ * checked on the host (an n_top outside its range or a rows[j] + 1 outside [0, n_targets): PPLHIP_INVALID_VALUE, nothing launched), so the
+ * call synchronises `stream` before it launches; a target outside [0, vocab) gives NaN / rank -1.  n_rows = 0: no launch. */
+PPLHIP_API int pplhip_op_prompt_logprobs(void* stream, const float* logits, int32_t stride, int32_t vocab, const int32_t* rows, int32_t n_rows,
+                                         const int64_t* targets, int64_t n_targets, const int32_t* n_top, float* out_logprob,
+                                         int32_t* out_rank, int32_t* out_top_tok, float* out_top_logprob);
 /* out_u[b] = u(seeds[b], draws[b]), the generator alone (device pointers) */
 PPLHIP_API int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u);
 

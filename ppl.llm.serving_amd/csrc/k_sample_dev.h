@@ -4,6 +4,8 @@
 // the row's temperature (already defaulted: row_temperature), its k / p / random number and the two places its answer goes; for equal
 // arguments it gives equal token and logprob bits from either file.  A third row function, top_logprobs_row (k_logprobs.hip), reports the
 // first n tokens of the same ranking with the same full-vocabulary logprob; it decides nothing and shares radix_pass with the top-k rule.
+// A fourth, prompt_logprob_row (k_prompt_logprobs.hip), scores one given token of a row of RAW logits: its logprob from the same two sweeps as
+// top_logprobs_row at temperature 1, and its rank in the same order.
 #pragma once
 #include "kernels.h"
 
@@ -322,18 +324,11 @@ __device__ __forceinline__ uint32_t rank_key(float x) {
     return order_key(x == 0.f ? 0.f : x);
 }
 
-__device__ __forceinline__ void top_logprobs_row(const float* __restrict__ row, bool vec, float t, int n, int vocab,
-                                                 int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
-    __shared__ float sf[TL_WAVES];
-    __shared__ int wsum[4], sel[4], hist[256];
-    __shared__ float cv[32];
-    __shared__ int ci[32];
+// the maximum sweep of a TL_THREADS block over x = row * invt (16-byte loads, four in flight per thread, over the first nv float4 chunks; the
+// rest element by element); sf: TL_WAVES floats of LDS, free again when it returns.  A maximum does not depend on the order it is taken in.
+__device__ __forceinline__ float tl_row_max(const float* __restrict__ row, int nv, float invt, int vocab, float* sf) {
     const int tid = threadIdx.x;
-    const float invt = 1.0f / t;
-    const int k = n < vocab ? n : vocab;
-    const int nv = vec ? vocab >> 2 : 0;   // float4 chunks; the tail (and unaligned rows) element by element
     const float4 none = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-
     float mx = -INFINITY;
     for (int c0 = tid; c0 < nv; c0 += 4 * TL_THREADS) {
         float4 v[4];
@@ -351,6 +346,22 @@ __device__ __forceinline__ void top_logprobs_row(const float* __restrict__ row, 
     __syncthreads();
     mx = fmaxf(fmaxf(sf[0], sf[1]), fmaxf(sf[2], sf[3]));
     __syncthreads();
+    return mx;
+}
+
+__device__ __forceinline__ void top_logprobs_row(const float* __restrict__ row, bool vec, float t, int n, int vocab,
+                                                 int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
+    __shared__ float sf[TL_WAVES];
+    __shared__ int wsum[4], sel[4], hist[256];
+    __shared__ float cv[32];
+    __shared__ int ci[32];
+    const int tid = threadIdx.x;
+    const float invt = 1.0f / t;
+    const int k = n < vocab ? n : vocab;
+    const int nv = vec ? vocab >> 2 : 0;   // float4 chunks; the tail (and unaligned rows) element by element
+    const float4 none = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+
+    const float mx = tl_row_max(row, nv, invt, vocab, sf);
     // the mass: per thread its chunks in order, (x + y) + (z + w) inside a chunk, then its tail elements; then a tree over the block
     float se = 0.f;
     for (int c0 = tid; c0 < nv; c0 += 4 * TL_THREADS) {
@@ -427,6 +438,61 @@ __device__ __forceinline__ void top_logprobs_row(const float* __restrict__ row, 
             out_lp[tid] = tid < k ? a.v - lse : -INFINITY;
         }
     }
+}
+
+// prompt logprobs (DESIGN.md "numerics", prompt logprobs row): one prompt position.  `row` holds the RAW fp32 logits of the position (the
+// model's own distribution: no temperature, no penalty, no logit rule -- the opposite of top_logprobs_row, which reports what the sampler
+// sees), `target` the prompt token that follows it.  *out_lp = x[target] - lse with the lse of top_logprobs_row at temperature 1: the same
+// maximum sweep (tl_row_max) and the same mass sweep in the same order -- per thread its 16-byte pieces in order, (x + y) + (z + w) inside a
+// piece, then its tail elements, six shuffle steps, (w0 + w1) + (w2 + w3) -- so where the target is among that function's entries for the
+// same row the two logprobs are equal bit for bit.  *out_rank = #{v : x[v] > x[t]} + #{v < t : x[v] == x[t]}, am_better's order (rank 0 is
+// the greedy token; float comparison, so -0 ties with +0), counted in the mass sweep and summed over the block in integers: exact.
+// Two row passes; a block of TL_THREADS threads.
+__device__ __forceinline__ void prompt_logprob_row(const float* __restrict__ row, bool vec, int target, int vocab, float* __restrict__ out_lp,
+                                                   int32_t* __restrict__ out_rank) {
+    __shared__ float sf[TL_WAVES];
+    __shared__ int sc[TL_WAVES];
+    const int tid = threadIdx.x;
+    const int nv = vec ? vocab >> 2 : 0;
+    const float4 none = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    const float xt = row[target];
+    const float mx = tl_row_max(row, nv, 1.0f, vocab, sf);
+    float se = 0.f;
+    int ahead = 0;
+    for (int c0 = tid; c0 < nv; c0 += 4 * TL_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 + u * TL_THREADS;
+            v[u] = c < nv ? reinterpret_cast<const float4*>(row)[c] : none;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            se += (__expf(v[u].x - mx) + __expf(v[u].y - mx)) + (__expf(v[u].z - mx) + __expf(v[u].w - mx));
+            const int c = c0 + u * TL_THREADS, i = c * 4;
+            if (c < nv) {   // (the -inf filler of a missing piece would tie with a target at -inf)
+                ahead += (v[u].x > xt || (v[u].x == xt && i < target)) + (v[u].y > xt || (v[u].y == xt && i + 1 < target)) +
+                         (v[u].z > xt || (v[u].z == xt && i + 2 < target)) + (v[u].w > xt || (v[u].w == xt && i + 3 < target));
+            }
+        }
+    }
+    for (int i = nv * 4 + tid; i < vocab; i += TL_THREADS) {
+        const float x = row[i];
+        se += __expf(x - mx);
+        ahead += x > xt || (x == xt && i < target);
+    }
+    se = wave_sum(se);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ahead += __shfl_xor(ahead, o, 64);
+    if ((tid & 63) == 0) { sf[tid >> 6] = se; sc[tid >> 6] = ahead; }
+    __syncthreads();
+    if (tid == 0) {
+        se = (sf[0] + sf[1]) + (sf[2] + sf[3]);
+        const float lse = mx + logf(se);
+        *out_lp = xt - lse;
+        *out_rank = (sc[0] + sc[1]) + (sc[2] + sc[3]);
+    }
+    __syncthreads();   // a caller may go on with top_logprobs_row on the same row
 }
 
 }  // namespace pplhip

@@ -279,6 +279,14 @@ struct LogitRuleTable {
 hipError_t launch_logit_edit(hipStream_t s, float* logits, int stride, int vocab, const int32_t* rows, int n_rows, const int32_t* slots,
                              const uint32_t* flags, const LogitRuleTable& table);
 
+// ---- k_prompt_logprobs.hip: prompt logprobs -------------------------------------------------------
+// One workgroup per listed position j < n_rows: logits row j ([n_rows, stride], raw), target tokens[rows[j] + 1] (the step's packed token
+// ids), n_top[j] in 0 .. 20.  out_lp / out_rank [n_rows]; out_top_tok / out_top_lp [n_rows, 20], written for n_top[j] >= 1 only (the first
+// n_top[j] slots).  A target outside [0, vocab) gives NaN / rank -1 and reads nothing.  No rows: no launch.
+hipError_t launch_prompt_logprobs(hipStream_t s, const float* logits, int stride, int vocab, const int32_t* rows, int n_rows,
+                                  const int64_t* tokens, const int32_t* n_top, float* out_lp, int32_t* out_rank, int32_t* out_top_tok,
+                                  float* out_top_lp);
+
 // ---- synth.hip --------------------------------------------------------------------------------
 // kinds as in oracle/llama_ref.c: 0 fp16 uniform(-amp,amp), 1 int8, 2 packed int4 (n bytes), 3 scale, 4 norm; and for the fp8 KV
 // slab only (no oracle counterpart): 5 e4m3 codes, 6 power-of-two fp16 scales; for the int4 KV slab: 7 nibble pairs 1..15, 8 scales of its rule

@@ -101,6 +101,10 @@ constexpr int64_t SROWS_BYTES = 8 + 8 + 4 + 4 + 4 + 4;
 constexpr int64_t TLP_IN_BYTES = 4 + 4 + 4;
 constexpr int64_t TLP_OUT_BYTES = (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
 static_assert(PPLHIP_TOP_LOGPROBS_MAX == TOP_LOGPROBS_MAX, "header and kernel disagree");
+// prompt logprobs, per position: gather i64 + row i32 + n_top i32 going up (+ 8 for the gather's entry 0), and coming down
+// logprob f32 + rank i32 + 20 x (token i32 + logprob f32)
+constexpr int64_t PLP_IN_BYTES = 8 + 4 + 4;
+constexpr int64_t PLP_OUT_BYTES = 4 + 4 + (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
 // logit rules: a slot's record in the device table and in the pinned staging ring is
 // head i32 [4] = {n_bias, n_stop, has_mask, 0} | bias tokens i32 [512] | bias values f32 [512] | stops i32 [64] | mask u32 [words, padded to 4]
 // so one copy carries a rule.  pplhip_logit_edit stages slots i32 [cap_B] | flags u32 [cap_B] | row list i32 [cap_B] in a block of its own.
@@ -185,6 +189,16 @@ struct Rank {
     std::vector<uint8_t> lr_has;
     char *h_lre = nullptr, *d_lre = nullptr;
     hipEvent_t lre_ev = nullptr;
+    // prompt logprobs (k_prompt_logprobs.hip), all allocated by the first pplhip_set_prompt_logprobs that asks, for cap_T positions.
+    // Going up in one copy, P the staged positions: gather i64 [P + 1] (entry j + 1 = row_j + 1: the final norm's gathering form reads row
+    // gather[j + 1] - 1) | rows i32 [P] | n_top i32 [P].  Coming down in one copy: logprob f32 [P] | rank i32 [P] | top tokens i32 [P, 20] |
+    // top logprobs f32 [P, 20] (the last two only when a position asked for them); behind PLP_OUT_BYTES x cap_T of the pinned block the
+    // rows of the last run, which the staging block cannot keep (the next step restages it before its run).
+    char *h_plp_in = nullptr, *d_plp_in = nullptr, *h_plp_out = nullptr, *d_plp_out = nullptr;
+    hipEvent_t plp_ev = nullptr;            // the copy out of h_plp_in is done
+    int64_t plp_n = 0;                      // positions of the staged step (pplhip_set_inputs clears it)
+    bool plp_top = false;                   // one of them asked for the ranking
+    int64_t plp_done = 0;                   // positions of the last pplhip_run
 
     // exchange region of the direct collectives (k_comm.hip): fine-grained, peer-mapped; holds the flag words and the buffers
     // the collectives work in place on (part, part2) or push into (logits_gather)
@@ -769,6 +783,9 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.h_lre) hipHostFree(R.h_lre);
         for (hipEvent_t e : R.lr_ev) if (e) hipEventDestroy(e);
         if (R.lre_ev) hipEventDestroy(R.lre_ev);
+        if (R.h_plp_in) hipHostFree(R.h_plp_in);
+        if (R.h_plp_out) hipHostFree(R.h_plp_out);
+        if (R.plp_ev) hipEventDestroy(R.plp_ev);
         if (R.stream) hipStreamDestroy(R.stream);
     }
     delete c;
@@ -1439,6 +1456,8 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
     Rank& R = c->ranks[rank];
     R.lora_ntiles = 0;   // the adapter assignment belongs to one step (pplhip_set_adapters)
     R.lora_stale = false;
+    R.plp_n = 0;         // so does the prompt-logprobs ask (pplhip_set_prompt_logprobs)
+    R.plp_top = false;
     const int64_t B = st->batch, T = st->num_tokens;
     if (B < 0 || T < 0 || B > R.cap_B || T > R.cap_T)
         return fail(c, rank, PPLHIP_INVALID_VALUE, "step exceeds max_running_batch / max_tokens_per_step");
@@ -1798,6 +1817,118 @@ int pplhip_set_adapters(pplhip_ctx* c, int rank, const int32_t* slots, int64_t b
     return 0;
 }
 
+// ---- prompt logprobs -------------------------------------------------------------------------------------------------------------------
+// the first ask of a rank: the device blocks, their pinned images and the staging event
+static int prompt_logprobs_alloc(pplhip_ctx* c, int rank) {
+    Rank& R = c->ranks[rank];
+    const int64_t cap = R.cap_T;
+    int rc;
+    char *d_in = nullptr, *d_out = nullptr;
+    if ((rc = dev_alloc(c, rank, (void**)&d_in, (uint64_t)(cap * PLP_IN_BYTES + 8)))) return rc;
+    if ((rc = dev_alloc(c, rank, (void**)&d_out, (uint64_t)(cap * PLP_OUT_BYTES)))) return rc;
+    if (!R.h_plp_in) HIPCK(c, rank, hipHostMalloc((void**)&R.h_plp_in, (size_t)(cap * PLP_IN_BYTES + 8), hipHostMallocDefault));
+    if (!R.h_plp_out) HIPCK(c, rank, hipHostMalloc((void**)&R.h_plp_out, (size_t)(cap * (PLP_OUT_BYTES + 4)), hipHostMallocDefault));
+    if (!R.plp_ev) HIPCK(c, rank, hipEventCreateWithFlags(&R.plp_ev, hipEventDisableTiming));
+    R.d_plp_out = d_out;
+    R.d_plp_in = d_in;   // last: the blocks count as there only when all of them are
+    return 0;
+}
+
+int pplhip_set_prompt_logprobs(pplhip_ctx* c, int rank, const int32_t* ask, int64_t batch) {
+    if (!c || rank < 0 || rank >= (int)c->ranks.size()) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[rank];
+    if (c->tp > 1 || c->tp_on)
+        return fail(c, rank, PPLHIP_UNSUPPORTED, "prompt logprobs under tensor parallelism (world_size > 1) are not supported: the lm_head is vocabulary-sharded");
+    if (!ask || batch != R.B) return fail(c, rank, PPLHIP_INVALID_VALUE, "pplhip_set_prompt_logprobs: one entry per request of the staged step");
+    R.plp_n = 0;
+    R.plp_top = false;
+    int64_t P = 0;
+    bool top = false;
+    for (int64_t b = 0; b < batch; ++b) {
+        if (ask[b] < -1 || ask[b] > PPLHIP_TOP_LOGPROBS_MAX)
+            return fail(c, rank, PPLHIP_INVALID_VALUE, "request " + std::to_string(b) + ": prompt logprobs ask outside [-1, PPLHIP_TOP_LOGPROBS_MAX]");
+        if (ask[b] < 0) continue;
+        const int64_t len = R.h_seq[b + 1] - R.h_seq[b];   // (batch == R.B > 0: pplhip_set_inputs staged and validated seq_starts)
+        if (len < 2) continue;
+        P += len - 1;
+        top = top || ask[b] > 0;
+    }
+    if (P == 0) return 0;   // exactly the step without the ask
+    HIPCK(c, rank, hipSetDevice(R.device));
+    if (!R.d_plp_in)
+        if (int rc = prompt_logprobs_alloc(c, rank)) return rc;
+    HIPCK(c, rank, hipEventSynchronize(R.plp_ev));   // the copy that last read the staging block is done (a fresh event has passed)
+    int64_t* gather = (int64_t*)R.h_plp_in;
+    int32_t* rows = (int32_t*)(R.h_plp_in + 8 * (P + 1));
+    int32_t* n_top = rows + P;
+    gather[0] = 0;   // never read
+    int64_t j = 0;
+    for (int64_t b = 0; b < batch; ++b) {
+        if (ask[b] < 0) continue;
+        for (int64_t r = R.h_seq[b]; r + 1 < R.h_seq[b + 1]; ++r, ++j) {   // the request's last row predicts its first generated token
+            gather[j + 1] = r + 1;
+            rows[j] = (int32_t)r;
+            n_top[j] = ask[b];
+        }
+    }
+    HIPCK(c, rank, hipMemcpyAsync(R.d_plp_in, R.h_plp_in, (size_t)(8 * (P + 1) + 8 * P), hipMemcpyHostToDevice, R.stream));
+    HIPCK(c, rank, hipEventRecord(R.plp_ev, R.stream));
+    R.plp_n = P;
+    R.plp_top = top;
+    return 0;
+}
+
+int pplhip_prompt_logprobs(pplhip_ctx* c, int rank, pplhip_prompt_logprobs_out* out) {
+    if (!c || rank < 0 || rank >= (int)c->ranks.size() || !out) return PPLHIP_INVALID_VALUE;
+    const Rank& R = c->ranks[rank];
+    memset(out, 0, sizeof(*out));
+    const int64_t P = R.plp_done;
+    if (P == 0) return 0;
+    out->positions = P;
+    out->rows = (const int32_t*)(R.h_plp_out + R.cap_T * PLP_OUT_BYTES);
+    out->logprobs = (const float*)R.h_plp_out;
+    out->ranks = (const int32_t*)(R.h_plp_out + 4 * P);
+    out->top_tokens = (const int32_t*)(R.h_plp_out + 8 * P);
+    out->top_logprobs = (const float*)(R.h_plp_out + 8 * P + 4 * P * PPLHIP_TOP_LOGPROBS_MAX);
+    return 0;
+}
+
+// The asked prompt rows of the staged step, in front of the step's own K11 and through its buffers: R.hn and R.logits are free until the
+// step's own norm and lm_head write them, and a chunk of cap_B rows is the largest M they were sized for.  Per chunk: the final
+// (Skip)RMSNorm of the chunk's rows, the lm_head, one workgroup per position; then one download for all chunks.
+// The rows are selected with the norm's gathering form (row gather[j + 1] - 1).  Checked in rmsnorm_kernel (k_elem.hip): called without
+// residual_out, as K11 calls it, the kernel folds the skip operand (part2 or its split-K slabs) into the row IN REGISTERS only -- R.h and
+// the skip operand are read, never written -- so nothing is folded twice, neither between two chunks nor between these rows and the last
+// rows the step's own K11 norm gathers afterwards (the two sets are disjoint anyway).
+// When the last layer's w2 left its split-K slabs unreduced in the workspace (sl_part2), the step's own norm still has to read them: the
+// lm_head here then runs without the workspace (no split-K) instead of overwriting them.
+static int run_prompt_logprobs(pplhip_ctx* c, int rank, hipStream_t s, const uint16_t* pending, const SplitSlabs& sl_part2) {
+    Rank& R = c->ranks[rank];
+    const pplhip_model_desc& d = c->d;
+    const int hd = d.hidden_dim, V = d.vocab_size;
+    const int64_t P = R.plp_n;
+    const bool slabs = pending && sl_part2.splits > 0;
+    const int64_t* gather = (const int64_t*)R.d_plp_in;
+    const int32_t* rows = (const int32_t*)(R.d_plp_in + 8 * (P + 1));
+    const int32_t* n_top = rows + P;
+    float* lp = (float*)R.d_plp_out;
+    int32_t* rk = (int32_t*)(R.d_plp_out + 4 * P);
+    int32_t* ttok = (int32_t*)(R.d_plp_out + 8 * P);
+    float* tlp = (float*)(R.d_plp_out + 8 * P + 4 * P * PPLHIP_TOP_LOGPROBS_MAX);
+    for (int64_t c0 = 0; c0 < P; c0 += R.cap_B) {
+        const int64_t cn = std::min<int64_t>(R.cap_B, P - c0);
+        HIPCK(c, rank, launch_rmsnorm(s, R.h, pending, R.norm, d.norm_eps, cn, hd, gather + c0, R.hn, nullptr, nullptr, nullptr, pending ? &sl_part2 : nullptr));
+        HIPCK(c, rank, launch_linear(s, R.hn, R.output.w, nullptr, 0, 0, cn, R.output.N, hd, R.logits, V, true, slabs ? nullptr : R.gemm_ws,
+                                     slabs ? 0 : R.gemm_ws_bytes));
+        HIPCK(c, rank, launch_prompt_logprobs(s, R.logits, V, V, rows + c0, (int)cn, R.d_tok, n_top + c0, lp + c0, rk + c0,
+                                              ttok + c0 * PPLHIP_TOP_LOGPROBS_MAX, tlp + c0 * PPLHIP_TOP_LOGPROBS_MAX));
+    }
+    memcpy(R.h_plp_out + R.cap_T * PLP_OUT_BYTES, R.h_plp_in + 8 * (P + 1), (size_t)P * 4);   // the rows, where the next step's staging leaves them alone
+    HIPCK(c, rank, hipMemcpyAsync(R.h_plp_out, R.d_plp_out, (size_t)(R.plp_top ? P * PLP_OUT_BYTES : P * 8), hipMemcpyDeviceToHost, s));
+    R.plp_done = P;
+    return 0;
+}
+
 // A chunk of a step: requests [b0, b0 + bn) = token rows [t0, t0 + tn); the first nd requests of the chunk are
 // decode rows.  A step runs as ONE chunk or as two (plan_step).
 using Chunk = pplhip_chunk;
@@ -2126,6 +2257,13 @@ static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& set
         HIPCK(c, rank, hipEventRecord(R.ev_join, R.stream2));
         HIPCK(c, rank, hipStreamWaitEvent(s, R.ev_join, 0));
     }
+    // prompt logprobs of the rows that asked (pplhip_set_prompt_logprobs), in front of K11 and through its buffers; a step nobody asks in
+    // issues exactly the launches below.  (An asking step has T != B and no tensor parallelism: one lane, no fused norm, no decode graph.)
+    R.plp_done = 0;
+    if (R.plp_n > 0) {
+        if (fuse || comm || dual) return fail(c, rank, PPLHIP_OTHER_ERROR, "prompt logprobs on a step with collectives or two lanes");
+        if ((rc = run_prompt_logprobs(c, rank, s, pending, lane[0].sl_part2))) return rc;
+    }
     // K11: last-token gather + final (Skip)RMSNorm (the last FFN output is folded into the residual of the gathered
     // rows only) + lm_head (+ all-gather of the vocab shards)
     const uint16_t* hn = R.hn;
@@ -2281,6 +2419,7 @@ int pplhip_run(pplhip_ctx* c, int rank, int cache_prefill) {
     Rank& R = c->ranks[rank];
     if (!R.kv_cache) return fail(c, rank, PPLHIP_INVALID_VALUE, "kv slab not allocated");
     HIPCK(c, rank, hipSetDevice(R.device));
+    R.plp_done = 0;   // the results of pplhip_prompt_logprobs belong to one run
     if (R.B == 0) return 0;
     if (R.lora_stale) return fail(c, rank, PPLHIP_INVALID_VALUE, "an adapter slot was unloaded after the step's adapters were set: set the inputs again");
     bool done = false;
@@ -2911,6 +3050,28 @@ int pplhip_op_logit_edit(void* stream, float* logits, int32_t stride, int32_t vo
     if (e == hipSuccess) e = launch_logit_edit(s, logits, stride, vocab, d_rows, (int)list.size(), slots, flags, tb);
     const hipError_t e2 = hipFreeAsync(d_rows, s);
     return op_rc(e != hipSuccess ? e : e2);
+}
+
+// prompt_logprobs_kernel alone.  rows and n_top are read back and checked here: the kernel indexes `targets` with the former
+int pplhip_op_prompt_logprobs(void* stream, const float* logits, int32_t stride, int32_t vocab, const int32_t* rows, int32_t n_rows,
+                              const int64_t* targets, int64_t n_targets, const int32_t* n_top, float* out_logprob, int32_t* out_rank,
+                              int32_t* out_top_tok, float* out_top_logprob) {
+    if (n_rows < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
+    if (n_rows == 0) return 0;
+    if (!logits || !rows || !targets || !n_top || !out_logprob || !out_rank) return PPLHIP_INVALID_VALUE;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> hr(n_rows), hn(n_rows);
+    hipError_t e = hipMemcpyAsync(hr.data(), rows, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hn.data(), n_top, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    bool top = false;
+    for (int32_t j = 0; j < n_rows; ++j) {
+        if (hn[j] < 0 || hn[j] > PPLHIP_TOP_LOGPROBS_MAX || hr[j] < -1 || (int64_t)hr[j] + 1 >= n_targets) return PPLHIP_INVALID_VALUE;
+        top = top || hn[j] > 0;
+    }
+    if (top && (!out_top_tok || !out_top_logprob)) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_prompt_logprobs(s, logits, stride, vocab, rows, n_rows, targets, n_top, out_logprob, out_rank, out_top_tok, out_top_logprob));
 }
 
 int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u) {

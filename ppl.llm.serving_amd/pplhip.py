@@ -89,6 +89,11 @@ class LogitEditArgs(C.Structure):
                 ("batch_stride", C.c_int32)]
 
 
+class PromptLogprobsOut(C.Structure):
+    _fields_ = [("positions", C.c_int64), ("rows", C.c_void_p), ("logprobs", C.c_void_p), ("ranks", C.c_void_p), ("top_tokens", C.c_void_p),
+                ("top_logprobs", C.c_void_p)]
+
+
 class PenaltyArgs(C.Structure):
     _fields_ = [("temperatures", C.c_void_p), ("repetition_penalties", C.c_void_p), ("presence_penalties", C.c_void_p),
                 ("frequency_penalties", C.c_void_p), ("batch_slots", C.c_void_p), ("batch", C.c_int32),
@@ -144,11 +149,11 @@ SYMBOLS = [
     "pplhip_kv_block_bytes", "pplhip_kv_capacity", "pplhip_kv_alloc", "pplhip_kv_ptrs", "pplhip_kv_read",
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
-    "pplhip_set_inputs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
+    "pplhip_set_inputs", "pplhip_set_prompt_logprobs", "pplhip_prompt_logprobs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
     "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_logit_edit", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -235,6 +240,10 @@ def lib():
         if hasattr(L, "pplhip_top_logprobs"):
             L.pplhip_top_logprobs.argtypes = [vp, vp, C.POINTER(TopLogprobsArgs), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
             L.pplhip_op_top_logprobs.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+        if hasattr(L, "pplhip_set_prompt_logprobs"):
+            L.pplhip_set_prompt_logprobs.argtypes = [vp, C.c_int, vp, i64]
+            L.pplhip_prompt_logprobs.argtypes = [vp, C.c_int, C.POINTER(PromptLogprobsOut)]
+            L.pplhip_op_prompt_logprobs.argtypes = [vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp]
         if hasattr(L, "pplhip_logit_edit"):
             L.pplhip_logit_rule_set.argtypes = [vp, i32, C.POINTER(LogitRule)]
             L.pplhip_logit_edit.argtypes = [vp, vp, C.POINTER(LogitEditArgs)]
@@ -512,6 +521,27 @@ class Context:
         """after set_inputs, before run: the adapter slot of every request of the step (-1: none)"""
         s = np.ascontiguousarray(slots, dtype=np.int32)
         self._ck(lib().pplhip_set_adapters(self.h, rank, s.ctypes.data, len(s)), rank, "set_adapters")
+
+    def set_prompt_logprobs(self, rank, ask):
+        """after set_inputs, before run: per request of the step -1 (off), 0 (logprob and rank of every prompt token) or n in 1 .. 20
+        (also the first n entries of every position's ranking)"""
+        a = np.ascontiguousarray(ask, dtype=np.int32)
+        self._ck(lib().pplhip_set_prompt_logprobs(self.h, rank, a.ctypes.data, len(a)), rank, "set_prompt_logprobs")
+
+    def prompt_logprobs(self, rank=0):
+        """the prompt logprobs of the last run, copied out of the library's pinned block: call it after a synchronisation (sync(),
+        copy_logits() or the sampler) and before the next run.  (rows [P], logprobs [P], ranks [P], top_tokens [P, 20], top_logprobs
+        [P, 20]); P = 0 when the run had no ask."""
+        o = PromptLogprobsOut()
+        self._ck(lib().pplhip_prompt_logprobs(self.h, rank, C.byref(o)), rank, "prompt_logprobs")
+        P = o.positions
+
+        def arr(p, ct, dt, shape):
+            if P == 0:
+                return np.empty(shape, dtype=dt)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=shape).copy()
+        return (arr(o.rows, C.c_int32, np.int32, (P,)), arr(o.logprobs, C.c_float, np.float32, (P,)), arr(o.ranks, C.c_int32, np.int32, (P,)),
+                arr(o.top_tokens, C.c_int32, np.int32, (P, TOP_LOGPROBS_MAX)), arr(o.top_logprobs, C.c_float, np.float32, (P, TOP_LOGPROBS_MAX)))
 
     def run(self, rank, cache_prefill=0):
         self._ck(lib().pplhip_run(self.h, rank, cache_prefill), rank, "run")

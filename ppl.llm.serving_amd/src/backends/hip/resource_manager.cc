@@ -36,6 +36,25 @@ RetCode HipRuntime::Run(bool is_prefix_cache_hit) {
     return FromPplHipStatus(pplhip_run(ctx_, rank_, is_prefix_cache_hit ? 1 : 0));
 }
 
+static_assert(PostProcessor::kTopLogprobsMax == PPLHIP_TOP_LOGPROBS_MAX, "interface and library disagree");
+
+RetCode HipRuntime::SetPromptLogprobs(const int32_t* ask_host, int64_t batch) {
+    return FromPplHipStatus(pplhip_set_prompt_logprobs(ctx_, rank_, ask_host, batch));
+}
+
+RetCode HipRuntime::GetPromptLogprobs(PromptLogprobsView* out) {
+    pplhip_prompt_logprobs_out o;
+    const int rc = pplhip_prompt_logprobs(ctx_, rank_, &o);
+    if (rc) return FromPplHipStatus(rc);
+    out->positions = o.positions;
+    out->rows = o.rows;
+    out->logprobs = o.logprobs;
+    out->ranks = o.ranks;
+    out->top_tokens = o.top_tokens;
+    out->top_logprobs = o.top_logprobs;
+    return RC_SUCCESS;
+}
+
 float* HipRuntime::GetLogits(int64_t* batch_stride) {
     float* p = nullptr;
     pplhip_logits(ctx_, rank_, &p, batch_stride);

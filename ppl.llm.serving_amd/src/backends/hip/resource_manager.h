@@ -19,6 +19,8 @@ public:
     HipRuntime(pplhip_ctx* ctx, int rank) : ctx_(ctx), rank_(rank) {}
     ppl::common::RetCode SetInputs(const StepInputs&) override;
     ppl::common::RetCode Run(bool is_prefix_cache_hit) override;
+    ppl::common::RetCode SetPromptLogprobs(const int32_t* ask_host, int64_t batch) override;
+    ppl::common::RetCode GetPromptLogprobs(PromptLogprobsView* out) override;
     float* GetLogits(int64_t* batch_stride) override;
     const char* GetLastError() const override { return pplhip_last_error(ctx_, rank_); }
 

@@ -42,6 +42,7 @@ public:
             t.n = (int32_t)std::min<size_t>(r.top_tokens.size(), PPLSRV_TOP_LOGPROBS_MAX);
             for (int32_t j = 0; j < t.n; ++j) { t.tokens[j] = r.top_tokens[j]; t.logprobs[j] = r.top_logprobs[j]; }
             top_.push_back(t);
+            prompt_.push_back(PromptLists{r.prompt_logprobs, r.prompt_ranks, r.prompt_top_tokens, r.prompt_top_logprobs});
         }
         cv_.notify_all();
     }
@@ -54,18 +55,52 @@ public:
         q_.push_back(o);
         text_.emplace_back();
         top_.emplace_back();
+        prompt_.emplace_back();
         cv_.notify_all();
     }
-    int Poll(pplsrv_response* out, int max, int timeout_ms, char* text_buf, int64_t text_cap, pplsrv_top_logprobs* tops) {
+    // where pplsrv_poll_prompt_logprobs wants a response's prompt lists: per response a record, the numbers back to back in the buffers
+    struct PromptOut {
+        pplsrv_prompt_logprobs* recs = nullptr;
+        float* logprobs = nullptr;
+        int32_t* ranks = nullptr;
+        int64_t cap = 0;
+        int32_t* top_tokens = nullptr;
+        float* top_logprobs = nullptr;
+        int64_t top_cap = 0;
+    };
+    int Poll(pplsrv_response* out, int max, int timeout_ms, char* text_buf, int64_t text_cap, pplsrv_top_logprobs* tops,
+             const PromptOut* po = nullptr) {
         std::unique_lock<std::mutex> lk(mu_);
         if (q_.empty() && timeout_ms > 0) cv_.wait_for(lk, std::chrono::milliseconds(timeout_ms), [&] { return !q_.empty(); });
         int n = 0;
-        int64_t used = 0;
+        int64_t used = 0, p_used = 0, t_used = 0;
         while (n < max && !q_.empty()) {
             const std::string& t = text_.front();
             // a response whose text does not fit any more stays queued for the next call (unless it could never fit)
             if (text_buf && !t.empty() && used + (int64_t)t.size() > text_cap && n > 0) break;
+            const PromptLists& pl = prompt_.front();
+            const int64_t np = (int64_t)pl.logprobs.size(), nt = (int64_t)pl.top_tokens.size();
+            const bool fits = po && po->logprobs && po->ranks && p_used + np <= po->cap && (nt == 0 || (po->top_tokens && po->top_logprobs && t_used + nt <= po->top_cap));
+            if (po && np > 0 && !fits && n > 0) break;   // the same rule for a response whose prompt lists do not fit any more
             out[n] = q_.front();
+            if (po && po->recs) {
+                pplsrv_prompt_logprobs& rec = po->recs[n];
+                rec.positions = (int32_t)np;
+                rec.n_top = np > 0 ? (int32_t)(nt / np) : 0;
+                rec.off = rec.top_off = -1;
+                if (np > 0 && fits) {
+                    memcpy(po->logprobs + p_used, pl.logprobs.data(), (size_t)np * 4);
+                    memcpy(po->ranks + p_used, pl.ranks.data(), (size_t)np * 4);
+                    rec.off = p_used;
+                    p_used += np;
+                    if (nt > 0) {
+                        memcpy(po->top_tokens + t_used, pl.top_tokens.data(), (size_t)nt * 4);
+                        memcpy(po->top_logprobs + t_used, pl.top_logprobs.data(), (size_t)nt * 4);
+                        rec.top_off = t_used;
+                        t_used += nt;
+                    }
+                }
+            }
             if (text_buf && !t.empty() && used + (int64_t)t.size() <= text_cap) {
                 memcpy(text_buf + used, t.data(), t.size());
                 out[n].text_off = used;
@@ -77,6 +112,7 @@ public:
             q_.pop_front();
             text_.pop_front();
             top_.pop_front();
+            prompt_.pop_front();
         }
         return n;
     }
@@ -87,6 +123,12 @@ private:
     std::deque<pplsrv_response> q_;
     std::deque<std::string> text_;  // Response::generated of q_[i]
     std::deque<pplsrv_top_logprobs> top_;  // Response::top_tokens / top_logprobs of q_[i]
+    struct PromptLists {
+        std::vector<float> logprobs;
+        std::vector<int32_t> ranks, top_tokens;
+        std::vector<float> top_logprobs;
+    };
+    std::deque<PromptLists> prompt_;       // Response::prompt_* of q_[i]
 };
 
 }  // namespace
@@ -185,6 +227,11 @@ int pplsrv_submit_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t*
 
 int pplsrv_submit_rules(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
                         const pplsrv_rule* const* rules, int32_t n) {
+    return pplsrv_submit_prompt_logprobs(s, reqs, slots, seeds, num_logprobs, rules, nullptr, n);
+}
+
+int pplsrv_submit_prompt_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                  const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs, int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -201,6 +248,7 @@ int pplsrv_submit_rules(pplsrv* s, const pplsrv_request* reqs, const int32_t* sl
         r->lora_slot = slots ? slots[i] : -1;
         r->seed = seeds ? seeds[i] : 0;
         r->num_logprobs = num_logprobs ? num_logprobs[i] : 0;
+        r->prompt_logprobs = prompt_logprobs ? prompt_logprobs[i] : -1;
         if (rules && rules[i]) {
             const pplsrv_rule& u = *rules[i];
             for (int32_t j = 0; j < u.n_bias; ++j) r->logit_bias.emplace_back(u.bias_tokens[j], u.bias_values[j]);
@@ -240,6 +288,21 @@ int pplsrv_poll_logprobs(pplsrv* s, pplsrv_response* out, int32_t max, int32_t t
                          pplsrv_top_logprobs* tops) {
     if (!s || !out || max <= 0) return 0;
     return s->conn.Poll(out, max, timeout_ms, text_buf, text_buf ? text_buf_bytes : 0, tops);
+}
+
+int pplsrv_poll_prompt_logprobs(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms, char* text_buf, int64_t text_buf_bytes,
+                                pplsrv_top_logprobs* tops, pplsrv_prompt_logprobs* prompts, float* logprob_buf, int32_t* rank_buf,
+                                int64_t buf_positions, int32_t* top_token_buf, float* top_logprob_buf, int64_t top_buf_entries) {
+    if (!s || !out || max <= 0) return 0;
+    QueueConnection::PromptOut po;
+    po.recs = prompts;
+    po.logprobs = logprob_buf;
+    po.ranks = rank_buf;
+    po.cap = logprob_buf && rank_buf ? buf_positions : 0;
+    po.top_tokens = top_token_buf;
+    po.top_logprobs = top_logprob_buf;
+    po.top_cap = top_token_buf && top_logprob_buf ? top_buf_entries : 0;
+    return s->conn.Poll(out, max, timeout_ms, text_buf, text_buf ? text_buf_bytes : 0, tops, &po);
 }
 
 int pplsrv_cancel(pplsrv* s, uint64_t id) {

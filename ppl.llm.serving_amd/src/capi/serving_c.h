@@ -116,6 +116,29 @@ typedef struct pplsrv_rule {
 } pplsrv_rule;
 PPLSRV_API int pplsrv_submit_rules(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
                                    const int32_t* num_logprobs, const pplsrv_rule* const* rules, int32_t n);
+/* Prompt logprobs (both structs keep their layout).  pplsrv_submit_prompt_logprobs is pplsrv_submit_rules with prompt_logprobs[i] =
+ * Request::prompt_logprobs of reqs[i]: -1 off, 0 the logprob and rank of every prompt token but the first under the model's own
+ * distribution, 1 .. 20 also that many entries of every position's ranking (above 20: 20, below -1: -1; NULL = nobody asks).  Such a
+ * request takes no prefix-cache hit.  On a backend without prompt logprobs (tensor parallelism among them) it fails alone (PPLSRV_FAILED).
+ * pplsrv_poll_prompt_logprobs is pplsrv_poll_logprobs (text_buf and tops may be NULL) with prompts[i] the record of out[i]: the response
+ * that carries a request's first token has positions = prompt length - 1 numbers at logprob_buf[off ..) and rank_buf[off ..), position
+ * t - 1 for prompt token t, and for n_top >= 1 positions x n_top entries at top_token_buf[top_off ..) / top_logprob_buf[top_off ..), n_top
+ * per position, best first (token -1 / -inf behind the vocabulary); every other response has positions = 0.  The buffers hold
+ * buf_positions and top_buf_entries numbers for the whole call, filled back to back; a response whose lists do not fit any more stays
+ * queued for the next call, and one that alone does not fit is delivered with off = top_off = -1. */
+typedef struct pplsrv_prompt_logprobs {
+    int32_t positions;
+    int32_t n_top;
+    int64_t off;
+    int64_t top_off;
+} pplsrv_prompt_logprobs;
+PPLSRV_API int pplsrv_submit_prompt_logprobs(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                             const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs,
+                                             int32_t n);
+PPLSRV_API int pplsrv_poll_prompt_logprobs(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms, char* text_buf,
+                                           int64_t text_buf_bytes, pplsrv_top_logprobs* tops, pplsrv_prompt_logprobs* prompts,
+                                           float* logprob_buf, int32_t* rank_buf, int64_t buf_positions, int32_t* top_token_buf,
+                                           float* top_logprob_buf, int64_t top_buf_entries);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

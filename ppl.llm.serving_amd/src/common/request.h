@@ -32,6 +32,10 @@ struct Request final {
     std::shared_ptr<std::unordered_set<int>> stop_tokens;
     int32_t lora_slot = -1;  // LoRA adapter slot of this request (HipResourceManager::LoadAdapter), -1 = the base model
     uint64_t seed = 0;       // sampling seed (GeneratorConfig::per_request_sampling), 0 = none: the generator gives the request one
+    // logprob and rank of every prompt token but the first under the model's own distribution (Response::prompt_logprobs): -1 off, 0 the
+    // token alone, 1 .. 20 also the first n entries of every position's ranking; above 20: 20, below -1: -1.  Such a request takes no
+    // prefix-cache hit (a cached prefix has no hidden states to score): its prefill starts at position 0
+    int32_t prompt_logprobs = -1;
     int32_t num_logprobs = 0;  // ranked alternatives per generated token (Response::top_tokens); above 20: 20, negative: 0
     // logit rules (DESIGN.md "numerics", logit rules row; validated when the request is admitted, logit_rule.h):
     std::vector<std::pair<int32_t, float>> logit_bias;   // (token, value added to its raw logit); -inf bans the token
@@ -54,6 +58,14 @@ struct Response final {
     // the request did not ask, else min(num_logprobs, vocab_size) entries; entry 0 is the greedy token
     std::vector<int32_t> top_tokens;
     std::vector<float> top_logprobs;
+    // Request::prompt_logprobs >= 0, on the response that carries the request's FIRST generated token only: for prompt position t = 1 ..
+    // L-1, at [t - 1], log softmax(logits[t-1])[prompt[t]] over the raw logits and the token's rank (0: it is the greedy token); for n >= 1
+    // also n entries per position, at [(t - 1) * n ..), best first, entries behind the vocabulary token -1 / -inf.  Empty otherwise
+    // (a prompt of one token asks for nothing)
+    std::vector<float> prompt_logprobs;
+    std::vector<int32_t> prompt_ranks;
+    std::vector<int32_t> prompt_top_tokens;
+    std::vector<float> prompt_top_logprobs;
 };
 
 struct GeneratorReqCounter final {

@@ -83,10 +83,29 @@ struct StepInputs {
     const int32_t* lora_slots = nullptr;     // [B] adapter slot per request, -1 = none; NULL when no request of the step has one
 };
 
+// Prompt logprobs of one step (DESIGN.md "numerics", prompt logprobs row): position i is packed row rows[i] of the step (ascending), scored
+// against token_inputs[rows[i] + 1]; top_tokens / top_logprobs are [positions, PostProcessor::kTopLogprobsMax], the first n slots of a
+// position whose request asked n >= 1 (entries behind the vocabulary: token -1).  Backend-owned host memory.
+struct PromptLogprobsView {
+    int64_t positions = 0;
+    const int32_t* rows = nullptr;
+    const float* logprobs = nullptr;
+    const int32_t* ranks = nullptr;
+    const int32_t* top_tokens = nullptr;
+    const float* top_logprobs = nullptr;
+};
+
 // the runtime handle of one tensor-parallel rank (ppl::nn::Runtime + its bound tensors in the reference)
 class Runtime {
 public:
     virtual ~Runtime() {}
+    // Prompt logprobs.  SetPromptLogprobs: ask_host [batch], -1 (off) .. 20 per request of the step SetInputs staged, between SetInputs
+    // and Run; request b with ask >= 0 has its rows s .. e-2 scored against the tokens that follow them, under the model's own
+    // distribution (raw logits).  The engine calls it only on steps in which a request asks.  GetPromptLogprobs: the results of the last
+    // Run, valid once the step's sampler call has returned and until the next Run.  A backend that cannot keeps these defaults, and the
+    // requests that ask are failed.
+    virtual ppl::common::RetCode SetPromptLogprobs(const int32_t* /*ask_host*/, int64_t /*batch*/) { return ppl::common::RC_UNSUPPORTED; }
+    virtual ppl::common::RetCode GetPromptLogprobs(PromptLogprobsView* /*out*/) { return ppl::common::RC_UNSUPPORTED; }
     virtual ppl::common::RetCode SetInputs(const StepInputs&) = 0;           // SetInputTask (async)
     virtual ppl::common::RetCode Run(bool is_prefix_cache_hit) = 0;          // RunModelTask (async)
     virtual float* GetLogits(int64_t* batch_stride) = 0;                     // logits tensor: device ptr + dim(1)

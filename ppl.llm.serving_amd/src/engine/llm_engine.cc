@@ -97,6 +97,22 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
     }
     step_counter_->global.set_input_cost += step_counter_->current.set_input_cost;
 
+    // prompt logprobs: the ask goes to rank 0 between its inputs and its run, only on steps in which a request asks (the generator takes a
+    // request's entry back after its first step); under tensor parallelism the backend refuses and the asking requests fail alone
+    bool prompt_asks = false;
+    for (int32_t n : in.prompt_logprobs_list) prompt_asks = prompt_asks || n >= 0;
+    if (prompt_asks) {
+        rc = runtimes_[0]->SetPromptLogprobs(in.prompt_logprobs_list.data(), running_batch);
+        if (rc == RC_UNSUPPORTED) {
+            out->prompt_unsupported = true;
+            prompt_asks = false;
+        } else if (rc != RC_SUCCESS) {
+            *error_msg = "SetPromptLogprobs failed: " + std::string(GetRetCodeStr(rc)) + ": " + runtimes_[0]->GetLastError();
+            LOG(ERROR) << *error_msg;
+            return RC_OTHER_ERROR;
+        }
+    }
+
     {
         utils::TimingGuard timing(&step_counter_->current.model_forward_cost);
         rc = utils::ParallelExecute(RunDecoder, device_worker_pool_, is_prefix_cache_hit, runtimes_);
@@ -172,6 +188,23 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
             *error_msg = std::string(per_request_sampling_ ? "SampleRows" : "SampleTopKTopP") + " failed: " + std::string(GetRetCodeStr(rc));
             LOG(ERROR) << *error_msg;
             return RC_OTHER_ERROR;
+        }
+        if (prompt_asks) {   // the sampler has synchronised: the step's prompt logprobs are readable
+            PromptLogprobsView v;
+            rc = rt0->GetPromptLogprobs(&v);
+            if (rc != RC_SUCCESS) {
+                *error_msg = "GetPromptLogprobs failed: " + std::string(GetRetCodeStr(rc));
+                LOG(ERROR) << *error_msg;
+                return RC_OTHER_ERROR;
+            }
+            const size_t P = (size_t)v.positions, cnt = P * PostProcessor::kTopLogprobsMax;
+            if (P > 0) {
+                out->prompt_rows.assign(v.rows, v.rows + P);
+                out->prompt_logprobs.assign(v.logprobs, v.logprobs + P);
+                out->prompt_ranks.assign(v.ranks, v.ranks + P);
+                out->prompt_top_tokens.assign(v.top_tokens, v.top_tokens + cnt);
+                out->prompt_top_logprobs.assign(v.top_logprobs, v.top_logprobs + cnt);
+            }
         }
         if (top_rows > 0) {
             const size_t cnt = (size_t)top_rows * PostProcessor::kTopLogprobsMax;

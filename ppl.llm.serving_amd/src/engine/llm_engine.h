@@ -37,6 +37,7 @@ struct ModelInput {
     std::vector<float> frequency_penalty_list;
     std::vector<int64_t> batch_slots;
     std::vector<int32_t> lora_slots;  // adapter slot per request (Request::lora_slot), -1 = none
+    std::vector<int32_t> prompt_logprobs_list;  // prompt logprobs per request (Request::prompt_logprobs, clamped to -1 .. 20; -1 again after the request's first step)
     std::vector<int32_t> num_logprobs_list;  // top-N logprobs per request (Request::num_logprobs, clamped to 0 .. 20)
     // logit rules per request: 0 = the request has none; bit 0 = apply the mask and bias of the rule in its batch slot, bit 1 = suppress
     // the rule's stop tokens (set while the request has produced fewer than min_new_tokens tokens)
@@ -50,7 +51,12 @@ struct ModelOutput {
     std::vector<int32_t> top_tokens;
     std::vector<float> top_logprobs;
     int32_t top_rows = 0;
-    bool top_unsupported = false;  // a row asked and the backend has no TopLogprobs: the generator fails those requests
+    bool top_unsupported = false;
+    // prompt logprobs of the step, ascending packed row: position i scores row prompt_rows[i]; the top arrays are
+    // [positions, PostProcessor::kTopLogprobsMax]
+    std::vector<int32_t> prompt_rows, prompt_ranks, prompt_top_tokens;
+    std::vector<float> prompt_logprobs, prompt_top_logprobs;
+    bool prompt_unsupported = false;  // a request asked and the backend has no SetPromptLogprobs: the generator fails those requests  // a row asked and the backend has no TopLogprobs: the generator fails those requests
     void Clear() {
         output_token.clear();
         logprobs.clear();
@@ -58,6 +64,12 @@ struct ModelOutput {
         top_logprobs.clear();
         top_rows = 0;
         top_unsupported = false;
+        prompt_rows.clear();
+        prompt_ranks.clear();
+        prompt_top_tokens.clear();
+        prompt_logprobs.clear();
+        prompt_top_logprobs.clear();
+        prompt_unsupported = false;
     }
     void Resize(int32_t n) {
         output_token.resize(n);

@@ -229,8 +229,12 @@ bool LLMGenerator::ReserveKv(const LlmRequest& req, Admission* adm, int32_t* coo
         const int64_t P = model_config_.page_size;
         // 1. longest chain of cached full pages: h_i = HashCombine(h_{i-1}, page i tokens)
         // (the chain of a request on an adapter starts from the adapter's uid: its K/V are not the base model's, nor another adapter's)
+        // A request that asks for prompt logprobs matches nothing: a cached prefix has no hidden states to score, so its prefill starts at
+        // position 0 and every position is computed.  It still publishes its pages in step 3, up to the first one that is cached already
+        // (an existing hash keeps its page, and a request's published pages are the leading ones of its list).
+        const bool scores_prompt = req.orig->prompt_logprobs >= 0;
         uint64_t prev_hash = req.lora_uid, start = 0;
-        for (; start + P <= tokens.size(); start += P) {
+        for (; !scores_prompt && start + P <= tokens.size(); start += P) {
             const uint64_t h = utils::HashCombine(prev_hash, tokens.data() + start, (int32_t)P);
             const int64_t page_id = prefix_cache_mgr_.Find(h);
             if (page_id == -1) break;
@@ -265,6 +269,7 @@ bool LLMGenerator::ReserveKv(const LlmRequest& req, Admission* adm, int32_t* coo
         // 3. publish the remaining full prompt pages
         for (uint64_t pos = start; pos + P <= tokens.size(); pos += P) {
             const uint64_t h = utils::HashCombine(prev_hash, tokens.data() + pos, (int32_t)P);
+            if (scores_prompt && prefix_cache_mgr_.Find(h) != -1) break;
             prefix_cache_mgr_.Insert(h, adm->page_list[pos / P]);
             prev_hash = h;
             adm->hash_list.push_back(h);
@@ -369,6 +374,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     t.lora_slot = r.lora_slot;
     t.seed = r.seed ? r.seed : SplitMix64(generator_config_.sampling_seed + ++unseeded_requests_);
     t.num_logprobs = std::min(std::max(r.num_logprobs, 0), PostProcessor::kTopLogprobsMax);
+    t.prompt_logprobs = std::min(std::max(r.prompt_logprobs, -1), PostProcessor::kTopLogprobsMax);
     // the logit rule goes up once, now that the request has its slot and before its first step.  A slot's record is never cleared: it is
     // read only while its owner's flags are set, and the next owner with a rule overwrites it
     uint32_t logit_flags = 0;
@@ -415,6 +421,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     in->batch_slots.push_back(t.slot_index);
     in->lora_slots.push_back(t.lora_slot);
     in->num_logprobs_list.push_back(t.num_logprobs);
+    in->prompt_logprobs_list.push_back(t.prompt_logprobs);
     in->logit_flags.push_back(logit_flags);
     if (mode == 0) in->cache_indices.push_back(adm.cache_index);
     else in->max_pages = std::max<int64_t>((int64_t)t.page_list.size(), in->max_pages);
@@ -469,6 +476,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
         in->batch_slots[keep] = in->batch_slots[i];
         in->lora_slots[keep] = in->lora_slots[i];
         in->num_logprobs_list[keep] = in->num_logprobs_list[i];
+        in->prompt_logprobs_list[keep] = in->prompt_logprobs_list[i];
         in->logit_flags[keep] = in->logit_flags[i];
         ++keep;
     }
@@ -486,6 +494,7 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
     in->batch_slots.resize(keep);
     in->lora_slots.resize(keep);
     in->num_logprobs_list.resize(keep);
+    in->prompt_logprobs_list.resize(keep);
     in->logit_flags.resize(keep);
     LOG(DEBUG) << "Rest tasks: " << keep;
 }
@@ -557,6 +566,10 @@ void LLMGenerator::SendTokens(const std::vector<TidGenToken>& tokens) {
         r.is_special = g.is_special;
         r.top_tokens = g.top_tokens;
         r.top_logprobs = g.top_logprobs;
+        r.prompt_logprobs = g.prompt_logprobs;
+        r.prompt_ranks = g.prompt_ranks;
+        r.prompt_top_tokens = g.prompt_top_tokens;
+        r.prompt_top_logprobs = g.prompt_top_logprobs;
         if (!g.is_token_in_out && tokenizer_) {
             int tok = g.token;
             tokenizer_->Decode(&tok, 1, &r.generated);
@@ -643,6 +656,7 @@ void LLMGenerator::Generate() {
             auto tokens = std::make_shared<std::vector<TidGenToken>>();
             tokens->reserve(running_batch);
             int32_t top_row = 0;  // the place of the next asking row in the compact top-N results
+            size_t prompt_pos = 0;  // the place of the next asking request's first position in the step's prompt logprobs
             for (int row = 0; row < running_batch; ++row) {
                 TidData* t = tid_list_[row];
                 ++t->gen_tokens_cnt;
@@ -664,7 +678,12 @@ void LLMGenerator::Generate() {
                 const bool hit_stop = t->early_stopping &&
                     (generator_config_.stop_tokens.count(tok) || (t->stop_tokens && t->stop_tokens->count(tok)));
                 // a request that asks for top-N logprobs on a backend without them fails alone: it leaves like a finished one, unanswered
-                const bool no_top = (t->num_logprobs > 0 && out.top_unsupported) || t->rule_failed;
+                // the prompt logprobs of a request arrive with its first token: its fed - 1 positions are the next ones of the step's results
+                const bool scores_prompt = in.prompt_logprobs_list[row] >= 0;
+                const size_t prompt_n = scores_prompt && !out.prompt_unsupported ? (size_t)(fed - 1) : 0;
+                in.prompt_logprobs_list[row] = -1;   // asked once: later steps carry nothing
+                const bool no_prompt = scores_prompt && out.prompt_unsupported;
+                const bool no_top = (t->num_logprobs > 0 && out.top_unsupported) || t->rule_failed || no_prompt;
                 if (t->rest_iters <= 0 || hit_stop || no_top) {
                     flag = t->rest_iters <= 0 ? FinishFlag::LENGTH : FinishFlag::EOS_TOKEN;
                     if (cool_down > 0) --cool_down;
@@ -672,12 +691,25 @@ void LLMGenerator::Generate() {
                     req_list_changed_ = true;
                 }
                 if (no_top) {
+                    prompt_pos += prompt_n;
                     if (t->rule_failed) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "logit rules: the backend could not take the request's rule");
+                    else if (no_prompt) conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "prompt_logprobs: the backend's runtime has no SetPromptLogprobs");
                     else conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "num_logprobs: the backend's post processor has no TopLogprobs");
                     continue;
                 }
                 tokens->push_back(TidGenToken{t->tid, tok, out.logprobs[row], flag, (uint64_t)t->steps, t->is_token_in_out,
-                                              generator_config_.special_tokens.count(tok) > 0, {}, {}});
+                                              generator_config_.special_tokens.count(tok) > 0, {}, {}, {}, {}, {}, {}});
+                if (prompt_n > 0 && prompt_pos + prompt_n <= out.prompt_logprobs.size()) {
+                    TidGenToken& g = tokens->back();
+                    const size_t n = (size_t)t->prompt_logprobs, W = (size_t)PostProcessor::kTopLogprobsMax;
+                    g.prompt_logprobs.assign(out.prompt_logprobs.begin() + prompt_pos, out.prompt_logprobs.begin() + prompt_pos + prompt_n);
+                    g.prompt_ranks.assign(out.prompt_ranks.begin() + prompt_pos, out.prompt_ranks.begin() + prompt_pos + prompt_n);
+                    for (size_t i = prompt_pos; n > 0 && i < prompt_pos + prompt_n; ++i) {
+                        g.prompt_top_tokens.insert(g.prompt_top_tokens.end(), out.prompt_top_tokens.begin() + i * W, out.prompt_top_tokens.begin() + i * W + n);
+                        g.prompt_top_logprobs.insert(g.prompt_top_logprobs.end(), out.prompt_top_logprobs.begin() + i * W, out.prompt_top_logprobs.begin() + i * W + n);
+                    }
+                }
+                prompt_pos += prompt_n;
                 if (t->num_logprobs > 0 && top_row < out.top_rows) {
                     // the row's first n slots; the ones behind the vocabulary (token -1) are padding
                     const int32_t* tt = out.top_tokens.data() + (size_t)top_row * PostProcessor::kTopLogprobsMax;

@@ -37,6 +37,9 @@ struct TidGenToken final {
     bool is_special;
     std::vector<int32_t> top_tokens;  // Response::top_tokens / top_logprobs
     std::vector<float> top_logprobs;
+    std::vector<float> prompt_logprobs;   // Response::prompt_* (the request's first token only)
+    std::vector<int32_t> prompt_ranks, prompt_top_tokens;
+    std::vector<float> prompt_top_logprobs;
 };
 
 struct FinishedTaskInfo final {
@@ -71,6 +74,7 @@ struct TidData final {
     int64_t cache_hit_count = 0;
     int32_t lora_slot = -1;  // holds a reference in the adapter registry until the request leaves
     uint64_t seed = 0;       // sampling seed: the request's own, or the generator's next one
+    int32_t prompt_logprobs = -1;  // Request::prompt_logprobs, clamped to -1 .. PostProcessor::kTopLogprobsMax
     int32_t num_logprobs = 0;  // Request::num_logprobs, clamped to 0 .. PostProcessor::kTopLogprobsMax
     int32_t min_new_tokens = 0;  // Request::min_new_tokens: bit 1 of the row's logit flags until this many tokens are out
     bool rule_failed = false;    // the upload of its logit rule failed: the request is failed on its first step

@@ -77,6 +77,7 @@ int main(int argc, char** argv) {
             auto r = std::make_shared<Request>((uint64_t)(run * batch + b), "", 1.0f, (uint32_t)gen_len);
             r->early_stopping = false;
             r->num_logprobs = a.Int("--num-logprobs");
+            r->prompt_logprobs = a.Int("--prompt-logprobs");
             r->token_ids = std::make_shared<std::vector<int>>(*prompts[b]);
             reqs.push_back(r);
         }

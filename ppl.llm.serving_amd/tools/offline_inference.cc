@@ -115,7 +115,10 @@ int main(int argc, char** argv) {
     }
 
     if (workload != "scenario")
-        for (auto& r : requests) r->num_logprobs = a.Int("--num-logprobs");
+        for (auto& r : requests) {
+            r->num_logprobs = a.Int("--num-logprobs");
+            r->prompt_logprobs = a.Int("--prompt-logprobs");
+        }
 
     // ---- LoRA adapters: slot = position in --lora-dirs; --lora-map cycled over the requests ---------------------
     {
@@ -191,12 +194,30 @@ int main(int argc, char** argv) {
                 }
                 std::cout << "\n";
             }
+            if (r->prompt_logprobs >= 0) {
+                // per prompt position t = 1 .. L-1: token:logprob:rank, then its alternatives in brackets as token:logprob; then the sum
+                const auto& pl = conn.records()[r->id].prompt;
+                const size_t P = pl.logprobs.size(), n = P ? pl.top_tokens.size() / P : 0;
+                const auto prec = std::cout.precision(9);
+                double sum = 0.0;
+                std::cout << "Prompt logprobs:";
+                for (size_t i = 0; i < P; ++i) {
+                    std::cout << (i ? " | " : " ") << (*r->token_ids)[i + 1] << ":" << pl.logprobs[i] << ":" << pl.ranks[i];
+                    if (n) std::cout << " [";
+                    for (size_t j = 0; j < n; ++j) std::cout << (j ? " " : "") << pl.top_tokens[i * n + j] << ":" << pl.top_logprobs[i * n + j];
+                    if (n) std::cout << "]";
+                    sum += pl.logprobs[i];
+                }
+                std::cout << "\nPrompt logprob sum: " << sum << "\n";
+                std::cout.precision(prec);
+            }
         }
         std::cout << "generation time: " << generate_us / 1e3 << "ms" << std::endl;
     } else if (workload == "scenario") {
         std::map<uint64_t, std::vector<int>> tokens;
         std::map<uint64_t, std::vector<std::vector<int32_t>>> top_tokens;
         std::map<uint64_t, std::vector<std::vector<float>>> top_logprobs;
+        std::map<uint64_t, scenario::PromptLogprobs> prompt;
         std::vector<uint64_t> failed;
         for (auto& r : requests) {
             auto& rec = conn.records()[r->id];
@@ -206,8 +227,9 @@ int main(int argc, char** argv) {
                 top_tokens[r->id] = rec.top_tokens;
                 top_logprobs[r->id] = rec.top_logprobs;
             }
+            if (!rec.failed && r->prompt_logprobs >= 0) prompt[r->id] = rec.prompt;
         }
-        scenario::PrintScenarioResult(tokens, failed, top_tokens, top_logprobs);
+        scenario::PrintScenarioResult(tokens, failed, top_tokens, top_logprobs, prompt);
     } else {
         std::vector<double> ttft, tpot;
         uint64_t out_tokens = 0, in_tokens = 0, failed = 0;

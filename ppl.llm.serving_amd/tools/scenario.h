@@ -4,10 +4,12 @@
 //                  "enable_penalty", "stop_tokens": [..]},
 //    "kv_cache_max_tokens": N,
 //    "requests": [{"id", "tokens": [..], "generation_length", "temperature", "top_p", "top_k", "repetition_penalty",
-//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed", "num_logprobs",
+//                  "presence_penalty", "frequency_penalty", "early_stopping", "stop_tokens": [..], "seed", "num_logprobs", "prompt_logprobs",
 //                  "logit_bias": [[token, value], ..], "allowed_tokens": [..], "banned_tokens": [..], "min_new_tokens"}]}
 // "seed" (this tree's Request only: the sampling seed of --per-request-sampling, 0 or absent = none) is ignored for a request type without it.
 // "num_logprobs" (this tree's Request only: ranked alternatives per generated token, 0 .. 20, 0 or absent = none) likewise.
+// "prompt_logprobs" (this tree's Request only: logprob and rank of every prompt token, -1 or absent = off, 0 .. 20 = with that many ranked
+// alternatives per position) likewise.
 // "logit_bias" / "allowed_tokens" / "banned_tokens" / "min_new_tokens" (this tree's Request only: its logit rule; a value may be the string
 // "-inf"; token ids are taken as written, an id outside the vocabulary fails the request) likewise.
 // Templates: Request / GeneratorConfig are this tree's or the reference's types (same member names by construction).
@@ -16,6 +18,7 @@
 
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <memory>
 #include <sstream>
 #include <unordered_set>
@@ -58,6 +61,11 @@ template <typename RequestT>
 void SetNumLogprobs(RequestT*, int32_t, long) {}
 
 template <typename RequestT>
+auto SetPromptLogprobs(RequestT* q, int32_t n, int) -> decltype(q->prompt_logprobs = n, void()) { q->prompt_logprobs = n; }
+template <typename RequestT>
+void SetPromptLogprobs(RequestT*, int32_t, long) {}
+
+template <typename RequestT>
 auto SetLogitRule(RequestT* q, const utils::JsonValue& r, int) -> decltype(q->min_new_tokens = 0, void()) {
     if (const utils::JsonValue* lb = r.Find("logit_bias"))
         for (const auto& p : lb->arr) {
@@ -90,6 +98,7 @@ std::vector<std::shared_ptr<RequestT>> ScenarioRequests(const utils::JsonValue& 
         q->early_stopping = r.GetBool("early_stopping", true);
         SetSeed(q.get(), (uint64_t)r.GetInt("seed", 0), 0);
         SetNumLogprobs(q.get(), (int32_t)r.GetInt("num_logprobs", 0), 0);
+        SetPromptLogprobs(q.get(), (int32_t)r.GetInt("prompt_logprobs", -1), 0);
         SetLogitRule(q.get(), r, 0);
         q->token_ids = std::make_shared<std::vector<int>>();
         if (const utils::JsonValue* t = r.Find("tokens"))
@@ -124,10 +133,68 @@ void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed) {
     std::cout << "}" << std::endl;
 }
 
+// (JSON has no infinity: a masked entry's logprob goes out as the lowest float)
+template <typename T>
+void PrintScenarioNumber(T v) {
+    if (v < (T)-3.0e38) std::cout << "-3.4028235e38";
+    else std::cout << v;
+}
+
+// what a request's first response brought when it asked for prompt logprobs (Response::prompt_*)
+struct PromptLogprobs {
+    std::vector<float> logprobs;
+    std::vector<int32_t> ranks;
+    std::vector<int32_t> top_tokens;   // n per position, flat
+    std::vector<float> top_logprobs;
+};
+
+// ,"prompt_logprobs": {"id": [..]}, "prompt_ranks": {"id": [..]}, "prompt_top_tokens" / "prompt_top_logprobs": {"id": [[n per position]]}
+// of the requests that asked (PromptMap: id -> PromptLogprobs); nothing when there is none
+template <typename PromptMap>
+void PrintScenarioPrompt(const PromptMap& prompt) {
+    if (prompt.empty()) return;
+    const auto prec = std::cout.precision(9);
+    auto flat = [&](const char* key, auto member) {
+        std::cout << ",\"" << key << "\":{";
+        bool first = true;
+        for (const auto& kv : prompt) {
+            const auto& v = kv.second.*member;
+            std::cout << (first ? "" : ",") << "\"" << kv.first << "\":[";
+            for (size_t i = 0; i < v.size(); ++i) { if (i) std::cout << ","; PrintScenarioNumber(v[i]); }
+            std::cout << "]";
+            first = false;
+        }
+        std::cout << "}";
+    };
+    auto nested = [&](const char* key, auto member) {
+        std::cout << ",\"" << key << "\":{";
+        bool first = true;
+        for (const auto& kv : prompt) {
+            const auto& v = kv.second.*member;
+            const size_t P = kv.second.logprobs.size(), n = P ? v.size() / P : 0;
+            std::cout << (first ? "" : ",") << "\"" << kv.first << "\":[";
+            for (size_t i = 0; i < P; ++i) {
+                std::cout << (i ? "," : "") << "[";
+                for (size_t j = 0; j < n; ++j) { if (j) std::cout << ","; PrintScenarioNumber(v[i * n + j]); }
+                std::cout << "]";
+            }
+            std::cout << "]";
+            first = false;
+        }
+        std::cout << "}";
+    };
+    flat("prompt_logprobs", &PromptLogprobs::logprobs);
+    flat("prompt_ranks", &PromptLogprobs::ranks);
+    nested("prompt_top_tokens", &PromptLogprobs::top_tokens);
+    nested("prompt_top_logprobs", &PromptLogprobs::top_logprobs);
+    std::cout.precision(prec);
+}
+
 // the same, plus "top_tokens" / "top_logprobs": {"id": [[..] per generated token]} of the requests that asked (TopMap: id -> per-token
-// lists); without such a request the line is PrintScenarioResult's
-template <typename TokMap, typename FailedVec, typename TopTokMap, typename TopLpMap>
-void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed, const TopTokMap& top_tokens, const TopLpMap& top_logprobs) {
+// lists) and the prompt logprobs (PrintScenarioPrompt); without such a request the line is PrintScenarioResult's
+template <typename TokMap, typename FailedVec, typename TopTokMap, typename TopLpMap, typename PromptMap = std::map<uint64_t, PromptLogprobs>>
+void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed, const TopTokMap& top_tokens, const TopLpMap& top_logprobs,
+                         const PromptMap& prompt = PromptMap()) {
     PrintScenarioBody(tokens, failed);
     auto lists = [](const char* key, const auto& m) {
         std::cout << ",\"" << key << "\":{";
@@ -155,6 +222,7 @@ void PrintScenarioResult(const TokMap& tokens, const FailedVec& failed, const To
         lists("top_logprobs", top_logprobs);
         std::cout.precision(prec);
     }
+    PrintScenarioPrompt(prompt);
     std::cout << "}" << std::endl;
 }
 

@@ -10,6 +10,7 @@
 #include "common/config.h"
 #include "common/request.h"
 #include "generator/llm_generator.h"
+#include "scenario.h"
 #include "simple_args.h"
 #include "utils/utils.h"
 
@@ -62,6 +63,7 @@ inline void DefineCommonFlags(Args* a) {
     a->Def("--seed", "1234", "workload seed");
     a->Def("--per-request-sampling", "false", "sample every request with its own top_k / top_p / temperature and its own seeded random sequence (off: the first row's top_k for the whole batch and rand(), as the reference)", true);
     a->Def("--num-logprobs", "0", "ranked alternatives per generated token (top-N logprobs, 0 .. 20) asked for by every request of a generated workload");
+    a->Def("--prompt-logprobs", "-1", "logprob and rank of every prompt token under the model's own distribution, asked for by every request of a generated workload: -1 off, 0 the token alone, 1 .. 20 also that many ranked alternatives per position (such a request takes no prefix-cache hit)");
     a->Def("--sampling-seed", "0", "with --per-request-sampling: the n-th request without a seed of its own gets splitmix64(this + n); 0: taken from std::random_device");
 }
 
@@ -125,6 +127,7 @@ public:
         std::vector<int> tokens;
         std::vector<std::vector<int32_t>> top_tokens;   // per generated token: Response::top_tokens / top_logprobs (empty: not asked)
         std::vector<std::vector<float>> top_logprobs;
+        ppl::llm::scenario::PromptLogprobs prompt;      // Response::prompt_* of the request's first response (empty: not asked)
         std::string text;
         Clock::time_point submit, first, last;
         bool finished = false, failed = false;
@@ -144,6 +147,7 @@ public:
             rec.tokens.push_back(r.token);
             rec.top_tokens.push_back(r.top_tokens);
             rec.top_logprobs.push_back(r.top_logprobs);
+            if (!r.prompt_logprobs.empty()) rec.prompt = ppl::llm::scenario::PromptLogprobs{r.prompt_logprobs, r.prompt_ranks, r.prompt_top_tokens, r.prompt_top_logprobs};
             rec.text += r.generated;   // text requests: the detokenised piece(s) of this response
             rec.last = now;
             if (r.finish_flag != ppl::llm::FinishFlag::NOT_FINISHED) {
