@@ -432,6 +432,45 @@ typedef struct pplhip_logit_edit_args {
 PPLHIP_API int pplhip_logit_rule_set(pplhip_ctx* ctx, int32_t slot, const pplhip_logit_rule* rule);
 PPLHIP_API int pplhip_logit_edit(pplhip_ctx* ctx, float* logits_device, const pplhip_logit_edit_args* args);
 
+/* Guided decoding (DESIGN.md "numerics", guided decoding row): the generated bytes of a request stay inside the language of a byte-level
+ * DFA.  A guide is trans [n_states, 256] (the next state of (state, byte); 255 is the dead state, which has no row), accept [n_states] and
+ * the end tokens, which are allowed exactly in accepting states whatever their bytes; a token without bytes is never allowed.  State 0
+ * is the start.  All pointers of these calls but logits_device are HOST memory and are read before the call returns.
+ * pplhip_guide_set_vocab, once per context (a second call, n_tok outside [1, vocab_size], offsets that do not start at 0 or decrease:
+ * PPLHIP_INVALID_VALUE): token t < n_tok is bytes[offsets[t] .. offsets[t + 1]), ids at or behind n_tok are empty; uploaded to local rank 0.
+ * pplhip_guide_load builds the slot's mask, one row of ceil(vocab_size / 32) words per state, with one kernel on local rank 0's stream and
+ * SYNCHRONISES: it happens once per distinct pattern, not per step.  PPLHIP_INVALID_VALUE before any device call, reason in
+ * pplhip_last_error: no vocabulary set, slot outside [0, PPLHIP_GUIDE_MAX_SLOTS) or loaded, n_states outside [1, PPLHIP_GUIDE_MAX_STATES],
+ * n_end outside [0, PPLHIP_LOGIT_STOP_MAX], an end token outside [0, vocab_size), a transition to a state >= n_states other than 255, a
+ * state with neither a live byte nor acceptance.  After the build, a state in which no token at all is allowed (a tokenizer without byte
+ * fallback may have no piece for a byte the pattern needs) frees the slot and returns PPLHIP_INVALID_VALUE with the state named.  That
+ * check is conservative: such a state might be reachable by bytes yet by no sequence of whole tokens, and the guide is refused all the same.
+ * pplhip_guide_unload synchronises local rank 0's stream, then frees the slot (not loaded: PPLHIP_INVALID_VALUE).
+ * pplhip_guide_edit: guide_slots (-1: the row does not ask) and states are host [batch]; one upload and one launch over the asking rows are
+ * queued on local rank 0's stream with no synchronisation; no asking row is no device call and no allocation.  Row b gets -inf at every
+ * token that row states[b] of its slot's mask does not allow.  Call it in front of pplhip_logit_edit and pplhip_penalty.  A slot that is
+ * not loaded or a state outside the slot's [0, n_states) in an asking row, vocab_size other than the model's, batch outside
+ * [0, max_running_batch] or batch_stride < vocab_size: PPLHIP_INVALID_VALUE before any device call.
+ * Arrived without a version bump: a client tells a library that has it by the symbol pplhip_guide_load (dlsym). */
+#define PPLHIP_GUIDE_MAX_SLOTS 16
+#define PPLHIP_GUIDE_MAX_STATES 255
+typedef struct pplhip_guide_desc {
+    const uint8_t* trans;         /* [n_states, 256] */
+    const uint8_t* accept;        /* [n_states] */
+    int32_t n_states;
+    const int32_t* end_tokens;    /* [n_end] */
+    int32_t n_end;
+} pplhip_guide_desc;
+typedef struct pplhip_guide_edit_args {
+    const int32_t* guide_slots;   /* host [B], -1: not asking */
+    const int32_t* states;        /* host [B] */
+    int32_t batch, vocab_size, batch_stride;
+} pplhip_guide_edit_args;
+PPLHIP_API int pplhip_guide_set_vocab(pplhip_ctx* ctx, const uint8_t* bytes, const int64_t* offsets, int32_t n_tok);
+PPLHIP_API int pplhip_guide_load(pplhip_ctx* ctx, int32_t slot, const pplhip_guide_desc* desc);
+PPLHIP_API int pplhip_guide_unload(pplhip_ctx* ctx, int32_t slot);
+PPLHIP_API int pplhip_guide_edit(pplhip_ctx* ctx, float* logits_device, const pplhip_guide_edit_args* args);
+
 /* in-place penalty on the logits of the last run, using the step's device-resident token_inputs /
  * seq_starts / start_pos (llm_engine.cc:204-216). */
 PPLHIP_API int pplhip_penalty(pplhip_ctx* ctx, float* logits_device, const pplhip_penalty_args* args);
@@ -634,6 +673,20 @@ PPLHIP_API int pplhip_op_logit_edit(void* stream, float* logits, int32_t stride,
 PPLHIP_API int pplhip_op_prompt_logprobs(void* stream, const float* logits, int32_t stride, int32_t vocab, const int32_t* rows, int32_t n_rows,
                                          const int64_t* targets, int64_t n_targets, const int32_t* n_top, float* out_logprob,
                                          int32_t* out_rank, int32_t* out_top_tok, float* out_top_logprob);
+/* the two guided-decoding kernels alone (csrc/k_guide.hip), for the tests and the timing script: caller-owned DEVICE memory only.
+ * pplhip_op_guide_build: trans [n_states, 256], accept [n_states], the vocabulary as tok_bytes / tok_off [n_tok + 1], end_tokens [n_end];
+ * writes words 0 .. ceil(vocab / 32) - 1 of mask [n_states, mask_stride] and ORs 1 into any [n_states] (the caller zeroes it) for every
+ * state that allows a token.  Only the shape is validated (n_states outside [1, 255], vocab <= 0, n_tok outside [0, vocab], n_end outside
+ * [0, 64], mask_stride < ceil(vocab / 32), a NULL array: PPLHIP_INVALID_VALUE, nothing launched).
+ * pplhip_op_guide_mask: guide_slots / states are [batch]; masks is [n_slots, n_states, mask_stride], n_slots <= 16.  rows NULL: the list of
+ * the rows with guide_slots[b] >= 0 is made on the host from a read-back, so the call synchronises `stream` before it launches; rows !=
+ * NULL: a device list of n_rows asking rows, launched as it is.  No asking row: no launch. */
+PPLHIP_API int pplhip_op_guide_build(void* stream, const uint8_t* trans, const uint8_t* accept, int32_t n_states, const uint8_t* tok_bytes,
+                                     const int64_t* tok_off, int32_t n_tok, const int32_t* end_tokens, int32_t n_end, int32_t vocab,
+                                     uint32_t* mask, int64_t mask_stride, uint32_t* any);
+PPLHIP_API int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
+                                    const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
+                                    const int32_t* rows, int32_t n_rows);
 /* out_u[b] = u(seeds[b], draws[b]), the generator alone (device pointers) */
 PPLHIP_API int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u);
 

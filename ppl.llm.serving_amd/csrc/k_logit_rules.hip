@@ -16,11 +16,13 @@
 //             -inf for every value validation lets through (finite or -inf), so "the mask wins" and "the stop wins" need no look-up
 // Bias tokens are unique (validated on the host), so pass 3 has no two writers of one element; two equal stops both store -inf.
 //
-// Mask pass, 16-byte path (stride % 4 == 0 and a 16-byte aligned base: the `vec` convention of the sampler kernels): a lane owns the four
+// Mask pass (mask_row_ninf of k_mask_dev.h, shared with k_guide.hip), 16-byte path (stride % 4 == 0 and a 16-byte aligned base: the `vec`
+// convention of the sampler kernels): a lane owns the four
 // consecutive tokens of piece c = 4c .. 4c + 3, whose bits are one nibble of mask word c >> 3, so a word serves eight lanes.  Nibble 0xf:
 // nothing at all.  Nibble 0: one 16-byte store of -inf.  Mixed: a 4-byte store per cleared bit.  The V % 4 tokens behind the last whole
 // piece, and every token of a row off the 16-byte path, go element by element.  No float at or behind V is ever addressed, whatever the
 // tail word's high bits say: the loops stop at V, and bias / stop tokens outside [0, V) are skipped.
+#include "k_mask_dev.h"
 #include "kernels.h"
 
 namespace pplhip {
@@ -45,21 +47,7 @@ __global__ __launch_bounds__(LR_THREADS) void logit_edit_kernel(float* logits, i
     if (edit && head[2]) {
         const uint32_t* __restrict__ mask = tb.mask + slot * tb.mask_stride;
         const bool vec = (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
-        const int nv = vec ? vocab >> 2 : 0;
-        for (int c = tid; c < nv; c += LR_THREADS) {
-            const uint32_t nib = (mask[c >> 3] >> ((c & 7) * 4)) & 15u;
-            if (nib == 15u) continue;
-            if (nib == 0u) {
-                reinterpret_cast<float4*>(row)[c] = make_float4(ninf, ninf, ninf, ninf);
-            } else {
-                float* p = row + c * 4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (!((nib >> j) & 1u)) p[j] = ninf;
-            }
-        }
-        for (int v = nv * 4 + tid; v < vocab; v += LR_THREADS)
-            if (!((mask[v >> 5] >> (v & 31)) & 1u)) row[v] = ninf;
+        mask_row_ninf<LR_THREADS>(row, mask, vocab, vec, tid);
     }
     __syncthreads();
     if (tid < n_stop) {

@@ -279,6 +279,27 @@ struct LogitRuleTable {
 hipError_t launch_logit_edit(hipStream_t s, float* logits, int stride, int vocab, const int32_t* rows, int n_rows, const int32_t* slots,
                              const uint32_t* flags, const LogitRuleTable& table);
 
+// ---- k_guide.hip: guided decoding ------------------------------------------------------------------
+// A guide is a byte-level DFA: trans [n_states, 256] names the next state, GUIDE_DEAD the dead one (it has no row); accept [n_states].
+// Its mask [n_states, mask_stride] words holds one allowed-token row per state, token v at bit v & 31 of word v >> 5.
+constexpr int GUIDE_MAX_SLOTS = 16;     // PPLHIP_GUIDE_MAX_SLOTS
+constexpr int GUIDE_MAX_STATES = 255;   // PPLHIP_GUIDE_MAX_STATES: live states 0 .. 254
+constexpr int GUIDE_DEAD = 255;
+struct GuideTable {
+    const uint32_t* mask[GUIDE_MAX_SLOTS];   // NULL: the slot is empty
+    int64_t mask_stride;                     // words from one state's row to the next, the same in every slot
+};
+// The vocabulary is tok_bytes with token t at [tok_off[t], tok_off[t + 1]), t < n_tok <= vocab; end_tokens [n_end] are allowed exactly in
+// accepting states.  Writes words 0 .. ceil(vocab / 32) - 1 of every state's mask row and ORs 1 into any[s] (zeroed by the caller) when
+// state s allows some token.  n_states <= GUIDE_MAX_STATES.
+hipError_t launch_guide_build(hipStream_t s, const uint8_t* trans, const uint8_t* accept, int n_states, const uint8_t* tok_bytes,
+                              const int64_t* tok_off, int n_tok, const int32_t* end_tokens, int n_end, int vocab, uint32_t* mask,
+                              int64_t mask_stride, uint32_t* any);
+// rows: device list of the n_rows batch rows with guide_slots[b] >= 0; guide_slots and states are indexed by the batch row.  Sets
+// logits[b * stride + v] to -inf for every v < vocab whose bit is clear in row states[b] of slot guide_slots[b].  No rows: no launch.
+hipError_t launch_guide_mask(hipStream_t s, float* logits, int stride, int vocab, const int32_t* rows, int n_rows, const int32_t* guide_slots,
+                             const int32_t* states, const GuideTable& table);
+
 // ---- k_prompt_logprobs.hip: prompt logprobs -------------------------------------------------------
 // One workgroup per listed position j < n_rows: logits row j ([n_rows, stride], raw), target tokens[rows[j] + 1] (the step's packed token
 // ids), n_top[j] in 0 .. 20.  out_lp / out_rank [n_rows]; out_top_tok / out_top_lp [n_rows, 20], written for n_top[j] >= 1 only (the first

@@ -109,6 +109,7 @@ constexpr int64_t PLP_OUT_BYTES = 4 + 4 + (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
 // head i32 [4] = {n_bias, n_stop, has_mask, 0} | bias tokens i32 [512] | bias values f32 [512] | stops i32 [64] | mask u32 [words, padded to 4]
 // so one copy carries a rule.  pplhip_logit_edit stages slots i32 [cap_B] | flags u32 [cap_B] | row list i32 [cap_B] in a block of its own.
 static_assert(PPLHIP_LOGIT_BIAS_MAX == LOGIT_BIAS_MAX && PPLHIP_LOGIT_STOP_MAX == LOGIT_STOP_MAX, "header and kernel disagree");
+static_assert(PPLHIP_GUIDE_MAX_SLOTS == GUIDE_MAX_SLOTS && PPLHIP_GUIDE_MAX_STATES == GUIDE_MAX_STATES && GUIDE_DEAD == 255, "header and kernel disagree");
 constexpr int64_t LR_HEAD = 16, LR_BIAS_TOK = LR_HEAD, LR_BIAS_VAL = LR_BIAS_TOK + 4 * LOGIT_BIAS_MAX,
                   LR_STOPS = LR_BIAS_VAL + 4 * LOGIT_BIAS_MAX, LR_MASK = LR_STOPS + 4 * LOGIT_STOP_MAX;
 constexpr int LR_RING = 4;   // staging records; a record is reused once the event behind its copy has passed
@@ -189,6 +190,15 @@ struct Rank {
     std::vector<uint8_t> lr_has;
     char *h_lre = nullptr, *d_lre = nullptr;
     hipEvent_t lre_ev = nullptr;
+    // guided decoding: the vocabulary (pplhip_guide_set_vocab; gd_n_tok < 0: none yet), the loaded slots' masks and state counts, and
+    // pplhip_guide_edit's staging block guide slots i32 [cap_B] | states i32 [cap_B] | row list i32 [cap_B] with the event of its copy
+    uint8_t* gd_bytes = nullptr;
+    int64_t* gd_off = nullptr;
+    int gd_n_tok = -1;
+    uint32_t* gd_mask[GUIDE_MAX_SLOTS] = {};
+    int gd_states[GUIDE_MAX_SLOTS] = {};
+    char *h_gde = nullptr, *d_gde = nullptr;
+    hipEvent_t gde_ev = nullptr;
     // prompt logprobs (k_prompt_logprobs.hip), all allocated by the first pplhip_set_prompt_logprobs that asks, for cap_T positions.
     // Going up in one copy, P the staged positions: gather i64 [P + 1] (entry j + 1 = row_j + 1: the final norm's gathering form reads row
     // gather[j + 1] - 1) | rows i32 [P] | n_top i32 [P].  Coming down in one copy: logprob f32 [P] | rank i32 [P] | top tokens i32 [P, 20] |
@@ -783,6 +793,12 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.h_lre) hipHostFree(R.h_lre);
         for (hipEvent_t e : R.lr_ev) if (e) hipEventDestroy(e);
         if (R.lre_ev) hipEventDestroy(R.lre_ev);
+        if (R.gd_bytes) hipFree(R.gd_bytes);
+        if (R.gd_off) hipFree(R.gd_off);
+        for (uint32_t* m : R.gd_mask) if (m) hipFree(m);
+        if (R.h_gde) hipHostFree(R.h_gde);
+        if (R.d_gde) hipFree(R.d_gde);
+        if (R.gde_ev) hipEventDestroy(R.gde_ev);
         if (R.h_plp_in) hipHostFree(R.h_plp_in);
         if (R.h_plp_out) hipHostFree(R.h_plp_out);
         if (R.plp_ev) hipEventDestroy(R.plp_ev);
@@ -2744,6 +2760,149 @@ int pplhip_logit_edit(pplhip_ctx* c, float* logits_device, const pplhip_logit_ed
     return 0;   // asynchronous: in stream order in front of the step's penalty, top-N logprobs and sampler
 }
 
+// ---- guided decoding ----------------------------------------------------------------------------------------------------------------
+
+int pplhip_guide_set_vocab(pplhip_ctx* c, const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) {
+    if (!c || !offsets) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    if (R.gd_n_tok >= 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: set already");
+    if (n_tok < 1 || n_tok > c->d.vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: n_tok outside [1, vocab_size]");
+    if (offsets[0] != 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: offsets[0] is not 0");
+    for (int i = 0; i < n_tok; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: offsets decrease at token " + std::to_string(i));
+    const int64_t total = offsets[n_tok];
+    if (total > 0 && !bytes) return PPLHIP_INVALID_VALUE;
+    HIPCK(c, 0, hipSetDevice(R.device));
+    uint8_t* d_bytes = nullptr;
+    int64_t* d_off = nullptr;
+    // (freed by pplhip_destroy even when a later step of this call fails: the fields are set as they come)
+    HIPCK(c, 0, hipMalloc((void**)&d_bytes, (size_t)std::max<int64_t>(total, 1)));
+    R.gd_bytes = d_bytes;
+    HIPCK(c, 0, hipMalloc((void**)&d_off, (size_t)(n_tok + 1) * 8));
+    R.gd_off = d_off;
+    if (!R.h_gde) HIPCK(c, 0, hipHostMalloc((void**)&R.h_gde, (size_t)R.cap_B * 12, hipHostMallocDefault));
+    if (!R.d_gde) HIPCK(c, 0, hipMalloc((void**)&R.d_gde, (size_t)R.cap_B * 12));
+    if (!R.gde_ev) HIPCK(c, 0, hipEventCreateWithFlags(&R.gde_ev, hipEventDisableTiming));
+    if (total > 0) HIPCK(c, 0, hipMemcpyAsync(d_bytes, bytes, (size_t)total, hipMemcpyHostToDevice, R.stream));
+    HIPCK(c, 0, hipMemcpyAsync(d_off, offsets, (size_t)(n_tok + 1) * 8, hipMemcpyHostToDevice, R.stream));
+    HIPCK(c, 0, hipStreamSynchronize(R.stream));   // the caller's arrays are pageable and free after this call
+    R.gd_n_tok = n_tok;
+    return 0;
+}
+
+int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
+    if (!c || !g) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    const int V = c->d.vocab_size;
+    if (R.gd_n_tok < 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: no vocabulary set (pplhip_guide_set_vocab)");
+    if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot outside [0, PPLHIP_GUIDE_MAX_SLOTS)");
+    if (R.gd_mask[slot]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot " + std::to_string(slot) + " is loaded");
+    const int S = g->n_states;
+    if (S < 1 || S > PPLHIP_GUIDE_MAX_STATES) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: n_states outside [1, PPLHIP_GUIDE_MAX_STATES]");
+    if (g->n_end < 0 || g->n_end > PPLHIP_LOGIT_STOP_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: n_end outside [0, PPLHIP_LOGIT_STOP_MAX]");
+    if (!g->trans || !g->accept || (g->n_end > 0 && !g->end_tokens)) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: a NULL array");
+    for (int i = 0; i < g->n_end; ++i)
+        if (g->end_tokens[i] < 0 || g->end_tokens[i] >= V)
+            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: end_tokens[" + std::to_string(i) + "] outside [0, vocab_size)");
+    for (int s = 0; s < S; ++s) {
+        bool live = g->accept[s] != 0;
+        for (int b = 0; b < 256; ++b) {
+            const int to = g->trans[s * 256 + b];
+            if (to != GUIDE_DEAD && to >= S)
+                return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(s) + " byte " + std::to_string(b) + " leads to state " +
+                                                            std::to_string(to) + " >= n_states");
+            live = live || to != GUIDE_DEAD;
+        }
+        if (!live) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(s) + " has neither a live byte nor acceptance");
+    }
+    HIPCK(c, 0, hipSetDevice(R.device));
+    const int64_t words = ((int64_t)V + 31) / 32;
+    // one scratch block: trans | accept (padded to 256) | any u32 [256] | end tokens i32 [64]
+    const size_t o_acc = (size_t)S * 256, o_any = o_acc + 256, o_end = o_any + 1024, scratch_bytes = o_end + 256;
+    char* scratch = nullptr;
+    uint32_t* mask = nullptr;
+    std::vector<uint32_t> any((size_t)S, 0);
+    hipError_t e = hipMalloc((void**)&scratch, scratch_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&mask, (size_t)S * words * 4);
+    hipStream_t s = R.stream;
+    if (e == hipSuccess) e = hipMemsetAsync(scratch + o_any, 0, 1024, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(scratch, g->trans, (size_t)S * 256, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(scratch + o_acc, g->accept, (size_t)S, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && g->n_end > 0) e = hipMemcpyAsync(scratch + o_end, g->end_tokens, (size_t)g->n_end * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_guide_build(s, (const uint8_t*)scratch, (const uint8_t*)(scratch + o_acc), S, R.gd_bytes, R.gd_off, R.gd_n_tok,
+                               (const int32_t*)(scratch + o_end), g->n_end, V, mask, words, (uint32_t*)(scratch + o_any));
+    if (e == hipSuccess) e = hipMemcpyAsync(any.data(), scratch + o_any, (size_t)S * 4, hipMemcpyDeviceToHost, s);
+    const hipError_t e_sync = hipStreamSynchronize(s);   // synchronous by design: once per distinct pattern
+    if (e == hipSuccess) e = e_sync;
+    if (scratch) hipFree(scratch);
+    if (e != hipSuccess) {
+        if (mask) hipFree(mask);
+        return fail(c, 0, e == hipErrorOutOfMemory ? PPLHIP_OUT_OF_MEMORY : PPLHIP_DEVICE_RUNTIME_ERROR, std::string("guide load: ") + hipGetErrorString(e));
+    }
+    for (int st = 0; st < S; ++st)
+        if (!any[st]) {
+            hipFree(mask);
+            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(st) + " allows no token of the vocabulary");
+        }
+    R.gd_mask[slot] = mask;
+    R.gd_states[slot] = S;
+    return 0;
+}
+
+int pplhip_guide_unload(pplhip_ctx* c, int32_t slot) {
+    if (!c) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS || !R.gd_mask[slot]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot is not loaded");
+    HIPCK(c, 0, hipSetDevice(R.device));
+    HIPCK(c, 0, hipStreamSynchronize(R.stream));   // a queued pplhip_guide_edit may still read the mask
+    HIPCK(c, 0, hipFree(R.gd_mask[slot]));
+    R.gd_mask[slot] = nullptr;
+    R.gd_states[slot] = 0;
+    return 0;
+}
+
+int pplhip_guide_edit(pplhip_ctx* c, float* logits_device, const pplhip_guide_edit_args* a) {
+    if (!c || !a || !logits_device || !a->guide_slots || !a->states) return PPLHIP_INVALID_VALUE;
+    Rank& R = c->ranks[0];
+    const int B = a->batch;
+    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
+    if (a->vocab_size != c->d.vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide edit: vocab_size is not the model's");
+    if (a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
+    int asked = 0;
+    for (int i = 0; i < B; ++i) {
+        const int32_t slot = a->guide_slots[i];
+        if (slot == -1) continue;
+        if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS || !R.gd_mask[slot])
+            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide edit: row " + std::to_string(i) + " asks with a slot that holds no guide");
+        if (a->states[i] < 0 || a->states[i] >= R.gd_states[slot])
+            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide edit: row " + std::to_string(i) + " is in a state outside its guide");
+        ++asked;
+    }
+    if (asked == 0) return 0;   // nobody asks: no HIP call
+    HIPCK(c, 0, hipSetDevice(R.device));
+    HIPCK(c, 0, hipEventSynchronize(R.gde_ev));   // the previous call's upload has left the staging block
+    const int64_t cap = R.cap_B;
+    int32_t* h_slots = (int32_t*)R.h_gde;
+    int32_t* h_states = (int32_t*)(R.h_gde + 4 * cap);
+    int32_t* h_rows = (int32_t*)(R.h_gde + 8 * cap);
+    int n = 0;
+    for (int i = 0; i < B; ++i) {
+        h_slots[i] = a->guide_slots[i];
+        h_states[i] = a->guide_slots[i] >= 0 ? a->states[i] : 0;
+        if (a->guide_slots[i] >= 0) h_rows[n++] = i;
+    }
+    hipStream_t s = R.stream;
+    HIPCK(c, 0, hipMemcpyAsync(R.d_gde, R.h_gde, (size_t)(8 * cap + 4 * (int64_t)asked), hipMemcpyHostToDevice, s));
+    HIPCK(c, 0, hipEventRecord(R.gde_ev, s));
+    GuideTable tb;
+    for (int i = 0; i < GUIDE_MAX_SLOTS; ++i) tb.mask[i] = R.gd_mask[i];
+    tb.mask_stride = ((int64_t)a->vocab_size + 31) / 32;
+    HIPCK(c, 0, launch_guide_mask(s, logits_device, a->batch_stride, a->vocab_size, (const int32_t*)(R.d_gde + 8 * cap), asked,
+                                  (const int32_t*)R.d_gde, (const int32_t*)(R.d_gde + 4 * cap), tb));
+    return 0;   // asynchronous: in stream order in front of the step's logit edit, penalty, top-N logprobs and sampler
+}
+
 int pplhip_penalty(pplhip_ctx* c, float* logits_device, const pplhip_penalty_args* a) {
     if (!c || !a || !logits_device) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[0];
@@ -3072,6 +3231,51 @@ int pplhip_op_prompt_logprobs(void* stream, const float* logits, int32_t stride,
     }
     if (top && (!out_top_tok || !out_top_logprob)) return PPLHIP_INVALID_VALUE;
     return op_rc(launch_prompt_logprobs(s, logits, stride, vocab, rows, n_rows, targets, n_top, out_logprob, out_rank, out_top_tok, out_top_logprob));
+}
+
+// the two k_guide.hip kernels alone on caller-owned memory
+int pplhip_op_guide_build(void* stream, const uint8_t* trans, const uint8_t* accept, int32_t n_states, const uint8_t* tok_bytes,
+                          const int64_t* tok_off, int32_t n_tok, const int32_t* end_tokens, int32_t n_end, int32_t vocab, uint32_t* mask,
+                          int64_t mask_stride, uint32_t* any) {
+    if (n_states < 1 || n_states > GUIDE_MAX_STATES || vocab <= 0 || n_tok < 0 || n_tok > vocab || n_end < 0 || n_end > LOGIT_STOP_MAX ||
+        mask_stride < ((int64_t)vocab + 31) / 32)
+        return PPLHIP_INVALID_VALUE;
+    if (!trans || !accept || !tok_bytes || !tok_off || !mask || !any || (n_end > 0 && !end_tokens)) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_guide_build((hipStream_t)stream, trans, accept, n_states, tok_bytes, tok_off, n_tok, end_tokens, n_end, vocab, mask,
+                                    mask_stride, any));
+}
+
+int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
+                         const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
+                         const int32_t* rows, int32_t n_rows) {
+    if (batch < 0 || vocab <= 0 || stride < vocab || n_rows < 0 || n_rows > batch || n_slots < 1 || n_slots > GUIDE_MAX_SLOTS ||
+        n_states < 1 || n_states > GUIDE_MAX_STATES || mask_stride < ((int64_t)vocab + 31) / 32)
+        return PPLHIP_INVALID_VALUE;
+    if (batch == 0) return 0;
+    if (!logits || !guide_slots || !states || !masks) return PPLHIP_INVALID_VALUE;
+    hipStream_t s = (hipStream_t)stream;
+    GuideTable tb;
+    for (int i = 0; i < GUIDE_MAX_SLOTS; ++i) tb.mask[i] = i < n_slots ? masks + (int64_t)i * n_states * mask_stride : nullptr;
+    tb.mask_stride = mask_stride;
+    if (rows) return op_rc(launch_guide_mask(s, logits, stride, vocab, rows, n_rows, guide_slots, states, tb));
+    std::vector<int32_t> gs(batch), st(batch), list;
+    hipError_t e = hipMemcpyAsync(gs.data(), guide_slots, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st.data(), states, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    for (int i = 0; i < batch; ++i) {
+        if (gs[i] < 0) continue;
+        if (gs[i] >= n_slots || st[i] < 0 || st[i] >= n_states) return PPLHIP_INVALID_VALUE;   // would read outside `masks`
+        list.push_back(i);
+    }
+    if (list.empty()) return 0;
+    int32_t* d_rows = nullptr;
+    if ((e = hipMallocAsync((void**)&d_rows, list.size() * 4, s)) != hipSuccess) return op_rc(e);
+    e = hipMemcpyAsync(d_rows, list.data(), list.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `list` is pageable and dies with this call
+    if (e == hipSuccess) e = launch_guide_mask(s, logits, stride, vocab, d_rows, (int)list.size(), guide_slots, states, tb);
+    const hipError_t e2 = hipFreeAsync(d_rows, s);
+    return op_rc(e != hipSuccess ? e : e2);
 }
 
 int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u) {

@@ -94,6 +94,20 @@ class PromptLogprobsOut(C.Structure):
                 ("top_logprobs", C.c_void_p)]
 
 
+GUIDE_MAX_SLOTS = 16     # PPLHIP_GUIDE_MAX_SLOTS
+GUIDE_MAX_STATES = 255   # PPLHIP_GUIDE_MAX_STATES
+GUIDE_DEAD = 255
+
+
+class GuideDesc(C.Structure):
+    _fields_ = [("trans", C.c_void_p), ("accept", C.c_void_p), ("n_states", C.c_int32), ("end_tokens", C.c_void_p), ("n_end", C.c_int32)]
+
+
+class GuideEditArgs(C.Structure):
+    _fields_ = [("guide_slots", C.c_void_p), ("states", C.c_void_p), ("batch", C.c_int32), ("vocab_size", C.c_int32),
+                ("batch_stride", C.c_int32)]
+
+
 class PenaltyArgs(C.Structure):
     _fields_ = [("temperatures", C.c_void_p), ("repetition_penalties", C.c_void_p), ("presence_penalties", C.c_void_p),
                 ("frequency_penalties", C.c_void_p), ("batch_slots", C.c_void_p), ("batch", C.c_int32),
@@ -150,10 +164,10 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_set_prompt_logprobs", "pplhip_prompt_logprobs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
-    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
+    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_guide_set_vocab", "pplhip_guide_load", "pplhip_guide_unload", "pplhip_guide_edit", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -248,6 +262,13 @@ def lib():
             L.pplhip_logit_rule_set.argtypes = [vp, i32, C.POINTER(LogitRule)]
             L.pplhip_logit_edit.argtypes = [vp, vp, C.POINTER(LogitEditArgs)]
             L.pplhip_op_logit_edit.argtypes = [vp, vp, i32, i32, i32] + [vp] * 8 + [i32]
+        if hasattr(L, "pplhip_guide_load"):
+            L.pplhip_guide_set_vocab.argtypes = [vp, vp, vp, i32]
+            L.pplhip_guide_load.argtypes = [vp, i32, C.POINTER(GuideDesc)]
+            L.pplhip_guide_unload.argtypes = [vp, i32]
+            L.pplhip_guide_edit.argtypes = [vp, vp, C.POINTER(GuideEditArgs)]
+            L.pplhip_op_guide_build.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, i64, vp]
+            L.pplhip_op_guide_mask.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i64, vp, i32]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
@@ -658,6 +679,50 @@ class Context:
         rc = lib().pplhip_logit_edit(self.h, logits_ptr, C.byref(a))
         if check:
             self._ck(rc, 0, "logit_edit")
+        return rc
+
+    def guide_set_vocab(self, token_bytes, check=True):
+        """the vocabulary of guided decoding, once: token_bytes = one bytes object per token id (ids behind the list are empty)."""
+        off = np.zeros(len(token_bytes) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(b) for b in token_bytes])
+        blob = np.frombuffer(b"".join(token_bytes) + b"\0", dtype=np.uint8)
+        rc = lib().pplhip_guide_set_vocab(self.h, blob.ctypes.data, off.ctypes.data, len(token_bytes))
+        if check:
+            self._ck(rc, 0, "guide_set_vocab")
+        return rc
+
+    def guide_load(self, slot, trans, accept, end_tokens=(), check=True):
+        """builds slot's allowed-token masks from a DFA: trans uint8 [n_states, 256] (255 = dead), accept uint8 [n_states].  Synchronous."""
+        tr = np.ascontiguousarray(trans, dtype=np.uint8)
+        ac = np.ascontiguousarray(accept, dtype=np.uint8)
+        en = np.ascontiguousarray(list(end_tokens), dtype=np.int32)
+        assert tr.ndim == 2 and tr.shape[1] == 256 and len(ac) == len(tr)
+        g = GuideDesc()
+        g.trans, g.accept, g.n_states, g.end_tokens, g.n_end = tr.ctypes.data, ac.ctypes.data, len(tr), en.ctypes.data, len(en)
+        rc = lib().pplhip_guide_load(self.h, int(slot), C.byref(g))
+        if check:
+            self._ck(rc, 0, "guide_load")
+        return rc
+
+    def guide_unload(self, slot, check=True):
+        rc = lib().pplhip_guide_unload(self.h, int(slot))
+        if check:
+            self._ck(rc, 0, "guide_unload")
+        return rc
+
+    def guide_edit(self, guide_slots, states, logits_ptr=None, check=True):
+        """queues the guide masks of the last run's logits (rank 0) for the rows with guide_slots != -1; asynchronous."""
+        a = GuideEditArgs()
+        gs = np.ascontiguousarray(guide_slots, dtype=np.int32)
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        assert len(gs) == len(st)
+        a.guide_slots, a.states = gs.ctypes.data, st.ctypes.data
+        a.batch, a.vocab_size, a.batch_stride = len(gs), self.desc.vocab_size, self.desc.vocab_size
+        if logits_ptr is None:
+            logits_ptr = self.logits_ptr(0)[0]
+        rc = lib().pplhip_guide_edit(self.h, logits_ptr, C.byref(a))
+        if check:
+            self._ck(rc, 0, "guide_edit")
         return rc
 
     def penalty(self, temperatures, repetition, presence, frequency, batch_slots, req_list_changed=True):

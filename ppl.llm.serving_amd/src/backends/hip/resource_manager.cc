@@ -157,6 +157,52 @@ RetCode HipPostProcessor::EditLogits(float* logits_device, const int64_t* batch_
     return FromPplHipStatus(st);
 }
 
+static_assert(PostProcessor::kGuideMaxSlots == PPLHIP_GUIDE_MAX_SLOTS && PostProcessor::kGuideMaxStates == PPLHIP_GUIDE_MAX_STATES &&
+                  GuideDfa::kMaxStates == PPLHIP_GUIDE_MAX_STATES && GuideDfa::kDead == 255,
+              "interface and library disagree");
+
+RetCode HipPostProcessor::SetGuideVocab(const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) {
+    if (guide_vocab_set_) return RC_SUCCESS;   // a second generator over this backend: the library takes the vocabulary once
+    const int st = pplhip_guide_set_vocab(ctx_, bytes, offsets, n_tok);
+    if (st) LOG(ERROR) << "guide vocabulary refused: " << pplhip_last_error(ctx_, 0);
+    guide_vocab_set_ = st == 0;
+    return FromPplHipStatus(st);
+}
+
+RetCode HipPostProcessor::LoadGuide(int32_t slot, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens) {
+    pplhip_guide_desc g;
+    memset(&g, 0, sizeof(g));
+    g.trans = dfa.trans.data();
+    g.accept = dfa.accept.data();
+    g.n_states = dfa.n_states;
+    g.end_tokens = end_tokens.data();
+    g.n_end = (int32_t)end_tokens.size();
+    const int st = pplhip_guide_load(ctx_, slot, &g);
+    if (st) LOG(ERROR) << "guide of slot " << slot << " refused: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
+RetCode HipPostProcessor::UnloadGuide(int32_t slot) {
+    const int st = pplhip_guide_unload(ctx_, slot);
+    if (st) LOG(ERROR) << "guide unload failed: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
+RetCode HipPostProcessor::GuideEdit(float* logits_device, const int32_t* guide_slots_host, const int32_t* states_host, int32_t batch,
+                                    int32_t vocab_size, int32_t batch_stride) {
+    if (batch == 0) return RC_SUCCESS;   // the generator's question whether guides are served
+    pplhip_guide_edit_args a;
+    memset(&a, 0, sizeof(a));
+    a.guide_slots = guide_slots_host;
+    a.states = states_host;
+    a.batch = batch;
+    a.vocab_size = vocab_size;
+    a.batch_stride = batch_stride;
+    const int st = pplhip_guide_edit(ctx_, logits_device, &a);
+    if (st) LOG(ERROR) << "guide edit failed: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
 RetCode HipPostProcessor::ApplyPenalty(const float* temperatures_host, const float* repetition_penalties_host,
                                        const float* presence_penalties_host, const float* frequency_penalties_host,
                                        const int64_t* batch_slots_host, const int64_t*, const int64_t*, const int64_t*,

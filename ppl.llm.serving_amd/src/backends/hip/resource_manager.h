@@ -51,9 +51,15 @@ public:
     ppl::common::RetCode SetLogitRule(int64_t slot, const LogitRule& rule) override;
     ppl::common::RetCode EditLogits(float* logits_device, const int64_t* batch_slots_host, const uint32_t* flags_host, int32_t batch,
                                     int32_t vocab_size, int32_t batch_stride) override;
+    ppl::common::RetCode SetGuideVocab(const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) override;
+    ppl::common::RetCode LoadGuide(int32_t slot, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens) override;
+    ppl::common::RetCode UnloadGuide(int32_t slot) override;
+    ppl::common::RetCode GuideEdit(float* logits_device, const int32_t* guide_slots_host, const int32_t* states_host, int32_t batch,
+                                   int32_t vocab_size, int32_t batch_stride) override;
 
 private:
     pplhip_ctx* ctx_;
+    bool guide_vocab_set_ = false;   // SetGuideVocab has reached the library, which takes the vocabulary once
 };
 
 // Owns everything device-side (context, KV slabs, runtimes, sampler, worker pool); LLMEngine / LLMGenerator hold

@@ -139,6 +139,15 @@ PPLSRV_API int pplsrv_poll_prompt_logprobs(pplsrv* s, pplsrv_response* out, int3
                                            int64_t text_buf_bytes, pplsrv_top_logprobs* tops, pplsrv_prompt_logprobs* prompts,
                                            float* logprob_buf, int32_t* rank_buf, int64_t buf_positions, int32_t* top_token_buf,
                                            float* top_logprob_buf, int64_t top_buf_entries);
+/* Guided decoding.  pplsrv_submit_guided is pplsrv_submit_prompt_logprobs with guide_regex[i] = Request::guide_regex of reqs[i]: a
+ * NUL-terminated regular expression (src/common/guide.h has the dialect) that the bytes of the request's generated tokens must match in
+ * full; NULL or "" = no guide; guide_regex NULL: nobody is guided.  The strings are read before the call returns.  The guide is compiled
+ * and checked when its request is admitted; a pattern outside the dialect or too large, a request that also carries allowed_tokens,
+ * banned_tokens, min_new_tokens, a -inf bias or early_stopping == 0, a server without a tokenizer, a backend without guides and a 17th
+ * pattern while 16 are in use each fail that request alone (PPLSRV_FAILED). */
+PPLSRV_API int pplsrv_submit_guided(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                    const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs,
+                                    const char* const* guide_regex, int32_t n);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

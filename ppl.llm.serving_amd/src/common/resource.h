@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "adapter_registry.h"
+#include "guide.h"
 #include "logit_rule.h"
 #include "ppl/common/retcode.h"
 #include "ppl/common/threadpool.h"
@@ -65,6 +66,26 @@ public:
     }
     virtual ppl::common::RetCode EditLogits(float* /*logits_device*/, const int64_t* /*batch_slots_host*/, const uint32_t* /*flags_host*/,
                                             int32_t /*batch*/, int32_t /*vocab_size*/, int32_t /*batch_stride*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
+    // Guided decoding (DESIGN.md "numerics", guided decoding row).  SetGuideVocab hands the backend the bytes of every token, once:
+    // token t < n_tok is bytes[offsets[t] .. offsets[t + 1]).  LoadGuide builds guide slot `slot` (0 .. kGuideMaxSlots - 1) from a DFA
+    // (guide.h) and the end tokens, which are allowed exactly in accepting states; BLOCKING, once per distinct pattern; RC_INVALID_VALUE
+    // when some state of the automaton allows no token of the vocabulary.  UnloadGuide frees a slot that no running request names.
+    // GuideEdit sets to -inf, in row b, every token that state states_host[b] of slot guide_slots_host[b] does not allow (-1: the row
+    // does not ask); NOT blocking; the engine calls it in front of EditLogits and only on steps with an asking row.  batch == 0 touches
+    // nothing and only tells whether the backend can do it.  A backend that cannot keeps these defaults, and guided requests are failed.
+    static constexpr int32_t kGuideMaxSlots = 16;
+    static constexpr int32_t kGuideMaxStates = 255;
+    virtual ppl::common::RetCode SetGuideVocab(const uint8_t* /*bytes*/, const int64_t* /*offsets*/, int32_t /*n_tok*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
+    virtual ppl::common::RetCode LoadGuide(int32_t /*slot*/, const GuideDfa& /*dfa*/, const std::vector<int32_t>& /*end_tokens*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
+    virtual ppl::common::RetCode UnloadGuide(int32_t /*slot*/) { return ppl::common::RC_UNSUPPORTED; }
+    virtual ppl::common::RetCode GuideEdit(float* /*logits_device*/, const int32_t* /*guide_slots_host*/, const int32_t* /*states_host*/,
+                                           int32_t /*batch*/, int32_t /*vocab_size*/, int32_t /*batch_stride*/) {
         return ppl::common::RC_UNSUPPORTED;
     }
 };

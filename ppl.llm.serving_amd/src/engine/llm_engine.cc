@@ -129,6 +129,19 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
         Runtime* rt0 = runtimes_[0];  // sampling happens on rank 0's logits only (src/engine/llm_engine.cc:200)
         int64_t stride = 0;
         float* logits = rt0->GetLogits(&stride);
+        // guided decoding: the asking rows lose every token their automaton's state does not allow, in front of everything else that
+        // reads or edits the logits; nothing on a step without an asking row
+        bool guided = false;
+        for (int32_t g : in.guide_slots) guided = guided || g >= 0;
+        if (guided) {
+            rc = post_processor_->GuideEdit(logits, in.guide_slots.data(), in.guide_states.data(), running_batch, model_config_.vocab_size,
+                                            (int32_t)stride);
+            if (rc != RC_SUCCESS) {
+                *error_msg = "GuideEdit failed: " + std::string(GetRetCodeStr(rc));
+                LOG(ERROR) << *error_msg;
+                return RC_OTHER_ERROR;
+            }
+        }
         // logit rules: in place and first, so a bias is in raw-logit units and the penalty, the top-N logprobs and the sampler all see
         // the edited rows; nothing on a step without a flag
         bool edits = false;

@@ -42,6 +42,10 @@ struct ModelInput {
     // logit rules per request: 0 = the request has none; bit 0 = apply the mask and bias of the rule in its batch slot, bit 1 = suppress
     // the rule's stop tokens (set while the request has produced fewer than min_new_tokens tokens)
     std::vector<uint32_t> logit_flags;
+    // guided decoding per request: the guide slot its pattern is loaded in (-1 = the request has no guide) and the state of the
+    // automaton after the bytes it has generated so far
+    std::vector<int32_t> guide_slots;
+    std::vector<int32_t> guide_states;
 };
 
 struct ModelOutput {
@@ -94,6 +98,27 @@ public:
         std::unique_lock<std::mutex> device_lock;  // as Execute: adapters load and unload on the same device
         if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
         return post_processor_->SetLogitRule(slot, rule);
+    }
+
+    // guided decoding: whether the backend's post processor has it (PostProcessor::GuideEdit with batch 0), and its three set-up calls
+    bool HasGuides() const {
+        return post_processor_ && post_processor_->GuideEdit(nullptr, nullptr, nullptr, 0, model_config_.vocab_size,
+                                                             model_config_.vocab_size) == ppl::common::RC_SUCCESS;
+    }
+    ppl::common::RetCode SetGuideVocab(const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) {
+        std::unique_lock<std::mutex> device_lock;  // as Execute: adapters load and unload on the same device
+        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
+        return post_processor_->SetGuideVocab(bytes, offsets, n_tok);
+    }
+    ppl::common::RetCode LoadGuide(int32_t slot, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens) {
+        std::unique_lock<std::mutex> device_lock;
+        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
+        return post_processor_->LoadGuide(slot, dfa, end_tokens);
+    }
+    ppl::common::RetCode UnloadGuide(int32_t slot) {
+        std::unique_lock<std::mutex> device_lock;
+        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
+        return post_processor_->UnloadGuide(slot);
     }
 
 private:

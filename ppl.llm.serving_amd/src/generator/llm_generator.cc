@@ -30,10 +30,12 @@ struct LLMGenerator::Admission {
     RetCode errcode = RC_INVALID_VALUE;
     bool has_rule = false;  // the request carries a logit rule: `rule` is its validated, merged form
     LogitRule rule;
+    int32_t guide_slot = -1;  // the request is guided: the slot it holds a reference on
 
     void ResetForRequest(int prompt_len) {
         errcode = RC_INVALID_VALUE;
         has_rule = false;
+        guide_slot = -1;
         cache_index = INT64_MAX;
         page_list.clear();
         slot_index = INT64_MAX;
@@ -71,6 +73,9 @@ LLMGenerator::~LLMGenerator() {
         req_signal_.NotifyOne();
         pthread_join(generate_thread_, nullptr);
     }
+    // the backend outlives the generator: its guide slots go back, so that the next generator finds them empty
+    for (int32_t i = 0; i < PostProcessor::kGuideMaxSlots; ++i)
+        if (!guides_[i].key.empty()) llm_engine_.UnloadGuide(i);
 }
 
 // reference CheckParameters, llm_generator.cc:114-144 (accepted combinations: SURVEY.md Q9)
@@ -288,6 +293,8 @@ bool LLMGenerator::ReserveKv(const LlmRequest& req, Admission* adm, int32_t* coo
     return true;
 }
 
+static std::string GuideExclusion(const Request& r);
+
 // the admission predicate handed to the request scheduler (reference check_func, llm_generator.cc:590-617).
 // true  -> the request leaves the queue (either admitted, or invalid and failed by StartRequest)
 // false -> it stays at the head (stash) and admission stops for this step
@@ -309,6 +316,15 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
         adm->errmsg = "id [" + std::to_string(req.orig->id) + "] generation length <= 0";
         return true;
     }
+    if (!req.orig->guide_regex.empty()) {
+        adm->errmsg = GuideExclusion(*req.orig);
+        if (!adm->errmsg.empty()) {
+            adm->errmsg = "id [" + std::to_string(req.orig->id) + "] " + adm->errmsg;
+            LOG(ERROR) << adm->errmsg;
+            adm->first_fill_len = -1;
+            return true;
+        }
+    }
     if (req.orig->HasLogitRule()) {  // validated once, here; an invalid rule fails its request alone (StartRequest)
         const Request& r = *req.orig;
         bool ok = llm_engine_.HasLogitRules();
@@ -329,10 +345,139 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
         }
         adm->has_rule = true;
     }
-    if (!ReserveKv(req, adm, cool_down, is_prefix_cache_hit)) return false;
+    if (!req.orig->guide_regex.empty() && !AdmitGuide(*req.orig, adm)) {  // a refused guide fails its request alone (StartRequest)
+        adm->errmsg = "id [" + std::to_string(req.orig->id) + "] " + adm->errmsg;
+        LOG(ERROR) << adm->errmsg;
+        adm->first_fill_len = -1;
+        return true;
+    }
+    if (!ReserveKv(req, adm, cool_down, is_prefix_cache_hit)) {
+        ReleaseGuide(adm->guide_slot);   // the request stays queued and asks again
+        adm->guide_slot = -1;
+        return false;
+    }
     ++adm->running_batch;
     ++adm->prefill_batch;
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------ guided decoding
+
+// the end tokens of a request: allowed exactly where its pattern is matched in full
+static std::vector<int32_t> GuideEndTokens(const Tokenizer* tokenizer, const GeneratorConfig& cfg, const Request& r) {
+    std::vector<int32_t> ends(cfg.stop_tokens.begin(), cfg.stop_tokens.end());
+    if (r.stop_tokens) ends.insert(ends.end(), r.stop_tokens->begin(), r.stop_tokens->end());
+    if (tokenizer) ends.push_back(tokenizer->GetEosId());
+    std::sort(ends.begin(), ends.end());
+    ends.erase(std::unique(ends.begin(), ends.end()), ends.end());
+    return ends;
+}
+
+// what a guided request may not carry: the exclusions keep "no token left alive" impossible by construction, as nothing else removes a
+// token the automaton counts on.  Empty: the request is fine
+static std::string GuideExclusion(const Request& r) {
+    if (!r.early_stopping) return "guide_regex: needs early_stopping (the request ends on an end token)";
+    if (r.allowed_tokens) return "guide_regex: cannot be combined with allowed_tokens";
+    if (!r.banned_tokens.empty()) return "guide_regex: cannot be combined with banned_tokens";
+    if (r.min_new_tokens > 0) return "guide_regex: cannot be combined with min_new_tokens";
+    for (const auto& p : r.logit_bias)
+        if (p.second == -INFINITY) return "guide_regex: cannot be combined with a -inf logit_bias";
+    return "";
+}
+
+bool LLMGenerator::AdmitGuide(const Request& r, Admission* adm) {
+    adm->errcode = RC_UNSUPPORTED;
+    if (!llm_engine_.HasGuides()) { adm->errmsg = "guide_regex: the backend's post processor has no GuideEdit"; return false; }
+    std::string bytes;
+    if (!tokenizer_ || !tokenizer_->TokenBytes(0, &bytes)) {
+        adm->errmsg = "guide_regex: needs a tokenizer that knows the bytes of its tokens (TokenBytes)";
+        return false;
+    }
+    if (guide_vocab_ == 0) {  // the first guided request: the vocabulary goes to the backend, once
+        const int32_t V = model_config_.vocab_size;
+        std::string blob;
+        std::vector<int64_t> offsets(1, 0);
+        for (int32_t t = 0; t < V; ++t) {
+            tokenizer_->TokenBytes(t, &bytes);
+            blob += bytes;
+            offsets.push_back((int64_t)blob.size());
+        }
+        const RetCode rc = llm_engine_.SetGuideVocab((const uint8_t*)blob.data(), offsets.data(), V);
+        guide_vocab_ = rc == RC_SUCCESS ? 1 : -1;
+        if (rc != RC_SUCCESS) LOG(ERROR) << "SetGuideVocab failed: " << GetRetCodeStr(rc);
+    }
+    if (guide_vocab_ < 0) {
+        adm->errcode = RC_OTHER_ERROR;
+        adm->errmsg = "guide_regex: the backend refused the vocabulary";
+        return false;
+    }
+    adm->errcode = RC_INVALID_VALUE;
+    const std::vector<int32_t> ends = GuideEndTokens(tokenizer_, generator_config_, r);
+    if ((int32_t)ends.size() > PostProcessor::kLogitStopMax) {
+        adm->errmsg = "guide_regex: more than " + std::to_string(PostProcessor::kLogitStopMax) + " end tokens";
+        return false;
+    }
+    for (int32_t t : ends)
+        if (t < 0 || t >= model_config_.vocab_size) {
+            adm->errmsg = "guide_regex: end token [" + std::to_string(t) + "] outside the vocabulary";
+            return false;
+        }
+    std::string key = r.guide_regex;
+    key.push_back('\0');
+    for (int32_t t : ends) key += std::to_string(t) + ",";
+    GuideDfa dfa;
+    bool cached = false;
+    for (const GuideSlot& g : guides_) cached = cached || g.key == key;
+    if (!cached && !CompileGuideRegex(r.guide_regex, &dfa, &adm->errmsg)) return false;
+    adm->guide_slot = AcquireGuide(key, dfa, ends, &adm->errmsg, &adm->errcode);
+    return adm->guide_slot >= 0;
+}
+
+int32_t LLMGenerator::AcquireGuide(const std::string& key, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens, std::string* err,
+                                   RetCode* errcode) {
+    const int32_t n = PostProcessor::kGuideMaxSlots;
+    int32_t pick = -1;
+    for (int32_t i = 0; i < n; ++i)
+        if (guides_[i].key == key) {
+            ++guides_[i].refs;
+            guides_[i].last_use = ++guide_clock_;
+            return i;
+        }
+    for (int32_t i = 0; i < n && pick < 0; ++i)
+        if (guides_[i].key.empty()) pick = i;
+    if (pick < 0) {  // evict the idle slot that was used longest ago
+        for (int32_t i = 0; i < n; ++i)
+            if (guides_[i].refs == 0 && (pick < 0 || guides_[i].last_use < guides_[pick].last_use)) pick = i;
+        if (pick < 0) {
+            *errcode = RC_OTHER_ERROR;
+            *err = "guide_regex: all " + std::to_string(n) + " guide slots are held by running requests";
+            return -1;
+        }
+        const RetCode rc = llm_engine_.UnloadGuide(pick);
+        if (rc != RC_SUCCESS) {
+            *errcode = RC_OTHER_ERROR;
+            *err = "guide_regex: UnloadGuide failed: " + std::string(GetRetCodeStr(rc));
+            return -1;
+        }
+        guides_[pick] = GuideSlot();
+    }
+    const RetCode rc = llm_engine_.LoadGuide(pick, dfa, end_tokens);
+    if (rc != RC_SUCCESS) {
+        *errcode = rc == RC_INVALID_VALUE ? RC_INVALID_VALUE : RC_OTHER_ERROR;
+        *err = rc == RC_INVALID_VALUE ? "guide_regex: some state of the pattern's automaton allows no token of the vocabulary"
+                                      : "guide_regex: LoadGuide failed: " + std::string(GetRetCodeStr(rc));
+        return -1;
+    }
+    guides_[pick].key = key;
+    guides_[pick].dfa = dfa;
+    guides_[pick].refs = 1;
+    guides_[pick].last_use = ++guide_clock_;
+    return pick;
+}
+
+void LLMGenerator::ReleaseGuide(int32_t slot) {
+    if (slot < 0 || slot >= PostProcessor::kGuideMaxSlots) return;
+    if (guides_[slot].refs > 0) --guides_[slot].refs;
 }
 
 // seed of a request that brings none: one step of the splitmix64 generator (Vigna) from state x
@@ -355,6 +500,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     if ((mode == 0 && adm.cache_index == INT64_MAX) || (mode == 1 && adm.page_list.empty())) {
         LOG(ERROR) << "catch invalid cache_index or page list";
         if (adapters_) adapters_->Release(r.lora_slot);
+        ReleaseGuide(adm.guide_slot);
         return false;
     }
     TidData& t = tid_data_map_.emplace(r.id, TidData()).first->second;
@@ -388,6 +534,15 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
             if (!adm.rule.bias_tokens.empty() || adm.rule.has_mask) logit_flags |= 1u;
             if (!adm.rule.stop_tokens.empty()) logit_flags |= 2u;
         }
+    }
+    if (adm.guide_slot >= 0) {
+        t.guide_slot = adm.guide_slot;
+        t.guide_state = 0;
+        // drawing an end token ends the request: the tokenizer's EOS counts as one of its stop tokens
+        auto stops = std::make_shared<std::unordered_set<int>>();
+        if (r.stop_tokens) *stops = *r.stop_tokens;
+        stops->insert(tokenizer_->GetEosId());
+        t.stop_tokens = stops;
     }
     if (mode == 0) {
         t.cache_index = (uint64_t)adm.cache_index;
@@ -423,6 +578,8 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     in->num_logprobs_list.push_back(t.num_logprobs);
     in->prompt_logprobs_list.push_back(t.prompt_logprobs);
     in->logit_flags.push_back(logit_flags);
+    in->guide_slots.push_back(t.guide_slot);
+    in->guide_states.push_back(t.guide_state);
     if (mode == 0) in->cache_indices.push_back(adm.cache_index);
     else in->max_pages = std::max<int64_t>((int64_t)t.page_list.size(), in->max_pages);
     return true;
@@ -478,6 +635,8 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
         in->num_logprobs_list[keep] = in->num_logprobs_list[i];
         in->prompt_logprobs_list[keep] = in->prompt_logprobs_list[i];
         in->logit_flags[keep] = in->logit_flags[i];
+        in->guide_slots[keep] = in->guide_slots[i];
+        in->guide_states[keep] = in->guide_states[i];
         ++keep;
     }
     tid_list_.resize(keep);
@@ -496,6 +655,8 @@ void LLMGenerator::CompactBatch(ModelInput* in) {
     in->num_logprobs_list.resize(keep);
     in->prompt_logprobs_list.resize(keep);
     in->logit_flags.resize(keep);
+    in->guide_slots.resize(keep);
+    in->guide_states.resize(keep);
     LOG(DEBUG) << "Rest tasks: " << keep;
 }
 
@@ -527,6 +688,7 @@ void LLMGenerator::DeleteTasks(ModelInput* in) {
         }
         if (t.slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t.slot_index, 1);
         if (adapters_) adapters_->Release(t.lora_slot);
+        ReleaseGuide(t.guide_slot);
         // (the reference adds to a by-value pointer here and so counts nothing -- SURVEY.md Q2; counted properly)
         worker_profiler_->req_counter.output_tokens_per_req += (uint64_t)t.gen_tokens_cnt;
         tid_data_map_.erase(it);
@@ -542,6 +704,7 @@ void LLMGenerator::ReleaseResource() {
         else page_mgr_.Free(t->page_list.data(), (int64_t)t->page_list.size());
         if (t->slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t->slot_index, 1);
         if (adapters_) adapters_->Release(t->lora_slot);
+        ReleaseGuide(t->guide_slot);
     }
     prefix_cache_mgr_.Reset();
     tid_list_.clear();
@@ -683,7 +846,19 @@ void LLMGenerator::Generate() {
                 const size_t prompt_n = scores_prompt && !out.prompt_unsupported ? (size_t)(fed - 1) : 0;
                 in.prompt_logprobs_list[row] = -1;   // asked once: later steps carry nothing
                 const bool no_prompt = scores_prompt && out.prompt_unsupported;
-                const bool no_top = (t->num_logprobs > 0 && out.top_unsupported) || t->rule_failed || no_prompt;
+                // a guided request walks its automaton over the bytes of every token that does not end it.  The mask allowed only tokens
+                // that keep the automaton alive, so the dead state here means kernel and host disagree: that request fails, alone
+                bool guide_broken = false;
+                if (t->guide_slot >= 0 && hit_stop) {
+                    guide_broken = !guides_[t->guide_slot].dfa.Accepting(t->guide_state);   // an end token in front of a full match
+                } else if (t->guide_slot >= 0) {
+                    std::string bytes;
+                    tokenizer_->TokenBytes(tok, &bytes);
+                    const int32_t to = bytes.empty() ? GuideDfa::kDead : guides_[t->guide_slot].dfa.Step(t->guide_state, bytes);
+                    if (to == GuideDfa::kDead) guide_broken = true;
+                    else in.guide_states[row] = t->guide_state = to;
+                }
+                const bool no_top = (t->num_logprobs > 0 && out.top_unsupported) || t->rule_failed || no_prompt || guide_broken;
                 if (t->rest_iters <= 0 || hit_stop || no_top) {
                     flag = t->rest_iters <= 0 ? FinishFlag::LENGTH : FinishFlag::EOS_TOKEN;
                     if (cool_down > 0) --cool_down;
@@ -692,7 +867,8 @@ void LLMGenerator::Generate() {
                 }
                 if (no_top) {
                     prompt_pos += prompt_n;
-                    if (t->rule_failed) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "logit rules: the backend could not take the request's rule");
+                    if (guide_broken) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "guide_regex: internal error: token [" + std::to_string(tok) + "] is not allowed in state [" + std::to_string(t->guide_state) + "] of the request's guide");
+                    else if (t->rule_failed) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "logit rules: the backend could not take the request's rule");
                     else if (no_prompt) conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "prompt_logprobs: the backend's runtime has no SetPromptLogprobs");
                     else conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "num_logprobs: the backend's post processor has no TopLogprobs");
                     continue;

@@ -78,6 +78,8 @@ struct TidData final {
     int32_t num_logprobs = 0;  // Request::num_logprobs, clamped to 0 .. PostProcessor::kTopLogprobsMax
     int32_t min_new_tokens = 0;  // Request::min_new_tokens: bit 1 of the row's logit flags until this many tokens are out
     bool rule_failed = false;    // the upload of its logit rule failed: the request is failed on its first step
+    int32_t guide_slot = -1;     // guided decoding: the guide slot the request holds a reference on until it leaves; -1: none
+    int32_t guide_state = 0;     // the state of its automaton after the bytes generated so far
 };
 
 struct LlmRequest final : public ppl::common::MPSCQueue::Node {
@@ -118,6 +120,11 @@ private:
     void CompactBatch(ModelInput* model_input);
     void ReleaseResource();
     void SendTokens(const std::vector<TidGenToken>& tokens);
+    // guided decoding: the admission check of a request with guide_regex (false: adm->errmsg / errcode say why), and the slot cache
+    bool AdmitGuide(const Request& r, Admission* adm);
+    int32_t AcquireGuide(const std::string& key, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens, std::string* err,
+                         ppl::common::RetCode* errcode);
+    void ReleaseGuide(int32_t slot);
     static void* GeneratorThreadFunc(void*);
 
 private:
@@ -151,6 +158,18 @@ private:
 
     // U+FFFD buffering of the text path (llm_generator.cc:84-99)
     std::map<uint64_t, std::vector<int>> decode_buffer_;
+
+    // guided decoding: the backend's guide slots as a cache from (pattern, end tokens) to slot.  A slot with refs == 0 stays loaded until
+    // its place is needed (least recently used first); guide_vocab_: 0 = not sent yet, 1 = the backend has the vocabulary, -1 = it refused
+    struct GuideSlot {
+        std::string key;   // empty: nothing loaded
+        GuideDfa dfa;
+        int32_t refs = 0;
+        uint64_t last_use = 0;
+    };
+    GuideSlot guides_[PostProcessor::kGuideMaxSlots];
+    uint64_t guide_clock_ = 0;
+    int guide_vocab_ = 0;
 
     StepObserver observer_ = nullptr;
     void* observer_arg_ = nullptr;

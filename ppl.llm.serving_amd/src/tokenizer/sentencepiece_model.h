@@ -15,6 +15,7 @@
 // tests/test_tokenizer.py, fixtures tests/golden/spm_*.model + spm_cases.json.
 #pragma once
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 #include <unordered_map>
@@ -36,6 +37,22 @@ public:
     int GetPieceSize() const { return (int)pieces_.size(); }
     const std::string& IdToPiece(int id) const { return pieces_[id].piece; }
     int PieceToId(const std::string& piece) const;
+    // the bytes piece `id` stands for in the text: a NORMAL or USER_DEFINED piece with U+2581 as a space, a BYTE piece's one byte;
+    // nothing for CONTROL, UNKNOWN and UNUSED pieces and for an id outside the model
+    void TokenBytes(int id, std::string* out) const {
+        out->clear();
+        if (id < 0 || id >= (int)pieces_.size()) return;
+        const Piece& p = pieces_[(size_t)id];
+        if (p.type == BYTE) {
+            if (p.piece.size() == 6) out->push_back((char)strtol(p.piece.substr(3, 2).c_str(), nullptr, 16));
+            return;
+        }
+        if (p.type != NORMAL && p.type != USER_DEFINED) return;
+        for (size_t i = 0; i < p.piece.size();) {
+            if (p.piece.compare(i, 3, "\xe2\x96\x81") == 0) { out->push_back(' '); i += 3; }
+            else out->push_back(p.piece[i++]);
+        }
+    }
     int bos_id() const { return bos_id_; }
     int eos_id() const { return eos_id_; }
     int unk_id() const { return unk_id_; }

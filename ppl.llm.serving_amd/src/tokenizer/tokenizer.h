@@ -15,6 +15,10 @@ public:
     virtual void Decode(int* token_ids, uint32_t len, std::string* output) const = 0;
     virtual int GetBosId() const = 0;
     virtual int GetEosId() const = 0;
+    // Guided decoding (DESIGN.md "numerics", guided decoding row): the bytes token `id` adds to the text, exactly as the streamed pieces
+    // concatenate (no dummy-prefix stripping); empty for a token that adds none (control tokens, ids behind the vocabulary).
+    // false: this tokenizer cannot tell, and guided requests are refused.
+    virtual bool TokenBytes(int /*id*/, std::string* /*bytes*/) const { return false; }
 };
 
 }}  // namespace ppl::llm

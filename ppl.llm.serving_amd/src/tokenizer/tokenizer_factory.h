@@ -35,6 +35,7 @@ public:
     }
     int GetBosId() const override { return sp_.bos_id(); }
     int GetEosId() const override { return sp_.eos_id(); }
+    bool TokenBytes(int id, std::string* bytes) const override { sp_.TokenBytes(id, bytes); return true; }
 
 private:
     SentencePieceModel sp_;
@@ -53,6 +54,7 @@ public:
     void Decode(int* token_ids, uint32_t len, std::string* output) const override { impl_->Decode(token_ids, len, output); }
     int GetBosId() const override { return impl_->GetBosId(); }
     int GetEosId() const override { return impl_->GetEosId(); }
+    bool TokenBytes(int id, std::string* bytes) const override { return impl_->TokenBytes(id, bytes); }
 
 private:
     std::unique_ptr<Tokenizer> impl_;

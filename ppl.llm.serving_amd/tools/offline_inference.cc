@@ -32,6 +32,8 @@ int main(int argc, char** argv) {
                                  "client_qps_measure's --request_rate");
     a.Def("--lora-dirs", "", "LoRA adapters to load: a,b,... (each holds lora.pplhip, tools/export_peft_lora.py); the slot is the position");
     a.Def("--lora-map", "", "adapter slot of every request, -1 = none: 0,-1,1,... cycled over the requests (needs --lora-dirs)");
+    a.Def("--guide-regex", "", "prompts4 / samples1024: guided decoding, every answer must match this regular expression in full (needs "
+                               "--tokenizer-path; a scenario gives each request its own \"guide_regex\")");
     if (!a.Parse(argc, argv)) return -1;
     if (a.Bool("--help")) { a.PrintHelp(); return 0; }
 
@@ -118,6 +120,7 @@ int main(int argc, char** argv) {
         for (auto& r : requests) {
             r->num_logprobs = a.Int("--num-logprobs");
             r->prompt_logprobs = a.Int("--prompt-logprobs");
+            r->guide_regex = a.Str("--guide-regex");
         }
 
     // ---- LoRA adapters: slot = position in --lora-dirs; --lora-map cycled over the requests ---------------------
