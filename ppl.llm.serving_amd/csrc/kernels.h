@@ -169,7 +169,7 @@ hipError_t launch_interleave_rows(hipStream_t s, const void* src, void* dst, int
 
 // ---- k_lora.hip: multi-LoRA, the low-rank update of a layer linear on the rows whose request carries an adapter --------------------
 constexpr int LORA_MAX_SLOTS = 64, LORA_MAX_RANK = 128;   // PPLHIP_LORA_MAX_SLOTS / PPLHIP_LORA_MAX_RANK
-// up to 16 token rows that share adapter slot `slot`; row[i] = -1 marks padding.  Built on the host (pplhip.cc lora_build_tiles).
+// up to 16 token rows that share adapter slot `slot`; row[i] = -1 marks padding.  Built on the host (rt_lora.cc lora_build_tiles).
 struct LoraTile {
     int32_t slot;
     int32_t n;          // rows in use (the first n of row[])

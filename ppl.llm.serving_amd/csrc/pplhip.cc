@@ -1,303 +1,17 @@
 // libpplhip.so -- the C ABI of include/pplhip.h: per-rank runtime (streams, weights, KV slab, step inputs,
 // activations), the decoder forward as a sequence of hand-written gfx950 kernels, RCCL collectives for tensor
 // parallelism, the sampler and per-request LoRA adapters (slots loaded at run time, a tile list per
-// step: "multi-LoRA" below).  This file replaces what the reference reaches through ppl.nn
+// step: "multi-LoRA").  The runtime replaces what the reference reaches through ppl.nn
 // (Engine/Runtime/Tensor, src/backends/cuda/resource_manager.cc:43-211) and ppl.llm.kernel.cuda.
-#include "../../include/pplhip.h"
-
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <unordered_map>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "kernels.h"
-
-using namespace pplhip;
-
-namespace {
-
-// activation format of the layer linears, from pplhip_model_desc.act_quant_bit (act_format, derived once at init):
-// fp16, int8 per token (online_i8i8), or e4m3fn per token under a power-of-two scale (online_f8f8)
-enum { ACT_FP16 = 0, ACT_I8 = 1, ACT_FP8 = 2 };
-
-struct Linear {
-    int N = 0, K = 0, qbit = 0, group = 0;
-    int Kp = 0;  // row stride on the device: K rounded up to the GEMM k-tile (64) with zero columns, so that a tensor-
-                 // parallel slice like 11008 / 8 = 1376 still runs on the DMA tile kernels (the activation operand is
-                 // padded with zeros to the same stride)
-    void* w = nullptr;
-    uint16_t* scale = nullptr;
-    uint64_t elt_bytes(uint64_t n) const { return qbit == 0 ? n * 2 : qbit == 8 ? n : n / 2; }
-    uint64_t w_bytes() const { return elt_bytes((uint64_t)N * K); }       // container (unpadded) size
-    uint64_t alloc_bytes() const { return elt_bytes((uint64_t)N * Kp); }  // device size
-    uint64_t s_bytes() const { return qbit == 0 ? 0 : qbit == 8 ? (uint64_t)N * 2 : (uint64_t)N * (K / group) * 2; }
-};
-
-struct GraphEntry { hipGraphExec_t exec; uint64_t tick; };
-
-struct Layer {
-    uint16_t* attn_norm = nullptr;
-    uint16_t* ffn_norm = nullptr;
-    Linear wqkv, wo, w13, w2;
-};
-
-// One adapter slot of a rank: per (layer, target) the two factors on the device, zero-padded to rank rp (a multiple of 16) and, for w2's
-// A, to the padded row stride Kp of the activation it multiplies.  Targets: 0 attention.wqkv, 1 attention.wo, 2 feed_forward.w2.
-enum { LORA_WQKV = 0, LORA_WO = 1, LORA_W2 = 2, LORA_TARGETS = 3 };
-struct LoraFactor {
-    uint16_t *a = nullptr, *b = nullptr;
-    int ra = 0, rb = 0;   // ranks the two arrived with
-};
-struct LoraAdapter {
-    bool committed = false;
-    float scale = 0.f;
-    std::vector<LoraFactor> f;   // [layer][target]; empty: nothing loaded
-};
-
-struct ProfEvent {
-    int cls;
-    hipEvent_t a, b;
-};
-
-// One collective channel of a rank: what two all-reduces need of their own to run side by side.  Channel 0 carries every collective
-// of a one-lane or two-chunk step, the self-test and the logits all-gather; channel 1 the second half-batch of a two-lane decode step.
-struct Channel {
-    int id = 0;                      // flag set of the direct collectives (k_comm.hip)
-    ncclComm_t comm = nullptr;       // RCCL communicator (a communicator serialises its streams, so each channel has one)
-    size_t x_scratch[2] = {0, 0};    // scratch double buffer: byte offsets inside the exchange region
-    uint32_t ar_count = 0;           // all-reduces issued (which scratch buffer is next)
-    uint32_t p2p_epoch = 0;          // epoch of the channel's flag words
-};
-
-// What the launches of one half-batch go out with.  run_launches builds a Lane per half on its stack for every step: lane 0 = the rank's
-// stream, workspaces and channel 0; lane 1 (two-lane decode only) = stream2, gemm_ws2, the attention workspace past the first half's
-// rows and channel 1.  Nothing in Rank is swapped while a step is issued, so an error return leaves nothing to restore.
-struct Lane {
-    hipStream_t stream = nullptr;
-    float* gemm_ws = nullptr;        // split-K partial slabs
-    float* attn_ws = nullptr;
-    size_t attn_ws_bytes = 0;
-    // split-K results left unreduced for the kernel that consumes them (kernels.h SplitSlabs): wqkv -> RoPE + KV write, wo -> FFN norm,
-    // w2 -> the next layer's attention norm (or the final norm)
-    SplitSlabs sl_qkv, sl_part, sl_part2;
-    Channel* ch = nullptr;
-};
-
-// pplhip_sample_rows stages one step's per-row arrays in one pinned block that goes up in one copy: for capacity cap_B,
-// seeds u64 [cap_B] | draws u64 [cap_B] | temperatures f32 [cap_B] | top_p f32 [cap_B] | top_k i32 [cap_B] | row list i32 [cap_B]
-constexpr int64_t SROWS_BYTES = 8 + 8 + 4 + 4 + 4 + 4;
-// pplhip_top_logprobs has a pinned block of its own (the step's sampler call restages h_srows while this one's copy may still be in
-// flight): temperatures f32 [cap_B] | num_logprobs i32 [cap_B] | row list i32 [cap_B] going up, and one block coming down, for `asked`
-// rows tokens i32 [asked, 20] | logprobs f32 [asked, 20]
-constexpr int64_t TLP_IN_BYTES = 4 + 4 + 4;
-constexpr int64_t TLP_OUT_BYTES = (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
-static_assert(PPLHIP_TOP_LOGPROBS_MAX == TOP_LOGPROBS_MAX, "header and kernel disagree");
-// prompt logprobs, per position: gather i64 + row i32 + n_top i32 going up (+ 8 for the gather's entry 0), and coming down
-// logprob f32 + rank i32 + 20 x (token i32 + logprob f32)
-constexpr int64_t PLP_IN_BYTES = 8 + 4 + 4;
-constexpr int64_t PLP_OUT_BYTES = 4 + 4 + (4 + 4) * PPLHIP_TOP_LOGPROBS_MAX;
-// logit rules: a slot's record in the device table and in the pinned staging ring is
-// head i32 [4] = {n_bias, n_stop, has_mask, 0} | bias tokens i32 [512] | bias values f32 [512] | stops i32 [64] | mask u32 [words, padded to 4]
-// so one copy carries a rule.  pplhip_logit_edit stages slots i32 [cap_B] | flags u32 [cap_B] | row list i32 [cap_B] in a block of its own.
-static_assert(PPLHIP_LOGIT_BIAS_MAX == LOGIT_BIAS_MAX && PPLHIP_LOGIT_STOP_MAX == LOGIT_STOP_MAX, "header and kernel disagree");
-static_assert(PPLHIP_GUIDE_MAX_SLOTS == GUIDE_MAX_SLOTS && PPLHIP_GUIDE_MAX_STATES == GUIDE_MAX_STATES && GUIDE_DEAD == 255, "header and kernel disagree");
-constexpr int64_t LR_HEAD = 16, LR_BIAS_TOK = LR_HEAD, LR_BIAS_VAL = LR_BIAS_TOK + 4 * LOGIT_BIAS_MAX,
-                  LR_STOPS = LR_BIAS_VAL + 4 * LOGIT_BIAS_MAX, LR_MASK = LR_STOPS + 4 * LOGIT_STOP_MAX;
-constexpr int LR_RING = 4;   // staging records; a record is reused once the event behind its copy has passed
-constexpr int64_t LRE_BYTES = 4 + 4 + 4;
-
-struct Rank {
-    int device = 0;
-    int global_rank = 0;
-    hipStream_t stream = nullptr;
-    Channel ch[2];                      // ch[1]: scratch pair when two-stream decode is on, communicator when it was asked for explicitly
-    hipStream_t comm_stream = nullptr;  // collectives of a two-chunk step (pplhip_run)
-    // two-lane decode (plan_step): the second half of a mid-size pure-decode step runs its layers on stream2, beside the first half on
-    // `stream`, with split-K / attention workspaces of its own (Lane); ev_fork / ev_join order the two around the step
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    float* gemm_ws2 = nullptr;
-    bool dual_seen = false;
-    hipEvent_t ev_compute[2] = {nullptr, nullptr}, ev_comm[2] = {nullptr, nullptr};
-    const int64_t* h_seq = nullptr;     // host copy of this step's seq_starts (lives in the staging buffer)
-    std::string err;
-
-    // weights
-    uint16_t* embed = nullptr;
-    uint16_t* norm = nullptr;
-    Linear output;
-    std::vector<Layer> layers;
-    float* rope = nullptr;
-    std::vector<void*> allocs;
-
-    // KV slab
-    uint64_t kv_tokens = 0;
-    void* kv_cache = nullptr;
-    uint16_t* kv_scale = nullptr;
-
-    // step inputs
-    int64_t* stage_host[2] = {nullptr, nullptr};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    int stage_cur = 0;
-    int64_t* step_dev = nullptr;  // packed: token_ids | seq_starts | kv_starts | start_pos | cache_indices(mode 0)
-    int64_t cap_T = 0, cap_B = 0;
-    int64_t *d_tok = nullptr, *d_seq = nullptr, *d_kvs = nullptr, *d_sp = nullptr, *d_ci = nullptr;
-    int64_t* pages_dev = nullptr;   // mode 1: [B, max_pages]
-    int64_t* pages_host = nullptr;  // pinned
-    uint64_t pages_cap = 0;
-    int64_t B = 0, T = 0, decoding_batches = 0, max_seq_len = 0, max_kv_len = 0, max_pages = 0;
-
-    // activations
-    uint16_t *h = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *part = nullptr, *part2 = nullptr, *gu = nullptr,
-             *act = nullptr, *hn = nullptr;
-    std::unordered_map<uint64_t, GraphEntry> graphs;  // captured pure-decode steps by shape (run_decode_graph)
-    uint64_t graph_tick = 0;
-    int8_t* xq = nullptr;  // online_i8i8: int8 activations [cap_T, max row] and per-token scales
-    float* sx = nullptr;
-    float* logits_local = nullptr;  // [B, V/tp] (tp > 1)
-    float* logits_gather = nullptr; // [tp, B, V/tp]
-    float* logits = nullptr;        // [B, V]
-    float* attn_ws = nullptr;
-    size_t attn_ws_bytes = 0;
-    float* gemm_ws = nullptr;  // split-K partial slabs (gemm_ws2: as many bytes)
-    size_t gemm_ws_bytes = 0;
-
-    // sampler (local rank 0)
-    float *d_temp = nullptr, *d_topp = nullptr, *d_rand = nullptr, *d_lp = nullptr;
-    int32_t* d_tokout = nullptr;
-    uint16_t* count_map = nullptr;
-    int64_t* d_slots = nullptr;
-    float *d_rep = nullptr, *d_pres = nullptr, *d_freq = nullptr, *d_ptemp = nullptr;
-    float* h_rand = nullptr;  // pinned
-    char *h_srows = nullptr, *d_srows = nullptr;  // pplhip_sample_rows: pinned staging and its device image, SROWS_BYTES per batch row
-    char *h_tlp_in = nullptr, *d_tlp_in = nullptr;    // pplhip_top_logprobs: TLP_IN_BYTES per batch row going up ...
-    char *h_tlp_out = nullptr, *d_tlp_out = nullptr;  // ... TLP_OUT_BYTES per batch row coming down
-    // logit rules, all allocated by the first pplhip_logit_rule_set: the device table (cap_B records of lr_rec bytes), the pinned
-    // staging ring with one event per record, which slots hold a rule, and pplhip_logit_edit's staging block with the event of its copy
-    char *lr_table = nullptr, *lr_stage = nullptr;
-    int64_t lr_rec = 0;
-    hipEvent_t lr_ev[LR_RING] = {};
-    int lr_next = 0;
-    std::vector<uint8_t> lr_has;
-    char *h_lre = nullptr, *d_lre = nullptr;
-    hipEvent_t lre_ev = nullptr;
-    // guided decoding: the vocabulary (pplhip_guide_set_vocab; gd_n_tok < 0: none yet), the loaded slots' masks and state counts, and
-    // pplhip_guide_edit's staging block guide slots i32 [cap_B] | states i32 [cap_B] | row list i32 [cap_B] with the event of its copy
-    uint8_t* gd_bytes = nullptr;
-    int64_t* gd_off = nullptr;
-    int gd_n_tok = -1;
-    uint32_t* gd_mask[GUIDE_MAX_SLOTS] = {};
-    int gd_states[GUIDE_MAX_SLOTS] = {};
-    char *h_gde = nullptr, *d_gde = nullptr;
-    hipEvent_t gde_ev = nullptr;
-    // prompt logprobs (k_prompt_logprobs.hip), all allocated by the first pplhip_set_prompt_logprobs that asks, for cap_T positions.
-    // Going up in one copy, P the staged positions: gather i64 [P + 1] (entry j + 1 = row_j + 1: the final norm's gathering form reads row
-    // gather[j + 1] - 1) | rows i32 [P] | n_top i32 [P].  Coming down in one copy: logprob f32 [P] | rank i32 [P] | top tokens i32 [P, 20] |
-    // top logprobs f32 [P, 20] (the last two only when a position asked for them); behind PLP_OUT_BYTES x cap_T of the pinned block the
-    // rows of the last run, which the staging block cannot keep (the next step restages it before its run).
-    char *h_plp_in = nullptr, *d_plp_in = nullptr, *h_plp_out = nullptr, *d_plp_out = nullptr;
-    hipEvent_t plp_ev = nullptr;            // the copy out of h_plp_in is done
-    int64_t plp_n = 0;                      // positions of the staged step (pplhip_set_inputs clears it)
-    bool plp_top = false;                   // one of them asked for the ranking
-    int64_t plp_done = 0;                   // positions of the last pplhip_run
-
-    // exchange region of the direct collectives (k_comm.hip): fine-grained, peer-mapped; holds the flag words and the buffers
-    // the collectives work in place on (part, part2) or push into (logits_gather)
-    char* xbase = nullptr;
-    size_t xbytes = 0, x_part = 0, x_part2 = 0, x_local = 0;  // byte offsets inside the region (the scratch pairs: Channel)
-    P2pPeers peers{};
-    bool peer_ipc[P2P_MAX_RANKS] = {};  // peers.base[g] came from hipIpcOpenMemHandle (closed on destroy)
-    uint32_t* p2p_status = nullptr;     // pinned host word a kernel raises when one of its bounded spins timed out
-    int32_t* d_flag = nullptr;          // one int for the cross-process agreement on the self-test
-    // stream hand-offs of the two-chunk schedule through device-memory epochs (k_comm.hip handoff_*): words 0..1 = "chunk i's
-    // partial sums are complete" (compute -> communication stream), 2..3 = "chunk i is reduced" (communication -> compute)
-    uint32_t* hflags = nullptr;
-    uint32_t h_ready_ep[2] = {0, 0}, h_done_ep[2] = {0, 0};
-
-    // multi-LoRA (k_lora.hip): adapters by slot, allocated when a slot is loaded
-    LoraAdapter lora[LORA_MAX_SLOTS];
-    int lora_committed = 0;                 // slots in use
-    std::vector<LoraSlot> lora_tab_host;    // [layer][target][slot]: what the kernels read, mirrored on the device (lora_tab)
-    LoraSlot* lora_tab = nullptr;
-    LoraTile* lora_tiles = nullptr;         // the staged step's tile list (device) and its pinned staging copy
-    LoraTile* lora_tiles_host = nullptr;
-    hipEvent_t lora_ev = nullptr;           // the copy out of lora_tiles_host is done
-    int64_t lora_tile_cap = 0;
-    uint16_t* lora_t = nullptr;             // shrink output [lora_tile_cap][16][LORA_MAX_RANK] fp16
-    int lora_ntiles = 0;                    // > 0: the staged step has rows on adapters (pplhip_set_adapters; pplhip_set_inputs clears it)
-    std::vector<uint8_t> lora_touch;        // [layer][target]: some adapter of the staged assignment changes this linear
-    bool lora_stale = false;                // a slot was unloaded under a staged assignment: pplhip_run wants new inputs first
-
-    // diagnosis (pplhip_debug_run_dump): residual stream h and the pending row-parallel FFN output after every layer
-    uint16_t* dump_dev = nullptr;  // [L+1][2][T, hidden] fp16 (slot 0 = h, slot 1 = pending), allocated for one run
-
-    // profiling
-    std::vector<ProfEvent> prof;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_free;
-};
-
-}  // namespace
-
-struct pplhip_ctx {
-    pplhip_model_desc d;
-    pplhip_opts o;
-    int kv_fmt = KV_FP16;  // KV cache format of (d.cache_quant_bit, d.cache_quant_group): kv_format(), derived once at init
-    int act_fmt = ACT_FP16;  // activation format of d.act_quant_bit: act_format(), derived once at init
-    int tp = 1;
-    bool tp_overlap = true;              // PPLHIP_TP_OVERLAP=0 keeps the collectives on the compute stream
-    // PPLHIP_TP_OVERLAP_MIN_TOKENS.  Measured on one MI355X with identity collectives (bench.py --emulate-tp 2/4/8,
-    // profiles/r01_tp_emulation.txt): the two-chunk schedule costs a 1024-row decode step +6..7 ms (27 us per
-    // cross-stream hand-off x 128, plus two half-size GEMM launches instead of one) -- about what the 64 all-reduces
-    // of 8 MB it hides are worth -- so it is used for steps that carry prefill tokens (T >= 2048: 16+ MB per
-    // all-reduce, chunks of >= 1024 rows keep the GEMM tiles full), not for pure decode steps of <= 1024 rows.
-    int64_t tp_overlap_min_tokens = 2048;
-    bool handoff_flags = true;  // PPLHIP_TP_HANDOFF=events: HIP events instead of device-memory epochs between the two streams
-    int tp_debug = 0;           // PPLHIP_TP_DEBUG (diagnosis): bit 0 = hand-off events are created anew instead of re-recorded inside a step,
-                                // bit 1 = chunks, but their collectives stay on the compute stream
-    bool defer_on = true;       // PPLHIP_DEFER_REDUCE=0: every split-K linear reduces its own slabs
-    bool tp_on = false;     // the tensor-parallel step schedule (collectives after wo / w2, logits gather) is active
-    // collectives: 2 = direct kernels over peer-mapped memory (k_comm.hip), 1 = RCCL, 0 = none.  PPLHIP_COMM=auto (default:
-    // direct when the self-test passes on every rank, else RCCL) | p2p (direct or fail) | rccl
-    int comm_mode = 0;
-    int comm_want = 0;      // 0 auto, 1 rccl only, 2 p2p only
-    bool p2p_connected = false;
-    uint64_t p2p_timeout_ticks = 0;  // s_memrealtime ticks (100 MHz)
-    // PPLHIP_DUAL_STREAM=1: pure-decode steps of dual_min_rows..dual_max_rows rows as two half-batches on two streams (run_launches)
-    // -1 (default): automatic -- under real tensor parallelism (a communicator over >= 2 ranks) pure-decode steps of 512..1024 rows run as
-    // two half-batches on two streams, so that each half's all-reduces overlap the other half's matmuls (the north star's schedule;
-    // +0.25 ms of compute per 1024-row 7B / TP8 step against ~2.2 ms of link time, profiles/r04_late_experiments.md 1); config 4's 256
-    // rows stay on one stream (halves of 128 rows measured -8 %).  Automatic only on the direct collectives (two channels, validated on
-    // one device at tp 2 / 4): two RCCL communicators running concurrently on one device have never run on >= 2 devices, so a
-    // group that fell back to RCCL keeps one stream unless PPLHIP_DUAL_STREAM=1 asks for it.  1: rows dual_min_rows..dual_max_rows at any tp; 0: never
-    int dual_mode = -1;
-    bool dual_auto = false;          // the automatic rule is in force (row window 512..1024)
-    int64_t dual_min_rows = 96, dual_max_rows = 512;
-    // Sequence-parallel residual stream (round 6): on the direct collectives the all-reduce behind wo / w2 also does the residual add and the
-    // RMSNorm that consumes it, on the rows the rank owns after the first shot, and the second shot gathers NORMED rows (k_comm.hip
-    // p2p_allreduce_norm_kernel): 1 / tp of the norm work per rank and one launch less per half-layer.  Each rank then keeps only its own
-    // rows of the residual stream h.  Not with int8 activations (the norm writes the quantised operand there), residual dumps, RCCL
-    // (plain all-reduce + replicated norm as before) or hidden > 8192.  PPLHIP_TP_FUSE_NORM=0: off (A/B runs)
-    bool fuse_norm_want = true;
-    bool emulate_tp = false;         // PPLHIP_EMULATE_TP (bench.py --emulate-tp): one rank's slice, collectives are local identities
-    int selftest = 0;                // direct collectives' start-up self-test: 0 not run, 1 passed on every rank, -1 failed (RCCL in charge)
-    std::string comm_notes;          // every fallback taken at start-up, in order (never silent: also on stderr)
-    bool graph_on = false;           // PPLHIP_DECODE_GRAPH=1: replay pure-decode steps as HIP graphs (opt-in, see run_decode_graph)
-    int64_t graph_max_batch = 64;    // above this a step is seconds of GPU work per thousand launches: nothing to gain
-    int H = 0, Hkv = 0, D = 0, inter = 0, vocab_local = 0;
-    std::vector<Rank> ranks;
-    std::string err;
-};
-
-namespace {
+// What lives where:
+//   pplhip.cc       (this file) init and destroy, weights, the KV slab, pplhip_set_inputs, the step plan and its launches (plan_step,
+//                   run_launches, the stream hand-offs of the two-chunk schedule, the decode graph), pplhip_run / sync / logits, profiling
+//   rt_comm.cc      the direct collectives' connection and self-test, pplhip_comm_*
+//   rt_lora.cc      multi-LoRA: adapter slots and the step's tile list
+//   rt_postproc.cc  what happens to the logits: samplers, penalty, top-N logprobs, logit rules, guided decoding, prompt logprobs
+//   rt_ops.cc       pplhip_op_*: single kernels and pure functions on caller-owned memory, for the tests (no context)
+//   rt_internal.h   what they share: Rank and pplhip_ctx, error reporting, the guarded staging block, the packed blocks' layouts
+#include "rt_internal.h"
 
 bool verbose() {   // PPLHIP_VERBOSE: messages on stderr (errors, the collectives' choice, graph capture)
     static const bool on = getenv("PPLHIP_VERBOSE") != nullptr;
@@ -317,21 +31,6 @@ int fail(pplhip_ctx* c, int rank, int code, const std::string& msg) {
     if (verbose()) fprintf(stderr, "[pplhip] error %d (rank %d): %s\n", code, rank, msg.c_str());
     return code;
 }
-
-#define HIPCK(c, r, expr)                                                                                            \
-    do {                                                                                                             \
-        hipError_t e__ = (expr);                                                                                     \
-        if (e__ != hipSuccess)                                                                                       \
-            return fail(c, r, e__ == hipErrorOutOfMemory ? PPLHIP_OUT_OF_MEMORY : PPLHIP_DEVICE_RUNTIME_ERROR,       \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                                         \
-    } while (0)
-
-#define NCCLCK(c, r, expr)                                                                                           \
-    do {                                                                                                             \
-        ncclResult_t e__ = (expr);                                                                                   \
-        if (e__ != ncclSuccess)                                                                                      \
-            return fail(c, r, PPLHIP_DEVICE_RUNTIME_ERROR, std::string(#expr) + ": " + ncclGetErrorString(e__));     \
-    } while (0)
 
 static inline float h2f_host(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 static inline uint16_t f2h_host(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
@@ -356,6 +55,8 @@ int dev_alloc(pplhip_ctx* c, int r, void** p, uint64_t bytes) {
     c->ranks[r].allocs.push_back(*p);
     return 0;
 }
+
+namespace {
 
 int linear_alloc(pplhip_ctx* c, int r, Linear* l, int N, int K, int qbit, int group, bool pad_k = false) {
     l->N = N; l->K = K; l->qbit = qbit; l->group = group;
@@ -394,11 +95,13 @@ bool find_tensor(pplhip_ctx* c, Rank& R, const char* name, void** ptr, uint64_t*
     return false;
 }
 
+}  // namespace
+
 // KV cache format of a (cache_quant_bit, cache_quant_group) pair at head_dim D, -1 when the pair is not one of the four:
 // (0, 1) fp16, (8, 8) int8 group 8, (8, D) fp8 e4m3 with one power-of-two scale per head row, (4, 32) int4 with one fp16 scale per 32
 // channels (the last two at D = 32, 64, 128).  Everything behind the sizes (make_kv_addr, pplhip_kv_block_bytes) works from the pair
 // itself: kv_row_bytes() bytes of codes and D / group scales per row.
-static int kv_format(int quant_bit, int quant_group, int D) {
+int kv_format(int quant_bit, int quant_group, int D) {
     if (quant_bit == 0 && quant_group == 1) return KV_FP16;
     if (quant_bit == 8 && quant_group == 8) return KV_I8G8;
     if (quant_bit == 8 && quant_group == D && (D == 32 || D == 64 || D == 128)) return KV_FP8;
@@ -424,6 +127,8 @@ KvAddr make_kv_addr(const pplhip_model_desc& d, int Hkv, int D, uint64_t tokens,
     a.page_shift = (a.page_size & (a.page_size - 1)) == 0 ? __builtin_ctz((unsigned)a.page_size) : -1;
     return a;
 }
+
+namespace {
 
 void prof_begin(pplhip_ctx* c, Rank& R, const Lane& lane, int cls, ProfEvent* ev) {
     ev->cls = -1;
@@ -463,208 +168,6 @@ int decode_split(const pplhip_plan_settings& s, int64_t nb, int64_t max_kv_len) 
         if (mode == 2 && split < 2 && max_kv_len >= 64) split = 2;
     }
     return split;
-}
-
-// ---- direct collectives: connection + self-test -------------------------------------------------------------------------
-
-// the direct path cannot be used: an error when it was demanded (or no RCCL communicator exists), else RCCL stays in charge
-int p2p_unavailable(pplhip_ctx* c, int rank, const std::string& why) {
-    if (c->comm_want == 2 || c->comm_mode != 1) return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, "direct collectives unavailable: " + why);
-    c->selftest = -1;
-    comm_note(c, "direct collectives unavailable (" + why + "): RCCL takes over");
-    return 0;
-}
-
-// Runs both collectives four times on changing patterns on every local rank (all ranks of the group do this at the same time,
-// in this process or in others) and compares with the exact answer.  Every rank then learns whether ALL ranks passed
-// (one RCCL all-reduce when a communicator exists); only then comm_mode becomes 2.
-// `local_failure`: this process could not even map its peers -- it skips the kernels but still takes part in the agreement, so that
-// the other processes (whose self-test kernels give up waiting for it after the bounded spin) do not wait in the all-reduce forever.
-int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
-    const int n = (int)c->ranks.size(), tp = c->tp, hd = c->d.hidden_dim;
-    // granules of the direct kernels (k_comm.hip): 16-byte pieces of the fp16 partial sums, 8- or 16-byte pieces of a shard's fp32
-    // logits rows; a model that does not fit them keeps RCCL instead of failing at its first real step
-    std::string shape_failure;
-    if (!local_failure && (c->vocab_local % 2 != 0 || hd % 8 != 0)) {
-        shape_failure = "vocab/tp must be even and hidden a multiple of 8 (vocab_local " + std::to_string(c->vocab_local) + ", hidden " + std::to_string(hd) + ")";
-        local_failure = &shape_failure;
-    }
-    const int64_t cnt = std::min<int64_t>((int64_t)1 << 20, c->ranks[0].cap_T * (int64_t)hd) / 8 * 8;
-    // the gather test: every rank's [grows, gcols] fp32 block -> [grows, gcols * tp]
-    const int64_t gcols = c->vocab_local / 2 * 2, grows = std::min<int64_t>(c->ranks[0].cap_B, std::max<int64_t>(1, ((int64_t)1 << 18) / gcols));
-    const int64_t gcnt = grows * gcols;
-    const char* e = getenv("PPLHIP_P2P_SELFTEST_MS");
-    const uint64_t ticks = (uint64_t)(e ? std::max(1, atoi(e)) : 10000) * 100000ull;
-    auto pat = [](int64_t i, int g, int round) { return p2p_pattern_value(i, g, round); };
-    bool ok = local_failure == nullptr;
-    std::string why = local_failure ? *local_failure : std::string();
-    std::vector<uint16_t> hbuf(cnt);
-    std::vector<float> gbuf(gcnt), gall;
-    for (int round = 0; round < 4 && ok; ++round) {
-        for (int r = 0; r < n; ++r) {
-            Rank& R = c->ranks[r];
-            HIPCK(c, r, hipSetDevice(R.device));
-            // inputs are written by a kernel on the rank's stream, like the partial sums and logits shards of a real step
-            HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, cnt, R.logits_local, gcnt, R.global_rank, round));
-        }
-        for (int r = 0; r < n; ++r) {
-            Rank& R = c->ranks[r];
-            Channel& ch = R.ch[0];
-            HIPCK(c, r, hipSetDevice(R.device));
-            HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], cnt, ++ch.p2p_epoch,
-                                             ticks, R.p2p_status));
-            HIPCK(c, r, launch_p2p_allgather(R.stream, R.peers, R.global_rank, tp, R.x_local, R.logits, grows, gcols * 4, (int64_t)gcols * 4 * tp,
-                                             ++ch.p2p_epoch, ticks, R.p2p_status));
-        }
-        for (int r = 0; r < n && ok; ++r) {
-            Rank& R = c->ranks[r];
-            HIPCK(c, r, hipSetDevice(R.device));
-            HIPCK(c, r, hipStreamSynchronize(R.stream));
-            if (*R.p2p_status) { ok = false; why = "spin timed out (status " + std::to_string(*R.p2p_status) + ")"; *R.p2p_status = 0; break; }
-            HIPCK(c, r, hipMemcpy(hbuf.data(), R.part, cnt * 2, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < cnt && ok; ++i) {
-                float want = 0.f;
-                for (int g = 0; g < tp; ++g) want += pat(i, g, round);
-                if ((float)__builtin_bit_cast(_Float16, hbuf[i]) != want) {
-                    ok = false;
-                    int64_t nbad = 0, last = i;
-                    for (int64_t j = i; j < cnt; ++j) {
-                        float w2 = 0.f;
-                        for (int g = 0; g < tp; ++g) w2 += pat(j, g, round);
-                        if ((float)__builtin_bit_cast(_Float16, hbuf[j]) != w2) { ++nbad; last = j; }
-                    }
-                    why = "all-reduce mismatch: round " + std::to_string(round) + " rank " + std::to_string(R.global_rank) + " first " + std::to_string(i) +
-                          " last " + std::to_string(last) + " bad " + std::to_string(nbad) + "/" + std::to_string(cnt) + " got " +
-                          std::to_string((float)__builtin_bit_cast(_Float16, hbuf[i])) + " want " + std::to_string(want);
-                }
-            }
-            gall.resize((size_t)gcnt * tp);
-            HIPCK(c, r, hipMemcpy(gall.data(), R.logits, gall.size() * 4, hipMemcpyDeviceToHost));
-            for (int g = 0; g < tp && ok; ++g)
-                for (int64_t i = 0; i < gcnt && ok; ++i)
-                    if (gall[(size_t)(i / gcols) * gcols * tp + (size_t)g * gcols + i % gcols] != pat(i, g, round + 2)) {
-                        ok = false;
-                        int64_t nbad = 0, last = i;
-                        for (int64_t j = i; j < gcnt; ++j)
-                            if (gall[(size_t)(j / gcols) * gcols * tp + (size_t)g * gcols + j % gcols] != pat(j, g, round + 2)) { ++nbad; last = j; }
-                        why = "all-gather mismatch: round " + std::to_string(round) + " rank " + std::to_string(R.global_rank) + " block " + std::to_string(g) +
-                              " first " + std::to_string(i) + " last " + std::to_string(last) + " bad " + std::to_string(nbad) + "/" + std::to_string(gcnt) +
-                              " got " + std::to_string(gall[(size_t)(i / gcols) * gcols * tp + (size_t)g * gcols + i % gcols]) + " want " + std::to_string(pat(i, g, round + 2)) +
-                              " prev-round " + std::to_string(pat(i, g, round + 1));
-                    }
-        }
-    }
-    // the fused all-reduce + residual add + RMSNorm (p2p_allreduce_norm_kernel, what a step issues when fuse_norm_active): against a LOCAL
-    // reference built from parts that are already verified -- the plain all-reduce above leaves the exact sums on every rank, the kernel's
-    // own one-rank form ("solo": same arithmetic, no peers) turns them into the expected residual and normed rows; the real kernel, run on
-    // the unreduced patterns, must then give the same bits in every row it gathered and in the residual rows it owns
-    const int64_t frows = hd > 0 ? cnt / hd : 0;
-    if (ok && c->fuse_norm_want && c->act_fmt == ACT_FP16 && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN && frows >= 1 &&
-        c->ranks[0].gemm_ws_bytes >= (size_t)frows * hd * 4 + (size_t)hd * 2) {
-        const int64_t fcnt = frows * hd;
-        std::vector<uint16_t> want_x(fcnt), want_h(fcnt);
-        for (int round = 0; round < 2 && ok; ++round) {
-            for (int r = 0; r < n; ++r) {
-                Rank& R = c->ranks[r];
-                Channel& ch = R.ch[0];
-                HIPCK(c, r, hipSetDevice(R.device));
-                uint16_t* xref = (uint16_t*)R.gemm_ws, *href = xref + fcnt, *w = href + fcnt;
-                HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, fcnt, nullptr, 0, R.global_rank, round + 4));
-                HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], fcnt, ++ch.p2p_epoch, ticks, R.p2p_status));
-                HIPCK(c, r, launch_p2p_pattern(R.stream, R.h, fcnt, nullptr, 0, 17, round + 4));    // the residual stream: the same on every rank
-                HIPCK(c, r, launch_p2p_pattern(R.stream, w, hd, nullptr, 0, 23, round + 4));
-                HIPCK(c, r, hipMemcpyAsync(href, R.h, (size_t)fcnt * 2, hipMemcpyDeviceToDevice, R.stream));
-                HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, 1, R.x_part, 0, frows, hd, href, w, c->d.norm_eps, xref, 0, ticks, R.p2p_status));
-                HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, fcnt, nullptr, 0, R.global_rank, round + 4));
-                HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], frows, hd, R.h, w, c->d.norm_eps,
-                                                      R.xn, ++ch.p2p_epoch, ticks, R.p2p_status));
-            }
-            for (int r = 0; r < n && ok; ++r) {
-                Rank& R = c->ranks[r];
-                HIPCK(c, r, hipSetDevice(R.device));
-                HIPCK(c, r, hipStreamSynchronize(R.stream));
-                if (*R.p2p_status) { ok = false; why = "fused all-reduce + norm: spin timed out (status " + std::to_string(*R.p2p_status) + ")"; *R.p2p_status = 0; break; }
-                HIPCK(c, r, hipMemcpy(want_x.data(), R.gemm_ws, (size_t)fcnt * 2, hipMemcpyDeviceToHost));
-                HIPCK(c, r, hipMemcpy(want_h.data(), (uint16_t*)R.gemm_ws + fcnt, (size_t)fcnt * 2, hipMemcpyDeviceToHost));
-                HIPCK(c, r, hipMemcpy(hbuf.data(), R.xn, (size_t)fcnt * 2, hipMemcpyDeviceToHost));
-                int64_t bad = 0, first = -1;
-                for (int64_t i = 0; i < fcnt; ++i) if (hbuf[i] != want_x[i]) { if (!bad) first = i; ++bad; }
-                if (bad) { ok = false; why = "fused all-reduce + norm: " + std::to_string(bad) + "/" + std::to_string(fcnt) + " normed values differ on rank " + std::to_string(R.global_rank) + " (first: row " + std::to_string(first / hd) + ")"; break; }
-                const int64_t per = (frows + tp - 1) / tp, lo = std::min<int64_t>(per * R.global_rank, frows), hi = std::min<int64_t>(lo + per, frows);
-                HIPCK(c, r, hipMemcpy(hbuf.data(), R.h, (size_t)fcnt * 2, hipMemcpyDeviceToHost));
-                for (int64_t i = lo * hd; i < hi * hd; ++i) if (hbuf[i] != want_h[i]) { ++bad; }
-                if (bad) { ok = false; why = "fused all-reduce + norm: " + std::to_string(bad) + " residual values of the owned rows differ on rank " + std::to_string(R.global_rank); break; }
-            }
-        }
-    }
-    // agreement: min over all ranks of the group
-    if (c->comm_mode == 1) {
-        for (int r = 0; r < n; ++r) {
-            Rank& R = c->ranks[r];
-            HIPCK(c, r, hipSetDevice(R.device));
-            const int32_t v = ok ? 1 : 0;
-            HIPCK(c, r, hipMemcpy(R.d_flag, &v, 4, hipMemcpyHostToDevice));
-        }
-        NCCLCK(c, -1, ncclGroupStart());
-        for (int r = 0; r < n; ++r) NCCLCK(c, r, ncclAllReduce(c->ranks[r].d_flag, c->ranks[r].d_flag, 1, ncclInt32, ncclMin, c->ranks[r].ch[0].comm, c->ranks[r].stream));
-        NCCLCK(c, -1, ncclGroupEnd());
-        for (int r = 0; r < n; ++r) {
-            Rank& R = c->ranks[r];
-            HIPCK(c, r, hipSetDevice(R.device));
-            HIPCK(c, r, hipStreamSynchronize(R.stream));
-            int32_t v = 0;
-            HIPCK(c, r, hipMemcpy(&v, R.d_flag, 4, hipMemcpyDeviceToHost));
-            if (!v && ok) { ok = false; why = "another rank failed its self-test"; }
-        }
-    }
-    if (!ok) {
-        // the check loop stopped at the first rank that showed a failure: drain EVERY local rank (the others normally time out on
-        // the same dead peer) and clear every status word, or the RCCL steps that follow would report a stale "timed out"
-        for (int r = 0; r < n; ++r) {
-            Rank& R = c->ranks[r];
-            (void)hipSetDevice(R.device);
-            (void)hipStreamSynchronize(R.stream);
-            if (R.p2p_status) *R.p2p_status = 0;
-        }
-        return p2p_unavailable(c, 0, "self-test: " + why);
-    }
-    c->comm_mode = 2;
-    c->selftest = 1;
-    if (verbose()) fprintf(stderr, "[pplhip] direct collectives over peer-mapped memory: self-test passed on %d local rank(s) of %d\n", n, tp);
-    return 0;
-}
-
-// all ranks of the group are in this process (the reference's mode, resource_manager.cc:392-422)
-int p2p_connect_local(pplhip_ctx* c) {
-    const int n = (int)c->ranks.size();
-    for (int r = 0; r < n; ++r) {
-        Rank& R = c->ranks[r];
-        HIPCK(c, r, hipSetDevice(R.device));
-        for (int g = 0; g < n; ++g) {
-            Rank& Q = c->ranks[g];
-            if (Q.device != R.device) {
-                hipError_t e = hipDeviceEnablePeerAccess(Q.device, 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); return p2p_unavailable(c, r, std::string("peer access: ") + hipGetErrorString(e)); }
-                (void)hipGetLastError();
-            }
-            R.peers.base[g] = Q.xbase;
-        }
-    }
-    c->p2p_connected = true;
-    return p2p_selftest(c);
-}
-
-// a kernel of the direct path gave up waiting for a peer: surfaced at the step's synchronisation points
-int p2p_check(pplhip_ctx* c, int rank) {
-    Rank& R = c->ranks[rank];
-    if (R.p2p_status && *R.p2p_status == 64)
-        return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, "stream hand-off timed out (compute / communication stream of a tensor-parallel step)");
-    if (c->comm_mode == 2 && R.p2p_status && *R.p2p_status) {
-        const uint32_t v = *R.p2p_status;
-        return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, "direct collective timed out waiting for rank " + std::to_string((v - 1) & 15) +
-                    ((v - 1) & 16 ? " (end barrier)" : " (start barrier)"));
-    }
-    return 0;
 }
 
 // ---- the hand-off between a compute stream and the communication stream (two-chunk schedule), once: device-memory epochs
@@ -708,11 +211,6 @@ int comm_pickup(pplhip_ctx* c, int rank, hipStream_t to, int i) {
 }
 
 }  // namespace
-
-static pplhip_plan_settings plan_settings(const pplhip_ctx* c, const Rank& R);
-static bool fuse_norm_active(const pplhip_plan_settings& s, bool dump);
-
-extern "C" {
 
 int pplhip_version(void) { return (1 << 16) | 2; }  // 1.1: pplhip_model_desc.act_quant_bit, comm_* and W8A8 operator entry points;
                                                     // 1.2: fp8 e4m3 KV cache (cache_quant_bit 8, cache_quant_group = head_dim),
@@ -770,38 +268,21 @@ void pplhip_destroy(pplhip_ctx* c) {
         for (auto& ad : R.lora) for (auto& f : ad.f) { if (f.a) hipFree(f.a); if (f.b) hipFree(f.b); }
         if (R.lora_tab) hipFree(R.lora_tab);
         if (R.lora_tiles) hipFree(R.lora_tiles);
-        if (R.lora_tiles_host) hipHostFree(R.lora_tiles_host);
         if (R.lora_t) hipFree(R.lora_t);
-        if (R.lora_ev) hipEventDestroy(R.lora_ev);
         for (int g = 0; g < P2P_MAX_RANKS; ++g)
             if (R.peer_ipc[g] && R.peers.base[g]) hipIpcCloseMemHandle(R.peers.base[g]);
         if (R.xbase) hipFree(R.xbase);
         if (R.p2p_status) hipHostFree(R.p2p_status);
         if (R.kv_cache) hipFree(R.kv_cache);
         if (R.kv_scale) hipFree(R.kv_scale);
-        for (int i = 0; i < 2; ++i) {
-            if (R.stage_host[i]) hipHostFree(R.stage_host[i]);
-            if (R.stage_ev[i]) hipEventDestroy(R.stage_ev[i]);
-        }
+        for (Stage* st : {&R.st_step[0], &R.st_step[1], &R.st_lora_tiles, &R.st_lre, &R.st_gde, &R.st_plp}) st->release();
+        for (Stage& st : R.st_rule) st.release();
         if (R.pages_host) hipHostFree(R.pages_host);
         if (R.pages_dev) hipFree(R.pages_dev);
-        if (R.h_rand) hipHostFree(R.h_rand);
-        if (R.h_srows) hipHostFree(R.h_srows);
-        if (R.h_tlp_in) hipHostFree(R.h_tlp_in);
-        if (R.h_tlp_out) hipHostFree(R.h_tlp_out);
-        if (R.lr_stage) hipHostFree(R.lr_stage);
-        if (R.h_lre) hipHostFree(R.h_lre);
-        for (hipEvent_t e : R.lr_ev) if (e) hipEventDestroy(e);
-        if (R.lre_ev) hipEventDestroy(R.lre_ev);
+        for (void* p : {(void*)R.h_rand, (void*)R.h_srows, (void*)R.h_tlp_in, (void*)R.h_tlp_out, (void*)R.h_plp_out}) if (p) hipHostFree(p);
         if (R.gd_bytes) hipFree(R.gd_bytes);
         if (R.gd_off) hipFree(R.gd_off);
         for (uint32_t* m : R.gd_mask) if (m) hipFree(m);
-        if (R.h_gde) hipHostFree(R.h_gde);
-        if (R.d_gde) hipFree(R.d_gde);
-        if (R.gde_ev) hipEventDestroy(R.gde_ev);
-        if (R.h_plp_in) hipHostFree(R.h_plp_in);
-        if (R.h_plp_out) hipHostFree(R.h_plp_out);
-        if (R.plp_ev) hipEventDestroy(R.plp_ev);
         if (R.stream) hipStreamDestroy(R.stream);
     }
     delete c;
@@ -1029,12 +510,9 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
 
         // step inputs
         R.cap_B = cap_B; R.cap_T = cap_T;
-        const uint64_t step_elems = (uint64_t)cap_T + 4 * (cap_B + 1);
-        for (int i = 0; i < 2; ++i) {
-            HIPCK(cp, r, hipHostMalloc((void**)&R.stage_host[i], step_elems * 8, hipHostMallocDefault));
-            HIPCK(cp, r, hipEventCreateWithFlags(&R.stage_ev[i], hipEventDisableTiming));
-        }
-        ALLOC(R.step_dev, step_elems * 8);
+        const size_t step_bytes = (size_t)StepInputsBlock(nullptr, cap_T, cap_B, true).bytes;
+        for (Stage& st : R.st_step) HIPCK(cp, r, st.allocate(step_bytes));
+        ALLOC(R.step_dev, step_bytes);
 
         // activations
         ALLOC(R.h, (uint64_t)cap_T * hd * 2);
@@ -1095,12 +573,12 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             ALLOC(R.d_temp, cap_B * 4); ALLOC(R.d_topp, cap_B * 4); ALLOC(R.d_rand, cap_B * 4);
             ALLOC(R.d_lp, cap_B * 4); ALLOC(R.d_tokout, cap_B * 4);
             HIPCK(cp, r, hipHostMalloc((void**)&R.h_rand, cap_B * 4, hipHostMallocDefault));
-            ALLOC(R.d_srows, cap_B * SROWS_BYTES);
-            HIPCK(cp, r, hipHostMalloc((void**)&R.h_srows, cap_B * SROWS_BYTES, hipHostMallocDefault));
-            ALLOC(R.d_tlp_in, cap_B * TLP_IN_BYTES);
-            HIPCK(cp, r, hipHostMalloc((void**)&R.h_tlp_in, cap_B * TLP_IN_BYTES, hipHostMallocDefault));
-            ALLOC(R.d_tlp_out, cap_B * TLP_OUT_BYTES);
-            HIPCK(cp, r, hipHostMalloc((void**)&R.h_tlp_out, cap_B * TLP_OUT_BYTES, hipHostMallocDefault));
+            ALLOC(R.d_srows, block_bytes<SampleRowsBlock>(cap_B));
+            HIPCK(cp, r, hipHostMalloc((void**)&R.h_srows, block_bytes<SampleRowsBlock>(cap_B), hipHostMallocDefault));
+            ALLOC(R.d_tlp_in, block_bytes<TopLogprobsIn>(cap_B));
+            HIPCK(cp, r, hipHostMalloc((void**)&R.h_tlp_in, block_bytes<TopLogprobsIn>(cap_B), hipHostMallocDefault));
+            ALLOC(R.d_tlp_out, block_bytes<TopLogprobsOut>(cap_B));
+            HIPCK(cp, r, hipHostMalloc((void**)&R.h_tlp_out, block_bytes<TopLogprobsOut>(cap_B), hipHostMallocDefault));
             if (opts->enable_penalty) {
                 ALLOC(R.count_map, (uint64_t)cap_B * d.vocab_size * 2);
                 ALLOC(R.d_slots, cap_B * 8);
@@ -1117,66 +595,6 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
     }
     *out = c.release();
     return 0;
-}
-
-int pplhip_comm_export(pplhip_ctx* c, int rank, void* handle_out) {
-    if (!c || rank < 0 || rank >= (int)c->ranks.size() || !handle_out) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[rank];
-    memset(handle_out, 0, PPLHIP_IPC_HANDLE_BYTES);
-    if (!R.xbase) return fail(c, rank, PPLHIP_INVALID_VALUE, "no exchange region (tensor parallelism is off)");
-    static_assert(sizeof(hipIpcMemHandle_t) <= PPLHIP_IPC_HANDLE_BYTES, "ipc handle size");
-    HIPCK(c, rank, hipSetDevice(R.device));
-    hipIpcMemHandle_t h;
-    HIPCK(c, rank, hipIpcGetMemHandle(&h, R.xbase));
-    memcpy(handle_out, &h, sizeof(h));
-    return 0;
-}
-
-int pplhip_comm_connect(pplhip_ctx* c, const void* all_handles) {
-    if (!c || !all_handles) return PPLHIP_INVALID_VALUE;
-    if (!c->tp_on || c->tp > P2P_MAX_RANKS) return fail(c, -1, PPLHIP_INVALID_VALUE, "nothing to connect");
-    if (c->comm_want == 1) return 0;  // PPLHIP_COMM=rccl
-    if (c->p2p_connected) return fail(c, -1, PPLHIP_INVALID_VALUE, "already connected");
-    const int n = (int)c->ranks.size(), base = c->o.rank_base;
-    for (int r = 0; r < n; ++r) {
-        Rank& R = c->ranks[r];
-        HIPCK(c, r, hipSetDevice(R.device));
-        for (int g = 0; g < c->tp; ++g) {
-            if (g >= base && g < base + n) {  // a rank of this process
-                Rank& Q = c->ranks[g - base];
-                if (Q.device != R.device) {
-                    hipError_t e = hipDeviceEnablePeerAccess(Q.device, 0);
-                    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
-                        (void)hipGetLastError();
-                        const std::string why = std::string("peer access: ") + hipGetErrorString(e);
-                        return p2p_selftest(c, &why);
-                    }
-                    (void)hipGetLastError();
-                }
-                R.peers.base[g] = Q.xbase;
-                continue;
-            }
-            hipIpcMemHandle_t h;
-            memcpy(&h, (const char*)all_handles + (size_t)g * PPLHIP_IPC_HANDLE_BYTES, sizeof(h));
-            void* ptr = nullptr;
-            hipError_t e = hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                const std::string why = std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(e);
-                return p2p_selftest(c, &why);
-            }
-            R.peers.base[g] = (char*)ptr;
-            R.peer_ipc[g] = true;
-        }
-    }
-    c->p2p_connected = true;
-    return p2p_selftest(c);
-}
-
-int pplhip_comm_mode(pplhip_ctx* c) { return c ? c->comm_mode : PPLHIP_INVALID_VALUE; }
-int pplhip_comm_fused_norm(pplhip_ctx* c) {
-    if (!c || c->ranks.empty()) return PPLHIP_INVALID_VALUE;
-    return fuse_norm_active(plan_settings(c, c->ranks[0]), c->ranks[0].dump_dev != nullptr) ? 1 : 0;
 }
 
 /* ------------------------------------------------------------------------------------------------ weights */
@@ -1514,22 +932,21 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
                 return fail(c, rank, PPLHIP_INVALID_VALUE, "token id outside the vocabulary at row " + std::to_string(t));
     }
     HIPCK(c, rank, hipSetDevice(R.device));
-    const int cur = R.stage_cur;
-    R.stage_cur ^= 1;
-    HIPCK(c, rank, hipEventSynchronize(R.stage_ev[cur]));  // the copy that last used this staging buffer is done
-    int64_t* hbuf = R.stage_host[cur];
-    // packed layout: token_ids[T] | seq_starts[B+1] | kv_starts[B+1] | start_pos[B] | cache_indices[B] (mode 0)
-    int64_t off = 0;
-    memcpy(hbuf + off, st->token_inputs, T * 8); R.d_tok = R.step_dev + off; off += T;
-    memcpy(hbuf + off, st->seq_starts, (B + 1) * 8); R.d_seq = R.step_dev + off; R.h_seq = hbuf + off; off += B + 1;
-    memcpy(hbuf + off, st->kv_starts, (B + 1) * 8); R.d_kvs = R.step_dev + off; off += B + 1;
-    memcpy(hbuf + off, st->start_pos, B * 8); R.d_sp = R.step_dev + off; off += B;
-    if (c->d.cache_mode == 0) {
-        if (B > 0 && !st->cache_indices) return PPLHIP_INVALID_VALUE;
-        memcpy(hbuf + off, st->cache_indices, B * 8); R.d_ci = R.step_dev + off; off += B;
-    }
-    HIPCK(c, rank, hipMemcpyAsync(R.step_dev, hbuf, off * 8, hipMemcpyHostToDevice, R.stream));
-    HIPCK(c, rank, hipEventRecord(R.stage_ev[cur], R.stream));
+    const bool contiguous = c->d.cache_mode == 0;   // (cache_indices != NULL then: the range check above refused a step without them)
+    Stage& stage = R.st_step[R.st_step_cur];
+    R.st_step_cur ^= 1;
+    char* hbuf;
+    HIPCK(c, rank, stage.begin(&hbuf));
+    const StepInputsBlock h(hbuf, T, B, contiguous), dv(R.step_dev, T, B, contiguous);
+    memcpy(h.token_ids, st->token_inputs, T * 8);
+    memcpy(h.seq_starts, st->seq_starts, (B + 1) * 8);
+    memcpy(h.kv_starts, st->kv_starts, (B + 1) * 8);
+    memcpy(h.start_pos, st->start_pos, B * 8);
+    if (contiguous) memcpy(h.cache_indices, st->cache_indices, B * 8);
+    R.d_tok = dv.token_ids; R.d_seq = dv.seq_starts; R.d_kvs = dv.kv_starts; R.d_sp = dv.start_pos;
+    if (contiguous) R.d_ci = dv.cache_indices;
+    R.h_seq = h.seq_starts;
+    HIPCK(c, rank, stage.upload(R.step_dev, (size_t)h.bytes, R.stream));
     if (c->d.cache_mode == 1 && st->req_list_changed) {  // src/engine/llm_engine.cc:67-71
         if (!st->cache_indices || st->max_pages <= 0) return fail(c, rank, PPLHIP_INVALID_VALUE, "page list missing");
         const uint64_t n = (uint64_t)B * st->max_pages;
@@ -1555,404 +972,10 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
     return 0;
 }
 
-
-// ---- multi-LoRA ------------------------------------------------------------------------------------------------------------------------
-// Tile list of a row -> slot map (-1: no adapter): every assigned row in exactly one tile, a tile's rows share one slot, unassigned rows in
-// none.  Slots in ascending order, rows of a slot in ascending order, 16 to a tile, the last tile of a slot padded with -1.
-static void lora_build_tiles(const int32_t* row_slots, int64_t T, std::vector<LoraTile>& out) {
-    int64_t cnt[LORA_MAX_SLOTS] = {0}, first[LORA_MAX_SLOTS];
-    for (int64_t m = 0; m < T; ++m) if (row_slots[m] >= 0) ++cnt[row_slots[m]];
-    int64_t nt = 0;
-    for (int s = 0; s < LORA_MAX_SLOTS; ++s) { first[s] = nt; nt += (cnt[s] + 15) / 16; }
-    LoraTile blank;
-    blank.slot = 0; blank.n = 0;
-    for (int i = 0; i < 16; ++i) blank.row[i] = -1;
-    out.assign((size_t)nt, blank);
-    int64_t pos[LORA_MAX_SLOTS] = {0};
-    for (int64_t m = 0; m < T; ++m) {
-        const int s = row_slots[m];
-        if (s < 0) continue;
-        LoraTile& tl = out[(size_t)(first[s] + pos[s] / 16)];
-        tl.slot = s;
-        tl.row[tl.n++] = (int32_t)m;
-        ++pos[s];
-    }
-}
-
-// what every adapter entry point refuses: tensor parallelism and quantised activations (include/pplhip.h)
-static int lora_guard(pplhip_ctx* c, int rank) {
-    if (!c || rank < 0 || rank >= (int)c->ranks.size()) return PPLHIP_INVALID_VALUE;
-    if (c->tp > 1) return fail(c, rank, PPLHIP_UNSUPPORTED, "LoRA adapters under tensor parallelism (world_size > 1) are not supported");
-    if (c->act_fmt != ACT_FP16) return fail(c, rank, PPLHIP_UNSUPPORTED, "LoRA adapters need fp16 activations (act_quant_bit 0): online_i8i8 / online_f8f8 keep no fp16 input of the linears");
-    return 0;
-}
-
-// the device buffers every adapter step shares, allocated when the first factor arrives
-static int lora_ensure_buffers(pplhip_ctx* c, int rank) {
-    Rank& R = c->ranks[rank];
-    if (R.lora_tab) return 0;
-    const size_t ntab = (size_t)c->d.num_layers * LORA_TARGETS * LORA_MAX_SLOTS;
-    const int64_t cap = R.cap_T / 16 + LORA_MAX_SLOTS + 1;
-    void *tab = nullptr, *tiles = nullptr, *t = nullptr, *host = nullptr;
-    hipEvent_t ev = nullptr;
-    hipError_t e = hipMalloc(&tab, ntab * sizeof(LoraSlot));
-    if (e == hipSuccess) e = hipMemset(tab, 0, ntab * sizeof(LoraSlot));
-    if (e == hipSuccess) e = hipMalloc(&tiles, (size_t)cap * sizeof(LoraTile));
-    if (e == hipSuccess) e = hipMalloc(&t, (size_t)cap * 16 * LORA_MAX_RANK * 2);
-    if (e == hipSuccess) e = hipHostMalloc(&host, (size_t)cap * sizeof(LoraTile), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (tab) hipFree(tab);
-        if (tiles) hipFree(tiles);
-        if (t) hipFree(t);
-        if (host) hipHostFree(host);
-        (void)hipGetLastError();
-        return fail(c, rank, PPLHIP_OUT_OF_MEMORY, std::string("adapter buffers: ") + hipGetErrorString(e));
-    }
-    R.lora_tab = (LoraSlot*)tab; R.lora_tiles = (LoraTile*)tiles; R.lora_t = (uint16_t*)t; R.lora_tiles_host = (LoraTile*)host;
-    R.lora_ev = ev; R.lora_tile_cap = cap;
-    R.lora_tab_host.assign(ntab, LoraSlot{nullptr, nullptr, 0, 0.f});
-    R.lora_touch.assign((size_t)c->d.num_layers * LORA_TARGETS, 0);
-    return 0;
-}
-
-static void lora_free_slot(Rank& R, int slot) {
-    LoraAdapter& ad = R.lora[slot];
-    for (auto& f : ad.f) { if (f.a) hipFree(f.a); if (f.b) hipFree(f.b); }
-    ad.f.clear();
-    if (ad.committed) --R.lora_committed;
-    ad.committed = false;
-    ad.scale = 0.f;
-}
-
-// the slot's column of the kernels' table, on the host mirror and the device (the stream is idle: nothing reads the table meanwhile)
-static int lora_publish_slot(pplhip_ctx* c, int rank, int slot) {
-    Rank& R = c->ranks[rank];
-    const LoraAdapter& ad = R.lora[slot];
-    const size_t n = (size_t)c->d.num_layers * LORA_TARGETS;
-    for (size_t i = 0; i < n; ++i) {
-        LoraSlot e{nullptr, nullptr, 0, 0.f};
-        if (ad.committed && ad.f[i].a) e = LoraSlot{ad.f[i].a, ad.f[i].b, (ad.f[i].ra + 15) / 16 * 16, ad.scale};
-        R.lora_tab_host[i * LORA_MAX_SLOTS + slot] = e;
-    }
-    HIPCK(c, rank, hipMemcpy(R.lora_tab, R.lora_tab_host.data(), R.lora_tab_host.size() * sizeof(LoraSlot), hipMemcpyHostToDevice));
-    return 0;
-}
-
-int pplhip_lora_set_tensor(pplhip_ctx* c, int rank, int slot, const char* name, const void* data, uint64_t bytes, int32_t r) {
-    if (int rc = lora_guard(c, rank)) return rc;
-    if (!name || !data) return PPLHIP_INVALID_VALUE;
-    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
-    if (r < 1 || r > LORA_MAX_RANK) return fail(c, rank, PPLHIP_INVALID_VALUE, std::string(name) + ": rank " + std::to_string(r) + " outside 1 .. " + std::to_string(LORA_MAX_RANK));
-    Rank& R = c->ranks[rank];
-    int l = -1;
-    char rest[128];
-    if (sscanf(name, "layers.%d.%127s", &l, rest) != 2 || l < 0 || l >= c->d.num_layers) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown adapter tensor ") + name);
-    if (!strncmp(rest, "feed_forward.w13.", 17))
-        return fail(c, rank, PPLHIP_UNSUPPORTED, std::string(name) + ": adapters on feed_forward.w13 (gate / up) are not supported, the fused SwiGLU epilogue never materialises them");
-    Layer& L = R.layers[l];
-    struct { const char* n; Linear* lin; } tab[LORA_TARGETS] = {{"attention.wqkv.", &L.wqkv}, {"attention.wo.", &L.wo}, {"feed_forward.w2.", &L.w2}};
-    int target = -1, is_b = -1;
-    for (int i = 0; i < LORA_TARGETS; ++i) {
-        const size_t nl = strlen(tab[i].n);
-        if (strncmp(rest, tab[i].n, nl)) continue;
-        if (!strcmp(rest + nl, "lora_a")) { target = i; is_b = 0; }
-        if (!strcmp(rest + nl, "lora_b")) { target = i; is_b = 1; }
-    }
-    if (target < 0) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown adapter tensor ") + name);
-    const Linear& lin = *tab[target].lin;
-    if (lin.Kp % 32 || lin.N % 16) return fail(c, rank, PPLHIP_UNSUPPORTED, std::string(name) + ": the adapter kernels need K % 32 == 0 and N % 16 == 0");
-    const uint64_t want = is_b ? (uint64_t)lin.N * r * 2 : (uint64_t)r * lin.K * 2;
-    if (bytes != want) return fail(c, rank, PPLHIP_INVALID_VALUE, std::string("tensor ") + name + ": got " + std::to_string(bytes) + " bytes, want " + std::to_string(want));
-    LoraAdapter& ad = R.lora[slot];
-    if (ad.committed) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " is committed: unload it first");
-    HIPCK(c, rank, hipSetDevice(R.device));
-    if (int rc = lora_ensure_buffers(c, rank)) return rc;
-    if (ad.f.empty()) ad.f.resize((size_t)c->d.num_layers * LORA_TARGETS);
-    LoraFactor& f = ad.f[(size_t)l * LORA_TARGETS + target];
-    const int rp = (r + 15) / 16 * 16;
-    // zero-padded on the device: A [rp, Kp] (rows past r and columns past K zero), B [N, rp] (columns past r zero)
-    const size_t pitch = is_b ? (size_t)rp * 2 : (size_t)lin.Kp * 2, rows = is_b ? (size_t)lin.N : (size_t)rp;
-    const size_t src_pitch = is_b ? (size_t)r * 2 : (size_t)lin.K * 2, src_rows = is_b ? (size_t)lin.N : (size_t)r;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, pitch * rows);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, rank, PPLHIP_OUT_OF_MEMORY, std::string("tensor ") + name + ": " + hipGetErrorString(e)); }
-    e = hipMemset(p, 0, pitch * rows);
-    if (e == hipSuccess) e = hipMemcpy2D(p, pitch, data, src_pitch, src_pitch, src_rows, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(p); return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, std::string("tensor ") + name + ": " + hipGetErrorString(e)); }
-    uint16_t*& dst = is_b ? f.b : f.a;
-    if (dst) hipFree(dst);
-    dst = (uint16_t*)p;
-    (is_b ? f.rb : f.ra) = r;
-    return 0;
-}
-
-int pplhip_lora_commit(pplhip_ctx* c, int rank, int slot, float scale) {
-    if (int rc = lora_guard(c, rank)) return rc;
-    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
-    Rank& R = c->ranks[rank];
-    LoraAdapter& ad = R.lora[slot];
-    if (ad.committed) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " is committed already");
-    if (!std::isfinite(scale)) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter scale is not finite");
-    int pairs = 0;
-    for (size_t i = 0; i < ad.f.size(); ++i) {
-        const LoraFactor& f = ad.f[i];
-        if (!f.a && !f.b) continue;
-        const std::string where = "layer " + std::to_string(i / LORA_TARGETS) + " target " + std::to_string(i % LORA_TARGETS);
-        if (!f.a || !f.b) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + ": " + where + " has one factor of two");
-        if (f.ra != f.rb) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + ": " + where + " has factors of ranks " + std::to_string(f.ra) + " and " + std::to_string(f.rb));
-        ++pairs;
-    }
-    if (!pairs) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " holds no factors");
-    HIPCK(c, rank, hipSetDevice(R.device));
-    HIPCK(c, rank, hipStreamSynchronize(R.stream));
-    ad.committed = true;
-    ad.scale = scale;
-    ++R.lora_committed;
-    const int rc = lora_publish_slot(c, rank, slot);
-    if (rc) {   // the device table did not take it: not committed, and the host mirror names none of its factors
-        ad.committed = false;
-        --R.lora_committed;
-        for (size_t i = 0; i < ad.f.size(); ++i) R.lora_tab_host[i * LORA_MAX_SLOTS + slot] = LoraSlot{nullptr, nullptr, 0, 0.f};
-    }
-    return rc;
-}
-
-int pplhip_lora_unload(pplhip_ctx* c, int rank, int slot) {
-    if (int rc = lora_guard(c, rank)) return rc;
-    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
-    Rank& R = c->ranks[rank];
-    if (R.lora[slot].f.empty()) return fail(c, rank, PPLHIP_NOT_FOUND, "adapter slot " + std::to_string(slot) + " is not loaded");
-    HIPCK(c, rank, hipSetDevice(R.device));
-    HIPCK(c, rank, hipStreamSynchronize(R.stream));
-    const bool was = R.lora[slot].committed;
-    lora_free_slot(R, slot);
-    if (R.lora_ntiles > 0) { R.lora_ntiles = 0; R.lora_stale = true; }
-    return was ? lora_publish_slot(c, rank, slot) : 0;
-}
-
-// container: pplhip_rank_load's, with the adapter names and lora.scale (fp32 [1]); the rank of a factor follows from its size
-int pplhip_lora_load(pplhip_ctx* c, int rank, int slot, const char* dir) {
-    if (int rc = lora_guard(c, rank)) return rc;
-    if (!dir) return PPLHIP_INVALID_VALUE;
-    if (slot < 0 || slot >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " out of range");
-    Rank& R = c->ranks[rank];
-    if (!R.lora[slot].f.empty()) return fail(c, rank, PPLHIP_INVALID_VALUE, "adapter slot " + std::to_string(slot) + " is in use: unload it first");
-    const std::string path = std::string(dir) + "/lora.pplhip";
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return fail(c, rank, PPLHIP_NOT_FOUND, "cannot open " + path);
-    char magic[8];
-    uint32_t count = 0;
-    int rc = 0;
-    bool have_scale = false;
-    float scale = 0.f;
-    std::vector<char> buf;
-    uint64_t max_bytes = 4;
-    for (const Layer& L : R.layers)
-        for (const Linear* lin : {&L.wqkv, &L.wo, &L.w2}) max_bytes = std::max<uint64_t>(max_bytes, (uint64_t)LORA_MAX_RANK * std::max(lin->N, lin->K) * 2);
-    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "PPLHIPW1", 8) || fread(&count, 4, 1, f) != 1) {
-        fclose(f);
-        return fail(c, rank, PPLHIP_INVALID_VALUE, "bad header in " + path);
-    }
-    for (uint32_t i = 0; i < count && !rc; ++i) {
-        uint32_t nl = 0; uint64_t nb = 0;
-        char name[256];
-        if (fread(&nl, 4, 1, f) != 1 || nl >= sizeof(name) || fread(name, 1, nl, f) != nl || fread(&nb, 8, 1, f) != 1) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, "truncated container " + path); break; }
-        name[nl] = 0;
-        const long pos = ftell(f);
-        fseek(f, (64 - pos % 64) % 64, SEEK_CUR);
-        // (no factor is larger than LORA_MAX_RANK rows or columns of the widest target linear: a corrupt size is refused, not allocated)
-        if (nb > max_bytes) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, std::string("tensor ") + name + " in " + path + ": " + std::to_string(nb) + " bytes is larger than any adapter tensor"); break; }
-        buf.resize(nb);
-        if (fread(buf.data(), 1, nb, f) != nb) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, "truncated container " + path); break; }
-        if (!strcmp(name, "lora.scale")) {
-            if (nb != 4) { rc = fail(c, rank, PPLHIP_INVALID_VALUE, "lora.scale must be one fp32"); break; }
-            memcpy(&scale, buf.data(), 4);
-            have_scale = true;
-            continue;
-        }
-        // rank from the size: lora_a is [r, K], lora_b [N, r] of the target linear
-        int l = -1;
-        char rest[128];
-        int64_t unit = 0;
-        if (sscanf(name, "layers.%d.%127s", &l, rest) == 2 && l >= 0 && l < c->d.num_layers) {
-            const Layer& L = R.layers[l];
-            const bool b = strstr(rest, ".lora_b") != nullptr;
-            if (!strncmp(rest, "attention.wqkv.", 15)) unit = b ? L.wqkv.N : L.wqkv.K;
-            else if (!strncmp(rest, "attention.wo.", 13)) unit = b ? L.wo.N : L.wo.K;
-            else if (!strncmp(rest, "feed_forward.w2.", 16)) unit = b ? L.w2.N : L.w2.K;
-        }
-        const int64_t r = unit > 0 && nb % (uint64_t)(unit * 2) == 0 ? (int64_t)(nb / (uint64_t)(unit * 2)) : 1;   // (a wrong size or name: set_tensor says which)
-        rc = pplhip_lora_set_tensor(c, rank, slot, name, buf.data(), nb, (int32_t)std::min<int64_t>(r, INT32_MAX));
-    }
-    fclose(f);
-    if (!rc && !have_scale) rc = fail(c, rank, PPLHIP_INVALID_VALUE, path + " has no lora.scale");
-    if (!rc) rc = pplhip_lora_commit(c, rank, slot, scale);
-    if (rc && !R.lora[slot].f.empty()) {   // nothing half loaded stays behind
-        const std::string msg = R.err;
-        lora_free_slot(R, slot);
-        R.err = msg;
-    }
-    return rc;
-}
-
-int pplhip_set_adapters(pplhip_ctx* c, int rank, const int32_t* slots, int64_t batch) {
-    if (int rc = lora_guard(c, rank)) return rc;
-    Rank& R = c->ranks[rank];
-    if (!slots || batch != R.B) return fail(c, rank, PPLHIP_INVALID_VALUE, "pplhip_set_adapters: one slot per request of the staged step");
-    R.lora_ntiles = 0;
-    R.lora_stale = false;
-    bool any = false;
-    for (int64_t b = 0; b < batch; ++b) {
-        const int s = slots[b];
-        if (s == -1) continue;
-        if (s < 0 || s >= LORA_MAX_SLOTS) return fail(c, rank, PPLHIP_INVALID_VALUE, "request " + std::to_string(b) + ": adapter slot " + std::to_string(s) + " out of range");
-        if (!R.lora[s].committed) return fail(c, rank, PPLHIP_INVALID_VALUE, "request " + std::to_string(b) + ": adapter slot " + std::to_string(s) + " is not loaded");
-        any = true;
-    }
-    if (!any) return 0;   // exactly the step without adapters
-    if (!R.h_seq) return fail(c, rank, PPLHIP_INVALID_VALUE, "pplhip_set_adapters before pplhip_set_inputs");
-    std::vector<int32_t> row_slots((size_t)R.T, -1);
-    for (int64_t b = 0; b < batch; ++b)
-        for (int64_t m = R.h_seq[b]; m < R.h_seq[b + 1]; ++m) row_slots[(size_t)m] = slots[b];   // (seq_starts validated by pplhip_set_inputs)
-    std::vector<LoraTile> tiles;
-    lora_build_tiles(row_slots.data(), R.T, tiles);
-    if ((int64_t)tiles.size() > R.lora_tile_cap) return fail(c, rank, PPLHIP_OTHER_ERROR, "adapter tile list exceeds its buffer");
-    std::fill(R.lora_touch.begin(), R.lora_touch.end(), 0);
-    for (int64_t b = 0; b < batch; ++b) {
-        if (slots[b] < 0) continue;
-        const LoraAdapter& ad = R.lora[slots[b]];
-        for (size_t i = 0; i < ad.f.size(); ++i) if (ad.f[i].a) R.lora_touch[i] = 1;
-    }
-    HIPCK(c, rank, hipSetDevice(R.device));
-    HIPCK(c, rank, hipEventSynchronize(R.lora_ev));   // the copy that last read the staging buffer is done
-    memcpy(R.lora_tiles_host, tiles.data(), tiles.size() * sizeof(LoraTile));
-    HIPCK(c, rank, hipMemcpyAsync(R.lora_tiles, R.lora_tiles_host, tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice, R.stream));
-    HIPCK(c, rank, hipEventRecord(R.lora_ev, R.stream));
-    R.lora_ntiles = (int)tiles.size();
-    return 0;
-}
-
-// ---- prompt logprobs -------------------------------------------------------------------------------------------------------------------
-// the first ask of a rank: the device blocks, their pinned images and the staging event
-static int prompt_logprobs_alloc(pplhip_ctx* c, int rank) {
-    Rank& R = c->ranks[rank];
-    const int64_t cap = R.cap_T;
-    int rc;
-    char *d_in = nullptr, *d_out = nullptr;
-    if ((rc = dev_alloc(c, rank, (void**)&d_in, (uint64_t)(cap * PLP_IN_BYTES + 8)))) return rc;
-    if ((rc = dev_alloc(c, rank, (void**)&d_out, (uint64_t)(cap * PLP_OUT_BYTES)))) return rc;
-    if (!R.h_plp_in) HIPCK(c, rank, hipHostMalloc((void**)&R.h_plp_in, (size_t)(cap * PLP_IN_BYTES + 8), hipHostMallocDefault));
-    if (!R.h_plp_out) HIPCK(c, rank, hipHostMalloc((void**)&R.h_plp_out, (size_t)(cap * (PLP_OUT_BYTES + 4)), hipHostMallocDefault));
-    if (!R.plp_ev) HIPCK(c, rank, hipEventCreateWithFlags(&R.plp_ev, hipEventDisableTiming));
-    R.d_plp_out = d_out;
-    R.d_plp_in = d_in;   // last: the blocks count as there only when all of them are
-    return 0;
-}
-
-int pplhip_set_prompt_logprobs(pplhip_ctx* c, int rank, const int32_t* ask, int64_t batch) {
-    if (!c || rank < 0 || rank >= (int)c->ranks.size()) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[rank];
-    if (c->tp > 1 || c->tp_on)
-        return fail(c, rank, PPLHIP_UNSUPPORTED, "prompt logprobs under tensor parallelism (world_size > 1) are not supported: the lm_head is vocabulary-sharded");
-    if (!ask || batch != R.B) return fail(c, rank, PPLHIP_INVALID_VALUE, "pplhip_set_prompt_logprobs: one entry per request of the staged step");
-    R.plp_n = 0;
-    R.plp_top = false;
-    int64_t P = 0;
-    bool top = false;
-    for (int64_t b = 0; b < batch; ++b) {
-        if (ask[b] < -1 || ask[b] > PPLHIP_TOP_LOGPROBS_MAX)
-            return fail(c, rank, PPLHIP_INVALID_VALUE, "request " + std::to_string(b) + ": prompt logprobs ask outside [-1, PPLHIP_TOP_LOGPROBS_MAX]");
-        if (ask[b] < 0) continue;
-        const int64_t len = R.h_seq[b + 1] - R.h_seq[b];   // (batch == R.B > 0: pplhip_set_inputs staged and validated seq_starts)
-        if (len < 2) continue;
-        P += len - 1;
-        top = top || ask[b] > 0;
-    }
-    if (P == 0) return 0;   // exactly the step without the ask
-    HIPCK(c, rank, hipSetDevice(R.device));
-    if (!R.d_plp_in)
-        if (int rc = prompt_logprobs_alloc(c, rank)) return rc;
-    HIPCK(c, rank, hipEventSynchronize(R.plp_ev));   // the copy that last read the staging block is done (a fresh event has passed)
-    int64_t* gather = (int64_t*)R.h_plp_in;
-    int32_t* rows = (int32_t*)(R.h_plp_in + 8 * (P + 1));
-    int32_t* n_top = rows + P;
-    gather[0] = 0;   // never read
-    int64_t j = 0;
-    for (int64_t b = 0; b < batch; ++b) {
-        if (ask[b] < 0) continue;
-        for (int64_t r = R.h_seq[b]; r + 1 < R.h_seq[b + 1]; ++r, ++j) {   // the request's last row predicts its first generated token
-            gather[j + 1] = r + 1;
-            rows[j] = (int32_t)r;
-            n_top[j] = ask[b];
-        }
-    }
-    HIPCK(c, rank, hipMemcpyAsync(R.d_plp_in, R.h_plp_in, (size_t)(8 * (P + 1) + 8 * P), hipMemcpyHostToDevice, R.stream));
-    HIPCK(c, rank, hipEventRecord(R.plp_ev, R.stream));
-    R.plp_n = P;
-    R.plp_top = top;
-    return 0;
-}
-
-int pplhip_prompt_logprobs(pplhip_ctx* c, int rank, pplhip_prompt_logprobs_out* out) {
-    if (!c || rank < 0 || rank >= (int)c->ranks.size() || !out) return PPLHIP_INVALID_VALUE;
-    const Rank& R = c->ranks[rank];
-    memset(out, 0, sizeof(*out));
-    const int64_t P = R.plp_done;
-    if (P == 0) return 0;
-    out->positions = P;
-    out->rows = (const int32_t*)(R.h_plp_out + R.cap_T * PLP_OUT_BYTES);
-    out->logprobs = (const float*)R.h_plp_out;
-    out->ranks = (const int32_t*)(R.h_plp_out + 4 * P);
-    out->top_tokens = (const int32_t*)(R.h_plp_out + 8 * P);
-    out->top_logprobs = (const float*)(R.h_plp_out + 8 * P + 4 * P * PPLHIP_TOP_LOGPROBS_MAX);
-    return 0;
-}
-
-// The asked prompt rows of the staged step, in front of the step's own K11 and through its buffers: R.hn and R.logits are free until the
-// step's own norm and lm_head write them, and a chunk of cap_B rows is the largest M they were sized for.  Per chunk: the final
-// (Skip)RMSNorm of the chunk's rows, the lm_head, one workgroup per position; then one download for all chunks.
-// The rows are selected with the norm's gathering form (row gather[j + 1] - 1).  Checked in rmsnorm_kernel (k_elem.hip): called without
-// residual_out, as K11 calls it, the kernel folds the skip operand (part2 or its split-K slabs) into the row IN REGISTERS only -- R.h and
-// the skip operand are read, never written -- so nothing is folded twice, neither between two chunks nor between these rows and the last
-// rows the step's own K11 norm gathers afterwards (the two sets are disjoint anyway).
-// When the last layer's w2 left its split-K slabs unreduced in the workspace (sl_part2), the step's own norm still has to read them: the
-// lm_head here then runs without the workspace (no split-K) instead of overwriting them.
-static int run_prompt_logprobs(pplhip_ctx* c, int rank, hipStream_t s, const uint16_t* pending, const SplitSlabs& sl_part2) {
-    Rank& R = c->ranks[rank];
-    const pplhip_model_desc& d = c->d;
-    const int hd = d.hidden_dim, V = d.vocab_size;
-    const int64_t P = R.plp_n;
-    const bool slabs = pending && sl_part2.splits > 0;
-    const int64_t* gather = (const int64_t*)R.d_plp_in;
-    const int32_t* rows = (const int32_t*)(R.d_plp_in + 8 * (P + 1));
-    const int32_t* n_top = rows + P;
-    float* lp = (float*)R.d_plp_out;
-    int32_t* rk = (int32_t*)(R.d_plp_out + 4 * P);
-    int32_t* ttok = (int32_t*)(R.d_plp_out + 8 * P);
-    float* tlp = (float*)(R.d_plp_out + 8 * P + 4 * P * PPLHIP_TOP_LOGPROBS_MAX);
-    for (int64_t c0 = 0; c0 < P; c0 += R.cap_B) {
-        const int64_t cn = std::min<int64_t>(R.cap_B, P - c0);
-        HIPCK(c, rank, launch_rmsnorm(s, R.h, pending, R.norm, d.norm_eps, cn, hd, gather + c0, R.hn, nullptr, nullptr, nullptr, pending ? &sl_part2 : nullptr));
-        HIPCK(c, rank, launch_linear(s, R.hn, R.output.w, nullptr, 0, 0, cn, R.output.N, hd, R.logits, V, true, slabs ? nullptr : R.gemm_ws,
-                                     slabs ? 0 : R.gemm_ws_bytes));
-        HIPCK(c, rank, launch_prompt_logprobs(s, R.logits, V, V, rows + c0, (int)cn, R.d_tok, n_top + c0, lp + c0, rk + c0,
-                                              ttok + c0 * PPLHIP_TOP_LOGPROBS_MAX, tlp + c0 * PPLHIP_TOP_LOGPROBS_MAX));
-    }
-    memcpy(R.h_plp_out + R.cap_T * PLP_OUT_BYTES, R.h_plp_in + 8 * (P + 1), (size_t)P * 4);   // the rows, where the next step's staging leaves them alone
-    HIPCK(c, rank, hipMemcpyAsync(R.h_plp_out, R.d_plp_out, (size_t)(R.plp_top ? P * PLP_OUT_BYTES : P * 8), hipMemcpyDeviceToHost, s));
-    R.plp_done = P;
-    return 0;
-}
-
-// A chunk of a step: requests [b0, b0 + bn) = token rows [t0, t0 + tn); the first nd requests of the chunk are
-// decode rows.  A step runs as ONE chunk or as two (plan_step).
-using Chunk = pplhip_chunk;
-using StepPlan = pplhip_step_plan;
 enum { SCHED_ONE_LANE = 0, SCHED_TWO_LANES = 1, SCHED_TWO_CHUNKS = 2 };   // pplhip_comm_info_t.schedule
 
 // what plan_step needs of the context and the rank, as they stand now (comm_mode changes when the ranks connect)
-static pplhip_plan_settings plan_settings(const pplhip_ctx* c, const Rank& R) {
+pplhip_plan_settings plan_settings(const pplhip_ctx* c, const Rank& R) {
     pplhip_plan_settings s;
     memset(&s, 0, sizeof(s));
     s.tp = c->tp; s.tp_on = c->tp_on; s.comm_mode = c->comm_mode;
@@ -1970,7 +993,7 @@ static pplhip_plan_settings plan_settings(const pplhip_ctx* c, const Rank& R) {
 }
 
 // the sequence-parallel residual stream is in force for this rank's steps (pplhip_ctx::fuse_norm_want)
-static bool fuse_norm_active(const pplhip_plan_settings& s, bool dump) {
+bool fuse_norm_active(const pplhip_plan_settings& s, bool dump) {
     const int hd = s.hidden_dim;
     return s.fuse_norm_want && s.tp_on && s.tp > 1 && s.act_fmt == ACT_FP16 && !dump && hd % 8 == 0 && hd <= P2P_NORM_MAX_HIDDEN &&
            (s.comm_mode == 2 || s.emulate_tp);
@@ -1978,7 +1001,7 @@ static bool fuse_norm_active(const pplhip_plan_settings& s, bool dump) {
 
 // The schedule of one step: a pure function of the settings and the step's shape (no HIP call, no environment read), so that what a
 // step runs (run_launches), what pplhip_comm_info reports and what the tests check (pplhip_op_step_plan) are one decision.
-static StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape& sh) {
+StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape& sh) {
     StepPlan p;
     memset(&p, 0, sizeof(p));
     const int64_t B = sh.batch, T = sh.num_tokens;
@@ -2033,7 +1056,7 @@ static StepPlan plan_step(const pplhip_plan_settings& s, const pplhip_step_shape
     return p;
 }
 
-static Lane make_lane(Rank& R, int i, int64_t attn_ws_off) {
+Lane make_lane(Rank& R, int i, int64_t attn_ws_off) {
     Lane ln;
     ln.stream = i ? R.stream2 : R.stream;
     ln.gemm_ws = i ? R.gemm_ws2 : R.gemm_ws;
@@ -2173,7 +1196,7 @@ static int layer_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const StepPlan& p
 // after the lane's work so far; the compute stream picks the result up later (comm_pickup, slot ci).
 // norm_w != NULL (fuse_norm_active): the collective also folds the reduced rows into the residual stream and normalises them with norm_w --
 // afterwards R.xn holds rmsnorm(h + sum) * norm_w for every row of the chunk and R.h the new residual on the rows this rank owns.
-static int chunk_allreduce(pplhip_ctx* c, int rank, Lane& lane, uint16_t* buf, const Chunk& k, int ci, bool overlapped, const uint16_t* norm_w = nullptr) {
+int chunk_allreduce(pplhip_ctx* c, int rank, Lane& lane, uint16_t* buf, const Chunk& k, int ci, bool overlapped, const uint16_t* norm_w) {
     Rank& R = c->ranks[rank];
     Channel& ch = *lane.ch;
     const int hd = c->d.hidden_dim;
@@ -2375,60 +1398,6 @@ static int run_decode_graph(pplhip_ctx* c, int rank, const pplhip_plan_settings&
     return 0;
 }
 
-int pplhip_comm_info(pplhip_ctx* c, int64_t rows, pplhip_comm_info_t* out) {
-    if (!c || !out) return PPLHIP_INVALID_VALUE;
-    memset(out, 0, sizeof(*out));
-    out->mode = c->comm_mode;
-    out->selftest = c->selftest;
-    out->has_rccl = !c->ranks.empty() && c->ranks[0].ch[0].comm != nullptr;
-    out->dual_min_rows = c->dual_mode ? c->dual_min_rows : 0;
-    out->dual_max_rows = c->dual_mode ? c->dual_max_rows : 0;
-    // the schedule plan_step picks for a pure-decode step of `rows` rows (one token per request; no residual dump, no graph capture)
-    static const int64_t held[1] = {0};   // "the rank holds a host copy of seq_starts": a pure-decode plan never reads it
-    const pplhip_step_shape shape{rows, rows, rows, 0, held, 0, 0, 0};
-    out->schedule = plan_step(plan_settings(c, c->ranks[0]), shape).schedule;
-    snprintf(out->notes, sizeof(out->notes), "%s", c->comm_notes.c_str());
-    return 0;
-}
-
-// one all-reduce of fp16 [rows, hidden], `iters` times back to back on the rank's stream, between two events.  Collective: every rank
-// of the group calls it with the same arguments.  path 0: the collectives in use; 1: RCCL (when a communicator exists).
-// The call enqueues AND synchronises: a context that holds several local ranks must call it from one thread per rank at the same time (like
-// pplhip_run under ParallelExecute) -- rank by rank from one thread would wait for peers that were never enqueued.
-int pplhip_comm_allreduce_us(pplhip_ctx* c, int rank, int64_t rows, int32_t iters, int32_t path, float* us) {
-    if (!c || rank < 0 || rank >= (int)c->ranks.size() || !us || iters < 1 || rows < 1) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[rank];
-    *us = -1.f;
-    if (!c->tp_on || rows > R.cap_T) return PPLHIP_INVALID_VALUE;
-    ncclComm_t rccl = R.ch[0].comm;
-    if (path == 1 && !rccl) return 0;                // no RCCL communicator: nothing to compare with
-    if (path == 0 && c->comm_mode != 2 && !rccl) return 0;
-    HIPCK(c, rank, hipSetDevice(R.device));
-    struct Ev {   // destroyed on every return path
-        hipEvent_t e = nullptr;
-        ~Ev() { if (e) (void)hipEventDestroy(e); }
-    } ev0, ev1;
-    HIPCK(c, rank, hipEventCreate(&ev0.e));
-    HIPCK(c, rank, hipEventCreate(&ev1.e));
-    hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    const int hd = c->d.hidden_dim;
-    const Chunk k{0, rows, 0, rows, rows};
-    Lane lane = make_lane(R, 0, 0);
-    const uint16_t* norm_w = fuse_norm_active(plan_settings(c, R), R.dump_dev != nullptr) ? R.norm : nullptr;
-    for (int it = -2; it < iters; ++it) {            // two warm-up rounds
-        if (it == 0) HIPCK(c, rank, hipEventRecord(e0, R.stream));
-        if (path == 1) NCCLCK(c, rank, ncclAllReduce(R.part, R.part, (size_t)rows * hd, ncclFloat16, ncclSum, rccl, R.stream));
-        else if (int rc = chunk_allreduce(c, rank, lane, R.part, k, 0, false, norm_w)) return rc;   // what a step issues
-    }
-    HIPCK(c, rank, hipEventRecord(e1, R.stream));
-    HIPCK(c, rank, hipStreamSynchronize(R.stream));
-    float ms = 0.f;
-    HIPCK(c, rank, hipEventElapsedTime(&ms, e0, e1));
-    *us = ms * 1e3f / (float)iters;
-    if (R.p2p_status && *R.p2p_status) return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, "a direct collective timed out during pplhip_comm_allreduce_us");
-    return 0;
-}
-
 int pplhip_run(pplhip_ctx* c, int rank, int cache_prefill) {
     (void)cache_prefill;  // K6 and K7 are one kernel here: attention always reads K/V back from the slab
     if (!c || rank < 0 || rank >= (int)c->ranks.size()) return PPLHIP_INVALID_VALUE;
@@ -2498,432 +1467,6 @@ int pplhip_copy_logits(pplhip_ctx* c, int rank, float* dst, int64_t batch) {
     return 0;
 }
 
-/* ------------------------------------------------------------------------------------------------ sampler */
-
-int pplhip_sample(pplhip_ctx* c, const float* logits_device, const pplhip_sample_args* a, int32_t* output_host,
-                  float* logprob_host) {
-    if (!c || !a || !logits_device || !output_host || !logprob_host) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int B = a->batch;
-    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
-    HIPCK(c, 0, hipSetDevice(R.device));
-    hipStream_t s = R.stream;
-    // src/backends/cuda/post_processor.cc:126,154-177: temperatures are skipped when the penalty kernel already
-    // applied them; device copies are refreshed only when the batch changed and (quirk Q3 of SURVEY.md, kept)
-    // passed to the kernel only on those steps.
-    const float* temps_host = a->enable_penalty ? nullptr : a->temperatures;
-    const float* temp_opt = nullptr;
-    const float* topp_opt = nullptr;
-    if (a->req_list_changed) {
-        if (temps_host) { HIPCK(c, 0, hipMemcpyAsync(R.d_temp, temps_host, B * 4, hipMemcpyHostToDevice, s)); temp_opt = R.d_temp; }
-        if (a->top_p) { HIPCK(c, 0, hipMemcpyAsync(R.d_topp, a->top_p, B * 4, hipMemcpyHostToDevice, s)); topp_opt = R.d_topp; }
-    }
-    static const bool trace = getenv("PPLHIP_SAMPLE_TRACE") != nullptr;  // diagnosis: what every sampling call was handed
-    if (trace) {
-        fprintf(stderr, "[sample] B %d top_k0 %d top_p0 %g changed %d penalty %d temps", B, a->default_top_k, a->default_top_p, a->req_list_changed, a->enable_penalty);
-        for (int i = 0; i < B && a->temperatures; ++i) fprintf(stderr, " %g", a->temperatures[i]);
-        fprintf(stderr, " top_p");
-        for (int i = 0; i < B && a->top_p; ++i) fprintf(stderr, " %g", a->top_p[i]);
-        fprintf(stderr, " top_k");
-        for (int i = 0; i < B && a->top_k; ++i) fprintf(stderr, " %d", a->top_k[i]);
-        fprintf(stderr, "\n");
-    }
-    // post_processor.cc:179-183: unseeded rand() sequence (one default value, then one per row)
-    const float default_rand = (float)rand() / (float)RAND_MAX;
-    (void)default_rand;
-    for (int i = 0; i < B; ++i) R.h_rand[i] = (float)rand() / (float)RAND_MAX;
-    if (a->default_top_k == 1) {
-        HIPCK(c, 0, launch_sample_greedy(s, logits_device, temp_opt, B, a->vocab_size, a->batch_stride, R.d_tokout, R.d_lp));
-    } else {
-        // top_k <= 0: top-p over the whole vocabulary; top_k > 1024 is clamped (k_sample.hip).  default_top_k is the FIRST
-        // row's client-supplied value: it must never turn into a batch-wide Execute failure.
-        HIPCK(c, 0, hipMemcpyAsync(R.d_rand, R.h_rand, B * 4, hipMemcpyHostToDevice, s));
-        HIPCK(c, 0, launch_sample_topk_topp(s, logits_device, temp_opt, topp_opt, R.d_rand, B, a->vocab_size, a->batch_stride,
-                                            a->default_top_k, a->default_top_p, nullptr, R.d_tokout, R.d_lp));
-    }
-    HIPCK(c, 0, hipMemcpyAsync(output_host, R.d_tokout, B * 4, hipMemcpyDeviceToHost, s));
-    HIPCK(c, 0, hipMemcpyAsync(logprob_host, R.d_lp, B * 4, hipMemcpyDeviceToHost, s));
-    HIPCK(c, 0, hipStreamSynchronize(s));  // the step's only host<->device synchronisation (post_processor.cc:212)
-    if (trace) {
-        std::vector<float> row(a->vocab_size);
-        for (int i = 0; i < B; ++i) {
-            (void)hipMemcpy(row.data(), logits_device + (size_t)i * a->batch_stride, (size_t)a->vocab_size * 4, hipMemcpyDeviceToHost);
-            double sum = 0;
-            int am = 0;
-            for (int v = 0; v < a->vocab_size; ++v) { sum += row[v]; if (row[v] > row[am]) am = v; }
-            fprintf(stderr, "[sample]   row %d -> token %d logprob %.6f | logits sum %.6f argmax %d (%.6f) rand %.8f\n", i, output_host[i], logprob_host[i], sum, am,
-                    row[am], R.h_rand[i]);
-        }
-    }
-    return p2p_check(c, 0);
-}
-
-// greedy rows (top_k == 1) first, then the others, each kind in batch order; returns the number of greedy rows
-static int sample_row_list(const int32_t* top_k, int B, int32_t* rows) {
-    int ng = 0;
-    for (int i = 0; i < B; ++i)
-        if (top_k[i] == 1) rows[ng++] = i;
-    int n = ng;
-    for (int i = 0; i < B; ++i)
-        if (top_k[i] != 1) rows[n++] = i;
-    return ng;
-}
-
-int pplhip_sample_rows(pplhip_ctx* c, const float* logits_device, const pplhip_sample_rows_args* a, int32_t* output_host,
-                       float* logprob_host) {
-    if (!c || !a || !logits_device || !output_host || !logprob_host) return PPLHIP_INVALID_VALUE;
-    if (!a->top_k || !a->top_p || !a->seeds || !a->draws) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int B = a->batch;
-    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
-    if (a->vocab_size <= 0 || a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
-    if (B == 0) return 0;
-    // every array, every call, one copy: the block keeps its capacity layout, so the copy is cap_B rows long only when B is
-    const int64_t cap = R.cap_B;
-    char* h = R.h_srows;
-    uint64_t* h_seed = (uint64_t*)h;
-    uint64_t* h_draw = (uint64_t*)(h + 8 * cap);
-    float* h_temp = (float*)(h + 16 * cap);
-    float* h_topp = (float*)(h + 20 * cap);
-    int32_t* h_topk = (int32_t*)(h + 24 * cap);
-    int32_t* h_rows = (int32_t*)(h + 28 * cap);
-    memcpy(h_seed, a->seeds, (size_t)B * 8);
-    memcpy(h_draw, a->draws, (size_t)B * 8);
-    if (a->temperatures) memcpy(h_temp, a->temperatures, (size_t)B * 4);
-    memcpy(h_topp, a->top_p, (size_t)B * 4);
-    memcpy(h_topk, a->top_k, (size_t)B * 4);
-    const int ng = sample_row_list(a->top_k, B, h_rows);
-    HIPCK(c, 0, hipSetDevice(R.device));
-    hipStream_t s = R.stream;
-    HIPCK(c, 0, hipMemcpyAsync(R.d_srows, h, (size_t)(28 * cap + 4 * (int64_t)B), hipMemcpyHostToDevice, s));
-    const char* d = R.d_srows;
-    HIPCK(c, 0, launch_sample_rows(s, logits_device, a->temperatures ? (const float*)(d + 16 * cap) : nullptr, (const int32_t*)(d + 24 * cap),
-                                   (const float*)(d + 20 * cap), (const uint64_t*)d, (const uint64_t*)(d + 8 * cap), nullptr,
-                                   (const int32_t*)(d + 28 * cap), ng, B - ng, a->vocab_size, a->batch_stride, R.d_tokout, R.d_lp));
-    HIPCK(c, 0, hipMemcpyAsync(output_host, R.d_tokout, B * 4, hipMemcpyDeviceToHost, s));
-    HIPCK(c, 0, hipMemcpyAsync(logprob_host, R.d_lp, B * 4, hipMemcpyDeviceToHost, s));
-    HIPCK(c, 0, hipStreamSynchronize(s));  // the one synchronisation, as in pplhip_sample
-    return p2p_check(c, 0);
-}
-
-// the rows with num_logprobs[b] in 1 .. 20, ascending; returns their number, or -1 for an entry outside [0, 20]
-static int top_logprobs_row_list(const int32_t* num_logprobs, int B, int32_t* rows) {
-    int n = 0;
-    for (int i = 0; i < B; ++i) {
-        if (num_logprobs[i] < 0 || num_logprobs[i] > PPLHIP_TOP_LOGPROBS_MAX) return -1;
-        if (num_logprobs[i] > 0) rows[n++] = i;
-    }
-    return n;
-}
-
-int pplhip_top_logprobs(pplhip_ctx* c, const float* logits_device, const pplhip_top_logprobs_args* a, const int32_t** tokens_out,
-                        const float** logprobs_out, int32_t* rows_out) {
-    if (!c || !a || !logits_device || !tokens_out || !logprobs_out || !rows_out || !a->num_logprobs) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int B = a->batch;
-    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
-    if (a->vocab_size <= 0 || a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
-    const int64_t cap = R.cap_B;
-    char* h = R.h_tlp_in;
-    // (the list is built in place: a refused call has launched nothing, and nothing of an earlier call still reads this block once the
-    // stream was synchronised, which the contract asks for between two calls)
-    const int asked = top_logprobs_row_list(a->num_logprobs, B, (int32_t*)(h + 8 * cap));
-    if (asked < 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "num_logprobs outside [0, PPLHIP_TOP_LOGPROBS_MAX]");
-    *tokens_out = (const int32_t*)R.h_tlp_out;
-    *logprobs_out = (const float*)(R.h_tlp_out + (int64_t)asked * 4 * PPLHIP_TOP_LOGPROBS_MAX);
-    *rows_out = asked;
-    if (asked == 0) return 0;   // nobody asked: no HIP call
-    if (a->temperatures) memcpy(h, a->temperatures, (size_t)B * 4);
-    memcpy(h + 4 * cap, a->num_logprobs, (size_t)B * 4);
-    HIPCK(c, 0, hipSetDevice(R.device));
-    hipStream_t s = R.stream;
-    HIPCK(c, 0, hipMemcpyAsync(R.d_tlp_in, h, (size_t)(8 * cap + 4 * (int64_t)asked), hipMemcpyHostToDevice, s));
-    const char* d = R.d_tlp_in;
-    int32_t* d_tok = (int32_t*)R.d_tlp_out;
-    float* d_lp = (float*)(R.d_tlp_out + (int64_t)asked * 4 * PPLHIP_TOP_LOGPROBS_MAX);
-    HIPCK(c, 0, launch_top_logprobs(s, logits_device, a->temperatures ? (const float*)d : nullptr, (const int32_t*)(d + 4 * cap),
-                                    (const int32_t*)(d + 8 * cap), asked, a->vocab_size, a->batch_stride, d_tok, d_lp));
-    HIPCK(c, 0, hipMemcpyAsync(R.h_tlp_out, R.d_tlp_out, (size_t)asked * TLP_OUT_BYTES, hipMemcpyDeviceToHost, s));
-    return 0;   // asynchronous: the step's sampler call (or pplhip_sync) is the synchronisation
-}
-
-// the first rule of a context: the table, the staging ring and the edit's staging block
-static int logit_rules_alloc(pplhip_ctx* c) {
-    Rank& R = c->ranks[0];
-    const int64_t words = ((int64_t)c->d.vocab_size + 31) / 32;
-    const int64_t rec = LR_MASK + (words + 3) / 4 * 16;
-    int rc;
-    char *table = nullptr, *d_lre = nullptr;
-    if ((rc = dev_alloc(c, 0, (void**)&table, (uint64_t)R.cap_B * rec))) return rc;
-    if ((rc = dev_alloc(c, 0, (void**)&d_lre, (uint64_t)R.cap_B * LRE_BYTES))) return rc;
-    if (!R.lr_stage) HIPCK(c, 0, hipHostMalloc((void**)&R.lr_stage, (size_t)(LR_RING * rec), hipHostMallocDefault));
-    if (!R.h_lre) HIPCK(c, 0, hipHostMalloc((void**)&R.h_lre, (size_t)(R.cap_B * LRE_BYTES), hipHostMallocDefault));
-    for (int i = 0; i < LR_RING; ++i)
-        if (!R.lr_ev[i]) HIPCK(c, 0, hipEventCreateWithFlags(&R.lr_ev[i], hipEventDisableTiming));
-    if (!R.lre_ev) HIPCK(c, 0, hipEventCreateWithFlags(&R.lre_ev, hipEventDisableTiming));
-    R.lr_has.assign((size_t)R.cap_B, 0);
-    R.d_lre = d_lre;
-    R.lr_rec = rec;
-    R.lr_table = table;   // last: the table counts as there only when everything is
-    return 0;
-}
-
-int pplhip_logit_rule_set(pplhip_ctx* c, int32_t slot, const pplhip_logit_rule* r) {
-    if (!c || !r) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int V = c->d.vocab_size;
-    const int64_t words = ((int64_t)V + 31) / 32;
-    if (slot < 0 || slot >= R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: slot outside [0, max_running_batch)");
-    if (r->n_bias < 0 || r->n_bias > PPLHIP_LOGIT_BIAS_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: n_bias outside [0, PPLHIP_LOGIT_BIAS_MAX]");
-    if (r->n_stop < 0 || r->n_stop > PPLHIP_LOGIT_STOP_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: n_stop outside [0, PPLHIP_LOGIT_STOP_MAX]");
-    if ((r->n_bias > 0 && (!r->bias_tokens || !r->bias_values)) || (r->n_stop > 0 && !r->stop_tokens))
-        return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: a count without its array");
-    // dead[v]: the token cannot be produced; seen[v]: it has a bias entry
-    std::vector<uint8_t> dead((size_t)V, 0), seen((size_t)V, 0);
-    for (int i = 0; i < r->n_bias; ++i) {
-        const int32_t t = r->bias_tokens[i];
-        const float v = r->bias_values[i];
-        if (t < 0 || t >= V) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: bias_tokens[" + std::to_string(i) + "] outside [0, vocab_size)");
-        if (v != v || v == INFINITY) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: bias_values[" + std::to_string(i) + "] is NaN or +inf");
-        if (seen[t]) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: bias_tokens[" + std::to_string(i) + "] has an entry already");
-        seen[t] = 1;
-        if (v == -INFINITY) dead[t] = 1;
-    }
-    for (int i = 0; i < r->n_stop; ++i) {
-        const int32_t t = r->stop_tokens[i];
-        if (t < 0 || t >= V) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: stop_tokens[" + std::to_string(i) + "] outside [0, vocab_size)");
-        dead[t] = 1;
-    }
-    bool alive = false;
-    for (int v = 0; v < V && !alive; ++v)
-        alive = !dead[v] && (!r->allowed_bits || ((r->allowed_bits[v >> 5] >> (v & 31)) & 1u));
-    if (!alive) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit rule: allowed_bits minus the banned and stop tokens leaves no token");
-    HIPCK(c, 0, hipSetDevice(R.device));
-    if (!R.lr_table)
-        if (int rc = logit_rules_alloc(c)) return rc;
-    const int k = R.lr_next;
-    HIPCK(c, 0, hipEventSynchronize(R.lr_ev[k]));   // the copy that last used this staging record (a fresh event has passed)
-    char* h = R.lr_stage + (int64_t)k * R.lr_rec;
-    int32_t* head = (int32_t*)h;
-    head[0] = r->n_bias; head[1] = r->n_stop; head[2] = r->allowed_bits ? 1 : 0; head[3] = 0;
-    if (r->n_bias) {
-        memcpy(h + LR_BIAS_TOK, r->bias_tokens, (size_t)r->n_bias * 4);
-        memcpy(h + LR_BIAS_VAL, r->bias_values, (size_t)r->n_bias * 4);
-    }
-    if (r->n_stop) memcpy(h + LR_STOPS, r->stop_tokens, (size_t)r->n_stop * 4);
-    if (r->allowed_bits) memcpy(h + LR_MASK, r->allowed_bits, (size_t)words * 4);
-    // (the parts behind the counts, and the mask of a rule without one, go up as the ring holds them: the kernel reads none of it)
-    HIPCK(c, 0, hipMemcpyAsync(R.lr_table + (int64_t)slot * R.lr_rec, h, (size_t)R.lr_rec, hipMemcpyHostToDevice, R.stream));
-    HIPCK(c, 0, hipEventRecord(R.lr_ev[k], R.stream));
-    R.lr_next = (k + 1) % LR_RING;
-    R.lr_has[slot] = 1;
-    return 0;
-}
-
-int pplhip_logit_edit(pplhip_ctx* c, float* logits_device, const pplhip_logit_edit_args* a) {
-    if (!c || !a || !logits_device || !a->batch_slots || !a->flags) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int B = a->batch;
-    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
-    if (a->vocab_size != c->d.vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit edit: vocab_size is not the model's");
-    if (a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
-    int asked = 0;
-    for (int i = 0; i < B; ++i) {
-        if (a->flags[i] > 3u) return fail(c, 0, PPLHIP_INVALID_VALUE, "logit edit: flags above 3");
-        if (!a->flags[i]) continue;
-        const int64_t slot = a->batch_slots[i];
-        if (slot < 0 || slot >= R.cap_B || !R.lr_table || !R.lr_has[slot])
-            return fail(c, 0, PPLHIP_INVALID_VALUE, "logit edit: row " + std::to_string(i) + " asks with a slot that holds no rule");
-        ++asked;
-    }
-    if (asked == 0) return 0;   // nobody asks: no HIP call
-    HIPCK(c, 0, hipSetDevice(R.device));
-    HIPCK(c, 0, hipEventSynchronize(R.lre_ev));   // the previous call's upload has left the staging block
-    const int64_t cap = R.cap_B;
-    int32_t* h_slots = (int32_t*)R.h_lre;
-    uint32_t* h_flags = (uint32_t*)(R.h_lre + 4 * cap);
-    int32_t* h_rows = (int32_t*)(R.h_lre + 8 * cap);
-    int n = 0;
-    for (int i = 0; i < B; ++i) {
-        h_slots[i] = a->flags[i] ? (int32_t)a->batch_slots[i] : 0;
-        h_flags[i] = a->flags[i];
-        if (a->flags[i]) h_rows[n++] = i;
-    }
-    hipStream_t s = R.stream;
-    HIPCK(c, 0, hipMemcpyAsync(R.d_lre, R.h_lre, (size_t)(8 * cap + 4 * (int64_t)asked), hipMemcpyHostToDevice, s));
-    HIPCK(c, 0, hipEventRecord(R.lre_ev, s));
-    const int64_t rw = R.lr_rec / 4;
-    const LogitRuleTable tb{(const int32_t*)R.lr_table, (const int32_t*)(R.lr_table + LR_BIAS_TOK), (const float*)(R.lr_table + LR_BIAS_VAL),
-                            (const int32_t*)(R.lr_table + LR_STOPS), (const uint32_t*)(R.lr_table + LR_MASK), rw, rw, rw, rw};
-    HIPCK(c, 0, launch_logit_edit(s, logits_device, a->batch_stride, a->vocab_size, (const int32_t*)(R.d_lre + 8 * cap), asked,
-                                  (const int32_t*)R.d_lre, (const uint32_t*)(R.d_lre + 4 * cap), tb));
-    return 0;   // asynchronous: in stream order in front of the step's penalty, top-N logprobs and sampler
-}
-
-// ---- guided decoding ----------------------------------------------------------------------------------------------------------------
-
-int pplhip_guide_set_vocab(pplhip_ctx* c, const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) {
-    if (!c || !offsets) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    if (R.gd_n_tok >= 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: set already");
-    if (n_tok < 1 || n_tok > c->d.vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: n_tok outside [1, vocab_size]");
-    if (offsets[0] != 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: offsets[0] is not 0");
-    for (int i = 0; i < n_tok; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide vocabulary: offsets decrease at token " + std::to_string(i));
-    const int64_t total = offsets[n_tok];
-    if (total > 0 && !bytes) return PPLHIP_INVALID_VALUE;
-    HIPCK(c, 0, hipSetDevice(R.device));
-    uint8_t* d_bytes = nullptr;
-    int64_t* d_off = nullptr;
-    // (freed by pplhip_destroy even when a later step of this call fails: the fields are set as they come)
-    HIPCK(c, 0, hipMalloc((void**)&d_bytes, (size_t)std::max<int64_t>(total, 1)));
-    R.gd_bytes = d_bytes;
-    HIPCK(c, 0, hipMalloc((void**)&d_off, (size_t)(n_tok + 1) * 8));
-    R.gd_off = d_off;
-    if (!R.h_gde) HIPCK(c, 0, hipHostMalloc((void**)&R.h_gde, (size_t)R.cap_B * 12, hipHostMallocDefault));
-    if (!R.d_gde) HIPCK(c, 0, hipMalloc((void**)&R.d_gde, (size_t)R.cap_B * 12));
-    if (!R.gde_ev) HIPCK(c, 0, hipEventCreateWithFlags(&R.gde_ev, hipEventDisableTiming));
-    if (total > 0) HIPCK(c, 0, hipMemcpyAsync(d_bytes, bytes, (size_t)total, hipMemcpyHostToDevice, R.stream));
-    HIPCK(c, 0, hipMemcpyAsync(d_off, offsets, (size_t)(n_tok + 1) * 8, hipMemcpyHostToDevice, R.stream));
-    HIPCK(c, 0, hipStreamSynchronize(R.stream));   // the caller's arrays are pageable and free after this call
-    R.gd_n_tok = n_tok;
-    return 0;
-}
-
-int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
-    if (!c || !g) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int V = c->d.vocab_size;
-    if (R.gd_n_tok < 0) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: no vocabulary set (pplhip_guide_set_vocab)");
-    if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot outside [0, PPLHIP_GUIDE_MAX_SLOTS)");
-    if (R.gd_mask[slot]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot " + std::to_string(slot) + " is loaded");
-    const int S = g->n_states;
-    if (S < 1 || S > PPLHIP_GUIDE_MAX_STATES) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: n_states outside [1, PPLHIP_GUIDE_MAX_STATES]");
-    if (g->n_end < 0 || g->n_end > PPLHIP_LOGIT_STOP_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: n_end outside [0, PPLHIP_LOGIT_STOP_MAX]");
-    if (!g->trans || !g->accept || (g->n_end > 0 && !g->end_tokens)) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: a NULL array");
-    for (int i = 0; i < g->n_end; ++i)
-        if (g->end_tokens[i] < 0 || g->end_tokens[i] >= V)
-            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: end_tokens[" + std::to_string(i) + "] outside [0, vocab_size)");
-    for (int s = 0; s < S; ++s) {
-        bool live = g->accept[s] != 0;
-        for (int b = 0; b < 256; ++b) {
-            const int to = g->trans[s * 256 + b];
-            if (to != GUIDE_DEAD && to >= S)
-                return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(s) + " byte " + std::to_string(b) + " leads to state " +
-                                                            std::to_string(to) + " >= n_states");
-            live = live || to != GUIDE_DEAD;
-        }
-        if (!live) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(s) + " has neither a live byte nor acceptance");
-    }
-    HIPCK(c, 0, hipSetDevice(R.device));
-    const int64_t words = ((int64_t)V + 31) / 32;
-    // one scratch block: trans | accept (padded to 256) | any u32 [256] | end tokens i32 [64]
-    const size_t o_acc = (size_t)S * 256, o_any = o_acc + 256, o_end = o_any + 1024, scratch_bytes = o_end + 256;
-    char* scratch = nullptr;
-    uint32_t* mask = nullptr;
-    std::vector<uint32_t> any((size_t)S, 0);
-    hipError_t e = hipMalloc((void**)&scratch, scratch_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&mask, (size_t)S * words * 4);
-    hipStream_t s = R.stream;
-    if (e == hipSuccess) e = hipMemsetAsync(scratch + o_any, 0, 1024, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(scratch, g->trans, (size_t)S * 256, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(scratch + o_acc, g->accept, (size_t)S, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && g->n_end > 0) e = hipMemcpyAsync(scratch + o_end, g->end_tokens, (size_t)g->n_end * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_guide_build(s, (const uint8_t*)scratch, (const uint8_t*)(scratch + o_acc), S, R.gd_bytes, R.gd_off, R.gd_n_tok,
-                               (const int32_t*)(scratch + o_end), g->n_end, V, mask, words, (uint32_t*)(scratch + o_any));
-    if (e == hipSuccess) e = hipMemcpyAsync(any.data(), scratch + o_any, (size_t)S * 4, hipMemcpyDeviceToHost, s);
-    const hipError_t e_sync = hipStreamSynchronize(s);   // synchronous by design: once per distinct pattern
-    if (e == hipSuccess) e = e_sync;
-    if (scratch) hipFree(scratch);
-    if (e != hipSuccess) {
-        if (mask) hipFree(mask);
-        return fail(c, 0, e == hipErrorOutOfMemory ? PPLHIP_OUT_OF_MEMORY : PPLHIP_DEVICE_RUNTIME_ERROR, std::string("guide load: ") + hipGetErrorString(e));
-    }
-    for (int st = 0; st < S; ++st)
-        if (!any[st]) {
-            hipFree(mask);
-            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(st) + " allows no token of the vocabulary");
-        }
-    R.gd_mask[slot] = mask;
-    R.gd_states[slot] = S;
-    return 0;
-}
-
-int pplhip_guide_unload(pplhip_ctx* c, int32_t slot) {
-    if (!c) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS || !R.gd_mask[slot]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot is not loaded");
-    HIPCK(c, 0, hipSetDevice(R.device));
-    HIPCK(c, 0, hipStreamSynchronize(R.stream));   // a queued pplhip_guide_edit may still read the mask
-    HIPCK(c, 0, hipFree(R.gd_mask[slot]));
-    R.gd_mask[slot] = nullptr;
-    R.gd_states[slot] = 0;
-    return 0;
-}
-
-int pplhip_guide_edit(pplhip_ctx* c, float* logits_device, const pplhip_guide_edit_args* a) {
-    if (!c || !a || !logits_device || !a->guide_slots || !a->states) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    const int B = a->batch;
-    if (B < 0 || B > R.cap_B) return fail(c, 0, PPLHIP_INVALID_VALUE, "batch exceeds max_running_batch");
-    if (a->vocab_size != c->d.vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide edit: vocab_size is not the model's");
-    if (a->batch_stride < a->vocab_size) return fail(c, 0, PPLHIP_INVALID_VALUE, "row stride below vocab_size");
-    int asked = 0;
-    for (int i = 0; i < B; ++i) {
-        const int32_t slot = a->guide_slots[i];
-        if (slot == -1) continue;
-        if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS || !R.gd_mask[slot])
-            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide edit: row " + std::to_string(i) + " asks with a slot that holds no guide");
-        if (a->states[i] < 0 || a->states[i] >= R.gd_states[slot])
-            return fail(c, 0, PPLHIP_INVALID_VALUE, "guide edit: row " + std::to_string(i) + " is in a state outside its guide");
-        ++asked;
-    }
-    if (asked == 0) return 0;   // nobody asks: no HIP call
-    HIPCK(c, 0, hipSetDevice(R.device));
-    HIPCK(c, 0, hipEventSynchronize(R.gde_ev));   // the previous call's upload has left the staging block
-    const int64_t cap = R.cap_B;
-    int32_t* h_slots = (int32_t*)R.h_gde;
-    int32_t* h_states = (int32_t*)(R.h_gde + 4 * cap);
-    int32_t* h_rows = (int32_t*)(R.h_gde + 8 * cap);
-    int n = 0;
-    for (int i = 0; i < B; ++i) {
-        h_slots[i] = a->guide_slots[i];
-        h_states[i] = a->guide_slots[i] >= 0 ? a->states[i] : 0;
-        if (a->guide_slots[i] >= 0) h_rows[n++] = i;
-    }
-    hipStream_t s = R.stream;
-    HIPCK(c, 0, hipMemcpyAsync(R.d_gde, R.h_gde, (size_t)(8 * cap + 4 * (int64_t)asked), hipMemcpyHostToDevice, s));
-    HIPCK(c, 0, hipEventRecord(R.gde_ev, s));
-    GuideTable tb;
-    for (int i = 0; i < GUIDE_MAX_SLOTS; ++i) tb.mask[i] = R.gd_mask[i];
-    tb.mask_stride = ((int64_t)a->vocab_size + 31) / 32;
-    HIPCK(c, 0, launch_guide_mask(s, logits_device, a->batch_stride, a->vocab_size, (const int32_t*)(R.d_gde + 8 * cap), asked,
-                                  (const int32_t*)R.d_gde, (const int32_t*)(R.d_gde + 4 * cap), tb));
-    return 0;   // asynchronous: in stream order in front of the step's logit edit, penalty, top-N logprobs and sampler
-}
-
-int pplhip_penalty(pplhip_ctx* c, float* logits_device, const pplhip_penalty_args* a) {
-    if (!c || !a || !logits_device) return PPLHIP_INVALID_VALUE;
-    Rank& R = c->ranks[0];
-    if (!R.count_map) return fail(c, 0, PPLHIP_INVALID_VALUE, "context was created without enable_penalty");
-    const int B = a->batch;
-    if (B < 0 || B > R.cap_B || B != R.B) return fail(c, 0, PPLHIP_INVALID_VALUE, "penalty batch does not match the step");
-    HIPCK(c, 0, hipSetDevice(R.device));
-    hipStream_t s = R.stream;
-    if (a->req_list_changed) {  // post_processor.cc:231-263
-        HIPCK(c, 0, hipMemcpyAsync(R.d_ptemp, a->temperatures, B * 4, hipMemcpyHostToDevice, s));
-        HIPCK(c, 0, hipMemcpyAsync(R.d_slots, a->batch_slots, B * 8, hipMemcpyHostToDevice, s));
-        HIPCK(c, 0, hipMemcpyAsync(R.d_rep, a->repetition_penalties, B * 4, hipMemcpyHostToDevice, s));
-        if (a->presence_penalties) HIPCK(c, 0, hipMemcpyAsync(R.d_pres, a->presence_penalties, B * 4, hipMemcpyHostToDevice, s));
-        if (a->frequency_penalties) HIPCK(c, 0, hipMemcpyAsync(R.d_freq, a->frequency_penalties, B * 4, hipMemcpyHostToDevice, s));
-    }
-    HIPCK(c, 0, launch_penalty(s, logits_device, R.d_ptemp, R.d_rep, a->presence_penalties ? R.d_pres : nullptr,
-                               a->frequency_penalties ? R.d_freq : nullptr, R.d_slots, R.d_tok, R.d_seq, R.d_sp, B,
-                               a->vocab_size, c->d.vocab_size, (int)R.decoding_batches, R.count_map));
-    return 0;
-}
-
 /* ------------------------------------------------------------------------------------------------ measurement */
 
 int pplhip_profile_reset(pplhip_ctx* c, int rank) {
@@ -2968,424 +1511,3 @@ int pplhip_mem_info(pplhip_ctx* c, int rank, uint64_t* free_bytes, uint64_t* tot
     if (total_bytes) *total_bytes = t;
     return 0;
 }
-
-/* ------------------------------------------------------------------------------------------------ operators */
-
-static int op_rc(hipError_t e) { return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? PPLHIP_INVALID_VALUE : PPLHIP_DEVICE_RUNTIME_ERROR); }
-
-int pplhip_op_embedding(void* stream, const int64_t* token_ids, const void* table, int64_t T, int32_t hidden, void* out) {
-    return op_rc(launch_embedding((hipStream_t)stream, token_ids, (const uint16_t*)table, T, hidden, (uint16_t*)out));
-}
-
-int pplhip_op_rmsnorm(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t T, int32_t hidden,
-                      void* out, void* residual_out) {
-    return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, T,
-                                hidden, nullptr, (uint16_t*)out, (uint16_t*)residual_out));
-}
-
-// split-K scratch of the stand-alone operators (the runtime owns its own per rank); one per device, never freed
-static float* op_linear_ws(size_t* bytes) {
-    static float* ws[16] = {nullptr};
-    static const size_t ws_bytes = (size_t)64 << 20;
-    int dev = 0;
-    *bytes = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    if (!ws[dev] && hipMalloc((void**)&ws[dev], ws_bytes) != hipSuccess) ws[dev] = nullptr;
-    if (ws[dev]) *bytes = ws_bytes;
-    return ws[dev];
-}
-
-int pplhip_op_linear(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M,
-                     int32_t N, int32_t K, void* y, int32_t out_fp32) {
-    size_t ws_bytes = 0;
-    float* ws = op_linear_ws(&ws_bytes);
-    return op_rc(launch_linear((hipStream_t)stream, (const uint16_t*)x, w, (const uint16_t*)scale, wq_bit, group, M, N, K, y, N,
-                               out_fp32 != 0, ws, ws_bytes));
-}
-
-// (the same scratch: without it 4 <= M <= 256 ran unsplit -- N / 128 blocks instead of a full chip)
-int pplhip_op_linear_swiglu(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M,
-                            int32_t N, int32_t K, void* y) {
-    size_t ws_bytes = 0;
-    float* ws = op_linear_ws(&ws_bytes);
-    return op_rc(launch_linear((hipStream_t)stream, (const uint16_t*)x, w, (const uint16_t*)scale, wq_bit, group, M, N, K, y, N / 2,
-                               false, ws, ws_bytes, true));
-}
-
-// launch_linear with the caller's row stride, workspace and pointers, and the route it takes (kernels.h LinearRoute); dry_run: the route and
-// status only, no HIP call at all (works without a device)
-int pplhip_op_linear_ex(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M, int32_t N,
-                        int32_t K, void* y, int64_t ldy, int32_t epi, void* ws, uint64_t ws_bytes, int32_t dry_run, char* route, int32_t route_len) {
-    LinearRoute r;
-    r.buf = route_len > 0 ? route : nullptr;
-    r.cap = route_len;
-    r.dry = dry_run != 0;
-    if (r.buf) r.buf[0] = 0;
-    if (epi < 0 || epi > 2) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_linear((hipStream_t)stream, (const uint16_t*)x, w, (const uint16_t*)scale, wq_bit, group, M, N, K, y, ldy, epi == 1,
-                               (float*)ws, (size_t)ws_bytes, epi == 2, nullptr, &r));
-}
-
-int pplhip_op_rmsnorm_quant(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t T, int32_t hidden,
-                            void* residual_out, void* q, float* sx) {
-    return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, T, hidden, nullptr,
-                                nullptr, (uint16_t*)residual_out, (int8_t*)q, sx));
-}
-
-int pplhip_op_quant_act(void* stream, const void* x, int64_t M, int32_t K, void* q, float* sx) {
-    return op_rc(launch_quant_act((hipStream_t)stream, (const uint16_t*)x, M, K, K, (int8_t*)q, K, sx));
-}
-
-int pplhip_op_quant_weight(void* stream, const void* w, int32_t N, int32_t K, void* q, void* scale) {
-    return op_rc(launch_quant_weight((hipStream_t)stream, (const uint16_t*)w, N, K, (int8_t*)q, K, (uint16_t*)scale));
-}
-
-int pplhip_op_linear_i8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M, int32_t N, int32_t K,
-                        void* y, int32_t out_fp32, int32_t swiglu) {
-    return op_rc(launch_linear_i8((hipStream_t)stream, (const int8_t*)xq, sx, (const int8_t*)w, (const uint16_t*)scale, M, N, K, y,
-                                  swiglu ? N / 2 : N, out_fp32 != 0, swiglu != 0));
-}
-
-int pplhip_op_rmsnorm_quant_f8(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t T, int32_t hidden,
-                               void* residual_out, void* q, float* sx) {
-    if (!q || !sx) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, T, hidden, nullptr,
-                                nullptr, (uint16_t*)residual_out, (int8_t*)q, sx, nullptr, true));
-}
-
-int pplhip_op_quant_act_f8(void* stream, const void* x, int64_t M, int32_t K, void* q, float* sx) {
-    return op_rc(launch_quant_act_f8((hipStream_t)stream, (const uint16_t*)x, M, K, K, (uint8_t*)q, K, sx));
-}
-
-int pplhip_op_quant_weight_f8(void* stream, const void* w, int32_t N, int32_t K, void* q, void* scale) {
-    return op_rc(launch_quant_weight_f8((hipStream_t)stream, (const uint16_t*)w, N, K, (uint8_t*)q, K, (uint16_t*)scale));
-}
-
-int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int64_t M, int32_t N, int32_t K,
-                        void* y, int32_t out_fp32, int32_t swiglu) {
-    return op_rc(launch_linear_f8((hipStream_t)stream, (const uint8_t*)xq, sx, (const uint8_t*)w, (const uint16_t*)scale, M, N, K, y,
-                                  swiglu ? N / 2 : N, out_fp32 != 0, swiglu != 0));
-}
-
-int pplhip_op_step_plan(const pplhip_plan_settings* settings, const pplhip_step_shape* shape, pplhip_step_plan* out) {
-    if (!settings || !shape || !out || shape->batch < 0 || shape->num_tokens < 0) return PPLHIP_INVALID_VALUE;
-    *out = plan_step(*settings, *shape);
-    return 0;
-}
-
-int pplhip_op_lora(void* stream, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t T, int32_t N, int32_t K, const int32_t* row_slots,
-                   int32_t n_slots, const void* const* A, const void* const* B, const int32_t* ranks, const float* scales, void* ws,
-                   uint64_t ws_bytes) {
-    // everything the kernels trust is checked here, before any HIP call
-    if (T < 0 || T > INT32_MAX || N <= 0 || K <= 0 || K % 32 || N % 16 || ldx < K || ldx % 8 || ldy < N) return PPLHIP_INVALID_VALUE;
-    if (n_slots < 0 || n_slots > LORA_MAX_SLOTS || (T > 0 && !row_slots) || (n_slots > 0 && (!A || !B || !ranks || !scales))) return PPLHIP_INVALID_VALUE;
-    if (((uintptr_t)x & 15) || ((uintptr_t)y & 1)) return PPLHIP_INVALID_VALUE;
-    LoraSlot tab[LORA_MAX_SLOTS];
-    for (int s = 0; s < LORA_MAX_SLOTS; ++s) tab[s] = LoraSlot{nullptr, nullptr, 0, 0.f};
-    for (int s = 0; s < n_slots; ++s) {
-        if (!A[s] && !B[s]) continue;
-        if (!A[s] || !B[s] || ranks[s] < 1 || ranks[s] > LORA_MAX_RANK || ((uintptr_t)A[s] & 15) || ((uintptr_t)B[s] & 15)) return PPLHIP_INVALID_VALUE;
-        tab[s] = LoraSlot{(const uint16_t*)A[s], (const uint16_t*)B[s], (ranks[s] + 15) / 16 * 16, scales[s]};
-    }
-    bool any = false;
-    for (int64_t m = 0; m < T; ++m) {
-        const int s = row_slots[m];
-        if (s == -1) continue;
-        if (s < 0 || s >= n_slots || !tab[s].a) return PPLHIP_INVALID_VALUE;   // out of range, or not loaded
-        any = true;
-    }
-    if (!any) return 0;
-    if (!x || !y || !ws) return PPLHIP_INVALID_VALUE;
-    std::vector<LoraTile> tiles;
-    lora_build_tiles(row_slots, T, tiles);
-    // workspace: slot table | tile list | t, each on a 256-byte boundary
-    const uint64_t tab_bytes = sizeof(tab), tile_bytes = (tiles.size() * sizeof(LoraTile) + 255) / 256 * 256;
-    const uint64_t pre = (256 - ((uintptr_t)ws & 255)) & 255;
-    const uint64_t need = pre + tab_bytes + tile_bytes + (uint64_t)tiles.size() * 16 * LORA_MAX_RANK * 2;
-    if (ws_bytes < need) return PPLHIP_INVALID_VALUE;
-    char* base = (char*)ws + pre;
-    hipStream_t s = (hipStream_t)stream;
-    // (pageable sources: each copy has left the host buffer when the call returns)
-    hipError_t e = hipMemcpyAsync(base, tab, tab_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + tab_bytes, tiles.data(), tiles.size() * sizeof(LoraTile), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_lora(s, (const LoraTile*)(base + tab_bytes), (int)tiles.size(), (const LoraSlot*)base, (const uint16_t*)x, ldx, (uint16_t*)y, ldy, N, K,
-                        (uint16_t*)(base + tab_bytes + tile_bytes));
-    return op_rc(e);
-}
-
-int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out) {
-    return op_rc(launch_silu_mul((hipStream_t)stream, (const uint16_t*)gate_up, T, inter, (uint16_t*)out));
-}
-
-// K12 / K13 alone, on the caller's buffers (the tests preload and read back the count map and pick vocab, stride and alignment)
-int pplhip_op_penalty(void* stream, float* logits, const float* temperatures, const float* rep, const float* presence,
-                      const float* frequency, const int64_t* batch_slots, const int64_t* token_inputs, const int64_t* seq_starts,
-                      const int64_t* start_pos, int32_t batch, int32_t vocab, int32_t stride, int32_t decoding_batches, uint16_t* count_map) {
-    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_penalty((hipStream_t)stream, logits, temperatures, rep, presence, frequency, batch_slots, token_inputs, seq_starts,
-                                start_pos, batch, vocab, stride, decoding_batches, count_map));
-}
-
-int pplhip_op_sample(void* stream, const float* logits, const float* temperatures, const float* top_p, const float* rnd, int32_t batch,
-                     int32_t vocab, int32_t stride, int32_t top_k, float default_top_p, int32_t* out_tok, float* out_logprob) {
-    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
-    if (top_k == 1)
-        return op_rc(launch_sample_greedy((hipStream_t)stream, logits, temperatures, batch, vocab, stride, out_tok, out_logprob));
-    if (!rnd && batch > 0) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_sample_topk_topp((hipStream_t)stream, logits, temperatures, top_p, rnd, batch, vocab, stride, top_k, default_top_p,
-                                         nullptr, out_tok, out_logprob));
-}
-
-// the per-request sampler alone.  The row list is made here: top_k is read back, compacted on the host and sent up again into stream-ordered
-// scratch (two synchronisations of `stream` in front of the launches) -- test support, the product entry point has the arrays on the host already
-int pplhip_op_sample_rows(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
-                          const uint64_t* seeds, const uint64_t* draws, const float* rnd, int32_t batch, int32_t vocab, int32_t stride,
-                          int32_t* out_tok, float* out_logprob) {
-    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
-    if (batch == 0) return 0;
-    if (!logits || !top_k || !top_p || !out_tok || !out_logprob || (!rnd && (!seeds || !draws))) return PPLHIP_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int32_t> k(batch), rows(batch);
-    hipError_t e = hipMemcpyAsync(k.data(), top_k, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    const int ng = sample_row_list(k.data(), batch, rows.data());
-    int32_t* d_rows = nullptr;
-    if ((e = hipMallocAsync((void**)&d_rows, (size_t)batch * 4, s)) != hipSuccess) return op_rc(e);
-    e = hipMemcpyAsync(d_rows, rows.data(), (size_t)batch * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call; the stream was idle anyway
-    if (e == hipSuccess)
-        e = launch_sample_rows(s, logits, temperatures, top_k, top_p, seeds, draws, rnd, d_rows, ng, batch - ng, vocab, stride, out_tok, out_logprob);
-    const hipError_t e2 = hipFreeAsync(d_rows, s);
-    return op_rc(e != hipSuccess ? e : e2);
-}
-
-// top_logprobs_kernel alone.  The row list is made here from a read-back of num_logprobs, as pplhip_op_sample_rows makes its own
-int pplhip_op_top_logprobs(void* stream, const float* logits, const float* temperatures, const int32_t* num_logprobs, int32_t batch,
-                           int32_t vocab, int32_t stride, int32_t* out_tok, float* out_logprob) {
-    if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
-    if (batch == 0) return 0;
-    if (!logits || !num_logprobs || !out_tok || !out_logprob) return PPLHIP_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int32_t> n(batch), rows(batch);
-    hipError_t e = hipMemcpyAsync(n.data(), num_logprobs, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    const int asked = top_logprobs_row_list(n.data(), batch, rows.data());
-    if (asked < 0) return PPLHIP_INVALID_VALUE;
-    if (asked == 0) return 0;
-    int32_t* d_rows = nullptr;
-    if ((e = hipMallocAsync((void**)&d_rows, (size_t)asked * 4, s)) != hipSuccess) return op_rc(e);
-    e = hipMemcpyAsync(d_rows, rows.data(), (size_t)asked * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call
-    if (e == hipSuccess) e = launch_top_logprobs(s, logits, temperatures, num_logprobs, d_rows, asked, vocab, stride, out_tok, out_logprob);
-    const hipError_t e2 = hipFreeAsync(d_rows, s);
-    return op_rc(e != hipSuccess ? e : e2);
-}
-
-// logit_edit_kernel alone on caller-owned memory; without `rows` the list is made here from a read-back of flags
-int pplhip_op_logit_edit(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const uint32_t* flags, const int32_t* slots,
-                         const int32_t* head, const int32_t* bias_tokens, const float* bias_values, const int32_t* stop_tokens,
-                         const uint32_t* mask, const int32_t* rows, int32_t n_rows) {
-    if (batch < 0 || vocab <= 0 || stride < vocab || n_rows < 0 || n_rows > batch) return PPLHIP_INVALID_VALUE;
-    if (batch == 0) return 0;
-    if (!logits || !flags || !slots || !head || !bias_tokens || !bias_values || !stop_tokens || !mask) return PPLHIP_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    const LogitRuleTable tb{head, bias_tokens, bias_values, stop_tokens, mask, 4, LOGIT_BIAS_MAX, LOGIT_STOP_MAX, ((int64_t)vocab + 31) / 32};
-    if (rows) return op_rc(launch_logit_edit(s, logits, stride, vocab, rows, n_rows, slots, flags, tb));
-    std::vector<uint32_t> f(batch);
-    std::vector<int32_t> list;
-    hipError_t e = hipMemcpyAsync(f.data(), flags, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    for (int i = 0; i < batch; ++i)
-        if (f[i]) list.push_back(i);
-    if (list.empty()) return 0;
-    int32_t* d_rows = nullptr;
-    if ((e = hipMallocAsync((void**)&d_rows, list.size() * 4, s)) != hipSuccess) return op_rc(e);
-    e = hipMemcpyAsync(d_rows, list.data(), list.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `list` is pageable and dies with this call
-    if (e == hipSuccess) e = launch_logit_edit(s, logits, stride, vocab, d_rows, (int)list.size(), slots, flags, tb);
-    const hipError_t e2 = hipFreeAsync(d_rows, s);
-    return op_rc(e != hipSuccess ? e : e2);
-}
-
-// prompt_logprobs_kernel alone.  rows and n_top are read back and checked here: the kernel indexes `targets` with the former
-int pplhip_op_prompt_logprobs(void* stream, const float* logits, int32_t stride, int32_t vocab, const int32_t* rows, int32_t n_rows,
-                              const int64_t* targets, int64_t n_targets, const int32_t* n_top, float* out_logprob, int32_t* out_rank,
-                              int32_t* out_top_tok, float* out_top_logprob) {
-    if (n_rows < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
-    if (n_rows == 0) return 0;
-    if (!logits || !rows || !targets || !n_top || !out_logprob || !out_rank) return PPLHIP_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int32_t> hr(n_rows), hn(n_rows);
-    hipError_t e = hipMemcpyAsync(hr.data(), rows, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hn.data(), n_top, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    bool top = false;
-    for (int32_t j = 0; j < n_rows; ++j) {
-        if (hn[j] < 0 || hn[j] > PPLHIP_TOP_LOGPROBS_MAX || hr[j] < -1 || (int64_t)hr[j] + 1 >= n_targets) return PPLHIP_INVALID_VALUE;
-        top = top || hn[j] > 0;
-    }
-    if (top && (!out_top_tok || !out_top_logprob)) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_prompt_logprobs(s, logits, stride, vocab, rows, n_rows, targets, n_top, out_logprob, out_rank, out_top_tok, out_top_logprob));
-}
-
-// the two k_guide.hip kernels alone on caller-owned memory
-int pplhip_op_guide_build(void* stream, const uint8_t* trans, const uint8_t* accept, int32_t n_states, const uint8_t* tok_bytes,
-                          const int64_t* tok_off, int32_t n_tok, const int32_t* end_tokens, int32_t n_end, int32_t vocab, uint32_t* mask,
-                          int64_t mask_stride, uint32_t* any) {
-    if (n_states < 1 || n_states > GUIDE_MAX_STATES || vocab <= 0 || n_tok < 0 || n_tok > vocab || n_end < 0 || n_end > LOGIT_STOP_MAX ||
-        mask_stride < ((int64_t)vocab + 31) / 32)
-        return PPLHIP_INVALID_VALUE;
-    if (!trans || !accept || !tok_bytes || !tok_off || !mask || !any || (n_end > 0 && !end_tokens)) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_guide_build((hipStream_t)stream, trans, accept, n_states, tok_bytes, tok_off, n_tok, end_tokens, n_end, vocab, mask,
-                                    mask_stride, any));
-}
-
-int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
-                         const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
-                         const int32_t* rows, int32_t n_rows) {
-    if (batch < 0 || vocab <= 0 || stride < vocab || n_rows < 0 || n_rows > batch || n_slots < 1 || n_slots > GUIDE_MAX_SLOTS ||
-        n_states < 1 || n_states > GUIDE_MAX_STATES || mask_stride < ((int64_t)vocab + 31) / 32)
-        return PPLHIP_INVALID_VALUE;
-    if (batch == 0) return 0;
-    if (!logits || !guide_slots || !states || !masks) return PPLHIP_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    GuideTable tb;
-    for (int i = 0; i < GUIDE_MAX_SLOTS; ++i) tb.mask[i] = i < n_slots ? masks + (int64_t)i * n_states * mask_stride : nullptr;
-    tb.mask_stride = mask_stride;
-    if (rows) return op_rc(launch_guide_mask(s, logits, stride, vocab, rows, n_rows, guide_slots, states, tb));
-    std::vector<int32_t> gs(batch), st(batch), list;
-    hipError_t e = hipMemcpyAsync(gs.data(), guide_slots, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(st.data(), states, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    for (int i = 0; i < batch; ++i) {
-        if (gs[i] < 0) continue;
-        if (gs[i] >= n_slots || st[i] < 0 || st[i] >= n_states) return PPLHIP_INVALID_VALUE;   // would read outside `masks`
-        list.push_back(i);
-    }
-    if (list.empty()) return 0;
-    int32_t* d_rows = nullptr;
-    if ((e = hipMallocAsync((void**)&d_rows, list.size() * 4, s)) != hipSuccess) return op_rc(e);
-    e = hipMemcpyAsync(d_rows, list.data(), list.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `list` is pageable and dies with this call
-    if (e == hipSuccess) e = launch_guide_mask(s, logits, stride, vocab, d_rows, (int)list.size(), guide_slots, states, tb);
-    const hipError_t e2 = hipFreeAsync(d_rows, s);
-    return op_rc(e != hipSuccess ? e : e2);
-}
-
-int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u) {
-    if (batch < 0 || (batch > 0 && (!seeds || !draws || !out_u))) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_sample_uniform((hipStream_t)stream, seeds, draws, batch, out_u));
-}
-
-static KvAddr view_addr(const pplhip_kv_view* v) {
-    pplhip_model_desc d;
-    memset(&d, 0, sizeof(d));
-    d.num_layers = v->num_layers;
-    d.cache_quant_bit = v->quant_bit; d.cache_quant_group = v->quant_group;
-    d.cache_layout = v->layout; d.cache_mode = v->mode; d.page_size = v->page_size;
-    return make_kv_addr(d, v->kv_heads, v->head_dim, (uint64_t)v->max_tokens, v->cache, (uint16_t*)v->scale, v->layer);
-}
-
-int pplhip_op_rope_kv_write(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
-                            const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
-                            int32_t num_heads) {
-    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
-    if (fmt < 0) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_rope_kv_write((hipStream_t)stream, (uint16_t*)qkv, cos_sin, view_addr(kv), fmt,
-                                      seq_starts, start_pos, cache_indices, max_pages, B, 0, T, num_heads, kv->kv_heads, kv->head_dim));
-}
-
-// ---- the row kernels with everything their launchers take (for the tests: not part of the product boundary) ----
-// slab description -> SplitSlabs of a [slab_M, N] launch; false: not a description a producer can leave
-static bool op_slabs(const float* ws, int32_t splits, const void* scale, int64_t M, int N, SplitSlabs* sl) {
-    *sl = SplitSlabs{};
-    if (splits == 0) return true;
-    if (splits < 0 || splits > 8 || !ws || M <= 0 || N <= 0 || N % 8 || ((uintptr_t)ws & 15) || ((uintptr_t)scale & 15)) return false;
-    *sl = SplitSlabs{ws, splits, (const uint16_t*)scale, N, M};
-    return true;
-}
-
-int pplhip_op_rmsnorm_form(int64_t rows, int32_t hidden, int32_t quant, int32_t wide_max_rows, char* buf, int32_t len) {
-    if (buf && len > 0) buf[0] = 0;
-    if (rows < 0 || quant < 0 || quant > 2) return PPLHIP_INVALID_VALUE;
-    RmsnormForm f;
-    const hipError_t e = rmsnorm_form(rows, hidden, wide_max_rows, &f);
-    if (e == hipSuccess && f.nt && buf && len > 0)
-        snprintf(buf, (size_t)len, "rmsnorm_kernel<%d,%d%s>", f.maxc, f.nt, quant == 2 ? ",f8" : (quant == 1 ? ",i8" : ""));
-    return op_rc(e);
-}
-
-int pplhip_op_rmsnorm_ex(void* stream, const void* x, const void* skip, const void* w, float eps, int64_t rows, int32_t hidden,
-                         const int64_t* gather_seq_starts, void* out, void* residual_out, void* q, float* sx, int32_t q_fp8,
-                         const float* slab_ws, int32_t slab_splits, const void* slab_scale, int64_t slab_M) {
-    SplitSlabs sl;
-    if (rows < 0 || !op_slabs(slab_ws, slab_splits, slab_scale, slab_M, hidden, &sl)) return PPLHIP_INVALID_VALUE;
-    if (rows > 0 && (!x || !w || (q ? !sx : !out))) return PPLHIP_INVALID_VALUE;
-    if (sl.splits && !gather_seq_starts && rows > slab_M) return PPLHIP_INVALID_VALUE;   // (gathered rows: the caller's seq_starts stay below slab_M)
-    return op_rc(launch_rmsnorm((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)skip, (const uint16_t*)w, eps, rows, hidden,
-                                gather_seq_starts, (uint16_t*)out, (uint16_t*)residual_out, (int8_t*)q, sx, &sl, q_fp8 != 0));
-}
-
-int pplhip_op_gather_last_rows(void* stream, const void* x, const int64_t* seq_starts, int64_t B, int32_t hidden, void* out) {
-    if (B < 0 || (B > 0 && (!x || !seq_starts || !out))) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_gather_last_rows((hipStream_t)stream, (const uint16_t*)x, seq_starts, B, hidden, (uint16_t*)out));
-}
-
-int pplhip_op_rope_kv_write_ex(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
-                               const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0, int64_t T,
-                               int32_t num_heads, const float* slab_ws, int32_t slab_splits, const void* slab_scale, int64_t slab_M) {
-    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
-    if (fmt < 0 || t0 < 0 || T < 0 || B < 0) return PPLHIP_INVALID_VALUE;
-    SplitSlabs sl;
-    if (!op_slabs(slab_ws, slab_splits, slab_scale, slab_M, (num_heads + 2 * kv->kv_heads) * kv->head_dim, &sl)) return PPLHIP_INVALID_VALUE;
-    return op_rc(launch_rope_kv_write((hipStream_t)stream, (uint16_t*)qkv, cos_sin, view_addr(kv), fmt, seq_starts, start_pos, cache_indices,
-                                      max_pages, B, t0, T, num_heads, kv->kv_heads, kv->head_dim, &sl));
-}
-
-// launch_linear (fp16 epilogue) with a non-null `defer`, as layer_linear calls it for wqkv / wo / w2: a split-K route leaves its slabs in ws
-int pplhip_op_linear_defer(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M, int32_t N,
-                           int32_t K, void* y, int64_t ldy, void* ws, uint64_t ws_bytes, int32_t dry_run, int32_t* splits,
-                           const void** slab_scale, char* route, int32_t route_len) {
-    LinearRoute r;
-    r.buf = route_len > 0 ? route : nullptr;
-    r.cap = route_len;
-    r.dry = dry_run != 0;
-    if (r.buf) r.buf[0] = 0;
-    SplitSlabs sl;
-    const hipError_t e = launch_linear((hipStream_t)stream, (const uint16_t*)x, w, (const uint16_t*)scale, wq_bit, group, M, N, K, y, ldy, false,
-                                       (float*)ws, (size_t)ws_bytes, false, &sl, &r);
-    if (splits) *splits = sl.splits;
-    if (slab_scale) *slab_scale = sl.scale;
-    return op_rc(e);
-}
-
-int pplhip_op_attention(void* stream, const void* qkv, const pplhip_kv_view* kv, const int64_t* seq_starts,
-                        const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
-                        int64_t decoding_batches, int64_t max_seq_len, int64_t max_kv_len, int32_t num_heads, int32_t split_k,
-                        void* workspace, uint64_t workspace_bytes, void* out) {
-    (void)T;
-    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
-    if (fmt < 0) return PPLHIP_INVALID_VALUE;
-    const int64_t nb = std::min<int64_t>(std::max<int64_t>(decoding_batches, 0), B);
-    int split = split_k < 1 ? 1 : split_k;
-    if (split > 1 && attn_decode_workspace_bytes(nb, num_heads, kv->head_dim, split) > workspace_bytes) return PPLHIP_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    const KvAddr a = view_addr(kv);
-    hipError_t e = hipSuccess;
-    if (nb > 0)
-        e = launch_attn_decode(s, (const uint16_t*)qkv, a, fmt, seq_starts, start_pos, cache_indices, max_pages, nb,
-                               num_heads, kv->kv_heads, kv->head_dim, max_kv_len, split, 256, (float*)workspace, (uint16_t*)out);
-    if (e == hipSuccess && B > nb)
-        e = launch_attn_prefill(s, (const uint16_t*)qkv, a, fmt, seq_starts, start_pos, cache_indices, max_pages, nb, B,
-                                num_heads, kv->kv_heads, kv->head_dim, max_seq_len, (uint16_t*)out, max_kv_len, (float*)workspace,
-                                (size_t)workspace_bytes, nb, T - nb);
-    return op_rc(e);
-}
-
-}  // extern "C"

@@ -34,7 +34,7 @@ def ulp16(v):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the tile list (pplhip.cc lora_build_tiles restated)
+# the tile list (rt_lora.cc lora_build_tiles restated)
 # ---------------------------------------------------------------------------------------------------------------
 def build_tiles(row_slots):
     """[(slot, [row, ...])]: slots ascending, a slot's rows ascending, 16 to a tile"""
