@@ -754,6 +754,57 @@ PPLHIP_API int pplhip_op_attention(void* stream, const void* qkv, const pplhip_k
                                    int32_t num_heads, int32_t split_k, void* workspace, uint64_t workspace_bytes,
                                    void* out);
 
+/* The direct collectives (csrc/k_comm.hip) as operators, for a context whose ranks all live in this process and run the direct mode
+ * (pplhip_comm_mode == 2).  One call runs a SEQUENCE of collectives: every item is enqueued on every local rank from the calling thread,
+ * back to back on the ranks' streams with no host synchronisation in between, then every rank is synchronised.  Channel 0 runs on the
+ * rank's stream, channel 1 (only in a context with two-stream decode) on its second stream, each with its own flag set, scratch pair and
+ * epoch counter -- the context's own counters, which the call advances exactly as a step would, so that steps still work afterwards.
+ *
+ * Per rank r an item takes host arrays and returns host copies of everything the collective may write (the caller puts canaries
+ * around the regions: the images are larger than the operands):
+ *   PPLHIP_COMM_ALLREDUCE       data[r]  fp16 [data_elems]: the image of the channel's data buffer, the first `count` elements are the partial
+ *                               sums; out0[r] fp16 [data_elems]: the buffer afterwards
+ *   PPLHIP_COMM_ALLREDUCE_NORM  data[r]  fp16 [rows, hidden] partial sums; image0[r] / image1[r] fp16 [image_elems]: the images of the residual
+ *                               rows h and of the normed matrix xn, rows first; w[r] fp16 [hidden]; out0[r] / out1[r] [image_elems]: h and xn
+ *                               afterwards.  `hidden` is the item's own (% 8, <= 8192), not the model's
+ *   PPLHIP_COMM_ALLGATHER       data[r]  fp32 [rows, cols]: the rank's shard; image0[r] fp32 [image_elems]: the image of the gather target, a
+ *                               [rows, dst_stride] matrix (dst_stride >= ranks x cols); out0[r] [image_elems]: the target afterwards.  Channel 0
+ * The inputs reach the collectives' buffers by device copies ordered on the rank's own stream in front of the item (staged on the device
+ * before anything is enqueued), the outputs leave by stream-ordered device copies into separate staging.  skew (may be NULL): skew[r]
+ * (0 .. 64) extra stream-ordered device copies in front of rank r's part of the item, so that the ranks arrive at different times.
+ * epoch_advance (< 2^31) is added to the channel's epoch counter on every rank in front of the item.
+ *
+ * PPLHIP_INVALID_VALUE, before anything is enqueued on any rank and with every counter unchanged: a shape that the data buffer, the scratch
+ * slice, the gather source or target cannot hold, or that the launcher refuses (count % 8, hidden % 8, hidden > 8192, odd cols or stride); a
+ * channel that does not exist; a second all-gather with no all-reduce on channel 0 between the two (the all-gather has no end barrier:
+ * the next one's inputs would overwrite a source that a peer may still read).  A status word that a kernel raised (a bounded wait ran
+ * out) is PPLHIP_DEVICE_RUNTIME_ERROR: pplhip_last_error names the rank and the word, which is cleared.
+ * counters receives local rank 0's epoch counters and all-reduce counts of both channels as the call leaves them (on every return with a
+ * valid context; the ranks' counters move together). */
+enum { PPLHIP_COMM_ALLREDUCE = 0, PPLHIP_COMM_ALLREDUCE_NORM = 1, PPLHIP_COMM_ALLGATHER = 2 };
+typedef struct pplhip_comm_item {
+    int32_t kind, channel;
+    uint32_t epoch_advance;
+    float eps;                      /* fused form */
+    int64_t count;                  /* all-reduce: fp16 elements */
+    int64_t rows, hidden;           /* fused form: rows x hidden; all-gather: rows */
+    int64_t cols, dst_stride;       /* all-gather: fp32 per rank and row; row stride of the target in fp32 */
+    int64_t data_elems, image_elems;
+    const void* const* data;        /* [ranks] */
+    const void* const* image0;      /* [ranks] */
+    const void* const* image1;      /* [ranks] */
+    const void* const* w;           /* [ranks] */
+    const int32_t* skew;            /* [ranks] or NULL */
+    void* const* out0;              /* [ranks] */
+    void* const* out1;              /* [ranks] */
+} pplhip_comm_item;
+typedef struct pplhip_comm_op_args {
+    const pplhip_comm_item* items;
+    int32_t n_items;
+    uint32_t* counters;             /* out [4] (may be NULL): epoch of channel 0, of channel 1, ar_count of channel 0, of channel 1 */
+} pplhip_comm_op_args;
+PPLHIP_API int pplhip_comm_op(pplhip_ctx* ctx, const pplhip_comm_op_args* args);
+
 /* builds the fp32 cos/sin table [max_position, head_dim] (cos first half, sin second half per row). */
 PPLHIP_API int pplhip_build_rope_table(float* host_out, int32_t max_position, int32_t head_dim, float theta);
 

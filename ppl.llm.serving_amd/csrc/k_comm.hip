@@ -17,6 +17,7 @@
 //                         start barriers that every peer only passes after leaving this kernel.
 //   Peers never WRITE each other's data, only flag words: a remote store into memory that a later local kernel reads with
 //   ordinary loads would depend on that GPU's caches holding no older copy of the line.
+//   Flag words of blocks that small collectives leave idle are lifted every 2^30 epochs (p2p_flag_refresh_kernel; kernels.h says why).
 //   all-gather of the fp32 logits shards: start barrier, every rank reads every peer's shard (published in the exchange
 //   region by a local copy) into its own gather buffer.
 //
@@ -106,6 +107,16 @@ __device__ __forceinline__ void cross_rank_barrier(const P2pPeers& peers, int me
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
     }
     __syncthreads();
+}
+
+// the words of one channel in the rank's own region (start and middle barrier: contiguous) that lag `epoch` -> epoch (kernels.h)
+__global__ __launch_bounds__(256) void p2p_flag_refresh_kernel(uint32_t* flags, uint32_t epoch) {
+    constexpr int WORDS = (int)(P2P_CHANNEL_FLAG_BYTES / 4);
+    for (int i = threadIdx.x; i < WORDS; i += 256) {
+        uint32_t w = ld_sys(flags + i);
+        if ((int32_t)(w - epoch) < 0)   // behind (a word never lags more than 2^31: kernels.h); a peer that is already further on is ahead
+            (void)__hip_atomic_compare_exchange_strong(flags + i, &w, epoch, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 __device__ __forceinline__ void add8(float* acc, u32x4 v) {
@@ -364,6 +375,13 @@ float p2p_pattern_value(int64_t i, int g, int round) { return (float)((int)((i *
 
 hipError_t launch_p2p_pattern(hipStream_t s, uint16_t* halfs, int64_t cnt, float* floats, int64_t gcnt, int g, int round) {
     hipLaunchKernelGGL(p2p_pattern_kernel, dim3(256), dim3(256), 0, s, halfs, cnt, floats, gcnt, g, round);
+    return hipGetLastError();
+}
+
+hipError_t launch_p2p_flag_refresh(hipStream_t s, char* my_base, int channel, uint32_t epoch) {
+    if (!my_base || channel < 0 || channel >= P2P_CHANNELS) return hipErrorInvalidValue;
+    static_assert(P2P_FLAGS_START == 0 && P2P_FLAGS_MID * 2 == P2P_CHANNEL_FLAG_BYTES, "a channel's words are one contiguous block");
+    hipLaunchKernelGGL(p2p_flag_refresh_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<uint32_t*>(my_base + (size_t)channel * P2P_CHANNEL_FLAG_BYTES), epoch);
     return hipGetLastError();
 }
 

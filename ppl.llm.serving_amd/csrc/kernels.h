@@ -201,9 +201,21 @@ constexpr int P2P_CHANNELS = 2;
 constexpr size_t P2P_CHANNEL_FLAG_BYTES = (size_t)2 * P2P_MAX_BLOCKS * P2P_MAX_RANKS * 4;
 constexpr size_t P2P_DATA_START = 8192;
 static_assert(P2P_CHANNELS * P2P_CHANNEL_FLAG_BYTES <= P2P_DATA_START, "flag words of every channel in front of the data");
+// A flag word belongs to ONE block index, and a collective of b blocks only raises the words of blocks 0 .. b-1: the words of higher
+// blocks stay where the last large collective left them.  Epochs are compared with (int32_t)(flag - epoch) < 0, which is right only
+// while a word lags its channel's counter by at most 2^31 -- a word that small collectives leave behind for longer compares as AHEAD,
+// and the block of the next large collective would pass its barriers without its peers.  So every P2P_FLAG_REFRESH_EPOCHS epochs of
+// a channel the runtime (p2p_next_epoch, rt_comm.cc) launches launch_p2p_flag_refresh on the stream in front of the next collective: it
+// lifts every word of the rank's OWN region (the words its own blocks wait on) that is behind the counter's value `epoch` to it.  Every
+// collective up to `epoch` of this rank is complete by then (stream order), so no block still waits for such a value, and every later
+// one waits for more.  A word that is ahead -- a peer has already entered a later collective -- is kept, also when the peer's store lands
+// between the load and the store here (compare-and-swap).  Behind and ahead are told apart by the same signed comparison: between two
+// refreshes the counter moves by less than 2^31 (pplhip_comm_op, which can move it in jumps, jumps by at most the refresh period).
+constexpr uint32_t P2P_FLAG_REFRESH_EPOCHS = 1u << 30;
 struct P2pPeers {
     char* base[P2P_MAX_RANKS];  // exchange region of every rank as mapped in this process (base[me] is the local one)
 };
+hipError_t launch_p2p_flag_refresh(hipStream_t s, char* my_base, int channel, uint32_t epoch);
 // all-reduce(sum) of fp16[count] at byte offset data_off of every rank's region (count % 4 == 0); scratch_off: a region
 // offset with room for ceil(count / n) fp16 that no other collective in flight uses
 hipError_t launch_p2p_allreduce(hipStream_t s, const P2pPeers& peers, int me, int n, size_t data_off, size_t scratch_off, int64_t count,
@@ -219,6 +231,10 @@ hipError_t launch_p2p_allreduce_norm(hipStream_t s, const P2pPeers& peers, int m
                                      uint32_t* status, int channel = 0);
 // rows x row_bytes at src_off of every rank's region (rank r's column block) -> columns [r * row_bytes, ...) of the local
 // [rows, dst_row_bytes] matrix dst (ordinary memory)
+// Sequence rule: the all-gather has a start barrier and NO end barrier -- a rank that leaves the kernel knows nothing about its peers'
+// reads of ITS shard.  So nothing may rewrite the source at src_off before a later all-reduce (plain or fused) of channel 0 on the same
+// stream: passing that one's start barrier means every peer has left the all-gather.  A step keeps the rule by itself (the next lm_head
+// writes the shards behind a whole step's all-reduces); pplhip_comm_op refuses a sequence that breaks it.
 hipError_t launch_p2p_allgather(hipStream_t s, const P2pPeers& peers, int me, int n, size_t src_off, void* dst, int64_t rows,
                                 int64_t row_bytes, int64_t dst_row_bytes, uint32_t epoch, uint64_t timeout_ticks, uint32_t* status);
 

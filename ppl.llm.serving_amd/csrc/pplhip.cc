@@ -529,6 +529,7 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
             R.x_part2 = R.x_part + up((size_t)cap_T * hd * 2);
             // a rank's reduced slice: <= half the buffer (n >= 2) -- as elements (plain all-reduce) or as whole rows (fused norm: ceil(T / 2) rows)
             const size_t slice_bytes = up(((size_t)cap_T / 2 + 1) * hd * 2 + 64);
+            R.x_slice_bytes = slice_bytes;
             R.x_local = R.x_part2 + up((size_t)cap_T * hd * 2);
             for (int ch = 0; ch < (c->dual_mode ? 2 : 1); ++ch)
                 for (int i = 0; i < 2; ++i) { R.ch[ch].x_scratch[i] = R.x_local; R.x_local += slice_bytes; }
@@ -1202,9 +1203,12 @@ int chunk_allreduce(pplhip_ctx* c, int rank, Lane& lane, uint16_t* buf, const Ch
     const int hd = c->d.hidden_dim;
     uint16_t* p = buf + k.t0 * hd;
     auto reduce_on = [&](hipStream_t st) -> int {
+        uint32_t ep = 0;
+        if (c->comm_mode == 2)
+            if (int rc = p2p_next_epoch(c, rank, ch, st, &ep)) return rc;
         if (norm_w && c->comm_mode == 2) {
             HIPCK(c, rank, launch_p2p_allreduce_norm(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase), ch.x_scratch[ch.ar_count++ & 1], k.tn,
-                                                     hd, R.h + k.t0 * hd, norm_w, c->d.norm_eps, R.xn + k.t0 * hd, ++ch.p2p_epoch, c->p2p_timeout_ticks,
+                                                     hd, R.h + k.t0 * hd, norm_w, c->d.norm_eps, R.xn + k.t0 * hd, ep, c->p2p_timeout_ticks,
                                                      R.p2p_status, ch.id));
             return 0;
         }
@@ -1219,7 +1223,7 @@ int chunk_allreduce(pplhip_ctx* c, int rank, Lane& lane, uint16_t* buf, const Ch
         }
         if (c->comm_mode == 2)
             HIPCK(c, rank, launch_p2p_allreduce(st, R.peers, R.global_rank, c->tp, (size_t)((char*)p - R.xbase), ch.x_scratch[ch.ar_count++ & 1], k.tn * hd,
-                                                ++ch.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status, ch.id));
+                                                ep, c->p2p_timeout_ticks, R.p2p_status, ch.id));
         else if (ch.comm)
             NCCLCK(c, rank, ncclAllReduce(p, p, (size_t)k.tn * hd, ncclFloat16, ncclSum, ch.comm, st));
         return 0;
@@ -1326,8 +1330,10 @@ static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& set
         Channel& ch = R.ch[0];
         auto gather_on = [&](hipStream_t cs) -> int {
             if (c->comm_mode == 2) {  // every rank pulls every shard straight into its [B, V] logits
+                uint32_t ep = 0;
+                if (int rc = p2p_next_epoch(c, rank, ch, cs, &ep)) return rc;
                 HIPCK(c, rank, launch_p2p_allgather(cs, R.peers, R.global_rank, c->tp, R.x_local, R.logits, B, (int64_t)vl * 4,
-                                                    (int64_t)d.vocab_size * 4, ++ch.p2p_epoch, c->p2p_timeout_ticks, R.p2p_status));
+                                                    (int64_t)d.vocab_size * 4, ep, c->p2p_timeout_ticks, R.p2p_status));
             } else if (ch.comm) {
                 NCCLCK(c, rank, ncclAllGather(R.logits_local, R.logits_gather, (size_t)B * vl, ncclFloat32, ch.comm, cs));
             } else {  // world size 1 without a communicator cannot happen (tp_on implies one of the two)

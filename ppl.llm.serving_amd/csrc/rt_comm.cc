@@ -3,6 +3,20 @@
 // (chunk_allreduce, the stream hand-offs of the two-chunk schedule) is in pplhip.cc.
 #include "rt_internal.h"
 
+static int p2p_refresh_if_due(pplhip_ctx* c, int rank, Channel& ch, hipStream_t s) {
+    if ((uint32_t)(ch.p2p_epoch - ch.refreshed_at) >= P2P_FLAG_REFRESH_EPOCHS) {
+        HIPCK(c, rank, launch_p2p_flag_refresh(s, c->ranks[rank].xbase, ch.id, ch.p2p_epoch));
+        ch.refreshed_at = ch.p2p_epoch;
+    }
+    return 0;
+}
+
+int p2p_next_epoch(pplhip_ctx* c, int rank, Channel& ch, hipStream_t s, uint32_t* epoch) {
+    if (int rc = p2p_refresh_if_due(c, rank, ch, s)) return rc;
+    *epoch = ++ch.p2p_epoch;
+    return 0;
+}
+
 namespace {
 
 // the direct path cannot be used: an error when it was demanded (or no RCCL communicator exists), else RCCL stays in charge
@@ -49,10 +63,13 @@ int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
             Rank& R = c->ranks[r];
             Channel& ch = R.ch[0];
             HIPCK(c, r, hipSetDevice(R.device));
-            HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], cnt, ++ch.p2p_epoch,
+            uint32_t ep = 0;
+            if (int rc = p2p_next_epoch(c, r, ch, R.stream, &ep)) return rc;
+            HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], cnt, ep,
                                              ticks, R.p2p_status));
+            if (int rc = p2p_next_epoch(c, r, ch, R.stream, &ep)) return rc;
             HIPCK(c, r, launch_p2p_allgather(R.stream, R.peers, R.global_rank, tp, R.x_local, R.logits, grows, gcols * 4, (int64_t)gcols * 4 * tp,
-                                             ++ch.p2p_epoch, ticks, R.p2p_status));
+                                             ep, ticks, R.p2p_status));
         }
         for (int r = 0; r < n && ok; ++r) {
             Rank& R = c->ranks[r];
@@ -108,14 +125,17 @@ int p2p_selftest(pplhip_ctx* c, const std::string* local_failure = nullptr) {
                 HIPCK(c, r, hipSetDevice(R.device));
                 uint16_t* xref = (uint16_t*)R.gemm_ws, *href = xref + fcnt, *w = href + fcnt;
                 HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, fcnt, nullptr, 0, R.global_rank, round + 4));
-                HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], fcnt, ++ch.p2p_epoch, ticks, R.p2p_status));
+                uint32_t ep = 0;
+                if (int rc = p2p_next_epoch(c, r, ch, R.stream, &ep)) return rc;
+                HIPCK(c, r, launch_p2p_allreduce(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], fcnt, ep, ticks, R.p2p_status));
                 HIPCK(c, r, launch_p2p_pattern(R.stream, R.h, fcnt, nullptr, 0, 17, round + 4));    // the residual stream: the same on every rank
                 HIPCK(c, r, launch_p2p_pattern(R.stream, w, hd, nullptr, 0, 23, round + 4));
                 HIPCK(c, r, hipMemcpyAsync(href, R.h, (size_t)fcnt * 2, hipMemcpyDeviceToDevice, R.stream));
                 HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, 1, R.x_part, 0, frows, hd, href, w, c->d.norm_eps, xref, 0, ticks, R.p2p_status));
                 HIPCK(c, r, launch_p2p_pattern(R.stream, R.part, fcnt, nullptr, 0, R.global_rank, round + 4));
+                if (int rc = p2p_next_epoch(c, r, ch, R.stream, &ep)) return rc;
                 HIPCK(c, r, launch_p2p_allreduce_norm(R.stream, R.peers, R.global_rank, tp, R.x_part, ch.x_scratch[ch.ar_count++ & 1], frows, hd, R.h, w, c->d.norm_eps,
-                                                      R.xn, ++ch.p2p_epoch, ticks, R.p2p_status));
+                                                      R.xn, ep, ticks, R.p2p_status));
             }
             for (int r = 0; r < n && ok; ++r) {
                 Rank& R = c->ranks[r];
@@ -318,5 +338,225 @@ int pplhip_comm_allreduce_us(pplhip_ctx* c, int rank, int64_t rows, int32_t iter
     HIPCK(c, rank, hipEventElapsedTime(&ms, e0, e1));
     *us = ms * 1e3f / (float)iters;
     if (R.p2p_status && *R.p2p_status) return fail(c, rank, PPLHIP_DEVICE_RUNTIME_ERROR, "a direct collective timed out during pplhip_comm_allreduce_us");
+    return 0;
+}
+
+// ---- pplhip_comm_op: the direct collectives as operators (include/pplhip.h) --------------------------------------------------------------
+namespace {
+
+constexpr size_t COMM_OP_SKEW_BYTES = (size_t)2 << 20;   // one skew copy moves this much inside the call's staging
+
+// where an item's arrays sit in a rank's staging block (the same on every rank) and how large they are
+struct CommOpPlace {
+    size_t data = 0, image0 = 0, image1 = 0, w = 0, out0 = 0, out1 = 0;            // byte offsets
+    size_t data_b = 0, image0_b = 0, image1_b = 0, w_b = 0;                       // bytes (out0 / out1: as image0 / image1; all-reduce: as data)
+};
+
+// the staging blocks of one call: freed, behind a synchronisation of every stream that may still use them, on every return path
+struct CommOpStaging {
+    pplhip_ctx* c;
+    std::vector<char*> base;
+    explicit CommOpStaging(pplhip_ctx* ctx) : c(ctx), base(ctx->ranks.size(), nullptr) {}
+    ~CommOpStaging() {
+        for (size_t r = 0; r < base.size(); ++r) {
+            Rank& R = c->ranks[r];
+            (void)hipSetDevice(R.device);
+            (void)hipStreamSynchronize(R.stream);
+            if (R.stream2) (void)hipStreamSynchronize(R.stream2);
+            if (base[r]) (void)hipFree(base[r]);
+        }
+    }
+};
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// the buffers of the fused form on a channel: a two-stream context gives each channel half of h and xn (its steps give each half-batch its rows)
+size_t comm_op_image_cap(const pplhip_ctx* c, const Rank& R) {
+    const size_t all = (size_t)R.cap_T * c->d.hidden_dim * 2;
+    return R.stream2 ? all / 2 / 16 * 16 : all;
+}
+
+// PPLHIP_INVALID_VALUE with the reason, or 0 and the item's sizes
+int comm_op_check(pplhip_ctx* c, const pplhip_comm_item& it, int idx, CommOpPlace& p) {
+    const int n = c->tp;
+    const Rank& R = c->ranks[0];
+    auto bad = [&](const std::string& why) { return fail(c, -1, PPLHIP_INVALID_VALUE, "pplhip_comm_op: item " + std::to_string(idx) + ": " + why); };
+    if (it.kind < PPLHIP_COMM_ALLREDUCE || it.kind > PPLHIP_COMM_ALLGATHER) return bad("kind");
+    if (it.channel < 0 || it.channel >= P2P_CHANNELS) return bad("channel");
+    if (it.channel == 1 && !R.stream2) return bad("channel 1 needs a context with two-stream decode");
+    if (it.epoch_advance >= 0x80000000u) return bad("epoch_advance must stay below 2^31");
+    if (!it.data || !it.out0) return bad("null array");
+    const size_t data_cap = (size_t)R.cap_T * c->d.hidden_dim * 2, slice = R.x_slice_bytes;
+    if (it.kind == PPLHIP_COMM_ALLREDUCE) {
+        if (it.count < 8 || it.count % 8) return bad("count must be a positive multiple of 8");
+        if (it.data_elems < it.count || (uint64_t)it.data_elems > data_cap / 2) return bad("the data buffer cannot hold it");
+        const int64_t per = (it.count / 8 + n - 1) / n;
+        if ((uint64_t)per * 16 > slice) return bad("the scratch slice cannot hold it");
+        p.data_b = (size_t)it.data_elems * 2;
+    } else if (it.kind == PPLHIP_COMM_ALLREDUCE_NORM) {
+        if (it.rows < 1 || it.hidden < 8 || it.hidden % 8 || it.hidden > P2P_NORM_MAX_HIDDEN) return bad("rows >= 1, hidden a multiple of 8 up to 8192");
+        if (it.rows > (int64_t)(data_cap / 2 / it.hidden)) return bad("the data buffer cannot hold it");
+        const int64_t need = it.rows * it.hidden;
+        if (it.data_elems != need) return bad("data_elems must be rows x hidden");
+        if (it.image_elems < need || (uint64_t)it.image_elems > comm_op_image_cap(c, R) / 2) return bad("h / xn cannot hold it");
+        const int64_t per = (it.rows + n - 1) / n;
+        if ((uint64_t)per * it.hidden * 2 > slice) return bad("the scratch slice cannot hold it");
+        if (!it.image0 || !it.image1 || !it.w || !it.out1) return bad("null array");
+        p.data_b = (size_t)need * 2;
+        p.image0_b = p.image1_b = (size_t)it.image_elems * 2;
+        p.w_b = (size_t)it.hidden * 2;
+    } else {
+        if (it.channel != 0) return bad("the all-gather runs on channel 0");
+        if (it.rows < 1 || it.cols < 2 || it.cols % 2 || it.dst_stride % 2) return bad("rows >= 1, cols and dst_stride even");
+        if (it.cols > (int64_t)1 << 40 || it.dst_stride > (int64_t)1 << 40 || it.rows > (int64_t)1 << 20) return bad("shape");
+        if (it.dst_stride < it.cols * n) return bad("dst_stride below ranks x cols");
+        const int64_t need = it.rows * it.cols;
+        if (it.data_elems != need || (uint64_t)need > (uint64_t)R.cap_B * c->vocab_local) return bad("the gather source cannot hold it");
+        if (it.image_elems < (it.rows - 1) * it.dst_stride + it.cols * n || (uint64_t)it.image_elems > (uint64_t)R.cap_B * c->d.vocab_size)
+            return bad("the gather target cannot hold it");
+        if (!it.image0) return bad("null array");
+        p.data_b = (size_t)need * 4;
+        p.image0_b = (size_t)it.image_elems * 4;
+    }
+    for (int r = 0; r < n; ++r) {
+        if (!it.data[r] || !it.out0[r] || (it.image0 && !it.image0[r])) return bad("null array");
+        if (it.kind == PPLHIP_COMM_ALLREDUCE_NORM && (!it.image1[r] || !it.w[r] || !it.out1[r])) return bad("null array");
+        if (it.skew && (it.skew[r] < 0 || it.skew[r] > 64)) return bad("skew must be 0 .. 64");
+    }
+    return 0;
+}
+
+void comm_op_counters(const pplhip_ctx* c, uint32_t* out) {
+    if (!out || c->ranks.empty()) return;
+    for (int ch = 0; ch < 2; ++ch) { out[ch] = c->ranks[0].ch[ch].p2p_epoch; out[2 + ch] = c->ranks[0].ch[ch].ar_count; }
+}
+
+}  // namespace
+
+int pplhip_comm_op(pplhip_ctx* c, const pplhip_comm_op_args* a) {
+    if (!c || !a) return PPLHIP_INVALID_VALUE;
+    comm_op_counters(c, a->counters);
+    const int n = (int)c->ranks.size();
+    if (c->comm_mode != 2 || n != c->tp || n < 2) return fail(c, -1, PPLHIP_INVALID_VALUE, "pplhip_comm_op: needs the direct collectives with every rank in this process");
+    if (a->n_items < 1 || a->n_items > 4096 || !a->items) return fail(c, -1, PPLHIP_INVALID_VALUE, "pplhip_comm_op: 1 .. 4096 items");
+    // ---- everything that can be refused is refused here: nothing is enqueued, no counter has moved ----
+    std::vector<CommOpPlace> place(a->n_items);
+    size_t total = 2 * COMM_OP_SKEW_BYTES;
+    bool gather_open = false;   // an all-gather that no all-reduce on channel 0 has followed yet (kernels.h, launch_p2p_allgather)
+    for (int i = 0; i < a->n_items; ++i) {
+        const pplhip_comm_item& it = a->items[i];
+        CommOpPlace& p = place[i];
+        if (int rc = comm_op_check(c, it, i, p)) return rc;
+        if (it.kind == PPLHIP_COMM_ALLGATHER) {
+            if (gather_open) return fail(c, -1, PPLHIP_INVALID_VALUE, "pplhip_comm_op: item " + std::to_string(i) +
+                                         ": a second all-gather with no all-reduce on channel 0 since the first (its inputs would overwrite a source a peer may still read)");
+            gather_open = true;
+        } else if (it.channel == 0) {
+            gather_open = false;
+        }
+        const size_t out0_b = it.kind == PPLHIP_COMM_ALLREDUCE ? p.data_b : p.image0_b;
+        p.data = total;   total += up256(p.data_b);
+        p.image0 = total; total += up256(p.image0_b);
+        p.image1 = total; total += up256(p.image1_b);
+        p.w = total;      total += up256(p.w_b);
+        p.out0 = total;   total += up256(out0_b);
+        p.out1 = total;   total += up256(p.image1_b);
+    }
+    // ---- staging: host -> device with synchronous copies, before any collective is enqueued (a copy that waited for a stream on which a
+    //      collective waits for a peer that is not enqueued yet would wait with it) ----
+    CommOpStaging st(c);
+    for (int r = 0; r < n; ++r) {
+        Rank& R = c->ranks[r];
+        HIPCK(c, r, hipSetDevice(R.device));
+        HIPCK(c, r, hipStreamSynchronize(R.stream));
+        if (R.stream2) HIPCK(c, r, hipStreamSynchronize(R.stream2));
+        HIPCK(c, r, hipMalloc((void**)&st.base[r], total));
+        HIPCK(c, r, hipMemset(st.base[r], 0, 2 * COMM_OP_SKEW_BYTES));
+        for (int i = 0; i < a->n_items; ++i) {
+            const pplhip_comm_item& it = a->items[i];
+            const CommOpPlace& p = place[i];
+            HIPCK(c, r, hipMemcpy(st.base[r] + p.data, it.data[r], p.data_b, hipMemcpyHostToDevice));
+            if (p.image0_b) HIPCK(c, r, hipMemcpy(st.base[r] + p.image0, it.image0[r], p.image0_b, hipMemcpyHostToDevice));
+            if (p.image1_b) HIPCK(c, r, hipMemcpy(st.base[r] + p.image1, it.image1[r], p.image1_b, hipMemcpyHostToDevice));
+            if (p.w_b) HIPCK(c, r, hipMemcpy(st.base[r] + p.w, it.w[r], p.w_b, hipMemcpyHostToDevice));
+        }
+        HIPCK(c, r, hipDeviceSynchronize());
+    }
+    // ---- the sequence: item by item, rank by rank, from this thread; device copies and kernels only ----
+    for (int i = 0; i < a->n_items; ++i) {
+        const pplhip_comm_item& it = a->items[i];
+        const CommOpPlace& p = place[i];
+        for (int r = 0; r < n; ++r) {
+            Rank& R = c->ranks[r];
+            Channel& ch = R.ch[it.channel];
+            hipStream_t s = it.channel ? R.stream2 : R.stream;
+            char* sb = st.base[r];
+            HIPCK(c, r, hipSetDevice(R.device));
+            for (int k = 0; it.skew && k < it.skew[r]; ++k)
+                HIPCK(c, r, hipMemcpyAsync(sb + COMM_OP_SKEW_BYTES, sb, COMM_OP_SKEW_BYTES, hipMemcpyDeviceToDevice, s));
+            // epoch_advance in steps of at most P2P_FLAG_REFRESH_EPOCHS: the counter gets there the way counting would take it, the
+            // refresh of idle blocks' flag words included
+            for (uint32_t left = it.epoch_advance; left;) {
+                const uint32_t step = std::min(left, P2P_FLAG_REFRESH_EPOCHS);
+                ch.p2p_epoch += step;
+                left -= step;
+                if (int rc = p2p_refresh_if_due(c, r, ch, s)) return rc;
+            }
+            uint32_t ep = 0;
+            if (int rc = p2p_next_epoch(c, r, ch, s, &ep)) return rc;
+            const size_t data_off = it.channel ? R.x_part2 : R.x_part;
+            if (it.kind == PPLHIP_COMM_ALLGATHER) {
+                HIPCK(c, r, hipMemcpyAsync(R.xbase + R.x_local, sb + p.data, p.data_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, hipMemcpyAsync(R.logits, sb + p.image0, p.image0_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, launch_p2p_allgather(s, R.peers, R.global_rank, n, R.x_local, R.logits, it.rows, it.cols * 4, it.dst_stride * 4, ep,
+                                                 c->p2p_timeout_ticks, R.p2p_status));
+                HIPCK(c, r, hipMemcpyAsync(sb + p.out0, R.logits, p.image0_b, hipMemcpyDeviceToDevice, s));
+            } else if (it.kind == PPLHIP_COMM_ALLREDUCE) {
+                HIPCK(c, r, hipMemcpyAsync(R.xbase + data_off, sb + p.data, p.data_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, launch_p2p_allreduce(s, R.peers, R.global_rank, n, data_off, ch.x_scratch[ch.ar_count++ & 1], it.count, ep,
+                                                 c->p2p_timeout_ticks, R.p2p_status, ch.id));
+                HIPCK(c, r, hipMemcpyAsync(sb + p.out0, R.xbase + data_off, p.data_b, hipMemcpyDeviceToDevice, s));
+            } else {
+                const size_t img_off = it.channel ? comm_op_image_cap(c, R) : 0;
+                uint16_t* h = (uint16_t*)((char*)R.h + img_off);
+                uint16_t* xn = (uint16_t*)((char*)R.xn + img_off);
+                HIPCK(c, r, hipMemcpyAsync(R.xbase + data_off, sb + p.data, p.data_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, hipMemcpyAsync(h, sb + p.image0, p.image0_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, hipMemcpyAsync(xn, sb + p.image1, p.image1_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, launch_p2p_allreduce_norm(s, R.peers, R.global_rank, n, data_off, ch.x_scratch[ch.ar_count++ & 1], it.rows, (int)it.hidden, h,
+                                                      (const uint16_t*)(sb + p.w), it.eps, xn, ep, c->p2p_timeout_ticks, R.p2p_status, ch.id));
+                HIPCK(c, r, hipMemcpyAsync(sb + p.out0, h, p.image0_b, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, r, hipMemcpyAsync(sb + p.out1, xn, p.image1_b, hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+    comm_op_counters(c, a->counters);
+    // ---- every rank, then the status words: all of them are cleared, the first one raised is reported ----
+    for (int r = 0; r < n; ++r) {
+        Rank& R = c->ranks[r];
+        HIPCK(c, r, hipSetDevice(R.device));
+        HIPCK(c, r, hipStreamSynchronize(R.stream));
+        if (R.stream2) HIPCK(c, r, hipStreamSynchronize(R.stream2));
+    }
+    int bad_rank = -1;
+    uint32_t bad_word = 0;
+    for (int r = 0; r < n; ++r) {
+        Rank& R = c->ranks[r];
+        if (*R.p2p_status && bad_rank < 0) { bad_rank = r; bad_word = *R.p2p_status; }
+        *R.p2p_status = 0;
+    }
+    if (bad_rank >= 0)
+        return fail(c, -1, PPLHIP_DEVICE_RUNTIME_ERROR, "pplhip_comm_op: rank " + std::to_string(bad_rank) + " raised status word " + std::to_string(bad_word) +
+                    " (a wait for rank " + std::to_string((bad_word - 1) & 15) + ((bad_word - 1) & 16 ? ", end barrier," : ", start barrier,") + " ran out)");
+    for (int r = 0; r < n; ++r) {
+        Rank& R = c->ranks[r];
+        HIPCK(c, r, hipSetDevice(R.device));
+        for (int i = 0; i < a->n_items; ++i) {
+            const pplhip_comm_item& it = a->items[i];
+            const CommOpPlace& p = place[i];
+            HIPCK(c, r, hipMemcpy(it.out0[r], st.base[r] + p.out0, it.kind == PPLHIP_COMM_ALLREDUCE ? p.data_b : p.image0_b, hipMemcpyDeviceToHost));
+            if (p.image1_b) HIPCK(c, r, hipMemcpy(it.out1[r], st.base[r] + p.out1, p.image1_b, hipMemcpyDeviceToHost));
+        }
+    }
     return 0;
 }

@@ -73,7 +73,8 @@ struct Channel {
     ncclComm_t comm = nullptr;       // RCCL communicator (a communicator serialises its streams, so each channel has one)
     size_t x_scratch[2] = {0, 0};    // scratch double buffer: byte offsets inside the exchange region
     uint32_t ar_count = 0;           // all-reduces issued (which scratch buffer is next)
-    uint32_t p2p_epoch = 0;          // epoch of the channel's flag words
+    uint32_t p2p_epoch = 0;          // epoch of the channel's flag words (taken through p2p_next_epoch)
+    uint32_t refreshed_at = 0;       // the counter's value when the flag words of idle blocks were last lifted (kernels.h)
 };
 
 // What the launches of one half-batch go out with.  run_launches builds a Lane per half on its stack for every step: lane 0 = the rank's
@@ -330,6 +331,7 @@ struct Rank {
     // the collectives work in place on (part, part2) or push into (logits_gather)
     char* xbase = nullptr;
     size_t xbytes = 0, x_part = 0, x_part2 = 0, x_local = 0;  // byte offsets inside the region (the scratch pairs: Channel)
+    size_t x_slice_bytes = 0;           // room of each scratch buffer of a channel
     P2pPeers peers{};
     bool peer_ipc[P2P_MAX_RANKS] = {};  // peers.base[g] came from hipIpcOpenMemHandle (closed on destroy)
     uint32_t* p2p_status = nullptr;     // pinned host word a kernel raises when one of its bounded spins timed out
@@ -445,6 +447,9 @@ int chunk_allreduce(pplhip_ctx* c, int rank, Lane& lane, uint16_t* buf, const Ch
 // rt_comm.cc
 int p2p_connect_local(pplhip_ctx* c);
 int p2p_check(pplhip_ctx* c, int rank);
+// the epoch of the channel's next collective, which the caller launches on `s` right away (in front of it, every P2P_FLAG_REFRESH_EPOCHS
+// epochs, the refresh of the flag words that idle blocks left behind)
+int p2p_next_epoch(pplhip_ctx* c, int rank, Channel& ch, hipStream_t s, uint32_t* epoch);
 // rt_lora.cc
 void lora_build_tiles(const int32_t* row_slots, int64_t T, std::vector<LoraTile>& out);
 // rt_postproc.cc

@@ -129,6 +129,21 @@ class CommInfo(C.Structure):
                 ("dual_min_rows", C.c_int64), ("dual_max_rows", C.c_int64), ("notes", C.c_char * 512)]
 
 
+# pplhip_comm_op (test support): the direct collectives as operators
+COMM_ALLREDUCE, COMM_ALLREDUCE_NORM, COMM_ALLGATHER = 0, 1, 2
+
+
+class CommItem(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("channel", C.c_int32), ("epoch_advance", C.c_uint32), ("eps", C.c_float), ("count", C.c_int64),
+                ("rows", C.c_int64), ("hidden", C.c_int64), ("cols", C.c_int64), ("dst_stride", C.c_int64), ("data_elems", C.c_int64),
+                ("image_elems", C.c_int64), ("data", C.c_void_p), ("image0", C.c_void_p), ("image1", C.c_void_p), ("w", C.c_void_p),
+                ("skew", C.c_void_p), ("out0", C.c_void_p), ("out1", C.c_void_p)]
+
+
+class CommOpArgs(C.Structure):
+    _fields_ = [("items", C.c_void_p), ("n_items", C.c_int32), ("counters", C.c_void_p)]
+
+
 # pplhip_op_step_plan (test support): the step schedule as a pure function
 SCHED_ONE_LANE, SCHED_TWO_LANES, SCHED_TWO_CHUNKS = 0, 1, 2   # CommInfo.schedule / StepPlan.schedule
 
@@ -158,7 +173,7 @@ class StepPlan(C.Structure):
 # every symbol include/pplhip.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "pplhip_version", "pplhip_device_count", "pplhip_get_unique_id", "pplhip_init", "pplhip_destroy",
-    "pplhip_comm_export", "pplhip_comm_connect", "pplhip_comm_mode", "pplhip_comm_fused_norm", "pplhip_comm_info", "pplhip_comm_allreduce_us",
+    "pplhip_comm_export", "pplhip_comm_connect", "pplhip_comm_mode", "pplhip_comm_fused_norm", "pplhip_comm_info", "pplhip_comm_allreduce_us", "pplhip_comm_op",
     "pplhip_last_error", "pplhip_rank_load", "pplhip_rank_set_tensor", "pplhip_rank_init_synthetic", "pplhip_rank_tie_output",
     "pplhip_kv_block_bytes", "pplhip_kv_capacity", "pplhip_kv_alloc", "pplhip_kv_ptrs", "pplhip_kv_read",
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
@@ -196,6 +211,8 @@ def lib():
         L.pplhip_comm_fused_norm.argtypes = [vp]
         L.pplhip_comm_info.argtypes = [vp, i64, C.POINTER(CommInfo)]
         L.pplhip_comm_allreduce_us.argtypes = [vp, C.c_int, i64, i32, i32, C.POINTER(f32)]
+        if hasattr(L, "pplhip_comm_op"):   # (PPLHIP_LIB may name a build from before it, as below)
+            L.pplhip_comm_op.argtypes = [vp, C.POINTER(CommOpArgs)]
         L.pplhip_rank_load.argtypes = [vp, C.c_int, C.c_char_p]
         L.pplhip_rank_set_tensor.argtypes = [vp, C.c_int, C.c_char_p, vp, u64]
         L.pplhip_rank_init_synthetic.argtypes = [vp, C.c_int, u64]
@@ -466,6 +483,75 @@ class Context:
         us = C.c_float(-1.0)
         self._ck(lib().pplhip_comm_allreduce_us(self.h, rank, rows, iters, path, C.byref(us)), rank, "comm_allreduce_us")
         return None if us.value < 0 else float(us.value)
+
+    def comm_op(self, items):
+        """pplhip_comm_op: a sequence of direct collectives on every local rank -> (status, outputs, counters).  An item is a dict: kind
+        (COMM_*), channel, epoch_advance, and per kind
+          all-reduce  count, data: per rank the fp16 image of the data buffer (the first count elements are the partial sums)
+          fused form  rows, hidden, eps, data: per rank fp16 [rows, hidden], h / xn: per rank the fp16 images of the residual rows and of
+                      the normed matrix, w: per rank fp16 [hidden]
+          all-gather  rows, cols, dst_stride, data: per rank fp32 [rows, cols], target: per rank the image of the gather target
+                      (any 4-byte type)
+        and optionally skew: per rank 0 .. 64 extra device copies in front of the rank's part.  outputs[i] is the list over the ranks
+        of what the item may have written: the data buffer, (h, xn), or the target, as arrays like the images.  counters: (epoch of
+        channel 0, of channel 1, all-reduces of channel 0, of channel 1) as the call leaves them.  A non-zero status leaves outputs None;
+        last_error() has the reason."""
+        n = self.n_local
+        arr, keep, outs = (CommItem * max(1, len(items)))(), [], []
+
+        def ptrs(arrays):
+            assert len(arrays) == n
+            p = (C.c_void_p * n)(*[a.ctypes.data for a in arrays])
+            keep.append((arrays, p))
+            return C.cast(p, C.c_void_p)
+
+        def images(arrays, dtype=None):
+            a = [np.ascontiguousarray(x) if dtype is None else np.ascontiguousarray(x, dtype=dtype) for x in arrays]
+            assert all(x.size == a[0].size and x.itemsize == a[0].itemsize for x in a)
+            return a
+
+        for i, it in enumerate(items):
+            ci = arr[i]
+            ci.kind, ci.channel, ci.epoch_advance = it["kind"], it.get("channel", 0), it.get("epoch_advance", 0)
+            ci.eps = it.get("eps", 0.0)
+            data = images(it["data"])
+            ci.data, ci.data_elems = ptrs(data), data[0].size
+            if it["kind"] == COMM_ALLREDUCE:
+                assert data[0].itemsize == 2
+                ci.count = it["count"]
+                out = [np.empty_like(x) for x in data]
+                ci.out0 = ptrs(out)
+                outs.append(out)
+            elif it["kind"] == COMM_ALLREDUCE_NORM:
+                h, xn, w = images(it["h"]), images(it["xn"]), images(it["w"])
+                assert data[0].itemsize == h[0].itemsize == xn[0].itemsize == w[0].itemsize == 2 and h[0].size == xn[0].size
+                assert w[0].size == it["hidden"]
+                ci.rows, ci.hidden, ci.image_elems = it["rows"], it["hidden"], h[0].size
+                ci.image0, ci.image1, ci.w = ptrs(h), ptrs(xn), ptrs(w)
+                oh, ox = [np.empty_like(x) for x in h], [np.empty_like(x) for x in xn]
+                ci.out0, ci.out1 = ptrs(oh), ptrs(ox)
+                outs.append(list(zip(oh, ox)))
+            else:
+                tgt = images(it["target"])
+                assert data[0].itemsize == tgt[0].itemsize == 4
+                ci.rows, ci.cols, ci.dst_stride, ci.image_elems = it["rows"], it["cols"], it["dst_stride"], tgt[0].size
+                ci.image0 = ptrs(tgt)
+                out = [np.empty_like(x) for x in tgt]
+                ci.out0 = ptrs(out)
+                outs.append(out)
+            if it.get("skew") is not None:
+                sk = np.ascontiguousarray(it["skew"], dtype=np.int32)
+                assert sk.size == n
+                keep.append(sk)
+                ci.skew = sk.ctypes.data
+        counters = (C.c_uint32 * 4)()
+        args = CommOpArgs(C.cast(arr, C.c_void_p), len(items), C.cast(counters, C.c_void_p))
+        rc = lib().pplhip_comm_op(self.h, C.byref(args))
+        return rc, (outs if rc == 0 else None), tuple(counters)
+
+    def last_error(self, rank=-1):
+        msg = lib().pplhip_last_error(self.h, rank)
+        return msg.decode() if msg else ""
 
     # weights
     def set_tensor(self, rank, name, arr):
