@@ -16,7 +16,13 @@ its mutations (MUTANTS) show that the bars would catch the named bugs.
 Poison: every slab row no request owns (other layer, gap slots, spare and padding pages) holds K = GAMMA e_0 -- it scores like a
 needle against every query (every Sylvester row starts with +1) -- and V = POISON_V on every channel.
 
-Slab addressing mirrors kv_strides_of / kv_slot (oracle/llama_ref.c); fp8 rows reuse tests/kv_fp8.py.
+Slab addressing mirrors kv_strides_of / kv_slot (oracle/llama_ref.c); fp8 rows reuse tests/kv_fp8.py, int4 rows tests/kv_i4.py.
+
+int4 ('i4': 32-channel groups, 15 levels, one fp16 scale per group): F1's K rows (and the poison rows) take a power-of-two scale per
+group, so that a small integer multiple of the needle amplitude round-trips exactly -- asserted for every K row, and a prefill
+needle whose key row would not round-trip is refused (see _f1_prefill); every V row and F2's K rows take the product's own scale rule
+(8 significant bits, not a power of two).  Every code x scale is an fp16 number, so the oracle runs on the fp16 slab the int4 slab
+stands for, with exact operands.
 """
 import ctypes as C
 import math
@@ -25,11 +31,12 @@ import numpy as np
 
 from oracle import ref
 from tests import kv_fp8 as F8
+from tests import kv_i4 as I4
 
 GAP = 160.0            # F1: the needle's scaled score beats every other visible key by at least this (e^-160 == 0 in fp32)
 GAMMA = 32768.0        # poison K on channel 0
 POISON_V = 2048.0      # poison V on every channel
-MAX_MULT = 6           # F1 needle multipliers 1..6 (fp8: integers <= 16 are exact e4m3 numbers, int8: codes <= 127)
+MAX_MULT = 6           # F1 needle multipliers 1..6 (fp8: integers <= 16 are exact e4m3 numbers, int8: codes <= 127, int4: <= 7)
 RISE_STEP, RISE_RAMP, RISE_MIN = 8.0, 2.0, 5.0   # F2 'rising': level step per 64-key tile, ramp inside a tile, asserted rise
 
 # kernel parameters the needle positions must straddle (csrc)
@@ -57,12 +64,14 @@ def gqa_form(fmt, H, Hkv, D):
     grp = H // Hkv
     if grp < 4 or grp > 16 or H % Hkv:
         return False
+    if fmt == "i4":
+        return D == 128
     return D in (64, 128) if fmt != "f16" else D in (32, 64, 128)
 
 
 def dec_key_step(fmt, D, threads=256):
     """keys per wave step and per block step of the multi-head decode kernel (AttnCfg, k_attn_dev.h)"""
-    lpt = D // (16 // (1 if fmt != "f16" else 2))
+    lpt = D // (32 if fmt == "i4" else 16 // (1 if fmt != "f16" else 2))   # int4: a lane piece is one group of 32 channels
     tpw = 64 // lpt
     nw = max(threads, D) // 64
     return tpw * DEC_UNROLL, nw * tpw * DEC_UNROLL
@@ -111,9 +120,10 @@ def view5(flat, layout, N, L, h, d):
     return flat.reshape(L, 2, h, N, d)
 
 
-def encode(fmt, x):
+def encode(fmt, x, pow2=False):
     """float rows [..., D] -> (codes, scales): fp16 values; int8 codes with one power-of-two fp16 scale per 8 channels (code x scale is
-    an fp16 number); fp8 e4m3 codes with the row's power-of-two scale (tests/kv_fp8.py)"""
+    an fp16 number); fp8 e4m3 codes with the row's power-of-two scale (tests/kv_fp8.py); int4 nibbles packed into [..., D / 2] bytes
+    with one fp16 scale per 32 channels: the product's rule (tests/kv_i4.py), or with pow2 the power of two 2^ceil(log2(amax / 7))"""
     x = np.asarray(x, dtype=np.float32)
     D = x.shape[-1]
     if fmt == "f16":
@@ -126,14 +136,34 @@ def encode(fmt, x):
         s = np.ldexp(np.float32(1.0), e.astype(np.int32))
         codes = np.clip(np.rint(g / s[..., None]), -127, 127).astype(np.int8)
         return codes.reshape(x.shape), s.astype(np.float16)
+    if fmt == "i4":
+        if not pow2:
+            q, s = I4.quantize_groups(x.astype(np.float16))
+            return I4.pack_nibbles(q).view(np.int8), s
+        g = x.reshape(x.shape[:-1] + (D // I4.GROUP, I4.GROUP))
+        amax = np.abs(g).max(-1)
+        e = np.ceil(np.log2(np.maximum(amax, 1e-30) / 7.0))
+        e = np.where(amax == 0, -14.0, np.clip(e, -14, 13))   # within the product's scale range [2^-14, 9344]
+        s = np.ldexp(np.float32(1.0), e.astype(np.int32))
+        q = np.clip(np.rint(g / s[..., None]), -7, 7).astype(np.int8)
+        return I4.pack_nibbles(q.reshape(x.shape)).view(np.int8), s.astype(np.float16)
     q, e = F8.quantize_rows(x.astype(np.float16))
     return q.view(np.int8), F8.scale_of(e)[..., None]
 
 
-def decode(fmt, codes, scales):
-    """(codes, scales) -> float64 rows"""
+def decode(fmt, codes, scales, i4_mut=None):
+    """(codes, scales) -> float64 rows; i4_mut: an int4 slab read wrongly ('nibble_order': low and high nibble swapped, 'bias8': the
+    + 8 of the stored nibble left in)"""
     if fmt == "f16":
         return codes.astype(np.float64)
+    if fmt == "i4":
+        q = I4.unpack_nibbles(codes).astype(np.float64)
+        if i4_mut == "nibble_order":
+            q = q.reshape(q.shape[:-1] + (-1, 2))[..., ::-1].reshape(q.shape)
+        if i4_mut == "bias8":
+            q = q + 8.0
+        g = q.reshape(q.shape[:-1] + (scales.shape[-1], I4.GROUP))
+        return (g * scales.astype(np.float64)[..., None]).reshape(q.shape)
     D = codes.shape[-1]
     if fmt == "i8":
         g = codes.astype(np.float64).reshape(codes.shape[:-1] + (D // 8, 8))
@@ -208,15 +238,16 @@ class Case:
         """the slab, all poison; the step's qkv rows (zero)"""
         D, Hkv, L, N, H = self.D, self.Hkv, self.L, self.N, self.H
         elems = N * L * 2 * Hkv * D
-        gsz = 8 if self.fmt == "i8" else D
-        self.cache = np.zeros(elems, dtype=np.float16 if self.fmt == "f16" else np.int8)
+        gsz = 8 if self.fmt == "i8" else (I4.GROUP if self.fmt == "i4" else D)
+        dw = D // 2 if self.fmt == "i4" else D   # slab elements per head row (int4: two channels per byte)
+        self.cache = np.zeros(elems // D * dw, dtype=np.float16 if self.fmt == "f16" else np.int8)
         self.scale = None if self.fmt == "f16" else np.zeros(elems // gsz, dtype=np.float16)
-        self.cv = view5(self.cache, self.layout, N, L, Hkv, D)
+        self.cv = view5(self.cache, self.layout, N, L, Hkv, dw)
         self.sv = None if self.scale is None else view5(self.scale, self.layout, N, L, Hkv, D // gsz)
         pk = np.zeros(D, dtype=np.float32)
         pk[0] = GAMMA
         for kv, row in ((0, pk), (1, np.full(D, POISON_V, dtype=np.float32))):
-            c, sc = encode(self.fmt, row)
+            c, sc = encode(self.fmt, row, pow2=True)   # (int4: GAMMA = 4 x 2^13 and POISON_V = 4 x 2^9 exactly)
             self.cv[:, kv] = c
             if self.sv is not None:
                 self.sv[:, kv] = sc
@@ -224,12 +255,17 @@ class Case:
         self.Kd, self.Vd = [], []
 
     def _put(self, b, K, V):
-        """writes request b's rows into the slab; returns their dequantised values (float32: fp16 numbers in every format)"""
+        """writes request b's rows into the slab; returns their dequantised values (float32: fp16 numbers in every format).
+        int4: F1's K rows take power-of-two scales and must round-trip exactly; V and F2's K take the product's scale rule"""
         H, Hkv, D = self.H, self.Hkv, self.D
         sl = self.slots(b, np.arange(self.kvlen[b]))
         deq = []
         for kv, rows in ((0, K), (1, V)):
-            c, sc = encode(self.fmt, rows)
+            exact = self.fmt == "i4" and kv == 0 and self.family is None
+            c, sc = encode(self.fmt, rows, pow2=exact)
+            if exact:
+                bad = np.argwhere((decode(self.fmt, c, sc) != rows).any(-1))
+                assert len(bad) == 0, f"{self.name}: request {b}: K rows (kv head, key) {bad[:4].tolist()} do not round-trip through int4"
             self.cv[self.layer, kv][:, sl] = c
             if self.sv is not None:
                 self.sv[self.layer, kv][:, sl] = sc
@@ -256,16 +292,16 @@ class Case:
         self._set_q()
         return self
 
-    def read(self, kv, hk, slots, scale_from=None, group_shift=False):
+    def read(self, kv, hk, slots, scale_from=None, group_shift=False, i4_mut=None):
         """dequantised slab rows of layer self.layer (float64); scale_from: read the scales of K (0) instead; group_shift: each
-        int8 group takes its neighbour's scale"""
+        int8 / int4 group takes its neighbour's scale; i4_mut: see decode"""
         c = self.cv[self.layer, kv][hk, slots]
         if self.sv is None:
             return c.astype(np.float64)
         s = self.sv[self.layer, kv if scale_from is None else scale_from][hk, slots]
         if group_shift:
             s = s[..., np.arange(s.shape[-1]) ^ 1]
-        return decode(self.fmt, c, s)
+        return decode(self.fmt, c, s, i4_mut)
 
     # ---------------------------------------------------------------- the oracle
     def desc(self):
@@ -275,10 +311,12 @@ class Case:
                              cache_layout=self.layout, cache_mode=self.mode, page_size=self.page_size)
 
     def oracle(self):
-        """ref_attention (fp32, oracle/llama_ref.c) on the slab; fp8: on the fp16 slab it stands for"""
+        """ref_attention (fp32, oracle/llama_ref.c) on the slab; fp8 and int4: on the fp16 slab it stands for"""
         d = self.desc()
         if self.fmt == "f8":
             cache, scale = F8.fp8_to_slab(self.cache, self.scale, self.D), None
+        elif self.fmt == "i4":
+            cache, scale = I4.i4_to_slab(self.cache, self.scale, self.D), None
         else:
             cache, scale = self.cache, self.scale
         q32 = np.ascontiguousarray(self.qkv.astype(np.float32))
@@ -294,6 +332,8 @@ class Case:
         v.max_tokens, v.num_layers, v.kv_heads, v.head_dim = self.N, self.L, self.Hkv, self.D
         qb = 0 if self.fmt == "f16" else 8
         v.quant_bit, v.quant_group = qb, (8 if self.fmt == "i8" else (self.D if self.fmt == "f8" else 1))
+        if self.fmt == "i4":
+            v.quant_bit, v.quant_group = 4, I4.GROUP
         v.layout, v.mode, v.page_size, v.layer = self.layout, self.mode, self.page_size, self.layer
         return v
 
@@ -356,9 +396,16 @@ def dirs_of(case, hq):
 # -------------------------------------------------------------------------------------------------------------------------------------
 # F1: exact needles
 # -------------------------------------------------------------------------------------------------------------------------------------
+def _group_factor(case):
+    """per-channel magnitude of V: neighbouring quant groups (int8: 8 channels, int4: 32) differ, so a neighbour's scale shows"""
+    gsz = {"i8": 8, "i4": I4.GROUP}.get(case.fmt)
+    return np.where((np.arange(case.D) // gsz) % 2 == 1, 0.3, 1.0) if gsz else np.ones(case.D)
+
+
 def _f1_values(case, n):
-    """distinct V rows; int8: odd groups smaller, so that neighbouring groups take different power-of-two scales"""
-    f = np.where((np.arange(case.D) // 8) % 2 == 1, 0.3, 1.0) if case.fmt == "i8" else np.ones(case.D)
+    """distinct V rows; int8: odd groups smaller, so that neighbouring groups take different power-of-two scales; int4: likewise
+    per 32 channels (product-rule scales)"""
+    f = _group_factor(case)
     return (case.rng.uniform(-3, 3, size=(case.Hkv, n, case.D)) * f).astype(np.float32)
 
 
@@ -436,10 +483,16 @@ def _f1_decode(case, b, Hd, a):
         case.needles_b[b].add(p)
 
 
+def _i4_exact(row):
+    """does a K row survive the int4 encoder with power-of-two scales unchanged?"""
+    return bool((decode("i4", *encode("i4", row, pow2=True)) == row).all())
+
+
 def _f1_prefill(case, b, Hd, a):
     """rows cycle through the head's directions; every direction gets a needle no later than its first row; rows at edge positions
     get a needle on their own diagonal key or a probe (a stronger needle one key past them) -- alternately -- while the direction
-    has multipliers left"""
+    has multipliers left.  int4: a needle whose key row would not round-trip is refused (put); a direction's first needle then
+    moves on to the next prefix edge or the row's own key"""
     s0, S, n = int(case.start_pos[b]), int(case.seqlens[b]), int(case.kvlen[b])
     st = case.edge_strides()
     edges = set(edge_positions(n, st + [PF_BM, 128, 256], (), case.rng))
@@ -460,6 +513,9 @@ def _f1_prefill(case, b, Hd, a):
         def put(d, p):
             if mult[d] >= MAX_MULT or p in used[d] or p >= n:
                 return False
+            # int4: the key row may already carry needles of other heads and directions; refuse a sum that 15 levels cannot hold
+            if case.fmt == "i4" and not _i4_exact(case.K[b][hk, p] + (mult[d] + 1) * a * Hd[d]):
+                return False
             mult[d] += 1
             used[d].add(p)
             case.K[b][hk, p] += mult[d] * a * Hd[d]
@@ -471,7 +527,11 @@ def _f1_prefill(case, b, Hd, a):
             d = ds[(i // run) % len(ds)]
             case.Q[t, hq] = Hd[d]
             if mult[d] == 0:     # first row of this direction: a needle in the cached prefix (at an edge) or on its own diagonal
-                if prefix and (k_pref % 3 != 2):
+                if case.fmt == "i4":   # a refused key falls through to the next prefix edges, then to the row's own diagonal key
+                    cands = [prefix[(k_pref + j) % len(prefix)] for j in range(len(prefix))] if prefix and (k_pref % 3 != 2) else []
+                    assert any(put(d, c) for c in cands + [p]), f"{case.name}: request {b} head {hq} row {i}: no needle fits int4"
+                    k_pref += 1
+                elif prefix and (k_pref % 3 != 2):
                     put(d, prefix[k_pref % len(prefix)])
                     k_pref += 1
                 else:
@@ -590,8 +650,8 @@ def f2(case, family):
         ds = [dirs_of(case, gi)[b % (D // grp)] for gi in range(grp)]
         for hk in range(case.Hkv):
             case.K[b][hk] = (sig.T @ Hd[ds] / math.sqrt(D)).astype(np.float32)
-        # V: |V| <= 3 with a non-zero mean; int8: odd groups smaller (different power-of-two scales)
-        f = np.where((np.arange(D) // 8) % 2 == 1, 0.3, 1.0) if case.fmt == "i8" else np.ones(D)
+        # V: |V| <= 3 with a non-zero mean; int8 / int4: odd groups smaller (different scales)
+        f = _group_factor(case)
         V = np.clip(0.8 + 0.9 * rng.randn(case.Hkv, n, D), -3, 3) * f
         for p in spec:
             V[:, p] = np.clip(-1.0 + 1.2 * rng.randn(case.Hkv, D), -3, 3) * f
@@ -626,7 +686,9 @@ def check_rising(case):
 # the float64 reference and its mutations
 # -------------------------------------------------------------------------------------------------------------------------------------
 MUTANTS = ["scale*1.01", "scale*0.99", "drop_last", "drop_first", "future_key", "slot+1@edge", "slot-1@edge", "page_swap",
-           "wrong_kv_head", "v_scale", "split_drop", "split_nomax"]
+           "wrong_kv_head", "v_scale", "split_drop", "split_nomax", "nibble_order", "bias8"]
+# the last two are int4's own: low and high nibble swapped in K and V; the + 8 of the stored nibble not taken out of K's score and
+# out of V.  (v_scale under int4: every 32-channel group takes its neighbour's scale; not at head_dim 32, which has one group.)
 # what each family is built to catch.  'rising' puts nearly all the mass on the newest tile by design (check_rising: every tile lifts
 # the maximum by >= 5, which drives the rescale and the split merges); the scores inside that tile span only 2 units, so a 1 %
 # scale error moves the output little, and key 0 and the edge slots far behind carry no weight.
@@ -670,8 +732,11 @@ def ref64(case, mut=None, edge=None):
         return None
     if mut == "page_swap" and case.mode == 0:
         return None
-    if mut == "v_scale" and case.fmt == "f16":
+    if mut == "v_scale" and (case.fmt == "f16" or (case.fmt == "i4" and D == I4.GROUP)):
         return None
+    if mut in ("nibble_order", "bias8") and case.fmt != "i4":
+        return None
+    i4_mut = mut if mut in ("nibble_order", "bias8") else None
     if mut in ("split_drop", "split_nomax") and not any(case.chunks(b, 0) and len(case.chunks(b, 0)) > 1 for b in range(case.B)):
         return None
     q = case.qkv[:, :H * D].astype(np.float64).reshape(case.T, H, D)
@@ -694,9 +759,9 @@ def ref64(case, mut=None, edge=None):
             sl[edge] = max(0, min(case.N - 1, sl[edge] + (1 if mut == "slot+1@edge" else -1)))
         for hk in range(case.Hkv):
             hr = (hk + 1) % case.Hkv if mut == "wrong_kv_head" else hk
-            K = case.read(0, hr, sl)
+            K = case.read(0, hr, sl, i4_mut=i4_mut)
             V = case.read(1, hr, sl, scale_from=0 if (mut == "v_scale" and case.fmt == "f8") else None,
-                          group_shift=(mut == "v_scale" and case.fmt == "i8"))
+                          group_shift=(mut == "v_scale" and case.fmt in ("i8", "i4")), i4_mut=i4_mut)
             rows = np.arange(S)
             vis_hi = s0 + rows + (1 if mut == "future_key" else 0)            # last visible key
             kk = np.arange(nk)[None, :]
@@ -796,6 +861,38 @@ def f1_decode_specs():
             specs.append(dict(name=f"{tag}_{fmt}_{H}x{Hkv}x128_s{split}_l3m1p{ps}", fmt=fmt, H=H, Hkv=Hkv, D=128, seqlens=[1] * len(kv),
                               start_pos=[n - 1 for n in kv], nb=len(kv), layout=3, mode=1, page_size=ps, split=split, seed=k))
             k += 1
+    return specs + _f1_decode_specs_i4()
+
+
+def _f1_decode_specs_i4():
+    """the int4 pass, with a counter of its own (the seeds and layouts of the specs above do not move).  int4 reaches the grouped-query
+    kernel at head_dim 128 only: groups 6 and 16 at head_dim 64 run the multi-head kernel"""
+    specs = []
+    k = 200
+    common = dict(fmt="i4", seqlens=[1] * len(DEC_KV), start_pos=[n - 1 for n in DEC_KV], nb=len(DEC_KV))
+    for H, Hkv, D in ((4, 4, 32), (4, 4, 64), (4, 4, 128), (8, 4, 128)):
+        for split in (1, 3, 8):
+            layout, mode = LAYOUT_MODES[k % len(LAYOUT_MODES)]
+            ps = 64 if k % 3 == 2 else 16
+            specs.append(dict(name=f"dec_i4_{H}x{Hkv}x{D}_s{split}_l{layout}m{mode}p{ps}", H=H, Hkv=Hkv, D=D, layout=layout, mode=mode,
+                              page_size=ps, split=split, seed=k, **common))
+            k += 1
+    for H, Hkv, D in ((8, 2, 128), (12, 2, 64), (8, 1, 128), (16, 1, 64)):
+        tag = "gqa_i4" if gqa_form("i4", H, Hkv, D) else f"dec_i4_g{H // Hkv}"
+        for split in (1, 3):
+            layout, mode = LAYOUT_MODES[k % len(LAYOUT_MODES)]
+            specs.append(dict(name=f"{tag}_{H}x{Hkv}x{D}_s{split}_l{layout}m{mode}", H=H, Hkv=Hkv, D=D, layout=layout, mode=mode,
+                              page_size=16, split=split, seed=k, **common))
+            k += 1
+    kv = [int(x) for x in np.random.RandomState(7).randint(1, 600, size=128)] + [1100, 2049]
+    specs.append(dict(name="gqa_small_i4", fmt="i4", H=16, Hkv=2, D=128, seqlens=[1] * len(kv), start_pos=[n - 1 for n in kv],
+                      nb=len(kv), layout=3, mode=1, page_size=16, split=2, seed=k))
+    k += 1
+    for tag, H, Hkv, ps, split, kv in (("dec", 8, 8, 2, 1, ODD_KV), ("dec", 8, 8, 12, 3, ODD_KV),
+                                       ("gqa", 8, 1, 8, 2, ODD_KV + [1100]), ("gqa", 8, 2, 12, 1, ODD_KV)):
+        specs.append(dict(name=f"{tag}_i4_{H}x{Hkv}x128_s{split}_l3m1p{ps}", fmt="i4", H=H, Hkv=Hkv, D=128, seqlens=[1] * len(kv),
+                          start_pos=[n - 1 for n in kv], nb=len(kv), layout=3, mode=1, page_size=ps, split=split, seed=k))
+        k += 1
     return specs
 
 
@@ -804,31 +901,39 @@ def f1_prefill_specs():
     specs = []
     k = 0
     for fmt in ("f16", "i8", "f8"):
-        for H, Hkv, D in ((4, 4, 32), (8, 2, 64)):
-            layout, mode = LAYOUT_MODES[k % len(LAYOUT_MODES)]
-            specs.append(dict(name=f"pf16_{fmt}_{H}x{Hkv}x{D}_l{layout}m{mode}", fmt=fmt, H=H, Hkv=Hkv, D=D, seqlens=[1, 1, 130, 64, 300],
-                              start_pos=[40, 5, 0, 64, 1000], nb=2, layout=layout, mode=mode, page_size=16, seed=k))
-            k += 1
-        # odd page sizes: 5 (the two keys of a staging item no longer share a page) and 12 (no shift addressing)
-        for ps in (5, 12):
-            specs.append(dict(name=f"pf16_{fmt}_8x2x64_l3m1p{ps}", fmt=fmt, H=8, Hkv=2, D=64, seqlens=[1, 1, 130, 64, 300],
-                              start_pos=[40, 5, 0, 64, 500], nb=2, layout=3, mode=1, page_size=ps, seed=k + 10 + ps))
-        specs.append(dict(name=f"p32_{fmt}_4x2x128_l3m1p12", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[1, 1, 130, 64, 300],
-                          start_pos=[40, 5, 0, 64, 500], nb=2, layout=3, mode=1, page_size=12, seed=k + 30))
-        specs.append(dict(name=f"p32w4_{fmt}", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[300, 129, 5, 200], start_pos=[0, 900, 70, 3000],
-                          nb=0, layout=3, mode=1, page_size=16, seed=k))
-        specs.append(dict(name=f"p32w8_{fmt}", fmt=fmt, H=4, Hkv=1, D=128, seqlens=[1100, 37], start_pos=[0, 2000], nb=0, layout=3,
-                          mode=0, seed=k + 1))
-        specs.append(dict(name=f"p32split_{fmt}", fmt=fmt, H=2, Hkv=2, D=128, seqlens=[300], start_pos=[1800], nb=0, layout=3,
-                          mode=1, page_size=16, seed=k + 2, ws=True))
-        specs.append(dict(name=f"p32split_behind_decode_{fmt}", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[1, 1, 1, 100],
-                          start_pos=[1500, 1200, 3000, 4000], nb=3, layout=3, mode=1, page_size=16, seed=k + 3, ws=True))
-        k += 4
+        specs += _f1_prefill_specs_of(fmt, k)
+        k += 6
+    return specs + _f1_prefill_specs_of("i4", 200)   # int4: a pass of its own, the counter above does not move
+
+
+def _f1_prefill_specs_of(fmt, k):
+    """the nine prefill specs of one format; k: the format's first seed / layout counter"""
+    specs = []
+    for H, Hkv, D in ((4, 4, 32), (8, 2, 64)):
+        layout, mode = LAYOUT_MODES[k % len(LAYOUT_MODES)]
+        specs.append(dict(name=f"pf16_{fmt}_{H}x{Hkv}x{D}_l{layout}m{mode}", fmt=fmt, H=H, Hkv=Hkv, D=D, seqlens=[1, 1, 130, 64, 300],
+                          start_pos=[40, 5, 0, 64, 1000], nb=2, layout=layout, mode=mode, page_size=16, seed=k))
+        k += 1
+    # odd page sizes: 5 (the two keys of a staging item no longer share a page) and 12 (no shift addressing)
+    for ps in (5, 12):
+        specs.append(dict(name=f"pf16_{fmt}_8x2x64_l3m1p{ps}", fmt=fmt, H=8, Hkv=2, D=64, seqlens=[1, 1, 130, 64, 300],
+                          start_pos=[40, 5, 0, 64, 500], nb=2, layout=3, mode=1, page_size=ps, seed=k + 10 + ps))
+    specs.append(dict(name=f"p32_{fmt}_4x2x128_l3m1p12", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[1, 1, 130, 64, 300],
+                      start_pos=[40, 5, 0, 64, 500], nb=2, layout=3, mode=1, page_size=12, seed=k + 30))
+    specs.append(dict(name=f"p32w4_{fmt}", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[300, 129, 5, 200], start_pos=[0, 900, 70, 3000],
+                      nb=0, layout=3, mode=1, page_size=16, seed=k))
+    specs.append(dict(name=f"p32w8_{fmt}", fmt=fmt, H=4, Hkv=1, D=128, seqlens=[1100, 37], start_pos=[0, 2000], nb=0, layout=3,
+                      mode=0, seed=k + 1))
+    specs.append(dict(name=f"p32split_{fmt}", fmt=fmt, H=2, Hkv=2, D=128, seqlens=[300], start_pos=[1800], nb=0, layout=3,
+                      mode=1, page_size=16, seed=k + 2, ws=True))
+    specs.append(dict(name=f"p32split_behind_decode_{fmt}", fmt=fmt, H=4, Hkv=2, D=128, seqlens=[1, 1, 1, 100],
+                      start_pos=[1500, 1200, 3000, 4000], nb=3, layout=3, mode=1, page_size=16, seed=k + 3, ws=True))
     return specs
 
 
 F1_CONFIG4 = dict(name="config4_i8", fmt="i8", H=8, Hkv=1, D=128, seqlens=[1] * 256, start_pos=[1999] * 256, nb=256, layout=3,
                   mode=1, page_size=16, L=1, layer=0, seed=44)
+F1_CONFIG4_I4 = dict(F1_CONFIG4, name="config4_i4", fmt="i4", seed=244)
 # config 2's decode launch: 1024 requests x 32 heads x kv 512-537, int8, 16-token pages shuffled over a ~557k-token slab whose V half
 # starts past 2^31 elements (64-bit slot arithmetic); built request by request (f1_stream)
 _KV2 = np.random.RandomState(42).randint(512, 538, size=1024)
@@ -848,6 +953,22 @@ F2_SPECS = [
     ("sink", dict(name="f2_pf_sink_f16_pf16", fmt="f16", H=4, Hkv=2, D=64, seqlens=[1, 200], start_pos=[900, 1000], nb=1, layout=3,
                   mode=0, seed=3)),
     ("rising", dict(name="f2_pf_rising_f16_p32", fmt="f16", H=2, Hkv=1, D=128, seqlens=[1100], start_pos=[0], nb=0, layout=3, mode=1,
+                    seed=3)),
+    # int4 (K by the product's scale rule): every family on decode and on prefill.  The rising cases keep one head per kv head: a K
+    # row is then a single +-1 direction times its score, which 15 levels hold to the scale's 8 bits however large the score
+    ("compete", dict(name="f2_dec_compete_i4_mha", fmt="i4", H=4, Hkv=4, D=128, seqlens=[1] * 3, start_pos=[699, 2047, 4096], nb=3,
+                     layout=3, mode=1, split=3, seed=3)),
+    ("sink", dict(name="f2_dec_sink_i4_gqa", fmt="i4", H=8, Hkv=1, D=128, seqlens=[1] * 3, start_pos=[1023, 4095, 7999], nb=3,
+                  layout=3, mode=1, split=8, seed=3)),
+    ("compete", dict(name="f2_dec_compete_i4_gqa", fmt="i4", H=8, Hkv=2, D=128, seqlens=[1] * 3, start_pos=[699, 2047, 4096], nb=3,
+                     layout=3, mode=1, split=3, seed=3)),
+    ("rising", dict(name="f2_dec_rising_i4_mha", fmt="i4", H=2, Hkv=2, D=64, seqlens=[1] * 2, start_pos=[2999, 8191], nb=2, layout=0,
+                    mode=0, split=8, seed=3)),
+    ("compete", dict(name="f2_pf_compete_i4_splitkv", fmt="i4", H=2, Hkv=2, D=128, seqlens=[300], start_pos=[1800], nb=0, layout=3,
+                     mode=1, seed=3, ws=True)),
+    ("sink", dict(name="f2_pf_sink_i4_pf16", fmt="i4", H=4, Hkv=2, D=64, seqlens=[1, 200], start_pos=[900, 1000], nb=1, layout=3,
+                  mode=0, seed=3)),
+    ("rising", dict(name="f2_pf_rising_i4_p32", fmt="i4", H=2, Hkv=2, D=128, seqlens=[1100], start_pos=[0], nb=0, layout=3, mode=1,
                     seed=3)),
 ]
 

@@ -1,6 +1,7 @@
 """CPU specification of the sharp attention inputs (tests/attn_sharp.py) that tests/test_gpu_attn_sharp.py runs on the device:
 F1 cases are exact gathers (the oracle agrees bit for bit), the float64 reference agrees with the oracle on F2 cases, every F2 case
-catches the named mutations at >= 4 x the bar the GPU test uses, and the F1 needles straddle at least one edge of every kind."""
+catches the named mutations at >= 4 x the bar the GPU test uses, and the F1 needles straddle at least one edge of every kind.
+Formats: fp16, int8-g8, fp8 and int4-g32; the int4 cases also show that their queries reach the format's own corrections."""
 import numpy as np
 import pytest
 
@@ -65,6 +66,46 @@ def test_f2_mutants_have_teeth(capsys):
     with capsys.disabled():
         print("\n" + "\n".join(lines))
     assert not fails, fails
+
+
+I4_F1_SPECS = [s for s in A.f1_decode_specs() + A.f1_prefill_specs() + [A.F1_CONFIG4_I4] if s["fmt"] == "i4"]
+
+
+@pytest.mark.parametrize("spec", I4_F1_SPECS, ids=lambda s: s["name"])
+def test_f1_i4_queries_reach_the_corrections(spec):
+    """int4 folds the + 8 of a stored nibble out of the score as 8 * sum(q) per 32-channel group, and packs two channels per byte:
+    some needle query sums to non-zero over a group (a Hadamard row d with d & 31 == 0; every other row sums to 0 over every group and
+    would hide a wrong correction), and some has an odd direction index (q[2j + 1] = -q[2j]: swapped nibbles negate its score).
+    Every K row of the case round-trips through the encoder exactly (asserted while the slab is written)."""
+    c = A.make(spec)
+    D = c.D
+    Hd = A.hadamard(D)
+    q = c.Q.reshape(-1, D).astype(np.float64)
+    d = (q @ Hd.T).argmax(-1)
+    assert (Hd[d] == q).all(), "a query is not a Hadamard row"
+    gsum = q.reshape(-1, D // 32, 32).sum(-1)
+    assert (gsum != 0).any(), "no query sums to non-zero over a 32-channel group"
+    assert ((gsum != 0).any(-1) == (d & 31 == 0)).all()
+    assert (d & 1 == 1).any(), "no query with an odd direction index"
+    if not getattr(c, "streamed", False):
+        for b in range(c.B):   # (redundant with the assertion in Case._put; kept where the property is stated)
+            k = c.read(0, np.arange(c.Hkv)[:, None], c.slots(b, np.arange(c.kvlen[b]))[None, :])
+            assert all(A._i4_exact(row) for row in k[np.abs(k).max(-1) > 0])
+
+
+def test_f1_config4_i4_is_a_gather():
+    """config 4's decode launch on the int4 cache (the grouped-query kernel): an exact gather the oracle reproduces bit for bit"""
+    assert A.F1_CONFIG4_I4["fmt"] == "i4" and A.gqa_form("i4", A.F1_CONFIG4_I4["H"], A.F1_CONFIG4_I4["Hkv"], A.F1_CONFIG4_I4["D"])
+    _gather_equals_oracle(A.F1_CONFIG4_I4)
+
+
+def test_i4_kernel_forms():
+    """the mirrors of the int4 dispatch and geometry: the grouped-query kernel at head_dim 128 only; a lane piece of the multi-head
+    kernel is a 32-channel group, so 16 / 32 / 64 rows per wave-load at head_dim 128 / 64 / 32 (x 4 in flight, x 4 waves)"""
+    assert A.gqa_form("i4", 8, 1, 128) and A.gqa_form("i4", 16, 2, 128)
+    assert not A.gqa_form("i4", 12, 2, 64) and not A.gqa_form("i4", 16, 1, 64) and not A.gqa_form("i4", 8, 4, 128)
+    assert [A.dec_key_step("i4", D) for D in (128, 64, 32)] == [(64, 256), (128, 512), (256, 1024)]
+    assert [A.dec_key_step("i8", D) for D in (128, 64, 32)] == [(32, 128), (64, 256), (128, 512)]
 
 
 def _pairs(pos, s):

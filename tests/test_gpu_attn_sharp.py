@@ -1,7 +1,8 @@
 """Sharp attention inputs on the device (tests/attn_sharp.py), all through pplhip_op_attention: F1 exact needles must come out as ONE
 V row, bit for bit, on every kernel form (multi-head and grouped-query decode in both block forms with their reduce, the 16-row and
-32-row prefill kernels, split-KV prefill) x fp16 / int8-g8 / fp8 x contiguous / paged x the four slab layouts; F2 sharp but
-unsaturated inputs against the oracle at the bars of tests/test_gpu_ops.py.  Every slot no request owns holds poison."""
+32-row prefill kernels, split-KV prefill) x fp16 / int8-g8 / fp8 / int4-g32 x contiguous / paged x the four slab layouts; F2 sharp but
+unsaturated inputs against the oracle at the bars of tests/test_gpu_ops.py.  Every slot no request owns holds poison.
+(int4 reaches the grouped-query kernel at head_dim 128 only; its groups 6 and 16 at head_dim 64 run the multi-head kernel.)"""
 import ctypes as C
 
 import numpy as np
@@ -61,6 +62,14 @@ def test_f1_config4_launch_shape():
     _f1(A.F1_CONFIG4)
 
 
+def test_f1_config4_i4_launch_shape():
+    """config 4's decode launch on the int4 cache: 256 requests x 8 query heads per KV head x 2000 keys, pages of 16"""
+    spec = A.F1_CONFIG4_I4
+    assert (spec["fmt"], spec["H"], spec["Hkv"], spec["D"], spec["nb"], spec["page_size"]) == ("i4", 8, 1, 128, 256, 16)
+    assert set(spec["start_pos"]) == {1999}
+    _f1(spec)
+
+
 def test_f1_config2_launch_shape():
     """config 2's decode launch: 1024 requests x 32 heads x kv 512-537, int8, pages of 16 shuffled over a slab whose V half starts
     past 2^31 elements"""
@@ -76,7 +85,8 @@ def test_f1_config2_launch_shape():
 
 @pytest.mark.parametrize("i", range(len(A.F2_SPECS)), ids=lambda i: A.F2_SPECS[i][1]["name"])
 def test_f2_against_oracle(i):
-    """sharp but unsaturated: competing keys, a sink over a long tail, a maximum rising on every tile -- at the existing bars"""
+    """sharp but unsaturated: competing keys, a sink over a long tail, a maximum rising on every tile -- at the existing bars
+    (int4 too: its operands are exact fp16 numbers, so it is held to the fp16 bars)"""
     m = load_pplhip()
     family, spec = A.F2_SPECS[i]
     c = A.make(spec, family)
