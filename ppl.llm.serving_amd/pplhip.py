@@ -811,7 +811,7 @@ class Context:
             self._ck(rc, 0, "guide_edit")
         return rc
 
-    def penalty(self, temperatures, repetition, presence, frequency, batch_slots, req_list_changed=True):
+    def penalty(self, temperatures, repetition, presence, frequency, batch_slots, req_list_changed=True, logits_ptr=None):
         a = PenaltyArgs()
         B = len(batch_slots)
         t = np.ascontiguousarray(temperatures, dtype=np.float32)
@@ -823,7 +823,9 @@ class Context:
         a.presence_penalties = None if p is None else p.ctypes.data
         a.frequency_penalties = None if f is None else f.ctypes.data
         a.batch, a.vocab_size, a.req_list_changed = B, self.desc.vocab_size, int(req_list_changed)
-        self._ck(lib().pplhip_penalty(self.h, self.logits_ptr(0)[0], C.byref(a)), 0, "penalty")
+        if logits_ptr is None:
+            logits_ptr = self.logits_ptr(0)[0]
+        self._ck(lib().pplhip_penalty(self.h, logits_ptr, C.byref(a)), 0, "penalty")
 
     # measurement
     def profile_reset(self, rank=0):

@@ -866,7 +866,9 @@ void LLMGenerator::Generate() {
                     req_list_changed_ = true;
                 }
                 if (no_top) {
+                    // the step's results hold this row's entries all the same: both cursors pass them, or the rows behind read them
                     prompt_pos += prompt_n;
+                    if (t->num_logprobs > 0 && top_row < out.top_rows) ++top_row;
                     if (guide_broken) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "guide_regex: internal error: token [" + std::to_string(tok) + "] is not allowed in state [" + std::to_string(t->guide_state) + "] of the request's guide");
                     else if (t->rule_failed) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "logit rules: the backend could not take the request's rule");
                     else if (no_prompt) conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "prompt_logprobs: the backend's runtime has no SetPromptLogprobs");
