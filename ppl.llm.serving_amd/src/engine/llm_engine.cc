@@ -1,5 +1,6 @@
 #include "llm_engine.h"
 
+#include <algorithm>
 #include <mutex>
 
 #include "../utils/utils.h"
@@ -60,6 +61,19 @@ static RetCode RunDecoder(uint32_t rank, bool is_prefix_cache_hit, const std::ve
     return rc;
 }
 
+// a failed call of the step: `what` failed with `rc` (`detail`: the backend's own words behind it); the step fails with RC_OTHER_ERROR
+static RetCode Fail(std::string* error_msg, const std::string& what, RetCode rc, const std::string& detail = "") {
+    *error_msg = what + " failed: " + GetRetCodeStr(rc) + detail;
+    LOG(ERROR) << *error_msg;
+    return RC_OTHER_ERROR;
+}
+
+// does any row of the step ask: the stages of a step nobody asks for are not called at all
+template <typename T, typename Pred>
+static bool AnyRow(const std::vector<T>& list, Pred asks) {
+    return std::any_of(list.begin(), list.end(), asks);
+}
+
 RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_prefix_cache_hit, ModelOutput* out,
                            std::string* error_msg) {
     const int32_t running_batch = (int32_t)in.start_pos.size();
@@ -80,47 +94,33 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
     // (src/engine/llm_engine.cc:63-71)
     step.cache_indices = model_config_.cache_mode == 0 ? in.cache_indices.data() : in.page_list.data();
     step.req_list_changed = req_list_changed;
-    for (int32_t s : in.lora_slots)
-        if (s >= 0) step.lora_slots = in.lora_slots.data();
-    // (a backend with adapters loads and unloads them on the same device workers: one or the other)
-    std::unique_lock<std::mutex> device_lock;
-    if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
+    if (AnyRow(in.lora_slots, [](int32_t s) { return s >= 0; })) step.lora_slots = in.lora_slots.data();
+    const auto device_lock = DeviceLock();
 
     {
         utils::TimingGuard timing(&step_counter_->current.set_input_cost);
         rc = utils::ParallelExecute(UploadInputs, device_worker_pool_, step, runtimes_);
-        if (rc != RC_SUCCESS) {
-            *error_msg = "ParallelExecute(SetInputTask) failed: " + std::string(GetRetCodeStr(rc));
-            LOG(ERROR) << *error_msg;
-            return RC_OTHER_ERROR;
-        }
+        if (rc != RC_SUCCESS) return Fail(error_msg, "ParallelExecute(SetInputTask)", rc);
     }
     step_counter_->global.set_input_cost += step_counter_->current.set_input_cost;
 
-    // prompt logprobs: the ask goes to rank 0 between its inputs and its run, only on steps in which a request asks (the generator takes a
-    // request's entry back after its first step); under tensor parallelism the backend refuses and the asking requests fail alone
-    bool prompt_asks = false;
-    for (int32_t n : in.prompt_logprobs_list) prompt_asks = prompt_asks || n >= 0;
+    // prompt logprobs: the ask goes to rank 0 between its inputs and its run, only on steps in which a request asks (the generator asks
+    // on a request's first step only); under tensor parallelism the backend refuses and the asking requests fail alone
+    bool prompt_asks = AnyRow(in.prompt_logprobs_list, [](int32_t n) { return n >= 0; });
     if (prompt_asks) {
         rc = runtimes_[0]->SetPromptLogprobs(in.prompt_logprobs_list.data(), running_batch);
         if (rc == RC_UNSUPPORTED) {
             out->prompt_unsupported = true;
             prompt_asks = false;
         } else if (rc != RC_SUCCESS) {
-            *error_msg = "SetPromptLogprobs failed: " + std::string(GetRetCodeStr(rc)) + ": " + runtimes_[0]->GetLastError();
-            LOG(ERROR) << *error_msg;
-            return RC_OTHER_ERROR;
+            return Fail(error_msg, "SetPromptLogprobs", rc, std::string(": ") + runtimes_[0]->GetLastError());
         }
     }
 
     {
         utils::TimingGuard timing(&step_counter_->current.model_forward_cost);
         rc = utils::ParallelExecute(RunDecoder, device_worker_pool_, is_prefix_cache_hit, runtimes_);
-        if (rc != RC_SUCCESS) {
-            *error_msg = "ParallelExecute(RunModelTask) failed: " + std::string(GetRetCodeStr(rc));
-            LOG(ERROR) << *error_msg;
-            return RC_OTHER_ERROR;
-        }
+        if (rc != RC_SUCCESS) return Fail(error_msg, "ParallelExecute(RunModelTask)", rc);
     }
     step_counter_->global.model_forward_cost += step_counter_->current.model_forward_cost;
 
@@ -131,57 +131,37 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
         float* logits = rt0->GetLogits(&stride);
         // guided decoding: the asking rows lose every token their automaton's state does not allow, in front of everything else that
         // reads or edits the logits; nothing on a step without an asking row
-        bool guided = false;
-        for (int32_t g : in.guide_slots) guided = guided || g >= 0;
-        if (guided) {
+        if (AnyRow(in.guide_slots, [](int32_t g) { return g >= 0; })) {
             rc = post_processor_->GuideEdit(logits, in.guide_slots.data(), in.guide_states.data(), running_batch, model_config_.vocab_size,
                                             (int32_t)stride);
-            if (rc != RC_SUCCESS) {
-                *error_msg = "GuideEdit failed: " + std::string(GetRetCodeStr(rc));
-                LOG(ERROR) << *error_msg;
-                return RC_OTHER_ERROR;
-            }
+            if (rc != RC_SUCCESS) return Fail(error_msg, "GuideEdit", rc);
         }
         // logit rules: in place and first, so a bias is in raw-logit units and the penalty, the top-N logprobs and the sampler all see
         // the edited rows; nothing on a step without a flag
-        bool edits = false;
-        for (uint32_t f : in.logit_flags) edits = edits || f != 0;
-        if (edits) {
+        if (AnyRow(in.logit_flags, [](uint32_t f) { return f != 0; })) {
             rc = post_processor_->EditLogits(logits, in.batch_slots.data(), in.logit_flags.data(), running_batch, model_config_.vocab_size,
                                              (int32_t)stride);
-            if (rc != RC_SUCCESS) {
-                *error_msg = "EditLogits failed: " + std::string(GetRetCodeStr(rc));
-                LOG(ERROR) << *error_msg;
-                return RC_OTHER_ERROR;
-            }
+            if (rc != RC_SUCCESS) return Fail(error_msg, "EditLogits", rc);
         }
         if (enable_penalty_) {
             rc = post_processor_->ApplyPenalty(in.temperatures.data(), in.repetition_penalty_list.data(), nullptr, nullptr,
                                                in.batch_slots.data(), rt0->GetTokenInputsDevice(), rt0->GetSeqStartsDevice(),
                                                rt0->GetStartPosDevice(), running_batch, model_config_.vocab_size,
                                                req_list_changed, logits);
-            if (rc != RC_SUCCESS) {
-                *error_msg = "Apply Penalty failed: " + std::string(GetRetCodeStr(rc));
-                LOG(ERROR) << *error_msg;
-                return RC_OTHER_ERROR;
-            }
+            if (rc != RC_SUCCESS) return Fail(error_msg, "Apply Penalty", rc);
         }
         // top-N logprobs: queued in front of the sampler, whose synchronisation makes the results readable; nothing on a step nobody asks in
         const int32_t* top_tok = nullptr;
         const float* top_lp = nullptr;
         int32_t top_rows = 0;
-        bool asks = false;
-        for (int32_t n : in.num_logprobs_list) asks = asks || n > 0;
-        if (asks) {
+        if (AnyRow(in.num_logprobs_list, [](int32_t n) { return n > 0; })) {
             rc = post_processor_->TopLogprobs(logits, enable_penalty_ ? nullptr : in.temperatures.data(), in.num_logprobs_list.data(),
                                               running_batch, model_config_.vocab_size, (int32_t)stride, &top_tok, &top_lp, &top_rows);
             if (rc == RC_UNSUPPORTED) {
                 out->top_unsupported = true;
                 top_rows = 0;
             } else if (rc != RC_SUCCESS) {
-                *error_msg = "TopLogprobs failed: " + std::string(GetRetCodeStr(rc));
-                LOG(ERROR) << *error_msg;
-                return RC_OTHER_ERROR;
+                return Fail(error_msg, "TopLogprobs", rc);
             }
         }
         if (per_request_sampling_) {
@@ -197,19 +177,11 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
                                                  req_list_changed, out->output_token.data(), out->logprobs.data(),
                                                  enable_penalty_);
         }
-        if (rc != RC_SUCCESS) {
-            *error_msg = std::string(per_request_sampling_ ? "SampleRows" : "SampleTopKTopP") + " failed: " + std::string(GetRetCodeStr(rc));
-            LOG(ERROR) << *error_msg;
-            return RC_OTHER_ERROR;
-        }
+        if (rc != RC_SUCCESS) return Fail(error_msg, per_request_sampling_ ? "SampleRows" : "SampleTopKTopP", rc);
         if (prompt_asks) {   // the sampler has synchronised: the step's prompt logprobs are readable
             PromptLogprobsView v;
             rc = rt0->GetPromptLogprobs(&v);
-            if (rc != RC_SUCCESS) {
-                *error_msg = "GetPromptLogprobs failed: " + std::string(GetRetCodeStr(rc));
-                LOG(ERROR) << *error_msg;
-                return RC_OTHER_ERROR;
-            }
+            if (rc != RC_SUCCESS) return Fail(error_msg, "GetPromptLogprobs", rc);
             const size_t P = (size_t)v.positions, cnt = P * PostProcessor::kTopLogprobsMax;
             if (P > 0) {
                 out->prompt_rows.assign(v.rows, v.rows + P);

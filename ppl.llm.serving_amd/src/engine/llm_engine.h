@@ -55,12 +55,12 @@ struct ModelOutput {
     std::vector<int32_t> top_tokens;
     std::vector<float> top_logprobs;
     int32_t top_rows = 0;
-    bool top_unsupported = false;
+    bool top_unsupported = false;  // a row asked and the backend has no TopLogprobs: the generator fails those requests
     // prompt logprobs of the step, ascending packed row: position i scores row prompt_rows[i]; the top arrays are
     // [positions, PostProcessor::kTopLogprobsMax]
     std::vector<int32_t> prompt_rows, prompt_ranks, prompt_top_tokens;
     std::vector<float> prompt_logprobs, prompt_top_logprobs;
-    bool prompt_unsupported = false;  // a request asked and the backend has no SetPromptLogprobs: the generator fails those requests  // a row asked and the backend has no TopLogprobs: the generator fails those requests
+    bool prompt_unsupported = false;  // a request asked and the backend has no SetPromptLogprobs: the generator fails those requests
     void Clear() {
         output_token.clear();
         logprobs.clear();
@@ -94,11 +94,7 @@ public:
         return post_processor_ && post_processor_->EditLogits(nullptr, nullptr, nullptr, 0, model_config_.vocab_size,
                                                               model_config_.vocab_size) == ppl::common::RC_SUCCESS;
     }
-    ppl::common::RetCode SetLogitRule(int64_t slot, const LogitRule& rule) {
-        std::unique_lock<std::mutex> device_lock;  // as Execute: adapters load and unload on the same device
-        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
-        return post_processor_->SetLogitRule(slot, rule);
-    }
+    ppl::common::RetCode SetLogitRule(int64_t slot, const LogitRule& rule) { auto lock = DeviceLock(); return post_processor_->SetLogitRule(slot, rule); }
 
     // guided decoding: whether the backend's post processor has it (PostProcessor::GuideEdit with batch 0), and its three set-up calls
     bool HasGuides() const {
@@ -106,22 +102,19 @@ public:
                                                              model_config_.vocab_size) == ppl::common::RC_SUCCESS;
     }
     ppl::common::RetCode SetGuideVocab(const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) {
-        std::unique_lock<std::mutex> device_lock;  // as Execute: adapters load and unload on the same device
-        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
-        return post_processor_->SetGuideVocab(bytes, offsets, n_tok);
+        auto lock = DeviceLock(); return post_processor_->SetGuideVocab(bytes, offsets, n_tok);
     }
     ppl::common::RetCode LoadGuide(int32_t slot, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens) {
-        std::unique_lock<std::mutex> device_lock;
-        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
-        return post_processor_->LoadGuide(slot, dfa, end_tokens);
+        auto lock = DeviceLock(); return post_processor_->LoadGuide(slot, dfa, end_tokens);
     }
-    ppl::common::RetCode UnloadGuide(int32_t slot) {
-        std::unique_lock<std::mutex> device_lock;
-        if (adapters_) device_lock = std::unique_lock<std::mutex>(adapters_->DeviceMutex());
-        return post_processor_->UnloadGuide(slot);
-    }
+    ppl::common::RetCode UnloadGuide(int32_t slot) { auto lock = DeviceLock(); return post_processor_->UnloadGuide(slot); }
 
 private:
+    // a backend with adapters loads and unloads them on the same device as the step and its set-up calls: one or the other at a time
+    std::unique_lock<std::mutex> DeviceLock() const {
+        return adapters_ ? std::unique_lock<std::mutex>(adapters_->DeviceMutex()) : std::unique_lock<std::mutex>();
+    }
+
     uint32_t tensor_parallel_size_;
     ppl::common::StaticThreadPool* device_worker_pool_;
     std::vector<Runtime*> runtimes_;

@@ -26,13 +26,27 @@ struct LLMGenerator::Admission {
     int64_t cache_hit_count = 0;
     int32_t running_batch = 0;
     int32_t prefill_batch = 0;
+    bool rejected = false;  // the request is invalid: it leaves the queue and StartRequest fails it with errcode / errmsg
     std::string errmsg;
     RetCode errcode = RC_INVALID_VALUE;
     bool has_rule = false;  // the request carries a logit rule: `rule` is its validated, merged form
     LogitRule rule;
     int32_t guide_slot = -1;  // the request is guided: the slot it holds a reference on
 
+    // an invalid request: true for the scheduler, so that it leaves the queue; `msg` may be errmsg itself
+    bool Reject(const std::string& msg, RetCode code = RC_INVALID_VALUE) {
+        rejected = true;
+        errmsg = msg;
+        errcode = code;
+        LOG(ERROR) << errmsg;
+        return true;
+    }
+    bool Reject(uint64_t id, const std::string& msg, RetCode code = RC_INVALID_VALUE) {
+        return Reject("id [" + std::to_string(id) + "] " + msg, code);
+    }
+
     void ResetForRequest(int prompt_len) {
+        rejected = false;
         errcode = RC_INVALID_VALUE;
         has_rule = false;
         guide_slot = -1;
@@ -56,7 +70,8 @@ LLMGenerator::LLMGenerator(const Resource& resource, const GeneratorConfig& gene
     , conn_(conn)
     , kv_cache_max_tokens_(resource.kv_cache_max_tokens)
     , llm_engine_(resource, model_config, generator_config.enable_penalty, generator_config.top_k, generator_config.top_p,
-                  generator_config.per_request_sampling) {
+                  generator_config.per_request_sampling)
+    , guide_cache_(&llm_engine_, resource.tokenizer, model_config.vocab_size) {
     if (generator_config_.per_request_sampling && generator_config_.sampling_seed == 0) {
         std::random_device rd;
         generator_config_.sampling_seed = ((uint64_t)rd() << 32) | rd();
@@ -73,9 +88,6 @@ LLMGenerator::~LLMGenerator() {
         req_signal_.NotifyOne();
         pthread_join(generate_thread_, nullptr);
     }
-    // the backend outlives the generator: its guide slots go back, so that the next generator finds them empty
-    for (int32_t i = 0; i < PostProcessor::kGuideMaxSlots; ++i)
-        if (!guides_[i].key.empty()) llm_engine_.UnloadGuide(i);
 }
 
 // reference CheckParameters, llm_generator.cc:114-144 (accepted combinations: SURVEY.md Q9)
@@ -188,12 +200,12 @@ void* LLMGenerator::GeneratorThreadFunc(void* arg) {
 
 // length clamps: reference CheckTotalLen, llm_generator.cc:441-478 (including that the total-length clamp is
 // computed from the REQUESTED generation length and may exceed max_output_tokens_per_request)
-static bool ClampLengths(const GeneratorConfig& cfg, const Request& r, int* first_fill_len, int* rest_iters, std::string* errmsg) {
+// false: the request cannot run, *errmsg says why
+static bool ClampLengths(const GeneratorConfig& cfg, const Request& r, int first_fill_len, int* rest_iters, std::string* errmsg) {
     const std::string idstr = "id [" + std::to_string(r.id) + "]";
-    if (*first_fill_len > cfg.max_input_tokens_per_request) {
-        *errmsg = idstr + " invalid input token len: " + std::to_string(*first_fill_len) +
+    if (first_fill_len > cfg.max_input_tokens_per_request) {
+        *errmsg = idstr + " invalid input token len: " + std::to_string(first_fill_len) +
                   ", server allowed max input len: " + std::to_string(cfg.max_input_tokens_per_request);
-        *first_fill_len = -1;
         return false;
     }
     *rest_iters = r.generation_length;
@@ -205,9 +217,9 @@ static bool ClampLengths(const GeneratorConfig& cfg, const Request& r, int* firs
         *rest_iters = cfg.max_output_tokens_per_request;
         if (*rest_iters <= 0) { *errmsg = msg; return false; }
     }
-    if (*first_fill_len + r.generation_length > cfg.max_total_tokens_per_request) {
-        const int clamped = cfg.max_total_tokens_per_request - *first_fill_len;
-        const std::string msg = idstr + ": total len in request is [" + std::to_string(*first_fill_len + r.generation_length) +
+    if (first_fill_len + r.generation_length > cfg.max_total_tokens_per_request) {
+        const int clamped = cfg.max_total_tokens_per_request - first_fill_len;
+        const std::string msg = idstr + ": total len in request is [" + std::to_string(first_fill_len + r.generation_length) +
                                 "] > [" + std::to_string(cfg.max_total_tokens_per_request) + "] from cmd. use [" +
                                 std::to_string(clamped) + "]";
         LOG(WARNING) << msg;
@@ -293,77 +305,7 @@ bool LLMGenerator::ReserveKv(const LlmRequest& req, Admission* adm, int32_t* coo
     return true;
 }
 
-static std::string GuideExclusion(const Request& r);
-
-// the admission predicate handed to the request scheduler (reference check_func, llm_generator.cc:590-617).
-// true  -> the request leaves the queue (either admitted, or invalid and failed by StartRequest)
-// false -> it stays at the head (stash) and admission stops for this step
-bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* cool_down, bool* is_prefix_cache_hit) {
-    adm->ResetForRequest((int)req.orig->token_ids->size());
-    // the prompt length counts against the step budget BEFORE the check and even for prefix-cache hits (SURVEY.md Q7)
-    adm->total_tokens_per_step += adm->first_fill_len;
-    if (adm->total_tokens_per_step > generator_config_.max_tokens_per_step) return false;
-    if (adm->first_fill_len == 0) {  // deviation: an empty prompt would reserve zero KV slots and feed no token
-        adm->errmsg = "id [" + std::to_string(req.orig->id) + "] empty prompt";
-        adm->first_fill_len = -1;
-        return true;
-    }
-    if (!ClampLengths(generator_config_, *req.orig, &adm->first_fill_len, &adm->rest_iters, &adm->errmsg)) {
-        LOG(ERROR) << adm->errmsg;
-        return true;
-    }
-    if (adm->rest_iters <= 0) {  // deviation: the reference reserves KV here and leaks it when StartRequest rejects
-        adm->errmsg = "id [" + std::to_string(req.orig->id) + "] generation length <= 0";
-        return true;
-    }
-    if (!req.orig->guide_regex.empty()) {
-        adm->errmsg = GuideExclusion(*req.orig);
-        if (!adm->errmsg.empty()) {
-            adm->errmsg = "id [" + std::to_string(req.orig->id) + "] " + adm->errmsg;
-            LOG(ERROR) << adm->errmsg;
-            adm->first_fill_len = -1;
-            return true;
-        }
-    }
-    if (req.orig->HasLogitRule()) {  // validated once, here; an invalid rule fails its request alone (StartRequest)
-        const Request& r = *req.orig;
-        bool ok = llm_engine_.HasLogitRules();
-        if (!ok) {
-            adm->errmsg = "logit rules: the backend's post processor has no EditLogits";
-            adm->errcode = RC_UNSUPPORTED;
-        } else {
-            std::vector<int> stops(generator_config_.stop_tokens.begin(), generator_config_.stop_tokens.end());
-            if (r.stop_tokens) stops.insert(stops.end(), r.stop_tokens->begin(), r.stop_tokens->end());
-            ok = BuildLogitRule(r.logit_bias, r.allowed_tokens.get(), r.banned_tokens, r.min_new_tokens, stops, model_config_.vocab_size,
-                                &adm->rule, &adm->errmsg);
-        }
-        if (!ok) {
-            adm->errmsg = "id [" + std::to_string(r.id) + "] " + adm->errmsg;
-            LOG(ERROR) << adm->errmsg;
-            adm->first_fill_len = -1;
-            return true;
-        }
-        adm->has_rule = true;
-    }
-    if (!req.orig->guide_regex.empty() && !AdmitGuide(*req.orig, adm)) {  // a refused guide fails its request alone (StartRequest)
-        adm->errmsg = "id [" + std::to_string(req.orig->id) + "] " + adm->errmsg;
-        LOG(ERROR) << adm->errmsg;
-        adm->first_fill_len = -1;
-        return true;
-    }
-    if (!ReserveKv(req, adm, cool_down, is_prefix_cache_hit)) {
-        ReleaseGuide(adm->guide_slot);   // the request stays queued and asks again
-        adm->guide_slot = -1;
-        return false;
-    }
-    ++adm->running_batch;
-    ++adm->prefill_batch;
-    return true;
-}
-
-// ------------------------------------------------------------------------------------------------ guided decoding
-
-// the end tokens of a request: allowed exactly where its pattern is matched in full
+// the end tokens of a guided request: allowed exactly where its pattern is matched in full
 static std::vector<int32_t> GuideEndTokens(const Tokenizer* tokenizer, const GeneratorConfig& cfg, const Request& r) {
     std::vector<int32_t> ends(cfg.stop_tokens.begin(), cfg.stop_tokens.end());
     if (r.stop_tokens) ends.insert(ends.end(), r.stop_tokens->begin(), r.stop_tokens->end());
@@ -385,99 +327,44 @@ static std::string GuideExclusion(const Request& r) {
     return "";
 }
 
-bool LLMGenerator::AdmitGuide(const Request& r, Admission* adm) {
-    adm->errcode = RC_UNSUPPORTED;
-    if (!llm_engine_.HasGuides()) { adm->errmsg = "guide_regex: the backend's post processor has no GuideEdit"; return false; }
-    std::string bytes;
-    if (!tokenizer_ || !tokenizer_->TokenBytes(0, &bytes)) {
-        adm->errmsg = "guide_regex: needs a tokenizer that knows the bytes of its tokens (TokenBytes)";
+// the admission predicate handed to the request scheduler (reference check_func, llm_generator.cc:590-617).
+// true  -> the request leaves the queue (either admitted, or invalid and failed by StartRequest)
+// false -> it stays at the head (stash) and admission stops for this step
+bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* cool_down, bool* is_prefix_cache_hit) {
+    adm->ResetForRequest((int)req.orig->token_ids->size());
+    // the prompt length counts against the step budget BEFORE the check and even for prefix-cache hits (SURVEY.md Q7)
+    adm->total_tokens_per_step += adm->first_fill_len;
+    if (adm->total_tokens_per_step > generator_config_.max_tokens_per_step) return false;
+    const Request& r = *req.orig;
+    if (adm->first_fill_len == 0) return adm->Reject(r.id, "empty prompt");  // deviation: it would reserve zero KV slots and feed no token
+    if (!ClampLengths(generator_config_, r, adm->first_fill_len, &adm->rest_iters, &adm->errmsg)) return adm->Reject(adm->errmsg);
+    // deviation: the reference reserves KV here and leaks it when StartRequest rejects
+    if (adm->rest_iters <= 0) return adm->Reject(r.id, "generation length <= 0");
+    const bool guided = !r.guide_regex.empty();
+    const std::string excluded = guided ? GuideExclusion(r) : "";
+    if (!excluded.empty()) return adm->Reject(r.id, excluded);
+    if (r.HasLogitRule()) {  // validated once, here; an invalid rule fails its request alone (StartRequest)
+        if (!llm_engine_.HasLogitRules())
+            return adm->Reject(r.id, "logit rules: the backend's post processor has no EditLogits", RC_UNSUPPORTED);
+        std::vector<int> stops(generator_config_.stop_tokens.begin(), generator_config_.stop_tokens.end());
+        if (r.stop_tokens) stops.insert(stops.end(), r.stop_tokens->begin(), r.stop_tokens->end());
+        if (!BuildLogitRule(r.logit_bias, r.allowed_tokens.get(), r.banned_tokens, r.min_new_tokens, stops, model_config_.vocab_size,
+                            &adm->rule, &adm->errmsg))
+            return adm->Reject(r.id, adm->errmsg);
+        adm->has_rule = true;
+    }
+    if (guided) {  // a refused guide fails its request alone (StartRequest)
+        adm->guide_slot = guide_cache_.Acquire(r.guide_regex, GuideEndTokens(tokenizer_, generator_config_, r), &adm->errmsg, &adm->errcode);
+        if (adm->guide_slot < 0) return adm->Reject(r.id, adm->errmsg, adm->errcode);
+    }
+    if (!ReserveKv(req, adm, cool_down, is_prefix_cache_hit)) {
+        guide_cache_.Release(adm->guide_slot);   // the request stays queued and asks again
+        adm->guide_slot = -1;
         return false;
     }
-    if (guide_vocab_ == 0) {  // the first guided request: the vocabulary goes to the backend, once
-        const int32_t V = model_config_.vocab_size;
-        std::string blob;
-        std::vector<int64_t> offsets(1, 0);
-        for (int32_t t = 0; t < V; ++t) {
-            tokenizer_->TokenBytes(t, &bytes);
-            blob += bytes;
-            offsets.push_back((int64_t)blob.size());
-        }
-        const RetCode rc = llm_engine_.SetGuideVocab((const uint8_t*)blob.data(), offsets.data(), V);
-        guide_vocab_ = rc == RC_SUCCESS ? 1 : -1;
-        if (rc != RC_SUCCESS) LOG(ERROR) << "SetGuideVocab failed: " << GetRetCodeStr(rc);
-    }
-    if (guide_vocab_ < 0) {
-        adm->errcode = RC_OTHER_ERROR;
-        adm->errmsg = "guide_regex: the backend refused the vocabulary";
-        return false;
-    }
-    adm->errcode = RC_INVALID_VALUE;
-    const std::vector<int32_t> ends = GuideEndTokens(tokenizer_, generator_config_, r);
-    if ((int32_t)ends.size() > PostProcessor::kLogitStopMax) {
-        adm->errmsg = "guide_regex: more than " + std::to_string(PostProcessor::kLogitStopMax) + " end tokens";
-        return false;
-    }
-    for (int32_t t : ends)
-        if (t < 0 || t >= model_config_.vocab_size) {
-            adm->errmsg = "guide_regex: end token [" + std::to_string(t) + "] outside the vocabulary";
-            return false;
-        }
-    std::string key = r.guide_regex;
-    key.push_back('\0');
-    for (int32_t t : ends) key += std::to_string(t) + ",";
-    GuideDfa dfa;
-    bool cached = false;
-    for (const GuideSlot& g : guides_) cached = cached || g.key == key;
-    if (!cached && !CompileGuideRegex(r.guide_regex, &dfa, &adm->errmsg)) return false;
-    adm->guide_slot = AcquireGuide(key, dfa, ends, &adm->errmsg, &adm->errcode);
-    return adm->guide_slot >= 0;
-}
-
-int32_t LLMGenerator::AcquireGuide(const std::string& key, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens, std::string* err,
-                                   RetCode* errcode) {
-    const int32_t n = PostProcessor::kGuideMaxSlots;
-    int32_t pick = -1;
-    for (int32_t i = 0; i < n; ++i)
-        if (guides_[i].key == key) {
-            ++guides_[i].refs;
-            guides_[i].last_use = ++guide_clock_;
-            return i;
-        }
-    for (int32_t i = 0; i < n && pick < 0; ++i)
-        if (guides_[i].key.empty()) pick = i;
-    if (pick < 0) {  // evict the idle slot that was used longest ago
-        for (int32_t i = 0; i < n; ++i)
-            if (guides_[i].refs == 0 && (pick < 0 || guides_[i].last_use < guides_[pick].last_use)) pick = i;
-        if (pick < 0) {
-            *errcode = RC_OTHER_ERROR;
-            *err = "guide_regex: all " + std::to_string(n) + " guide slots are held by running requests";
-            return -1;
-        }
-        const RetCode rc = llm_engine_.UnloadGuide(pick);
-        if (rc != RC_SUCCESS) {
-            *errcode = RC_OTHER_ERROR;
-            *err = "guide_regex: UnloadGuide failed: " + std::string(GetRetCodeStr(rc));
-            return -1;
-        }
-        guides_[pick] = GuideSlot();
-    }
-    const RetCode rc = llm_engine_.LoadGuide(pick, dfa, end_tokens);
-    if (rc != RC_SUCCESS) {
-        *errcode = rc == RC_INVALID_VALUE ? RC_INVALID_VALUE : RC_OTHER_ERROR;
-        *err = rc == RC_INVALID_VALUE ? "guide_regex: some state of the pattern's automaton allows no token of the vocabulary"
-                                      : "guide_regex: LoadGuide failed: " + std::string(GetRetCodeStr(rc));
-        return -1;
-    }
-    guides_[pick].key = key;
-    guides_[pick].dfa = dfa;
-    guides_[pick].refs = 1;
-    guides_[pick].last_use = ++guide_clock_;
-    return pick;
-}
-
-void LLMGenerator::ReleaseGuide(int32_t slot) {
-    if (slot < 0 || slot >= PostProcessor::kGuideMaxSlots) return;
-    if (guides_[slot].refs > 0) --guides_[slot].refs;
+    ++adm->running_batch;
+    ++adm->prefill_batch;
+    return true;
 }
 
 // seed of a request that brings none: one step of the splitmix64 generator (Vigna) from state x
@@ -489,9 +376,9 @@ static uint64_t SplitMix64(uint64_t x) {
 }
 
 // reference ParseRequest, llm_generator.cc:193-261
-bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, ModelInput* in) {
+bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm) {
     const Request& r = *req.orig;
-    if (adm.rest_iters <= 0 || adm.first_fill_len == -1) {
+    if (adm.rejected) {
         conn_->NotifyFailure(r.id, adm.errcode, adm.errmsg);
         if (adapters_) adapters_->Release(r.lora_slot);
         return true;
@@ -500,7 +387,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     if ((mode == 0 && adm.cache_index == INT64_MAX) || (mode == 1 && adm.page_list.empty())) {
         LOG(ERROR) << "catch invalid cache_index or page list";
         if (adapters_) adapters_->Release(r.lora_slot);
-        ReleaseGuide(adm.guide_slot);
+        guide_cache_.Release(adm.guide_slot);
         return false;
     }
     TidData& t = tid_data_map_.emplace(r.id, TidData()).first->second;
@@ -523,7 +410,6 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
     t.prompt_logprobs = std::min(std::max(r.prompt_logprobs, -1), PostProcessor::kTopLogprobsMax);
     // the logit rule goes up once, now that the request has its slot and before its first step.  A slot's record is never cleared: it is
     // read only while its owner's flags are set, and the next owner with a rule overwrites it
-    uint32_t logit_flags = 0;
     if (adm.has_rule) {
         t.min_new_tokens = r.min_new_tokens;
         const RetCode rule_rc = llm_engine_.SetLogitRule(t.slot_index, adm.rule);
@@ -531,8 +417,8 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
             LOG(ERROR) << "id [" << r.id << "] SetLogitRule failed: " << GetRetCodeStr(rule_rc);
             t.rule_failed = true;
         } else {
-            if (!adm.rule.bias_tokens.empty() || adm.rule.has_mask) logit_flags |= 1u;
-            if (!adm.rule.stop_tokens.empty()) logit_flags |= 2u;
+            if (!adm.rule.bias_tokens.empty() || adm.rule.has_mask) t.logit_flags |= 1u;
+            if (!adm.rule.stop_tokens.empty()) t.logit_flags |= 2u;
         }
     }
     if (adm.guide_slot >= 0) {
@@ -563,33 +449,18 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm, Mod
         t.next_tokens = std::make_shared<std::vector<int>>(r.token_ids->begin() + hit, r.token_ids->end());
         t.start_pos = hit;
     }
-    tid_list_.push_back(&t);
-    in->start_pos.push_back(t.start_pos);
-    in->temperatures.push_back(t.temperature);
-    in->top_p_list.push_back(t.top_p);
-    in->top_k_list.push_back(t.top_k);
-    in->seed_list.push_back(t.seed);
-    in->draw_list.push_back(0);
-    in->repetition_penalty_list.push_back(t.repetition_penalty);
-    in->presence_penalty_list.push_back(t.presence_penalty);
-    in->frequency_penalty_list.push_back(t.frequency_penalty);
-    in->batch_slots.push_back(t.slot_index);
-    in->lora_slots.push_back(t.lora_slot);
-    in->num_logprobs_list.push_back(t.num_logprobs);
-    in->prompt_logprobs_list.push_back(t.prompt_logprobs);
-    in->logit_flags.push_back(logit_flags);
-    in->guide_slots.push_back(t.guide_slot);
-    in->guide_states.push_back(t.guide_state);
-    if (mode == 0) in->cache_indices.push_back(adm.cache_index);
-    else in->max_pages = std::max<int64_t>((int64_t)t.page_list.size(), in->max_pages);
+    tid_list_.push_back(&t);  // its row of the step's lists: PackStep
     return true;
 }
 
 // ------------------------------------------------------------------------------------------------ packing
 
-// reference UpdateInput, llm_generator.cc:263-298
+// reference UpdateInput, llm_generator.cc:263-298.  The one place that writes a per-row list of ModelInput: every list is rebuilt from the
+// requests' records on every step, so a row carries its own request's values whatever joined or left in front of it.  Only the page
+// table and its width wait for a change of the row set
 void LLMGenerator::PackStep(bool req_list_changed, ModelInput* in) const {
     const size_t n = tid_list_.size();
+    in->decoding_batches = 0;
     in->max_seq_len = 0;
     in->max_kv_len = 0;
     in->token_inputs.clear();
@@ -597,8 +468,17 @@ void LLMGenerator::PackStep(bool req_list_changed, ModelInput* in) const {
     in->kv_starts.assign(1, 0);
     in->seq_starts.reserve(n + 1);
     in->kv_starts.reserve(n + 1);
+    in->start_pos.clear(); in->cache_indices.clear(); in->batch_slots.clear(); in->lora_slots.clear();
+    in->temperatures.clear(); in->top_p_list.clear(); in->top_k_list.clear(); in->seed_list.clear(); in->draw_list.clear();
+    in->repetition_penalty_list.clear(); in->presence_penalty_list.clear(); in->frequency_penalty_list.clear();
+    in->num_logprobs_list.clear(); in->prompt_logprobs_list.clear(); in->logit_flags.clear();
+    in->guide_slots.clear(); in->guide_states.clear();
     const bool repack_pages = req_list_changed && model_config_.cache_mode == 1;
-    if (repack_pages) in->page_list.assign(n * in->max_pages, INT64_MAX);
+    if (repack_pages) {
+        in->max_pages = 0;
+        for (const TidData* t : tid_list_) in->max_pages = std::max<int64_t>(in->max_pages, (int64_t)t->page_list.size());
+        in->page_list.assign(n * in->max_pages, INT64_MAX);
+    }
     for (size_t i = 0; i < n; ++i) {
         const TidData* t = tid_list_[i];
         const int64_t seqlen = (int64_t)t->next_tokens->size();
@@ -608,104 +488,74 @@ void LLMGenerator::PackStep(bool req_list_changed, ModelInput* in) const {
         in->max_seq_len = std::max(in->max_seq_len, seqlen);
         in->max_kv_len = std::max(in->max_kv_len, t->start_pos + seqlen);
         if (repack_pages) std::copy(t->page_list.begin(), t->page_list.end(), in->page_list.begin() + i * in->max_pages);
+        if (t->steps > 0) ++in->decoding_batches;  // the decode rows are the first ones: a request joins at the end of the batch
+        in->start_pos.push_back(t->start_pos);
+        if (model_config_.cache_mode == 0) in->cache_indices.push_back((int64_t)t->cache_index);
+        in->batch_slots.push_back(t->slot_index);
+        in->lora_slots.push_back(t->lora_slot);
+        in->temperatures.push_back(t->temperature);
+        in->top_p_list.push_back(t->top_p);
+        in->top_k_list.push_back(t->top_k);
+        in->seed_list.push_back(t->seed);
+        in->draw_list.push_back((uint64_t)t->gen_tokens_cnt);
+        in->repetition_penalty_list.push_back(t->repetition_penalty);
+        in->presence_penalty_list.push_back(t->presence_penalty);
+        in->frequency_penalty_list.push_back(t->frequency_penalty);
+        in->num_logprobs_list.push_back(t->num_logprobs);
+        in->prompt_logprobs_list.push_back(t->steps == 0 ? t->prompt_logprobs : -1);  // asked once: later steps carry nothing
+        in->logit_flags.push_back(t->logit_flags);
+        in->guide_slots.push_back(t->guide_slot);
+        in->guide_states.push_back(t->guide_state);
     }
 }
 
-// reference RemoveFinishedTask, llm_generator.cc:300-340: stable compaction of every per-row vector
-void LLMGenerator::CompactBatch(ModelInput* in) {
-    const int mode = model_config_.cache_mode;
-    size_t keep = 0;
-    if (mode == 1) in->max_pages = 0;
-    for (size_t i = 0; i < tid_list_.size(); ++i) {
-        if (!tid_list_[i]) continue;
-        tid_list_[keep] = tid_list_[i];
-        if (mode == 0) in->cache_indices[keep] = in->cache_indices[i];
-        else in->max_pages = std::max<int64_t>(in->max_pages, (int64_t)tid_list_[i]->page_list.size());
-        in->start_pos[keep] = in->start_pos[i];
-        in->temperatures[keep] = in->temperatures[i];
-        in->top_p_list[keep] = in->top_p_list[i];
-        in->top_k_list[keep] = in->top_k_list[i];
-        in->seed_list[keep] = in->seed_list[i];
-        in->draw_list[keep] = in->draw_list[i];
-        in->repetition_penalty_list[keep] = in->repetition_penalty_list[i];
-        in->presence_penalty_list[keep] = in->presence_penalty_list[i];
-        in->frequency_penalty_list[keep] = in->frequency_penalty_list[i];
-        in->batch_slots[keep] = in->batch_slots[i];
-        in->lora_slots[keep] = in->lora_slots[i];
-        in->num_logprobs_list[keep] = in->num_logprobs_list[i];
-        in->prompt_logprobs_list[keep] = in->prompt_logprobs_list[i];
-        in->logit_flags[keep] = in->logit_flags[i];
-        in->guide_slots[keep] = in->guide_slots[i];
-        in->guide_states[keep] = in->guide_states[i];
-        ++keep;
+// reference RemoveFinishedTask, llm_generator.cc:300-340: the rows that left are taken out, the others keep their order
+void LLMGenerator::CompactBatch() {
+    tid_list_.erase(std::remove(tid_list_.begin(), tid_list_.end(), nullptr), tid_list_.end());
+    LOG(DEBUG) << "Rest tasks: " << tid_list_.size();
+}
+
+// a leaving request gives back its KV, its batch slot and its references on an adapter and a guide.  keep_cached_pages: its hashed prompt
+// pages go back to the prefix cache (LRU once unreferenced) and only the rest to the page pool
+void LLMGenerator::ReleaseRequest(const TidData& t, bool keep_cached_pages) {
+    if (model_config_.cache_mode == 0) {
+        idx_mgr_.Free(t.cache_index, (uint64_t)t.total_len - 1);
+    } else {
+        const int64_t hashed = keep_cached_pages ? (int64_t)t.hash_list.size() : 0;
+        prefix_cache_mgr_.DecRefCount(t.hash_list.data(), hashed);
+        page_mgr_.Free(t.page_list.data() + hashed, (int64_t)t.page_list.size() - hashed);
     }
-    tid_list_.resize(keep);
-    if (mode == 0) in->cache_indices.resize(keep);
-    in->start_pos.resize(keep);
-    in->temperatures.resize(keep);
-    in->top_p_list.resize(keep);
-    in->top_k_list.resize(keep);
-    in->seed_list.resize(keep);
-    in->draw_list.resize(keep);
-    in->repetition_penalty_list.resize(keep);
-    in->presence_penalty_list.resize(keep);
-    in->frequency_penalty_list.resize(keep);
-    in->batch_slots.resize(keep);
-    in->lora_slots.resize(keep);
-    in->num_logprobs_list.resize(keep);
-    in->prompt_logprobs_list.resize(keep);
-    in->logit_flags.resize(keep);
-    in->guide_slots.resize(keep);
-    in->guide_states.resize(keep);
-    LOG(DEBUG) << "Rest tasks: " << keep;
+    if (t.slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t.slot_index, 1);
+    if (adapters_) adapters_->Release(t.lora_slot);
+    guide_cache_.Release(t.guide_slot);
 }
 
 // reference DeleteTasks, llm_generator.cc:387-439
-void LLMGenerator::DeleteTasks(ModelInput* in) {
+void LLMGenerator::DeleteTasks() {
     FinishedTaskInfo info;
     while (finished_tasks_.Pop(&info)) {
         auto it = tid_data_map_.find(info.id);
         if (it == tid_data_map_.end()) continue;  // finished by the worker and cancelled by the connection at once
         TidData& t = it->second;
-        --in->decoding_batches;
-        size_t row = 0;
-        while (row < tid_list_.size() && !(tid_list_[row] && tid_list_[row]->tid == info.id)) ++row;
-        if (row == tid_list_.size()) continue;
-        tid_list_[row] = nullptr;
+        const auto row = std::find(tid_list_.begin(), tid_list_.end(), &t);
+        if (row == tid_list_.end()) continue;
+        *row = nullptr;
         // the batch rows shift: the device page table, the penalty slots and the sampler's per-row parameters must be
         // re-uploaded by the next Execute even when nothing finished in the worker and nothing new was admitted (a
         // cancel from the connection on an otherwise quiet step; the reference leaves the flag untouched here)
         req_list_changed_ = true;
-        if (model_config_.cache_mode == 0) {
-            idx_mgr_.Free(t.cache_index, (uint64_t)t.total_len - 1);
-        } else if (generator_config_.enable_prefix_cache) {
-            // hashed prompt pages go back to the prefix cache (LRU once unreferenced); the rest to the page pool
-            const int64_t hashed = (int64_t)t.hash_list.size();
-            prefix_cache_mgr_.DecRefCount(t.hash_list.data(), hashed);
-            page_mgr_.Free(t.page_list.data() + hashed, (int64_t)t.page_list.size() - hashed);
-        } else {
-            page_mgr_.Free(t.page_list.data(), (int64_t)t.page_list.size());
-        }
-        if (t.slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t.slot_index, 1);
-        if (adapters_) adapters_->Release(t.lora_slot);
-        ReleaseGuide(t.guide_slot);
+        ReleaseRequest(t, true);  // (only a request admitted through the prefix cache has hashed pages)
         // (the reference adds to a by-value pointer here and so counts nothing -- SURVEY.md Q2; counted properly)
         worker_profiler_->req_counter.output_tokens_per_req += (uint64_t)t.gen_tokens_cnt;
         tid_data_map_.erase(it);
         ++worker_profiler_->finished_task_cnt;
     }
-    CompactBatch(in);
+    CompactBatch();
 }
 
-// reference ReleaseResource, llm_generator.cc:368-385 (after a failed Execute)
+// reference ReleaseResource, llm_generator.cc:368-385 (after a failed Execute): every page goes to the pool, and the prefix cache is dropped
 void LLMGenerator::ReleaseResource() {
-    for (TidData* t : tid_list_) {
-        if (model_config_.cache_mode == 0) idx_mgr_.Free(t->cache_index, (uint64_t)t->total_len - 1);
-        else page_mgr_.Free(t->page_list.data(), (int64_t)t->page_list.size());
-        if (t->slot_index != INT64_MAX) batch_slots_mgr_.Free((uint64_t)t->slot_index, 1);
-        if (adapters_) adapters_->Release(t->lora_slot);
-        ReleaseGuide(t->guide_slot);
-    }
+    for (const TidData* t : tid_list_) ReleaseRequest(*t, false);
     prefix_cache_mgr_.Reset();
     tid_list_.clear();
     tid_data_map_.clear();
@@ -716,39 +566,134 @@ void LLMGenerator::ReleaseResource() {
 
 // reference DecodeAndSendTask, llm_generator.cc:58-112: one Response per request per step; text requests buffer up
 // to three tokens while the piece decodes to U+FFFD
-void LLMGenerator::SendTokens(const std::vector<TidGenToken>& tokens) {
+void LLMGenerator::SendTokens(std::vector<TidGenToken>* tokens) {
     static const char kReplacement[] = "\xef\xbf\xbd";
-    std::vector<Response> rsp(tokens.size());
-    for (size_t i = 0; i < tokens.size(); ++i) {
-        const TidGenToken& g = tokens[i];
-        Response& r = rsp[i];
-        r.id = g.tid;
-        r.token = g.token;
-        r.finish_flag = g.finish_flag;
-        r.logprob = g.logprob;
-        r.is_special = g.is_special;
-        r.top_tokens = g.top_tokens;
-        r.top_logprobs = g.top_logprobs;
-        r.prompt_logprobs = g.prompt_logprobs;
-        r.prompt_ranks = g.prompt_ranks;
-        r.prompt_top_tokens = g.prompt_top_tokens;
-        r.prompt_top_logprobs = g.prompt_top_logprobs;
+    std::vector<Response> rsp;
+    rsp.reserve(tokens->size());
+    for (TidGenToken& g : *tokens) {
+        rsp.push_back(std::move(g.rsp));
+        Response& r = rsp.back();
         if (!g.is_token_in_out && tokenizer_) {
-            int tok = g.token;
+            int tok = r.token;
             tokenizer_->Decode(&tok, 1, &r.generated);
             if (r.generated == kReplacement) {
-                std::vector<int>& buf = decode_buffer_[g.tid];
-                buf.push_back(g.token);
+                std::vector<int>& buf = decode_buffer_[r.id];
+                buf.push_back(r.token);
                 r.generated.clear();
                 if (buf.size() == 3) {
                     tokenizer_->Decode(buf.data(), 3, &r.generated);
                     buf.clear();
                 }
             }
-            if (g.finish_flag != FinishFlag::NOT_FINISHED) decode_buffer_.erase(g.tid);
+            if (r.finish_flag != FinishFlag::NOT_FINISHED) decode_buffer_.erase(r.id);
         }
     }
     conn_->Send(rsp);
+}
+
+// ------------------------------------------------------------------------------------------------ one row of a finished step
+
+// The step's two compact result lists (ModelOutput's top-N rows and prompt positions), read front to back.  A row takes its entries of
+// both in one call, before anything decides whether it is answered: what a failing row would leave behind, the row behind it would read
+class StepResults final {
+public:
+    struct Slice {
+        size_t prompt_pos = 0, prompt_n = 0;  // the row's positions of the step's prompt logprobs; prompt_n == 0: none
+        int32_t top_row = -1;                 // its row of the step's top-N results; -1: none
+    };
+    explicit StepResults(const ModelOutput& out) : out_(out) {}
+    // prompt_n: the prompt positions the step scored for the row; asks_top: the row asked for top-N logprobs
+    Slice Take(size_t prompt_n, bool asks_top) {
+        Slice s;
+        if (prompt_pos_ + prompt_n <= out_.prompt_logprobs.size()) {
+            s.prompt_pos = prompt_pos_;
+            s.prompt_n = prompt_n;
+        }
+        prompt_pos_ += prompt_n;
+        if (asks_top && top_row_ < out_.top_rows) s.top_row = top_row_++;
+        return s;
+    }
+
+private:
+    const ModelOutput& out_;
+    size_t prompt_pos_ = 0;
+    int32_t top_row_ = 0;
+};
+
+// advance: the row has produced `tok`, which is its next input.  Returns the number of tokens the step fed it
+static int64_t AdvanceRow(TidData* t, int tok) {
+    const int64_t fed = (int64_t)t->next_tokens->size();
+    t->next_tokens = std::make_shared<std::vector<int>>(1, tok);
+    t->start_pos += fed;
+    ++t->gen_tokens_cnt;
+    ++t->steps;  // a prefill row has become a decode row
+    --t->rest_iters;
+    if (t->gen_tokens_cnt >= t->min_new_tokens) t->logit_flags &= ~2u;  // the stops are free from the next step on
+    return fed;
+}
+
+// walk: a guided request takes its automaton over the bytes of every token that does not end it.  The mask allowed only tokens that keep
+// the automaton alive, so the dead state here means kernel and host disagree.  false: the guide is broken, and the state stays where it was
+bool LLMGenerator::WalkGuide(TidData* t, int tok, bool hit_stop) const {
+    if (t->guide_slot < 0) return true;
+    const GuideDfa& dfa = guide_cache_.Dfa(t->guide_slot);
+    if (hit_stop) return dfa.Accepting(t->guide_state);  // an end token in front of a full match
+    std::string bytes;
+    tokenizer_->TokenBytes(tok, &bytes);
+    const int32_t to = bytes.empty() ? GuideDfa::kDead : dfa.Step(t->guide_state, bytes);
+    if (to == GuideDfa::kDead) return false;
+    t->guide_state = to;
+    return true;
+}
+
+// decide: does the request fail on this step, alone, and with which words.  The first reason that holds speaks
+static bool RowFailure(const TidData& t, int tok, bool guide_broken, bool no_prompt, bool no_top, RetCode* code, std::string* msg) {
+    *code = guide_broken || t.rule_failed ? RC_OTHER_ERROR : RC_UNSUPPORTED;
+    if (guide_broken) {
+        *msg = "guide_regex: internal error: token [" + std::to_string(tok) + "] is not allowed in state [" + std::to_string(t.guide_state) +
+               "] of the request's guide";
+    } else if (t.rule_failed) {
+        *msg = "logit rules: the backend could not take the request's rule";
+    } else if (no_prompt) {
+        *msg = "prompt_logprobs: the backend's runtime has no SetPromptLogprobs";
+    } else if (no_top) {
+        *msg = "num_logprobs: the backend's post processor has no TopLogprobs";
+    } else {
+        return false;
+    }
+    return true;
+}
+
+// emit: the Response of the row's token, with the row's slice of the step's results
+static TidGenToken EmitToken(const TidData& t, int tok, float logprob, FinishFlag flag, bool is_special, const ModelOutput& out,
+                             const StepResults::Slice& mine) {
+    TidGenToken g;
+    g.is_token_in_out = t.is_token_in_out;
+    Response& r = g.rsp;
+    r.id = t.tid;
+    r.token = tok;
+    r.finish_flag = flag;
+    r.logprob = logprob;
+    r.is_special = is_special;
+    if (mine.prompt_n > 0) {  // the prompt logprobs of a request go out with its first token
+        const size_t from = mine.prompt_pos, to = from + mine.prompt_n, n = (size_t)t.prompt_logprobs, W = (size_t)PostProcessor::kTopLogprobsMax;
+        r.prompt_logprobs.assign(out.prompt_logprobs.begin() + from, out.prompt_logprobs.begin() + to);
+        r.prompt_ranks.assign(out.prompt_ranks.begin() + from, out.prompt_ranks.begin() + to);
+        for (size_t i = from; n > 0 && i < to; ++i) {
+            r.prompt_top_tokens.insert(r.prompt_top_tokens.end(), out.prompt_top_tokens.begin() + i * W, out.prompt_top_tokens.begin() + i * W + n);
+            r.prompt_top_logprobs.insert(r.prompt_top_logprobs.end(), out.prompt_top_logprobs.begin() + i * W, out.prompt_top_logprobs.begin() + i * W + n);
+        }
+    }
+    if (mine.top_row >= 0) {
+        // the row's first n slots; the ones behind the vocabulary (token -1) are padding
+        const int32_t* tt = out.top_tokens.data() + (size_t)mine.top_row * PostProcessor::kTopLogprobsMax;
+        const float* tl = out.top_logprobs.data() + (size_t)mine.top_row * PostProcessor::kTopLogprobsMax;
+        int32_t n = 0;
+        while (n < t.num_logprobs && tt[n] >= 0) ++n;
+        r.top_tokens.assign(tt, tt + n);
+        r.top_logprobs.assign(tl, tl + n);
+    }
+    return g;
 }
 
 // ------------------------------------------------------------------------------------------------ the step loop
@@ -789,7 +734,7 @@ void LLMGenerator::Generate() {
                 ++worker_profiler_->req_counter.waiting_cnt;
                 worker_profiler_->req_counter.waiting_cost += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(
                     std::chrono::high_resolution_clock::now() - req->enqueue_ts).count();
-                if (!StartRequest(*req, adm, &in)) break;
+                if (!StartRequest(*req, adm)) break;
                 req_list_changed_ = true;
             }
             running_batch = (int)tid_list_.size();
@@ -818,90 +763,36 @@ void LLMGenerator::Generate() {
             decoder_thread_pool_.Wait();  // the previous step's responses are out
             auto tokens = std::make_shared<std::vector<TidGenToken>>();
             tokens->reserve(running_batch);
-            int32_t top_row = 0;  // the place of the next asking row in the compact top-N results
-            size_t prompt_pos = 0;  // the place of the next asking request's first position in the step's prompt logprobs
+            StepResults results(out);
             for (int row = 0; row < running_batch; ++row) {
                 TidData* t = tid_list_[row];
-                ++t->gen_tokens_cnt;
-                ++in.draw_list[row];
-                if (t->gen_tokens_cnt >= t->min_new_tokens) in.logit_flags[row] &= ~2u;  // the stops are free from the next step on
                 const int tok = out.output_token[row];
-                const int64_t fed = (int64_t)t->next_tokens->size();
-                t->next_tokens = std::make_shared<std::vector<int>>(1, tok);
-                if (t->steps == 0) {  // prefill row becomes a decode row
-                    in.start_pos[row] += fed;
-                    ++in.decoding_batches;
-                } else {
-                    ++in.start_pos[row];
-                }
-                t->start_pos += fed;
-                ++t->steps;
-                --t->rest_iters;
-                FinishFlag flag = FinishFlag::NOT_FINISHED;
+                // the prompt logprobs of a request arrive with its first token: its fed - 1 positions are the next ones of the step's results
+                const bool scores_prompt = t->steps == 0 && t->prompt_logprobs >= 0;
+                const int64_t fed = AdvanceRow(t, tok);
+                const StepResults::Slice mine = results.Take(scores_prompt && !out.prompt_unsupported ? (size_t)(fed - 1) : 0, t->num_logprobs > 0);
                 const bool hit_stop = t->early_stopping &&
                     (generator_config_.stop_tokens.count(tok) || (t->stop_tokens && t->stop_tokens->count(tok)));
-                // a request that asks for top-N logprobs on a backend without them fails alone: it leaves like a finished one, unanswered
-                // the prompt logprobs of a request arrive with its first token: its fed - 1 positions are the next ones of the step's results
-                const bool scores_prompt = in.prompt_logprobs_list[row] >= 0;
-                const size_t prompt_n = scores_prompt && !out.prompt_unsupported ? (size_t)(fed - 1) : 0;
-                in.prompt_logprobs_list[row] = -1;   // asked once: later steps carry nothing
-                const bool no_prompt = scores_prompt && out.prompt_unsupported;
-                // a guided request walks its automaton over the bytes of every token that does not end it.  The mask allowed only tokens
-                // that keep the automaton alive, so the dead state here means kernel and host disagree: that request fails, alone
-                bool guide_broken = false;
-                if (t->guide_slot >= 0 && hit_stop) {
-                    guide_broken = !guides_[t->guide_slot].dfa.Accepting(t->guide_state);   // an end token in front of a full match
-                } else if (t->guide_slot >= 0) {
-                    std::string bytes;
-                    tokenizer_->TokenBytes(tok, &bytes);
-                    const int32_t to = bytes.empty() ? GuideDfa::kDead : guides_[t->guide_slot].dfa.Step(t->guide_state, bytes);
-                    if (to == GuideDfa::kDead) guide_broken = true;
-                    else in.guide_states[row] = t->guide_state = to;
-                }
-                const bool no_top = (t->num_logprobs > 0 && out.top_unsupported) || t->rule_failed || no_prompt || guide_broken;
-                if (t->rest_iters <= 0 || hit_stop || no_top) {
+                const bool guide_broken = !WalkGuide(t, tok, hit_stop);
+                // a request that asks for what the backend does not have, or whose rule or guide broke, fails alone: it leaves like a
+                // finished one, unanswered
+                RetCode fail_code;
+                std::string fail_msg;
+                const bool failed = RowFailure(*t, tok, guide_broken, scores_prompt && out.prompt_unsupported,
+                                               t->num_logprobs > 0 && out.top_unsupported, &fail_code, &fail_msg);
+                FinishFlag flag = FinishFlag::NOT_FINISHED;
+                if (t->rest_iters <= 0 || hit_stop || failed) {
                     flag = t->rest_iters <= 0 ? FinishFlag::LENGTH : FinishFlag::EOS_TOKEN;
                     if (cool_down > 0) --cool_down;
                     finished_tasks_.Push(FinishedTaskInfo(t->tid, FinishedTaskInfo::FROM_WORKER));
                     req_list_changed_ = true;
                 }
-                if (no_top) {
-                    // the step's results hold this row's entries all the same: both cursors pass them, or the rows behind read them
-                    prompt_pos += prompt_n;
-                    if (t->num_logprobs > 0 && top_row < out.top_rows) ++top_row;
-                    if (guide_broken) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "guide_regex: internal error: token [" + std::to_string(tok) + "] is not allowed in state [" + std::to_string(t->guide_state) + "] of the request's guide");
-                    else if (t->rule_failed) conn_->NotifyFailure(t->tid, RC_OTHER_ERROR, "logit rules: the backend could not take the request's rule");
-                    else if (no_prompt) conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "prompt_logprobs: the backend's runtime has no SetPromptLogprobs");
-                    else conn_->NotifyFailure(t->tid, RC_UNSUPPORTED, "num_logprobs: the backend's post processor has no TopLogprobs");
-                    continue;
-                }
-                tokens->push_back(TidGenToken{t->tid, tok, out.logprobs[row], flag, (uint64_t)t->steps, t->is_token_in_out,
-                                              generator_config_.special_tokens.count(tok) > 0, {}, {}, {}, {}, {}, {}});
-                if (prompt_n > 0 && prompt_pos + prompt_n <= out.prompt_logprobs.size()) {
-                    TidGenToken& g = tokens->back();
-                    const size_t n = (size_t)t->prompt_logprobs, W = (size_t)PostProcessor::kTopLogprobsMax;
-                    g.prompt_logprobs.assign(out.prompt_logprobs.begin() + prompt_pos, out.prompt_logprobs.begin() + prompt_pos + prompt_n);
-                    g.prompt_ranks.assign(out.prompt_ranks.begin() + prompt_pos, out.prompt_ranks.begin() + prompt_pos + prompt_n);
-                    for (size_t i = prompt_pos; n > 0 && i < prompt_pos + prompt_n; ++i) {
-                        g.prompt_top_tokens.insert(g.prompt_top_tokens.end(), out.prompt_top_tokens.begin() + i * W, out.prompt_top_tokens.begin() + i * W + n);
-                        g.prompt_top_logprobs.insert(g.prompt_top_logprobs.end(), out.prompt_top_logprobs.begin() + i * W, out.prompt_top_logprobs.begin() + i * W + n);
-                    }
-                }
-                prompt_pos += prompt_n;
-                if (t->num_logprobs > 0 && top_row < out.top_rows) {
-                    // the row's first n slots; the ones behind the vocabulary (token -1) are padding
-                    const int32_t* tt = out.top_tokens.data() + (size_t)top_row * PostProcessor::kTopLogprobsMax;
-                    const float* tl = out.top_logprobs.data() + (size_t)top_row * PostProcessor::kTopLogprobsMax;
-                    int32_t n = 0;
-                    while (n < t->num_logprobs && tt[n] >= 0) ++n;
-                    tokens->back().top_tokens.assign(tt, tt + n);
-                    tokens->back().top_logprobs.assign(tl, tl + n);
-                    ++top_row;
-                }
+                if (failed) conn_->NotifyFailure(t->tid, fail_code, fail_msg);
+                else tokens->push_back(EmitToken(*t, tok, out.logprobs[row], flag, generator_config_.special_tokens.count(tok) > 0, out, mine));
             }
             // detokenise + send overlaps the next step (llm_generator.cc:738-745)
-            decoder_thread_pool_.RunAsync([this, tokens](uint32_t, uint32_t) { SendTokens(*tokens); });
-            if (finished_tasks_.Size() > 0) DeleteTasks(&in);
+            decoder_thread_pool_.RunAsync([this, tokens](uint32_t, uint32_t) { SendTokens(tokens.get()); });
+            if (finished_tasks_.Size() > 0) DeleteTasks();
         }
         counters.global.post_process_cost += counters.current.post_process_cost;
 

@@ -20,26 +20,17 @@
 #include "../utils/index_manager.h"
 #include "../utils/mpsc_request_scheduler.h"
 #include "../utils/prefix_cache_manager.h"
+#include "guide_cache.h"
 #include "ppl/common/allocators.h"
 #include "ppl/common/mpsc_queue.h"
 #include "ppl/common/threadpool.h"
 
 namespace ppl { namespace llm {
 
-// one generated token on its way to the connection
+// one generated token on its way to the connection: its Response, all but the text (SendTokens decodes that)
 struct TidGenToken final {
-    uint64_t tid;
-    int token;
-    float logprob;
-    FinishFlag finish_flag;
-    uint64_t steps;
+    Response rsp;
     bool is_token_in_out;
-    bool is_special;
-    std::vector<int32_t> top_tokens;  // Response::top_tokens / top_logprobs
-    std::vector<float> top_logprobs;
-    std::vector<float> prompt_logprobs;   // Response::prompt_* (the request's first token only)
-    std::vector<int32_t> prompt_ranks, prompt_top_tokens;
-    std::vector<float> prompt_top_logprobs;
 };
 
 struct FinishedTaskInfo final {
@@ -49,7 +40,8 @@ struct FinishedTaskInfo final {
     uint32_t type;
 };
 
-// per running request (reference TidData, llm_generator.h:79-103)
+// per running request (reference TidData, llm_generator.h:79-103).  Everything a request carries from step to step lives here and only
+// here: PackStep builds every per-row list of ModelInput from these records, every step
 struct TidData final {
     uint64_t tid = 0;
     float temperature = 1.f;
@@ -76,7 +68,8 @@ struct TidData final {
     uint64_t seed = 0;       // sampling seed: the request's own, or the generator's next one
     int32_t prompt_logprobs = -1;  // Request::prompt_logprobs, clamped to -1 .. PostProcessor::kTopLogprobsMax
     int32_t num_logprobs = 0;  // Request::num_logprobs, clamped to 0 .. PostProcessor::kTopLogprobsMax
-    int32_t min_new_tokens = 0;  // Request::min_new_tokens: bit 1 of the row's logit flags until this many tokens are out
+    uint32_t logit_flags = 0;    // ModelInput::logit_flags of its row: 0 without a rule, and when the backend refused the rule
+    int32_t min_new_tokens = 0;  // Request::min_new_tokens: bit 1 of logit_flags until this many tokens are out
     bool rule_failed = false;    // the upload of its logit rule failed: the request is failed on its first step
     int32_t guide_slot = -1;     // guided decoding: the guide slot the request holds a reference on until it leaves; -1: none
     int32_t guide_state = 0;     // the state of its automaton after the bytes generated so far
@@ -114,17 +107,14 @@ private:
     void Generate();
     bool AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* cool_down, bool* is_prefix_cache_hit);
     bool ReserveKv(const LlmRequest& req, Admission* adm, int32_t* cool_down, bool* is_prefix_cache_hit);
-    bool StartRequest(const LlmRequest& req, const Admission& adm, ModelInput* model_input);
+    bool StartRequest(const LlmRequest& req, const Admission& adm);
     void PackStep(bool req_list_changed, ModelInput* model_input) const;
-    void DeleteTasks(ModelInput* model_input);
-    void CompactBatch(ModelInput* model_input);
+    bool WalkGuide(TidData* t, int tok, bool hit_stop) const;
+    void DeleteTasks();
+    void CompactBatch();
+    void ReleaseRequest(const TidData& t, bool keep_cached_pages);
     void ReleaseResource();
-    void SendTokens(const std::vector<TidGenToken>& tokens);
-    // guided decoding: the admission check of a request with guide_regex (false: adm->errmsg / errcode say why), and the slot cache
-    bool AdmitGuide(const Request& r, Admission* adm);
-    int32_t AcquireGuide(const std::string& key, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens, std::string* err,
-                         ppl::common::RetCode* errcode);
-    void ReleaseGuide(int32_t slot);
+    void SendTokens(std::vector<TidGenToken>* tokens);
     static void* GeneratorThreadFunc(void*);
 
 private:
@@ -135,6 +125,7 @@ private:
     Connection* conn_;
     uint64_t kv_cache_max_tokens_ = 0;
     LLMEngine llm_engine_;
+    GuideCache guide_cache_;  // behind the engine it unloads its slots through when it goes
     ppl::common::StaticThreadPool decoder_thread_pool_;
 
     // running batch: row order == ModelInput row order
@@ -158,18 +149,6 @@ private:
 
     // U+FFFD buffering of the text path (llm_generator.cc:84-99)
     std::map<uint64_t, std::vector<int>> decode_buffer_;
-
-    // guided decoding: the backend's guide slots as a cache from (pattern, end tokens) to slot.  A slot with refs == 0 stays loaded until
-    // its place is needed (least recently used first); guide_vocab_: 0 = not sent yet, 1 = the backend has the vocabulary, -1 = it refused
-    struct GuideSlot {
-        std::string key;   // empty: nothing loaded
-        GuideDfa dfa;
-        int32_t refs = 0;
-        uint64_t last_use = 0;
-    };
-    GuideSlot guides_[PostProcessor::kGuideMaxSlots];
-    uint64_t guide_clock_ = 0;
-    int guide_vocab_ = 0;
 
     StepObserver observer_ = nullptr;
     void* observer_arg_ = nullptr;
