@@ -43,11 +43,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(const uint16_t* __restrict__ 
     __shared__ __attribute__((aligned(16))) uint16_t Ws[G_BN * G_BK];
     __shared__ __attribute__((aligned(16))) uint16_t Xs[G_BM * G_BK];
 
-    // XCD-aware tile mapping: XCD x = id % 8 walks weight tiles n = x, x+8, ... and for each all m tiles
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int nt = xcd + 8 * (slot / m_tiles);
-    const int mt = slot % m_tiles;
+    int nt, mt;
+    xcd_tile((int)blockIdx.x, m_tiles, nt, mt);
     if (nt >= n_tiles) return;
     const int n0 = nt * G_BN;
     const int64_t m0 = (int64_t)mt * G_BM;
@@ -199,13 +196,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(const uint16_t* __restrict__ 
 }
 
 // stand-alone launch of the tile body (k_gemm_dev.h)
-struct DmaKernel { int wq, epi, stages, wl, bm, maxg; };  // template arguments of a launch (launch_linear)
 template <int WQ, int EPI, int G_ST, int WL, int BM = G_BM, int MAXG = W4_MAXG>
 __global__ __launch_bounds__(WL == 6 ? 768 : (WL == 5 ? 512 : 256)) void gemm_dma_kernel(const uint16_t* __restrict__ x, const void* __restrict__ wv,
                                                              const uint16_t* __restrict__ scale, int64_t M, int N, int K,
                                                              void* __restrict__ yv, int64_t ldy, int n_tiles, int m_tiles,
                                                              int map_mode, int kt_per_split, float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) char smem[gemm_dma_lds_bytes<WQ, G_ST, BM, MAXG>()];
+    __shared__ __attribute__((aligned(16))) char smem[gemm_dma_lds_bytes(WQ, G_ST, BM, MAXG)];
     gemm_dma_body<WQ, EPI, G_ST, WL, BM>(x, wv, scale, M, N, K, yv, ldy, n_tiles, m_tiles, map_mode, kt_per_split, ws, (int)blockIdx.x,
                                      (int)blockIdx.y, (int)gridDim.y, smem);
 }
@@ -221,17 +217,13 @@ __global__ __launch_bounds__(WL == 6 ? 768 : (WL == 5 ? 512 : 256)) void gemm_dm
 // Round 4, second step: the activation sub-tile is as tall as the batch needs (BM = 16 / 32 / 64 rows), so that the LDS a block does not
 // spend on padding rows holds more stages of the weight stream: what bounds these steps is weight bytes in flight per CU (32 KiB with two
 // 64-row blocks of two stages; 64 KiB with three stages of a 16- or 32-row block, two blocks per CU).
-constexpr int S_KS = 2;                                             // 64-deep sub-tiles per stage
-constexpr int S_WB = G_BN * G_BK * S_KS;                            // weight bytes per stage: 16 KiB
-template <int BM> constexpr int s_xb() { return S_KS * BM * G_BK * 2; }  // activation bytes per stage: 4 / 8 / 16 KiB
-struct Half128Kernel { int epi, st, bm; };                          // template arguments of a launch (launch_linear)
-
+// (S_KS = 2 64-deep sub-tiles per stage, S_WB weight and s_xb(BM) activation bytes per stage: k_gemm_tiles.h)
 template <int EPI, int ST, int BM>
 __global__ __launch_bounds__(256) void gemm_w8_half128_kernel(const uint16_t* __restrict__ x, const int8_t* __restrict__ w,
                                                               const uint16_t* __restrict__ scale, int64_t M, int N, int K,
                                                               void* __restrict__ yv, int64_t ldy, int n_tiles, int kt_per_split,
                                                               float* __restrict__ ws) {
-    constexpr int XB = s_xb<BM>(), NJ = BM / 16;
+    constexpr int XB = s_xb(BM), NJ = BM / 16;
     constexpr int XP = XB / 1024, WP = S_WB / 1024, PP = (XP + WP) / 4;   // 1-KiB DMA pieces per stage: X, W, per wave (5 / 6 / 8)
     static_assert((XP + WP) % 4 == 0, "every wave issues the same number of pieces");
     extern __shared__ __attribute__((aligned(16))) char smem_h[];  // ST x X, then ST x W
@@ -291,10 +283,7 @@ __global__ __launch_bounds__(256) void gemm_w8_half128_kernel(const uint16_t* __
         if (d < ktiles) issue(d, (kt0 + d) * (G_BK * S_KS));
     int st = 0, stn = D % ST;
     for (int t = 0; t < ktiles; ++t) {
-        const int younger = (ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1);
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PP) : "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PP) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ring_wait<PP>((ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1));
         __syncthreads();
         if (t + D < ktiles) issue(stn, (kt0 + t + D) * (G_BK * S_KS));
         const char* xs0 = Xs0 + st * XB;
@@ -362,8 +351,6 @@ __global__ __launch_bounds__(256) void gemm_w8_half128_kernel(const uint16_t* __
 // reads ~40 % fewer LDS bytes and converts half as many weight fragments, and each activation / weight byte fetched
 // from L2 feeds twice the flops.  One block per CU (3-stage ring = 144 KiB LDS), prefetch distance 2.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int H_BN = 256, H_BM = 256, H_ST = 3;
-
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_w8_dma256_kernel(const uint16_t* __restrict__ x, const int8_t* __restrict__ w,
                                                              const uint16_t* __restrict__ scale, int64_t M, int N, int K,
@@ -372,15 +359,10 @@ __global__ __launch_bounds__(512) void gemm_w8_dma256_kernel(const uint16_t* __r
     uint16_t* const Xs0 = reinterpret_cast<uint16_t*>(smem256);
     int8_t* const Wq0 = reinterpret_cast<int8_t*>(smem256 + H_ST * H_BM * G_BK * 2);
 
-    // block -> tile: XCD x = id % 8 owns the weight tiles n == x (mod 8) and walks them in super-tiles of gn (n) x gm (m) tiles, m
-    // fastest inside a super-tile, super-tiles m-major: the ~32 blocks an XCD runs at a time then touch gn weight tiles and gm
-    // activation tiles per K step instead of 1 and 32 (gn = 1, gm = m_tiles: the old order), i.e. a third of the bytes through its L2
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int per_super = gn * gm, sm_count = m_tiles / gm;
-    const int sup = slot / per_super, within = slot % per_super;
-    const int nt = xcd + 8 * ((sup / sm_count) * gn + within / gm);
-    const int mt = (sup % sm_count) * gm + within % gm;
+    // block -> tile in super-tiles (xcd_super_tile): the ~32 blocks an XCD runs at a time touch gn weight tiles and gm activation tiles
+    // per K step instead of 1 and 32, i.e. a third of the bytes through its L2
+    int nt, mt;
+    xcd_super_tile((int)blockIdx.x, m_tiles, gn, gm, nt, mt);
     if (nt >= n_tiles) return;
     const int n0 = nt * H_BN;
     const int64_t m0 = (int64_t)mt * H_BM;
@@ -527,10 +509,12 @@ __global__ __launch_bounds__(512) void gemm_w8_dma256_kernel(const uint16_t* __r
     }
 }
 
+// MFMA skinny kernel, M <= 16: one 16-row activation tile (MT = 1 is the only form compiled)
 template <int WQ, int MT, int EPI, int NW>
 __global__ __launch_bounds__(NW * 64) void gemv_kernel(const uint16_t* __restrict__ x, const void* __restrict__ wv,
                                                    const uint16_t* __restrict__ scale, int64_t M, int N, int K, int group,
                                                    void* __restrict__ yv, int64_t ldy) {
+    static_assert(MT == 1, "launch_linear takes this kernel up to 16 rows only");
     constexpr int KL = WQ == 8 ? 16 : (WQ == 4 ? 32 : 8);  // k elements in one lane's 16 bytes
     constexpr int KSTEP = KL * 4;                          // k elements per wave-load
     constexpr int NKS = KL / 8;                            // MFMA k-steps per load
@@ -624,27 +608,6 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const uint16_t* __restric
     }
 }
 
-template <int WQ, int EPI>
-static hipError_t launch_gemv(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int group, int64_t M,
-                              int N, int K, void* y, int64_t ldy, LinearRoute* route) {
-    dim3 grid((unsigned)((N + 15) / 16));
-    const int mt = (int)((M + 15) / 16);
-    static const int forced_nw = tune_int("PPLHIP_GEMV_WAVES", 0);
-    // up to 1024 row tiles -> 8 K slices per tile so that every CU has enough waves streaming (profiles/gemm_microbench.py)
-    const int nw = forced_nw ? forced_nw : ((N + 15) / 16 <= 1024 ? 8 : 4);
-    if (mt != 1 && mt != 2) return hipErrorInvalidValue;
-    if (route) {
-        route->add("kernel=gemv_kernel<%d,%d,%s,%d> splits=1 reduce=none order=plain", WQ, mt, epi_name(EPI), nw == 8 ? 8 : 4);
-        if (route->dry) return hipSuccess;
-    }
-    dispatch_int<1, 2>(mt, [&](auto MT) {
-        dispatch_int<8, 4>(nw, [&](auto NW) {
-            hipLaunchKernelGGL((gemv_kernel<WQ, MT, EPI, NW>), grid, dim3(NW * 64), 0, s, x, w, scale, M, N, K, group, y, ldy);
-        });
-    });
-    return hipGetLastError();
-}
-
 // split-K reduce: y[m][n] = (sum_z slab[z][m][n]) * scale[n]  (scale == NULL: 1)
 template <int EPI>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, int splits, int64_t M, int N,
@@ -674,308 +637,140 @@ hipError_t launch_splitk_reduce(hipStream_t s, const float* ws, int splits, int6
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// launch_linear: validate -> plan_linear (linear_plan.cc: which kernel, which grid, which template arguments) -> route text -> launch.
+// The launchers below instantiate a family's kernels from its part of the plan; a family with dynamic LDS names its instantiations in
+// ONE list that both the opt-in and the dispatch walk.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct LinearArgs {   // the operands of one part
+    hipStream_t s;
+    const uint16_t* x;
+    const void* w;
+    const uint16_t* scale;
+    int group, N, K;
+    void* y;
+    int64_t ldy;
+    float* ws;
+};
+
+void run_gemv(const LinearPart& p, const LinearArgs& a) {
+    dispatch_int<0, 8, 4>(p.wq, [&](auto WQ) {
+        dispatch_epi(p.epi, [&](auto E) {
+            dispatch_int<8, 4>(p.nw, [&](auto NW) {
+                hipLaunchKernelGGL((gemv_kernel<WQ, 1, E, NW>), dim3(p.grid_x), dim3(p.threads), 0, a.s, a.x, a.w, a.scale, p.M, a.N, a.K, a.group, a.y, a.ldy);
+            });
+        });
+    });
+}
+
+void run_w8_256(const LinearPart& p, const LinearArgs& a) {
+    static LdsOptIn once;
+    if (once.first()) for_each_epi([](auto E) { set_max_lds(H_LDS, gemm_w8_dma256_kernel<E>); });
+    dispatch_epi(p.epi, [&](auto E) {
+        hipLaunchKernelGGL((gemm_w8_dma256_kernel<E>), dim3(p.grid_x), dim3(p.threads), p.lds, a.s, a.x, (const int8_t*)a.w, a.scale, p.M, a.N, a.K, a.y,
+                           a.ldy, p.n_tiles, p.m_tiles, (int)p.map.gn, (int)p.map.gm, p.staged);
+    });
+}
+
+// the (stages, activation rows) instantiations of gemm_w8_half128_kernel; two stages: 64-row sub-tiles only
+template <class F>
+void for_each_half128(F&& f) {
+    f(int_c<3>{}, int_c<16>{}); f(int_c<3>{}, int_c<32>{}); f(int_c<2>{}, int_c<64>{}); f(int_c<3>{}, int_c<64>{});
+    f(int_c<3>{}, int_c<80>{}); f(int_c<3>{}, int_c<96>{}); f(int_c<3>{}, int_c<112>{}); f(int_c<3>{}, int_c<128>{});
+}
+void run_w8_half128(const LinearPart& p, const LinearArgs& a) {
+    static LdsOptIn once;
+    if (once.first())
+        for_each_epi([](auto E) {
+            for_each_half128([&](auto ST, auto BM) { set_max_lds(half128_lds_bytes(ST, BM), gemm_w8_half128_kernel<E, ST, BM>); });
+        });
+    dispatch_epi(p.epi, [&](auto E) {
+        for_each_half128([&](auto ST, auto BM) {
+            if (ST == p.stages && BM == p.bm)
+                hipLaunchKernelGGL((gemm_w8_half128_kernel<E, ST, BM>), dim3(p.grid_x, p.grid_y), dim3(p.threads), p.lds, a.s, a.x, (const int8_t*)a.w,
+                                   a.scale, p.M, a.N, a.K, a.y, a.ldy, p.n_tiles, p.kt_per, a.ws);
+        });
+    });
+}
+
+void run_ring(const LinearPart& p, const LinearArgs& a) {
+    dispatch_int<8, 4, 0>(p.wq, [&](auto WQ) {
+        dispatch_epi(p.epi, [&](auto E) {
+            dispatch_int<2, 3, 4>(p.stages, [&](auto ST) {
+                auto go = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y), dim3(p.threads), 0, a.s, a.x, a.w, a.scale, p.M, a.N, a.K, a.y, a.ldy, p.n_tiles,
+                                       p.m_tiles, map_pack(p.map), p.kt_per, a.ws);
+                };
+                if constexpr (WQ == 8 && ST >= 3) {
+                    if (p.wl == 6) return go(gemm_dma_kernel<WQ, E, ST, 6>);
+                }
+                if (p.wl == 5) go(gemm_dma_kernel<WQ, E, ST, 5>);
+                else if (p.bm == 64) go(gemm_dma_kernel<WQ, E, ST, 1, 64>);
+                else if (p.maxg == 16) go(gemm_dma_kernel<WQ, E, ST, 1, G_BM, 16>);
+                else go(gemm_dma_kernel<WQ, E, ST, 1>);
+            });
+        });
+    });
+}
+
+void run_generic(const LinearPart& p, const LinearArgs& a) {
+    dispatch_int<0, 8, 4>(p.wq, [&](auto WQ) {
+        dispatch_epi(p.epi, [&](auto E) {
+            hipLaunchKernelGGL((gemm_kernel<WQ, E>), dim3(p.grid_x), dim3(p.threads), 0, a.s, a.x, a.w, a.scale, p.M, a.N, a.K, a.group, a.y, a.ldy,
+                               p.n_tiles, p.m_tiles);
+        });
+    });
+}
+
+}  // namespace
+
 hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int wq_bit, int group,
                          int64_t M, int N, int K, void* y, int64_t ldy, bool out_fp32, float* ws, size_t ws_bytes, bool swiglu, SplitSlabs* defer,
                          LinearRoute* route) {
     if (defer) *defer = SplitSlabs{};
     if (M == 0) return hipSuccess;
     if (swiglu && out_fp32) return hipErrorInvalidValue;
-    const int epi = swiglu ? EPI_SWIGLU : (out_fp32 ? EPI_F32 : EPI_F16);
-    if (N % 4 || ldy % 4) return hipErrorInvalidValue;
-    if (wq_bit == 0 && K % 8) return hipErrorInvalidValue;
-    if (wq_bit == 8 && K % 16) return hipErrorInvalidValue;
-    if (wq_bit == 4 && (K % 32 || group % 32 || K % group)) return hipErrorInvalidValue;
-    // A few rows above a multiple of 1024 (a saturated continuous-batching step: 1024 decode rows + the prompt chunk of a newly admitted
-    // request) would add a ninth / seventeenth 128-row tile to every column block -- a whole extra round of tiles for a few rows (7B layer
-    // GEMMs at M = 1040: 555 us against 414 us at M = 1024).  The rows up to the multiple go through the shapes that fit, the rest as a
-    // second, small launch.
-    static const int msplit = tune_int("PPLHIP_GEMM_MSPLIT", 256);  // largest rest that is split off (0: never); measured: rest 16 / 76 / 128 / 256 -13 / -10 / -11 / -5 %, 384 equal
-    if (msplit && M > 1024 && M < 3584 && (M & 1023) != 0 && (M & 1023) <= msplit) {
-        const int64_t m_main = M & ~(int64_t)1023, m_rest = M - m_main;
-        const size_t yelt = out_fp32 ? 4 : 2;
-        hipError_t e = launch_linear(s, x, w, scale, wq_bit, group, m_main, N, K, y, ldy, out_fp32, ws, ws_bytes, swiglu, nullptr, route);
-        if (e != hipSuccess) return e;
-        if (route) route->add(";");
-        return launch_linear(s, x + m_main * K, w, scale, wq_bit, group, m_rest, N, K, (char*)y + (size_t)m_main * ldy * yelt, ldy, out_fp32, ws,
-                             ws_bytes, swiglu, nullptr, route);
-    }
-    static const bool no_skinny = tune_set("PPLHIP_GEMM_NOSKINNY"), force_generic = tune_set("PPLHIP_GEMM_GENERIC");
-    // the skinny kernel up to 3 rows; from 4 rows the half-height tile kernel (64 activation rows, split-K) is faster: 7B decode step at batch
-    // 4 / 8 / 12 / 16 3.64 / 3.90 / 4.40 / 4.74 -> 3.56 / 3.73 / 3.81 / 4.18 ms (profiles/small_batch_latency.py); PPLHIP_GEMV_MAX_M overrides
-    static const int gemv_max_m = tune_int("PPLHIP_GEMV_MAX_M", 3);
-    // up to 4 rows (PPLHIP_GEMV_STREAM_MAX_M): the streaming GEMV of k_gemv.hip -- whole 1-KiB row pieces per wave-load, no matrix unit
-    if (M <= gemv_stream_max_m(wq_bit, group, N, K) && !no_skinny && !force_generic)
-        return launch_gemv_stream(s, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, route);
-    // (without a split-K workspace the half-height tiles would run as N / 128 unsplit blocks: the skinny kernel keeps its 16 rows there)
-    // (int8 weights with K % 128 == 0: from 3 rows the half-height tiles with 16-row activation sub-tiles are faster than either GEMV)
-    const int skinny_max = wq_bit == 8 && K % (G_BK * 2) == 0 && gemv_max_m > 2 && !tune_set("PPLHIP_GEMV_MAX_M") ? 2 : gemv_max_m;
-    if (M <= (ws && ws_bytes ? skinny_max : 16) && M <= 16 && !no_skinny) {
-        if (wq_bit == 0 || wq_bit == 8 || wq_bit == 4) {
-            hipError_t e = hipSuccess;
-            dispatch_int<0, 8, 4>(wq_bit, [&](auto WQ) {
-                dispatch_epi(epi, [&](auto E) { e = launch_gemv<WQ, E>(s, x, w, scale, group, M, N, K, y, ldy, route); });
-            });
-            return e;
-        }
-    }
-    // W4A16 at a few hundred rows (config 4: the 70B / TP8 slice at batch 256): 128 x 64 tiles, DMA waves beside MFMA waves whose fragment
-    // registers roll (k_gemm_pc.hip, round 5) -- for the shapes whose 128 x 64 tiles fill most CUs WITHOUT K slabs (wo / w13 / w2 of that
-    // slice: 256 / 224 / 256 blocks).  A shape that needs slabs anyway (wqkv: 40 tiles) stays on the ring kernel below: measured in the
-    // step, 12.70 -> 12.49 ms (profiles/r05_w4_pc_experiments.md).  PPLHIP_GEMM_PC=0: the ring kernel for everything (A/B runs)
-    static const int pc_mode = getenv("PPLHIP_GEMM_PC") ? atoi(getenv("PPLHIP_GEMM_PC")) : 1;
-    if (pc_mode && wq_bit == 4 && M > 128 && M <= 512 && !force_generic && (int64_t)((N + 63) / 64) * ((M + 127) / 128) >= 160 &&
-        linear_w4_pc_supported(group, M, N, K, x, w, scale, y, ldy, epi))
-        return launch_linear_w4_pc(s, x, w, scale, M, N, K, y, ldy, epi, route);
-    // W8A16 at 512 <= M < 4096 with N >= 8192 (wqkv / w13 of a decode step at batch ~1024): one 128 x 384 block per CU whose twelve
-    // consumer waves share the activation tile (k_gemm_wide.hip) when its tiles fill the chip's rounds; PPLHIP_GEMM_WIDE=0: never
-    static const int wide = tune_int("PPLHIP_GEMM_WIDE", 1);
-    if (wide && wq_bit == 8 && K % G_BK == 0 && M >= 512 && (M < 4096 || wide == 2) && N >= 8192) {
-        const int nc = wide == 2 ? 12 : linear_w8_wide_waves(M, N);  // (2: experiments -- every eligible shape, any M)
-        // (round 4's hand-scheduled K loop for this block tile -- equal speed, both on the chip's power limit -- lives under profiles/probes/gemm_asm/ since round 6)
-        if (nc) return launch_linear_w8_wide(s, x, (const int8_t*)w, scale, M, N, K, y, ldy, epi, nc, route);
-    }
-    // (Round 6, measured and not adopted: 128 x 96 / 64 x 96 tiles whose four multiplying waves split each K tile by k-step on 32 x 32 x 16
-    // MFMAs -- 232 / 256 blocks instead of 176 / 96 for the 7B / TP8 slice's w13 / wqkv, 22 KiB of fragment reads per K tile instead of 72.
-    // Parity-green, and no faster: w13 35.5 against 34.9 us, the emulated TP-8 step +0.07 ms.  Its ablation builds say why -- with the MFMAs
-    // compiled out the K loop still takes 0.29 us per tile: the 22-24 KiB of LDS-DMA per K tile and CU move at ~40 B / clk whatever the tile
-    // computes, and ~9 us of every launch are dispatch, first-byte latency, the final exchange and the stores.
-    // profiles/probes/gemm_ks/, profiles/r06_tp_slice_gemm_experiments.md)
-    const int n_tiles = (N + G_BN - 1) / G_BN;
-    const int m_tiles = (int)((M + G_BM - 1) / G_BM);
-    const int n_tiles_pad = (n_tiles + 7) / 8 * 8;
-    dim3 grid((unsigned)(n_tiles_pad * m_tiles)), block(256);
-    static const int min_m256 = tune_int("PPLHIP_GEMM_256_MIN_M", 3584);  // measured (7B layer): M = 3584 1435 vs 1501 us, 3072 1277 vs 1264, 2560 equal, 2048 941 vs 851
-    if (wq_bit == 8 && K % G_BK == 0 && M >= min_m256 && N >= 1024 && !force_generic) {
-        // (Round 6, measured and not adopted: the same block tile on v_mfma_f32_32x32x16_f16 -- four waves of 64 (n) x 256 (m) with 256 resident
-        // accumulators, or this kernel's eight waves of 32 x 256 -- with two rolling fragment sets and LDS-DMA pieces on a scalar base: a third
-        // fewer instructions per flop, parity-green, and 13 % SLOWER (1.05-1.06 against 1.21 PFLOP/s at M = 8192, profiles/r06_gemm_big_ab.log).
-        // The counters that motivated it -- 2.25 other instructions per MFMA here against 0.72 in the vendor library's kernel, same L2 hit rates,
-        // same bytes -- are in profiles/r06_gemm_bigm_counters.md; the kernel is kept under profiles/probes/gemm_big/.)
-        const int nt2 = (N + H_BN - 1) / H_BN, mt2 = (int)((M + H_BM - 1) / H_BM);
-        const size_t lds = (size_t)H_ST * (H_BM * G_BK * 2 + H_BN * G_BK);
-        // super-tile shape: gm = the largest divisor of mt2 <= 4 (X tiles carry twice the bytes of W tiles), gn = up to 8 weight tiles
-        // of the XCD's share; the share is padded to whole super-tiles (the extra blocks return at once)
-        static const int forced_gm = tune_int("PPLHIP_GEMM256_GM", 0);
-        static const int forced_gn = tune_int("PPLHIP_GEMM256_GN", 0);
-        const int nl = (nt2 + 7) / 8;  // weight tiles per XCD
-        int gm = 4;
-        if (forced_gm > 0) gm = forced_gm;
-        while (gm > 1 && mt2 % gm) --gm;
-        if (mt2 % gm) gm = 1;
-        int gn = forced_gn > 0 ? forced_gn : 8;
-        if (gn > nl) gn = nl;
-        const int nl_pad = (nl + gn - 1) / gn * gn;
-        dim3 g256((unsigned)(8 * nl_pad * mt2));
-        static const int no_stage = tune_set("PPLHIP_GEMM_DIRECT_EPILOGUE") ? 1 : 0;  // A/B runs
-        const int staged = !no_stage && ldy % 8 == 0 && ((uintptr_t)y & 15) == 0 && (epi != EPI_SWIGLU || N % 16 == 0) ? 1 : 0;
-        if (route) {
-            route->add("kernel=gemm_w8_dma256_kernel<%s> splits=1 reduce=none order=super(%dx%d) epilogue=%s", epi_name(epi), gm, gn,
-                       staged ? "staged" : "direct");
-            if (route->dry) return hipSuccess;
-        }
-        static LdsOptIn once;
-        if (once.first()) set_max_lds(lds, gemm_w8_dma256_kernel<EPI_F16>, gemm_w8_dma256_kernel<EPI_F32>, gemm_w8_dma256_kernel<EPI_SWIGLU>);
-        dispatch_epi(epi, [&](auto E) {
-            hipLaunchKernelGGL((gemm_w8_dma256_kernel<E>), g256, dim3(512), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm, staged);
-        });
-        return hipGetLastError();
-    }
-    // W4: group 128 = two K tiles; one block keeps at most W4_MAXG groups of scales in LDS
-    const bool w4_fast = wq_bit == 4 && group == 128 && K % 128 == 0 &&
-                         (K / 128 <= W4_MAXG || (ws && (size_t)((K / 128 + W4_MAXG - 1) / W4_MAXG) * M * N * sizeof(float) <= ws_bytes));
-    // (Round 4, measured and removed: W4 at 128 < M <= 256 as ONE 256-row tile per weight tile -- 4 waves of 32 (n) x 256 (m), every int4
-    // fragment converted once for 16 MFMAs instead of 8 -- is SLOWER on the 70B / TP8 shapes: w13 49.1 -> 53.4 us, w2 31.5 -> 38.9 us at
-    // M = 256; 236 VGPRs and 88 KiB of LDS leave one wave per SIMD.  profiles/r04_w4_m256_sweep.log)
-    if ((wq_bit == 8 || wq_bit == 0 || w4_fast) && K % G_BK == 0 && !force_generic) {
-        static const int forced = tune_int("PPLHIP_GEMM_MAP", -1);
-        // measured (profiles/gemm_microbench.py, M = 1024): weight tiles per XCD (mode 0) beats activation slices per XCD
-        // (mode 1) by 2-4 % on every layer shape
-        int map_mode = (forced == 1 && m_tiles % 8 == 0) ? 1 : 0;
-        dim3 g2 = map_mode == 1 ? dim3((unsigned)(n_tiles * m_tiles)) : grid;
-        static const bool force_super = tune_set("PPLHIP_GEMM128_GM");  // experiments at M <= 1024
-        if (map_mode == 0 && (m_tiles > 8 || force_super)) {
-            // more than 8 activation tiles (M > 1024): walk the XCD's weight tiles in super-tiles of 12 (n) x 8 (m) -- at M = 1024 the
-            // plain order already is that shape; at M = 8192 it degenerates to 1.5 weight tiles x 64 activation tiles in flight per XCD
-            static const int forced_gm = tune_int("PPLHIP_GEMM128_GM", 0);
-            static const int forced_gn = tune_int("PPLHIP_GEMM128_GN", 0);
-            int gm = forced_gm > 0 ? forced_gm : 8;
-            while (gm > 1 && m_tiles % gm) --gm;
-            const int nl = n_tiles_pad / 8;
-            int gn = forced_gn > 0 ? forced_gn : 12;
-            if (gn > nl) gn = nl;
-            if (gm > 1 && gn <= 255 && gm <= 255) {
-                map_mode |= (gm << 16) | (gn << 24);
-                g2 = dim3((unsigned)(8 * ((nl + gn - 1) / gn * gn) * m_tiles));
-            }
-        }
-        static const int ablate = tune_int("PPLHIP_GEMM_ABLATE", 0);  // diagnosis only: wrong results
-        map_mode |= ablate << 8;
-        static const int forced_st = tune_int("PPLHIP_GEMM_STAGES", 0);
-        // few blocks per CU -> deeper ring (latency is hidden inside the block); many -> more blocks per CU
-        int stages = (int64_t)n_tiles * m_tiles <= 256 ? 4 : 2;  // measured: profiles/gemm_microbench.py
-        if (forced_st >= 2 && forced_st <= 4) stages = forced_st;
-        if (wq_bit == 0 && stages == 4) stages = 3;  // fp16 weights: 4 x 32 KiB would leave one block per CU anyway
-        // split-K for small M: too few output tiles to pull HBM bandwidth (weights must stream at full rate)
-        const int kt_all = K / G_BK;
-        int splits = 1;
-        static const int forced_split = tune_int("PPLHIP_GEMM_SPLITK", 0);
-        const int64_t tiles = (int64_t)n_tiles * m_tiles;
-        // (also at larger M when a tensor-parallel slice leaves fewer output tiles than CUs)
-        if (ws && ((M <= 256 && tiles < 512) || tiles < 200 || forced_split > 0)) {
-            // enough blocks to fill the chip, but every split writes an fp32 slab of the whole output: keep >= min_kt K
-            // tiles per split (measured at M = 64 / 256 on the 70B/TP8 shapes and M = 1024 on 7B/TP8 slices)
-            static const int env_minkt = tune_int("PPLHIP_GEMM_MINKT", 0);
-            const int target = M <= 64 ? 768 : 512;
-            splits = (int)((target + tiles - 1) / tiles);
-            const int cap = (M <= 64 || tiles <= 32) ? 8 : 4;  // (M = 128..256 sweeps: more than 4 slabs never paid)
-            if (splits > cap) splits = cap;
-            if (M > 64 && tiles >= 160) splits = 1;             // most CUs busy already: a slab costs more (176 tiles, 7B/TP8 w13: 36 vs 42 us)
-            const int min_kt = env_minkt ? env_minkt : ((M <= 64 || tiles <= 64) ? 16 : 28);
-            if (splits > kt_all / min_kt) splits = kt_all / min_kt > 0 ? kt_all / min_kt : 1;
-            if (forced_split > 0) splits = forced_split;
-            while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
-        }
-        if (wq_bit == 4 && splits < (kt_all + 2 * W4_MAXG - 1) / (2 * W4_MAXG)) splits = (kt_all + 2 * W4_MAXG - 1) / (2 * W4_MAXG);
-        int kt_per = (kt_all + splits - 1) / splits;
-        if (wq_bit == 4) kt_per = (kt_per + 1) & ~1;  // whole quantisation groups per split
-        splits = (kt_all + kt_per - 1) / kt_per;  // no empty split
-        // K slabs: two stages when several blocks share a CU; a launch of at most one block per CU keeps the deep ring (the LDS is free anyway):
-        // W8 7B at M = 256 wo 21.3 -> 19.8 us, w2 38.8 -> 33.4; 13B / TP2 at M = 512 wo 28.0 -> 24.3, w2 56.8 -> 52.1; fp16 70B / TP8 w2 30.0 ->
-        // 26.0; W4 70B / TP8 w2 31.1 -> 30.1 (profiles/r04_splitk_stages_sweep.log).  Until the last session of round 4 this line forced two
-        // stages on EVERY split launch and overrode PPLHIP_GEMM_STAGES, so the earlier stage sweeps never ran 3 / 4 stages on split shapes.
-        static const int split_deep = tune_int("PPLHIP_GEMM_SPLIT_DEEP", 1);   // 0: always two stages
-        // (W4 half-height tiles at M <= 64 are the exception: w2 of the 70B / TP8 slice 19.4 -> 21.0 us with the deep ring.)  In the steps:
-        // 7B / TP8 slice at 1024 rows 7.97 -> 7.69 ms, config 4 per rank 13.68 -> 13.54, 7B TP 1 at batch 160-512 -0.3..-1.9 % (r04_split_deep_ab.log)
-        if (splits > 1 && !(forced_st >= 2 && forced_st <= 4))
-            stages = (split_deep && tiles * splits <= 256 && !(wq_bit == 4 && M <= 64)) ? (wq_bit == 0 ? 3 : 4) : 2;
-        g2.y = splits;
-        // at most one block per CU (<= 256 blocks): 8 waves, 4 of them producers that only issue the ring's LDS-DMA (two waves
-        // per SIMD from the one block, the DMA issue runs beside the MFMA stream: wo 59 -> 46 us, w2 120 -> 95 us at
-        // M = 1024); more blocks: 4 waves of 32(n) x 128(m), two blocks per CU (the specialised form is not faster there)
-        static const int forced_wl = tune_int("PPLHIP_GEMM_WL", 0);
-        int wl = (forced_wl == 1 || forced_wl == 5) ? forced_wl : (tiles * splits <= 256 ? 5 : 1);
-        // 16 < M <= 64: half-height tiles (64 activation rows), 4-wave blocks
-        static const int forced_half = tune_int("PPLHIP_GEMM_HALF", -1);
-        const bool half = forced_half >= 0 ? (forced_half == 1 && M <= 64) : M <= 64;  // 7B layer GEMMs at M = 64: 102 -> 84 us, M = 32: 90 -> 74 us
-        if (half) wl = 1;
-        // W8, one block per CU: eight consumer waves, each group multiplying one of the two k-steps of a tile (w2 at M = 1024: 100 -> 96 us)
-        if ((forced_wl == 6 || (forced_wl == 0 && wl == 5)) && wq_bit == 8 && stages >= 3 && splits == 1) wl = 6;
-        // W8, half-height tiles: the 128-deep K tile (whole 128-byte lines of every weight row per LDS-DMA piece; gemm_w8_half128_kernel),
-        // activation sub-tile 16 / 32 / 64 rows; three stages when two blocks of them fit a CU (BM <= 32) or the grid is one block per CU
-        static const int half128 = tune_int("PPLHIP_GEMM_HALF128", 1);  // 0: off; 2: always 64-row sub-tiles
-        // ... and 64 < M <= 128 with 80- .. 128-row sub-tiles (steps of 16 rows; three stages, one block per CU) for the shapes that need split-K
-        // anyway (7B at M = 128, HBM-cold: wqkv 33.1 -> 29.3 us, wo 21.2 -> 18.9, w2 27.9 -> 26.3; w13 -- 172 tiles, no split -- stays on the
-        // 128 x 128 ring kernel with its eight consumer waves above 80 rows: 34.7 against 42.0 us at 128).  Decode step at batch 72 / 96 / 128
-        // 6.20 / 6.85 / 7.92 -> 5.70 / 6.53 / 7.76 ms.  PPLHIP_GEMM_HALF128_MAX_M=64: off
-        static const int half128_max_m = tune_int("PPLHIP_GEMM_HALF128_MAX_M", 128);
-        // split-K slabs: ONE block per CU, not three.  A slab costs 8 M N bytes (written here, read by the reduce or the consuming
-        // kernel) against N K / splits weight bytes -- at M = 64 and K / splits = 683 that is 0.75 extra bytes per weight byte, and it
-        // is written when all blocks finish together.  Measured on the 7B shapes, HBM-cold (profiles/r04_splitk_sweep.log): w13 at
-        // M = 64 with 5 / 1 slabs 37.6 / 29.9 us (and no reduce kernel), wqkv 6 / 2 slabs 25.1 / 20.7 us; wo / w2 (32 tiles) keep 8
-        static const int h_blocks = tune_int("PPLHIP_GEMM_HALF128_BLOCKS", 256);
-        int sp = splits;
-        const int kt128 = K / (G_BK * S_KS);
-        if (ws && forced_split <= 0) {
-            sp = h_blocks / n_tiles;
-            if (sp > 8) sp = 8;
-            if (sp < 1) sp = 1;
-            while (sp > 1 && (size_t)sp * M * N * sizeof(float) > ws_bytes) --sp;
-        }
-        if (sp > kt128) sp = kt128 > 0 ? kt128 : 1;
-        static const int half128_unsplit_max_m = tune_int("PPLHIP_GEMM_HALF128_UNSPLIT_MAX_M", 80);  // (w13: 80-row sub-tile 31.0-31.6 vs 32.4-32.6 us at M = 72-80, 96 rows 34.4 vs 33.1)
-        if (half128 && (half || (M <= 128 && M <= half128_max_m && (sp > 1 || M <= half128_unsplit_max_m) && m_tiles == 1)) && wq_bit == 8 && K % (G_BK * S_KS) == 0) {
-            const int kt_per128 = (kt128 + sp - 1) / sp;
-            sp = (kt128 + kt_per128 - 1) / kt_per128;
-            // (above 64 rows in steps of 16: a 72-row step on a 128-row sub-tile would pay 128 rows of LDS traffic and MFMAs)
-            const int bm = M > 64 ? (int)((M + 15) / 16 * 16) : (half128 == 2 ? 64 : (M <= 16 ? 16 : (M <= 32 ? 32 : 64)));
-            const int st = (bm <= 32 || bm > 64 || (int64_t)n_tiles * sp <= 256) ? 3 : 2;
-            const Half128Kernel hk{epi, st, bm};  // the template arguments: named in the route record and launched from the same struct
-            const size_t lds = (size_t)hk.st * ((size_t)S_KS * hk.bm * G_BK * 2 + S_WB);
-            if (route) {
-                route->add("kernel=gemm_w8_half128_kernel<%s,%d,%d> splits=%d kchunk=%d", epi_name(hk.epi), hk.st, hk.bm, sp, kt_per128 * G_BK * S_KS);
-                if (sp == 1) route->add("reduce=none");
-                else if (defer && epi == EPI_F16 && N % 8 == 0 && sp <= 8) route->add("reduce=deferred");
-                else route->add("reduce=splitk_reduce_kernel<%s>", epi_name(epi));
-                route->add("order=plain");
-                if (route->dry) return hipSuccess;
-            }
-            static LdsOptIn once;
-            if (once.first())
-                for_each_epi([](auto E) {
-                    auto opt_in = [&](auto ST, auto BM) { set_max_lds(ST * (s_xb<BM>() + S_WB), gemm_w8_half128_kernel<E, ST, BM>); };
-                    opt_in(int_c<3>{}, int_c<16>{}); opt_in(int_c<3>{}, int_c<32>{}); opt_in(int_c<2>{}, int_c<64>{}); opt_in(int_c<3>{}, int_c<64>{});
-                    opt_in(int_c<3>{}, int_c<80>{}); opt_in(int_c<3>{}, int_c<96>{}); opt_in(int_c<3>{}, int_c<112>{}); opt_in(int_c<3>{}, int_c<128>{});
-                });
-            dim3 gh((unsigned)n_tiles, (unsigned)sp);
-            dispatch_epi(hk.epi, [&](auto E) {
-                dispatch_int<16, 32, 80, 96, 112, 128, 64>(hk.bm, [&](auto BM) {
-                    auto go = [&](auto ST) {
-                        hipLaunchKernelGGL((gemm_w8_half128_kernel<E, ST, BM>), gh, dim3(256), lds, s, x, (const int8_t*)w, scale, M, N, K, y, ldy, n_tiles, kt_per128, ws);
-                    };
-                    if constexpr (BM == 64) { if (hk.st == 3) go(int_c<3>{}); else go(int_c<2>{}); }   // two stages: 64-row sub-tiles only
-                    else go(int_c<3>{});
-                });
-            });
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess || sp == 1) return e;
-            if (defer && epi == EPI_F16 && N % 8 == 0 && sp <= 8) { *defer = SplitSlabs{ws, sp, scale, N, M}; return e; }  // the consumer reduces
-            return launch_splitk_reduce(s, ws, sp, M, N, scale, y, ldy, epi);
-        }
-        // W4 with K slabs of at most 32 tiles (16 quantisation groups): the scale area shrinks from 16 to 4 KiB and three blocks fit a CU
-        static const int w4_sc16 = tune_int("PPLHIP_GEMM_W4_SC16", 1);
-        const bool w4_small_sc = w4_sc16 && wq_bit == 4 && splits > 1 && kt_per <= 32 && wl == 1 && !half && stages == 2;
-        // the ring kernel's template arguments, chosen once: the route record names them and the launch below instantiates from them
-        DmaKernel dk{wq_bit, epi, stages, 1, G_BM, W4_MAXG};
-        if (wl == 6 && wq_bit == 8 && stages >= 3) dk.wl = 6;
-        else if (wl == 5) dk.wl = 5;
-        else if (half) dk.bm = 64;
-        else if (wq_bit == 4 && stages == 2 && w4_small_sc) dk.maxg = 16;
-        if (route) {
-            char tail[16] = "";  // the defaulted arguments BM and MAXG appear only where they differ
-            if (dk.maxg != W4_MAXG) snprintf(tail, sizeof tail, ",%d,%d", dk.bm, dk.maxg);
-            else if (dk.bm != G_BM) snprintf(tail, sizeof tail, ",%d", dk.bm);
-            route->add("kernel=gemm_dma_kernel<%d,%s,%d,%d%s>", dk.wq, epi_name(dk.epi), dk.stages, dk.wl, tail);
-            route->add("splits=%d kchunk=%d", splits, kt_per * G_BK);
-            if (splits == 1) route->add("reduce=none");
-            else if (defer && epi == EPI_F16 && N % 8 == 0 && splits <= 8) route->add("reduce=deferred");
-            else route->add("reduce=splitk_reduce_kernel<%s>", epi_name(epi));
-            if ((map_mode & 0xff) == 1) route->add("order=xcd_m");
-            else if ((map_mode >> 16) & 0xff) route->add("order=super(%dx%d)", (map_mode >> 16) & 0xff, (map_mode >> 24) & 0xff);
-            else route->add("order=plain");
-            if (route->dry) return hipSuccess;
-        }
-        dispatch_int<8, 4, 0>(dk.wq, [&](auto WQ) {
-            dispatch_epi(dk.epi, [&](auto E) {
-                dispatch_int<2, 3, 4>(dk.stages, [&](auto ST) {
-                    auto go = [&](auto kernel, unsigned threads) {
-                        hipLaunchKernelGGL(kernel, g2, dim3(threads), 0, s, x, w, scale, M, N, K, y, ldy, n_tiles, m_tiles, map_mode, kt_per, ws);
-                    };
-                    if constexpr (WQ == 8 && ST >= 3) {
-                        if (dk.wl == 6) return go(gemm_dma_kernel<WQ, E, ST, 6>, 768);
-                    }
-                    if (dk.wl == 5) go(gemm_dma_kernel<WQ, E, ST, 5>, 512);
-                    else if (dk.bm == 64) go(gemm_dma_kernel<WQ, E, ST, 1, 64>, 256);
-                    else if (dk.maxg == 16) go(gemm_dma_kernel<WQ, E, ST, 1, G_BM, 16>, 256);
-                    else go(gemm_dma_kernel<WQ, E, ST, 1>, 256);
-                });
-            });
-        });
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess || splits == 1) return e;
-        if (defer && epi == EPI_F16 && N % 8 == 0 && splits <= 8) { *defer = SplitSlabs{ws, splits, wq_bit == 8 ? scale : nullptr, N, M}; return e; }
-        return launch_splitk_reduce(s, ws, splits, M, N, wq_bit == 8 ? scale : nullptr, y, ldy, epi);
-    }
-    if (wq_bit != 0 && wq_bit != 8 && wq_bit != 4) return hipErrorInvalidValue;
+    LinearProblem pr;
+    pr.wq_bit = wq_bit, pr.group = group, pr.M = M, pr.N = N, pr.K = K, pr.ldy = ldy;
+    pr.epi = swiglu ? EPI_SWIGLU : (out_fp32 ? EPI_F32 : EPI_F16);
+    pr.ws_bytes = ws ? ws_bytes : 0;
+    pr.accept_defer = defer != nullptr;
+    pr.x = (uintptr_t)x, pr.w = (uintptr_t)w, pr.scale = (uintptr_t)scale, pr.y = (uintptr_t)y;
+    if (!linear_problem_valid(pr)) return hipErrorInvalidValue;
+    static const LinearTuning tuning = LinearTuning::from_env();
+    const LinearPlan plan = plan_linear(pr, tuning);
+    if (!plan.ok) return hipErrorInvalidValue;
     if (route) {
-        route->add("kernel=gemm_kernel<%d,%s> splits=1 reduce=none order=plain", wq_bit, epi_name(epi));
+        char text[512];
+        format_route(plan, text, (int)sizeof text);
+        route->add("%s", text);
         if (route->dry) return hipSuccess;
     }
-    dispatch_int<0, 8, 4>(wq_bit, [&](auto WQ) {
-        dispatch_epi(epi, [&](auto E) {
-            hipLaunchKernelGGL((gemm_kernel<WQ, E>), grid, block, 0, s, x, w, scale, M, N, K, group, y, ldy, n_tiles, m_tiles);
-        });
-    });
-    return hipGetLastError();
+    const uint16_t* rscale = wq_bit == 8 ? scale : nullptr;   // the channel scales a reduce applies
+    for (int i = 0; i < plan.n_parts; ++i) {
+        const LinearPart& p = plan.part[i];
+        const LinearArgs a{s, x + p.m0 * K, w, scale, group, N, K, (char*)y + (size_t)p.m0 * ldy * (out_fp32 ? 4 : 2), ldy, ws};
+        hipError_t e = hipSuccess;
+        bool sub = false;   // a sub-launcher checked its own launch
+        switch (p.family) {
+            case LF_GEMV_STREAM: sub = true, e = launch_gemv_stream(s, a.x, w, scale, wq_bit, group, p.M, N, K, a.y, ldy, p.epi); break;
+            case LF_W4_PC: sub = true, e = launch_linear_w4_pc(s, a.x, w, scale, p.M, N, K, a.y, ldy, p.epi); break;
+            case LF_W8_WIDE: sub = true, e = launch_linear_w8_wide(s, a.x, (const int8_t*)w, scale, p.M, N, K, a.y, ldy, p.epi, p.nc); break;
+            case LF_GEMV: run_gemv(p, a); break;
+            case LF_W8_256: run_w8_256(p, a); break;
+            case LF_W8_HALF128: run_w8_half128(p, a); break;
+            case LF_RING: run_ring(p, a); break;
+            case LF_GENERIC: run_generic(p, a); break;
+        }
+        if (!sub) e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        // split-K: the slabs go to the consumer (defer) or through the reduce kernel
+        if (p.reduce == LR_DEFERRED) *defer = SplitSlabs{ws, p.splits, rscale, N, p.M};
+        else if (p.reduce == LR_KERNEL && (e = launch_splitk_reduce(s, ws, p.splits, p.M, N, rscale, a.y, ldy, p.epi)) != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace pplhip

@@ -1,12 +1,11 @@
-// Device side of the tile GEMM (128 x 128 x 64, LDS-DMA ring): constants, epilogues, conversion helpers and the block body
-// gemm_dma_body; k_gemm.hip wraps it into the kernels and k_gemm_i8.hip shares the helpers.
+// Device side of the tile GEMMs (LDS-DMA rings): tile order, epilogues, ring wait, conversion helpers and the block body gemm_dma_body
+// of the 128 x 128 x 64 kernel; k_gemm.hip wraps it into the kernels, k_gemm_wide.hip, k_gemm_pc.hip, k_gemv.hip and k_gemm_i8.hip share the
+// helpers.  The tile sizes are in k_gemm_tiles.h.
 #pragma once
 #include "kernels.h"
 #include "k_launch.h"
 
 namespace pplhip {
-
-constexpr int G_BN = 128, G_BM = 128, G_BK = 64;
 
 __device__ __forceinline__ int g_swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
@@ -14,7 +13,8 @@ __device__ __forceinline__ int g_swz(int row, int chunk) { return chunk ^ ((row 
 // (gate_0, up_0, gate_1, up_1, ...), so the 4 consecutive output channels a lane owns are two (gate, up) pairs and the
 // lane writes silu(gate) * up for both: y is then [M, N/2] (K10 fused into the producing GEMM; numerics as the separate
 // kernel: gate and up are rounded to fp16 first).
-enum { EPI_F16 = 0, EPI_F32 = 1, EPI_SWIGLU = 2 };
+// (The wave-tile loops around store4 -- scales as one uint2, NI x NJ tiles -- and the fp32 slab store stay written out in each kernel: as
+// one shared function they changed the instruction selection of every kernel that used them, against the bar of profiles/asm_compare.py.)
 template <int EPI>
 __device__ __forceinline__ void store4(void* yv, int64_t ldy, int64_t m, int n, float v0, float v1, float v2, float v3) {
     if constexpr (EPI == EPI_F32) {
@@ -37,6 +37,56 @@ inline void dispatch_epi(int epi, F&& f) {
 }
 template <class F>
 inline void for_each_epi(F&& f) { f(int_c<EPI_F16>{}); f(int_c<EPI_F32>{}); f(int_c<EPI_SWIGLU>{}); }
+// route record of a sub-launcher called on its own: its part's text (format_route, linear_plan.h); true: a dry run, nothing to launch
+inline bool route_part(LinearRoute* route, const LinearPart& p) {
+    if (!route) return false;
+    char text[256];
+    format_route(p, text, (int)sizeof text);
+    route->add("%s", text);
+    return route->dry;
+}
+
+// Block -> (weight tile nt, activation tile mt).  Block b runs on XCD b % 8 (MI355X_MICROARCH), so XCD x = id % 8 owns the weight tiles
+// n == x (mod 8): its L2 serves a weight tile to all the M tiles that share it.  nt >= n_tiles: a block of the padding that rounds the XCD's
+// share of weight tiles up (the kernel returns at once).
+struct XcdSlot { int xcd, slot; };
+__device__ __forceinline__ XcdSlot xcd_slot(int id) { return XcdSlot{id & 7, id >> 3}; }
+// The walk of one XCD, slot -> (q, mt): its q-th weight tile (nt = xcd + 8 q) and the activation tile.
+// plain order: for each of its weight tiles, all m tiles
+__device__ __forceinline__ void walk_plain(int slot, int m_tiles, int& q, int& mt) {
+    q = slot / m_tiles;
+    mt = slot % m_tiles;
+}
+// super-tiles of gn (n) x gm (m) tiles (gm divides m_tiles), m fastest inside a super-tile, super-tiles m-major: the blocks an XCD runs at a
+// time then share gn weight and gm activation tiles per K step instead of 1 and all (gn = 1, gm = m_tiles: the plain order)
+__device__ __forceinline__ void walk_super(int slot, int m_tiles, int gn, int gm, int& q, int& mt) {
+    const int per_super = gn * gm, sm_count = m_tiles / gm;
+    const int sup = slot / per_super, within = slot % per_super;
+    q = (sup / sm_count) * gn + within / gm;
+    mt = (sup % sm_count) * gm + within % gm;
+}
+__device__ __forceinline__ void xcd_tile(int id, int m_tiles, int& nt, int& mt) {
+    const XcdSlot b = xcd_slot(id);
+    int q;
+    walk_plain(b.slot, m_tiles, q, mt);
+    nt = b.xcd + 8 * q;
+}
+__device__ __forceinline__ void xcd_super_tile(int id, int m_tiles, int gn, int gm, int& nt, int& mt) {
+    const XcdSlot b = xcd_slot(id);
+    int q;
+    walk_super(b.slot, m_tiles, gn, gm, q, mt);
+    nt = b.xcd + 8 * q;
+}
+
+// Wait of a DMA ring whose waves issue PT LDS-DMA instructions per tile: "all but the newest PT * younger have landed" == the oldest
+// tile in flight is complete when `younger` younger tiles have been issued (prefetch distance <= 3)
+template <int PT>
+__device__ __forceinline__ void ring_wait(int younger, bool never = false) {   // never: the ablation that issues the DMA and does not wait
+    if (never) {}
+    else if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PT) : "memory");
+    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // W8A16 fast path (K % 64 == 0): both operands go global -> LDS by DMA (global_load_lds_dwordx4: no staging VGPRs, no
@@ -77,22 +127,13 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
 
-constexpr int W4_MAXG = 64;  // W4: quantisation groups (of 128 along K) whose scales one block keeps in LDS
-
-// WL = wave layout of the 128x128x64 block tile:
-//   0: 4 waves, 2x2, each 64(n) x 64(m);  1: 4 waves, 4x1, each 32(n) x 128(m) x k64;
+// WL = wave layout of the 128x128x64 block tile (1, 5 or 6: every multiplying wave owns 32 weight rows and all activation rows of the tile, so
+// each weight fragment is converted (int8/int4 -> fp16) by exactly one wave and feeds NJ MFMAs):
+//   1: 4 waves, 4x1, each 32(n) x 128(m) x k64;
 //   5: 8 waves: 4 consumers with the layout of 1 and 4 producers that do nothing but issue the ring's LDS-DMA;
 //   6: 12 waves: 8 consumers -- the four of 5 twice, group h multiplying only k-step h of every K tile (two consumer waves per SIMD whose
 //      read / convert / MFMA chains overlap), partial sums added through LDS at the end -- and 4 producers; needs G_ST >= 3;
-// WQ = 8: int8 weights + per-channel scale; WQ = 0: fp16; WQ = 4: int4, group 128
-// LDS bytes gemm_dma_body needs
-// MAXG (W4): quantisation groups whose scales the block keeps in LDS -- W4_MAXG, or 16 for launches whose K slabs span at most 32 tiles
-// (44 instead of 56 KiB with two stages: three blocks per CU instead of two)
-template <int WQ, int G_ST, int BM = G_BM, int MAXG = W4_MAXG>
-constexpr int gemm_dma_lds_bytes() {
-    constexpr int WB2 = WQ == 8 ? 2 : (WQ == 4 ? 1 : 4);
-    return G_ST * (BM * G_BK * 2 + G_BN * G_BK * WB2 / 2) + (WQ == 4 ? MAXG * G_BN * 2 : 0);
-}
+// WQ = 8: int8 weights + per-channel scale; WQ = 0: fp16; WQ = 4: int4, group 128.  LDS bytes: gemm_dma_lds_bytes (k_gemm_tiles.h)
 
 // BM = 64 (WL 1 only): half-height tile for 16 < M <= 64 -- half the activation bytes per stage and half the MFMAs of a 128-row tile whose
 // upper half would only repeat row M - 1
@@ -105,6 +146,7 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
     constexpr int WB2 = WQ == 8 ? 2 : (WQ == 4 ? 1 : 4);   // half-bytes per weight element
     constexpr int W_STAGE = G_BN * G_BK * WB2 / 2;         // 8 KiB (int8) / 16 KiB (fp16) / 4 KiB (int4)
     constexpr int NT = 256;                                // threads that move tile pieces (WL 5: the 4 producer waves)
+    static_assert(WL == 1 || WL == 5 || WL == 6, "wave layouts: 4 waves, 4 + 4 producers, 8 + 4 producers");
     static_assert(BM == G_BM || (BM == 64 && WL == 1), "half-height tiles: 4-wave layout only");
     constexpr int X_DMA = BM * G_BK * 2 / (NT * 16);       // DMA instructions per wave per tile for X (4; 2 at BM = 64)
     constexpr int W_DMA = W_STAGE / (NT * 16);             // ... for W (2 int8, 4 fp16, 1 int4)
@@ -115,29 +157,22 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
     uint16_t* const Sc = reinterpret_cast<uint16_t*>(smem + G_ST * (BM * G_BK * 2 + W_STAGE));
     const char* w = reinterpret_cast<const char*>(wv);
 
-    // block -> tile.  map_mode 1 (m_tiles % 8 == 0): XCD x = id % 8 owns the activation row-tiles m == x (mod 8) and
+    // block -> tile.  map.order 1 (m_tiles % 8 == 0): XCD x = id % 8 owns the activation row-tiles m == x (mod 8) and
     // walks all weight tiles, so its 4 MiB L2 keeps that 1 MiB activation slice resident for the whole GEMM and the
-    // weights stream through once per XCD.  map_mode 0: XCD x owns weight tiles n == x (mod 8) and walks all m tiles.
-    const int id = block_id;
-    const int xcd = id & 7, slot = id >> 3;
+    // weights stream through once per XCD.  order 0: XCD x owns weight tiles n == x (mod 8) and walks all m tiles, plainly or (map.gm != 0)
+    // in super-tiles: the ~96 blocks an XCD runs at a time then share gn weight and gm activation tiles per K step
+    const MapMode map = map_unpack(map_mode);
+    const XcdSlot b = xcd_slot(block_id);
     int nt, mt;
-    if ((map_mode & 0xff) == 1) {
+    if (map.order == 1) {
         const int mg = m_tiles >> 3;
-        mt = xcd + 8 * (slot % mg);
-        nt = slot / mg;
+        mt = b.xcd + 8 * (b.slot % mg);
+        nt = b.slot / mg;
     } else {
-        // super-tiles of gn (n) x gm (m) tiles, m fastest inside, super-tiles m-major (gm = m_tiles: the plain n-major walk).  The ~96 blocks
-        // an XCD runs at a time then share gn weight and gm activation tiles per K step (k_gemm.hip, gemm_w8_dma256_kernel)
-        const int gm = (map_mode >> 16) & 0xff, gn = (map_mode >> 24) & 0xff;
-        if (gm == 0) {
-            nt = xcd + 8 * (slot / m_tiles);
-            mt = slot % m_tiles;
-        } else {
-            const int per_super = gn * gm, sm_count = m_tiles / gm;
-            const int sup = slot / per_super, within = slot % per_super;
-            nt = xcd + 8 * ((sup / sm_count) * gn + within / gm);
-            mt = (sup % sm_count) * gm + within % gm;
-        }
+        int q;
+        if (map.gm == 0) walk_plain(b.slot, m_tiles, q, mt);
+        else walk_super(b.slot, m_tiles, map.gn, map.gm, q, mt);
+        nt = b.xcd + 8 * q;
     }
     if (nt >= n_tiles) return;
     const int n0 = nt * G_BN;
@@ -149,11 +184,8 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
     const int tid = PC ? (threadIdx.x & 255) : threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kh = WL == 6 ? (int)((threadIdx.x >> 8) & 1) : 0;  // WL 6: the k-step of every tile this consumer multiplies
     const int l15 = lane & 15, kq = lane >> 4;
-    // WL 1: every wave owns 32 weight rows and all 128 activation rows of the tile, so each weight fragment is converted
-    // (int8/int4 -> fp16) by exactly one wave and feeds 8 MFMAs; WL 0 converts every fragment in two waves for 4 MFMAs
-    constexpr int NI = WL ? 2 : 4, NJ = WL ? BM / 16 : 4;
-    const int wn = WL ? wave : wave >> 1, wm = WL ? 0 : wave & 1;
-    const int nb = wn * (NI * 16), mb = wm * (NJ * 16);  // row bases of this wave inside the tile
+    constexpr int NI = 2, NJ = BM / 16;   // wave tile: 32 weight rows x all activation rows
+    const int nb = wave * (NI * 16);      // first weight row of this wave inside the tile
 
     // per-lane DMA sources (constant over K except for the k0 term)
     const uint16_t* xsrc[X_DMA];
@@ -239,11 +271,7 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
         // The LDS-DMA issue (~100 cycles per piece for the issuing wave) now runs beside the consumers' MFMA stream on
         // the SIMD instead of in front of it.
         for (int t = 0; t < ktiles; ++t) {
-            const int younger = (ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1);
-            constexpr int PT = X_DMA + W_DMA;
-            if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PT) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ring_wait<X_DMA + W_DMA>((ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1));
             __syncthreads();
             if (t + D < ktiles) issue(stn, (kt0 + t + D) * G_BK);
             stn = stn == G_ST - 1 ? 0 : stn + 1;
@@ -253,15 +281,11 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
     }
     for (int t = 0; t < ktiles; ++t) {
         const int younger = (ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1);
-        if constexpr (!PC) {   // every wave issues PT = X_DMA + W_DMA DMA instructions per tile
-            constexpr int PT = X_DMA + W_DMA;
-            if (map_mode & 0x200) {}  // ablation 2 (PPLHIP_GEMM_ABLATE=2, wrong results): the DMA is issued but never waited for
-            else if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PT) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (!PC) {   // every wave issues X_DMA + W_DMA DMA instructions per tile
+            ring_wait<X_DMA + W_DMA>(younger, map.ablate & 2);  // ablation 2 (PPLHIP_GEMM_ABLATE=2, wrong results): the DMA is issued but never waited for
         }
         __syncthreads();  // tile t is published; the stage read during iteration t-1 (== stage of tile t+D) is free
-        if constexpr (!PC) if (t + D < ktiles && !(map_mode & 0x100)) issue(stn, (kt0 + t + D) * G_BK);  // 0x100: ablation (PPLHIP_GEMM_ABLATE)
+        if constexpr (!PC) if (t + D < ktiles && !(map.ablate & 1)) issue(stn, (kt0 + t + D) * G_BK);  // ablation 1 (PPLHIP_GEMM_ABLATE): no refills
         const uint16_t* xs = Xs0 + st * (BM * G_BK);
         const char* wq = Wq0 + st * W_STAGE;
         st = st == G_ST - 1 ? 0 : st + 1;
@@ -306,7 +330,7 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
             }
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const int row = mb + j * 16 + l15;
+                const int row = j * 16 + l15;
                 bfr[j] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4*>(&xs[row * G_BK + g_swz(row, ks * 4 + kq) * 8]));
             }
 #ifdef GEMM_SETPRIO
@@ -351,7 +375,7 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
             if (n >= N) continue;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const int64_t m = m0 + mb + j * 16 + l15;
+                const int64_t m = m0 + j * 16 + l15;
                 if (m < M) *reinterpret_cast<float4*>(slab + m * N + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
             }
         }
@@ -365,7 +389,7 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
         if constexpr (WQ == 8) sh = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(scale + n));
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            const int64_t m = m0 + mb + j * 16 + l15;
+            const int64_t m = m0 + j * 16 + l15;
             if (m >= M) continue;
             store4<EPI>(yv, ldy, m, n, acc[i][j][0] * (float)sh[0], acc[i][j][1] * (float)sh[1], acc[i][j][2] * (float)sh[2],
                         acc[i][j][3] * (float)sh[3]);
@@ -379,7 +403,7 @@ __device__ __forceinline__ void gemm_dma_body(const uint16_t* __restrict__ x, co
 //   grid = N / 16 weight-row tiles; block = 4 waves = 4 contiguous K slices of that tile, summed through LDS;
 //   a wave-load fetches 16 rows x 64 contiguous bytes; lane (row = lane & 15, kq = lane >> 4) multiplies its 16 bytes
 //   (int8: 16 k, two MFMA k-steps; fp16: 8 k; int4: 32 k, four k-steps) against the matching activation fragment
-//   (activations are tiny and L1/L2 resident); up to MT = 2 row tiles of 16 activations reuse each weight fragment.
+//   (activations are tiny and L1/L2 resident).
 // ---------------------------------------------------------------------------------------------------------------
 
 }  // namespace pplhip

@@ -197,16 +197,6 @@ __device__ __forceinline__ void store_wave_tile(void* yv, int64_t ldy, const flo
     }
 }
 
-// block -> (weight tile nt, activation tile mt): the M tiles of one weight tile run on one XCD (block b -> XCD b % 8).  false: a block
-// of the padding that rounds the weight tiles up to 8
-__device__ __forceinline__ bool xcd_tile(int n_tiles, int m_tiles, int& nt, int& mt) {
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    nt = xcd + 8 * (slot / m_tiles);
-    mt = slot % m_tiles;
-    return nt < n_tiles;
-}
-
 // LDS-DMA source of lane position p (16-byte chunk p & 7 of tile row p >> 3) of a [rows][128 B] tile that starts at row row0 of the
 // matrix base [nrows][K]: rows past the matrix repeat its last row (never stored), the chunk is XOR-swizzled on the source side (the
 // DMA writes LDS linearly)
@@ -228,7 +218,8 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
     extern __shared__ __attribute__((aligned(16))) char smem_i8[];  // ST x (X 16 KiB) then ST x (W 16 KiB)
     constexpr int TILE = I_BM * I_BK;
     int nt, mt;
-    if (!xcd_tile(n_tiles, m_tiles, nt, mt)) return;
+    xcd_tile((int)blockIdx.x, m_tiles, nt, mt);
+    if (nt >= n_tiles) return;
     const int n0 = nt * I_BN;
     const int64_t m0 = (int64_t)mt * I_BM;
     const bool producer = threadIdx.x >= 256;
@@ -258,10 +249,7 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
             if (d < ktiles) issue(d, d * I_BK);
         int stn = D % ST;
         for (int t = 0; t < ktiles; ++t) {
-            const int younger = (ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1);
-            if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PT) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ring_wait<PT>((ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1));
             __syncthreads();
             if (t + D < ktiles) issue(stn, (t + D) * I_BK);
             stn = stn == ST - 1 ? 0 : stn + 1;
@@ -300,7 +288,8 @@ __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(cons
                                                                              int n_tiles, int m_tiles) {
     extern __shared__ __attribute__((aligned(16))) char smem_i8[];  // IW_ST x (X 16 KiB) then IW_ST x (W 48 KiB)
     int nt, mt;
-    if (!xcd_tile(n_tiles, m_tiles, nt, mt)) return;
+    xcd_tile((int)blockIdx.x, m_tiles, nt, mt);
+    if (nt >= n_tiles) return;
     const int n0 = nt * IW_BN;
     const int64_t m0 = (int64_t)mt * I_BM;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -360,14 +349,10 @@ __global__ __launch_bounds__(512) void gemm_i8_256_kernel(const int8_t* __restri
                                                           int gn, int gm) {
     extern __shared__ __attribute__((aligned(16))) char smem_i8[];  // ST x (X 16 KiB) then ST x (W 16 KiB)
     constexpr int TILE = 256 * 64;
-    // XCD id % 8 walks its weight tiles in super-tiles of gn (n) x gm (m) tiles (k_gemm.hip, gemm_w8_dma256_kernel): the blocks it runs at a
-    // time share gn weight and gm activation tiles per K step
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int per_super = gn * gm, sm_count = m_tiles / gm;
-    const int sup = slot / per_super, within = slot % per_super;
-    const int nt = xcd + 8 * ((sup / sm_count) * gn + within / gm);
-    const int mt = (sup % sm_count) * gm + within % gm;
+    // XCD id % 8 walks its weight tiles in super-tiles of gn (n) x gm (m) tiles (xcd_super_tile): the blocks it runs at a time share gn
+    // weight and gm activation tiles per K step
+    int nt, mt;
+    xcd_super_tile((int)blockIdx.x, m_tiles, gn, gm, nt, mt);
     if (nt >= n_tiles) return;
     const int n0 = nt * 256;
     const int64_t m0 = (int64_t)mt * 256;
@@ -419,10 +404,7 @@ __global__ __launch_bounds__(512) void gemm_i8_256_kernel(const int8_t* __restri
         if (d < ktiles) issue(d, d * 64);
     int st = 0, stn = D % ST;
     for (int t = 0; t < ktiles; ++t) {
-        const int younger = (ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1);
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PT) : "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ring_wait<PT>((ktiles - 1 - t) < (D - 1) ? (ktiles - 1 - t) : (D - 1));
         __syncthreads();
         if (t + D < ktiles) issue(stn, (t + D) * 64);
         const char* sb = smem_i8 + st * TILE;

@@ -38,14 +38,7 @@ namespace {
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 
-constexpr int PC_BM = 128, PC_BN = 64;
-constexpr int PC_XT = PC_BM * 64 * 2;   // one 64-deep activation tile: 16 KiB
-constexpr int PC_XB = 2 * PC_XT;        // activation bytes per super-tile: 32 KiB
-constexpr int PC_NS = 4;                // ring slots (activations, raw weights, scales), super-tiles
-constexpr int PC_RAWB = PC_BN * 64;     // raw int4 bytes per super-tile: 4 KiB (1 KiB per producer wave)
-constexpr int PC_SCB = 1024;            // scale slot: one dword per producer lane
-constexpr int PC_LDS = PC_NS * (PC_XB + PC_RAWB + PC_SCB);
-static_assert(PC_LDS <= 160 * 1024, "one block per CU");
+// (tile and ring sizes PC_BM .. PC_LDS: k_gemm_tiles.h)
 
 // LDS-DMA, 16 / 4 bytes per lane: wave-uniform 64-bit base in SGPRs + per-lane 32-bit byte offset (the per-tile address update is
 // then scalar arithmetic).  M0 written and restored in the same statement (cdna_hip_programming.md 5.7).
@@ -101,9 +94,8 @@ __global__ __launch_bounds__(512) void gemm_w4_pc_kernel(const uint16_t* __restr
     char* const Scl = Raw + PC_NS * PC_RAWB;
 
     // XCD id % 8 owns the weight tiles n == id (mod 8); the m tiles of a weight tile are neighbours on that XCD (its L2 serves the second)
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int nt = xcd + 8 * (slot / m_tiles), mt = slot % m_tiles;
+    int nt, mt;
+    xcd_tile((int)blockIdx.x, m_tiles, nt, mt);
     if (nt >= n_tiles) return;
     const int n0 = nt * PC_BN;
     const int64_t m0 = (int64_t)mt * PC_BM;
@@ -366,30 +358,16 @@ __global__ __launch_bounds__(512) void gemm_w4_pc_kernel(const uint16_t* __restr
 
 }  // namespace
 
-// Shapes this kernel takes: int4 weights in groups of 128, K % 128 == 0, N % 4 == 0 (N % 16 == 0 with the fused SwiGLU), 16-byte aligned
-// output rows, 32-bit byte offsets inside x and w.
-bool linear_w4_pc_supported(int group, int64_t M, int N, int K, const void* x, const void* w, const void* scale, const void* y, int64_t ldy, int epi) {
-    if (group != 128 || K % 128 || K < 128 || N % 4 || M < 1) return false;
-    if (epi != EPI_F16 && epi != EPI_SWIGLU) return false;
-    if (epi == EPI_SWIGLU && N % 16) return false;
-    if (ldy % 8 || ((uintptr_t)y & 15)) return false;
-    // the LDS-DMA fetches x and w in 16-byte pieces and the scale as the aligned dword around fp16 element n G + g
-    if (((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)scale & 3)) return false;
-    if ((uint64_t)M * (uint64_t)K * 2 >= (1ull << 32) || (uint64_t)N * (uint64_t)K / 2 >= (1ull << 32)) return false;
-    if ((uint64_t)N * (uint64_t)(K / 128) >= (1ull << 30)) return false;
-    return true;
-}
-
+// The shapes this kernel takes: linear_w4_pc_supported (linear_plan.h); grid from plan_w4_pc, the part plan_linear holds for this family
 hipError_t launch_linear_w4_pc(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int64_t M, int N, int K, void* y,
                                int64_t ldy, int epi, LinearRoute* route) {
-    const int n_tiles = (N + PC_BN - 1) / PC_BN, m_tiles = (int)((M + PC_BM - 1) / PC_BM);
-    if (route) {
-        route->add("kernel=gemm_w4_pc_kernel<%s> splits=1 reduce=none order=plain", epi_name(epi));
-        if (route->dry) return hipSuccess;
-    }
+    LinearPart p;
+    plan_w4_pc(M, N, epi, &p);
+    if (route_part(route, p)) return hipSuccess;
+    const int n_tiles = p.n_tiles, m_tiles = p.m_tiles;
     static LdsOptIn once;
     if (once.first()) set_max_lds(PC_LDS, gemm_w4_pc_kernel<EPI_F16>, gemm_w4_pc_kernel<EPI_SWIGLU>);
-    dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles)), block(512);
+    dim3 grid(p.grid_x), block(p.threads);
     const uint8_t* wq = reinterpret_cast<const uint8_t*>(w);
 #ifdef PC_ABLATE_BUILD
     const int abl = getenv("PPLHIP_PC_ABL") ? atoi(getenv("PPLHIP_PC_ABL")) : 0;

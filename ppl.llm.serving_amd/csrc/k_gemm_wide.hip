@@ -13,8 +13,7 @@ namespace pplhip {
 
 namespace {
 
-constexpr int WD_BM = 128, WD_NP = 4;
-constexpr int WD_XB = WD_BM * G_BK * 2;   // activation bytes per stage: 16 KiB
+// (WD_BM = 128 activation rows, WD_NP = 4 producer waves, WD_XB = 16 KiB of activations per stage: k_gemm_tiles.h)
 constexpr int WD_XP = WD_XB / 1024;       // = 16 one-KiB DMA pieces
 
 // 16 waves: 12 consumers (wave w: weight rows 32 w .. + 32 x all 128 activation rows) and 4 producers (one per SIMD) that do nothing
@@ -31,10 +30,8 @@ __global__ __launch_bounds__((NC + WD_NP) * 64) void gemm_w8_wide_kernel(const u
     char* const Xs0 = smem_wd;
     char* const Wq0 = smem_wd + ST * WD_XB;
 
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;  // XCD id % 8 owns the weight tiles n == xcd (mod 8) and all their m tiles
-    const int nt = xcd + 8 * (slot / m_tiles);
-    const int mt = slot % m_tiles;
+    int nt, mt;
+    xcd_tile((int)blockIdx.x, m_tiles, nt, mt);
     if (nt >= n_tiles) return;
     const int n0 = nt * WD_BN;
     const int64_t m0 = (int64_t)mt * WD_BM;
@@ -158,32 +155,19 @@ __global__ __launch_bounds__((NC + WD_NP) * 64) void gemm_w8_wide_kernel(const u
 
 }  // namespace
 
-// 12 consumer waves when the 128 x 384 tiles fill whole rounds of 256 one-per-CU blocks well enough, else 0 (the 128 x 128 kernel with its three
-// independent blocks per CU is the better choice).  Narrower blocks were measured and lose: w13 at M = 1024 (N = 22016) with 11 consumer waves
-// (504 blocks, two almost full rounds) 205-208 us against 191-194 us with 12 (464 blocks) -- the round time does not shrink with the tile.
-int linear_w8_wide_waves(int64_t M, int N) {
-    const int64_t m_tiles = (M + WD_BM - 1) / WD_BM;
-    const int64_t tiles = (N + 383) / 384 * m_tiles, rounds = (tiles + 255) / 256;
-    const double eff = (double)N * (double)M / ((double)rounds * 256.0 * 384.0 * WD_BM);
-    // measured: with more than two rounds the 128 x 128 kernel catches up (w13 at M = 2048: 4 rounds 382 us against 367 us) unless the fit is exact
-    return (eff >= 0.85 && (rounds <= 2 || eff >= 0.97)) ? 12 : 0;
-}
-
-// W8A16, K % 64 == 0, N % 4 == 0.  epi: EPI_F16 / EPI_F32 / EPI_SWIGLU; nc from linear_w8_wide_waves
+// W8A16, K % 64 == 0, N % 4 == 0.  epi: EPI_F16 / EPI_F32 / EPI_SWIGLU; nc from linear_w8_wide_waves (linear_plan.h); grid and LDS from
+// plan_w8_wide, the part plan_linear holds for this family
 hipError_t launch_linear_w8_wide(hipStream_t s, const uint16_t* x, const int8_t* w, const uint16_t* scale, int64_t M, int N, int K, void* y,
                                  int64_t ldy, int epi, int nc, LinearRoute* route) {
-    if (nc != 12) return hipErrorInvalidValue;
-    const int bn = 32 * nc;
-    const int n_tiles = (N + bn - 1) / bn, m_tiles = (int)((M + WD_BM - 1) / WD_BM);
-    constexpr int ST = 3;
-    const size_t lds = (size_t)ST * (WD_XB + bn * G_BK);
-    if (route) {
-        route->add("kernel=gemm_w8_wide_kernel<%s,%d,%d> splits=1 reduce=none order=plain", epi_name(epi), ST, nc);
-        if (route->dry) return hipSuccess;
-    }
+    LinearPart p;
+    if (!plan_w8_wide(M, N, epi, nc, &p)) return hipErrorInvalidValue;
+    if (route_part(route, p)) return hipSuccess;
+    constexpr int ST = WD_ST;
+    const size_t lds = p.lds;
+    const int n_tiles = p.n_tiles, m_tiles = p.m_tiles;
     static LdsOptIn once;
-    if (once.first()) set_max_lds(lds, gemm_w8_wide_kernel<EPI_F16, ST, 12>, gemm_w8_wide_kernel<EPI_F32, ST, 12>, gemm_w8_wide_kernel<EPI_SWIGLU, ST, 12>);
-    dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles));
+    if (once.first()) for_each_epi([&](auto E) { set_max_lds(lds, gemm_w8_wide_kernel<E, ST, 12>); });
+    dim3 grid(p.grid_x);
 #ifdef WD_ABLATE_BUILD  // diagnosis (wrong results): PPLHIP_GEMM_WIDE_ABLATE = 1 no refills, 2 no conversion, 4 one activation row, 8 no barriers
     static const int abl = getenv("PPLHIP_GEMM_WIDE_ABLATE") ? atoi(getenv("PPLHIP_GEMM_WIDE_ABLATE")) : 0;   // (an ablation build reads its switch itself: no TUNING=1 needed)
     bool ablated = true;

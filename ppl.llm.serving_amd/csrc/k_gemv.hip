@@ -21,8 +21,7 @@ namespace pplhip {
 
 namespace {
 
-constexpr int GV_NW = 8, GV_RB = 16, GV_U = 8;  // most waves per block, most weight rows per wave, rows in flight per wave
-
+// (GV_NW = 8 waves per block at most, GV_RB = 16 weight rows per wave at most, GV_U = 8 rows in flight per wave: k_gemm_tiles.h)
 template <int WQ>
 struct GvCfg {
     static constexpr int KL = WQ == 8 ? 16 : (WQ == 4 ? 32 : 8);   // k elements in a lane's 16 bytes
@@ -174,47 +173,19 @@ __global__ __launch_bounds__(NW * 64) void gemv_stream_kernel(const uint16_t* __
 
 }  // namespace
 
-// largest M this kernel takes; 0 when the shape does not fit it (the caller then uses the tile kernels)
-int gemv_stream_max_m(int wq_bit, int group, int N, int K) {
-    // default: 4 rows; 2 for int8 weights that the half-height tile kernel of k_gemm.hip takes (K % 128 == 0) -- with 16-row activation
-    // sub-tiles and one block per CU it overtakes the GEMV from 3 rows (7B decode step at batch 2 / 3 / 4 / 5: GEMV 2.48 / 2.75 / 3.00 / -,
-    // tiles - / see DESIGN.md / 2.68 / 2.74 ms)
-    static const int env_m = getenv("PPLHIP_GEMV_STREAM_MAX_M") ? atoi(getenv("PPLHIP_GEMV_STREAM_MAX_M")) : -1;
-    const int max_m = env_m >= 0 ? env_m : (wq_bit == 8 && K % 128 == 0 ? 2 : 4);
-    const int kl = wq_bit == 8 ? 16 : (wq_bit == 4 ? 32 : 8);
-    if (K % kl) return 0;
-    if (wq_bit == 4 && (group % 32 || K % group)) return 0;
-    const int pieces = (K / kl + 63) / 64;
-    if (pieces > 3 * GV_NW) return 0;  // at most three pieces per wave and row (K <= 24576 int8)
-    (void)N;
-    return max_m > 4 ? 4 : max_m;
-}
-
+// The shapes this kernel takes: gemv_stream_max_m (linear_plan.h); block shape and grid from plan_gemv_stream, the part plan_linear holds
+// for this family
 hipError_t launch_gemv_stream(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int wq_bit, int group, int64_t M, int N,
                               int K, void* y, int64_t ldy, int epi, LinearRoute* route) {
-    const int kl = wq_bit == 8 ? 16 : (wq_bit == 4 ? 32 : 8);
-    const int pieces = (K / kl + 63) / 64;
-    int nwk_log2 = 0;
-    while ((1 << nwk_log2) < pieces && nwk_log2 < 3) ++nwk_log2;
-    const int nwk = 1 << nwk_log2, npw = (pieces + nwk - 1) / nwk;
-    const int nw = nwk <= 4 ? 4 : 8;                                   // small blocks: the grid balances over the 256 CUs
-    // 16 rows per wave when that still leaves >= 8 waves per CU, else 8
-    const int64_t waves16 = (int64_t)((N + 15) / 16) * nwk;
-    const int nb = waves16 >= 2048 ? 2 : 1;
-    const int rows = (nw / nwk) * nb * GV_U;
-    dim3 grid((unsigned)((N + rows - 1) / rows)), block(nw * 64);
-    if (M < 1 || M > 4 || npw > 3) return hipErrorInvalidValue;
-    if (wq_bit != 8 && wq_bit != 4 && wq_bit != 0) return hipErrorInvalidValue;
-    if (route) {
-        route->add("kernel=gemv_stream_kernel<%d,%d,%s,%d>", wq_bit, (int)M, epi_name(epi), nw);
-        route->add("splits=1 reduce=none order=plain nwk=%d nb=%d", nwk, nb);
-        if (route->dry) return hipSuccess;
-    }
+    LinearPart p;
+    if (!plan_gemv_stream(wq_bit, M, N, K, epi, &p)) return hipErrorInvalidValue;
+    if (route_part(route, p)) return hipSuccess;
     dispatch_int<8, 4, 0>(wq_bit, [&](auto WQ) {
         dispatch_int<1, 2, 3, 4>((int)M, [&](auto MM) {
             dispatch_epi(epi, [&](auto E) {
-                dispatch_int<4, 8>(nw, [&](auto NW) {
-                    hipLaunchKernelGGL((gemv_stream_kernel<WQ, MM, E, NW>), grid, block, 0, s, x, w, scale, N, K, group, y, ldy, nwk_log2, npw, nb);
+                dispatch_int<4, 8>(p.nw, [&](auto NW) {
+                    hipLaunchKernelGGL((gemv_stream_kernel<WQ, MM, E, NW>), dim3(p.grid_x), dim3(p.threads), 0, s, x, w, scale, N, K, group, y, ldy,
+                                       p.nwk_log2, p.npw, p.nb);
                 });
             });
         });

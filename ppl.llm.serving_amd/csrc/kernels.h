@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "k_common.h"
+#include "linear_plan.h"
 
 namespace pplhip {
 
@@ -28,7 +29,6 @@ struct LinearRoute {
     bool dry = false;
     void add(const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // one token, space-separated from the previous one
 };
-inline const char* epi_name(int epi) { return epi == 1 ? "f32" : (epi == 2 ? "swiglu" : "f16"); }   // EPI_F16 / EPI_F32 / EPI_SWIGLU
 #ifdef __HIPCC__
 // 8 consecutive outputs n .. n + 7 of row m, as fp16-rounded floats
 __device__ __forceinline__ void slab_load8(const SplitSlabs& sl, int64_t m, int n, float* o) {
@@ -134,10 +134,9 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
 hipError_t launch_linear_w8_wide(hipStream_t s, const uint16_t* x, const int8_t* w, const uint16_t* scale, int64_t M, int N, int K, void* y,
                                  int64_t ldy, int epi, int nc, LinearRoute* route = nullptr);
 // W4A16 (group 128) on 128 (m) x 64 (n) tiles, no K slabs (k_gemm_pc.hip): a few hundred rows; epi 0 fp16 / 2 fused SwiGLU
-bool linear_w4_pc_supported(int group, int64_t M, int N, int K, const void* x, const void* w, const void* scale, const void* y, int64_t ldy, int epi);
 hipError_t launch_linear_w4_pc(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int64_t M, int N, int K, void* y,
                                int64_t ldy, int epi, LinearRoute* route = nullptr);
-int linear_w8_wide_waves(int64_t M, int N);  // 12 when the 128 x 384 tiles fill rounds of 256 blocks well enough, else 0
+// (which of them takes a problem: plan_linear, linear_plan.h -- with gemv_stream_max_m, linear_w8_wide_waves and linear_w4_pc_supported)
 hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int wq_bit, int group,
                          int64_t M, int N, int K, void* y, int64_t ldy, bool out_fp32, float* ws = nullptr, size_t ws_bytes = 0,
                          bool swiglu = false, SplitSlabs* defer = nullptr,   // defer: a split-K launch leaves its slabs unreduced there
@@ -145,7 +144,6 @@ hipError_t launch_linear(hipStream_t s, const uint16_t* x, const void* w, const 
 // y = (sum of `splits` fp32 slabs [M][N] at ws) * scale (NULL: 1), epilogue epi (0 fp16 / 1 fp32 / 2 fused SwiGLU)
 hipError_t launch_splitk_reduce(hipStream_t s, const float* ws, int splits, int64_t M, int N, const uint16_t* scale, void* y, int64_t ldy, int epi);
 // ---- k_gemv.hip: streaming GEMV, 1 <= M <= 4 (whole 1-KiB row pieces per wave-load; VALU dot products) ----------------------------
-int gemv_stream_max_m(int wq_bit, int group, int N, int K);  // largest M the kernel takes for this shape (0: none)
 hipError_t launch_gemv_stream(hipStream_t s, const uint16_t* x, const void* w, const uint16_t* scale, int wq_bit, int group, int64_t M, int N,
                               int K, void* y, int64_t ldy, int epi, LinearRoute* route = nullptr);
 // ---- k_gemm_i8.hip: online_i8i8 (W8A8) ------------------------------------------------------------

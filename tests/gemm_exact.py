@@ -800,7 +800,6 @@ def all_cases():
 # compiled instantiations that no call reaches with the product defaults (no PPLHIP_* switch set): the sweep asserts that it reaches none
 # of them.  (pattern over the kernel token, reason)
 UNREACHABLE = [
-    (r"gemv_kernel<\d,2,", "MT = 2 needs 17 to 32 rows; the skinny route requires M <= 16"),
     (r"gemm_dma_kernel<\d,\w+,2,5>", "the 5-wave layout runs only when tiles x splits <= 256, which always selects the deep ring"),
     (r"gemm_dma_kernel<0,\w+,4,", "fp16 weights never take 4 stages (4 x 32 KiB: lowered to 3)"),
     (r"gemm_dma_kernel<[48],\w+,3,", "int8 and int4 weights take 2 or 4 stages, never 3"),
@@ -818,10 +817,9 @@ def compiled_instantiations():
             for e in E:
                 for nw in (4, 8):
                     out.add(f"gemv_stream_kernel<{wq},{M},{e},{nw}>")
-        for mt in (1, 2):
-            for e in E:
-                for nw in (4, 8):
-                    out.add(f"gemv_kernel<{wq},{mt},{e},{nw}>")
+        for e in E:
+            for nw in (4, 8):
+                out.add(f"gemv_kernel<{wq},1,{e},{nw}>")
         for e in E:
             out.add(f"gemm_kernel<{wq},{e}>")
             for st in (2, 3, 4):
