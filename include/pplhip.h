@@ -471,6 +471,27 @@ PPLHIP_API int pplhip_guide_load(pplhip_ctx* ctx, int32_t slot, const pplhip_gui
 PPLHIP_API int pplhip_guide_unload(pplhip_ctx* ctx, int32_t slot);
 PPLHIP_API int pplhip_guide_edit(pplhip_ctx* ctx, float* logits_device, const pplhip_guide_edit_args* args);
 
+/* Wide guides (a JSON schema's automaton): pplhip_guide_load16 is pplhip_guide_load with 16-bit transitions.  trans is uint16
+ * [n_states, 256], the dead state is 0xFFFF (PPLHIP_GUIDE16_DEAD; it has no row) and n_states is in [1, PPLHIP_GUIDE16_MAX_STATES]: state
+ * 255 is an ordinary live state here.  The slots are the same sixteen and a slot holds either kind; pplhip_guide_unload and
+ * pplhip_guide_edit serve both, the latter with the slot's own n_states as the bound of a row's state.  Validation, its messages, the
+ * check after the build and the return codes are those of pplhip_guide_load (an allocation that fails: PPLHIP_OUT_OF_MEMORY, the slot
+ * stays empty).  A slot's mask takes n_states * ceil(vocab_size / 32) * 4 bytes of device memory: 62.6 MiB for 4096 states at a vocabulary
+ * of 128,256, 15.6 MiB at 32,000.  The build is one launch over (token block, chunk of pplhip_guide16_state_chunk() states) that reads
+ * the table from global memory.
+ * Arrived without a version bump: a client tells a library that has it by the symbol pplhip_guide_load16 (dlsym). */
+#define PPLHIP_GUIDE16_MAX_STATES 4096
+#define PPLHIP_GUIDE16_DEAD 0xFFFF
+typedef struct pplhip_guide_desc16 {
+    const uint16_t* trans;        /* [n_states, 256] */
+    const uint8_t* accept;        /* [n_states] */
+    int32_t n_states;
+    const int32_t* end_tokens;    /* [n_end] */
+    int32_t n_end;
+} pplhip_guide_desc16;
+PPLHIP_API int pplhip_guide_load16(pplhip_ctx* ctx, int32_t slot, const pplhip_guide_desc16* desc);
+PPLHIP_API int32_t pplhip_guide16_state_chunk(void);   /* states per workgroup of the wide build's grid (for the tests' edge cases) */
+
 /* in-place penalty on the logits of the last run, using the step's device-resident token_inputs /
  * seq_starts / start_pos (llm_engine.cc:204-216). */
 PPLHIP_API int pplhip_penalty(pplhip_ctx* ctx, float* logits_device, const pplhip_penalty_args* args);
@@ -687,6 +708,14 @@ PPLHIP_API int pplhip_op_guide_build(void* stream, const uint8_t* trans, const u
 PPLHIP_API int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
                                     const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
                                     const int32_t* rows, int32_t n_rows);
+/* the same two for wide guides: trans is uint16 [n_states, 256] with the dead state 0xFFFF, and n_states of both is in [1, 4096].
+ * pplhip_op_guide_mask16 is pplhip_op_guide_mask's kernel and validation with that bound. */
+PPLHIP_API int pplhip_op_guide_build16(void* stream, const uint16_t* trans, const uint8_t* accept, int32_t n_states, const uint8_t* tok_bytes,
+                                       const int64_t* tok_off, int32_t n_tok, const int32_t* end_tokens, int32_t n_end, int32_t vocab,
+                                       uint32_t* mask, int64_t mask_stride, uint32_t* any);
+PPLHIP_API int pplhip_op_guide_mask16(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
+                                      const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
+                                      const int32_t* rows, int32_t n_rows);
 /* out_u[b] = u(seeds[b], draws[b]), the generator alone (device pointers) */
 PPLHIP_API int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u);
 

@@ -309,6 +309,14 @@ struct GuideTable {
 hipError_t launch_guide_build(hipStream_t s, const uint8_t* trans, const uint8_t* accept, int n_states, const uint8_t* tok_bytes,
                               const int64_t* tok_off, int n_tok, const int32_t* end_tokens, int n_end, int vocab, uint32_t* mask,
                               int64_t mask_stride, uint32_t* any);
+// The wide guide: trans is uint16 [n_states, 256], GUIDE16_DEAD the dead state, n_states <= GUIDE16_MAX_STATES; everything else as above.
+// The grid is (token block, chunk of GUIDE16_STATE_CHUNK states); a next state at or behind n_states counts as dead.
+constexpr int GUIDE16_MAX_STATES = 4096;   // PPLHIP_GUIDE16_MAX_STATES: live states 0 .. 4095
+constexpr int GUIDE16_DEAD = 0xFFFF;
+constexpr int GUIDE16_STATE_CHUNK = 64;
+hipError_t launch_guide_build16(hipStream_t s, const uint16_t* trans, const uint8_t* accept, int n_states, const uint8_t* tok_bytes,
+                                const int64_t* tok_off, int n_tok, const int32_t* end_tokens, int n_end, int vocab, uint32_t* mask,
+                                int64_t mask_stride, uint32_t* any);
 // rows: device list of the n_rows batch rows with guide_slots[b] >= 0; guide_slots and states are indexed by the batch row.  Sets
 // logits[b * stride + v] to -inf for every v < vocab whose bit is clear in row states[b] of slot guide_slots[b].  No rows: no launch.
 hipError_t launch_guide_mask(hipStream_t s, float* logits, int stride, int vocab, const int32_t* rows, int n_rows, const int32_t* guide_slots,

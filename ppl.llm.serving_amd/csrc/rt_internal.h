@@ -225,6 +225,7 @@ struct StepInputsBlock : Packed {
 // so one copy carries a rule.
 static_assert(PPLHIP_LOGIT_BIAS_MAX == LOGIT_BIAS_MAX && PPLHIP_LOGIT_STOP_MAX == LOGIT_STOP_MAX, "header and kernel disagree");
 static_assert(PPLHIP_GUIDE_MAX_SLOTS == GUIDE_MAX_SLOTS && PPLHIP_GUIDE_MAX_STATES == GUIDE_MAX_STATES && GUIDE_DEAD == 255, "header and kernel disagree");
+static_assert(PPLHIP_GUIDE16_MAX_STATES == GUIDE16_MAX_STATES && PPLHIP_GUIDE16_DEAD == GUIDE16_DEAD, "header and kernel disagree");
 constexpr int64_t LR_HEAD = 16, LR_BIAS_TOK = LR_HEAD, LR_BIAS_VAL = LR_BIAS_TOK + 4 * LOGIT_BIAS_MAX,
                   LR_STOPS = LR_BIAS_VAL + 4 * LOGIT_BIAS_MAX, LR_MASK = LR_STOPS + 4 * LOGIT_STOP_MAX;
 constexpr int LR_RING = 4;   // staging records; a record is reused once the copy out of it is done

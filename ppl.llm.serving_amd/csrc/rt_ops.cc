@@ -276,11 +276,22 @@ int pplhip_op_guide_build(void* stream, const uint8_t* trans, const uint8_t* acc
                                     mask_stride, any));
 }
 
-int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
+int pplhip_op_guide_build16(void* stream, const uint16_t* trans, const uint8_t* accept, int32_t n_states, const uint8_t* tok_bytes,
+                            const int64_t* tok_off, int32_t n_tok, const int32_t* end_tokens, int32_t n_end, int32_t vocab, uint32_t* mask,
+                            int64_t mask_stride, uint32_t* any) {
+    if (n_states < 1 || n_states > GUIDE16_MAX_STATES || vocab <= 0 || n_tok < 0 || n_tok > vocab || n_end < 0 || n_end > LOGIT_STOP_MAX ||
+        mask_stride < ((int64_t)vocab + 31) / 32)
+        return PPLHIP_INVALID_VALUE;
+    if (!trans || !accept || !tok_bytes || !tok_off || !mask || !any || (n_end > 0 && !end_tokens)) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_guide_build16((hipStream_t)stream, trans, accept, n_states, tok_bytes, tok_off, n_tok, end_tokens, n_end, vocab, mask,
+                                      mask_stride, any));
+}
+
+static int op_guide_mask(int max_states, void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
                          const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
                          const int32_t* rows, int32_t n_rows) {
     if (batch < 0 || vocab <= 0 || stride < vocab || n_rows < 0 || n_rows > batch || n_slots < 1 || n_slots > GUIDE_MAX_SLOTS ||
-        n_states < 1 || n_states > GUIDE_MAX_STATES || mask_stride < ((int64_t)vocab + 31) / 32)
+        n_states < 1 || n_states > max_states || mask_stride < ((int64_t)vocab + 31) / 32)
         return PPLHIP_INVALID_VALUE;
     if (batch == 0) return 0;
     if (!logits || !guide_slots || !states || !masks) return PPLHIP_INVALID_VALUE;
@@ -307,6 +318,20 @@ int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vo
     if (e == hipSuccess) e = launch_guide_mask(s, logits, stride, vocab, d_rows, (int)list.size(), guide_slots, states, tb);
     const hipError_t e2 = hipFreeAsync(d_rows, s);
     return op_rc(e != hipSuccess ? e : e2);
+}
+
+int pplhip_op_guide_mask(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
+                         const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
+                         const int32_t* rows, int32_t n_rows) {
+    return op_guide_mask(GUIDE_MAX_STATES, stream, logits, stride, vocab, batch, guide_slots, states, masks, n_slots, n_states, mask_stride, rows,
+                         n_rows);
+}
+
+int pplhip_op_guide_mask16(void* stream, float* logits, int32_t stride, int32_t vocab, int32_t batch, const int32_t* guide_slots,
+                           const int32_t* states, const uint32_t* masks, int32_t n_slots, int32_t n_states, int64_t mask_stride,
+                           const int32_t* rows, int32_t n_rows) {
+    return op_guide_mask(GUIDE16_MAX_STATES, stream, logits, stride, vocab, batch, guide_slots, states, masks, n_slots, n_states, mask_stride,
+                         rows, n_rows);
 }
 
 int pplhip_op_sample_uniform(void* stream, const uint64_t* seeds, const uint64_t* draws, int32_t batch, float* out_u) {

@@ -281,7 +281,9 @@ int pplhip_guide_set_vocab(pplhip_ctx* c, const uint8_t* bytes, const int64_t* o
     return 0;
 }
 
-int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
+// pplhip_guide_load and pplhip_guide_load16: T is the table's state type, `dead` its dead state, max_states / max_name the bound of n_states
+template <typename T, typename Desc, typename Launch>
+static int guide_load(pplhip_ctx* c, int32_t slot, const Desc* g, int dead, int max_states, const char* max_name, Launch launch) {
     if (!c || !g) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[0];
     const int V = c->d.vocab_size;
@@ -289,7 +291,7 @@ int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
     if (slot < 0 || slot >= PPLHIP_GUIDE_MAX_SLOTS) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot outside [0, PPLHIP_GUIDE_MAX_SLOTS)");
     if (R.gd_mask[slot]) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: slot " + std::to_string(slot) + " is loaded");
     const int S = g->n_states;
-    if (S < 1 || S > PPLHIP_GUIDE_MAX_STATES) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: n_states outside [1, PPLHIP_GUIDE_MAX_STATES]");
+    if (S < 1 || S > max_states) return fail(c, 0, PPLHIP_INVALID_VALUE, std::string("guide: n_states outside [1, ") + max_name + "]");
     if (g->n_end < 0 || g->n_end > PPLHIP_LOGIT_STOP_MAX) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: n_end outside [0, PPLHIP_LOGIT_STOP_MAX]");
     if (!g->trans || !g->accept || (g->n_end > 0 && !g->end_tokens)) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: a NULL array");
     for (int i = 0; i < g->n_end; ++i)
@@ -299,30 +301,31 @@ int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
         bool live = g->accept[s] != 0;
         for (int b = 0; b < 256; ++b) {
             const int to = g->trans[s * 256 + b];
-            if (to != GUIDE_DEAD && to >= S)
+            if (to != dead && to >= S)
                 return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(s) + " byte " + std::to_string(b) + " leads to state " +
                                                             std::to_string(to) + " >= n_states");
-            live = live || to != GUIDE_DEAD;
+            live = live || to != dead;
         }
         if (!live) return fail(c, 0, PPLHIP_INVALID_VALUE, "guide: state " + std::to_string(s) + " has neither a live byte nor acceptance");
     }
     HIPCK(c, 0, hipSetDevice(R.device));
     const int64_t words = ((int64_t)V + 31) / 32;
-    // one scratch block: trans | accept (padded to 256) | any u32 [256] | end tokens i32 [64]
-    const size_t o_acc = (size_t)S * 256, o_any = o_acc + 256, o_end = o_any + 1024, scratch_bytes = o_end + 256;
+    // one scratch block: trans | accept (padded to 256) | any u32 (a multiple of 256 of them) | end tokens i32 [64]
+    const size_t pad = ((size_t)S + 255) / 256 * 256;
+    const size_t o_acc = (size_t)S * 256 * sizeof(T), o_any = o_acc + pad, o_end = o_any + pad * 4, scratch_bytes = o_end + 256;
     char* scratch = nullptr;
     uint32_t* mask = nullptr;
     std::vector<uint32_t> any((size_t)S, 0);
     hipError_t e = hipMalloc((void**)&scratch, scratch_bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&mask, (size_t)S * words * 4);
     hipStream_t s = R.stream;
-    if (e == hipSuccess) e = hipMemsetAsync(scratch + o_any, 0, 1024, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(scratch, g->trans, (size_t)S * 256, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(scratch + o_any, 0, pad * 4, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(scratch, g->trans, (size_t)S * 256 * sizeof(T), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(scratch + o_acc, g->accept, (size_t)S, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && g->n_end > 0) e = hipMemcpyAsync(scratch + o_end, g->end_tokens, (size_t)g->n_end * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = launch_guide_build(s, (const uint8_t*)scratch, (const uint8_t*)(scratch + o_acc), S, R.gd_bytes, R.gd_off, R.gd_n_tok,
-                               (const int32_t*)(scratch + o_end), g->n_end, V, mask, words, (uint32_t*)(scratch + o_any));
+        e = launch(s, (const T*)scratch, (const uint8_t*)(scratch + o_acc), S, R.gd_bytes, R.gd_off, R.gd_n_tok,
+                   (const int32_t*)(scratch + o_end), g->n_end, V, mask, words, (uint32_t*)(scratch + o_any));
     if (e == hipSuccess) e = hipMemcpyAsync(any.data(), scratch + o_any, (size_t)S * 4, hipMemcpyDeviceToHost, s);
     const hipError_t e_sync = hipStreamSynchronize(s);   // synchronous by design: once per distinct pattern
     if (e == hipSuccess) e = e_sync;
@@ -340,6 +343,16 @@ int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
     R.gd_states[slot] = S;
     return 0;
 }
+
+int pplhip_guide_load(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc* g) {
+    return guide_load<uint8_t>(c, slot, g, GUIDE_DEAD, PPLHIP_GUIDE_MAX_STATES, "PPLHIP_GUIDE_MAX_STATES", launch_guide_build);
+}
+
+int pplhip_guide_load16(pplhip_ctx* c, int32_t slot, const pplhip_guide_desc16* g) {
+    return guide_load<uint16_t>(c, slot, g, GUIDE16_DEAD, PPLHIP_GUIDE16_MAX_STATES, "PPLHIP_GUIDE16_MAX_STATES", launch_guide_build16);
+}
+
+int32_t pplhip_guide16_state_chunk(void) { return GUIDE16_STATE_CHUNK; }
 
 int pplhip_guide_unload(pplhip_ctx* c, int32_t slot) {
     if (!c) return PPLHIP_INVALID_VALUE;

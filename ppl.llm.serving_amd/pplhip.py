@@ -179,10 +179,10 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_set_prompt_logprobs", "pplhip_prompt_logprobs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
-    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_guide_set_vocab", "pplhip_guide_load", "pplhip_guide_unload", "pplhip_guide_edit", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
+    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_guide_set_vocab", "pplhip_guide_load", "pplhip_guide_unload", "pplhip_guide_edit", "pplhip_guide_load16", "pplhip_guide16_state_chunk", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_guide_build16", "pplhip_op_guide_mask16", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -286,6 +286,12 @@ def lib():
             L.pplhip_guide_edit.argtypes = [vp, vp, C.POINTER(GuideEditArgs)]
             L.pplhip_op_guide_build.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, i64, vp]
             L.pplhip_op_guide_mask.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i64, vp, i32]
+        if hasattr(L, "pplhip_guide_load16"):
+            L.pplhip_guide_load16.argtypes = [vp, i32, C.POINTER(GuideDesc)]   # (the descriptor's layout is pplhip_guide_desc's)
+            L.pplhip_guide16_state_chunk.argtypes = []
+            L.pplhip_guide16_state_chunk.restype = i32
+            L.pplhip_op_guide_build16.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, i64, vp]
+            L.pplhip_op_guide_mask16.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i64, vp, i32]
         L.pplhip_op_rope_kv_write.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i32]
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
@@ -788,6 +794,19 @@ class Context:
         rc = lib().pplhip_guide_load(self.h, int(slot), C.byref(g))
         if check:
             self._ck(rc, 0, "guide_load")
+        return rc
+
+    def guide_load16(self, slot, trans, accept, end_tokens=(), check=True):
+        """guide_load for a wide guide: trans uint16 [n_states, 256] (0xFFFF = dead), up to 4096 states.  Synchronous."""
+        tr = np.ascontiguousarray(trans, dtype=np.uint16)
+        ac = np.ascontiguousarray(accept, dtype=np.uint8)
+        en = np.ascontiguousarray(end_tokens, dtype=np.int32)
+        assert tr.ndim == 2 and tr.shape[1] == 256 and len(ac) == len(tr)
+        g = GuideDesc()
+        g.trans, g.accept, g.n_states, g.end_tokens, g.n_end = tr.ctypes.data, ac.ctypes.data, len(tr), en.ctypes.data, len(en)
+        rc = lib().pplhip_guide_load16(self.h, int(slot), C.byref(g))
+        if check:
+            self._ck(rc, 0, "guide_load16")
         return rc
 
     def guide_unload(self, slot, check=True):

@@ -182,6 +182,23 @@ RetCode HipPostProcessor::LoadGuide(int32_t slot, const GuideDfa& dfa, const std
     return FromPplHipStatus(st);
 }
 
+static_assert(PostProcessor::kGuide16MaxStates == PPLHIP_GUIDE16_MAX_STATES && GuideDfa16::kMaxStates == PPLHIP_GUIDE16_MAX_STATES &&
+                  GuideDfa16::kDead == PPLHIP_GUIDE16_DEAD,
+              "interface and library disagree");
+
+RetCode HipPostProcessor::LoadGuide16(int32_t slot, const GuideDfa16& dfa, const std::vector<int32_t>& end_tokens) {
+    pplhip_guide_desc16 g;
+    memset(&g, 0, sizeof(g));
+    g.trans = dfa.trans.data();
+    g.accept = dfa.accept.data();
+    g.n_states = dfa.n_states;
+    g.end_tokens = end_tokens.data();
+    g.n_end = (int32_t)end_tokens.size();
+    const int st = pplhip_guide_load16(ctx_, slot, &g);
+    if (st) LOG(ERROR) << "guide of slot " << slot << " refused: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
 RetCode HipPostProcessor::UnloadGuide(int32_t slot) {
     const int st = pplhip_guide_unload(ctx_, slot);
     if (st) LOG(ERROR) << "guide unload failed: " << pplhip_last_error(ctx_, 0);

@@ -53,6 +53,7 @@ public:
                                     int32_t vocab_size, int32_t batch_stride) override;
     ppl::common::RetCode SetGuideVocab(const uint8_t* bytes, const int64_t* offsets, int32_t n_tok) override;
     ppl::common::RetCode LoadGuide(int32_t slot, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens) override;
+    ppl::common::RetCode LoadGuide16(int32_t slot, const GuideDfa16& dfa, const std::vector<int32_t>& end_tokens) override;
     ppl::common::RetCode UnloadGuide(int32_t slot) override;
     ppl::common::RetCode GuideEdit(float* logits_device, const int32_t* guide_slots_host, const int32_t* states_host, int32_t batch,
                                    int32_t vocab_size, int32_t batch_stride) override;

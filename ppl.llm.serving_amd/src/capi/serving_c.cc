@@ -237,6 +237,12 @@ int pplsrv_submit_prompt_logprobs(pplsrv* s, const pplsrv_request* reqs, const i
 
 int pplsrv_submit_guided(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
                          const pplsrv_rule* const* rules, const int32_t* prompt_logprobs, const char* const* guide_regex, int32_t n) {
+    return pplsrv_submit_guided_json(s, reqs, slots, seeds, num_logprobs, rules, prompt_logprobs, guide_regex, nullptr, n);
+}
+
+int pplsrv_submit_guided_json(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
+                              const pplsrv_rule* const* rules, const int32_t* prompt_logprobs, const char* const* guide_regex,
+                              const char* const* guide_json_schema, int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -255,6 +261,7 @@ int pplsrv_submit_guided(pplsrv* s, const pplsrv_request* reqs, const int32_t* s
         r->num_logprobs = num_logprobs ? num_logprobs[i] : 0;
         r->prompt_logprobs = prompt_logprobs ? prompt_logprobs[i] : -1;
         if (guide_regex && guide_regex[i]) r->guide_regex = guide_regex[i];
+        if (guide_json_schema && guide_json_schema[i]) r->guide_json_schema = guide_json_schema[i];
         if (rules && rules[i]) {
             const pplsrv_rule& u = *rules[i];
             for (int32_t j = 0; j < u.n_bias; ++j) r->logit_bias.emplace_back(u.bias_tokens[j], u.bias_values[j]);

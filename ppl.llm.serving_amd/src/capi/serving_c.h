@@ -148,6 +148,14 @@ PPLSRV_API int pplsrv_poll_prompt_logprobs(pplsrv* s, pplsrv_response* out, int3
 PPLSRV_API int pplsrv_submit_guided(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
                                     const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs,
                                     const char* const* guide_regex, int32_t n);
+/* The same by a JSON schema.  pplsrv_submit_guided_json is pplsrv_submit_guided with guide_json_schema[i] = Request::guide_json_schema of
+ * reqs[i]: the NUL-terminated text of a JSON schema (src/common/guide_json.h has the subset and the one layout of the answer's text);
+ * NULL or "" = no schema; guide_json_schema NULL: nobody has one.  The answer of such a request is a JSON document that fits the schema.
+ * What fails a request with guide_regex fails this one alone too, as do a schema outside the subset or of more than 4096 states, a
+ * request that carries both a pattern and a schema, and a backend without wide guides. */
+PPLSRV_API int pplsrv_submit_guided_json(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                         const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs,
+                                         const char* const* guide_regex, const char* const* guide_json_schema, int32_t n);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

@@ -8,8 +8,9 @@
 // possessive quantifiers, a non-ASCII character inside a class, an empty language, and an automaton of more than 255 states.
 // A `{` that does not begin a well-formed quantifier is a literal, as are `}` and a `]` outside a class.
 //
-// Pipeline: Thompson NFA -> subset construction -> every state that cannot reach an accepting one becomes the dead state -> minimised by
-// partition refinement.  State 0 is the start; states are numbered in breadth-first order of their first byte.
+// Pipeline (guide_tree.h, shared with the JSON-schema front end of guide_json.h): Thompson NFA -> subset construction -> every state that
+// cannot reach an accepting one becomes the dead state -> minimised by partition refinement.  State 0 is the start; states are numbered
+// in breadth-first order of their first byte.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,6 +28,26 @@ struct GuideDfa final {
     std::vector<uint8_t> accept;  // [n_states]: the bytes so far are a full match
 
     // the state after `bytes` from `state`; kDead as soon as the dead state is met (and for a state outside the automaton)
+    int Step(int state, const uint8_t* bytes, size_t n) const {
+        for (size_t i = 0; i < n; ++i) {
+            if (state < 0 || state >= n_states) return kDead;
+            state = trans[(size_t)state * 256 + bytes[i]];
+        }
+        return state >= 0 && state < n_states ? state : kDead;
+    }
+    int Step(int state, const std::string& bytes) const { return Step(state, (const uint8_t*)bytes.data(), bytes.size()); }
+    bool Accepting(int state) const { return state >= 0 && state < n_states && accept[(size_t)state] != 0; }
+};
+
+// The wide automaton of a JSON schema (guide_json.h): 16-bit states, up to 4096 live ones.  State 255 is an ordinary state here
+// (PostProcessor::LoadGuide16).
+struct GuideDfa16 final {
+    static constexpr int kDead = 0xFFFF;     // the dead state: no row in `trans`, never left
+    static constexpr int kMaxStates = 4096;  // live states 0 .. 4095 (PostProcessor::kGuide16MaxStates)
+    int n_states = 0;
+    std::vector<uint16_t> trans;  // [n_states][256]
+    std::vector<uint8_t> accept;  // [n_states]
+
     int Step(int state, const uint8_t* bytes, size_t n) const {
         for (size_t i = 0; i < n; ++i) {
             if (state < 0 || state >= n_states) return kDead;

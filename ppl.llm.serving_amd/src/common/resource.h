@@ -83,6 +83,12 @@ public:
     virtual ppl::common::RetCode LoadGuide(int32_t /*slot*/, const GuideDfa& /*dfa*/, const std::vector<int32_t>& /*end_tokens*/) {
         return ppl::common::RC_UNSUPPORTED;
     }
+    // the same for the wide automaton of a JSON schema (up to kGuide16MaxStates states); the slots are the same, a slot holds either
+    // kind, and UnloadGuide / GuideEdit serve both.  A backend without it keeps this default: a request with a schema then fails alone
+    static constexpr int32_t kGuide16MaxStates = 4096;
+    virtual ppl::common::RetCode LoadGuide16(int32_t /*slot*/, const GuideDfa16& /*dfa*/, const std::vector<int32_t>& /*end_tokens*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
     virtual ppl::common::RetCode UnloadGuide(int32_t /*slot*/) { return ppl::common::RC_UNSUPPORTED; }
     virtual ppl::common::RetCode GuideEdit(float* /*logits_device*/, const int32_t* /*guide_slots_host*/, const int32_t* /*states_host*/,
                                            int32_t /*batch*/, int32_t /*vocab_size*/, int32_t /*batch_stride*/) {

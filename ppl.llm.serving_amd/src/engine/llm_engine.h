@@ -107,6 +107,9 @@ public:
     ppl::common::RetCode LoadGuide(int32_t slot, const GuideDfa& dfa, const std::vector<int32_t>& end_tokens) {
         auto lock = DeviceLock(); return post_processor_->LoadGuide(slot, dfa, end_tokens);
     }
+    ppl::common::RetCode LoadGuide16(int32_t slot, const GuideDfa16& dfa, const std::vector<int32_t>& end_tokens) {
+        auto lock = DeviceLock(); return post_processor_->LoadGuide16(slot, dfa, end_tokens);
+    }
     ppl::common::RetCode UnloadGuide(int32_t slot) { auto lock = DeviceLock(); return post_processor_->UnloadGuide(slot); }
 
 private:

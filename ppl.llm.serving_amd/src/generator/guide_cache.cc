@@ -28,10 +28,11 @@ bool GuideCache::SendVocab() {
     return vocab_sent_ > 0;
 }
 
-int32_t GuideCache::Acquire(const std::string& regex, const std::vector<int32_t>& end_tokens, std::string* err, RetCode* errcode) {
+int32_t GuideCache::Acquire(Kind kind, const std::string& text, const std::vector<int32_t>& end_tokens, std::string* err, RetCode* errcode) {
+    const bool wide = kind == Kind::kJsonSchema;
     const auto refuse = [&](RetCode code, const std::string& msg) {
         *errcode = code;
-        *err = "guide_regex: " + msg;
+        *err = (wide ? "guide_json_schema: " : "guide_regex: ") + msg;
         return -1;
     };
     if (!engine_->HasGuides()) return refuse(RC_UNSUPPORTED, "the backend's post processor has no GuideEdit");
@@ -44,7 +45,8 @@ int32_t GuideCache::Acquire(const std::string& regex, const std::vector<int32_t>
     for (int32_t t : end_tokens)
         if (t < 0 || t >= vocab_size_) return refuse(RC_INVALID_VALUE, "end token [" + std::to_string(t) + "] outside the vocabulary");
 
-    std::string key = regex;
+    std::string key(1, wide ? 'J' : 'R');
+    key += text;
     key.push_back('\0');
     for (int32_t t : end_tokens) key += std::to_string(t) + ",";
     const int32_t n = PostProcessor::kGuideMaxSlots;
@@ -55,8 +57,9 @@ int32_t GuideCache::Acquire(const std::string& regex, const std::vector<int32_t>
             return i;
         }
     GuideDfa dfa;
+    GuideDfa16 dfa16;
     *errcode = RC_INVALID_VALUE;
-    if (!CompileGuideRegex(regex, &dfa, err)) return -1;
+    if (!(wide ? CompileGuideJsonSchema(text, &dfa16, err) : CompileGuideRegex(text, &dfa, err))) return -1;
     int32_t pick = -1;
     for (int32_t i = 0; i < n && pick < 0; ++i)
         if (slots_[i].key.empty()) pick = i;
@@ -68,11 +71,16 @@ int32_t GuideCache::Acquire(const std::string& regex, const std::vector<int32_t>
         if (rc != RC_SUCCESS) return refuse(RC_OTHER_ERROR, "UnloadGuide failed: " + std::string(GetRetCodeStr(rc)));
         slots_[pick] = Slot();
     }
-    const RetCode rc = engine_->LoadGuide(pick, dfa, end_tokens);
-    if (rc == RC_INVALID_VALUE) return refuse(RC_INVALID_VALUE, "some state of the pattern's automaton allows no token of the vocabulary");
-    if (rc != RC_SUCCESS) return refuse(RC_OTHER_ERROR, "LoadGuide failed: " + std::string(GetRetCodeStr(rc)));
+    const RetCode rc = wide ? engine_->LoadGuide16(pick, dfa16, end_tokens) : engine_->LoadGuide(pick, dfa, end_tokens);
+    if (wide && rc == RC_UNSUPPORTED) return refuse(RC_UNSUPPORTED, "the backend's post processor has no LoadGuide16");
+    if (rc == RC_INVALID_VALUE)
+        return refuse(RC_INVALID_VALUE, std::string("some state of the ") + (wide ? "schema" : "pattern") +
+                                            "'s automaton allows no token of the vocabulary");
+    if (rc != RC_SUCCESS) return refuse(RC_OTHER_ERROR, std::string(wide ? "LoadGuide16" : "LoadGuide") + " failed: " + GetRetCodeStr(rc));
     slots_[pick].key = key;
-    slots_[pick].dfa = dfa;
+    slots_[pick].wide = wide;
+    slots_[pick].dfa = std::move(dfa);
+    slots_[pick].dfa16 = std::move(dfa16);
     slots_[pick].refs = 1;
     slots_[pick].last_use = ++clock_;
     return pick;

@@ -318,12 +318,14 @@ static std::vector<int32_t> GuideEndTokens(const Tokenizer* tokenizer, const Gen
 // what a guided request may not carry: the exclusions keep "no token left alive" impossible by construction, as nothing else removes a
 // token the automaton counts on.  Empty: the request is fine
 static std::string GuideExclusion(const Request& r) {
-    if (!r.early_stopping) return "guide_regex: needs early_stopping (the request ends on an end token)";
-    if (r.allowed_tokens) return "guide_regex: cannot be combined with allowed_tokens";
-    if (!r.banned_tokens.empty()) return "guide_regex: cannot be combined with banned_tokens";
-    if (r.min_new_tokens > 0) return "guide_regex: cannot be combined with min_new_tokens";
+    if (!r.guide_regex.empty() && !r.guide_json_schema.empty()) return "guide_json_schema: cannot be combined with guide_regex";
+    const std::string field = r.guide_regex.empty() ? "guide_json_schema" : "guide_regex";
+    if (!r.early_stopping) return field + ": needs early_stopping (the request ends on an end token)";
+    if (r.allowed_tokens) return field + ": cannot be combined with allowed_tokens";
+    if (!r.banned_tokens.empty()) return field + ": cannot be combined with banned_tokens";
+    if (r.min_new_tokens > 0) return field + ": cannot be combined with min_new_tokens";
     for (const auto& p : r.logit_bias)
-        if (p.second == -INFINITY) return "guide_regex: cannot be combined with a -inf logit_bias";
+        if (p.second == -INFINITY) return field + ": cannot be combined with a -inf logit_bias";
     return "";
 }
 
@@ -340,7 +342,7 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
     if (!ClampLengths(generator_config_, r, adm->first_fill_len, &adm->rest_iters, &adm->errmsg)) return adm->Reject(adm->errmsg);
     // deviation: the reference reserves KV here and leaks it when StartRequest rejects
     if (adm->rest_iters <= 0) return adm->Reject(r.id, "generation length <= 0");
-    const bool guided = !r.guide_regex.empty();
+    const bool guided = !r.guide_regex.empty() || !r.guide_json_schema.empty();
     const std::string excluded = guided ? GuideExclusion(r) : "";
     if (!excluded.empty()) return adm->Reject(r.id, excluded);
     if (r.HasLogitRule()) {  // validated once, here; an invalid rule fails its request alone (StartRequest)
@@ -354,7 +356,10 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
         adm->has_rule = true;
     }
     if (guided) {  // a refused guide fails its request alone (StartRequest)
-        adm->guide_slot = guide_cache_.Acquire(r.guide_regex, GuideEndTokens(tokenizer_, generator_config_, r), &adm->errmsg, &adm->errcode);
+        const bool schema = r.guide_regex.empty();
+        adm->guide_slot = guide_cache_.Acquire(schema ? GuideCache::Kind::kJsonSchema : GuideCache::Kind::kRegex,
+                                               schema ? r.guide_json_schema : r.guide_regex,
+                                               GuideEndTokens(tokenizer_, generator_config_, r), &adm->errmsg, &adm->errcode);
         if (adm->guide_slot < 0) return adm->Reject(r.id, adm->errmsg, adm->errcode);
     }
     if (!ReserveKv(req, adm, cool_down, is_prefix_cache_hit)) {
@@ -424,6 +429,7 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm) {
     if (adm.guide_slot >= 0) {
         t.guide_slot = adm.guide_slot;
         t.guide_state = 0;
+        t.guide_schema = r.guide_regex.empty();
         // drawing an end token ends the request: the tokenizer's EOS counts as one of its stop tokens
         auto stops = std::make_shared<std::unordered_set<int>>();
         if (r.stop_tokens) *stops = *r.stop_tokens;
@@ -636,12 +642,11 @@ static int64_t AdvanceRow(TidData* t, int tok) {
 // the automaton alive, so the dead state here means kernel and host disagree.  false: the guide is broken, and the state stays where it was
 bool LLMGenerator::WalkGuide(TidData* t, int tok, bool hit_stop) const {
     if (t->guide_slot < 0) return true;
-    const GuideDfa& dfa = guide_cache_.Dfa(t->guide_slot);
-    if (hit_stop) return dfa.Accepting(t->guide_state);  // an end token in front of a full match
+    if (hit_stop) return guide_cache_.Accepting(t->guide_slot, t->guide_state);  // an end token in front of a full match
     std::string bytes;
     tokenizer_->TokenBytes(tok, &bytes);
-    const int32_t to = bytes.empty() ? GuideDfa::kDead : dfa.Step(t->guide_state, bytes);
-    if (to == GuideDfa::kDead) return false;
+    const int32_t to = bytes.empty() ? -1 : guide_cache_.Step(t->guide_slot, t->guide_state, bytes);
+    if (to < 0) return false;
     t->guide_state = to;
     return true;
 }
@@ -650,8 +655,8 @@ bool LLMGenerator::WalkGuide(TidData* t, int tok, bool hit_stop) const {
 static bool RowFailure(const TidData& t, int tok, bool guide_broken, bool no_prompt, bool no_top, RetCode* code, std::string* msg) {
     *code = guide_broken || t.rule_failed ? RC_OTHER_ERROR : RC_UNSUPPORTED;
     if (guide_broken) {
-        *msg = "guide_regex: internal error: token [" + std::to_string(tok) + "] is not allowed in state [" + std::to_string(t.guide_state) +
-               "] of the request's guide";
+        *msg = std::string(t.guide_schema ? "guide_json_schema" : "guide_regex") + ": internal error: token [" + std::to_string(tok) +
+               "] is not allowed in state [" + std::to_string(t.guide_state) + "] of the request's guide";
     } else if (t.rule_failed) {
         *msg = "logit rules: the backend could not take the request's rule";
     } else if (no_prompt) {

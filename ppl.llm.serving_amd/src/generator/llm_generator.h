@@ -73,6 +73,7 @@ struct TidData final {
     bool rule_failed = false;    // the upload of its logit rule failed: the request is failed on its first step
     int32_t guide_slot = -1;     // guided decoding: the guide slot the request holds a reference on until it leaves; -1: none
     int32_t guide_state = 0;     // the state of its automaton after the bytes generated so far
+    bool guide_schema = false;   // the guide is a JSON schema's (guide_json_schema), not a regular expression's
 };
 
 struct LlmRequest final : public ppl::common::MPSCQueue::Node {

@@ -16,6 +16,7 @@ struct JsonValue {
     std::string str;
     std::vector<JsonValue> arr;
     std::map<std::string, JsonValue> obj;
+    std::vector<std::string> keys;   // OBJECT: the keys in document order (obj sorts them); a repeated key keeps its first place
 
     const JsonValue* Find(const std::string& key) const {
         if (type != OBJECT) return nullptr;
@@ -118,6 +119,7 @@ private:
                 Skip();
                 if (!At(':')) return false;
                 ++pos_;
+                if (!v->obj.count(key)) v->keys.push_back(key);
                 if (!Value(&v->obj[key])) return false;
                 Skip();
                 if (At(',')) { ++pos_; continue; }

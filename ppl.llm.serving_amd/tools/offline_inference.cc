@@ -8,6 +8,7 @@
 //                           ignored; prints ONE JSON line with tokens/s and the TTFT distribution
 //                           (metric definitions: client_qps_measure.cc:285-287,331,337-340)
 #include <algorithm>
+#include <fstream>
 #include <iostream>
 #include <random>
 #include <sstream>
@@ -34,6 +35,9 @@ int main(int argc, char** argv) {
     a.Def("--lora-map", "", "adapter slot of every request, -1 = none: 0,-1,1,... cycled over the requests (needs --lora-dirs)");
     a.Def("--guide-regex", "", "prompts4 / samples1024: guided decoding, every answer must match this regular expression in full (needs "
                                "--tokenizer-path; a scenario gives each request its own \"guide_regex\")");
+    a.Def("--guide-json-schema", "", "prompts4 / samples1024: guided decoding, every answer is a JSON document that fits the schema in this FILE "
+                                     "(src/common/guide_json.h; needs --tokenizer-path; a scenario gives each request its own "
+                                     "\"guide_json_schema\")");
     if (!a.Parse(argc, argv)) return -1;
     if (a.Bool("--help")) { a.PrintHelp(); return 0; }
 
@@ -116,8 +120,20 @@ int main(int argc, char** argv) {
         return -1;
     }
 
+    std::string guide_json_schema;
+    if (!a.Str("--guide-json-schema").empty()) {
+        std::ifstream ifs(a.Str("--guide-json-schema"));
+        if (!ifs.is_open()) {
+            std::cerr << "cannot read --guide-json-schema " << a.Str("--guide-json-schema") << "\n";
+            return -1;
+        }
+        std::stringstream buf;
+        buf << ifs.rdbuf();
+        guide_json_schema = buf.str();
+    }
     if (workload != "scenario")
         for (auto& r : requests) {
+            r->guide_json_schema = guide_json_schema;
             r->num_logprobs = a.Int("--num-logprobs");
             r->prompt_logprobs = a.Int("--prompt-logprobs");
             r->guide_regex = a.Str("--guide-regex");
