@@ -567,6 +567,16 @@ PPLHIP_API int pplhip_op_linear_ex(void* stream, const void* x, const void* w, c
                                    int64_t M, int32_t N, int32_t K, void* y, int64_t ldy, int32_t epi, void* ws, uint64_t ws_bytes,
                                    int32_t dry_run, char* route, int32_t route_len);
 
+/* pplhip_op_linear_i8 (act_fmt PPLHIP_ACT_QUANT_I8) / pplhip_op_linear_f8 (act_fmt PPLHIP_ACT_QUANT_FP8) with the caller's row stride
+ * ldy (elements) and epilogue epi (0 fp16, 1 fp32, 2 fused SwiGLU: y[M, N/2]), and the route record and dry run of
+ * pplhip_op_linear_ex: route receives e.g.
+ * "kernel=gemm_i8_pc_kernel<f16,4,f8> grid=8x1 threads=512 lds=131072 n_tiles=1 m_tiles=1" -- the kernel template with all its
+ * arguments, the grid, the block size, the dynamic LDS bytes and the tile counts.  dry_run != 0: the route and the status exactly
+ * as a launch would give them, no HIP call at all (no device needed).  For the tests: not part of the product boundary. */
+PPLHIP_API int pplhip_op_linear_q8_ex(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int32_t act_fmt,
+                                      int64_t M, int32_t N, int32_t K, void* y, int64_t ldy, int32_t epi, int32_t dry_run, char* route,
+                                      int32_t route_len);
+
 /* The step schedule as a pure function (pplhip.cc plan_step: no HIP call, no environment read, no context, no device): what
  * pplhip_run executes for a step of this shape under these settings, and what pplhip_comm_info reports.  For the tests: not part of
  * the product boundary.  A chunk is requests [b0, b0 + bn) = token rows [t0, t0 + tn), its first nd requests decode rows. */

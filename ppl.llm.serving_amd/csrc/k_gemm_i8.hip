@@ -35,7 +35,7 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // accumulator of a 16 x 16 tile: exact int32 sums (int8) or fp32 (fp8 -- exact as well for operands whose sums stay below 2^24)
 template <bool F8> using qacc_t = std::conditional_t<F8, f4v, i4v>;
 
-constexpr int I_BN = 128, I_BM = 128, I_BK = 128;
+// (the tile sizes I_BN / I_BM / I_BK and IW_* are in k_gemm_tiles.h: the launch plan sizes its grids from them)
 
 __device__ __forceinline__ float block_max_256(float v, float* red) {
 #pragma unroll
@@ -278,8 +278,6 @@ __global__ __launch_bounds__(512) void gemm_i8_pc_kernel(const int8_t* __restric
 // tile 64 x 64 like the waves of the kernel above, share ONE activation tile; four producer waves keep a two-stage ring of 64 KiB filled.
 // Two co-resident 128 x 128 blocks move 64 KiB per 1024 MFMA cycles and CU -- the whole 64 B / clk of the CU's vector-memory path --, this
 // block moves 64 KiB per 3072 (profiles/r03_gemm_experiments.md #16-17).  Taken when its tiles fill rounds of 256 one-per-CU blocks.
-constexpr int IW_BN = 384, IW_NC = 12, IW_NP = 4, IW_ST = 2;
-constexpr int IW_XB = I_BM * I_BK, IW_WB = IW_BN * I_BK;       // 16 KiB + 48 KiB per stage
 constexpr int IW_PP = (IW_XB + IW_WB) / 1024 / IW_NP;           // 16 one-KiB pieces per producer wave and tile (4 activation + 12 weight)
 template <int EPI, bool F8>
 __global__ __launch_bounds__((IW_NC + IW_NP) * 64) void gemm_i8_wide_kernel(const int8_t* __restrict__ xq, const float* __restrict__ sx,
@@ -534,100 +532,88 @@ hipError_t launch_quant_weight_f8(hipStream_t s, const uint16_t* w, int N, int K
     return hipGetLastError();
 }
 
-// the int8 (F8 false) and fp8 (F8 true) launches share one dispatch table, except that fp8 has no 256 x 256 form (steps of M >= 4096
-// take the 128 x 128 producer / consumer form)
+// launch_linear_q8: validate -> plan_linear_q8 (linear_plan.cc: which kernel, which grid, which template arguments; int8 and fp8 share the
+// dispatch table, except that fp8 has no 256 x 256 form) -> route text -> one switch on the family.  The LDS opt-in stays a launch-time
+// action (once per device and format), so a dry run makes no HIP call.
 template <bool F8>
 static hipError_t launch_linear_q8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M,
-                                   int N, int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
+                                   int N, int K, void* y, int64_t ldy, bool out_fp32, bool swiglu, LinearRoute* route) {
     if (M == 0) return hipSuccess;
     if (swiglu && out_fp32) return hipErrorInvalidValue;
-    if (N % 4 || ldy % 4 || K % 16) return hipErrorInvalidValue;
     const int epi = swiglu ? EPI_SWIGLU : (out_fp32 ? EPI_F32 : EPI_F16);
-    static const bool force_generic = tune_set("PPLHIP_GEMM_GENERIC");
-    if (M > 32 && K % I_BK == 0 && !force_generic) {
-        const int n_tiles = (N + I_BN - 1) / I_BN, m_tiles = (int)((M + I_BM - 1) / I_BM);
-        static const int min_m256 = tune_int("PPLHIP_GEMM_I8_256_MIN_M", 4096);  // measured: M = 4096 layer 888 us (1.87 POP/s) vs 1110, M = 2048 554 vs 459 us
-        if (!F8 && M >= min_m256 && N >= 1024) {
-            const int nt2 = (N + 255) / 256, mt2 = (int)((M + 255) / 256);
-            static const int st256 = tune_int("PPLHIP_GEMM_I8_256_ST", 4) == 3 ? 3 : 4;
-            const size_t lds2 = (size_t)st256 * 2 * 256 * 64;
-            static LdsOptIn once;  // (per device: see k_launch.h)
+    if (!linear_q8_valid(M, N, K, ldy, epi)) return hipErrorInvalidValue;
+    static const Q8Tuning tuning = Q8Tuning::from_env();
+    const Q8Plan p = plan_linear_q8(F8, M, N, K, ldy, epi, tuning);
+    if (!p.ok) return hipErrorInvalidValue;
+    if (route) {
+        char text[256];
+        format_route(p, text, (int)sizeof text);
+        route->add("%s", text);
+        if (route->dry) return hipSuccess;
+    }
+    const dim3 grid(p.grid_x, p.grid_y), block(p.threads);
+    switch (p.family) {
+        case QF_256:
+            if constexpr (!F8) {
+                static LdsOptIn once;  // (per device: see k_launch.h)
+                if (once.first())
+                    for_each_epi([](auto E) {
+                        set_max_lds(i8_256_lds_bytes(3), gemm_i8_256_kernel<E, 3>);
+                        set_max_lds(i8_256_lds_bytes(4), gemm_i8_256_kernel<E, 4>);
+                    });
+                dispatch_epi(epi, [&](auto E) {
+                    dispatch_int<3, 4>(p.stages, [&](auto ST) {
+                        hipLaunchKernelGGL((gemm_i8_256_kernel<E, ST>), grid, block, p.lds, s, xq, sx, w, scale, M, N, K, y, ldy, p.n_tiles, p.m_tiles,
+                                           p.gn, p.gm);
+                    });
+                });
+                break;
+            }
+            return hipErrorInvalidValue;   // (the plan gives fp8 no 256 x 256 form)
+        case QF_WIDE: {
+            static LdsOptIn once;
+            if (once.first())
+                set_max_lds(i8_wide_lds_bytes(), gemm_i8_wide_kernel<EPI_F16, F8>, gemm_i8_wide_kernel<EPI_F32, F8>, gemm_i8_wide_kernel<EPI_SWIGLU, F8>);
+            dispatch_epi(epi, [&](auto E) {
+                hipLaunchKernelGGL((gemm_i8_wide_kernel<E, F8>), grid, block, p.lds, s, xq, sx, w, scale, M, N, K, y, ldy, p.n_tiles, p.m_tiles);
+            });
+            break;
+        }
+        case QF_PC: {
+            static LdsOptIn once;
             if (once.first())
                 for_each_epi([](auto E) {
-                    set_max_lds(3 * 2 * 256 * 64, gemm_i8_256_kernel<E, 3>);
-                    set_max_lds(4 * 2 * 256 * 64, gemm_i8_256_kernel<E, 4>);
+                    set_max_lds(i8_pc_lds_bytes(3), gemm_i8_pc_kernel<E, 3, F8>);
+                    set_max_lds(i8_pc_lds_bytes(4), gemm_i8_pc_kernel<E, 4, F8>);
+                    set_max_lds(i8_pc_lds_bytes(2), gemm_i8_pc_kernel<E, 2, F8>);
                 });
-            static const int forced_gm = tune_int("PPLHIP_GEMM256_GM", 0);
-            static const int forced_gn = tune_int("PPLHIP_GEMM256_GN", 0);
-            const int nl = (nt2 + 7) / 8;
-            int gm = forced_gm > 0 ? forced_gm : 4;
-            while (gm > 1 && mt2 % gm) --gm;
-            int gn = forced_gn > 0 ? forced_gn : 8;
-            if (gn > nl) gn = nl;
-            dim3 g2((unsigned)(8 * ((nl + gn - 1) / gn * gn) * mt2));
             dispatch_epi(epi, [&](auto E) {
-                dispatch_int<3, 4>(st256, [&](auto ST) {
-                    hipLaunchKernelGGL((gemm_i8_256_kernel<E, ST>), g2, dim3(512), lds2, s, xq, sx, w, scale, M, N, K, y, ldy, nt2, mt2, gn, gm);
+                dispatch_int<2, 3, 4>(p.stages, [&](auto ST) {
+                    hipLaunchKernelGGL((gemm_i8_pc_kernel<E, ST, F8>), grid, block, p.lds, s, xq, sx, w, scale, M, N, K, y, ldy, p.n_tiles, p.m_tiles);
                 });
             });
-            return hipGetLastError();
+            break;
         }
-        // 128 x 384 tiles when they fill rounds of 256 one-per-CU blocks (the rule of linear_w8_wide_waves, k_gemm_wide.hip)
-        static const int wide = tune_int("PPLHIP_GEMM_I8_WIDE", 1);
-        if (wide && M >= 512 && N >= 8192 && linear_w8_wide_waves(M, N) == 12) {
-            const int ntw = (N + IW_BN - 1) / IW_BN;
-            const size_t ldsw = (size_t)IW_ST * (IW_XB + IW_WB);
-            static LdsOptIn once;
-            if (once.first()) set_max_lds(ldsw, gemm_i8_wide_kernel<EPI_F16, F8>, gemm_i8_wide_kernel<EPI_F32, F8>, gemm_i8_wide_kernel<EPI_SWIGLU, F8>);
-            dim3 gw((unsigned)((ntw + 7) / 8 * 8 * m_tiles));
+        case QF_GEMV:
             dispatch_epi(epi, [&](auto E) {
-                hipLaunchKernelGGL((gemm_i8_wide_kernel<E, F8>), gw, dim3((IW_NC + IW_NP) * 64), ldsw, s, xq, sx, w, scale, M, N, K, y, ldy, ntw, m_tiles);
+                auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, xq, sx, w, scale, M, N, K, y, ldy); };
+                if (p.mt == 2) go(gemv_i8_kernel<2, E, 4, F8>);
+                else if (p.nw == 8) go(gemv_i8_kernel<1, E, 8, F8>);
+                else go(gemv_i8_kernel<1, E, 4, F8>);
             });
-            return hipGetLastError();
-        }
-        // 8-wave producer / consumer blocks for everything else (measured at M = 1024 against the 4-wave kernel this file held until it
-        // had lost on every shape: wo 32.5 -> 28.6 us and w2 76.0 -> 51.4 us with a 4-stage ring, one block per CU; w13 116.6 -> 106.0 us
-        // with two stages, two blocks per CU; wqkv 62.1 vs 63.6 us; M = 2048 layer 502 -> 459 us, M = 8192 equal).  In a tuning build
-        // PPLHIP_GEMM_I8_PC = 3 / 4 forces that ring depth; any other value, 0 included, runs the two-stage form.
-        static const int forced_pc = tune_int("PPLHIP_GEMM_I8_PC", -1);
-        int pc = forced_pc >= 0 ? forced_pc : ((int64_t)n_tiles * m_tiles <= 256 ? 4 : 2);
-        if (pc != 3 && pc != 4) pc = 2;
-        const size_t lds_pc = (size_t)pc * 2 * I_BM * I_BK;
-        static LdsOptIn once;
-        if (once.first())
-            for_each_epi([](auto E) {
-                set_max_lds(3 * 2 * I_BM * I_BK, gemm_i8_pc_kernel<E, 3, F8>);
-                set_max_lds(4 * 2 * I_BM * I_BK, gemm_i8_pc_kernel<E, 4, F8>);
-                set_max_lds(2 * 2 * I_BM * I_BK, gemm_i8_pc_kernel<E, 2, F8>);
-            });
-        dim3 grid((unsigned)((n_tiles + 7) / 8 * 8 * m_tiles));
-        dispatch_epi(epi, [&](auto E) {
-            dispatch_int<2, 3, 4>(pc, [&](auto ST) {
-                hipLaunchKernelGGL((gemm_i8_pc_kernel<E, ST, F8>), grid, dim3(512), lds_pc, s, xq, sx, w, scale, M, N, K, y, ldy, n_tiles, m_tiles);
-            });
-        });
-        return hipGetLastError();
+            break;
     }
-    // skinny / generic: one 16-row activation tile per block up to 16 rows (eight K slices while the row tiles are few), else two
-    const int nblk = (N + 15) / 16;
-    dim3 grid((unsigned)nblk, M <= 16 ? 1u : (unsigned)((M + 31) / 32));
-    dispatch_epi(epi, [&](auto E) {
-        auto go = [&](auto kernel, unsigned threads) { hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, s, xq, sx, w, scale, M, N, K, y, ldy); };
-        if (M > 16) go(gemv_i8_kernel<2, E, 4, F8>, 256);
-        else if (nblk <= 1024) go(gemv_i8_kernel<1, E, 8, F8>, 512);
-        else go(gemv_i8_kernel<1, E, 4, F8>, 256);
-    });
     return hipGetLastError();
 }
 
 hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M, int N,
-                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
-    return launch_linear_q8<false>(s, xq, sx, w, scale, M, N, K, y, ldy, out_fp32, swiglu);
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu, LinearRoute* route) {
+    return launch_linear_q8<false>(s, xq, sx, w, scale, M, N, K, y, ldy, out_fp32, swiglu, route);
 }
 
 hipError_t launch_linear_f8(hipStream_t s, const uint8_t* xq, const float* sx, const uint8_t* w, const uint16_t* scale, int64_t M, int N,
-                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu) {
-    return launch_linear_q8<true>(s, (const int8_t*)xq, sx, (const int8_t*)w, scale, M, N, K, y, ldy, out_fp32, swiglu);
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu, LinearRoute* route) {
+    return launch_linear_q8<true>(s, (const int8_t*)xq, sx, (const int8_t*)w, scale, M, N, K, y, ldy, out_fp32, swiglu, route);
 }
 
 }  // namespace pplhip

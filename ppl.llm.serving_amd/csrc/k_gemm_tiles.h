@@ -45,6 +45,21 @@ constexpr int PC_LDS = PC_NS * (PC_XB + PC_RAWB + PC_SCB);
 // streaming GEMV (gemv_stream_kernel): most waves per block, most weight rows per wave, rows in flight per wave
 constexpr int GV_NW = 8, GV_RB = 16, GV_U = 8;
 
+// quantised-activation kernels (k_gemm_i8.hip; int8 and fp8 alike): block tile 128 (n) x 128 (m) x 128 (k) of one-byte codes, ring stages of
+// X 16 KiB + W 16 KiB (gemm_i8_pc_kernel); the 128 x 384 blocks (gemm_i8_wide_kernel): twelve consumer + four producer waves, two stages of
+// X 16 KiB + W 48 KiB; the 256 x 256 x 64 blocks (gemm_i8_256_kernel, int8 only): stages of X 16 KiB + W 16 KiB; the skinny kernel
+// (gemv_i8_kernel): 16 weight rows per block, 16-row activation tiles
+constexpr int I_BN = 128, I_BM = 128, I_BK = 128;
+constexpr int IW_BN = 384, IW_NC = 12, IW_NP = 4, IW_ST = 2;
+constexpr int IW_XB = I_BM * I_BK, IW_WB = IW_BN * I_BK;       // 16 KiB + 48 KiB per stage
+constexpr int I2_BN = 256, I2_BM = 256, I2_BK = 64;
+constexpr int IV_BN = 16, IV_BM = 16;
+constexpr int i8_pc_lds_bytes(int st) { return st * 2 * I_BM * I_BK; }
+constexpr int i8_wide_lds_bytes() { return IW_ST * (IW_XB + IW_WB); }
+constexpr int i8_256_lds_bytes(int st) { return st * 2 * I2_BM * I2_BK; }
+// static LDS of the skinny kernel: the partial accumulators of its NW - 1 other K slices, MT row tiles of 64 lanes x 16 bytes
+constexpr int i8_gemv_lds_bytes(int mt, int nw) { return (nw - 1) * mt * 64 * 16; }
+
 constexpr int LDS_PER_CU = 160 * 1024;
 static_assert(H_LDS <= LDS_PER_CU && PC_LDS <= LDS_PER_CU && wide_lds_bytes(WD_ST, 12) <= LDS_PER_CU, "one block per CU");
 

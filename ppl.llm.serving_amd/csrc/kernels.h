@@ -152,8 +152,9 @@ hipError_t launch_quant_act(hipStream_t s, const uint16_t* x, int64_t M, int K, 
 // per-output-row int8 weights from an fp16 [N, K] matrix: q [N, ldq], scale [N] fp16
 hipError_t launch_quant_weight(hipStream_t s, const uint16_t* w, int N, int K, int8_t* q, int64_t ldq, uint16_t* scale);
 // y[M,N] = fp16/fp32( (sum_k xq * w) * sx[m] * scale[n] ); K = row stride of xq and w (K % 16 == 0)
+// (which kernel takes a problem: plan_linear_q8, linear_plan.h; route: the path taken (tests), null: no record)
 hipError_t launch_linear_i8(hipStream_t s, const int8_t* xq, const float* sx, const int8_t* w, const uint16_t* scale, int64_t M, int N,
-                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu);
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu, LinearRoute* route = nullptr);
 // online_f8f8 (fp8 e4m3fn W8A8): per-row codes under one power-of-two scale (the fp8 KV row rule, k_common.h fp8_row_exp / fp8_quant)
 // activations: q [M, ldq] (columns K..ldq-1 zeroed), sx [M] = 2^e (fp32)
 hipError_t launch_quant_act_f8(hipStream_t s, const uint16_t* x, int64_t M, int K, int64_t ldx, uint8_t* q, int64_t ldq, float* sx);
@@ -161,7 +162,7 @@ hipError_t launch_quant_act_f8(hipStream_t s, const uint16_t* x, int64_t M, int 
 hipError_t launch_quant_weight_f8(hipStream_t s, const uint16_t* w, int N, int K, uint8_t* q, int64_t ldq, uint16_t* scale);
 // y[M,N] = fp16/fp32( (sum_k xq * w) * sx[m] * scale[n] ), fp32 sums; K = row stride of xq and w (K % 16 == 0)
 hipError_t launch_linear_f8(hipStream_t s, const uint8_t* xq, const float* sx, const uint8_t* w, const uint16_t* scale, int64_t M, int N,
-                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu);
+                            int K, void* y, int64_t ldy, bool out_fp32, bool swiglu, LinearRoute* route = nullptr);
 // dst row r = src row perm(r): r even -> r/2 (gate), r odd -> half + r/2 (up).  row_bytes % 4 == 0.
 hipError_t launch_interleave_rows(hipStream_t s, const void* src, void* dst, int rows, int64_t row_bytes);
 

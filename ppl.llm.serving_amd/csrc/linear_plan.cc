@@ -326,6 +326,97 @@ int format_route(const LinearPart& p, char* buf, int cap) {
     return n < cap ? n : cap - 1;
 }
 
+// ---- the quantised-activation linears --------------------------------------------------------------------------------------------------
+Q8Tuning Q8Tuning::from_env() {
+    Q8Tuning t;
+    t.force_generic = tune_set("PPLHIP_GEMM_GENERIC");
+    t.min_m256 = tune_int("PPLHIP_GEMM_I8_256_MIN_M", t.min_m256);
+    t.st256 = tune_int("PPLHIP_GEMM_I8_256_ST", t.st256);
+    t.gm256 = tune_int("PPLHIP_GEMM256_GM", t.gm256);
+    t.gn256 = tune_int("PPLHIP_GEMM256_GN", t.gn256);
+    t.wide = tune_int("PPLHIP_GEMM_I8_WIDE", t.wide);
+    t.pc = tune_int("PPLHIP_GEMM_I8_PC", t.pc);
+    return t;
+}
+
+bool linear_q8_valid(int64_t M, int N, int K, int64_t ldy, int epi) {
+    if (M < 1 || (epi != EPI_F16 && epi != EPI_F32 && epi != EPI_SWIGLU)) return false;
+    return !(N % 4 || ldy % 4 || K % 16);
+}
+
+// int8 and fp8 share one dispatch table, except that fp8 has no 256 x 256 form (steps of M >= 4096 take the 128 x 128 producer / consumer
+// form)
+Q8Plan plan_linear_q8(bool f8, int64_t M, int N, int K, int64_t ldy, int epi, const Q8Tuning& t) {
+    Q8Plan p;
+    (void)ldy;
+    p.ok = true, p.f8 = f8, p.epi = epi;
+    if (M > 32 && K % I_BK == 0 && !t.force_generic) {
+        const int n_tiles = (N + I_BN - 1) / I_BN, m_tiles = (int)((M + I_BM - 1) / I_BM);
+        if (!f8 && M >= t.min_m256 && N >= 1024) {
+            // super-tile shape: gm = the largest divisor of the activation tiles <= 4, gn = up to 8 weight tiles of the XCD's share; the share
+            // is padded to whole super-tiles (the extra blocks return at once)
+            const int nt2 = (N + I2_BN - 1) / I2_BN, mt2 = (int)((M + I2_BM - 1) / I2_BM);
+            const int nl = (nt2 + 7) / 8;
+            int gm = t.gm256 > 0 ? t.gm256 : 4;
+            while (gm > 1 && mt2 % gm) --gm;
+            int gn = t.gn256 > 0 ? t.gn256 : 8;
+            if (gn > nl) gn = nl;
+            p.family = QF_256;
+            p.stages = t.st256 == 3 ? 3 : 4;
+            p.bn = I2_BN, p.bm = I2_BM, p.bk = I2_BK;
+            p.n_tiles = nt2, p.m_tiles = mt2, p.gn = gn, p.gm = gm;
+            p.grid_x = (unsigned)(8 * ((nl + gn - 1) / gn * gn) * mt2), p.threads = 512, p.lds = (size_t)i8_256_lds_bytes(p.stages);
+            return p;
+        }
+        // 128 x 384 tiles when they fill rounds of 256 one-per-CU blocks (the rule of linear_w8_wide_waves)
+        if (t.wide && M >= 512 && N >= 8192 && linear_w8_wide_waves(M, N) == 12) {
+            p.family = QF_WIDE;
+            p.stages = IW_ST;
+            p.bn = IW_BN, p.bm = I_BM, p.bk = I_BK;
+            p.n_tiles = (N + IW_BN - 1) / IW_BN, p.m_tiles = m_tiles;
+            p.grid_x = xcd_grid(p.n_tiles, m_tiles), p.threads = (unsigned)(IW_NC + IW_NP) * 64, p.lds = (size_t)i8_wide_lds_bytes();
+            return p;
+        }
+        // 8-wave producer / consumer blocks for everything else (measured at M = 1024 against the 4-wave kernel k_gemm_i8.hip held until it
+        // had lost on every shape: wo 32.5 -> 28.6 us and w2 76.0 -> 51.4 us with a 4-stage ring, one block per CU; w13 116.6 -> 106.0 us
+        // with two stages, two blocks per CU; wqkv 62.1 vs 63.6 us; M = 2048 layer 502 -> 459 us, M = 8192 equal)
+        int pc = t.pc >= 0 ? t.pc : ((int64_t)n_tiles * m_tiles <= 256 ? 4 : 2);
+        if (pc != 3 && pc != 4) pc = 2;
+        p.family = QF_PC;
+        p.stages = pc;
+        p.bn = I_BN, p.bm = I_BM, p.bk = I_BK;
+        p.n_tiles = n_tiles, p.m_tiles = m_tiles;
+        p.grid_x = xcd_grid(n_tiles, m_tiles), p.threads = 512, p.lds = (size_t)i8_pc_lds_bytes(pc);
+        return p;
+    }
+    // skinny / generic: one 16-row activation tile per block up to 16 rows (eight K slices while the row tiles are few), else two
+    const int nblk = (N + IV_BN - 1) / IV_BN;
+    p.family = QF_GEMV;
+    p.mt = M > 16 ? 2 : 1;
+    p.nw = M > 16 ? 4 : (nblk <= 1024 ? 8 : 4);
+    p.bn = IV_BN, p.bm = p.mt * IV_BM;
+    p.n_tiles = nblk, p.m_tiles = M <= 16 ? 1 : (int)((M + 31) / 32);
+    p.grid_x = (unsigned)nblk, p.grid_y = (unsigned)p.m_tiles, p.threads = (unsigned)p.nw * 64;
+    return p;
+}
+
+int format_route(const Q8Plan& p, char* buf, int cap) {
+    char kernel[96], order[32] = "";
+    const char *e = epi_name(p.epi), *f = p.f8 ? "f8" : "i8";
+    switch (p.family) {
+        case QF_GEMV: snprintf(kernel, sizeof kernel, "gemv_i8_kernel<%d,%s,%d,%s>", p.mt, e, p.nw, f); break;
+        case QF_PC: snprintf(kernel, sizeof kernel, "gemm_i8_pc_kernel<%s,%d,%s>", e, p.stages, f); break;
+        case QF_WIDE: snprintf(kernel, sizeof kernel, "gemm_i8_wide_kernel<%s,%s>", e, f); break;
+        case QF_256:
+            snprintf(kernel, sizeof kernel, "gemm_i8_256_kernel<%s,%d>", e, p.stages);
+            snprintf(order, sizeof order, " order=super(%dx%d)", p.gm, p.gn);
+            break;
+    }
+    const int n = snprintf(buf, (size_t)cap, "kernel=%s grid=%ux%u threads=%u lds=%zu n_tiles=%d m_tiles=%d%s", kernel, p.grid_x, p.grid_y,
+                           p.threads, p.lds, p.n_tiles, p.m_tiles, order);
+    return n < cap ? n : cap - 1;
+}
+
 int format_route(const LinearPlan& plan, char* buf, int cap) {
     int len = 0;
     if (cap > 0) buf[0] = 0;

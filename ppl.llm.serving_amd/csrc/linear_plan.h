@@ -123,6 +123,43 @@ bool plan_w8_wide(int64_t M, int N, int epi, int nc, LinearPart* part);
 int format_route(const LinearPart& part, char* buf, int cap);
 int format_route(const LinearPlan& plan, char* buf, int cap);
 
+// ---- the quantised-activation linears (launch_linear_i8 / launch_linear_f8, k_gemm_i8.hip): the same seam ------------------------------------
+//   launch_linear_q8 = validate -> plan_linear_q8 -> format_route (if asked) -> one switch on the family -> launch.
+// The switches it reads (a tuning build only, k_tune.h), with the compiled-in values as defaults; from_env() fills them once per process.
+struct Q8Tuning {
+    bool force_generic = false;   // PPLHIP_GEMM_GENERIC (set): the skinny / generic kernel for every shape
+    // 256 x 256 blocks from this many rows (int8 only); measured: M = 4096 layer 888 us (1.87 POP/s) vs 1110, M = 2048 554 vs 459 us
+    int min_m256 = 4096;          // PPLHIP_GEMM_I8_256_MIN_M
+    int st256 = 4;                // PPLHIP_GEMM_I8_256_ST (3: a three-stage ring; any other value: four)
+    int gm256 = 0, gn256 = 0;     // PPLHIP_GEMM256_GM / _GN (0: 4 x 8)
+    int wide = 1;                 // PPLHIP_GEMM_I8_WIDE (0: never the 128 x 384 blocks)
+    // ring depth of the 128 x 128 producer / consumer blocks: 3 / 4 force it, any other value >= 0 runs two stages; < 0: four stages for
+    // launches of <= 256 tiles, else two
+    int pc = -1;                  // PPLHIP_GEMM_I8_PC
+    static Q8Tuning from_env();
+};
+
+enum Q8Family { QF_GEMV, QF_PC, QF_WIDE, QF_256 };
+// One launch.  Template arguments by family (FMT: i8 / f8):
+//   QF_GEMV gemv_i8_kernel<mt, epi, nw, FMT>     QF_PC gemm_i8_pc_kernel<epi, stages, FMT>     QF_WIDE gemm_i8_wide_kernel<epi, FMT>
+//   QF_256 gemm_i8_256_kernel<epi, stages> (int8 only)
+struct Q8Plan {
+    bool ok = false;              // false: no kernel takes the problem (an argument error)
+    Q8Family family = QF_GEMV;
+    bool f8 = false;
+    int epi = EPI_F16, stages = 0, mt = 0, nw = 0;   // mt: 16-row activation tiles per block of the skinny kernel
+    unsigned grid_x = 0, grid_y = 1, threads = 0;
+    size_t lds = 0;               // dynamic LDS bytes
+    int bn = 0, bm = 0, bk = 0;   // weight rows / activation rows / k of a block tile (bk 0: the waves split K)
+    int n_tiles = 0, m_tiles = 0;
+    int gn = 0, gm = 0;           // QF_256: super-tiles of gn (n) x gm (m) tiles
+};
+// the argument rules of launch_linear_i8 / _f8 (M > 0): N and ldy multiples of 4, K a multiple of the 16-byte load, no fp32 SwiGLU
+bool linear_q8_valid(int64_t M, int N, int K, int64_t ldy, int epi);
+Q8Plan plan_linear_q8(bool f8, int64_t M, int N, int K, int64_t ldy, int epi, const Q8Tuning& t);
+// "kernel=<template<args>> grid= threads= lds= n_tiles= m_tiles= [order=super(gm x gn)]"; returns the length
+int format_route(const Q8Plan& plan, char* buf, int cap);
+
 // largest M the streaming GEMV takes for this shape (0: none); env_max_m: LinearTuning::gemv_stream_max_m
 int gemv_stream_max_m(int wq_bit, int group, int N, int K, int env_max_m);
 // 12 consumer waves when the 128 x 384 tiles fill whole rounds of 256 one-per-CU blocks well enough, else 0

@@ -98,6 +98,25 @@ int pplhip_op_linear_f8(void* stream, const void* xq, const float* sx, const voi
                                   swiglu ? N / 2 : N, out_fp32 != 0, swiglu != 0));
 }
 
+// launch_linear_i8 / _f8 with the caller's row stride and the route it takes (kernels.h LinearRoute); dry_run: the route and status only, no
+// HIP call at all (works without a device)
+int pplhip_op_linear_q8_ex(void* stream, const void* xq, const float* sx, const void* w, const void* scale, int32_t act_fmt, int64_t M,
+                           int32_t N, int32_t K, void* y, int64_t ldy, int32_t epi, int32_t dry_run, char* route, int32_t route_len) {
+    LinearRoute r;
+    r.buf = route_len > 0 ? route : nullptr;
+    r.cap = route_len;
+    r.dry = dry_run != 0;
+    if (r.buf) r.buf[0] = 0;
+    if (epi < 0 || epi > 2) return PPLHIP_INVALID_VALUE;
+    if (act_fmt == PPLHIP_ACT_QUANT_I8)
+        return op_rc(launch_linear_i8((hipStream_t)stream, (const int8_t*)xq, sx, (const int8_t*)w, (const uint16_t*)scale, M, N, K, y, ldy,
+                                      epi == 1, epi == 2, &r));
+    if (act_fmt == PPLHIP_ACT_QUANT_FP8)
+        return op_rc(launch_linear_f8((hipStream_t)stream, (const uint8_t*)xq, sx, (const uint8_t*)w, (const uint16_t*)scale, M, N, K, y, ldy,
+                                      epi == 1, epi == 2, &r));
+    return PPLHIP_INVALID_VALUE;
+}
+
 int pplhip_op_step_plan(const pplhip_plan_settings* settings, const pplhip_step_shape* shape, pplhip_step_plan* out) {
     if (!settings || !shape || !out || shape->batch < 0 || shape->num_tokens < 0) return PPLHIP_INVALID_VALUE;
     *out = plan_step(*settings, *shape);

@@ -180,7 +180,7 @@ SYMBOLS = [
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_set_prompt_logprobs", "pplhip_prompt_logprobs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
     "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_guide_set_vocab", "pplhip_guide_load", "pplhip_guide_unload", "pplhip_guide_edit", "pplhip_guide_load16", "pplhip_guide16_state_chunk", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
-    "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
+    "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_linear_q8_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
     "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_guide_build16", "pplhip_op_guide_mask16", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
@@ -261,6 +261,8 @@ def lib():
         L.pplhip_op_quant_act_f8.argtypes = [vp, vp, i64, i32, vp, vp]
         L.pplhip_op_quant_weight_f8.argtypes = [vp, vp, i32, i32, vp, vp]
         L.pplhip_op_linear_f8.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, i32]
+        if hasattr(L, "pplhip_op_linear_q8_ex"):   # (PPLHIP_LIB may name a build from before it, as above)
+            L.pplhip_op_linear_q8_ex.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, i32, vp, i64, i32, i32, C.c_char_p, i32]
         L.pplhip_op_silu_mul.argtypes = [vp, vp, i64, i32, vp]
         L.pplhip_op_penalty.argtypes = [vp] * 10 + [i32, i32, i32, i32, vp]
         L.pplhip_op_sample.argtypes = [vp] * 5 + [i32, i32, i32, i32, f32, vp, vp]
@@ -312,6 +314,13 @@ def linear_route(x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws=None, ws_b
     """pplhip_op_linear_ex: (status, route text).  Pointers are integers (device addresses; a dry run never dereferences them)."""
     buf = C.create_string_buffer(1024)
     rc = lib().pplhip_op_linear_ex(stream, x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws, ws_bytes, int(dry_run), buf, 1024)
+    return rc, buf.value.decode()
+
+
+def linear_q8_route(xq, sx, w, scale, act_fmt, M, N, K, y, ldy, epi, dry_run=True, stream=None):
+    """pplhip_op_linear_q8_ex (act_fmt 8: int8, 0x108: fp8 e4m3): (status, route text).  Pointers are integers, as in linear_route."""
+    buf = C.create_string_buffer(1024)
+    rc = lib().pplhip_op_linear_q8_ex(stream, xq, sx, w, scale, act_fmt, M, N, K, y, ldy, epi, int(dry_run), buf, 1024)
     return rc, buf.value.decode()
 
 

@@ -4,6 +4,8 @@
 // Every plan is checked against the conditions the kernels rely on (check_part / check_plan below); the first plan that breaks one is
 // named on stderr with its input line and the program exits 1.
 // The x / w / scale addresses are the aligned fake ones of tests/gemm_exact.py dry_route (scale 0 for fp16 weights).
+// `linear_plan_trace q8`: the plan of the quantised-activation linears (plan_linear_q8) instead.
+// stdin, one problem per line:   act_fmt(8 | 264) M N K epi ldy          stdout and the checks (check_q8 below): as above
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -114,7 +116,102 @@ static std::string check_plan(const LinearProblem& pr, const LinearPlan& plan) {
     return "";
 }
 
-int main() {
+// the quantised-activation kernels (k_gemm_i8.hip): "" or the condition a plan breaks
+static std::string check_q8(int64_t M, int N, int K, const Q8Plan& p) {
+    REQUIRE(p.grid_x >= 1 && p.grid_y >= 1 && p.n_tiles >= 1 && p.m_tiles >= 1);
+    REQUIRE((int64_t)p.n_tiles * p.bn >= N && (int64_t)(p.n_tiles - 1) * p.bn < N);
+    REQUIRE((int64_t)p.m_tiles * p.bm >= M && (int64_t)(p.m_tiles - 1) * p.bm < M);
+    REQUIRE(p.lds <= (size_t)LDS_PER_CU && p.threads <= 1024);
+    if (p.family == QF_GEMV) {
+        // any M, K % 16 == 0: blockIdx.x walks 16 weight rows, blockIdx.y the 16 / 32-row activation groups; static LDS only
+        REQUIRE(K % 16 == 0);
+        REQUIRE(p.grid_x == (unsigned)p.n_tiles && p.grid_y == (unsigned)p.m_tiles && p.lds == 0);
+        REQUIRE((p.mt == 1 && (p.nw == 4 || p.nw == 8) && M <= 16) || (p.mt == 2 && p.nw == 4 && M > 16));
+        REQUIRE(p.bn == IV_BN && p.bm == p.mt * IV_BM && p.threads == (unsigned)p.nw * 64);
+        REQUIRE(i8_gemv_lds_bytes(p.mt, p.nw) <= 64 * 1024);
+        return "";
+    }
+    // the tile kernels: M > 32 and whole 128-deep K tiles only
+    REQUIRE(M > 32 && K % 128 == 0 && K % p.bk == 0 && p.grid_y == 1);
+    // the grid covers n_tiles * m_tiles after the round-up to the 8 XCDs, each tile by exactly one block
+    REQUIRE((uint64_t)p.grid_x >= (uint64_t)p.n_tiles * (uint64_t)p.m_tiles && p.grid_x % 8 == 0);
+    if (p.family != QF_256) REQUIRE(p.grid_x == (unsigned)((p.n_tiles + 7) / 8 * 8 * p.m_tiles));
+    if (p.family == QF_256) REQUIRE(p.gm >= 1 && p.gn >= 1 && p.m_tiles % p.gm == 0 && p.grid_x % (8u * p.gn * p.gm) == 0);
+    if (p.grid_x <= 8192) {
+        LinearPart q;   // (block_tile's fields)
+        q.family = LF_RING, q.n_tiles = p.n_tiles, q.m_tiles = p.m_tiles;
+        q.map = MapMode{0, 0, (uint8_t)p.gm, (uint8_t)p.gn};
+        std::vector<int> hits((size_t)p.n_tiles * p.m_tiles, 0);
+        for (unsigned id = 0; id < p.grid_x; ++id) {
+            int nt, mt;
+            if (!block_tile(q, id, &nt, &mt)) continue;
+            REQUIRE(nt >= 0 && mt >= 0 && mt < p.m_tiles);
+            ++hits[(size_t)nt * p.m_tiles + mt];
+        }
+        for (int h : hits) REQUIRE(h == 1);
+    }
+    // dynamic LDS = stages x (activation + weight bytes of a stage)
+    REQUIRE(p.stages >= 2 && p.lds == (size_t)p.stages * (size_t)(p.bm + p.bn) * p.bk);
+    switch (p.family) {
+        case QF_PC:
+            REQUIRE(p.bn == 128 && p.bm == 128 && p.bk == 128 && p.threads == 512 && p.stages <= 4);
+            REQUIRE(p.lds == (size_t)i8_pc_lds_bytes(p.stages));
+            break;
+        case QF_WIDE:
+            REQUIRE(p.bn == 384 && p.bm == 128 && p.bk == 128 && p.stages == IW_ST && p.threads == (unsigned)(IW_NC + IW_NP) * 64);
+            REQUIRE(M >= 512 && N >= 8192 && linear_w8_wide_waves(M, N) == 12);
+            REQUIRE(p.lds == (size_t)i8_wide_lds_bytes());
+            break;
+        case QF_256:
+            REQUIRE(!p.f8 && N >= 1024);
+            REQUIRE(p.bn == 256 && p.bm == 256 && p.bk == 64 && p.threads == 512 && (p.stages == 3 || p.stages == 4));
+            REQUIRE(p.lds == (size_t)i8_256_lds_bytes(p.stages));
+            break;
+        default: return "family";
+    }
+    return "";
+}
+
+static int main_q8() {
+    const Q8Tuning tuning = Q8Tuning::from_env();
+    static const char* kQ8Family[] = {"gemv", "pc", "wide", "256"};
+    char line[256], route[256];
+    long lineno = 0;
+    while (fgets(line, sizeof line, stdin)) {
+        ++lineno;
+        int fmt, N, K, epi;
+        long long M, ldy;
+        if (sscanf(line, "%d %lld %d %d %d %lld", &fmt, &M, &N, &K, &epi, &ldy) != 6) {
+            fprintf(stderr, "line %ld: expected 'act_fmt M N K epi ldy': %s", lineno, line);
+            return 2;
+        }
+        if (M == 0 && (fmt == 8 || fmt == 0x108) && epi >= 0 && epi <= 2) {
+            printf("0\t\t\n");
+            continue;
+        }
+        if ((fmt != 8 && fmt != 0x108) || !linear_q8_valid(M, N, K, ldy, epi)) {
+            printf("-2\t\t\n");
+            continue;
+        }
+        const Q8Plan p = plan_linear_q8(fmt == 0x108, M, N, K, ldy, epi, tuning);
+        if (!p.ok) {
+            printf("-2\t\t\n");
+            continue;
+        }
+        format_route(p, route, (int)sizeof route);
+        printf("0\t%s\tfamily=%s stages=%d bn=%d bm=%d bk=%d\n", route, kQ8Family[p.family], p.stages, p.bn, p.bm, p.bk);
+        const std::string bad = check_q8(M, N, K, p);
+        if (!bad.empty()) {
+            fflush(stdout);
+            fprintf(stderr, "line %ld breaks an invariant: %s\n  %s", lineno, bad.c_str(), line);
+            return 1;
+        }
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "q8") return main_q8();
     const LinearTuning tuning = LinearTuning::from_env();
     char line[512], route[512];
     long lineno = 0;
