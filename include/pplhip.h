@@ -369,6 +369,28 @@ typedef struct pplhip_sample_rows_args {
 PPLHIP_API int pplhip_sample_rows(pplhip_ctx* ctx, const float* logits_device, const pplhip_sample_rows_args* args,
                                   int32_t* output_host, float* logprob_host);
 
+/* pplhip_sample_rows with two more truncations per row (DESIGN.md "numerics", min_p / typical_p row).  min_p[b] keeps the candidates whose
+ * probability is at least min_p[b] times the most probable one's: off when <= 0 or NaN, values above 1 count as 1.  typical_p[b] is
+ * locally typical sampling over what top_k, top_p and min_p left, renormalised: the tokens are ordered by |-ln q - H| (H the entropy of q,
+ * ties by rank), the shortest prefix whose mass reaches typical_p[b] is kept, and the pick walks the kept tokens in rank order; off when
+ * <= 0, >= 1 or NaN.  Either pointer may be NULL: off for every row.  A row with top_k == 1 is greedy whatever else it carries; a row with
+ * both off is answered by pplhip_sample_rows' rule, bit for bit in token and logprob, and a call in which every row is so issues exactly
+ * the copies and launches of pplhip_sample_rows.  The reported logprob stays the full-vocabulary one: truncation does not renormalise it.
+ * A per-request parameter never fails the batch.  Validation, staging and the one synchronisation are pplhip_sample_rows'.
+ * Arrived without a version bump: a client tells a library that has it by the symbol pplhip_sample_rows2 (dlsym). */
+typedef struct pplhip_sample_rows2_args {
+    const float* temperatures;   /* the first eight fields: pplhip_sample_rows_args */
+    const int32_t* top_k;
+    const float* top_p;
+    const uint64_t* seeds;
+    const uint64_t* draws;
+    int32_t batch, vocab_size, batch_stride;
+    const float* min_p;          /* host [B] or NULL */
+    const float* typical_p;      /* host [B] or NULL */
+} pplhip_sample_rows2_args;
+PPLHIP_API int pplhip_sample_rows2(pplhip_ctx* ctx, const float* logits_device, const pplhip_sample_rows2_args* args,
+                                   int32_t* output_host, float* logprob_host);
+
 /* Top-N logprobs (DESIGN.md "numerics", top-N logprobs row): for every batch row b with n = num_logprobs[b] > 0 the first n tokens of the
  * ranking "x = logit * (1 / temperature) descending, ties by ascending token index" and logprob = x - logsumexp(x) over the whole
  * vocabulary, the number the samplers report for their token.  Entry 0 is the row's greedy token.  Entries j >= vocab_size are token -1,
@@ -679,6 +701,13 @@ PPLHIP_API int pplhip_op_sample(void* stream, const float* logits, const float* 
 PPLHIP_API int pplhip_op_sample_rows(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
                                      const uint64_t* seeds, const uint64_t* draws, const float* rnd, int32_t batch, int32_t vocab,
                                      int32_t stride, int32_t* out_tok, float* out_logprob);
+/* pplhip_op_sample_rows plus the two truncation arrays of pplhip_sample_rows2_args as DEVICE pointers [batch] (either may be NULL: off for
+ * every row), read back with top_k for the row list: a third launch for the rows with top_k != 1 and min_p or typical_p on, none when
+ * there is no such row -- the call then issues exactly the launches of pplhip_op_sample_rows. */
+PPLHIP_API int pplhip_op_sample_rows2(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
+                                      const float* min_p, const float* typical_p, const uint64_t* seeds, const uint64_t* draws,
+                                      const float* rnd, int32_t batch, int32_t vocab, int32_t stride, int32_t* out_tok,
+                                      float* out_logprob);
 /* the top-N logprobs kernel alone (csrc/k_logprobs.hip), for the tests: DEVICE pointers.  temperatures may be NULL; num_logprobs [batch] in
  * 0 .. PPLHIP_TOP_LOGPROBS_MAX (anything else: PPLHIP_INVALID_VALUE, nothing launched).  out_tok / out_logprob are [asked, 20], `asked` the
  * number of rows with num_logprobs > 0, in ascending batch row; row j's slots behind its n are not written.  The row list is made on the

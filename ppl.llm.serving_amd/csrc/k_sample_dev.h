@@ -160,9 +160,57 @@ __device__ __forceinline__ int radix_pass(int vocab, int shift, KeyFn key_live, 
     return bin;
 }
 
-// A block of ST_THREADS threads; t: the row's temperature, top_k / tp / rnd: its k, top_p and random number in [0, 1)
-__device__ __forceinline__ void sample_topk_topp_row(const float* __restrict__ row, float t, int top_k, float tp, float rnd, int vocab,
-                                                     int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
+// Inclusive scan of a[0 .. n2) in LDS, n2 <= TOPK_MAX a power of two, by a block of ST_THREADS threads (Hillis-Steele; every round reads
+// all its operands into registers, then a barrier, then adds: no second buffer needed).  The caller's barrier stands behind the writes of
+// `a`; the last round's barrier stands behind the scan.
+__device__ __forceinline__ void lds_scan_incl(float* a, int n2) {
+    const int tid = threadIdx.x;
+    for (int o = 1; o < n2; o <<= 1) {
+        float add[TOPK_MAX / 256];
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX / 256; ++j) {
+            const int i = tid + j * 256;
+            add[j] = (i < n2 && i >= o) ? a[i - o] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX / 256; ++j) {
+            const int i = tid + j * 256;
+            if (i < n2) a[i] += add[j];
+        }
+        __syncthreads();
+    }
+}
+
+// Bitonic sort of the n2 (a power of two <= TOPK_MAX) pairs (v[i], idx[i]) in LDS by a block of ST_THREADS threads; first(va, ia, vb, ib):
+// a ranks before b, a strict total order of the pairs.  The caller's barrier stands behind the writes, the last step's behind the sort.
+template <typename First>
+__device__ __forceinline__ void lds_bitonic_sort(float* v, int* idx, int n2, First first) {
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int str = size >> 1; str > 0; str >>= 1) {
+            for (int p = tid; p < (n2 >> 1); p += 256) {
+                const int lo = ((p / str) * str * 2) + (p % str), hi = lo + str;
+                const bool desc = ((lo & size) == 0);  // this sub-sequence ends up "best first"
+                const float va = v[lo], vb = v[hi];
+                const int ia = idx[lo], ib = idx[hi];
+                if (first(va, ia, vb, ib) != desc) { v[lo] = vb; v[hi] = va; idx[lo] = ib; idx[hi] = ia; }
+            }
+            __syncthreads();
+        }
+}
+
+// The body of sample_topk_topp_row (TRUNC false: min_p and typ are not read) and of sample_trunc_row (TRUNC true), which share the candidates,
+// their masses, the scan and the top-p cut.  Everything that sample_trunc_row adds stands under `if constexpr (TRUNC)`, so the other
+// instantiation is the function it was before the two were one: the same floating-point operations on the same operands in the same order
+// (the build has no fast-math and -ffp-contract=off, so the compiler may move them but not change them; the sort and the scan only moved
+// into lds_bitonic_sort / lds_scan_incl), hence the same token and logprob bits -- tests/test_gpu_sampler_exact.py and
+// tests/test_gpu_sample_rows.py hold it to that.
+// A block of ST_THREADS threads; t: the row's temperature, top_k / tp / rnd: its k, top_p and random number in [0, 1); min_p / typ: as
+// row_min_p / row_typical_p give them (0: off)
+template <bool TRUNC>
+__device__ __forceinline__ void sample_candidates_row(const float* __restrict__ row, float t, int top_k, float tp, float min_p, float typ,
+                                                      float rnd, int vocab, int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
     __shared__ float sf[4];
     __shared__ int wsum[4], sel[4], hist[256];
     __shared__ float cv[TOPK_MAX];   // candidate values x = logit / temperature
@@ -231,21 +279,10 @@ __device__ __forceinline__ void sample_topk_topp_row(const float* __restrict__ r
     __syncthreads();
     for (int i = k + tid; i < n2; i += 256) { cv[i] = -INFINITY; ci[i] = 0x7fffffff; }
     __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int str = size >> 1; str > 0; str >>= 1) {
-            for (int p = tid; p < (n2 >> 1); p += 256) {
-                const int lo = ((p / str) * str * 2) + (p % str), hi = lo + str;
-                const bool desc = ((lo & size) == 0);  // this sub-sequence ends up "best first"
-                const float va = cv[lo], vb = cv[hi];
-                const int ia = ci[lo], ib = ci[hi];
-                const bool a_first = va > vb || (va == vb && ia < ib);  // a ranks before b
-                if (a_first != desc) { cv[lo] = vb; cv[hi] = va; ci[lo] = ib; ci[hi] = ia; }
-            }
-            __syncthreads();
-        }
-    // masses exp(x - max) of the sorted candidates and their inclusive scan (Hillis-Steele over <= 1024 entries; every round reads
-    // all its operands into registers, then a barrier, then adds: no second buffer needed)
+    lds_bitonic_sort(cv, ci, n2, [](float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); });
+    // masses exp(x - max) of the sorted candidates and their inclusive scan
     float xv[TOPK_MAX / 256];
+    float ev[TRUNC ? TOPK_MAX / 256 : 1];   // sample_trunc_row keeps the masses too
 #pragma unroll
     for (int j = 0; j < TOPK_MAX / 256; ++j) {
         const int i = tid + j * 256;
@@ -260,25 +297,14 @@ __device__ __forceinline__ void sample_topk_topp_row(const float* __restrict__ r
             const float e = i < k ? expf(xv[j] - mx) : 0.f;
             cum[i] = e;
             with_mass += e > 0.f;
+            if constexpr (TRUNC) ev[j] = e;
+        } else if constexpr (TRUNC) {
+            ev[j] = 0.f;
         }
     }
     if (with_mass) atomicAdd(&sel[2], with_mass);
     __syncthreads();
-    for (int o = 1; o < n2; o <<= 1) {
-        float add[TOPK_MAX / 256];
-#pragma unroll
-        for (int j = 0; j < TOPK_MAX / 256; ++j) {
-            const int i = tid + j * 256;
-            add[j] = (i < n2 && i >= o) ? cum[i - o] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < TOPK_MAX / 256; ++j) {
-            const int i = tid + j * 256;
-            if (i < n2) cum[i] += add[j];
-        }
-        __syncthreads();
-    }
+    lds_scan_incl(cum, n2);
     // Candidates without mass (masked logits: -inf) sort last and are never the answer: the decisions below run over the km candidates that
     // carry mass.  (Every entry of the scan is summed in a tree of its own, so the sums are not monotone to the last bit: a massless entry
     // could exceed a target of rand ~ 1 that the last entry with mass just missed.)
@@ -293,21 +319,144 @@ __device__ __forceinline__ void sample_topk_topp_row(const float* __restrict__ r
         if (i < km && cum[i] / tot >= tp) atomicMin(&sel[0], i);
     }
     __syncthreads();
-    const int keep = sel[0] + 1;
-    const float target = rnd * cum[keep - 1];
+    int keep = sel[0] + 1;
+    int pick = -1;
+    if constexpr (TRUNC) {
+        // min_p: keep_m = the number of candidates with mass e >= min_p (e_0 = expf(0) = 1 exactly: "p >= min_p * p_max"; a prefix of the
+        // sorted list, at least one; min_p == 0 counts all km); keep = min(keep_p, keep_m)
+        if (tid == 0) sel[3] = 0;   // (the gather's counter, free since the gather)
+        __syncthreads();
+        int n_m = 0;
 #pragma unroll
-    for (int j = 0; j < TOPK_MAX / 256; ++j) {
-        const int i = tid + j * 256;
-        if (i < keep && cum[i] > target) atomicMin(&sel[1], i);
+        for (int j = 0; j < TOPK_MAX / 256; ++j) n_m += (tid + j * 256 < km && ev[j] >= min_p);
+        if (n_m) atomicAdd(&sel[3], n_m);
+        __syncthreads();
+        const int keep_m = sel[3] > 0 ? sel[3] : 1;
+        if (keep_m < keep) keep = keep_m;
+        if (typ > 0.f) {   // (uniform over the block)
+            // typical_p over the `keep` survivors, renormalised: q = e / S, lq = ln q, H = -sum q lq, s = |-lq - H|
+            __shared__ float sk[TOPK_MAX];   // the keys s, sorted ascending; then the scan of q in that order
+            __shared__ int sr[TOPK_MAX];     // the rank each key came from
+            const float S = cum[keep - 1];
+            const float lS = logf(S);
+            __syncthreads();                 // everybody has S: cum becomes q by rank
+            float lq[TOPK_MAX / 256];
+            float h = 0.f;                   // per thread its <= 4 terms in order, then the tree of wave_sum, then (w0 + w1) + (w2 + w3)
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                lq[j] = 0.f;
+                if (i < keep) {
+                    lq[j] = (xv[j] - mx) - lS;
+                    const float q = ev[j] / S;
+                    cum[i] = q;
+                    h += q * lq[j];
+                }
+            }
+            h = wave_sum(h);
+            if ((tid & 63) == 0) sf[tid >> 6] = h;
+            if (tid == 0) { sel[0] = keep - 1; sel[2] = -1; }   // (km and keep_p are in registers)
+            __syncthreads();
+            const float H = -((sf[0] + sf[1]) + (sf[2] + sf[3]));
+            int n2t = 1;
+            while (n2t < keep) n2t <<= 1;
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                if (i < n2t) {
+                    sk[i] = i < keep ? fabsf(-lq[j] - H) : INFINITY;
+                    sr[i] = i < keep ? i : 0x7fffffff;
+                }
+            }
+            __syncthreads();
+            lds_bitonic_sort(sk, sr, n2t, [](float va, int ia, float vb, int ib) { return va < vb || (va == vb && ia < ib); });
+            // cq = the scan of q in s order; n_t = 1 + first j with cq[j] >= typ (keep when none)
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                if (i < n2t) {   // (the first `keep` entries are the survivors, their keys being finite; the bound holds for a NaN row too)
+                    const int r = sr[i];
+                    sk[i] = (i < keep && (unsigned)r < (unsigned)keep) ? cum[r] : 0.f;
+                }
+            }
+            __syncthreads();
+            lds_scan_incl(sk, n2t);
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                if (i < keep && sk[i] >= typ) atomicMin(&sel[0], i);
+            }
+            __syncthreads();
+            const int n_t = sel[0] + 1;
+            // membership by rank, then the masses of the members in RANK order and their scan: the pick is a function of the set alone
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                if (i < n2t) cum[i] = 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                if (i < n_t) {
+                    const int r = sr[i];
+                    if ((unsigned)r < (unsigned)keep) cum[r] = 1.f;
+                }
+            }
+            __syncthreads();
+            bool member[TOPK_MAX / 256];
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                member[j] = i < keep && cum[i] != 0.f;
+                if (i < n2t) cum[i] = member[j] ? ev[j] : 0.f;
+            }
+            __syncthreads();
+            lds_scan_incl(cum, n2t);
+            const float target = rnd * cum[keep - 1];
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX / 256; ++j) {
+                const int i = tid + j * 256;
+                if (member[j]) {
+                    if (cum[i] > target) atomicMin(&sel[1], i);
+                    atomicMax(&sel[2], i);   // the last member: the answer when no sum exceeds the target
+                }
+            }
+            __syncthreads();
+            pick = sel[1] < keep ? sel[1] : (sel[2] > 0 ? sel[2] : 0);
+        }
     }
-    __syncthreads();
-    const int pick = sel[1] < keep ? sel[1] : keep - 1;
+    if (pick < 0) {
+        const float target = rnd * cum[keep - 1];
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX / 256; ++j) {
+            const int i = tid + j * 256;
+            if (i < keep && cum[i] > target) atomicMin(&sel[1], i);
+        }
+        __syncthreads();
+        pick = sel[1] < keep ? sel[1] : keep - 1;
+    }
 #pragma unroll
     for (int j = 0; j < TOPK_MAX / 256; ++j)
         if (tid + j * 256 == pick) {
             *out_tok = ci[pick];
             *out_lp = xv[j] - (mx + logf(se));
         }
+}
+
+__device__ __forceinline__ void sample_topk_topp_row(const float* __restrict__ row, float t, int top_k, float tp, float rnd, int vocab,
+                                                     int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
+    sample_candidates_row<false>(row, t, top_k, tp, 0.f, 0.f, rnd, vocab, out_tok, out_lp);
+}
+
+// min_p / typical_p truncation (DESIGN.md "numerics", min_p / typical_p row): the candidates, masses, scan and top-p cut of
+// sample_topk_topp_row; then keep = min(keep_p, #{e >= min_p}); then, with typical_p on, the survivors renormalised and ordered by
+// |-ln q - H| (ties by rank), cut where their mass reaches typical_p, and the pick over the members in rank order.  The logprob is the
+// full-vocabulary one of the other row functions.  Every loop runs to k, km, keep, n2 or n2t <= TOPK_MAX.  A block of ST_THREADS threads;
+// LDS: the three 4 KiB arrays of sample_topk_topp_row and two more.
+__device__ __forceinline__ void sample_trunc_row(const float* __restrict__ row, float t, int top_k, float tp, float min_p, float typ, float rnd,
+                                                 int vocab, int32_t* __restrict__ out_tok, float* __restrict__ out_lp) {
+    sample_candidates_row<true>(row, t, top_k, tp, row_min_p(min_p), row_typical_p(typ), rnd, vocab, out_tok, out_lp);
 }
 
 // top-N logprobs (DESIGN.md "numerics", top-N logprobs row): the first n entries of the ranking "x = logits / temperature descending, ties

@@ -3,8 +3,10 @@
 // two row functions K13 instantiates -- so a row's token and logprob bits equal those of sample_greedy_kernel / sample_topk_topp_kernel
 // launched on that row with the row's parameters.
 //
-// Form taken: TWO launches over a host-compacted row list, greedy rows (top_k == 1) at SG_THREADS = 1024 threads, all other rows at
-// ST_THREADS = 256; a launch with no rows is not issued, so an all-greedy and an all-sampling batch cost exactly one launch.  Why not one
+// Form taken: up to THREE launches over a host-compacted row list, greedy rows (top_k == 1) at SG_THREADS = 1024 threads, the other rows
+// at ST_THREADS = 256, the ones that ask for a min_p or typical_p cut (sample_trunc_row) apart from the ones that do not; a launch with no
+// rows is not issued, so an all-greedy and an all-sampling batch cost exactly one launch and a batch in which nobody asks for a cut takes
+// the launches it took before the third kind existed.  Why not one
 // launch whose blocks branch per row: the two row functions are written for different block widths (the width fixes the summation order,
 // i.e. the logprob bits), so a common block would have to be 1024 threads wide with 768 of them idle through every barrier of a sampling
 // row, and the kernel would carry the larger register and LDS footprint of the two for every row.  With the list each kind keeps exactly
@@ -67,9 +69,24 @@ __global__ __launch_bounds__(ST_THREADS) void sample_rows_topk_topp_kernel(const
                          out_lp + b);
 }
 
+// the truncating rows (min_p or typical_p on): min_p / typical_p may be NULL (off for every row)
+__global__ __launch_bounds__(ST_THREADS) void sample_rows_trunc_kernel(const float* __restrict__ logits, const float* __restrict__ temperatures,
+                                                                       const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                                       const float* __restrict__ min_p, const float* __restrict__ typical_p,
+                                                                       const uint64_t* __restrict__ seeds, const uint64_t* __restrict__ draws,
+                                                                       const float* __restrict__ rnd, const int32_t* __restrict__ rows,
+                                                                       int vocab, int stride, int32_t* __restrict__ out_tok,
+                                                                       float* __restrict__ out_lp) {
+    const int b = rows[blockIdx.x];
+    const float u = rnd ? rnd[b] : philox_uniform(seeds[b], draws[b]);
+    sample_trunc_row(logits + (int64_t)b * stride, row_temperature(temperatures, b), top_k[b], top_p[b], min_p ? min_p[b] : 0.f,
+                     typical_p ? typical_p[b] : 0.f, u, vocab, out_tok + b, out_lp + b);
+}
+
 hipError_t launch_sample_rows(hipStream_t s, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
                               const uint64_t* seeds, const uint64_t* draws, const float* rnd, const int32_t* rows, int n_greedy,
-                              int n_sampling, int vocab, int stride, int32_t* out_tok, float* out_logprob) {
+                              int n_sampling, int vocab, int stride, int32_t* out_tok, float* out_logprob, const float* min_p,
+                              const float* typical_p, int n_trunc) {
     if (n_greedy > 0) {
         hipLaunchKernelGGL(sample_rows_greedy_kernel, dim3(n_greedy), dim3(SG_THREADS), 0, s, logits, temperatures, rows, vocab, stride,
                            out_tok, out_logprob);
@@ -78,6 +95,11 @@ hipError_t launch_sample_rows(hipStream_t s, const float* logits, const float* t
     if (n_sampling > 0) {
         hipLaunchKernelGGL(sample_rows_topk_topp_kernel, dim3(n_sampling), dim3(ST_THREADS), 0, s, logits, temperatures, top_k, top_p, seeds,
                            draws, rnd, rows + n_greedy, vocab, stride, out_tok, out_logprob);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (n_trunc > 0) {
+        hipLaunchKernelGGL(sample_rows_trunc_kernel, dim3(n_trunc), dim3(ST_THREADS), 0, s, logits, temperatures, top_k, top_p, min_p, typical_p,
+                           seeds, draws, rnd, rows + n_greedy + n_sampling, vocab, stride, out_tok, out_logprob);
         if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;

@@ -262,9 +262,17 @@ hipError_t launch_penalty(hipStream_t s, float* logits, const float* temperature
 // ---- k_sample_rows.hip: the per-request sampler ---------------------------------------------------
 // rows: device list of batch rows, the n_greedy rows with top_k == 1 first, then the n_sampling others; every other array is indexed by
 // the batch row.  temperatures may be NULL; rnd != NULL replaces u(seeds, draws).  One launch per non-empty kind.
+// Behind the n_sampling rows the list holds the n_trunc truncating rows (top_k != 1 with min_p or typical_p on, row_min_p / row_typical_p below); min_p /
+// typical_p may be NULL (off for every row).
 hipError_t launch_sample_rows(hipStream_t s, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
                               const uint64_t* seeds, const uint64_t* draws, const float* rnd, const int32_t* rows, int n_greedy,
-                              int n_sampling, int vocab, int stride, int32_t* out_tok, float* out_logprob);
+                              int n_sampling, int vocab, int stride, int32_t* out_tok, float* out_logprob, const float* min_p = nullptr,
+                              const float* typical_p = nullptr, int n_trunc = 0);
+// The defaults of the two truncations, one rule for the host's row list and the kernel: min_p is off (0) when it is <= 0 or NaN and counts
+// as 1 above 1; typical_p is off (0) when it is <= 0, >= 1 or NaN.  A row with top_k == 1 is greedy whatever else it carries; a row with
+// both off is a sampling row (sample_topk_topp_row answers it); every other row is a truncating row (sample_trunc_row).
+__host__ __device__ inline float row_min_p(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }
+__host__ __device__ inline float row_typical_p(float v) { return (v > 0.f && v < 1.f) ? v : 0.f; }
 // out_u[b] = u(seeds[b], draws[b]): Philox4x32-10, word 0, 24 bits
 hipError_t launch_sample_uniform(hipStream_t s, const uint64_t* seeds, const uint64_t* draws, int batch, float* out_u);
 

@@ -153,15 +153,19 @@ template <class Block> size_t block_bytes(int64_t n) { return (size_t)Block(null
 
 static_assert(PPLHIP_TOP_LOGPROBS_MAX == TOP_LOGPROBS_MAX, "header and kernel disagree");
 
-// pplhip_sample_rows: one step's per-row arrays, for capacity cap_B; the copy ends behind the rows of the list that are in use
+// pplhip_sample_rows / pplhip_sample_rows2: one step's per-row arrays, for capacity cap_B; the copy ends behind the rows of the list that
+// are in use.  min_p / typical_p stand behind the list, so a call without a truncating row copies exactly the bytes it copied before
+// the two columns existed; a call with one copies them too (the list in full, cap_B entries)
 struct SampleRowsBlock : Packed {
     uint64_t *seeds, *draws;
     float *temperatures, *top_p;
     int32_t *top_k, *rows;
+    float *min_p, *typical_p;
     SampleRowsBlock(void* b, int64_t cap) : Packed(b) {
         seeds = col<uint64_t>(cap); draws = col<uint64_t>(cap);
         temperatures = col<float>(cap); top_p = col<float>(cap);
         top_k = col<int32_t>(cap); rows = col<int32_t>(cap);
+        min_p = col<float>(cap); typical_p = col<float>(cap);
     }
 };
 // pplhip_top_logprobs, going up (a block of its own: the step's sampler call restages the sampler's while this one's copy may still be in
@@ -454,6 +458,6 @@ int p2p_next_epoch(pplhip_ctx* c, int rank, Channel& ch, hipStream_t s, uint32_t
 // rt_lora.cc
 void lora_build_tiles(const int32_t* row_slots, int64_t T, std::vector<LoraTile>& out);
 // rt_postproc.cc
-int sample_row_list(const int32_t* top_k, int B, int32_t* rows);
+int sample_row_list(const int32_t* top_k, const float* min_p, const float* typical_p, int B, int32_t* rows, int* n_trunc);
 int top_logprobs_row_list(const int32_t* num_logprobs, int B, int32_t* rows);
 int run_prompt_logprobs(pplhip_ctx* c, int rank, hipStream_t s, const uint16_t* pending, const SplitSlabs& sl_part2);

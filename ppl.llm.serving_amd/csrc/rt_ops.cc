@@ -192,21 +192,34 @@ int pplhip_op_sample(void* stream, const float* logits, const float* temperature
 int pplhip_op_sample_rows(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
                           const uint64_t* seeds, const uint64_t* draws, const float* rnd, int32_t batch, int32_t vocab, int32_t stride,
                           int32_t* out_tok, float* out_logprob) {
+    return pplhip_op_sample_rows2(stream, logits, temperatures, top_k, top_p, nullptr, nullptr, seeds, draws, rnd, batch, vocab, stride, out_tok,
+                                  out_logprob);
+}
+
+// ... with the two truncation arrays (either may be NULL), read back like top_k for the third kind of the row list
+int pplhip_op_sample_rows2(void* stream, const float* logits, const float* temperatures, const int32_t* top_k, const float* top_p,
+                           const float* min_p, const float* typical_p, const uint64_t* seeds, const uint64_t* draws, const float* rnd,
+                           int32_t batch, int32_t vocab, int32_t stride, int32_t* out_tok, float* out_logprob) {
     if (batch < 0 || vocab <= 0 || stride < vocab) return PPLHIP_INVALID_VALUE;
     if (batch == 0) return 0;
     if (!logits || !top_k || !top_p || !out_tok || !out_logprob || (!rnd && (!seeds || !draws))) return PPLHIP_INVALID_VALUE;
     hipStream_t s = (hipStream_t)stream;
     std::vector<int32_t> k(batch), rows(batch);
+    std::vector<float> mp(min_p ? batch : 0), ty(typical_p ? batch : 0);
     hipError_t e = hipMemcpyAsync(k.data(), top_k, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && min_p) e = hipMemcpyAsync(mp.data(), min_p, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && typical_p) e = hipMemcpyAsync(ty.data(), typical_p, (size_t)batch * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return op_rc(e);
-    const int ng = sample_row_list(k.data(), batch, rows.data());
+    int nt = 0;
+    const int ng = sample_row_list(k.data(), min_p ? mp.data() : nullptr, typical_p ? ty.data() : nullptr, batch, rows.data(), &nt);
     int32_t* d_rows = nullptr;
     if ((e = hipMallocAsync((void**)&d_rows, (size_t)batch * 4, s)) != hipSuccess) return op_rc(e);
     e = hipMemcpyAsync(d_rows, rows.data(), (size_t)batch * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable and dies with this call; the stream was idle anyway
     if (e == hipSuccess)
-        e = launch_sample_rows(s, logits, temperatures, top_k, top_p, seeds, draws, rnd, d_rows, ng, batch - ng, vocab, stride, out_tok, out_logprob);
+        e = launch_sample_rows(s, logits, temperatures, top_k, top_p, seeds, draws, rnd, d_rows, ng, batch - ng - nt, vocab, stride, out_tok, out_logprob,
+                               min_p, typical_p, nt);
     const hipError_t e2 = hipFreeAsync(d_rows, s);
     return op_rc(e != hipSuccess ? e : e2);
 }

@@ -71,19 +71,34 @@ int pplhip_sample(pplhip_ctx* c, const float* logits_device, const pplhip_sample
     return p2p_check(c, 0);
 }
 
-// greedy rows (top_k == 1) first, then the others, each kind in batch order; returns the number of greedy rows
-int sample_row_list(const int32_t* top_k, int B, int32_t* rows) {
+// greedy rows (top_k == 1) first, then the sampling rows, then the truncating rows (min_p or typical_p on: kernels.h row_min_p /
+// row_typical_p; either array may be NULL), each kind in batch order; returns the number of greedy rows, *n_trunc the truncating ones
+int sample_row_list(const int32_t* top_k, const float* min_p, const float* typical_p, int B, int32_t* rows, int* n_trunc) {
+    const auto trunc = [&](int i) {
+        return (min_p && row_min_p(min_p[i]) > 0.f) || (typical_p && row_typical_p(typical_p[i]) > 0.f);
+    };
     int ng = 0;
     for (int i = 0; i < B; ++i)
         if (top_k[i] == 1) rows[ng++] = i;
     int n = ng;
     for (int i = 0; i < B; ++i)
-        if (top_k[i] != 1) rows[n++] = i;
+        if (top_k[i] != 1 && !trunc(i)) rows[n++] = i;
+    *n_trunc = B - n;
+    for (int i = 0; i < B; ++i)
+        if (top_k[i] != 1 && trunc(i)) rows[n++] = i;
     return ng;
 }
 
 int pplhip_sample_rows(pplhip_ctx* c, const float* logits_device, const pplhip_sample_rows_args* a, int32_t* output_host,
                        float* logprob_host) {
+    if (!a) return PPLHIP_INVALID_VALUE;
+    const pplhip_sample_rows2_args a2{a->temperatures, a->top_k, a->top_p, a->seeds, a->draws, a->batch, a->vocab_size, a->batch_stride,
+                                      nullptr, nullptr};
+    return pplhip_sample_rows2(c, logits_device, &a2, output_host, logprob_host);
+}
+
+int pplhip_sample_rows2(pplhip_ctx* c, const float* logits_device, const pplhip_sample_rows2_args* a, int32_t* output_host,
+                        float* logprob_host) {
     if (!c || !a || !logits_device || !output_host || !logprob_host) return PPLHIP_INVALID_VALUE;
     if (!a->top_k || !a->top_p || !a->seeds || !a->draws) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[0];
@@ -98,12 +113,17 @@ int pplhip_sample_rows(pplhip_ctx* c, const float* logits_device, const pplhip_s
     if (a->temperatures) memcpy(h.temperatures, a->temperatures, (size_t)B * 4);
     memcpy(h.top_p, a->top_p, (size_t)B * 4);
     memcpy(h.top_k, a->top_k, (size_t)B * 4);
-    const int ng = sample_row_list(a->top_k, B, h.rows);
+    int nt = 0;
+    const int ng = sample_row_list(a->top_k, a->min_p, a->typical_p, B, h.rows, &nt);
+    // without a truncating row: the copy and the launches of a call that carries neither array
+    if (nt > 0 && a->min_p) memcpy(h.min_p, a->min_p, (size_t)B * 4);
+    if (nt > 0 && a->typical_p) memcpy(h.typical_p, a->typical_p, (size_t)B * 4);
     HIPCK(c, 0, hipSetDevice(R.device));
     hipStream_t s = R.stream;
-    HIPCK(c, 0, hipMemcpyAsync(R.d_srows, R.h_srows, h.upto(h.rows + B), hipMemcpyHostToDevice, s));
+    HIPCK(c, 0, hipMemcpyAsync(R.d_srows, R.h_srows, nt > 0 ? h.upto(h.typical_p + B) : h.upto(h.rows + B), hipMemcpyHostToDevice, s));
     HIPCK(c, 0, launch_sample_rows(s, logits_device, a->temperatures ? d.temperatures : nullptr, d.top_k, d.top_p, d.seeds, d.draws, nullptr,
-                                   d.rows, ng, B - ng, a->vocab_size, a->batch_stride, R.d_tokout, R.d_lp));
+                                   d.rows, ng, B - ng - nt, a->vocab_size, a->batch_stride, R.d_tokout, R.d_lp,
+                                   a->min_p ? d.min_p : nullptr, a->typical_p ? d.typical_p : nullptr, nt));
     HIPCK(c, 0, hipMemcpyAsync(output_host, R.d_tokout, B * 4, hipMemcpyDeviceToHost, s));
     HIPCK(c, 0, hipMemcpyAsync(logprob_host, R.d_lp, B * 4, hipMemcpyDeviceToHost, s));
     HIPCK(c, 0, hipStreamSynchronize(s));  // the one synchronisation, as in pplhip_sample

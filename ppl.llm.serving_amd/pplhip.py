@@ -67,6 +67,10 @@ class SampleRowsArgs(C.Structure):
                 ("batch", C.c_int32), ("vocab_size", C.c_int32), ("batch_stride", C.c_int32)]
 
 
+class SampleRows2Args(C.Structure):
+    _fields_ = SampleRowsArgs._fields_ + [("min_p", C.c_void_p), ("typical_p", C.c_void_p)]
+
+
 TOP_LOGPROBS_MAX = 20   # PPLHIP_TOP_LOGPROBS_MAX
 
 
@@ -179,10 +183,10 @@ SYMBOLS = [
     "pplhip_kv_write", "pplhip_kv_fill_synthetic",
     "pplhip_lora_set_tensor", "pplhip_lora_commit", "pplhip_lora_load", "pplhip_lora_unload", "pplhip_set_adapters", "pplhip_op_lora",
     "pplhip_set_inputs", "pplhip_set_prompt_logprobs", "pplhip_prompt_logprobs", "pplhip_run", "pplhip_debug_run_dump", "pplhip_logits", "pplhip_copy_logits", "pplhip_sync",
-    "pplhip_sample", "pplhip_sample_rows", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_guide_set_vocab", "pplhip_guide_load", "pplhip_guide_unload", "pplhip_guide_edit", "pplhip_guide_load16", "pplhip_guide16_state_chunk", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
+    "pplhip_sample", "pplhip_sample_rows", "pplhip_sample_rows2", "pplhip_top_logprobs", "pplhip_logit_rule_set", "pplhip_logit_edit", "pplhip_guide_set_vocab", "pplhip_guide_load", "pplhip_guide_unload", "pplhip_guide_edit", "pplhip_guide_load16", "pplhip_guide16_state_chunk", "pplhip_penalty", "pplhip_profile_reset", "pplhip_profile_get", "pplhip_profile_mode", "pplhip_mem_info",
     "pplhip_op_embedding", "pplhip_op_rmsnorm", "pplhip_op_linear", "pplhip_op_linear_swiglu", "pplhip_op_linear_ex", "pplhip_op_linear_q8_ex", "pplhip_op_step_plan", "pplhip_op_rmsnorm_quant", "pplhip_op_quant_act", "pplhip_op_quant_weight",
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
-    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_guide_build16", "pplhip_op_guide_mask16", "pplhip_op_rope_kv_write",
+    "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_rows2", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_guide_build16", "pplhip_op_guide_mask16", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -269,6 +273,9 @@ def lib():
         if hasattr(L, "pplhip_sample_rows"):
             L.pplhip_sample_rows.argtypes = [vp, vp, C.POINTER(SampleRowsArgs), vp, vp]
             L.pplhip_op_sample_rows.argtypes = [vp] * 8 + [i32, i32, i32, vp, vp]
+        if hasattr(L, "pplhip_sample_rows2"):
+            L.pplhip_sample_rows2.argtypes = [vp, vp, C.POINTER(SampleRows2Args), vp, vp]
+            L.pplhip_op_sample_rows2.argtypes = [vp] * 10 + [i32, i32, i32, vp, vp]
             L.pplhip_op_sample_uniform.argtypes = [vp, vp, vp, i32, vp]
         if hasattr(L, "pplhip_top_logprobs"):
             L.pplhip_top_logprobs.argtypes = [vp, vp, C.POINTER(TopLogprobsArgs), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
@@ -723,6 +730,27 @@ class Context:
         if logits_ptr is None:
             logits_ptr = self.logits_ptr(0)[0]
         self._ck(lib().pplhip_sample_rows(self.h, logits_ptr, C.byref(a), tok.ctypes.data, lp.ctypes.data), 0, "sample_rows")
+        return tok, lp
+
+    def sample_rows2(self, top_k, top_p, seeds, draws, min_p=None, typical_p=None, temperatures=None, logits_ptr=None):
+        """sample_rows with a min_p and a typical_p per batch row (None: off for every row)"""
+        a = SampleRows2Args()
+        k = np.ascontiguousarray(top_k, dtype=np.int32)
+        p = np.ascontiguousarray(top_p, dtype=np.float32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        dr = np.ascontiguousarray(draws, dtype=np.uint64)
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float32)
+        t, mp, ty = f32(temperatures), f32(min_p), f32(typical_p)
+        batch = len(k)
+        assert len(p) == len(sd) == len(dr) == batch and all(v is None or len(v) == batch for v in (t, mp, ty))
+        a.top_k, a.top_p, a.seeds, a.draws = k.ctypes.data, p.ctypes.data, sd.ctypes.data, dr.ctypes.data
+        a.temperatures, a.min_p, a.typical_p = (None if v is None else v.ctypes.data for v in (t, mp, ty))
+        a.batch, a.vocab_size, a.batch_stride = batch, self.desc.vocab_size, self.desc.vocab_size
+        tok = np.empty(batch, dtype=np.int32)
+        lp = np.empty(batch, dtype=np.float32)
+        if logits_ptr is None:
+            logits_ptr = self.logits_ptr(0)[0]
+        self._ck(lib().pplhip_sample_rows2(self.h, logits_ptr, C.byref(a), tok.ctypes.data, lp.ctypes.data), 0, "sample_rows2")
         return tok, lp
 
     def top_logprobs(self, num_logprobs, temperatures=None, logits_ptr=None):

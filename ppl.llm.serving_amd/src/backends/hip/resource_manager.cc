@@ -107,6 +107,28 @@ RetCode HipPostProcessor::SampleRows(const float* logits_device, const float* te
     return FromPplHipStatus(st);
 }
 
+RetCode HipPostProcessor::SampleRowsTrunc(const float* logits_device, const float* temperatures_host, const int32_t* top_k_host,
+                                          const float* top_p_host, const float* min_p_host, const float* typical_p_host,
+                                          const uint64_t* seeds_host, const uint64_t* draws_host, int32_t batch, int32_t vocab_size,
+                                          int32_t batch_stride, int32_t* output_host, float* logprob_host) {
+    if (batch == 0) return RC_SUCCESS;
+    pplhip_sample_rows2_args a;
+    memset(&a, 0, sizeof(a));
+    a.temperatures = temperatures_host;
+    a.top_k = top_k_host;
+    a.top_p = top_p_host;
+    a.seeds = seeds_host;
+    a.draws = draws_host;
+    a.batch = batch;
+    a.vocab_size = vocab_size;
+    a.batch_stride = batch_stride;
+    a.min_p = min_p_host;
+    a.typical_p = typical_p_host;
+    const int st = pplhip_sample_rows2(ctx_, logits_device, &a, output_host, logprob_host);
+    if (st) LOG(ERROR) << "per-request sampling with min_p / typical_p failed: " << pplhip_last_error(ctx_, 0);
+    return FromPplHipStatus(st);
+}
+
 static_assert(PostProcessor::kTopLogprobsMax == PPLHIP_TOP_LOGPROBS_MAX, "interface and library disagree");
 
 RetCode HipPostProcessor::TopLogprobs(const float* logits_device, const float* temperatures_host, const int32_t* num_logprobs_host,

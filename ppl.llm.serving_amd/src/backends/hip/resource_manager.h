@@ -42,6 +42,10 @@ public:
                                       const int64_t* batch_slots_host, const int64_t* token_inputs, const int64_t* seqstarts,
                                       const int64_t* start_pos, int32_t batch, int32_t vocab_size, bool req_list_changed,
                                       float* logits) override;
+    ppl::common::RetCode SampleRowsTrunc(const float* logits_device, const float* temperatures_host, const int32_t* top_k_host,
+                                         const float* top_p_host, const float* min_p_host, const float* typical_p_host,
+                                         const uint64_t* seeds_host, const uint64_t* draws_host, int32_t batch, int32_t vocab_size,
+                                         int32_t batch_stride, int32_t* output_host, float* logprob_host) override;
     ppl::common::RetCode SampleRows(const float* logits_device, const float* temperatures_host, const int32_t* top_k_host,
                                     const float* top_p_host, const uint64_t* seeds_host, const uint64_t* draws_host, int32_t batch,
                                     int32_t vocab_size, int32_t batch_stride, int32_t* output_host, float* logprob_host) override;

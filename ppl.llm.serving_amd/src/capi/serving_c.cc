@@ -243,6 +243,12 @@ int pplsrv_submit_guided(pplsrv* s, const pplsrv_request* reqs, const int32_t* s
 int pplsrv_submit_guided_json(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
                               const pplsrv_rule* const* rules, const int32_t* prompt_logprobs, const char* const* guide_regex,
                               const char* const* guide_json_schema, int32_t n) {
+    return pplsrv_submit_sampling(s, reqs, slots, seeds, num_logprobs, rules, prompt_logprobs, guide_regex, guide_json_schema, nullptr, nullptr, n);
+}
+
+int pplsrv_submit_sampling(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds, const int32_t* num_logprobs,
+                           const pplsrv_rule* const* rules, const int32_t* prompt_logprobs, const char* const* guide_regex,
+                           const char* const* guide_json_schema, const float* min_p, const float* typical_p, int32_t n) {
     if (!s || (n > 0 && !reqs)) return -(int)ppl::common::RC_INVALID_VALUE;
     for (int i = 0; i < n; ++i) {
         const pplsrv_request& q = reqs[i];
@@ -251,6 +257,8 @@ int pplsrv_submit_guided_json(pplsrv* s, const pplsrv_request* reqs, const int32
         r->temperature = q.temperature;
         r->top_p = q.top_p;
         r->top_k = q.top_k;
+        if (min_p) r->min_p = min_p[i];
+        if (typical_p) r->typical_p = typical_p[i];
         r->repetition_penalty = q.repetition_penalty;
         r->presence_penalty = q.presence_penalty;
         r->frequency_penalty = q.frequency_penalty;

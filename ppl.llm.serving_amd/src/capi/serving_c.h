@@ -156,6 +156,14 @@ PPLSRV_API int pplsrv_submit_guided(pplsrv* s, const pplsrv_request* reqs, const
 PPLSRV_API int pplsrv_submit_guided_json(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
                                          const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs,
                                          const char* const* guide_regex, const char* const* guide_json_schema, int32_t n);
+/* min_p / typical_p (DESIGN.md "numerics", min_p / typical_p row).  pplsrv_submit_sampling is pplsrv_submit_guided_json with
+ * min_p[i] = Request::min_p and typical_p[i] = Request::typical_p of reqs[i]; either array NULL: nobody asks (min_p 0, typical_p 1).
+ * min_p is off when <= 0 or NaN, typical_p when <= 0, >= 1 or NaN.  A request that turns one on on a server created without
+ * per_request_sampling, or over a backend without the truncating sampler, fails alone (PPLSRV_FAILED).  pplsrv_request keeps its layout. */
+PPLSRV_API int pplsrv_submit_sampling(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, const uint64_t* seeds,
+                                      const int32_t* num_logprobs, const pplsrv_rule* const* rules, const int32_t* prompt_logprobs,
+                                      const char* const* guide_regex, const char* const* guide_json_schema, const float* min_p,
+                                      const float* typical_p, int32_t n);
 /* waits up to timeout_ms for at least one response, then returns up to `max` of them (0 on timeout) */
 PPLSRV_API int pplsrv_poll(pplsrv* s, pplsrv_response* out, int32_t max, int32_t timeout_ms);
 /* the same, plus the generated text of text requests (what DecodeAndSendTask, llm_generator.cc:58-112, put into Response::generated:

@@ -41,6 +41,23 @@ public:
                                             float* /*logprob_host*/) {
         return ppl::common::RC_UNSUPPORTED;
     }
+    // SampleRows with two more truncations per row (DESIGN.md "numerics", min_p / typical_p row): min_p_host[b] keeps the candidates whose
+    // probability is at least min_p times the most probable one's (off when <= 0 or NaN), typical_p_host[b] is locally typical sampling
+    // over what is left (off when <= 0, >= 1 or NaN).  The engine calls it only on steps in which a row has one of the two on
+    // (RowTruncates), SampleRows on every other step.  batch == 0 touches nothing and only tells whether the backend can do it (the
+    // generator asks so when a request that sets either is admitted); a backend that cannot keeps this default, and the requests that
+    // ask are failed.
+    virtual ppl::common::RetCode SampleRowsTrunc(const float* /*logits_device*/, const float* /*temperatures_host*/,
+                                                 const int32_t* /*top_k_host*/, const float* /*top_p_host*/, const float* /*min_p_host*/,
+                                                 const float* /*typical_p_host*/, const uint64_t* /*seeds_host*/,
+                                                 const uint64_t* /*draws_host*/, int32_t /*batch*/, int32_t /*vocab_size*/,
+                                                 int32_t /*batch_stride*/, int32_t* /*output_host*/, float* /*logprob_host*/) {
+        return ppl::common::RC_UNSUPPORTED;
+    }
+    // whether a row with these parameters is a truncating row: not greedy, and min_p or typical_p on
+    static bool RowTruncates(int32_t top_k, float min_p, float typical_p) {
+        return top_k != 1 && (min_p > 0.f || (typical_p > 0.f && typical_p < 1.f));
+    }
     // Top-N logprobs of the rows with num_logprobs_host[b] > 0 (0 .. kTopLogprobsMax), on the logits the step's sampler is about to see.
     // NOT blocking: *tokens / *logprobs point at backend-owned host memory, [*rows, kTopLogprobsMax] each, row j = the j-th asking batch
     // row, valid once the step's sampler call (SampleTopKTopP / SampleRows) has returned and until the next TopLogprobs.  Entries behind

@@ -164,7 +164,20 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
                 return Fail(error_msg, "TopLogprobs", rc);
             }
         }
-        if (per_request_sampling_) {
+        const char* sampler = per_request_sampling_ ? "SampleRows" : "SampleTopKTopP";
+        // (a ModelInput packed without the two lists asks for nothing)
+        const bool has_trunc_lists = in.min_p_list.size() == (size_t)running_batch && in.typical_p_list.size() == (size_t)running_batch;
+        bool truncates = false;
+        for (int32_t b = 0; b < running_batch && per_request_sampling_ && has_trunc_lists && !truncates; ++b)
+            truncates = PostProcessor::RowTruncates(in.top_k_list[b], in.min_p_list[b], in.typical_p_list[b]);
+        if (truncates) {
+            // a row of the step cuts its tail by min_p or typical_p: the sampler that knows the two; every other step takes today's call
+            sampler = "SampleRowsTrunc";
+            rc = post_processor_->SampleRowsTrunc(logits, enable_penalty_ ? nullptr : in.temperatures.data(), in.top_k_list.data(),
+                                                  in.top_p_list.data(), in.min_p_list.data(), in.typical_p_list.data(), in.seed_list.data(),
+                                                  in.draw_list.data(), running_batch, model_config_.vocab_size, (int32_t)stride,
+                                                  out->output_token.data(), out->logprobs.data());
+        } else if (per_request_sampling_) {
             // every row its own parameters and random number (the penalty step has applied the temperatures already)
             rc = post_processor_->SampleRows(logits, enable_penalty_ ? nullptr : in.temperatures.data(), in.top_k_list.data(),
                                              in.top_p_list.data(), in.seed_list.data(), in.draw_list.data(), running_batch,
@@ -177,7 +190,7 @@ RetCode LLMEngine::Execute(const ModelInput& in, bool req_list_changed, bool is_
                                                  req_list_changed, out->output_token.data(), out->logprobs.data(),
                                                  enable_penalty_);
         }
-        if (rc != RC_SUCCESS) return Fail(error_msg, per_request_sampling_ ? "SampleRows" : "SampleTopKTopP", rc);
+        if (rc != RC_SUCCESS) return Fail(error_msg, sampler, rc);
         if (prompt_asks) {   // the sampler has synchronised: the step's prompt logprobs are readable
             PromptLogprobsView v;
             rc = rt0->GetPromptLogprobs(&v);

@@ -28,6 +28,8 @@ struct ModelInput {
     std::vector<int64_t> kv_starts;
     std::vector<float> temperatures;
     std::vector<float> top_p_list;
+    std::vector<float> min_p_list;      // Request::min_p per request (<= 0 or NaN: off)
+    std::vector<float> typical_p_list;  // Request::typical_p per request (<= 0, >= 1 or NaN: off)
     std::vector<int32_t> top_k_list;
     std::vector<uint64_t> seed_list;  // sampling seed per request (per_request_sampling)
     std::vector<uint64_t> draw_list;  // tokens the request has produced so far: 0 on the step that ends its prefill
@@ -95,6 +97,13 @@ public:
                                                               model_config_.vocab_size) == ppl::common::RC_SUCCESS;
     }
     ppl::common::RetCode SetLogitRule(int64_t slot, const LogitRule& rule) { auto lock = DeviceLock(); return post_processor_->SetLogitRule(slot, rule); }
+
+    // min_p / typical_p: whether the backend's post processor has the truncating sampler (PostProcessor::SampleRowsTrunc with batch 0)
+    bool HasSampleRowsTrunc() const {
+        return post_processor_ && post_processor_->SampleRowsTrunc(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                                                                   model_config_.vocab_size, model_config_.vocab_size, nullptr,
+                                                                   nullptr) == ppl::common::RC_SUCCESS;
+    }
 
     // guided decoding: whether the backend's post processor has it (PostProcessor::GuideEdit with batch 0), and its three set-up calls
     bool HasGuides() const {

@@ -345,6 +345,12 @@ bool LLMGenerator::AdmitRequest(const LlmRequest& req, Admission* adm, int32_t* 
     const bool guided = !r.guide_regex.empty() || !r.guide_json_schema.empty();
     const std::string excluded = guided ? GuideExclusion(r) : "";
     if (!excluded.empty()) return adm->Reject(r.id, excluded);
+    if (r.AsksTruncation()) {  // min_p / typical_p: a request that cannot be served as it asks fails alone (StartRequest)
+        if (!generator_config_.per_request_sampling)
+            return adm->Reject(r.id, "min_p / typical_p: need per_request_sampling", RC_UNSUPPORTED);
+        if (!llm_engine_.HasSampleRowsTrunc())
+            return adm->Reject(r.id, "min_p / typical_p: the backend's post processor has no SampleRowsTrunc", RC_UNSUPPORTED);
+    }
     if (r.HasLogitRule()) {  // validated once, here; an invalid rule fails its request alone (StartRequest)
         if (!llm_engine_.HasLogitRules())
             return adm->Reject(r.id, "logit rules: the backend's post processor has no EditLogits", RC_UNSUPPORTED);
@@ -400,6 +406,8 @@ bool LLMGenerator::StartRequest(const LlmRequest& req, const Admission& adm) {
     t.temperature = r.temperature;
     t.top_p = r.top_p;
     t.top_k = r.top_k;
+    t.min_p = r.min_p;
+    t.typical_p = r.typical_p;
     t.repetition_penalty = r.repetition_penalty;
     t.presence_penalty = r.presence_penalty;
     t.frequency_penalty = r.frequency_penalty;
@@ -475,7 +483,7 @@ void LLMGenerator::PackStep(bool req_list_changed, ModelInput* in) const {
     in->seq_starts.reserve(n + 1);
     in->kv_starts.reserve(n + 1);
     in->start_pos.clear(); in->cache_indices.clear(); in->batch_slots.clear(); in->lora_slots.clear();
-    in->temperatures.clear(); in->top_p_list.clear(); in->top_k_list.clear(); in->seed_list.clear(); in->draw_list.clear();
+    in->temperatures.clear(); in->top_p_list.clear(); in->min_p_list.clear(); in->typical_p_list.clear(); in->top_k_list.clear(); in->seed_list.clear(); in->draw_list.clear();
     in->repetition_penalty_list.clear(); in->presence_penalty_list.clear(); in->frequency_penalty_list.clear();
     in->num_logprobs_list.clear(); in->prompt_logprobs_list.clear(); in->logit_flags.clear();
     in->guide_slots.clear(); in->guide_states.clear();
@@ -501,6 +509,8 @@ void LLMGenerator::PackStep(bool req_list_changed, ModelInput* in) const {
         in->lora_slots.push_back(t->lora_slot);
         in->temperatures.push_back(t->temperature);
         in->top_p_list.push_back(t->top_p);
+        in->min_p_list.push_back(t->min_p);
+        in->typical_p_list.push_back(t->typical_p);
         in->top_k_list.push_back(t->top_k);
         in->seed_list.push_back(t->seed);
         in->draw_list.push_back((uint64_t)t->gen_tokens_cnt);

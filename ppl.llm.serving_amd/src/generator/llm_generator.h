@@ -46,6 +46,8 @@ struct TidData final {
     uint64_t tid = 0;
     float temperature = 1.f;
     float top_p = 0.f;
+    float min_p = 0.f;
+    float typical_p = 1.f;
     int32_t top_k = 1;
     float repetition_penalty = 1.f;
     float presence_penalty = 0.f;
