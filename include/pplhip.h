@@ -822,6 +822,44 @@ PPLHIP_API int pplhip_op_attention(void* stream, const void* qkv, const pplhip_k
                                    int32_t num_heads, int32_t split_k, void* workspace, uint64_t workspace_bytes,
                                    void* out);
 
+/* ---- shared-prefix decode attention (csrc/k_attn_decode_shared.hip).  Arrived without a version bump: a client tells a library that has
+ * it by the symbol pplhip_op_attention_shared (dlsym).
+ * pplhip_op_shared_prefix_groups: which decode rows (b < decoding_batches) of a paged batch share leading pages.  Host arrays only, no
+ * HIP call, no device needed.  pages [B, max_pages], start_pos [B].  Rows whose page 0 is equal form a bucket; its P is the number of
+ * leading pages equal in all its rows times page_size, clamped to floor(min start_pos / page_size) * page_size (the page that holds a
+ * row's current token is never shared, every row keeps a key of its own) and rounded down to a multiple of 16.  A bucket with fewer than
+ * min_rows rows or P < min_tokens forms no group; min_rows <= 0 or page_size % 16 != 0: no groups at all.  group [B] receives the
+ * row's group or -1, group_tokens [up to B] each group's P, *n_groups the count; groups are numbered by their first row. */
+PPLHIP_API int pplhip_op_shared_prefix_groups(const int64_t* pages, int64_t max_pages, const int64_t* start_pos, int64_t B,
+                                              int64_t decoding_batches, int32_t page_size, int32_t min_rows, int64_t min_tokens,
+                                              int32_t* group, int64_t* group_tokens, int32_t* n_groups);
+/* Decode attention of B decode rows (rows only: no prefill requests) whose groups read their shared keys [0, P) once per tile of up to
+ * 16 (request, head) query rows: three launches -- the rows' own keys [P, start_pos] by the ordinary decode kernels on positions and a page
+ * table shifted by P, the shared keys by attn_decode_shared_kernel, one log-sum-exp merge.  out [B, H * D] fp16.
+ * qkv, seq_starts, workspace and out are device pointers; start_pos [B], cache_indices [B, max_pages], group [B] and group_tokens
+ * [n_groups] are HOST arrays (the call derives the shifted forms from them and uploads what the launches read into the workspace).
+ * own_split below 2 counts as 2, shared_split below 1 as 1.
+ * PPLHIP_UNSUPPORTED: anything but a paged cache with page_size % 16 == 0, fp16 or int8 (group 8) KV, head_dim 128 or 64 and
+ * num_heads / kv_heads <= 16.  PPLHIP_INVALID_VALUE: a workspace below pplhip_op_attention_shared_workspace_bytes, a P that is not a
+ * multiple of 16 and of page_size, P > start_pos[b] on a member row, a group id outside [-1, n_groups).  Both before any HIP call. */
+PPLHIP_API int pplhip_op_attention_shared(void* stream, const void* qkv, const pplhip_kv_view* kv, const int64_t* seq_starts,
+                                          const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B,
+                                          int32_t num_heads, const int32_t* group, const int64_t* group_tokens, int32_t n_groups,
+                                          int32_t own_split, int32_t shared_split, void* workspace, uint64_t workspace_bytes, void* out);
+/* The same inside a context (paged cache): min_rows > 0 turns detection on in pplhip_set_inputs (min_rows 0: off, the default -- no
+ * launch, upload or result differs from a library without the feature).  Groups are formed by the rule above whenever a step arrives with
+ * req_list_changed (or with another cut of the step into chunks), per chunk of the step's plan: a chunk of the two-lane or two-chunk
+ * schedule sees the rows inside it, a group cut by the boundary is two groups.  Every step with a group uploads the rows' shifted positions;
+ * a chunk with a group runs the three launches in place of the ordinary decode attention.  A context with the feature on captures no
+ * decode graphs.  PPLHIP_UNSUPPORTED (and the feature stays off) where
+ * pplhip_op_attention_shared would say so.  Call it between steps.
+ * pplhip_shared_prefix_info: groups, rows inside groups and the sum of the groups' shared tokens of the rank's last pplhip_run, zeros
+ * when that run took the ordinary path. */
+PPLHIP_API int pplhip_shared_prefix(pplhip_ctx* ctx, int32_t min_rows, int64_t min_tokens);
+PPLHIP_API int pplhip_shared_prefix_info(pplhip_ctx* ctx, int rank, int64_t* groups, int64_t* rows_in_groups, int64_t* shared_tokens);
+PPLHIP_API uint64_t pplhip_op_attention_shared_workspace_bytes(int64_t B, int32_t num_heads, int32_t head_dim, int64_t max_pages,
+                                                               int32_t own_split, int32_t shared_split);
+
 /* The direct collectives (csrc/k_comm.hip) as operators, for a context whose ranks all live in this process and run the direct mode
  * (pplhip_comm_mode == 2).  One call runs a SEQUENCE of collectives: every item is enqueued on every local rank from the calling thread,
  * back to back on the ranks' streams with no host synchronisation in between, then every rank is synchronised.  Channel 0 runs on the

@@ -70,7 +70,7 @@ template <int QBIT, int D>
 static hipError_t launch_decode_t(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, const int64_t* seq_starts,
                                   const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t nb,
                                   int H, int Hkv, int split, int threads, float* workspace, uint16_t* out, hipEvent_t t0,
-                                  hipEvent_t t1) {
+                                  hipEvent_t t1, bool reduce) {
     const int nw = threads / 64;
     const size_t lds = (size_t)nw * (D + 2) * sizeof(float);
     // t0 / t1: start and stop timestamps taken from the kernel's own dispatch packet -- no extra barrier packets on the stream
@@ -82,15 +82,16 @@ static hipError_t launch_decode_t(hipStream_t s, const uint16_t* qkv, const KvAd
         hipLaunchKernelGGL((attn_decode_kernel<QBIT, D>), dim3(H, (unsigned)nb, split), dim3(threads), lds, s, qkv, kv,
                            seq_starts, start_pos, cache_indices, max_pages, H, Hkv, split, workspace, out);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess || split == 1) return e;
+    if (e != hipSuccess || split == 1 || !reduce) return e;
     return launch_attn_reduce(s, workspace, split, nb * H, D, out);
 }
 
 hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                               const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                               int64_t max_pages, int64_t nb, int H, int Hkv, int D, int64_t max_kv_len, int split,
-                              int threads, float* workspace, uint16_t* out, hipEvent_t t0, hipEvent_t t1) {
+                              int threads, float* workspace, uint16_t* out, hipEvent_t t0, hipEvent_t t1, bool reduce) {
     if (nb == 0) return hipSuccess;
+    if (!reduce && split < 2) return hipErrorInvalidValue;   // (the caller's merge reads partial rows)
     static const int forced_tpb = tune_int("PPLHIP_ATTN_TPB", 0);  // tuning only
     if (forced_tpb) threads = forced_tpb;
     if (threads < 64 || threads > 64 * DEC_MAX_WAVES || threads % 64) return hipErrorInvalidValue;
@@ -101,7 +102,7 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
     if (attn_decode_gqa_supported(kv_fmt, H, Hkv, D) && !no_gqa) {
         hipError_t e = launch_attn_decode_gqa(s, qkv, kv, kv_fmt, seq_starts, start_pos, cache_indices, max_pages, nb, H,
                                               Hkv, D, split, workspace, out, t0, t1);
-        if (e != hipSuccess || split == 1) return e;
+        if (e != hipSuccess || split == 1 || !reduce) return e;
         return launch_attn_reduce(s, workspace, split, nb * H, D, out);
     }
     if ((kv_fmt != KV_FP16 && kv_fmt != KV_I8G8 && kv_fmt != KV_FP8 && kv_fmt != KV_I4G32) || (D != 128 && D != 64 && D != 32)) return hipErrorInvalidValue;
@@ -109,7 +110,7 @@ hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& 
     dispatch_int<KV_I8G8, KV_FP16, KV_FP8, KV_I4G32>(kv_fmt, [&](auto QB) {
         dispatch_int<128, 64, 32>(D, [&](auto DD) {
             e = launch_decode_t<QB, DD>(s, qkv, kv, seq_starts, start_pos, cache_indices, max_pages, nb, H, Hkv, split, threads, workspace,
-                                        out, t0, t1);
+                                        out, t0, t1, reduce);
         });
     });
     return e;

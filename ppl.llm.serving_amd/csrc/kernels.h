@@ -97,7 +97,8 @@ size_t attn_decode_workspace_bytes(int64_t nb, int H, int D, int split);
 hipError_t launch_attn_decode(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt,
                               const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                               int64_t max_pages, int64_t nb, int H, int Hkv, int D, int64_t max_kv_len, int split,
-                              int threads, float* workspace, uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+                              int threads, float* workspace, uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
+                              bool reduce = true);   // reduce false (split >= 2): the partial rows stay in `workspace`, `out` is not written
 // merges the `nsplit` partial rows of each of n_row_heads (row, head) pairs of `ws` ([row][head][split][D + 2] floats) into out
 // ([row][head][D] fp16): the end of every split launch -- both decode kernels and the split-KV prefill
 hipError_t launch_attn_reduce(hipStream_t s, const float* ws, int nsplit, int64_t n_row_heads, int D, uint16_t* out);
@@ -125,6 +126,54 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
                                   const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
                                   int64_t max_pages, int64_t nb, int H, int Hkv, int D, int split, float* workspace,
                                   uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+
+// ---- k_attn_decode_shared.hip: shared-prefix decode attention -----------------------------------------
+// up to 16 query rows (request, head of one KV head's group) of ONE prefix group: requests row[0], row[grp], ... (n of them; column c
+// belongs to request c / grp, row[c] = -1 marks padding) over the group's shared keys [0, tokens), addressed through the page table of
+// batch row `lead`.  Built on the host (rt_shared_prefix.cc shared_build_tiles).
+struct SharedTile {
+    int32_t n, tokens, lead;
+    int32_t row[16];
+};
+// paged cache with page_size % 16 == 0, KV_FP16 / KV_I8G8, head_dim 128 / 64, H / Hkv <= 16
+bool attn_shared_supported(int kv_fmt, int cache_mode, int page_size, int H, int Hkv, int D);
+// partial rows (O[D] unnormalised, m, l) of every tile's rows over its shared keys -> workspace fp32 [row][head][split][D + 2] (rows in
+// no tile are not written); cache_indices: the UNSHIFTED page table [rows, max_pages]
+hipError_t launch_attn_decode_shared(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
+                                     const int64_t* cache_indices, int64_t max_pages, const SharedTile* tiles, int ntiles, int H, int Hkv,
+                                     int D, int split, float* workspace);
+// out[row][head] = merge of the row's own_split partial rows of ws_own and, where row_tokens[row] > 0, its shared_split rows of ws_shared
+hipError_t launch_attn_shared_merge(hipStream_t s, const float* ws_own, int own_split, const float* ws_shared, int shared_split,
+                                    const int32_t* row_tokens, int64_t nb, int H, int D, uint16_t* out);
+// ---- rt_shared_prefix.cc: the host side of the above (pure functions, no HIP call) ----
+// Prefix groups of decode rows [0, nb) of a page table [nb, max_pages]: rows whose page 0 is equal form a bucket; its P = (leading pages
+// equal in all its rows) * page_size, clamped to floor(min start_pos / page_size) * page_size (the page of a row's current token is never
+// shared, every row keeps a key of its own) and rounded down to a multiple of 16; a bucket of fewer than min_rows rows or with P <
+// max(min_tokens, 16) forms no group, nor does any when page_size % 16 != 0.  group[b] = the row's group (numbered by first row) or -1,
+// group_tokens[g] = P (room for nb / max(min_rows, 1) entries, at most nb).  Returns the number of groups.
+int shared_prefix_groups(const int64_t* pages, int64_t max_pages, const int64_t* start_pos, int64_t nb, int page_size, int min_rows,
+                         int64_t min_tokens, int32_t* group, int64_t* group_tokens);
+// the tile list of rows [0, nb): every group's rows in batch order, 16 / grp requests per tile (at most nb tiles); returns the count
+int shared_build_tiles(const int32_t* group, const int64_t* group_tokens, int n_groups, int64_t nb, int grp, SharedTile* out);
+// What the three launches read besides the step's inputs, as ONE block (host image -> one copy): shifted positions start_pos - P_b, the
+// page table with row b shifted left by P_b / page_size columns, P_b per row and the tile list (room for nb tiles)
+struct SharedPlanBlock {
+    int64_t *own_pos, *own_pages;
+    int32_t* row_tokens;
+    SharedTile* tiles;
+    size_t bytes;
+    SharedPlanBlock(void* base, int64_t nb, int64_t max_pages) {
+        char* p = (char*)base;
+        own_pos = (int64_t*)p; p += nb * 8;
+        own_pages = (int64_t*)p; p += nb * max_pages * 8;
+        row_tokens = (int32_t*)p; p += (nb + 1) / 2 * 8;
+        tiles = (SharedTile*)p; p += nb * sizeof(SharedTile);
+        bytes = (size_t)(p - (char*)base);
+    }
+};
+// fills own_pages, row_tokens and tiles of the host image (everything that changes only with the page table); returns the tile count
+int shared_plan_fill(const SharedPlanBlock& h, const int64_t* pages, int64_t max_pages, int64_t nb, int page_size, int grp,
+                     const int32_t* group, const int64_t* group_tokens, int n_groups);
 
 // ---- k_gemm.hip -------------------------------------------------------------------------------
 // y[M,N] = x[M,K] . W[N,K]^T (+ per-channel / per-group scales).  wq_bit 0/8/4.  out_fp32: y is float.

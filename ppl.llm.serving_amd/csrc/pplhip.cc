@@ -130,12 +130,12 @@ KvAddr make_kv_addr(const pplhip_model_desc& d, int Hkv, int D, uint64_t tokens,
 
 namespace {
 
-void prof_begin(pplhip_ctx* c, Rank& R, const Lane& lane, int cls, ProfEvent* ev) {
+void prof_begin(pplhip_ctx* c, Rank& R, const Lane& lane, int cls, ProfEvent* ev, bool in_light_mode = false) {
     ev->cls = -1;
     if (!c->o.enable_profiling) return;
     // 2 = light: only the decode-attention launches (through hipExtLaunchKernel's start / stop events) and the whole run.  An event record is a barrier packet on the
     // stream: the full set (10 per layer) costs a batch-1024 decode step 1.3 ms of 43.9 (profiles/probes/prof_overhead.py)
-    if (c->o.enable_profiling == 2 && cls != PPLHIP_PROF_RUN) return;   // (decode attention: timed through its own launch)
+    if (c->o.enable_profiling == 2 && cls != PPLHIP_PROF_RUN && !in_light_mode) return;   // (decode attention: timed through its own launch)
     std::pair<hipEvent_t, hipEvent_t> p;
     if (!R.prof_free.empty()) { p = R.prof_free.back(); R.prof_free.pop_back(); }
     else { hipEventCreate(&p.first); hipEventCreate(&p.second); }
@@ -279,6 +279,7 @@ void pplhip_destroy(pplhip_ctx* c) {
         for (Stage& st : R.st_rule) st.release();
         if (R.pages_host) hipHostFree(R.pages_host);
         if (R.pages_dev) hipFree(R.pages_dev);
+        shared_prefix_release(R);
         for (void* p : {(void*)R.h_rand, (void*)R.h_srows, (void*)R.h_tlp_in, (void*)R.h_tlp_out, (void*)R.h_plp_out}) if (p) hipHostFree(p);
         if (R.gd_bytes) hipFree(R.gd_bytes);
         if (R.gd_off) hipFree(R.gd_off);
@@ -966,6 +967,7 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
         R.max_pages = st->max_pages;
     }
     if (c->d.cache_mode == 1) R.d_ci = R.pages_dev;
+    if (R.sp_min_rows > 0) shared_prefix_stage(R, st);   // shared-prefix decode attention (opt-in): the groups are formed at the run, per chunk
     R.B = B; R.T = T;
     R.decoding_batches = st->decoding_batches;
     R.max_seq_len = st->max_seq_len;
@@ -1132,7 +1134,15 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
     // decode rows of the chunk: per-request arrays shifted to the chunk (q rows stay absolute through seq_starts);
     // prefill requests: absolute request range
     const int64_t ci_stride = d.cache_mode == 1 ? R.max_pages : 1;
-    if (k.nd > 0) {
+    // shared-prefix groups among the chunk's decode rows (shared_prefix_plan formed them in front of the first layer): own part, shared
+    // part, merge (rt_shared_prefix.cc).  Three launches: an event pair around them, also in the light profiling mode
+    const Rank::SpChunk* const shared = shared_prefix_chunk(c, R, k, split, lane.attn_ws_bytes);
+    if (shared) {
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_DECODE, &ev, /*in_light_mode=*/true);
+        if (int rc = shared_prefix_attention(c, rank, lane, kv, *shared, split, threads)) return rc;
+        prof_end(R, lane, &ev);
+    }
+    if (k.nd > 0 && !shared) {
         // light profiling: the launch carries its own start / stop events (timestamps of the dispatch packet, no barrier
         // packets on the stream; with split-K the reduce kernel is not included)
         const bool light = c->o.enable_profiling == 2;
@@ -1263,6 +1273,7 @@ static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& set
     Lane lane[2] = {make_lane(R, 0, 0), make_lane(R, 1, p.lane1_ws_off)};
     auto lane_of = [&](int i) -> Lane& { return lane[dual ? i : 0]; };
 
+    if (int rc0 = shared_prefix_plan(c, rank, p)) return rc0;   // (feature off: clears pplhip_shared_prefix_info's counters, nothing else)
     ProfEvent ev_run, ev;
     prof_begin(c, R, lane[0], PPLHIP_PROF_RUN, &ev_run);
     HIPCK(c, rank, launch_embedding(s, R.d_tok, R.embed, T, hd, R.h));
@@ -1371,6 +1382,7 @@ static int run_decode_graph(pplhip_ctx* c, int rank, const pplhip_plan_settings&
     const int64_t nb_decode = std::min<int64_t>(std::max<int64_t>(R.decoding_batches, 0), B);
     if (!c->graph_on || c->tp_on || c->o.enable_profiling || R.T != B || nb_decode != B || B > c->graph_max_batch) return 0;
     if (R.lora_ntiles > 0) return 0;   // the tile list is this step's own: neither captured nor replayed
+    if (R.sp_min_rows > 0) return 0;   // (so are the shared-prefix tile lists, formed per chunk at the run)
     const uint64_t key = (uint64_t)B | ((uint64_t)decode_split(settings, B, R.max_kv_len) << 24) | ((uint64_t)R.max_pages << 32);
     auto it = R.graphs.find(key);
     if (it == R.graphs.end()) {  // first sight: run eagerly (one-time function attributes, lazily loaded code objects)

@@ -359,6 +359,30 @@ struct Rank {
     std::vector<uint8_t> lora_touch;        // [layer][target]: some adapter of the staged assignment changes this linear
     bool lora_stale = false;                // a slot was unloaded under a staged assignment: pplhip_run wants new inputs first
 
+    // shared-prefix decode attention (pplhip_shared_prefix, rt_shared_prefix.cc; k_attn_decode_shared.hip).  sp_min_rows 0: off, nothing
+    // below is touched.  The groups are formed per CHUNK of the step's plan (a chunk's decode rows b0 .. b0 + nd; a group cut by the chunk
+    // boundary is two groups), when the request list or the cut changes; rows in a chunk's tiles count from b0.  Device block sp_dev:
+    // shifted positions of all batch rows first (they go up every step), then one SharedPlanBlock (kernels.h) per chunk with groups.
+    // Both uploads go through double-buffered stages: no host wait for the stream.
+    struct SpChunk {
+        int64_t b0 = 0, nd = 0;
+        int n_groups = 0, ntiles = 0;
+        int64_t rows = 0, tokens = 0;   // rows inside groups; sum of the groups' P
+        uint64_t off = 0;               // of the chunk's SharedPlanBlock in sp_dev
+    };
+    int sp_min_rows = 0;
+    int64_t sp_min_tokens = 0;
+    bool sp_dirty = true;                             // the request list changed since the groups were formed
+    std::vector<int64_t> sp_start_pos;                // the staged step's start_pos (host)
+    std::vector<int32_t> sp_row_tokens;               // P of every batch row (0: in no group)
+    SpChunk sp_chunk[2];
+    char* sp_dev = nullptr;
+    uint64_t sp_cap = 0;                              // bytes of sp_dev and of each plan stage
+    Stage st_sp_plan[2], st_sp_pos[2];
+    int st_sp_plan_cur = 0, st_sp_cur = 0;
+    float* sp_ws = nullptr;                           // shared partial rows [cap_B][H][SP_SPLIT_MAX][D + 2]
+    int64_t sp_last[3] = {0, 0, 0};                   // groups, rows in groups, shared tokens of the last run (summed over its chunks)
+
     // diagnosis (pplhip_debug_run_dump): residual stream h and the pending row-parallel FFN output after every layer
     uint16_t* dump_dev = nullptr;  // [L+1][2][T, hidden] fp16 (slot 0 = h, slot 1 = pending), allocated for one run
 
@@ -457,6 +481,18 @@ int p2p_check(pplhip_ctx* c, int rank);
 int p2p_next_epoch(pplhip_ctx* c, int rank, Channel& ch, hipStream_t s, uint32_t* epoch);
 // rt_lora.cc
 void lora_build_tiles(const int32_t* row_slots, int64_t T, std::vector<LoraTile>& out);
+// rt_shared_prefix.cc
+constexpr int SP_SPLIT_MAX = 4;
+// pplhip_set_inputs: keeps the step's start_pos and notes a changed request list (no HIP call)
+void shared_prefix_stage(Rank& R, const pplhip_step* st);
+// run_launches, once per step in front of the first layer, on the rank's stream: (re)forms the groups of the plan's chunks where needed
+// and uploads what the step's launches read
+int shared_prefix_plan(pplhip_ctx* c, int rank, const pplhip_step_plan& p);
+// the chunk's groups, or NULL: the chunk runs the ordinary decode attention
+const Rank::SpChunk* shared_prefix_chunk(const pplhip_ctx* c, const Rank& R, const pplhip_chunk& k, int split, size_t attn_ws_bytes);
+// the chunk's decode attention through the shared path: own part, shared part, merge
+int shared_prefix_attention(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const Rank::SpChunk& sc, int split, int threads);
+void shared_prefix_release(Rank& R);
 // rt_postproc.cc
 int sample_row_list(const int32_t* top_k, const float* min_p, const float* typical_p, int B, int32_t* rows, int* n_trunc);
 int top_logprobs_row_list(const int32_t* num_logprobs, int B, int32_t* rows);

@@ -476,3 +476,77 @@ int pplhip_op_attention(void* stream, const void* qkv, const pplhip_kv_view* kv,
     return op_rc(e);
 }
 
+int pplhip_op_shared_prefix_groups(const int64_t* pages, int64_t max_pages, const int64_t* start_pos, int64_t B, int64_t decoding_batches,
+                                   int32_t page_size, int32_t min_rows, int64_t min_tokens, int32_t* group, int64_t* group_tokens,
+                                   int32_t* n_groups) {
+    if (!pages || !start_pos || !group || !group_tokens || !n_groups || B < 0 || max_pages <= 0 || page_size <= 0) return PPLHIP_INVALID_VALUE;
+    const int64_t nb = std::min<int64_t>(std::max<int64_t>(decoding_batches, 0), B);
+    *n_groups = shared_prefix_groups(pages, max_pages, start_pos, nb, page_size, min_rows, min_tokens, group, group_tokens);
+    for (int64_t b = nb; b < B; ++b) group[b] = -1;
+    return 0;
+}
+
+// device workspace of pplhip_op_attention_shared: own partials | shared partials | page table | plan block, each on a 256-byte boundary
+struct SharedOpWs {
+    uint64_t own, shared, pages, plan, bytes;
+    SharedOpWs(int64_t B, int H, int D, int64_t max_pages, int own_split, int shared_split) {
+        auto up = [](uint64_t v) { return (v + 255) / 256 * 256; };
+        own = 0;
+        shared = own + up(attn_decode_workspace_bytes(B, H, D, own_split));
+        pages = shared + up((uint64_t)B * H * shared_split * (D + 2) * 4);
+        plan = pages + up((uint64_t)B * max_pages * 8);
+        bytes = plan + up(SharedPlanBlock(nullptr, B, max_pages).bytes) + 256;   // (+ 256: the caller's pointer may sit anywhere)
+    }
+};
+
+uint64_t pplhip_op_attention_shared_workspace_bytes(int64_t B, int32_t num_heads, int32_t head_dim, int64_t max_pages, int32_t own_split,
+                                                    int32_t shared_split) {
+    if (B < 0 || num_heads <= 0 || head_dim <= 0 || max_pages <= 0) return 0;
+    return SharedOpWs(B, num_heads, head_dim, max_pages, std::max(own_split, 2), std::max(shared_split, 1)).bytes;
+}
+
+int pplhip_op_attention_shared(void* stream, const void* qkv, const pplhip_kv_view* kv, const int64_t* seq_starts, const int64_t* start_pos,
+                               const int64_t* cache_indices, int64_t max_pages, int64_t B, int32_t num_heads, const int32_t* group,
+                               const int64_t* group_tokens, int32_t n_groups, int32_t own_split, int32_t shared_split, void* workspace,
+                               uint64_t workspace_bytes, void* out) {
+    // everything the kernels trust is checked here, before any HIP call
+    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
+    if (fmt < 0 || B < 0 || B > INT32_MAX || n_groups < 0 || max_pages <= 0 || num_heads <= 0) return PPLHIP_INVALID_VALUE;
+    if (!attn_shared_supported(fmt, kv->mode, kv->page_size, num_heads, kv->kv_heads, kv->head_dim)) return PPLHIP_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!qkv || !seq_starts || !start_pos || !cache_indices || !group || (n_groups > 0 && !group_tokens) || !workspace || !out)
+        return PPLHIP_INVALID_VALUE;
+    own_split = std::max(own_split, 2);   // the own launch must leave partial rows: split 1 writes `out` itself
+    shared_split = std::max(shared_split, 1);
+    const int H = num_heads, D = kv->head_dim, ps = kv->page_size;
+    for (int g = 0; g < n_groups; ++g)
+        if (group_tokens[g] < 16 || group_tokens[g] % 16 || group_tokens[g] % ps || group_tokens[g] / ps > max_pages || group_tokens[g] > INT32_MAX)
+            return PPLHIP_INVALID_VALUE;
+    for (int64_t b = 0; b < B; ++b) {
+        if (group[b] < -1 || group[b] >= n_groups || start_pos[b] < 0) return PPLHIP_INVALID_VALUE;
+        if (group[b] >= 0 && group_tokens[group[b]] > start_pos[b]) return PPLHIP_INVALID_VALUE;   // a row keeps a key of its own
+    }
+    const SharedOpWs L(B, H, D, max_pages, own_split, shared_split);
+    if (workspace_bytes < L.bytes) return PPLHIP_INVALID_VALUE;
+    char* base = (char*)workspace + ((256 - ((uintptr_t)workspace & 255)) & 255);
+    // host image of the plan block, then two copies (pageable sources: each copy has left the host buffer when the call returns)
+    std::vector<int64_t> img((SharedPlanBlock(nullptr, B, max_pages).bytes + 7) / 8);
+    const SharedPlanBlock h(img.data(), B, max_pages), d(base + L.plan, B, max_pages);
+    const int ntiles = shared_plan_fill(h, cache_indices, max_pages, B, ps, H / kv->kv_heads, group, group_tokens, n_groups);
+    for (int64_t b = 0; b < B; ++b) h.own_pos[b] = start_pos[b] - h.row_tokens[b];
+    hipStream_t s = (hipStream_t)stream;
+    const KvAddr a = view_addr(kv);
+    hipError_t e = hipMemcpyAsync(base + L.pages, cache_indices, (size_t)B * max_pages * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + L.plan, img.data(), h.bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_attn_decode(s, (const uint16_t*)qkv, a, fmt, seq_starts, d.own_pos, d.own_pages, max_pages, B, H, kv->kv_heads, D, 0, own_split, 256,
+                               (float*)(base + L.own), (uint16_t*)out, nullptr, nullptr, /*reduce=*/false);
+    if (e == hipSuccess)
+        e = launch_attn_decode_shared(s, (const uint16_t*)qkv, a, fmt, seq_starts, (const int64_t*)(base + L.pages), max_pages, d.tiles, ntiles, H,
+                                      kv->kv_heads, D, shared_split, (float*)(base + L.shared));
+    if (e == hipSuccess)
+        e = launch_attn_shared_merge(s, (const float*)(base + L.own), own_split, (const float*)(base + L.shared), shared_split, d.row_tokens, B, H,
+                                     D, (uint16_t*)out);
+    return op_rc(e);
+}
+

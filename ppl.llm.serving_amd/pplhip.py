@@ -188,6 +188,8 @@ SYMBOLS = [
     "pplhip_op_linear_i8", "pplhip_op_rmsnorm_quant_f8", "pplhip_op_quant_act_f8", "pplhip_op_quant_weight_f8", "pplhip_op_linear_f8",
     "pplhip_op_silu_mul", "pplhip_op_penalty", "pplhip_op_sample", "pplhip_op_sample_rows", "pplhip_op_sample_rows2", "pplhip_op_sample_uniform", "pplhip_op_top_logprobs", "pplhip_op_prompt_logprobs", "pplhip_op_logit_edit", "pplhip_op_guide_build", "pplhip_op_guide_mask", "pplhip_op_guide_build16", "pplhip_op_guide_mask16", "pplhip_op_rope_kv_write",
     "pplhip_op_attention", "pplhip_build_rope_table",
+    "pplhip_op_shared_prefix_groups", "pplhip_op_attention_shared", "pplhip_op_attention_shared_workspace_bytes",
+    "pplhip_shared_prefix", "pplhip_shared_prefix_info",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
 
@@ -305,6 +307,13 @@ def lib():
         L.pplhip_op_attention.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
                                           vp, u64, vp]
         L.pplhip_build_rope_table.argtypes = [vp, i32, i32, f32]
+        if hasattr(L, "pplhip_op_attention_shared"):   # (PPLHIP_LIB may name a build from before shared-prefix attention)
+            L.pplhip_op_shared_prefix_groups.argtypes = [vp, i64, vp, i64, i64, i32, i32, i64, vp, vp, vp]
+            L.pplhip_op_attention_shared.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i32, vp, vp, i32, i32, i32, vp, u64, vp]
+            L.pplhip_op_attention_shared_workspace_bytes.argtypes = [i64, i32, i32, i64, i32, i32]
+            L.pplhip_op_attention_shared_workspace_bytes.restype = u64
+            L.pplhip_shared_prefix.argtypes = [vp, i32, i64]
+            L.pplhip_shared_prefix_info.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         # (the row-kernel test entries: PPLHIP_LIB may name a build from before them, as above)
         if hasattr(L, "pplhip_op_rmsnorm_form"):
             L.pplhip_op_rmsnorm_form.argtypes = [i64, i32, i32, i32, C.c_char_p, i32]
@@ -674,6 +683,16 @@ class Context:
 
     def run(self, rank, cache_prefill=0):
         self._ck(lib().pplhip_run(self.h, rank, cache_prefill), rank, "run")
+
+    def shared_prefix(self, min_rows, min_tokens):
+        """shared-prefix decode attention on (min_rows > 0) or off (0)"""
+        self._ck(lib().pplhip_shared_prefix(self.h, min_rows, min_tokens), -1, "shared_prefix")
+
+    def shared_prefix_info(self, rank):
+        """(groups, rows in groups, shared tokens) of the rank's last run"""
+        v = [C.c_int64(), C.c_int64(), C.c_int64()]
+        self._ck(lib().pplhip_shared_prefix_info(self.h, rank, *[C.byref(x) for x in v]), rank, "shared_prefix_info")
+        return tuple(int(x.value) for x in v)
 
     def run_dump(self, rank, num_tokens):
         """diagnosis: run the step and return the residual stream after every layer, fp32 [L+1, T, hidden] (oracle convention)"""

@@ -267,6 +267,8 @@ def add_flags(ap):
     ap.add_argument("--max-prefill-batch", type=int, default=64)
     ap.add_argument("--max-cooldown-request", type=int, default=2)
     ap.add_argument("--enable-prefix-cache", action="store_true")
+    ap.add_argument("--shared-prefix-attention", action="store_true",
+                    help="with --enable-prefix-cache: decode rows behind one cached prompt read its KV pages once per tile of query rows")
     ap.add_argument("--enable-penalty", action="store_true")
     ap.add_argument("--stop-tokens", default="")
     ap.add_argument("--tokenizer-path", default="", help="sentencepiece model; without it only the token-in/token-out path is served")
@@ -305,6 +307,11 @@ async def serve(a, ready=None):
     rc = lib.pplsrv_create_ex(C.byref(make_config(a)), int(a.per_request_sampling), a.sampling_seed, C.byref(h))
     if rc != 0:
         raise RuntimeError(f"pplsrv_create_ex failed: RetCode {-rc}")
+    if a.shared_prefix_attention:
+        lib.pplsrv_enable_shared_prefix_attention.argtypes = [C.c_void_p]
+        rc = lib.pplsrv_enable_shared_prefix_attention(h)
+        if rc != 0:
+            raise RuntimeError(f"pplsrv_enable_shared_prefix_attention failed: RetCode {-rc}")
     srv = Serving(lib, h, bool(a.tokenizer_path))
     srv.start(asyncio.get_running_loop())
     server = grpc.aio.server(options=[("grpc.max_receive_message_length", 64 << 20), ("grpc.max_send_message_length", 64 << 20)])

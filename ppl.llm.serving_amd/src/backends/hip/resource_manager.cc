@@ -397,6 +397,17 @@ RetCode HipResourceManager::Init(const ModelConfig& mc, const ResourceConfig& rc
     return post_processor->InitPostProcessorMem(rc.max_running_batch, mc.vocab_size, rc.enable_penalty);
 }
 
+RetCode HipResourceManager::EnableSharedPrefixAttention() {
+    if (!ctx) return RC_INVALID_VALUE;
+    const int st = pplhip_shared_prefix(ctx, 2, 64);
+    if (st == PPLHIP_UNSUPPORTED) {
+        LOG(WARNING) << "shared-prefix attention needs a paged KV cache (fp16 or int8, pages of a multiple of 16 tokens): left off";
+        return RC_SUCCESS;
+    }
+    if (st) LOG(ERROR) << "pplhip_shared_prefix failed: " << pplhip_last_error(ctx, -1);
+    return FromPplHipStatus(st);
+}
+
 static RetCode LoadAdapterRank(uint32_t id, pplhip_ctx* ctx, int slot, const std::string& dir) {
     const int st = pplhip_lora_load(ctx, (int)id, slot, dir.c_str());
     if (st) LOG(ERROR) << "load adapter [" << dir << "] into slot [" << slot << "] on rank [" << id << "] failed: " << pplhip_last_error(ctx, (int)id);

@@ -78,6 +78,10 @@ struct HipResourceManager final {
     // fresh uid; unloads a slot unless a pending or running request names it (RC_INVALID_VALUE).  Callable while the generator runs.
     ppl::common::RetCode LoadAdapter(int slot, const std::string& dir);
     ppl::common::RetCode UnloadAdapter(int slot);
+    // GeneratorConfig::enable_shared_prefix_attention: shared-prefix decode attention on every rank (pplhip_shared_prefix(ctx, 2, 64): at
+    // least two rows behind at least 64 shared tokens -- reasoned values, not measured ones).  After Init, before the generator runs.  A
+    // cache format or geometry without a shared kernel logs a warning and leaves the ordinary path in place (RC_SUCCESS).
+    ppl::common::RetCode EnableSharedPrefixAttention();
 
     ppl::common::StaticThreadPool device_worker_pool_;
     std::vector<ResourceItem> items;

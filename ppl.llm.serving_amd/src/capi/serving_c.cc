@@ -202,6 +202,11 @@ int pplsrv_create_ex(const pplsrv_config* cfg, int32_t per_request_sampling, uin
 
 int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n) { return pplsrv_submit_lora(s, reqs, nullptr, n); }
 
+int pplsrv_enable_shared_prefix_attention(pplsrv* s) {
+    if (!s) return -(int)ppl::common::RC_INVALID_VALUE;
+    return -(int)s->resource_manager.EnableSharedPrefixAttention();
+}
+
 int pplsrv_load_adapter(pplsrv* s, int32_t slot, const char* dir) {
     if (!s || !dir) return -(int)ppl::common::RC_INVALID_VALUE;
     return -(int)s->resource_manager.LoadAdapter(slot, dir);

@@ -73,6 +73,10 @@ PPLSRV_API int pplsrv_submit(pplsrv* s, const pplsrv_request* reqs, int32_t n);
  * running request names; pplsrv_submit_lora is pplsrv_submit with slots[i] the adapter of reqs[i] (-1 = none; slots NULL = none at all).
  * A request that names a slot nothing is loaded in fails (PPLSRV_FAILED).  K/V pages computed under an adapter are shared through the
  * prefix cache only among requests on the same load of that adapter. */
+/* GeneratorConfig::enable_shared_prefix_attention as a call of its own (the config struct keeps its layout): shared-prefix decode
+ * attention for the server's context, meaningful with enable_prefix_cache.  Right after pplsrv_create*, before the first submit.  A cache
+ * format without a shared kernel is logged and left on the ordinary path (returns 0). */
+PPLSRV_API int pplsrv_enable_shared_prefix_attention(pplsrv* s);
 PPLSRV_API int pplsrv_load_adapter(pplsrv* s, int32_t slot, const char* dir);
 PPLSRV_API int pplsrv_unload_adapter(pplsrv* s, int32_t slot);
 PPLSRV_API int pplsrv_submit_lora(pplsrv* s, const pplsrv_request* reqs, const int32_t* slots, int32_t n);

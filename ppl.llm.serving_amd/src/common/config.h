@@ -62,6 +62,9 @@ struct GeneratorConfig final {
     int32_t max_prefill_batch = 0;               // --max-prefill-batch (1 with the prefix cache, offline_inference.cc:97-99)
     int max_cooldown_request = 2;                // --max-cooldown-request: finished requests to wait for when KV is full
     bool enable_prefix_cache = false;            // --enable-prefix-cache (needs cache_mode 1)
+    // decode rows behind one cached prompt read its pages once per tile of query rows (HipResourceManager::EnableSharedPrefixAttention);
+    // meaningful only with enable_prefix_cache, which is what makes requests hold the same leading pages
+    bool enable_shared_prefix_attention = false; // --shared-prefix-attention
     // ---- token classes -------------------------------------------------------------------------------------------
     std::set<int> stop_tokens;                   // --stop-tokens: EOS-like tokens
     std::set<int> special_tokens;                // --special_tokens: reported as Response::is_special

@@ -42,6 +42,7 @@ int main(int argc, char** argv) {
     hip::HipResourceManager resource_manager;
     RetCode st = resource_manager.Init(mc, rc);
     if (st != RC_SUCCESS) { std::cerr << "init HipResourceManager failed: " << GetRetCodeStr(st) << "\n"; return -1; }
+    if (gc.enable_shared_prefix_attention && resource_manager.EnableSharedPrefixAttention() != RC_SUCCESS) return -1;
     Resource resource;
     resource_manager.FillResource(&resource);
 

@@ -52,6 +52,7 @@ int main(int argc, char** argv) {
             return -1;
         }
         scenario::ScenarioGeneratorConfig(scn, &gc);
+        gc.enable_shared_prefix_attention = scenario::ScenarioSharedPrefixAttention(scn, gc.enable_shared_prefix_attention);
         rc.enable_penalty = gc.enable_penalty;
         rc.max_running_batch = gc.max_running_batch;
         rc.max_tokens_per_step = gc.max_tokens_per_step;
@@ -64,6 +65,7 @@ int main(int argc, char** argv) {
         std::cerr << "init HipResourceManager failed: " << GetRetCodeStr(st) << "\n";
         return -1;
     }
+    if (gc.enable_shared_prefix_attention && resource_manager.EnableSharedPrefixAttention() != RC_SUCCESS) return -1;
     Resource resource;
     resource_manager.FillResource(&resource);
     std::unique_ptr<Tokenizer> tokenizer;

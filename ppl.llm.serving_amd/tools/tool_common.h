@@ -47,6 +47,7 @@ inline void DefineCommonFlags(Args* a) {
     a->Def("--tokenizer-type", "sentencepiece", "sentencepiece (the huggingface json tokenizer is not provided)");
     a->Def("--tokenizer-config-path", "", "unused by the sentencepiece tokenizer");
     a->Def("--enable-prefix-cache", "false", "is enable prefix cache", true);
+    a->Def("--shared-prefix-attention", "false", "with --enable-prefix-cache: decode rows behind one cached prompt read its KV pages once per tile of query rows (shared-prefix decode attention)", true);
     a->Def("--max-prefill-batch", "64", "max prefill batches per step");
     a->Def("--enable-profiling", "false", "print profiling message", true);
     // flags of the reference's tools that only its server reads: accepted so that a command line carries over unchanged
@@ -104,6 +105,7 @@ inline bool FillConfigs(const Args& a, ppl::llm::ResourceConfig* rc, ppl::llm::G
     ppl::llm::utils::ParseTokens(a.Str("--special_tokens"), &gc->special_tokens);
     gc->max_cooldown_request = a.Int("--max-cooldown-request");
     gc->enable_prefix_cache = a.Bool("--enable-prefix-cache");
+    gc->enable_shared_prefix_attention = a.Bool("--shared-prefix-attention");
     gc->max_prefill_batch = gc->enable_prefix_cache ? 1 : a.Int("--max-prefill-batch");  // offline_inference.cc:97-99
     gc->enable_profiling = a.Bool("--enable-profiling");
 
