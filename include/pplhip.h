@@ -860,6 +860,40 @@ PPLHIP_API int pplhip_shared_prefix_info(pplhip_ctx* ctx, int rank, int64_t* gro
 PPLHIP_API uint64_t pplhip_op_attention_shared_workspace_bytes(int64_t B, int32_t num_heads, int32_t head_dim, int64_t max_pages,
                                                                int32_t own_split, int32_t shared_split);
 
+/* ---- mixture-of-experts feed-forward block (Mixtral; csrc/k_moe.hip).  Arrived without a version bump: a client tells a library that has
+ * it by the symbol pplhip_moe (dlsym).
+ * For a normed row x with E experts and k experts per token: router logits r_e = x . gate_e (gate fp16 [E, hidden], fp32 sums); the k largest
+ * are chosen, ties to the lower expert, slots by descending logit; p_s = exp(r_s - r_max) / sum over the k slots; y = fp16(sum_s p_s .
+ * w2_{e_s}(h_s)), h_s = fp16(silu(gate) . up) of expert e_s's w13 as the dense fused SwiGLU forms it, summed in slot order in fp32 with one
+ * rounding.  No floating-point atomics: a call repeated gives the same bits.  Limits: E <= 64, k <= 8, k <= E, hidden % 64 == 0, fp16 or
+ * W8A16 weights.
+ * pplhip_op_moe_route: ids / weights [T, k] and counts [64] (the histogram of ids; entries from E on are zero).
+ * pplhip_op_moe_ffn: x [T, hidden] -> y [T, ldy] fp16.  The expert weights are stacked: w13 [E, 2 inter, hidden] with the rows interleaved
+ * (gate_i, up_i) as pplhip_op_linear_swiglu takes them, w2 [E, hidden, inter_p] with K zero-padded to inter_p = inter rounded up to 64;
+ * wq_bit 8: int8 codes with fp16 row scales scale13 [E, 2 inter] and scale2 [E, hidden]; wq_bit 0: fp16, scales NULL.  workspace: device
+ * memory of pplhip_op_moe_ffn_workspace_bytes bytes, contents irrelevant.  Five launches, no host synchronisation.
+ * pplhip_op_moe_tile_rows: the height of the grouped GEMMs' row tiles for a step of T rows -- 32 while T k <= 32 E, else 128. */
+PPLHIP_API int pplhip_op_moe_route(void* stream, const void* x, const void* gate, int64_t T, int32_t hidden, int32_t num_experts,
+                                   int32_t experts_per_token, int32_t* ids, float* weights, int32_t* counts);
+PPLHIP_API int pplhip_op_moe_ffn(void* stream, const void* x, const void* gate, const void* w13, const void* scale13, const void* w2,
+                                 const void* scale2, int32_t wq_bit, int64_t T, int32_t num_experts, int32_t experts_per_token, int32_t hidden,
+                                 int32_t inter, void* workspace, uint64_t workspace_bytes, void* y, int64_t ldy);
+PPLHIP_API uint64_t pplhip_op_moe_ffn_workspace_bytes(int64_t T, int32_t num_experts, int32_t experts_per_token, int32_t hidden, int32_t inter);
+PPLHIP_API int32_t pplhip_op_moe_tile_rows(int64_t T, int32_t experts_per_token, int32_t num_experts);
+/* The same inside a context: call it after pplhip_init and before any weight is loaded.  Every layer's dense w13 / w2 are released and E
+ * experts of the descriptor's weight format allocated in their place (intermediate_dim is ONE expert's) with the fp16 router matrix, and the
+ * step's routing buffers are sized for max_tokens_per_step; the feed-forward block of every step then runs the five launches above.  A
+ * context that never calls it allocates and launches exactly what it did before.  Tensor names (pplhip_rank_set_tensor / pplhip_rank_load):
+ * layers.L.feed_forward.gate.weight [E, hidden] fp16, layers.L.feed_forward.experts.J.w13.weight / .scale and ...experts.J.w2.weight /
+ * .scale in the dense tensors' container layout; the dense layers.L.feed_forward.w13 / w2 names no longer exist.
+ * pplhip_rank_init_synthetic fills gate and experts from the seed.
+ * PPLHIP_INVALID_VALUE behind a loaded or generated weight or a second call.  All or nothing: on any failure (an allocation included)
+ * the context stays the dense one it was.
+ * PPLHIP_UNSUPPORTED (reason in pplhip_last_error(ctx, -1), nothing changed): more than 64 experts, more than 8 experts per token or more
+ * than there are experts, W4A16 weights, online_i8i8 / online_f8f8 activations, world_size > 1, hidden_dim % 64 != 0, an adapter tensor on
+ * feed_forward.w2 already loaded; afterwards pplhip_lora_set_tensor refuses feed_forward.w2 the same way. */
+PPLHIP_API int pplhip_moe(pplhip_ctx* ctx, int32_t num_experts, int32_t experts_per_token);
+
 /* The direct collectives (csrc/k_comm.hip) as operators, for a context whose ranks all live in this process and run the direct mode
  * (pplhip_comm_mode == 2).  One call runs a SEQUENCE of collectives: every item is enqueued on every local rank from the calling thread,
  * back to back on the ranks' streams with no host synchronisation in between, then every rank is synchronised.  Channel 0 runs on the

@@ -135,6 +135,7 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 //      read / convert / MFMA chains overlap), partial sums added through LDS at the end -- and 4 producers; needs G_ST >= 3;
 // WQ = 8: int8 weights + per-channel scale; WQ = 0: fp16; WQ = 4: int4, group 128.  LDS bytes: gemm_dma_lds_bytes (k_gemm_tiles.h)
 
+// (k_moe.hip moe_gemm_kernel carries a copy of the WL 1 ring, swizzle and fragment reads of this body: a change here is made there too.)
 // BM = 64 (WL 1 only): half-height tile for 16 < M <= 64 -- half the activation bytes per stage and half the MFMAs of a 128-row tile whose
 // upper half would only repeat row M - 1
 template <int WQ, int EPI, int G_ST, int WL, int BM = G_BM>

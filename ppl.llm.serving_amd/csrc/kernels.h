@@ -236,6 +236,24 @@ struct LoraSlot {
 hipError_t launch_lora(hipStream_t s, const LoraTile* tiles, int ntiles, const LoraSlot* slots, const uint16_t* x, int64_t ldx, uint16_t* y,
                        int64_t ldy, int N, int K, uint16_t* t);
 
+// ---- k_moe.hip: mixture-of-experts feed-forward block (Mixtral) -------------------------------------------------------------------
+constexpr int MOE_MAX_EXPERTS = 64, MOE_MAX_TOP_K = 8;   // a router logit per lane of a wave; top-k slots
+// height of the grouped GEMMs' m-tiles for a step of T rows: 32 while the average expert has at most 32 rows (T k <= 32 E), else 128
+int moe_tile_rows(int64_t T, int k, int E);
+// bytes launch_moe_ffn needs at `workspace` for T rows (non-decreasing in T: a buffer sized for the largest step serves every smaller one)
+size_t moe_ffn_workspace_bytes(int64_t T, int E, int k, int hidden, int inter);
+// router alone: ids / weights [T, k] (slots by descending logit, ties to the lower expert; softmax over the k logits), counts [64] += the
+// histogram of ids.  counts_clean false: a one-block kernel zeroes counts first.  gate fp16 [E, hidden]; hidden % 64 == 0
+hipError_t launch_moe_route(hipStream_t s, const uint16_t* x, const uint16_t* gate, int64_t T, int hidden, int E, int k, int32_t* ids,
+                            float* weights, int32_t* counts, bool counts_clean);
+// y[t] = fp16(sum_s p_s . w2_{e_s}(swiglu(w13_{e_s} x[t]))) for T rows of x [T, hidden]; y rows have stride ldy.  Weights are stacked by
+// expert: w13 [E, 2 inter, hidden] with rows interleaved (gate, up) like the dense fused SwiGLU, w2 [E, hidden, inter_p] with K zero-padded to
+// inter_p = inter rounded up to 64; wq_bit 0 (fp16) or 8 (int8 + fp16 row scales scale13 [E, 2 inter], scale2 [E, hidden]).  Five launches,
+// no host synchronisation.  counts_clean: the workspace's expert counts are zero (as a previous call leaves them); false zeroes them first.
+hipError_t launch_moe_ffn(hipStream_t s, const uint16_t* x, const uint16_t* gate, const void* w13, const uint16_t* scale13, const void* w2,
+                          const uint16_t* scale2, int wq_bit, int64_t T, int E, int k, int hidden, int inter, void* workspace, bool counts_clean,
+                          uint16_t* y, int64_t ldy);
+
 // ---- k_comm.hip ------------------------------------------------------------------------------
 // direct (all-links) tensor-parallel collectives over peer-mapped exchange regions; see the file header.
 constexpr int P2P_MAX_RANKS = 8;

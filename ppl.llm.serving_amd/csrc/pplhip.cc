@@ -84,6 +84,7 @@ bool find_tensor(pplhip_ctx* c, Rank& R, const char* name, void** ptr, uint64_t*
     Layer& L = R.layers[l];
     if (!strcmp(rest, "attention_norm.weight")) { *ptr = L.attn_norm; *bytes = (uint64_t)hd * 2; return true; }
     if (!strcmp(rest, "ffn_norm.weight")) { *ptr = L.ffn_norm; *bytes = (uint64_t)hd * 2; return true; }
+    if (c->moe_E && !strncmp(rest, "feed_forward.", 13)) return moe_find_tensor(c, R, L, rest, ptr, bytes, lin_out);   // gate and experts; no dense w13 / w2
     struct { const char* n; Linear* lin; } tab[] = {{"attention.wqkv", &L.wqkv}, {"attention.wo", &L.wo},
                                                       {"feed_forward.w13", &L.w13}, {"feed_forward.w2", &L.w2}};
     for (auto& t : tab) {
@@ -604,10 +605,11 @@ int pplhip_init(const pplhip_model_desc* desc, const pplhip_opts* opts, pplhip_c
 int pplhip_rank_set_tensor(pplhip_ctx* c, int rank, const char* name, const void* data, uint64_t bytes) {
     if (!c || rank < 0 || rank >= (int)c->ranks.size() || !name || !data) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[rank];
+    c->weights_touched = true;
     void* p; uint64_t b;
     Linear* lin = nullptr;
     if (!find_tensor(c, R, name, &p, &b, &lin)) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown tensor ") + name);
-    const char* w13 = strstr(name, "feed_forward.w13.");
+    const char* w13 = strstr(name, ".w13.");   // (feed_forward.w13.* and feed_forward.experts.J.w13.*)
     if (lin && lin->qbit == 8 && c->act_fmt != ACT_FP16 && bytes == (uint64_t)lin->N * lin->K * 2) {
         // online_i8i8 / f8f8 "online" half: an fp16 [N, K] matrix for a 1-byte linear is quantised per output row on the device
         HIPCK(c, rank, hipSetDevice(R.device));
@@ -695,9 +697,10 @@ int pplhip_rank_load(pplhip_ctx* c, int rank, const char* slice_dir) {
 int pplhip_rank_init_synthetic(pplhip_ctx* c, int rank, uint64_t seed) {
     if (!c || rank < 0 || rank >= (int)c->ranks.size()) return PPLHIP_INVALID_VALUE;
     Rank& R = c->ranks[rank];
+    c->weights_touched = true;
     HIPCK(c, rank, hipSetDevice(R.device));
     const int hd = c->d.hidden_dim;
-    const uint32_t st = 1u + (uint32_t)R.global_rank;
+    uint32_t st = 1u + (uint32_t)R.global_rank;   // (the lambdas below read it when they run)
     const float AMP = 0.034641016f;
     auto tid = [](int layer, int slot) { return (uint32_t)((layer + 1) * 32 + slot); };
     hipStream_t s = R.stream;
@@ -729,27 +732,45 @@ int pplhip_rank_init_synthetic(pplhip_ctx* c, int rank, uint64_t seed) {
         HIPCK(c, rank, launch_synth_fill(s, 4, seed, tid(l, 6), 0, 0.f, hd, L.ffn_norm));
         HIPCK(c, rank, lin(L.wqkv, l, 2));
         HIPCK(c, rank, lin(L.wo, l, 4));
-        {   // generated in container order, then row-interleaved like an uploaded tensor
-            Linear tmp = L.w13;
-            HIPCK(c, rank, hipMalloc(&tmp.w, L.w13.w_bytes()));
-            if (L.w13.s_bytes()) HIPCK(c, rank, hipMalloc((void**)&tmp.scale, L.w13.s_bytes()));
+        // w13 is generated in container order, then row-interleaved like an uploaded tensor; w2 contiguous, then copied into zero-padded rows
+        auto ffn_pair = [&](Linear& w13, Linear& w2) -> int {
+            Linear tmp = w13;
+            HIPCK(c, rank, hipMalloc(&tmp.w, w13.w_bytes()));
+            if (w13.s_bytes()) HIPCK(c, rank, hipMalloc((void**)&tmp.scale, w13.s_bytes()));
             HIPCK(c, rank, lin(tmp, l, 7));
-            HIPCK(c, rank, launch_interleave_rows(s, tmp.w, L.w13.w, L.w13.N, (int64_t)(L.w13.w_bytes() / L.w13.N)));
-            if (L.w13.s_bytes()) HIPCK(c, rank, launch_interleave_rows(s, tmp.scale, L.w13.scale, L.w13.N, (int64_t)(L.w13.s_bytes() / L.w13.N)));
+            HIPCK(c, rank, launch_interleave_rows(s, tmp.w, w13.w, w13.N, (int64_t)(w13.w_bytes() / w13.N)));
+            if (w13.s_bytes()) HIPCK(c, rank, launch_interleave_rows(s, tmp.scale, w13.scale, w13.N, (int64_t)(w13.s_bytes() / w13.N)));
             HIPCK(c, rank, hipStreamSynchronize(s));
             hipFree(tmp.w);
             if (tmp.scale) hipFree(tmp.scale);
-        }
-        if (L.w2.Kp == L.w2.K) {
-            HIPCK(c, rank, lin(L.w2, l, 9));
-        } else {  // generated contiguous, then copied into the zero-padded rows
-            Linear tmp = L.w2;
-            HIPCK(c, rank, hipMalloc(&tmp.w, L.w2.w_bytes()));
-            HIPCK(c, rank, lin(tmp, l, 9));  // scale goes straight to L.w2.scale (same pointer)
-            const size_t rb = (size_t)L.w2.elt_bytes(L.w2.K), rbp = (size_t)L.w2.elt_bytes(L.w2.Kp);
-            HIPCK(c, rank, hipMemcpy2DAsync(L.w2.w, rbp, tmp.w, rb, rb, L.w2.N, hipMemcpyDeviceToDevice, s));
-            HIPCK(c, rank, hipStreamSynchronize(s));
-            hipFree(tmp.w);
+            if (w2.Kp == w2.K) {
+                HIPCK(c, rank, lin(w2, l, 9));
+            } else {
+                Linear tmp2 = w2;
+                HIPCK(c, rank, hipMalloc(&tmp2.w, w2.w_bytes()));
+                HIPCK(c, rank, lin(tmp2, l, 9));  // scale goes straight to w2.scale (same pointer)
+                const size_t rb = (size_t)w2.elt_bytes(w2.K), rbp = (size_t)w2.elt_bytes(w2.Kp);
+                HIPCK(c, rank, hipMemcpy2DAsync(w2.w, rbp, tmp2.w, rb, rb, w2.N, hipMemcpyDeviceToDevice, s));
+                HIPCK(c, rank, hipStreamSynchronize(s));
+                hipFree(tmp2.w);
+            }
+            return 0;
+        };
+        if (!c->moe_E) {
+            if (int rc = ffn_pair(L.w13, L.w2)) return rc;
+        } else {   // expert j: the dense pair's tensors drawn from stream 64 (j + 1) + st; the gate like a linear's fp16 weights
+            HIPCK(c, rank, launch_synth_fill(s, 0, seed, tid(l, 13), st, AMP, (uint64_t)c->moe_E * hd, L.moe_gate));
+            const uint32_t st0 = st;
+            for (int j = 0; j < c->moe_E; ++j) {
+                Linear w13 = L.w13, w2 = L.w2;
+                w13.w = (char*)L.w13.w + (uint64_t)j * L.w13.alloc_bytes();
+                w2.w = (char*)L.w2.w + (uint64_t)j * L.w2.alloc_bytes();
+                if (L.w13.scale) { w13.scale = L.w13.scale + (uint64_t)j * L.w13.N; w2.scale = L.w2.scale + (uint64_t)j * L.w2.N; }
+                st = st0 + 64u * (uint32_t)(j + 1);
+                const int rc = ffn_pair(w13, w2);
+                st = st0;
+                if (rc) return rc;
+            }
         }
     }
     HIPCK(c, rank, hipStreamSynchronize(s));
@@ -1192,6 +1213,12 @@ static int layer_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const StepPlan& p
         HIPCK(c, rank, launch_rmsnorm(s, h, R.part + k.t0 * hd, L.ffn_norm, d.norm_eps, k.tn, hd, nullptr, xn, h, a8 ? R.xq : nullptr,
                                       a8 ? R.sx : nullptr, &lane.sl_part, c->act_fmt == ACT_FP8));
     lane.sl_part = SplitSlabs{};
+    if (c->moe_E) {   // route -> bucket -> grouped w13 -> grouped w2 -> combine, straight into part2's rows
+        prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
+        if (int rc = moe_ffn_part(c, rank, lane, L, xn, k.tn, R.part2 + k.t0 * hd)) return rc;
+        prof_end(R, lane, &ev);
+        return 0;
+    }
     prof_begin(c, R, lane, PPLHIP_PROF_GEMM, &ev);
     if (int rc = layer_linear(c, rank, lane, L.w13, xn, k.tn, act, L.w2.Kp, /*swiglu=*/true, a8)) return rc;
     prof_end(R, lane, &ev);

@@ -45,7 +45,8 @@ struct GraphEntry { hipGraphExec_t exec; uint64_t tick; };
 struct Layer {
     uint16_t* attn_norm = nullptr;
     uint16_t* ffn_norm = nullptr;
-    Linear wqkv, wo, w13, w2;
+    Linear wqkv, wo, w13, w2;        // mixture of experts (rt_moe.cc): w13 / w2 are ONE expert's shape over E stacked experts
+    uint16_t* moe_gate = nullptr;    // router matrix fp16 [E, hidden]
 };
 
 // One adapter slot of a rank: per (layer, target) the two factors on the device, zero-padded to rank rp (a multiple of 16) and, for w2's
@@ -383,6 +384,11 @@ struct Rank {
     float* sp_ws = nullptr;                           // shared partial rows [cap_B][H][SP_SPLIT_MAX][D + 2]
     int64_t sp_last[3] = {0, 0, 0};                   // groups, rows in groups, shared tokens of the last run (summed over its chunks)
 
+    // mixture of experts (pplhip_moe, rt_moe.cc): the step's routing buffers and expert rows (k_moe.hip), null in a dense context
+    void* moe_ws = nullptr;
+    bool moe_counts_clean = false;                    // the workspace's expert counts are zero (every launch leaves them so)
+    Linear moe_view;                                  // the expert a tensor name addressed last (moe_find_tensor)
+
     // diagnosis (pplhip_debug_run_dump): residual stream h and the pending row-parallel FFN output after every layer
     uint16_t* dump_dev = nullptr;  // [L+1][2][T, hidden] fp16 (slot 0 = h, slot 1 = pending), allocated for one run
 
@@ -437,6 +443,8 @@ struct pplhip_ctx {
     bool graph_on = false;           // PPLHIP_DECODE_GRAPH=1: replay pure-decode steps as HIP graphs (opt-in, see run_decode_graph)
     int64_t graph_max_batch = 64;    // above this a step is seconds of GPU work per thousand launches: nothing to gain
     int H = 0, Hkv = 0, D = 0, inter = 0, vocab_local = 0;
+    int moe_E = 0, moe_k = 0;        // pplhip_moe: experts and experts per token (0: a dense model)
+    bool weights_touched = false;    // a tensor was set, loaded or generated: pplhip_moe comes too late
     std::vector<Rank> ranks;
     std::string err;
 };
@@ -493,6 +501,9 @@ const Rank::SpChunk* shared_prefix_chunk(const pplhip_ctx* c, const Rank& R, con
 // the chunk's decode attention through the shared path: own part, shared part, merge
 int shared_prefix_attention(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const Rank::SpChunk& sc, int split, int threads);
 void shared_prefix_release(Rank& R);
+// rt_moe.cc
+bool moe_find_tensor(pplhip_ctx* c, Rank& R, Layer& L, const char* rest, void** ptr, uint64_t* bytes, Linear** lin);
+int moe_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const Layer& L, const uint16_t* xn, int64_t tn, uint16_t* out);
 // rt_postproc.cc
 int sample_row_list(const int32_t* top_k, const float* min_p, const float* typical_p, int B, int32_t* rows, int* n_trunc);
 int top_logprobs_row_list(const int32_t* num_logprobs, int B, int32_t* rows);

@@ -102,6 +102,7 @@ int pplhip_lora_set_tensor(pplhip_ctx* c, int rank, int slot, const char* name, 
         if (!strcmp(rest + nl, "lora_b")) { target = i; is_b = 1; }
     }
     if (target < 0) return fail(c, rank, PPLHIP_NOT_FOUND, std::string("unknown adapter tensor ") + name);
+    if (c->moe_E && target == LORA_W2) return fail(c, rank, PPLHIP_UNSUPPORTED, std::string(name) + ": adapters on feed_forward.w2 are not supported on a mixture-of-experts model");
     const Linear& lin = *tab[target].lin;
     if (lin.Kp % 32 || lin.N % 16) return fail(c, rank, PPLHIP_UNSUPPORTED, std::string(name) + ": the adapter kernels need K % 32 == 0 and N % 16 == 0");
     const uint64_t want = is_b ? (uint64_t)lin.N * r * 2 : (uint64_t)r * lin.K * 2;

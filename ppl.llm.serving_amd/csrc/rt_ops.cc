@@ -164,6 +164,29 @@ int pplhip_op_lora(void* stream, const void* x, int64_t ldx, void* y, int64_t ld
     return op_rc(e);
 }
 
+// mixture-of-experts block (k_moe.hip): the router alone, and the whole block on stacked expert weights
+int pplhip_op_moe_route(void* stream, const void* x, const void* gate, int64_t T, int32_t hidden, int32_t num_experts, int32_t experts_per_token,
+                        int32_t* ids, float* weights, int32_t* counts) {
+    return op_rc(launch_moe_route((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)gate, T, hidden, num_experts, experts_per_token, ids,
+                                  weights, counts, /*counts_clean=*/false));
+}
+
+uint64_t pplhip_op_moe_ffn_workspace_bytes(int64_t T, int32_t num_experts, int32_t experts_per_token, int32_t hidden, int32_t inter) {
+    return moe_ffn_workspace_bytes(T, num_experts, experts_per_token, hidden, inter);
+}
+
+int32_t pplhip_op_moe_tile_rows(int64_t T, int32_t experts_per_token, int32_t num_experts) { return moe_tile_rows(T, experts_per_token, num_experts); }
+
+int pplhip_op_moe_ffn(void* stream, const void* x, const void* gate, const void* w13, const void* scale13, const void* w2, const void* scale2,
+                      int32_t wq_bit, int64_t T, int32_t num_experts, int32_t experts_per_token, int32_t hidden, int32_t inter, void* workspace,
+                      uint64_t workspace_bytes, void* y, int64_t ldy) {
+    if (T < 0 || num_experts < 1 || experts_per_token < 1 || hidden < 1 || inter < 1 || ldy < hidden) return PPLHIP_INVALID_VALUE;
+    if (workspace_bytes < moe_ffn_workspace_bytes(T, num_experts, experts_per_token, hidden, inter)) return PPLHIP_INVALID_VALUE;
+    return op_rc(launch_moe_ffn((hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)gate, w13, (const uint16_t*)scale13, w2,
+                                (const uint16_t*)scale2, wq_bit, T, num_experts, experts_per_token, hidden, inter, workspace,
+                                /*counts_clean=*/false, (uint16_t*)y, ldy));
+}
+
 int pplhip_op_silu_mul(void* stream, const void* gate_up, int64_t T, int32_t inter, void* out) {
     return op_rc(launch_silu_mul((hipStream_t)stream, (const uint16_t*)gate_up, T, inter, (uint16_t*)out));
 }

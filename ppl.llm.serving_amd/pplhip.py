@@ -190,6 +190,7 @@ SYMBOLS = [
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_shared_prefix_groups", "pplhip_op_attention_shared", "pplhip_op_attention_shared_workspace_bytes",
     "pplhip_shared_prefix", "pplhip_shared_prefix_info",
+    "pplhip_moe", "pplhip_op_moe_route", "pplhip_op_moe_ffn", "pplhip_op_moe_ffn_workspace_bytes", "pplhip_op_moe_tile_rows",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
 
@@ -314,6 +315,14 @@ def lib():
             L.pplhip_op_attention_shared_workspace_bytes.restype = u64
             L.pplhip_shared_prefix.argtypes = [vp, i32, i64]
             L.pplhip_shared_prefix_info.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        if hasattr(L, "pplhip_moe"):   # (PPLHIP_LIB may name a build from before the mixture-of-experts block)
+            L.pplhip_moe.argtypes = [vp, i32, i32]
+            L.pplhip_op_moe_route.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]
+            L.pplhip_op_moe_ffn.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp, u64, vp, i64]
+            L.pplhip_op_moe_ffn_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+            L.pplhip_op_moe_ffn_workspace_bytes.restype = u64
+            L.pplhip_op_moe_tile_rows.argtypes = [i64, i32, i32]
+            L.pplhip_op_moe_tile_rows.restype = i32
         # (the row-kernel test entries: PPLHIP_LIB may name a build from before them, as above)
         if hasattr(L, "pplhip_op_rmsnorm_form"):
             L.pplhip_op_rmsnorm_form.argtypes = [i64, i32, i32, i32, C.c_char_p, i32]
@@ -687,6 +696,10 @@ class Context:
     def shared_prefix(self, min_rows, min_tokens):
         """shared-prefix decode attention on (min_rows > 0) or off (0)"""
         self._ck(lib().pplhip_shared_prefix(self.h, min_rows, min_tokens), -1, "shared_prefix")
+
+    def moe(self, num_experts, experts_per_token):
+        """a mixture-of-experts model: call it before any weight is loaded (pplhip_moe)"""
+        self._ck(lib().pplhip_moe(self.h, num_experts, experts_per_token), -1, "moe")
 
     def shared_prefix_info(self, rank):
         """(groups, rows in groups, shared tokens) of the rank's last run"""

@@ -378,6 +378,13 @@ RetCode HipResourceManager::Init(const ModelConfig& mc, const ResourceConfig& rc
         LOG(ERROR) << "pplhip_init failed: " << GetRetCodeStr(FromPplHipStatus(st));
         return FromPplHipStatus(st);
     }
+    if (mc.num_experts > 0) {   // a mixture-of-experts model: before any weight is loaded (InitRank)
+        const int ms = pplhip_moe(ctx, mc.num_experts, mc.experts_per_token);
+        if (ms) {
+            LOG(ERROR) << "pplhip_moe(" << mc.num_experts << ", " << mc.experts_per_token << ") failed: " << pplhip_last_error(ctx, -1);
+            return FromPplHipStatus(ms);
+        }
+    }
     tensor_parallel_size = (uint32_t)tp;
     items.resize(tp);
     runtimes.resize(tp);

@@ -63,6 +63,8 @@ bool ParseModelConfigFromString(const std::string& text, ModelConfig* mc) {
     mc->max_position = (int32_t)doc.GetInt("max_position", mc->max_position);
     mc->weight_quant_bit = (int32_t)doc.GetInt("weight_quant_bit", mc->weight_quant_bit);
     mc->weight_quant_group = (int32_t)doc.GetInt("weight_quant_group", mc->weight_quant_group);
+    mc->num_experts = (int32_t)doc.GetInt("num_experts", mc->num_experts);
+    mc->experts_per_token = (int32_t)doc.GetInt("experts_per_token", mc->experts_per_token);
     return true;
 }
 

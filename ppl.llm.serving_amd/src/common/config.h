@@ -95,6 +95,8 @@ struct ModelConfig final {
     int32_t max_position = 8192;
     int32_t weight_quant_bit = 0;      // 0 / 8 (W8A16) / 4 (W4A16)
     int32_t weight_quant_group = 128;  // W4A16 group size along K
+    int32_t num_experts = 0;           // mixture of experts (Mixtral): experts per layer, 0 = a dense model; intermediate_dim is one expert's
+    int32_t experts_per_token = 0;     // ... and how many of them a token is routed to
 };
 
 bool ParseModelConfig(const std::string& model_param_path, ModelConfig* model_config);

@@ -13,6 +13,11 @@ quantise each slice:
             two nibbles per byte, low nibble = even k
 RoPE: HF checkpoints use the half-split pairing this backend implements, so q/k rows are taken as they are.
 
+A Mixtral checkpoint (model_type "mixtral"; tensor-parallel size 1, fp16 or w8a16) is a mixture-of-experts model: params.json gets
+num_experts / experts_per_token (intermediate_dim is one expert's), every layer the fp16 router `layers.L.feed_forward.gate.weight` and
+per expert J `layers.L.feed_forward.experts.J.w13` (HF w1 = gate rows, then w3 = up rows) and `...experts.J.w2`, quantised like the dense
+tensors.  Both HF layouts are read: per-expert `block_sparse_moe.experts.J.w1/w2/w3` and the stacked `mlp.experts.gate_up_proj / down_proj`.
+
     python export_hf_llama.py --model-dir /path/to/hf_llama --out /path/to/model --tensor-parallel-size 2 --quant w8a16
 """
 import argparse
@@ -97,6 +102,9 @@ def convert(sd, cfg, tp, quant, group):
     if H % tp or Hkv % tp or inter % tp or V % tp:
         raise ValueError("heads / kv heads / intermediate size / vocab must be divisible by the tensor-parallel size")
     h, hk, it, vl = H // tp, Hkv // tp, inter // tp, V // tp
+    moe = cfg.get("num_local_experts", 0) if cfg.get("model_type") == "mixtral" else 0
+    if moe and (tp != 1 or quant == "w4a16"):
+        raise ValueError("a mixture-of-experts model is exported at tensor-parallel size 1, fp16 or w8a16")
     f16 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float16)
     lm_head = sd.get("lm_head.weight", sd["model.embed_tokens.weight"])  # tied embeddings
     slices = []
@@ -120,6 +128,18 @@ def convert(sd, cfg, tp, quant, group):
             put(f"layers.{l}.attention.wqkv", np.concatenate([q[r * h * D:(r + 1) * h * D], k[r * hk * D:(r + 1) * hk * D],
                                                                v[r * hk * D:(r + 1) * hk * D]], 0))
             put(f"layers.{l}.attention.wo", sd[p + "self_attn.o_proj.weight"][:, r * h * D:(r + 1) * h * D])
+            if moe:
+                old = p + "block_sparse_moe.gate.weight" in sd
+                out[f"layers.{l}.feed_forward.gate.weight"] = f16(sd[p + ("block_sparse_moe" if old else "mlp") + ".gate.weight"])
+                for j in range(moe):
+                    if old:
+                        e = p + f"block_sparse_moe.experts.{j}."
+                        w13, w2 = np.concatenate([sd[e + "w1.weight"], sd[e + "w3.weight"]], 0), sd[e + "w2.weight"]
+                    else:   # stacked: gate_up_proj [E, 2 inter, hidden] (gate rows, then up rows), down_proj [E, hidden, inter]
+                        w13, w2 = sd[p + "mlp.experts.gate_up_proj"][j], sd[p + "mlp.experts.down_proj"][j]
+                    put(f"layers.{l}.feed_forward.experts.{j}.w13", w13)
+                    put(f"layers.{l}.feed_forward.experts.{j}.w2", w2)
+                continue
             put(f"layers.{l}.feed_forward.w13", np.concatenate([sd[p + "mlp.gate_proj.weight"][r * it:(r + 1) * it],
                                                                   sd[p + "mlp.up_proj.weight"][r * it:(r + 1) * it]], 0))
             put(f"layers.{l}.feed_forward.w2", sd[p + "mlp.down_proj.weight"][:, r * it:(r + 1) * it])
@@ -144,6 +164,8 @@ def params_json(cfg, args):
          "weight_quant_bit": {"none": 0, "w8a16": 8, "w4a16": 4}[args.quant], "weight_quant_group": args.quant_group}
     if args.cache_mode == 1:
         p["page_size"] = args.page_size
+    if cfg.get("model_type") == "mixtral":
+        p["num_experts"], p["experts_per_token"] = cfg["num_local_experts"], cfg["num_experts_per_tok"]
     return p
 
 
@@ -163,8 +185,8 @@ def main(argv=None):
     ap.add_argument("--page-size", type=int, default=16)
     args = ap.parse_args(argv)
     cfg = json.load(open(os.path.join(args.model_dir, "config.json")))
-    if cfg.get("model_type", "llama") != "llama":
-        sys.exit(f"model_type {cfg.get('model_type')} is not LLaMA")
+    if cfg.get("model_type", "llama") not in ("llama", "mixtral"):
+        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA nor Mixtral")
     sd = load_state_dict(args.model_dir)
     slices = convert(sd, cfg, args.tensor_parallel_size, args.quant, args.quant_group)
     os.makedirs(args.out, exist_ok=True)
