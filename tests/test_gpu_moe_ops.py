@@ -10,6 +10,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 # (T, E, k, hidden, inter, biased gate); T "lo" / "hi": either side of the short / tall tile threshold pplhip_op_moe_tile_rows reports
+# (tied logits, k = 1, the bucket kernel's second and third pass, hidden 64 / 192 / 320, row counts on a tile boundary and stale workspace
+# state are in tests/test_gpu_moe_exact.py, bit for bit on the exactly summable operands of tests/moe_exact.py)
 SHAPES = [(1, 8, 2, 128, 64, False), (5, 4, 4, 128, 160, False), (37, 8, 2, 256, 192, False), (200, 4, 2, 128, 64, True),
           (64, 64, 8, 128, 64, False), ("lo", 8, 2, 128, 64, False), ("hi", 8, 2, 128, 64, False)]
 
