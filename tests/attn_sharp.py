@@ -23,6 +23,10 @@ group, so that a small integer multiple of the needle amplitude round-trips exac
 needle whose key row would not round-trip is refused (see _f1_prefill); every V row and F2's K rows take the product's own scale rule
 (8 significant bits, not a power of two).  Every code x scale is an fp16 number, so the oracle runs on the fp16 slab the int4 slab
 stands for, with exact operands.
+
+Shared-prefix decode attention (pplhip_op_attention_shared) has its cases at the end of the module: SharedCase (requests whose page
+tables share leading pages, the shared rows written into the slab once), the host mirrors of the shared launch's splits, wave strides
+and tiles, f1_shared / f2_shared, and the float64 reference of the three launches with that path's own mutations (SHARED_MUTANTS).
 """
 import ctypes as C
 import math
@@ -254,22 +258,26 @@ class Case:
         self.qkv = np.zeros((self.T, (H + 2 * Hkv) * D), dtype=np.float16)
         self.Kd, self.Vd = [], []
 
-    def _put(self, b, K, V):
-        """writes request b's rows into the slab; returns their dequantised values (float32: fp16 numbers in every format).
-        int4: F1's K rows take power-of-two scales and must round-trip exactly; V and F2's K take the product's scale rule"""
-        H, Hkv, D = self.H, self.Hkv, self.D
-        sl = self.slots(b, np.arange(self.kvlen[b]))
+    def _put_at(self, sl, K, V, who):
+        """writes rows K, V ([Hkv, len(sl), D]) into slots sl of the slab; returns their dequantised values (float32: fp16 numbers in
+        every format).  int4: F1's K rows take power-of-two scales and must round-trip exactly; V and F2's K take the product's rule"""
         deq = []
         for kv, rows in ((0, K), (1, V)):
             exact = self.fmt == "i4" and kv == 0 and self.family is None
             c, sc = encode(self.fmt, rows, pow2=exact)
             if exact:
                 bad = np.argwhere((decode(self.fmt, c, sc) != rows).any(-1))
-                assert len(bad) == 0, f"{self.name}: request {b}: K rows (kv head, key) {bad[:4].tolist()} do not round-trip through int4"
+                assert len(bad) == 0, f"{self.name}: {who}: K rows (kv head, key) {bad[:4].tolist()} do not round-trip through int4"
             self.cv[self.layer, kv][:, sl] = c
             if self.sv is not None:
                 self.sv[self.layer, kv][:, sl] = sc
             deq.append(decode(self.fmt, c, sc).astype(np.float32))
+        return deq
+
+    def _put(self, b, K, V):
+        """writes request b's rows into the slab (_put_at) and its new rows into the step's qkv; returns the dequantised rows"""
+        H, Hkv, D = self.H, self.Hkv, self.D
+        deq = self._put_at(self.slots(b, np.arange(self.kvlen[b])), K, V, f"request {b}")
         r0, r1 = self.seq_starts[b], self.seq_starts[b + 1]
         pos = np.arange(self.start_pos[b], self.kvlen[b])
         # the step's own K / V rows equal the slab rows
@@ -725,7 +733,10 @@ def _softmax_out(s, V, chunks=None, mut=None):
 
 def ref64(case, mut=None, edge=None):
     """float64 attention over the slab as the kernels should read it; `mut` (one of MUTANTS) reads it wrongly, `edge` the key the
-    slot mutants move.  Returns None when the mutation does not apply to this case."""
+    slot mutants move.  Returns None when the mutation does not apply to this case.  A SharedCase is computed as the three launches
+    of the shared path form it, under that path's own mutants (SHARED_MUTANTS)."""
+    if isinstance(case, SharedCase):
+        return _ref64_shared(case, mut)
     D, H, grp = case.D, case.H, case.grp
     sm = 1.0 / math.sqrt(D) * (1.01 if mut == "scale*1.01" else 0.99 if mut == "scale*0.99" else 1.0)
     if mut == "wrong_kv_head" and case.Hkv == 1:
@@ -988,3 +999,554 @@ def make(spec, family=None):
     if stream:
         return f1_stream(c)
     return f1(c) if family is None else f2(c, family)
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------
+# shared-prefix decode attention (pplhip_op_attention_shared: k_attn_decode_shared.hip, rt_shared_prefix.cc)
+# -------------------------------------------------------------------------------------------------------------------------------------
+SH_SUB, SH_WAVES, SP_SPLIT_MAX = 16, 4, 4   # keys per sub-tile, waves per block (k_attn_decode_shared.hip); rt_internal.h
+
+
+def shared_split_ranges(P, split):
+    """[s_beg, s_end) sub-tile ranges of the shared splits: per = ceil(nsub / split) sub-tiles of 16 keys each; a range with
+    s_beg >= s_end is empty (its partial row stays m = -1e30, l = 0)"""
+    nsub = P // SH_SUB
+    per = -(-nsub // split)
+    return [(s * per, min(s * per + per, nsub)) for s in range(split)]
+
+
+def shared_wave_steps(s_beg, s_end):
+    """{sub-tile: (wave, step, register buffer)}: wave w takes sub-tile s_beg + w + 4 k at its step k, in buffer k % 2"""
+    return {s: ((s - s_beg) % SH_WAVES, (s - s_beg) // SH_WAVES, (s - s_beg) // SH_WAVES % 2) for s in range(s_beg, s_end)}
+
+
+def shared_tiles(group, group_tokens, grp):
+    """mirror of shared_build_tiles: a group's rows in batch order, 16 // grp requests per tile, a tile opened by the group's first
+    row without one; tiles sorted by group (stable).  lead: the tile's last member; cols: the request of each of the 16 columns
+    (-1: padding)"""
+    per = 16 // grp
+    tiles, open_ = [], {}
+    for b, g in enumerate(group):
+        g = int(g)
+        if g < 0:
+            continue
+        if g not in open_:
+            open_[g] = len(tiles)
+            tiles.append(dict(g=g, tokens=int(group_tokens[g]), rows=[]))
+        t = tiles[open_[g]]
+        t["rows"].append(b)
+        if len(t["rows"]) == per:
+            del open_[g]
+    tiles.sort(key=lambda t: t["g"])
+    for t in tiles:
+        t["lead"] = t["rows"][-1]
+        t["cols"] = [r for r in t["rows"] for _ in range(grp)] + [-1] * (16 - len(t["rows"]) * grp)
+        t["pad"] = t["cols"].count(-1)
+    return tiles
+
+
+def own_chunks(n_own, own_split, gqa):
+    """[beg, end) ranges of the own launch over the SHIFTED positions [0, n_own): own_split is at least 2, the grouped-query kernel
+    rounds a split to whole 128-key strips"""
+    return split_chunks(n_own, max(own_split, 2), gqa)
+
+
+class SharedCase(Case):
+    """one pplhip_op_attention_shared launch: decode rows only, paged.  groups: P of every prefix group (a multiple of 16 and of the
+    page size), numbered by first member row; rows: (group or -1, own keys) per row.  A group's members all carry the same leading
+    P / page_size page ids; the shared rows (self.KS[g], self.VS[g]: [Hkv, P, D]) go into the slab once.  self.K[b], self.V[b] hold
+    a row's OWN keys [Hkv, own_b, D] (key P + j at index j).  group / group_tokens are what the operator takes: written down here."""
+
+    def __init__(self, fmt, H, Hkv, D, groups, rows, page_size=16, layout=3, shared_split=1, own_split=2, seed=0, name="", L=2, layer=1):
+        gid = np.array([g for g, _ in rows], dtype=np.int32)
+        own = np.array([n for _, n in rows], dtype=np.int64)
+        gt = np.array(groups, dtype=np.int64)
+        P = np.where(gid >= 0, gt[np.maximum(gid, 0)], 0).astype(np.int64)
+        assert (own >= 1).all() and all(p >= 16 and p % 16 == 0 and p % page_size == 0 for p in groups)
+        first = [gid.tolist().index(g) for g in range(len(groups))]
+        assert first == sorted(first), "groups are numbered by their first row"
+        super().__init__(fmt, H, Hkv, D, [1] * len(rows), P + own - 1, nb=len(rows), layout=layout, mode=1, page_size=page_size, L=L,
+                         layer=layer, split=max(own_split, 2), seed=seed, name=name)
+        self.group, self.group_tokens, self.P, self.own = gid, gt, P, own
+        self.shared_split, self.own_split = shared_split, max(own_split, 2)
+        ps = page_size
+        npg = (self.kvlen + ps - 1) // ps
+        own_pg = npg - P // ps
+        n_pages = int(gt.sum()) // ps + int(own_pg.sum()) + 3
+        order = self.rng.permutation(n_pages)
+        self.spare_page = int(order[-1])
+        k = 0
+        gpages = []
+        for p in groups:
+            gpages.append(order[k:k + p // ps])
+            k += p // ps
+        self.cache_idx = np.full((self.B, self.max_pages), self.spare_page, dtype=np.int64)
+        for b in range(self.B):
+            if gid[b] >= 0:
+                self.cache_idx[b, :P[b] // ps] = gpages[gid[b]]
+            self.cache_idx[b, P[b] // ps:npg[b]] = order[k:k + own_pg[b]]
+            k += own_pg[b]
+        self.N = n_pages * ps
+        self.members = [[b for b in range(self.B) if gid[b] == g] for g in range(len(groups))]
+        loose = [b for b in range(self.B) if gid[b] < 0]
+        self.rank = [self.members[gid[b]].index(b) if gid[b] >= 0 else loose.index(b) for b in range(self.B)]
+        self.tiles = shared_tiles(gid, gt, self.grp)
+        self.tile_of = {b: (i, t["rows"].index(b)) for i, t in enumerate(self.tiles) for b in t["rows"]}
+        self.KS = [np.zeros((Hkv, int(p), D), dtype=np.float32) for p in groups]
+        self.VS = [np.zeros((Hkv, int(p), D), dtype=np.float32) for p in groups]
+        self.K = [np.zeros((Hkv, int(n), D), dtype=np.float32) for n in own]
+        self.V = [np.zeros((Hkv, int(n), D), dtype=np.float32) for n in own]
+
+    def krow(self, b, hk, p):
+        """the K row (a view) of key p of request b: a shared row below P"""
+        P = int(self.P[b])
+        return self.KS[self.group[b]][hk, p] if p < P else self.K[b][hk, p - P]
+
+    def finish(self):
+        self._alloc()
+        H, Hkv, D = self.H, self.Hkv, self.D
+        shared = [self._put_at(self.slots(m[0], np.arange(int(p))), self.KS[g], self.VS[g], f"group {g}")
+                  for g, (m, p) in enumerate(zip(self.members, self.group_tokens))]
+        for b in range(self.B):
+            own = self._put_at(self.slots(b, np.arange(int(self.P[b]), int(self.kvlen[b]))), self.K[b], self.V[b], f"request {b}")
+            g = self.group[b]
+            kd, vd = own if g < 0 else [np.concatenate([s, o], axis=1) for s, o in zip(shared[g], own)]
+            self.qkv[b, H * D:(H + Hkv) * D] = kd[:, -1].reshape(-1)   # the current token's K / V rows equal the slab rows
+            self.qkv[b, (H + Hkv) * D:] = vd[:, -1].reshape(-1)
+            self.Kd.append(kd)
+            self.Vd.append(vd)
+        self.K = self.V = self.KS = self.VS = None
+        self._set_q()
+        return self
+
+    def own_chunks(self, b):
+        """the own launch's split ranges of request b as key positions (>= P)"""
+        P = int(self.P[b])
+        return [(P + beg, P + end) for beg, end in own_chunks(int(self.own[b]), self.own_split, gqa_form(self.fmt, self.H, self.Hkv, self.D))]
+
+    def shared_chunks(self, b):
+        """the non-empty shared split ranges of request b as key positions (< P)"""
+        return [(SH_SUB * s0, SH_SUB * s1) for s0, s1 in shared_split_ranges(int(self.P[b]), self.shared_split) if s0 < s1]
+
+    def chunks(self, b, i):
+        """every partial row the merge combines for request b"""
+        return self.shared_chunks(b) + self.own_chunks(b)
+
+
+def shared_edge_positions(P, split, page_size):
+    """(kind, key) pairs of the shared part that the F1 winners must reach, from the mirrors above; both sides of every split start
+    come first (a group of two members has few winners to place)"""
+    out = [("first", 0), ("last", P - 1)]
+    for s0, s1 in shared_split_ranges(P, split):
+        if 0 < s0 < s1:
+            out += [("split-", SH_SUB * s0 - 1), ("split+", SH_SUB * s0)]
+    if P > SH_SUB:
+        out += [("subtile-", SH_SUB - 1), ("subtile+", SH_SUB)]
+    if P > page_size:
+        out += [("page-", page_size - 1), ("page+", page_size)]
+    for s0, s1 in shared_split_ranges(P, split):
+        if s0 >= s1:
+            continue
+        if s1 - s0 > SH_WAVES:
+            out += [("stride-", SH_SUB * (s0 + SH_WAVES) - 1), ("stride+", SH_SUB * (s0 + SH_WAVES))]
+            out.append(("buffer1", SH_SUB * min(s0 + SH_WAVES + 1, s1 - 1) + 7))
+        if s1 - s0 > 2 * SH_WAVES:
+            out.append(("buffer0again", SH_SUB * min(s0 + 2 * SH_WAVES + 2, s1 - 1) + 9))
+        out.append(("split_last", SH_SUB * (s1 - 1) + 3))
+    return out
+
+
+def shared_kinds(case, b, p):
+    """the edge kinds key p of request b stands on (independently of shared_edge_positions: from the split / wave / chunk mirrors)"""
+    P, n, ps = int(case.P[b]), int(case.kvlen[b]), case.page_size
+    kinds = set()
+    if p == n - 1:
+        kinds.add("current")
+    if p >= P:
+        if P and p == P:
+            kinds.add("own_first")
+        for beg, _ in case.own_chunks(b)[1:]:
+            kinds |= {"own_split-"} if p == beg - 1 else ({"own_split+"} if p == beg else set())
+        return kinds
+    kinds |= {"first"} if p == 0 else set()
+    kinds |= {"last"} if p == P - 1 else set()
+    s = p // SH_SUB
+    for tag, edge in (("subtile", SH_SUB), ("page", ps)):
+        if p % edge == edge - 1 and p + 1 < P:
+            kinds.add(tag + "-")
+        if p % edge == 0 and p > 0:
+            kinds.add(tag + "+")
+    for s0, s1 in shared_split_ranges(P, case.shared_split):
+        if not s0 <= s < s1:
+            if s == s0 - 1 and p % SH_SUB == SH_SUB - 1 and s0 < s1:
+                kinds.add("split-")
+            continue
+        if s == s0 and s0 > 0 and p % SH_SUB == 0:
+            kinds.add("split+")
+        wave, step, buf = shared_wave_steps(s0, s1)[s]
+        if step == 1 and wave == 0 and p % SH_SUB == 0:
+            kinds.add("stride+")
+        if step == 0 and wave == SH_WAVES - 1 and p % SH_SUB == SH_SUB - 1 and s + 1 < s1:
+            kinds.add("stride-")
+        if step >= 1 and buf == 1:
+            kinds.add("buffer1")
+        if step >= 2 and buf == 0:
+            kinds.add("buffer0again")
+        if s == s1 - 1:
+            kinds.add("split_last")   # (every prefetch from here on is clamped to this sub-tile)
+    return kinds
+
+
+SHARED_KINDS = ["first", "last", "own_first", "current", "subtile-", "subtile+", "page-", "page+", "split-", "split+", "stride-", "stride+",
+                "buffer1", "buffer0again", "split_last", "own_split-", "own_split+"]
+
+
+def f1_shared(case):
+    """F1 on a SharedCase.  Direction of (request, head): row `rank in the group` of the head's disjoint Hadamard set, so the columns
+    of one tile and KV head all differ.  Every (group, head, direction) has ONE shared needle of multiplier 2; the row's own part
+    holds a needle of the same direction of multiplier 1 (the shared key wins, the own one is the decoy) or 3 (the other way round),
+    alternating over (rank + head).  The own keys of a tile's lead row carry a multiplier-5 needle in the direction of the tile's
+    first request: invisible unless the shared range overruns P through the lead's table."""
+    Hd, a = hadamard(case.D), alpha_of(case.D)
+    for g in range(len(case.group_tokens)):
+        case.VS[g][:] = _f1_values(case, int(case.group_tokens[g]))
+    for b in range(case.B):
+        case.V[b][:] = _f1_values(case, int(case.own[b]))
+    gqa = gqa_form(case.fmt, case.H, case.Hkv, case.D)
+    strides = [s for s in case.edge_strides()]
+    spos = [[p for _, p in shared_edge_positions(int(P), case.shared_split, case.page_size)] for P in case.group_tokens]
+    sh_needle = {}
+    ks = [0] * len(spos)   # shared winners take successive edge positions, decoys walk the list from its end
+    kd = [0] * len(spos)
+    ko = 0
+    for b in range(case.B):
+        g, P, n, r = int(case.group[b]), int(case.P[b]), int(case.kvlen[b]), case.rank[b]
+        own = n - P
+        rel = {0, own - 1}
+        for beg, _ in own_chunks(own, case.own_split, gqa)[1:]:
+            rel |= {beg - 1, beg}
+        for s in strides:
+            rel |= {s - 1, s} if s < own else set()
+        opos = sorted(rel)
+        for hq in range(case.H):
+            hk = hq // case.grp
+            ds = dirs_of(case, hq)
+            d = ds[r % len(ds)]
+            case.Q[b, hq] = Hd[d]
+            shared_wins = g >= 0 and (r + hq) % 2 == 0
+            if g >= 0:
+                if (g, hq, d) not in sh_needle:
+                    if shared_wins:
+                        p = spos[g][ks[g] % len(spos[g])]
+                        ks[g] += 1
+                    else:
+                        kd[g] += 1
+                        p = spos[g][-kd[g] % len(spos[g])]
+                    sh_needle[g, hq, d] = p
+                    case.KS[g][hk, p] += 2 * a * Hd[d]
+                case.needles_b[b].add(sh_needle[g, hq, d])
+            p = opos[ko % len(opos)]
+            ko += 1
+            case.K[b][hk, p] += (1 if shared_wins else 3) * a * Hd[d]
+            case.needles_b[b].add(P + p)
+    for t in case.tiles:
+        if len(t["rows"]) < 2:
+            continue
+        lead, head = t["lead"], t["rows"][0]
+        for hq in range(case.H):
+            ds = dirs_of(case, hq)
+            assert ds[case.rank[head] % len(ds)] != ds[case.rank[lead] % len(ds)]
+            case.K[lead][hq // case.grp, min(3, int(case.own[lead]) - 1)] += 5 * a * Hd[ds[case.rank[head] % len(ds)]]
+    return case.finish()
+
+
+# what the three launches read, and the shared path's own ways of being wrong
+SHARED_MUTANTS = ["sh_short", "own_recount", "own_overshift", "other_table", "col_neighbour", "tile2_drop", "sh_split_drop", "merge_nomax",
+                  "sh_drop", "own_drop", "sh_wrong_kv_head", "sh_v_scale", "sh_scale*1.01", "sh_overrun"]
+# sh_short: the shared range one sub-tile short; own_recount: the last shared sub-tile also counted by the own part; own_overshift: the
+# own table shifted one page too far; other_table: the shared pages read through a row outside the group; col_neighbour: a tile's
+# columns bound to the next request of the tile; tile2_drop: a group's second tile never computed; sh_split_drop: the last non-empty
+# shared split dropped; merge_nomax: the two parts merged without the max rescale; sh_drop / own_drop: a part dropped;
+# sh_wrong_kv_head, sh_v_scale (int8 group scales of V shifted), sh_scale*1.01: in the shared part only; sh_overrun: the shared range
+# one sub-tile past P, through the lead's table.
+SHARED_F1_MUTANTS = ["sh_short", "sh_overrun", "other_table", "col_neighbour", "tile2_drop", "sh_wrong_kv_head", "own_overshift"]
+# the mutants that change which keys are visible: each must move an F1 winner (own_recount leaves a gather unchanged: F2 alone)
+APPLIES["shared"] = set(SHARED_MUTANTS)
+
+
+def _shared_segments(case, b, hk, mut):
+    """the partial rows of (request b, kv head hk) as the launches form them: [(part, slots, q row, kv head, scale factor, V scales
+    shifted)], part 0 = own, 1 = shared.  (Whether a mutation applies to the case at all: _shared_applies.)"""
+    ps, P, n, g = case.page_size, int(case.P[b]), int(case.kvlen[b]), int(case.group[b])
+
+    def through(row, pos):   # slots of key positions through a row's page table; past the table: the spare page
+        pg = pos // ps
+        page = np.where(pg < case.max_pages, case.cache_idx[row, np.minimum(pg, case.max_pages - 1)], case.spare_page)
+        return page * ps + pos % ps
+
+    segs = []
+    if mut != "own_drop" or g < 0:
+        chunks = case.own_chunks(b)
+        for k, (beg, end) in enumerate(chunks):
+            if k == 0 and mut == "own_recount" and g >= 0:
+                beg -= SH_SUB
+            pos = np.arange(beg, end)
+            if mut == "own_overshift" and g >= 0:
+                pos = pos + ps
+            segs.append((0, through(b, pos), b, hk, 1.0, False))
+    if g < 0 or mut == "sh_drop":
+        return segs
+    ti, j = case.tile_of[b]
+    tile = case.tiles[ti]
+    if mut == "tile2_drop" and [t["g"] for t in case.tiles[:ti]].count(g) == 1:
+        return segs
+    lead, qrow = tile["lead"], b
+    if mut == "other_table":
+        others = [r for r in range(case.B) if case.group[r] != g]
+        lead = next((r for r in others if case.group[r] >= 0), others[0])
+    if mut == "col_neighbour":
+        qrow = tile["rows"][(j + 1) % len(tile["rows"])]
+    hr = (hk + 1) % case.Hkv if mut == "sh_wrong_kv_head" else hk
+    ranges = [(s0, s1) for s0, s1 in shared_split_ranges(P, case.shared_split) if s0 < s1]
+    for k, (s0, s1) in enumerate(ranges):
+        last = k == len(ranges) - 1
+        if last and mut == "sh_split_drop":
+            continue
+        if last:
+            s1 += {"sh_short": -1, "sh_overrun": 1}.get(mut, 0)
+        pos = np.arange(SH_SUB * s0, SH_SUB * s1)
+        segs.append((1, through(lead, pos), qrow, hr, 1.01 if mut == "sh_scale*1.01" else 1.0, mut == "sh_v_scale"))
+    return segs
+
+
+def _shared_applies(case, mut):
+    if mut in ("col_neighbour",):
+        return any(len(t["rows"]) > 1 for t in case.tiles)
+    if mut == "tile2_drop":
+        return any([t["g"] for t in case.tiles].count(g) > 1 for g in range(len(case.group_tokens)))
+    if mut == "sh_split_drop":
+        return any(len(case.shared_chunks(m[0])) > 1 for m in case.members)
+    if mut == "sh_wrong_kv_head":
+        return case.Hkv > 1
+    if mut == "sh_v_scale":
+        return case.fmt == "i8"
+    if mut == "other_table":
+        return any(case.group[r] != case.group[0] for r in range(case.B))
+    return mut is None or mut in SHARED_MUTANTS
+
+
+def _ref64_shared(case, mut=None, gather=False):
+    """float64 result of the three launches on a SharedCase (own splits, shared splits, the two-part merge); gather: instead the
+    identity (slot * Hkv + kv head) of the top-scoring key per (row, head), -1 where none is visible"""
+    if not _shared_applies(case, mut):
+        return None
+    D, H, grp = case.D, case.H, case.grp
+    q = case.qkv[:, :H * D].astype(np.float64).reshape(case.T, H, D)
+    out = np.zeros((case.T, H, D))
+    ident = np.full((case.T, H), -1, dtype=np.int64)
+    memo = {}
+
+    def rd(kv, hr, sl, shift):
+        key = (kv, hr, shift, sl.tobytes())
+        if key not in memo:
+            memo[key] = case.read(kv, hr, sl, group_shift=shift)
+        return memo[key]
+
+    for b in range(case.B):
+        for hk in range(case.Hkv):
+            part = [[], []]
+            best = np.full(grp, -np.inf)
+            for p, sl, qrow, hr, f, vshift in _shared_segments(case, b, hk, mut):
+                if len(sl) == 0:
+                    continue
+                s = (q[qrow, hk * grp:(hk + 1) * grp] @ rd(0, hr, sl, False).T) * (f / math.sqrt(D))   # [grp, keys]
+                if gather:
+                    top = s.argmax(-1)
+                    sc = s[np.arange(grp), top]
+                    upd = sc > best
+                    best = np.where(upd, sc, best)
+                    ident[b, hk * grp:(hk + 1) * grp] = np.where(upd, sl[top] * case.Hkv + hr, ident[b, hk * grp:(hk + 1) * grp])
+                    continue
+                m = s.max(-1, keepdims=True)
+                e = np.exp(s - m)
+                part[p].append((m, e.sum(-1, keepdims=True), e @ rd(1, hr, sl, vshift)))
+            if gather:
+                continue
+            merged = []
+            for rows in part:   # each part's splits by log-sum-exp
+                if rows:
+                    mm = np.max([m for m, _, _ in rows], axis=0)
+                    merged.append((mm, sum(l * np.exp(m - mm) for m, l, _ in rows), sum(o * np.exp(m - mm) for m, _, o in rows)))
+            mm = np.max([m for m, _, _ in merged], axis=0)
+            w = [np.ones_like(m) if mut == "merge_nomax" else np.exp(m - mm) for m, _, _ in merged]
+            out[b, hk * grp:(hk + 1) * grp] = sum(o * x for (_, _, o), x in zip(merged, w)) / sum(l * x for (_, l, _), x in zip(merged, w))
+    return ident if gather else out.reshape(case.T, H * D)
+
+
+def shared_teeth(case, want=None):
+    """{mutant: max |mutant - ref64| / bar} of a SharedCase (None: does not apply)"""
+    want = ref64(case) if want is None else want
+    bar = bar_of(case, want)
+    res = {}
+    for mname in SHARED_MUTANTS:
+        got = ref64(case, mname)
+        res[mname] = None if got is None else float((np.abs(got - want) / bar).max())
+    return res
+
+
+def f2_shared(case, family, where):
+    """an F2 family on a SharedCase; where: the part that carries the competing keys / the sink / the newest level -- 'shared', 'own'
+    or 'straddle' (both sides of P).  Members of a group alternate between two query variants (two direction sets); the shared rows
+    hold one score pattern per variant, so the neighbouring request of a tile scores the shared keys differently."""
+    rng, D, grp = case.rng, case.D, case.grp
+    Hd = hadamard(D)
+    case.family, case.where = family, where
+    dsv = [[dirs_of(case, gi)[v] for gi in range(grp)] for v in range(2)]
+    f = _group_factor(case)
+    top = RISE_STEP * (int(case.kvlen.max()) // P3_BN + 2)
+
+    def sigma(P, own, shared_part):
+        """scores [grp, P] of a group's shared keys, or [grp, own] of a row's own keys behind P shared ones; the designed positions"""
+        n, lo = P + own, (0 if shared_part else P)
+        cnt = P if shared_part else own
+        j = lo + np.arange(cnt)
+        sig = np.zeros((grp, cnt))
+        spec = set()
+        mine = where == "straddle" or (where == "shared") == shared_part or P == 0   # does this part carry the designed mass?
+        if shared_part:
+            ch = [(SH_SUB * a, SH_SUB * b) for a, b in shared_split_ranges(P, case.shared_split) if a < b]
+            edges = sorted({0, P - 1, SH_SUB - 1, min(SH_SUB, P - 1), ch[-1][0], max(ch[-1][0] - 1, 0), P - SH_SUB})
+        else:
+            edges = sorted({0, own - 1} | {x for beg, _ in own_chunks(own, case.own_split, gqa_form(case.fmt, case.H, case.Hkv, D))[1:]
+                                           for x in (beg - 1, beg)})
+        for gi in range(grp):
+            if family == "compete":
+                sig[gi] = -math.log(n) + 0.5 + 0.3 * rng.randn(cnt)
+                if mine:
+                    picks = [P - 1 if shared_part else 0] + [edges[(gi * 5 + k * 3) % len(edges)] for k in range(3)]
+                    for p, o in zip(picks, rng.permutation([0.0, -0.6, -1.4, -2.5])):
+                        sig[gi, p] = 2.0 + o
+                        spec.add(p)
+            elif family == "sink":
+                sig[gi] = 0.5 * rng.randn(cnt)
+                if mine:
+                    p = (P - 1 if where == "straddle" else 0) if shared_part else 0
+                    sig[gi, p] = math.log(max(n - 1, 1)) - (0.7 if where == "straddle" and P else 0.0)
+                    spec.add(p)
+                if not shared_part:
+                    sig[gi, own - 1] = max(sig[gi, own - 1], math.log(max(n - 1, 1)) - 1.0)
+                    spec.add(own - 1)
+            else:   # rising over the absolute position; 'shared': the own keys far below every shared level
+                sig[gi] = RISE_STEP * (j // P3_BN) + RISE_RAMP * (j % P3_BN) / P3_BN + 0.05 * rng.randn(cnt)
+                if where == "shared" and not shared_part and P:
+                    sig[gi] -= top
+                spec.update(p for p in edges)
+        return sig, spec
+
+    def values(cnt, spec):
+        V = np.clip(0.8 + 0.9 * rng.randn(case.Hkv, cnt, D), -3, 3) * f
+        for p in spec:
+            V[:, p] = np.clip(-1.0 + 1.2 * rng.randn(case.Hkv, D), -3, 3) * f
+        return V.astype(np.float32)
+
+    for g, P in enumerate(case.group_tokens):
+        P = int(P)
+        own = int(np.median(case.own[case.members[g]]))
+        spec = set()
+        for v in range(2):
+            sig, sp = sigma(P, own, True)
+            spec |= sp
+            for hk in range(case.Hkv):
+                case.KS[g][hk] += (sig.T @ Hd[dsv[v]] / math.sqrt(D)).astype(np.float32)
+        case.VS[g][:] = values(P, spec)
+    for b in range(case.B):
+        v = case.rank[b] % 2 if case.group[b] >= 0 else 0
+        sig, spec = sigma(int(case.P[b]), int(case.own[b]), False)
+        for hk in range(case.Hkv):
+            case.K[b][hk] = (sig.T @ Hd[dsv[v]] / math.sqrt(D)).astype(np.float32)
+        case.V[b][:] = values(int(case.own[b]), spec)
+        case.special[b] = sorted(int(case.P[b]) + p for p in spec)
+        for hq in range(case.H):
+            case.Q[b, hq] = Hd[dsv[v][hq % grp]]
+    case.finish()
+    if family == "rising" and where != "shared":
+        check_rising(case)
+    return case
+
+
+OWN_LENS = [1, 2, 15, 16, 17, 33, 130, 700]
+
+
+def _shared_rows(pattern, own_lens=OWN_LENS):
+    """rows of a spec from a string of group letters ('A', 'B', ... in order of first use; '.': a loose row); own lengths cycle
+    through own_lens; a lower-case letter is a member with start_pos == P (one own key)"""
+    names = []
+    rows = []
+    for k, ch in enumerate(pattern):
+        if ch == ".":
+            rows.append((-1, own_lens[k % len(own_lens)]))
+            continue
+        if ch.upper() not in names:
+            names.append(ch.upper())
+        rows.append((names.index(ch.upper()), 1 if ch.islower() else own_lens[k % len(own_lens)]))
+    return rows
+
+
+def f1_shared_specs():
+    """formats x (H, Hkv, D) of groups 1 / 3 / 6 / 8 / 16 (16 / 5 / 2 / 2 / 1 requests per tile, 0 / 1 / 4 / 0 / 0 padding columns) x
+    pages of 16 / 32 / 48 / 64 x the four layouts x shared splits 1 / 3 / 4 x own splits 2 / 3"""
+    S = []
+
+    def add(fmt, H, Hkv, D, ps, layout, ss, os_, groups, pattern):
+        k = len(S)
+        S.append(dict(name=f"sh_{fmt}_{H}x{Hkv}x{D}_p{ps}_l{layout}_s{ss}o{os_}_" + "_".join(str(g) for g in groups), fmt=fmt, H=H, Hkv=Hkv,
+                      D=D, groups=groups, rows=_shared_rows(pattern), page_size=ps, layout=layout, shared_split=ss, own_split=os_,
+                      seed=300 + k))
+
+    # P = 2048 with 17 members at group 1 (a full tile + a tile of one member and 15 padding columns), P = 16, loose rows between
+    add("f16", 4, 4, 128, 16, 3, 4, 2, [2048, 16], "AAA.AAAABAAAAA.AAAAbA...")
+    # two groups whose tiles interleave in row order (19 + 8 members at group 1: tiles of 16 + 3 and of 8), a member at start_pos == P
+    add("i8", 4, 4, 128, 16, 2, 3, 3, [272, 48], "ABAABAA.ABAAAbAABAAAA.ABAaAABAA")
+    # group 3: five requests and a padding column per tile; pages of 48 (no shift: the division path)
+    add("i8", 6, 2, 64, 48, 2, 3, 3, [48, 96], "AAB.AAABAAa.BAAAAbAAA.AA")
+    add("f16", 6, 2, 64, 16, 1, 4, 2, [272, 16], "AAAAAA.BAAAAAAb.AAAAaAAA")
+    # group 6: two requests and four padding columns per tile; P = 4096 with two members
+    add("f16", 12, 2, 128, 32, 0, 4, 2, [64, 4096], "AAAB.AAAAAAaB.AAAAAAAA.AA")
+    add("i8", 12, 2, 128, 16, 3, 1, 3, [272, 48], "AAAAAB.AAABAAAAb.AAAAAAA")
+    # group 8
+    add("i8", 8, 1, 128, 64, 1, 3, 3, [4096, 128], "AB.BBBBBABBbBB.BBBBBB.BB")
+    add("f16", 8, 1, 128, 48, 0, 4, 2, [240, 48], "AAAAB.AAAABAAAAb.AAAAaAA")
+    # group 16: one request per tile
+    add("f16", 16, 1, 64, 16, 3, 3, 2, [272, 48, 16], "AABC.AAABAAC.AAAAbAAA.AA")
+    add("i8", 16, 1, 64, 32, 2, 1, 3, [64, 2048], "AAAB.AAAAAAaB.AAAAAAAA.A")
+    return S
+
+
+def _f2_rows(where):
+    lens = {"straddle": [1, 2, 15, 16, 17, 33], "own": [130, 700, 130, 257], "shared": [1, 17, 130, 33, 2]}[where]
+    return _shared_rows("AAB.AABA.ABA", lens)
+
+
+def _f2s(family, where, fmt, H, Hkv, D, ps, layout, ss, os_, groups):
+    return (family, where, dict(name=f"f2_sh_{family}_{where}_{fmt}_{H}x{Hkv}x{D}_p{ps}_s{ss}o{os_}", fmt=fmt, H=H, Hkv=Hkv, D=D,
+                                groups=groups, rows=_f2_rows(where), page_size=ps, layout=layout, shared_split=ss, own_split=os_, seed=5))
+
+
+# 12 rows each: group A of 7 members (more than one tile from group 3 up), group B of 3, two loose rows.  'rising' on fp16 K (see F2_SPECS)
+F2_SHARED_SPECS = [
+    _f2s("compete", "straddle", "i8", 12, 2, 128, 16, 3, 3, 2, [272, 48]),
+    _f2s("compete", "shared", "f16", 6, 2, 64, 48, 2, 4, 2, [288, 48]),
+    _f2s("compete", "own", "i8", 4, 4, 128, 32, 3, 1, 3, [288, 64]),
+    _f2s("sink", "straddle", "f16", 8, 1, 128, 64, 1, 3, 2, [320, 64]),
+    _f2s("sink", "shared", "i8", 16, 1, 64, 16, 3, 4, 2, [272, 16]),
+    _f2s("sink", "own", "i8", 6, 2, 64, 16, 0, 3, 3, [272, 48]),
+    _f2s("rising", "straddle", "f16", 4, 4, 128, 16, 3, 3, 2, [272, 48]),
+    _f2s("rising", "shared", "f16", 12, 2, 128, 32, 2, 4, 2, [288, 96]),
+    _f2s("rising", "own", "f16", 8, 1, 128, 48, 3, 3, 3, [288, 48]),
+]
+
+
+def make_shared(spec, family=None, where=None):
+    """SharedCase of a spec: F1, or an F2 family with its mass in `where`"""
+    c = SharedCase(**spec)
+    return f1_shared(c) if family is None else f2_shared(c, family, where)

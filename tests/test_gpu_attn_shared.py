@@ -1,5 +1,7 @@
 """Shared-prefix decode attention (pplhip_op_attention_shared: own part + attn_decode_shared_kernel + merge) against a float64 numpy
-reference: dequantise the cache, softmax(q K^T / sqrt(D)) V per row and head.  Bound: test_attention_decode's (tests/test_gpu_ops.py)."""
+reference: dequantise the cache, softmax(q K^T / sqrt(D)) V per row and head.  Bound: test_attention_decode's (tests/test_gpu_ops.py).
+Pages of 16 in every case, and the same rows on pages of 32, 48 and 64 (test_attention_shared_page_sizes).  Exact needles and sharp
+softmax inputs on this path: tests/test_gpu_attn_shared_sharp.py."""
 import ctypes as C
 import functools
 
@@ -17,12 +19,15 @@ PS = 16
 KIND = ["L" if b in (2, 8, 17) else ("B" if b in (4, 12) else "A") for b in range(24)]
 OWN = {"A": [1, 15, 16, 17, 130, 33, 2], "B": [17, 1], "L": [1, 50, 300]}   # keys of a row's own (loose rows: all its keys)
 SHARED = {"A": 48, "B": 272, "L": 0}
+# shared tokens of groups A and B on the other page sizes (multiples of the page; B keeps an odd number of sub-tiles or of pages)
+SHARED_OF = {16: SHARED, 32: {"A": 64, "B": 288, "L": 0}, 48: {"A": 48, "B": 240, "L": 0}, 64: {"A": 64, "B": 320, "L": 0}}
 
 
 class Case:
-    def __init__(self, H, Hkv, D, quant, layout, dominant=None):
+    def __init__(self, H, Hkv, D, quant, layout, dominant=None, PS=PS):
         rng = np.random.RandomState(H * 7 + D + quant + layout)
-        self.H, self.Hkv, self.D, self.quant, self.layout = H, Hkv, D, quant, layout
+        self.H, self.Hkv, self.D, self.quant, self.layout, self.PS = H, Hkv, D, quant, layout, PS
+        SHARED = SHARED_OF[PS]
         seen = {"A": 0, "B": 0, "L": 0}
         own = []
         for k in KIND:
@@ -35,13 +40,14 @@ class Case:
         npg = (self.kv_len + PS - 1) // PS
         self.max_pages = int(npg.max())
         own_pg = npg - self.P // PS
-        free = list(rng.permutation(int(own_pg.sum()) + 3 + 17 + 4))
-        shared_pages = {"A": [free.pop() for _ in range(3)], "B": [free.pop() for _ in range(17)], "L": []}   # written once, every member points at them
+        n_sh = {k: SHARED[k] // PS for k in "AB"}   # (pages of 16: 3 and 17)
+        free = list(rng.permutation(int(own_pg.sum()) + n_sh["A"] + n_sh["B"] + 4))
+        shared_pages = {"A": [free.pop() for _ in range(n_sh["A"])], "B": [free.pop() for _ in range(n_sh["B"])], "L": []}   # written once, every member points at them
         self.pages = np.full((self.B, self.max_pages), np.iinfo(np.int64).max, dtype=np.int64)
         for b, k in enumerate(KIND):
             self.pages[b, :npg[b]] = shared_pages[k] + [free.pop() for _ in range(own_pg[b])]
         self.group = np.array([{"A": 0, "B": 1, "L": -1}[k] for k in KIND], dtype=np.int32)
-        self.group_tokens = np.array([48, 272], dtype=np.int64)
+        self.group_tokens = np.array([SHARED["A"], SHARED["B"]], dtype=np.int64)
         self.N = (len(free) + int(own_pg.sum()) + 20) * PS
         # the slab of 2 layers as [layer, k/v, (slot, head | head, slot), channel]; layer 1 is used
         shape = (2, 2, self.N, Hkv, D) if layout == 2 else (2, 2, Hkv, self.N, D)
@@ -69,6 +75,7 @@ class Case:
         self.want, self.margin = self.reference(dominant)
 
     def reference(self, dominant):
+        PS = self.PS
         kv = self.cache[1].astype(np.float64)
         if self.quant:
             kv = kv * np.repeat(self.scale[1].astype(np.float64), 8, axis=-1)
@@ -98,7 +105,7 @@ class Case:
         v.cache, v.scale = dcache.data_ptr(), (dscale.data_ptr() if self.quant else None)
         v.max_tokens, v.num_layers, v.kv_heads, v.head_dim = self.N, 2, self.Hkv, self.D
         v.quant_bit, v.quant_group = self.quant, (quant_group or (8 if self.quant else 1))
-        v.layout, v.mode, v.page_size, v.layer = self.layout, 1, PS, 1
+        v.layout, v.mode, v.page_size, v.layer = self.layout, 1, self.PS, 1
         need = m.lib().pplhip_op_attention_shared_workspace_bytes(self.B, self.H, self.D, self.max_pages, own_split, shared_split)
         ws = torch.empty(need - ws_short, dtype=torch.uint8, device="cuda")
         out = torch.zeros((self.B, self.H * self.D), dtype=torch.float16, device="cuda") if out is None else out
@@ -117,9 +124,9 @@ def check(got, want):
 
 
 @functools.lru_cache(maxsize=None)
-def shape_case(H, Hkv, D, quant, layout):
+def shape_case(H, Hkv, D, quant, layout, PS=PS):
     """one case (and its reference) per shape, shared by the two splits"""
-    return Case(H, Hkv, D, quant, layout)
+    return Case(H, Hkv, D, quant, layout, PS=PS)
 
 
 @pytest.mark.parametrize("shared_split", [1, 3])
@@ -129,6 +136,19 @@ def shape_case(H, Hkv, D, quant, layout):
 def test_attention_shared(quant, layout, H, Hkv, D, shared_split):
     m = load_pplhip()
     case = shape_case(H, Hkv, D, quant, layout)
+    rc, got = case.run(m, shared_split)
+    assert rc == 0, rc
+    check(got, case.want)
+
+
+@pytest.mark.parametrize("shared_split", [1, 3])
+@pytest.mark.parametrize("quant", [0, 8])
+@pytest.mark.parametrize("page_size,layout,H,Hkv,D", [(ps, 2 + (k + j) % 2, *shape) for k, ps in enumerate((32, 48, 64)) for j, shape in
+                                                      enumerate([(4, 4, 128), (8, 2, 64), (16, 1, 128), (12, 2, 128)])])
+def test_attention_shared_page_sizes(page_size, layout, H, Hkv, D, quant, shared_split):
+    """the same rows, shapes, splits and bound on pages of 32, 48 (no shift: the division path) and 64"""
+    m = load_pplhip()
+    case = shape_case(H, Hkv, D, quant, layout, page_size)
     rc, got = case.run(m, shared_split)
     assert rc == 0, rc
     check(got, case.want)
