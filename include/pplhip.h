@@ -860,6 +860,39 @@ PPLHIP_API int pplhip_shared_prefix_info(pplhip_ctx* ctx, int rank, int64_t* gro
 PPLHIP_API uint64_t pplhip_op_attention_shared_workspace_bytes(int64_t B, int32_t num_heads, int32_t head_dim, int64_t max_pages,
                                                                int32_t own_split, int32_t shared_split);
 
+/* ---- sliding-window attention (Mistral's mask; csrc/k_attn_window.hip).  Arrived without a version bump: a client tells a library that has
+ * it by the symbol pplhip_sliding_window (dlsym).
+ * Window W >= 1: the query at absolute position p attends keys max(0, p - W + 1) .. p (W keys, its own included); everything else is
+ * pplhip_op_attention's arithmetic.  head_dim 128 and an fp16 or int8 (group 8) KV cache only, contiguous or paged.
+ * pplhip_op_window_shift: the decode rows' shifted forms.  Host arrays only, no HIP call, no device needed.  start_pos [decoding_batches],
+ * cache_indices [decoding_batches] (cache_mode 0) or [decoding_batches, max_pages] (cache_mode 1).  A row's first key is
+ * f = max(0, start_pos - W + 1).  cache_mode 0: pos_out = start_pos - f, table_out[b] = slot + f, skip_out = 0, *table_width = 1.
+ * cache_mode 1: the row's table starts at page f / page_size: pos_out = start_pos - (f / page_size) page_size, skip_out = f % page_size (the
+ * keys of that page in front of the window, which the kernels leave out), table_out [decoding_batches, *table_width] with *table_width the
+ * most pages a row still needs (room for decoding_batches x max_pages entries is enough).  Rows with f == 0 come back unchanged.
+ * *max_kv_len_out (may be NULL): the largest pos_out + 1. */
+PPLHIP_API int pplhip_op_window_shift(const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t decoding_batches,
+                                      int32_t cache_mode, int32_t page_size, int32_t window, int64_t* pos_out, int64_t* table_out,
+                                      int64_t* table_width, int32_t* skip_out, int64_t* max_kv_len_out);
+/* pplhip_op_attention under window W: decode rows through the shift above and the ordinary decode kernels (contiguous cache) or their
+ * skip-aware forms (paged cache), prefill and cache-prefill rows through the band prefill kernel, which walks only the key tiles that meet
+ * a query block's band.  Arguments as pplhip_op_attention; the workspace needs, behind its split-K partials, 512 + decoding_batches x
+ * (16 + 8 x max_pages) bytes for the shifted arrays (PPLHIP_INVALID_VALUE below that; none without decode rows), and the call waits for the stream once to read
+ * the decode rows' positions.  window <= 0, or window >= max_kv_len, is exactly pplhip_op_attention: the same launches, the same bits.
+ * PPLHIP_UNSUPPORTED before any HIP call (window > 0): head_dim other than 128, an fp8 or int4 KV cache. */
+PPLHIP_API int pplhip_op_attention_window(void* stream, const void* qkv, const pplhip_kv_view* kv, const int64_t* seq_starts,
+                                          const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
+                                          int64_t decoding_batches, int64_t max_seq_len, int64_t max_kv_len, int32_t num_heads,
+                                          int32_t split_k, void* workspace, uint64_t workspace_bytes, void* out, int32_t window);
+/* The same inside a context: every step's attention runs under window W (0: off, the default -- a context that never calls this allocates,
+ * uploads and launches exactly what a library without the feature does).  Call it between steps.  A step in which the window binds (some
+ * request's kv length exceeds W) uploads its decode rows' shifted arrays once and routes every chunk's attention through the launches above;
+ * the decode split heuristic sees min(max_kv_len, W + page_size - 1).  A context with a window set captures no decode graphs: the shifted
+ * arrays are an upload of the step's own, and the table width moves.  KV slots and pages behind the window stay allocated.
+ * PPLHIP_UNSUPPORTED (reason in pplhip_last_error(ctx, -1), nothing changed) where pplhip_op_attention_window would say so, and when
+ * shared-prefix detection is on; pplhip_shared_prefix refuses a context with a window set the same way. */
+PPLHIP_API int pplhip_sliding_window(pplhip_ctx* ctx, int32_t window);
+
 /* ---- mixture-of-experts feed-forward block (Mixtral; csrc/k_moe.hip).  Arrived without a version bump: a client tells a library that has
  * it by the symbol pplhip_moe (dlsym).
  * For a normed row x with E experts and k experts per token: router logits r_e = x . gate_e (gate fp16 [E, hidden], fp32 sums); the k largest

@@ -10,11 +10,14 @@ constexpr int DEC_UNROLL = 4;
 constexpr int DEC_MAX_WAVES = 8;
 
 // one workgroup's share: query head hq of decode request b, K-split sp of `split`; nw = waves of the block
-template <int QBIT, int D>
+// WIN (k_attn_window.hip, sliding-window rows on a paged cache whose positions and page table the host shifted, rt_window.cc): the row's
+// keys begin at skip[b] inside its first page, and the splits share [skip[b], kv_len) -- no key in front of it is loaded, none needs a mask
+template <int QBIT, int D, int WIN = 0>
 __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qkv, const KvAddr& kv, const int64_t* __restrict__ seq_starts,
                                                  const int64_t* __restrict__ start_pos, const int64_t* __restrict__ cache_indices,
                                                  int64_t max_pages, int H, int Hkv, int split, float* __restrict__ workspace,
-                                                 uint16_t* __restrict__ out, int hq, int64_t b, int sp, int nw, float* smem) {
+                                                 uint16_t* __restrict__ out, int hq, int64_t b, int sp, int nw, float* smem,
+                                                 const int32_t* __restrict__ skip = nullptr) {
     using C = AttnCfg<QBIT, D>;   // a lane holds one 16-byte piece of a row: CH channels
     constexpr int CH = C::CH, LPT = C::LPT, TPW = C::TPW;
     // smem: [nw][D + 2] floats, provided by the caller
@@ -28,8 +31,9 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
 
     const int64_t kv_len = start_pos[b] + 1;  // decode row: one new token at position start_pos[b]
     // token range of this split
-    const int64_t per = (kv_len + split - 1) / split;
-    const int64_t tbeg = sp * per;
+    const int64_t first = WIN ? skip[b] : 0;
+    const int64_t per = (kv_len - first + split - 1) / split;
+    const int64_t tbeg = first + sp * per;
     const int64_t tend = (tbeg + per < kv_len) ? tbeg + per : kv_len;
 
     // q fragment (unscaled fp16 -> fp32); the softmax scale is applied to the score

@@ -127,6 +127,28 @@ hipError_t launch_attn_decode_gqa(hipStream_t s, const uint16_t* qkv, const KvAd
                                   int64_t max_pages, int64_t nb, int H, int Hkv, int D, int split, float* workspace,
                                   uint16_t* out, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
+// ---- k_attn_window.hip: sliding-window attention (window W: position p attends keys max(0, p - W + 1) .. p) ----
+// head_dim 128, KV_FP16 / KV_I8G8, both cache modes
+bool attn_window_supported(int kv_fmt, int D);
+// requests [b0, B): band attention of their new tokens (the band prefill kernel; no workspace, no split-KV form)
+hipError_t launch_attn_prefill_window(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
+                                      const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t b0, int64_t B, int H,
+                                      int Hkv, int D, int64_t max_seq_len, int window, uint16_t* out);
+// decode rows [0, nb) of a PAGED cache whose positions and page table window_shift (below) shifted: launch_attn_decode's kernels in their
+// WIN form, keys below skip[b] left out; split > 1 ends in launch_attn_reduce.  (A contiguous cache needs no kernel of its own: shifted
+// slots and positions go to launch_attn_decode.)
+hipError_t launch_attn_decode_window(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
+                                     const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, const int32_t* skip, int64_t nb,
+                                     int H, int Hkv, int D, int split, int threads, float* workspace, uint16_t* out);
+// ---- rt_window.cc: the host side of the above (a pure function, no HIP call) ----
+// Decode rows [0, nb) under window W: f = max(0, start_pos - W + 1) is a row's first key.  cache_mode 0: pos_out = start_pos - f,
+// table_out[b] = slot + f (width 1), skip_out = 0.  cache_mode 1: the row's table starts at page f / page_size -- table_out is [nb, width],
+// width = the most pages a row still needs (entries past a row's own need repeat what the source table holds there, 0 past its end);
+// pos_out = start_pos - (f / page_size) page_size, skip_out = f % page_size.  Rows with f == 0 come back unchanged.  table_out may be
+// NULL: sizes only.  Returns the width; *max_kv_len_out = the largest pos_out + 1.
+int64_t window_shift(const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t nb, int cache_mode, int page_size,
+                     int64_t window, int64_t* pos_out, int64_t* table_out, int32_t* skip_out, int64_t* max_kv_len_out);
+
 // ---- k_attn_decode_shared.hip: shared-prefix decode attention -----------------------------------------
 // up to 16 query rows (request, head of one KV head's group) of ONE prefix group: requests row[0], row[grp], ... (n of them; column c
 // belongs to request c / grp, row[c] = -1 marks padding) over the group's shared keys [0, tokens), addressed through the page table of

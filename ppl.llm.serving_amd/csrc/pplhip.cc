@@ -281,6 +281,7 @@ void pplhip_destroy(pplhip_ctx* c) {
         if (R.pages_host) hipHostFree(R.pages_host);
         if (R.pages_dev) hipFree(R.pages_dev);
         shared_prefix_release(R);
+        window_release(R);
         for (void* p : {(void*)R.h_rand, (void*)R.h_srows, (void*)R.h_tlp_in, (void*)R.h_tlp_out, (void*)R.h_plp_out}) if (p) hipHostFree(p);
         if (R.gd_bytes) hipFree(R.gd_bytes);
         if (R.gd_off) hipFree(R.gd_off);
@@ -989,6 +990,7 @@ int pplhip_set_inputs(pplhip_ctx* c, int rank, const pplhip_step* st) {
     }
     if (c->d.cache_mode == 1) R.d_ci = R.pages_dev;
     if (R.sp_min_rows > 0) shared_prefix_stage(R, st);   // shared-prefix decode attention (opt-in): the groups are formed at the run, per chunk
+    if (c->window > 0) window_stage(c, R, st);           // sliding-window attention (opt-in): the decode rows are shifted at the run
     R.B = B; R.T = T;
     R.decoding_batches = st->decoding_batches;
     R.max_seq_len = st->max_seq_len;
@@ -1163,7 +1165,19 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
         if (int rc = shared_prefix_attention(c, rank, lane, kv, *shared, split, threads)) return rc;
         prof_end(R, lane, &ev);
     }
-    if (k.nd > 0 && !shared) {
+    // sliding window that binds in this step (rt_window.cc): decode rows on their shifted arrays, prefill rows on the band kernel
+    const bool windowed = c->window > 0 && window_active(c, R);
+    if (windowed && k.nd > 0) {
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_DECODE, &ev, /*in_light_mode=*/true);
+        if (int rc = window_attention_decode(c, rank, lane, kv, k, split, threads)) return rc;
+        prof_end(R, lane, &ev);
+    }
+    if (windowed && k.bn > k.nd) {
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_PREFILL, &ev);
+        if (int rc = window_attention_prefill(c, rank, lane, kv, k)) return rc;
+        prof_end(R, lane, &ev);
+    }
+    if (k.nd > 0 && !shared && !windowed) {
         // light profiling: the launch carries its own start / stop events (timestamps of the dispatch packet, no barrier
         // packets on the stream; with split-K the reduce kernel is not included)
         const bool light = c->o.enable_profiling == 2;
@@ -1180,7 +1194,7 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
         if (light) R.prof.push_back(ev);
         else prof_end(R, lane, &ev);
     }
-    if (k.bn > k.nd) {
+    if (k.bn > k.nd && !windowed) {
         prof_begin(c, R, lane, PPLHIP_PROF_ATTN_PREFILL, &ev);
         // (decode requests own one token row each, so the prefill requests' rows are [t0 + nd, t0 + tn): the split-KV form for short suffixes)
         HIPCK(c, rank, launch_attn_prefill(s, R.qkv, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci, R.max_pages, k.b0 + k.nd,
@@ -1284,8 +1298,9 @@ static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& set
 
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     if (settings.dual_mode && settings.has_stream2) (void)hipStreamIsCapturing(s, &cst);   // (only a two-lane step depends on it)
-    const pplhip_step_shape shape{B, T, R.decoding_batches, R.max_kv_len, R.h_seq, cst != hipStreamCaptureStatusNone, R.dump_dev != nullptr,
-                                  R.lora_ntiles > 0};
+    // (under a binding sliding window a decode row reads at most W + page_size - 1 keys: the split heuristic sees that length)
+    const pplhip_step_shape shape{B, T, R.decoding_batches, c->window > 0 ? window_split_kv_len(c, R) : R.max_kv_len, R.h_seq,
+                                  cst != hipStreamCaptureStatusNone, R.dump_dev != nullptr, R.lora_ntiles > 0};
     const StepPlan p = plan_step(settings, shape);
     const Chunk* ck = p.chunk;
     const int nck = p.num_chunks;
@@ -1301,6 +1316,8 @@ static int run_launches(pplhip_ctx* c, int rank, const pplhip_plan_settings& set
     auto lane_of = [&](int i) -> Lane& { return lane[dual ? i : 0]; };
 
     if (int rc0 = shared_prefix_plan(c, rank, p)) return rc0;   // (feature off: clears pplhip_shared_prefix_info's counters, nothing else)
+    if (c->window > 0)
+        if (int rc0 = window_plan(c, rank)) return rc0;
     ProfEvent ev_run, ev;
     prof_begin(c, R, lane[0], PPLHIP_PROF_RUN, &ev_run);
     HIPCK(c, rank, launch_embedding(s, R.d_tok, R.embed, T, hd, R.h));
@@ -1410,6 +1427,7 @@ static int run_decode_graph(pplhip_ctx* c, int rank, const pplhip_plan_settings&
     if (!c->graph_on || c->tp_on || c->o.enable_profiling || R.T != B || nb_decode != B || B > c->graph_max_batch) return 0;
     if (R.lora_ntiles > 0) return 0;   // the tile list is this step's own: neither captured nor replayed
     if (R.sp_min_rows > 0) return 0;   // (so are the shared-prefix tile lists, formed per chunk at the run)
+    if (c->window > 0) return 0;       // (and the sliding window's shifted rows: an upload per step, a table width that moves)
     const uint64_t key = (uint64_t)B | ((uint64_t)decode_split(settings, B, R.max_kv_len) << 24) | ((uint64_t)R.max_pages << 32);
     auto it = R.graphs.find(key);
     if (it == R.graphs.end()) {  // first sight: run eagerly (one-time function attributes, lazily loaded code objects)

@@ -384,6 +384,17 @@ struct Rank {
     float* sp_ws = nullptr;                           // shared partial rows [cap_B][H][SP_SPLIT_MAX][D + 2]
     int64_t sp_last[3] = {0, 0, 0};                   // groups, rows in groups, shared tokens of the last run (summed over its chunks)
 
+    // sliding-window attention (pplhip_sliding_window, rt_window.cc; k_attn_window.hip; the window itself is pplhip_ctx::window).  Off: nothing
+    // below is touched.  On: pplhip_set_inputs keeps the decode rows' positions (and slots of a contiguous cache); the run, in front of the
+    // first layer, shifts them and the page table to each row's window and uploads one block -- positions | table [rows, win_width] | skips --
+    // through a double-buffered stage.  A chunk's decode rows read their part of it.
+    std::vector<int64_t> win_start_pos, win_slots;
+    char* win_dev = nullptr;
+    uint64_t win_cap = 0;                             // bytes of win_dev and of each stage
+    Stage st_win[2];
+    int st_win_cur = 0;
+    int64_t win_nd = 0, win_width = 1, win_max_kv = 0;   // decode rows in the block (0: this step has none), table width, largest shifted kv length
+
     // mixture of experts (pplhip_moe, rt_moe.cc): the step's routing buffers and expert rows (k_moe.hip), null in a dense context
     void* moe_ws = nullptr;
     bool moe_counts_clean = false;                    // the workspace's expert counts are zero (every launch leaves them so)
@@ -444,6 +455,7 @@ struct pplhip_ctx {
     int64_t graph_max_batch = 64;    // above this a step is seconds of GPU work per thousand launches: nothing to gain
     int H = 0, Hkv = 0, D = 0, inter = 0, vocab_local = 0;
     int moe_E = 0, moe_k = 0;        // pplhip_moe: experts and experts per token (0: a dense model)
+    int32_t window = 0;              // pplhip_sliding_window: attention window in tokens (0: off)
     bool weights_touched = false;    // a tensor was set, loaded or generated: pplhip_moe comes too late
     std::vector<Rank> ranks;
     std::string err;
@@ -501,6 +513,21 @@ const Rank::SpChunk* shared_prefix_chunk(const pplhip_ctx* c, const Rank& R, con
 // the chunk's decode attention through the shared path: own part, shared part, merge
 int shared_prefix_attention(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const Rank::SpChunk& sc, int split, int threads);
 void shared_prefix_release(Rank& R);
+// rt_window.cc
+// the window binds in the staged step (on, and some request's kv length exceeds it): only then does a step leave the ordinary launches
+bool window_active(const pplhip_ctx* c, const Rank& R);
+// pplhip_set_inputs: keeps the decode rows' start_pos (and slots) on the host (no HIP call)
+void window_stage(const pplhip_ctx* c, Rank& R, const pplhip_step* st);
+// the kv length the decode split heuristic sees: min(max_kv_len, W + page_size - 1) where the window binds
+int64_t window_split_kv_len(const pplhip_ctx* c, const Rank& R);
+// run_launches, once per step in front of the first layer: shifts the decode rows to their windows and uploads what the launches read
+int window_plan(pplhip_ctx* c, int rank);
+// the chunk's attention under the window: its decode rows (k.nd > 0) through the shifted arrays, its prefill rows (k.bn > k.nd) through the
+// band kernel -- two calls, so that the caller books them under their own profiling classes
+int window_attention_decode(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const pplhip_chunk& k, int split, int threads);
+int window_attention_prefill(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const pplhip_chunk& k);
+void window_release(Rank& R);
+KvAddr view_kv_addr(const pplhip_kv_view* v);   // rt_ops.cc
 // rt_moe.cc
 bool moe_find_tensor(pplhip_ctx* c, Rank& R, Layer& L, const char* rest, void** ptr, uint64_t* bytes, Linear** lin);
 int moe_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const Layer& L, const uint16_t* xn, int64_t tn, uint16_t* out);

@@ -403,6 +403,8 @@ static KvAddr view_addr(const pplhip_kv_view* v) {
     return make_kv_addr(d, v->kv_heads, v->head_dim, (uint64_t)v->max_tokens, v->cache, (uint16_t*)v->scale, v->layer);
 }
 
+KvAddr view_kv_addr(const pplhip_kv_view* v) { return view_addr(v); }   // (for rt_window.cc's operator)
+
 int pplhip_op_rope_kv_write(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
                             const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
                             int32_t num_heads) {

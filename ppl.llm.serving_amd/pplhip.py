@@ -190,6 +190,7 @@ SYMBOLS = [
     "pplhip_op_attention", "pplhip_build_rope_table",
     "pplhip_op_shared_prefix_groups", "pplhip_op_attention_shared", "pplhip_op_attention_shared_workspace_bytes",
     "pplhip_shared_prefix", "pplhip_shared_prefix_info",
+    "pplhip_op_window_shift", "pplhip_op_attention_window", "pplhip_sliding_window",
     "pplhip_moe", "pplhip_op_moe_route", "pplhip_op_moe_ffn", "pplhip_op_moe_ffn_workspace_bytes", "pplhip_op_moe_tile_rows",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
 ]
@@ -315,6 +316,11 @@ def lib():
             L.pplhip_op_attention_shared_workspace_bytes.restype = u64
             L.pplhip_shared_prefix.argtypes = [vp, i32, i64]
             L.pplhip_shared_prefix_info.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        if hasattr(L, "pplhip_sliding_window"):   # (PPLHIP_LIB may name a build from before sliding-window attention)
+            L.pplhip_op_window_shift.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, vp, C.POINTER(i64), vp, C.POINTER(i64)]
+            L.pplhip_op_attention_window.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
+                                                     vp, u64, vp, i32]
+            L.pplhip_sliding_window.argtypes = [vp, i32]
         if hasattr(L, "pplhip_moe"):   # (PPLHIP_LIB may name a build from before the mixture-of-experts block)
             L.pplhip_moe.argtypes = [vp, i32, i32]
             L.pplhip_op_moe_route.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]
@@ -333,6 +339,19 @@ def lib():
                                                  C.c_char_p, i32]
         _LIB = L
     return _LIB
+
+
+def window_shift(start_pos, cache_indices, cache_mode, page_size, window):
+    """pplhip_op_window_shift on host arrays (start_pos [nb]; cache_indices [nb] or [nb, max_pages]):
+    (status, positions [nb], table [nb, width], skip [nb], largest shifted kv length)"""
+    sp = np.ascontiguousarray(start_pos, dtype=np.int64)
+    ci = np.ascontiguousarray(cache_indices, dtype=np.int64)
+    nb, mp = len(sp), (ci.shape[1] if cache_mode == 1 else 1)
+    pos, tab, skip = np.empty(nb, np.int64), np.empty(nb * mp, np.int64), np.empty(nb, np.int32)
+    width, max_kv = C.c_int64(), C.c_int64()
+    rc = lib().pplhip_op_window_shift(sp.ctypes.data, ci.ctypes.data, mp, nb, cache_mode, page_size, window, pos.ctypes.data, tab.ctypes.data,
+                                      C.byref(width), skip.ctypes.data, C.byref(max_kv))
+    return rc, pos, tab[:nb * width.value].reshape(nb, max(width.value, 1)) if rc == 0 else tab, skip, max_kv.value
 
 
 def linear_route(x, w, scale, wq_bit, group, M, N, K, y, ldy, epi, ws=None, ws_bytes=0, dry_run=True, stream=None):
@@ -696,6 +715,10 @@ class Context:
     def shared_prefix(self, min_rows, min_tokens):
         """shared-prefix decode attention on (min_rows > 0) or off (0)"""
         self._ck(lib().pplhip_shared_prefix(self.h, min_rows, min_tokens), -1, "shared_prefix")
+
+    def sliding_window(self, window):
+        """sliding-window attention: position p attends keys max(0, p - window + 1) .. p (0: off)"""
+        self._ck(lib().pplhip_sliding_window(self.h, window), -1, "sliding_window")
 
     def moe(self, num_experts, experts_per_token):
         """a mixture-of-experts model: call it before any weight is loaded (pplhip_moe)"""

@@ -385,6 +385,13 @@ RetCode HipResourceManager::Init(const ModelConfig& mc, const ResourceConfig& rc
             return FromPplHipStatus(ms);
         }
     }
+    if (mc.sliding_window > 0) {   // a windowed model served causally gives wrong logits past W tokens: refuse what the kernels cannot window
+        const int ws = pplhip_sliding_window(ctx, mc.sliding_window);
+        if (ws) {
+            LOG(ERROR) << "pplhip_sliding_window(" << mc.sliding_window << ") failed: " << pplhip_last_error(ctx, -1);
+            return FromPplHipStatus(ws);
+        }
+    }
     tensor_parallel_size = (uint32_t)tp;
     items.resize(tp);
     runtimes.resize(tp);

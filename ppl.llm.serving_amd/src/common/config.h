@@ -97,6 +97,7 @@ struct ModelConfig final {
     int32_t weight_quant_group = 128;  // W4A16 group size along K
     int32_t num_experts = 0;           // mixture of experts (Mixtral): experts per layer, 0 = a dense model; intermediate_dim is one expert's
     int32_t experts_per_token = 0;     // ... and how many of them a token is routed to
+    int32_t sliding_window = 0;        // attention window in tokens (Mistral: position p attends keys p - W + 1 .. p); absent, null or 0 = off
 };
 
 bool ParseModelConfig(const std::string& model_param_path, ModelConfig* model_config);

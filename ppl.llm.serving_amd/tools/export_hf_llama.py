@@ -166,6 +166,8 @@ def params_json(cfg, args):
         p["page_size"] = args.page_size
     if cfg.get("model_type") == "mixtral":
         p["num_experts"], p["experts_per_token"] = cfg["num_local_experts"], cfg["num_experts_per_tok"]
+    if cfg.get("sliding_window") is not None:   # (Mistral, the first Mixtral checkpoints; absent or null: no key, the file as it always was)
+        p["sliding_window"] = int(cfg["sliding_window"])
     return p
 
 
@@ -185,8 +187,8 @@ def main(argv=None):
     ap.add_argument("--page-size", type=int, default=16)
     args = ap.parse_args(argv)
     cfg = json.load(open(os.path.join(args.model_dir, "config.json")))
-    if cfg.get("model_type", "llama") not in ("llama", "mixtral"):
-        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA nor Mixtral")
+    if cfg.get("model_type", "llama") not in ("llama", "mistral", "mixtral"):   # (Mistral: LLaMA's tensors plus a sliding window)
+        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA, Mistral nor Mixtral")
     sd = load_state_dict(args.model_dir)
     slices = convert(sd, cfg, args.tensor_parallel_size, args.quant, args.quant_group)
     os.makedirs(args.out, exist_ok=True)

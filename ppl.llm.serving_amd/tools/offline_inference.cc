@@ -38,6 +38,8 @@ int main(int argc, char** argv) {
     a.Def("--guide-json-schema", "", "prompts4 / samples1024: guided decoding, every answer is a JSON document that fits the schema in this FILE "
                                      "(src/common/guide_json.h; needs --tokenizer-path; a scenario gives each request its own "
                                      "\"guide_json_schema\")");
+    a.Def("--sliding-window", "0", "attention window in tokens (position p attends keys p - N + 1 .. p); overrides params.json's "
+                                   "\"sliding_window\"; 0: what params.json says");
     if (!a.Parse(argc, argv)) return -1;
     if (a.Bool("--help")) { a.PrintHelp(); return 0; }
 
@@ -45,6 +47,7 @@ int main(int argc, char** argv) {
     GeneratorConfig gc;
     ModelConfig mc;
     if (!tools::FillConfigs(a, &rc, &gc, &mc)) return -1;
+    if (a.Int("--sliding-window") > 0) mc.sliding_window = a.Int("--sliding-window");
     utils::JsonValue scn;
     if (a.Str("--workload") == "scenario") {
         if (!scenario::LoadScenario(a.Str("--scenario-file"), &scn)) {
