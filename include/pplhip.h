@@ -927,6 +927,30 @@ PPLHIP_API int32_t pplhip_op_moe_tile_rows(int64_t T, int32_t experts_per_token,
  * feed_forward.w2 already loaded; afterwards pplhip_lora_set_tensor refuses feed_forward.w2 the same way. */
 PPLHIP_API int pplhip_moe(pplhip_ctx* ctx, int32_t num_experts, int32_t experts_per_token);
 
+/* ---- QKV bias and per-head QK-norm (Qwen2 / Qwen3; csrc/k_rope_prologue.hip).  Arrived without a version bump: a client tells a library
+ * that has it by the symbol pplhip_qkv_prologue (dlsym).
+ * Between the wqkv projection (and any adapter update of it) and the rotation, for a token row y of the fused qkv [T, (H + 2 Hkv) D]:
+ * bias != NULL: a = fp16(fp32(y) + fp32(bias[col])) on every q, k and v column, bias fp16 [(H + 2 Hkv) D] in wqkv's row order;
+ * q_norm / k_norm != NULL (both or neither): every q and every k head row, never v, becomes n[i] = fp16(fp32(a[i]) / sqrt(mean_i(a[i]^2) + eps)
+ * * fp32(w[i])), the mean over the head's D channels in fp32, w = q_norm for q heads and k_norm for k heads, fp16 [D] shared by the heads.
+ * Then rotation, the in-place q store and the cache write exactly as pplhip_op_rope_kv_write_ex does them, in every cache format, in the
+ * same single pass.  The three pointers are device pointers, 16-byte aligned.  All three NULL: pplhip_op_rope_kv_write_ex itself, the same
+ * launch and bits.  PPLHIP_INVALID_VALUE: one norm weight without the other; with the norm on, a head_dim that is no power of two >= 32
+ * or a negative eps. */
+PPLHIP_API int pplhip_op_rope_kv_write_prologue(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv,
+                                                const int64_t* seq_starts, const int64_t* start_pos, const int64_t* cache_indices,
+                                                int64_t max_pages, int64_t B, int64_t t0, int64_t T, int32_t num_heads, const float* slab_ws,
+                                                int32_t slab_splits, const void* slab_scale, int64_t slab_M, const void* bias,
+                                                const void* q_norm, const void* k_norm, float eps);
+/* The same inside a context: call it after pplhip_init and before any weight is loaded, with qkv_bias and / or qk_norm non-zero.  Every
+ * layer of every rank gets layers.L.attention.wqkv.bias (fp16 [(H + 2 Hkv) D / world_size], the rank's slice in its wqkv's row order,
+ * zeros) and / or layers.L.attention.q_norm.weight and layers.L.attention.k_norm.weight (fp16 [head_dim], replicated, ones), which
+ * pplhip_rank_set_tensor and pplhip_rank_load then accept and pplhip_rank_init_synthetic leaves alone; every step's RoPE + KV write runs
+ * the operator above with them and eps, also inside captured decode graphs.  A context that never calls it allocates and launches exactly
+ * what it did before.  PPLHIP_INVALID_VALUE behind a loaded or generated weight, on a second call, with both switches zero, or where the
+ * operator would say so. */
+PPLHIP_API int pplhip_qkv_prologue(pplhip_ctx* ctx, int32_t qkv_bias, int32_t qk_norm, float eps);
+
 /* The direct collectives (csrc/k_comm.hip) as operators, for a context whose ranks all live in this process and run the direct mode
  * (pplhip_comm_mode == 2).  One call runs a SEQUENCE of collectives: every item is enqueued on every local rank from the calling thread,
  * back to back on the ranks' streams with no host synchronisation in between, then every rank is synchronised.  Channel 0 runs on the

@@ -90,6 +90,19 @@ hipError_t launch_rope_kv_write(hipStream_t s, uint16_t* qkv, const float* cos_s
                                 int Hkv, int D, const SplitSlabs* qkv_slabs = nullptr);  // token rows [t0, t0 + T) of the step's B requests;
                                                    // qkv_slabs: the rows come from unreduced split-K slabs of a [T, N] launch (slab row = token row - t0); rotated q -> qkv
 
+// ---- k_rope_prologue.hip ----------------------------------------------------------------------
+// What Qwen2 / Qwen3 put between the wqkv projection and the rotation (each part NULL: off; q_norm and k_norm come together):
+// bias fp16 [(H + 2 Hkv) D] added to every q, k and v column, then RMSNorm(eps) with weights q_norm / k_norm fp16 [D] over every q / k head row
+struct QkvPrologue {
+    const uint16_t* bias = nullptr;
+    const uint16_t *q_norm = nullptr, *k_norm = nullptr;
+    float eps = 0.f;
+};
+// launch_rope_kv_write with the prologue in front of the rotation, in the same pass; all parts NULL: launch_rope_kv_write itself
+hipError_t launch_rope_kv_prologue(hipStream_t s, uint16_t* qkv, const float* cos_sin, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
+                                   const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0, int64_t T,
+                                   int H, int Hkv, int D, const SplitSlabs* qkv_slabs, const QkvPrologue& pr);
+
 // ---- k_attn_decode.hip ------------------------------------------------------------------------
 // rows [0, nb) of the batch are single-token queries; q row of request b is qkv row seq_starts[b].
 // split > 1 uses `workspace` (fp32 [nb, H, split, D+2]).

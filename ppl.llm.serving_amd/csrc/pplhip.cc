@@ -84,6 +84,7 @@ bool find_tensor(pplhip_ctx* c, Rank& R, const char* name, void** ptr, uint64_t*
     Layer& L = R.layers[l];
     if (!strcmp(rest, "attention_norm.weight")) { *ptr = L.attn_norm; *bytes = (uint64_t)hd * 2; return true; }
     if (!strcmp(rest, "ffn_norm.weight")) { *ptr = L.ffn_norm; *bytes = (uint64_t)hd * 2; return true; }
+    if (c->qkv_prologue && qkv_prologue_find_tensor(c, L, rest, ptr, bytes)) return true;
     if (c->moe_E && !strncmp(rest, "feed_forward.", 13)) return moe_find_tensor(c, R, L, rest, ptr, bytes, lin_out);   // gate and experts; no dense w13 / w2
     struct { const char* n; Linear* lin; } tab[] = {{"attention.wqkv", &L.wqkv}, {"attention.wo", &L.wo},
                                                       {"feed_forward.w13", &L.w13}, {"feed_forward.w2", &L.w2}};
@@ -1151,8 +1152,12 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
     prof_end(R, lane, &ev);
     if (int rc = layer_lora(c, rank, lane, l, LORA_WQKV, R.xn, hd, R.qkv, nqkv, hd)) return rc;
     const KvAddr kv = make_kv_addr(d, Hkv, D, R.kv_tokens, R.kv_cache, R.kv_scale, l);
-    HIPCK(c, rank, launch_rope_kv_write(s, R.qkv, R.rope, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci,
-                                        R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &lane.sl_qkv));
+    if (c->qkv_prologue)   // Qwen's bias / head norms in front of the rotation, in the same pass (k_rope_prologue.hip)
+        HIPCK(c, rank, launch_rope_kv_prologue(s, R.qkv, R.rope, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci,
+                                               R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &lane.sl_qkv, L.pro));
+    else
+        HIPCK(c, rank, launch_rope_kv_write(s, R.qkv, R.rope, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci,
+                                            R.max_pages, R.B, k.t0, k.tn, H, Hkv, D, &lane.sl_qkv));
     lane.sl_qkv = SplitSlabs{};
     // decode rows of the chunk: per-request arrays shifted to the chunk (q rows stay absolute through seq_starts);
     // prefill requests: absolute request range

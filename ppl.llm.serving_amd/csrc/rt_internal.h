@@ -47,6 +47,7 @@ struct Layer {
     uint16_t* ffn_norm = nullptr;
     Linear wqkv, wo, w13, w2;        // mixture of experts (rt_moe.cc): w13 / w2 are ONE expert's shape over E stacked experts
     uint16_t* moe_gate = nullptr;    // router matrix fp16 [E, hidden]
+    QkvPrologue pro;                 // pplhip_qkv_prologue (rt_qkv_prologue.cc): wqkv's bias and the q / k head norms, null in a LLaMA context
 };
 
 // One adapter slot of a rank: per (layer, target) the two factors on the device, zero-padded to rank rp (a multiple of 16) and, for w2's
@@ -456,7 +457,8 @@ struct pplhip_ctx {
     int H = 0, Hkv = 0, D = 0, inter = 0, vocab_local = 0;
     int moe_E = 0, moe_k = 0;        // pplhip_moe: experts and experts per token (0: a dense model)
     int32_t window = 0;              // pplhip_sliding_window: attention window in tokens (0: off)
-    bool weights_touched = false;    // a tensor was set, loaded or generated: pplhip_moe comes too late
+    bool weights_touched = false;    // a tensor was set, loaded or generated: pplhip_moe / pplhip_qkv_prologue come too late
+    bool qkv_prologue = false;       // pplhip_qkv_prologue was called: the layers' Layer::pro are in use
     std::vector<Rank> ranks;
     std::string err;
 };
@@ -531,6 +533,8 @@ KvAddr view_kv_addr(const pplhip_kv_view* v);   // rt_ops.cc
 // rt_moe.cc
 bool moe_find_tensor(pplhip_ctx* c, Rank& R, Layer& L, const char* rest, void** ptr, uint64_t* bytes, Linear** lin);
 int moe_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const Layer& L, const uint16_t* xn, int64_t tn, uint16_t* out);
+// rt_qkv_prologue.cc: "attention.wqkv.bias", "attention.q_norm.weight", "attention.k_norm.weight" of a layer -> the device range
+bool qkv_prologue_find_tensor(const pplhip_ctx* c, const Layer& L, const char* rest, void** ptr, uint64_t* bytes);
 // rt_postproc.cc
 int sample_row_list(const int32_t* top_k, const float* min_p, const float* typical_p, int B, int32_t* rows, int* n_trunc);
 int top_logprobs_row_list(const int32_t* num_logprobs, int B, int32_t* rows);

@@ -461,6 +461,21 @@ int pplhip_op_rope_kv_write_ex(void* stream, void* qkv, const float* cos_sin, co
                                       max_pages, B, t0, T, num_heads, kv->kv_heads, kv->head_dim, &sl));
 }
 
+// the same with Qwen's prologue in front of the rotation (k_rope_prologue.hip); all three NULL: the call above
+int pplhip_op_rope_kv_write_prologue(void* stream, void* qkv, const float* cos_sin, const pplhip_kv_view* kv, const int64_t* seq_starts,
+                                     const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t t0, int64_t T,
+                                     int32_t num_heads, const float* slab_ws, int32_t slab_splits, const void* slab_scale, int64_t slab_M,
+                                     const void* bias, const void* q_norm, const void* k_norm, float eps) {
+    const int fmt = kv ? kv_format(kv->quant_bit, kv->quant_group, kv->head_dim) : -1;
+    if (fmt < 0 || t0 < 0 || T < 0 || B < 0) return PPLHIP_INVALID_VALUE;
+    SplitSlabs sl;
+    if (!op_slabs(slab_ws, slab_splits, slab_scale, slab_M, (num_heads + 2 * kv->kv_heads) * kv->head_dim, &sl)) return PPLHIP_INVALID_VALUE;
+    QkvPrologue pr;
+    pr.bias = (const uint16_t*)bias; pr.q_norm = (const uint16_t*)q_norm; pr.k_norm = (const uint16_t*)k_norm; pr.eps = eps;
+    return op_rc(launch_rope_kv_prologue((hipStream_t)stream, (uint16_t*)qkv, cos_sin, view_addr(kv), fmt, seq_starts, start_pos, cache_indices,
+                                         max_pages, B, t0, T, num_heads, kv->kv_heads, kv->head_dim, &sl, pr));
+}
+
 // launch_linear (fp16 epilogue) with a non-null `defer`, as layer_linear calls it for wqkv / wo / w2: a split-K route leaves its slabs in ws
 int pplhip_op_linear_defer(void* stream, const void* x, const void* w, const void* scale, int32_t wq_bit, int32_t group, int64_t M, int32_t N,
                            int32_t K, void* y, int64_t ldy, void* ws, uint64_t ws_bytes, int32_t dry_run, int32_t* splits,

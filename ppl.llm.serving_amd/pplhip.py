@@ -193,6 +193,7 @@ SYMBOLS = [
     "pplhip_op_window_shift", "pplhip_op_attention_window", "pplhip_sliding_window",
     "pplhip_moe", "pplhip_op_moe_route", "pplhip_op_moe_ffn", "pplhip_op_moe_ffn_workspace_bytes", "pplhip_op_moe_tile_rows",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
+    "pplhip_op_rope_kv_write_prologue", "pplhip_qkv_prologue",
 ]
 
 
@@ -337,6 +338,10 @@ def lib():
             L.pplhip_op_rope_kv_write_ex.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i32, vp, i32, vp, i64]
             L.pplhip_op_linear_defer.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, i64, vp, u64, i32, C.POINTER(i32), C.POINTER(vp),
                                                  C.c_char_p, i32]
+        if hasattr(L, "pplhip_qkv_prologue"):   # (PPLHIP_LIB may name a build from before the QKV bias / QK-norm prologue)
+            L.pplhip_op_rope_kv_write_prologue.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i32, vp, i32, vp, i64,
+                                                           vp, vp, vp, f32]
+            L.pplhip_qkv_prologue.argtypes = [vp, i32, i32, f32]
         _LIB = L
     return _LIB
 
@@ -719,6 +724,10 @@ class Context:
     def sliding_window(self, window):
         """sliding-window attention: position p attends keys max(0, p - window + 1) .. p (0: off)"""
         self._ck(lib().pplhip_sliding_window(self.h, window), -1, "sliding_window")
+
+    def qkv_prologue(self, qkv_bias=False, qk_norm=False, eps=1e-6):
+        """Qwen2's bias on wqkv and / or Qwen3's RMSNorm on the q and k head rows: call it before any weight is loaded (pplhip_qkv_prologue)"""
+        self._ck(lib().pplhip_qkv_prologue(self.h, int(qkv_bias), int(qk_norm), eps), -1, "qkv_prologue")
 
     def moe(self, num_experts, experts_per_token):
         """a mixture-of-experts model: call it before any weight is loaded (pplhip_moe)"""

@@ -392,6 +392,13 @@ RetCode HipResourceManager::Init(const ModelConfig& mc, const ResourceConfig& rc
             return FromPplHipStatus(ws);
         }
     }
+    if (mc.qkv_bias || mc.qk_norm) {   // Qwen2 / Qwen3: the tensors must exist before the containers are read
+        const int qs = pplhip_qkv_prologue(ctx, mc.qkv_bias, mc.qk_norm, mc.norm_eps);
+        if (qs) {
+            LOG(ERROR) << "pplhip_qkv_prologue(" << mc.qkv_bias << ", " << mc.qk_norm << ") failed: " << pplhip_last_error(ctx, -1);
+            return FromPplHipStatus(qs);
+        }
+    }
     tensor_parallel_size = (uint32_t)tp;
     items.resize(tp);
     runtimes.resize(tp);

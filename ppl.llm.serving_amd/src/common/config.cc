@@ -65,6 +65,8 @@ bool ParseModelConfigFromString(const std::string& text, ModelConfig* mc) {
     mc->weight_quant_group = (int32_t)doc.GetInt("weight_quant_group", mc->weight_quant_group);
     mc->num_experts = (int32_t)doc.GetInt("num_experts", mc->num_experts);
     mc->experts_per_token = (int32_t)doc.GetInt("experts_per_token", mc->experts_per_token);
+    mc->qkv_bias = doc.GetBool("qkv_bias", mc->qkv_bias);
+    mc->qk_norm = doc.GetBool("qk_norm", mc->qk_norm);
     if (const utils::JsonValue* v = doc.Find("sliding_window")) {   // (HF writes null where a checkpoint has no window)
         if (v->type == utils::JsonValue::NUMBER && v->AsInt() >= 0) mc->sliding_window = (int32_t)v->AsInt();
         else if (v->type != utils::JsonValue::NUL) {

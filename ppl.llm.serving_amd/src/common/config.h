@@ -98,6 +98,8 @@ struct ModelConfig final {
     int32_t num_experts = 0;           // mixture of experts (Mixtral): experts per layer, 0 = a dense model; intermediate_dim is one expert's
     int32_t experts_per_token = 0;     // ... and how many of them a token is routed to
     int32_t sliding_window = 0;        // attention window in tokens (Mistral: position p attends keys p - W + 1 .. p); absent, null or 0 = off
+    bool qkv_bias = false;             // Qwen2: a bias on the q / k / v projections (layers.L.attention.wqkv.bias)
+    bool qk_norm = false;              // Qwen3: an RMSNorm (norm_eps) over every q and k head row (layers.L.attention.q_norm / k_norm.weight)
 };
 
 bool ParseModelConfig(const std::string& model_param_path, ModelConfig* model_config);

@@ -18,6 +18,12 @@ num_experts / experts_per_token (intermediate_dim is one expert's), every layer 
 per expert J `layers.L.feed_forward.experts.J.w13` (HF w1 = gate rows, then w3 = up rows) and `...experts.J.w2`, quantised like the dense
 tensors.  Both HF layouts are read: per-expert `block_sparse_moe.experts.J.w1/w2/w3` and the stacked `mlp.experts.gate_up_proj / down_proj`.
 
+A Qwen2 / Qwen2.5 checkpoint (model_type "qwen2") is LLaMA plus a bias on the q / k / v projections: params.json gets qkv_bias and every
+layer `layers.L.attention.wqkv.bias`, the three biases fused and sliced in wqkv's row order.  A Qwen3 dense checkpoint (model_type "qwen3")
+is LLaMA plus an RMSNorm over every q and k head row: params.json gets qk_norm and every layer `layers.L.attention.q_norm.weight` /
+`k_norm.weight` ([head_dim], the same on every rank), and the bias too where the checkpoint has attention_bias.  Both need
+head_dim * num_attention_heads == hidden_size: the model description derives head_dim.
+
     python export_hf_llama.py --model-dir /path/to/hf_llama --out /path/to/model --tensor-parallel-size 2 --quant w8a16
 """
 import argparse
@@ -94,8 +100,18 @@ def quant_w4(w, group):
     return packed, scale
 
 
+def qwen_prologue(cfg):
+    """(qkv_bias, qk_norm) of a checkpoint: what stands between its wqkv projection and the rotation"""
+    mt = cfg.get("model_type")
+    return mt == "qwen2" or (mt == "qwen3" and bool(cfg.get("attention_bias"))), mt == "qwen3"
+
+
 def convert(sd, cfg, tp, quant, group):
     """-> list of per-rank {name: array} in container naming"""
+    qkv_bias, qk_norm = qwen_prologue(cfg)
+    if (qkv_bias or qk_norm) and cfg.get("head_dim", cfg["hidden_size"] // cfg["num_attention_heads"]) * cfg["num_attention_heads"] != cfg["hidden_size"]:
+        raise ValueError(f"head_dim {cfg['head_dim']} x num_attention_heads {cfg['num_attention_heads']} is not hidden_size {cfg['hidden_size']}: "
+                         "the model description derives head_dim from the two")
     H, Hkv = cfg["num_attention_heads"], cfg.get("num_key_value_heads", cfg["num_attention_heads"])
     hd, inter, V, L = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"], cfg["num_hidden_layers"]
     D = hd // H
@@ -127,6 +143,13 @@ def convert(sd, cfg, tp, quant, group):
             q, k, v = sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"]
             put(f"layers.{l}.attention.wqkv", np.concatenate([q[r * h * D:(r + 1) * h * D], k[r * hk * D:(r + 1) * hk * D],
                                                                v[r * hk * D:(r + 1) * hk * D]], 0))
+            if qkv_bias:   # fused like wqkv's rows: the rank's q, k and v pieces
+                qb, kb, vb = sd[p + "self_attn.q_proj.bias"], sd[p + "self_attn.k_proj.bias"], sd[p + "self_attn.v_proj.bias"]
+                out[f"layers.{l}.attention.wqkv.bias"] = f16(np.concatenate([qb[r * h * D:(r + 1) * h * D], kb[r * hk * D:(r + 1) * hk * D],
+                                                                             vb[r * hk * D:(r + 1) * hk * D]]))
+            if qk_norm:
+                out[f"layers.{l}.attention.q_norm.weight"] = f16(sd[p + "self_attn.q_norm.weight"])
+                out[f"layers.{l}.attention.k_norm.weight"] = f16(sd[p + "self_attn.k_norm.weight"])
             put(f"layers.{l}.attention.wo", sd[p + "self_attn.o_proj.weight"][:, r * h * D:(r + 1) * h * D])
             if moe:
                 old = p + "block_sparse_moe.gate.weight" in sd
@@ -166,8 +189,14 @@ def params_json(cfg, args):
         p["page_size"] = args.page_size
     if cfg.get("model_type") == "mixtral":
         p["num_experts"], p["experts_per_token"] = cfg["num_local_experts"], cfg["num_experts_per_tok"]
-    if cfg.get("sliding_window") is not None:   # (Mistral, the first Mixtral checkpoints; absent or null: no key, the file as it always was)
+    qwen = cfg.get("model_type") in ("qwen2", "qwen3")   # (their configs name a window that use_sliding_window switches, usually off)
+    if cfg.get("sliding_window") is not None and (not qwen or cfg.get("use_sliding_window")):   # (Mistral, the first Mixtral checkpoints; absent or null: no key, the file as it always was)
         p["sliding_window"] = int(cfg["sliding_window"])
+    qkv_bias, qk_norm = qwen_prologue(cfg)   # (keys only for such checkpoints)
+    if qkv_bias:
+        p["qkv_bias"] = True
+    if qk_norm:
+        p["qk_norm"] = True
     return p
 
 
@@ -187,8 +216,8 @@ def main(argv=None):
     ap.add_argument("--page-size", type=int, default=16)
     args = ap.parse_args(argv)
     cfg = json.load(open(os.path.join(args.model_dir, "config.json")))
-    if cfg.get("model_type", "llama") not in ("llama", "mistral", "mixtral"):   # (Mistral: LLaMA's tensors plus a sliding window)
-        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA, Mistral nor Mixtral")
+    if cfg.get("model_type", "llama") not in ("llama", "mistral", "mixtral", "qwen2", "qwen3"):   # (Mistral: LLaMA's tensors plus a sliding window)
+        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA, Mistral, Mixtral, Qwen2 nor Qwen3")
     sd = load_state_dict(args.model_dir)
     slices = convert(sd, cfg, args.tensor_parallel_size, args.quant, args.quant_group)
     os.makedirs(args.out, exist_ok=True)
