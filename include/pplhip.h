@@ -951,6 +951,35 @@ PPLHIP_API int pplhip_op_rope_kv_write_prologue(void* stream, void* qkv, const f
  * operator would say so. */
 PPLHIP_API int pplhip_qkv_prologue(pplhip_ctx* ctx, int32_t qkv_bias, int32_t qk_norm, float eps);
 
+/* ---- ALiBi attention (per-head linear position bias: Baichuan-13B / Baichuan2-13B, Bloom, MPT; csrc/k_attn_alibi.hip).  Arrived without a
+ * version bump: a client tells a library that has it by the symbol pplhip_alibi (dlsym).
+ * q and k are NOT rotated.  For the query at absolute position p = start_pos[b] + i, the key at position j <= p and query head h:
+ * score = dot(q, k_j) / sqrt(head_dim) + slopes[h] * (j - p) in fp32; softmax, the fp32 running (m, l, O), the single rounding to fp16 and
+ * the K / V dequantisation are pplhip_op_attention's.  (HF adds slopes[h] * j per row; the softmax does not see the shift.)  Decode rows
+ * form the biased score in one fma; the prefill kernel's rounding is described in its file header.  A head with slope 0 gives
+ * pplhip_op_attention's bits.  Multi-head models with head_dim 128 and an fp16 or int8 (group 8) KV cache only, contiguous or paged.
+ * pplhip_op_alibi_slopes: the standard slopes of num_heads heads (Press et al., as HF builds them) into host_out [num_heads]: with n the
+ * largest power of two <= num_heads, head i < n gets 2^(-8 (i + 1) / n), the remaining heads 2^(-4 (2 t + 1) / n), t = 0, 1, ...  Host only,
+ * no HIP call.
+ * pplhip_op_attention_alibi: pplhip_op_attention's arguments and its routing of decode rows and other rows, plus slopes_device, fp32
+ * [num_heads] on the device.  The caller leaves q and k unrotated (pplhip_op_rope_kv_write with a table of cos 1 and sin 0 writes the cache
+ * as it is).  Prefill rows behind a cached prefix never take a split-KV form.  slopes_device == NULL is exactly pplhip_op_attention: the
+ * same launches.  PPLHIP_UNSUPPORTED before any HIP call: head_dim other than 128, num_heads != kv_heads, an fp8 or int4 KV cache. */
+PPLHIP_API int pplhip_op_alibi_slopes(int32_t num_heads, float* host_out);
+PPLHIP_API int pplhip_op_attention_alibi(void* stream, const void* qkv, const pplhip_kv_view* kv, const int64_t* seq_starts,
+                                         const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t B, int64_t T,
+                                         int64_t decoding_batches, int64_t max_seq_len, int64_t max_kv_len, int32_t num_heads,
+                                         int32_t split_k, void* workspace, uint64_t workspace_bytes, void* out, const float* slopes_device);
+/* The same inside a context: call it after pplhip_init and before the first step (keys already in the cache stay as they were written).
+ * slopes_host [num_heads] fp32, non-negative; NULL: the standard ones.  Uploads the slopes, replaces the context's cos / sin table by cos 1,
+ * sin 0 -- the RoPE + KV-write kernels run unchanged and leave q and k as they are, up to a zero's sign -- and routes every chunk's
+ * attention through the launches above, also inside captured decode graphs.  The QKV prologue, adapters, the mixture-of-experts block and
+ * quantised activations work as without it.  A context that never calls it allocates, uploads and launches exactly what it did before.
+ * PPLHIP_UNSUPPORTED (reason in pplhip_last_error(ctx, -1), nothing changed) where pplhip_op_attention_alibi would say so, with
+ * world_size > 1, with a sliding window set and when shared-prefix detection is on; pplhip_sliding_window and pplhip_shared_prefix refuse
+ * an ALiBi context the same way. */
+PPLHIP_API int pplhip_alibi(pplhip_ctx* ctx, const float* slopes_host);
+
 /* The direct collectives (csrc/k_comm.hip) as operators, for a context whose ranks all live in this process and run the direct mode
  * (pplhip_comm_mode == 2).  One call runs a SEQUENCE of collectives: every item is enqueued on every local rank from the calling thread,
  * back to back on the ranks' streams with no host synchronisation in between, then every rank is synchronised.  Channel 0 runs on the

@@ -12,12 +12,14 @@ constexpr int DEC_MAX_WAVES = 8;
 // one workgroup's share: query head hq of decode request b, K-split sp of `split`; nw = waves of the block
 // WIN (k_attn_window.hip, sliding-window rows on a paged cache whose positions and page table the host shifted, rt_window.cc): the row's
 // keys begin at skip[b] inside its first page, and the splits share [skip[b], kv_len) -- no key in front of it is loaded, none needs a mask
-template <int QBIT, int D, int WIN = 0>
+// ALIBI (k_attn_alibi.hip): the key at absolute position j gets slopes[hq] * (j - pos) on its scaled score, one fma; every split works on
+// absolute positions, so the partial rows merge as they always did.  ALIBI = 0 compiles to the code it was
+template <int QBIT, int D, int WIN = 0, int ALIBI = 0>
 __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qkv, const KvAddr& kv, const int64_t* __restrict__ seq_starts,
                                                  const int64_t* __restrict__ start_pos, const int64_t* __restrict__ cache_indices,
                                                  int64_t max_pages, int H, int Hkv, int split, float* __restrict__ workspace,
                                                  uint16_t* __restrict__ out, int hq, int64_t b, int sp, int nw, float* smem,
-                                                 const int32_t* __restrict__ skip = nullptr) {
+                                                 const int32_t* __restrict__ skip = nullptr, const float* __restrict__ slopes = nullptr) {
     using C = AttnCfg<QBIT, D>;   // a lane holds one 16-byte piece of a row: CH channels
     constexpr int CH = C::CH, LPT = C::LPT, TPW = C::TPW;
     // smem: [nw][D + 2] floats, provided by the caller
@@ -65,6 +67,7 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
         qsum[0] = s * 8.0f;
     }
     const float sm_scale = 1.0f / sqrtf((float)D);
+    const float slope = ALIBI ? slopes[hq] : 0.f;
 
     float m = -1e30f, l = 0.f;
     float acc[CH];
@@ -181,7 +184,10 @@ __device__ __forceinline__ void attn_decode_body(const uint16_t* __restrict__ qk
 #pragma unroll
             for (int o = 1; o < LPT; o <<= 1) d += __shfl_xor(d, o, 64);
             if constexpr (QBIT == KV_FP8) d *= h2f((uint16_t)ksc[u]);   // exact: a power of two
-            s[u] = valid[u] ? d * sm_scale : -1e30f;
+            if constexpr (ALIBI)   // j - pos <= 0, exact as a float (|j - pos| < 2^24); a masked key's distance is never used
+                s[u] = valid[u] ? fmaf(slope, (float)(int)(t0 + u * TPW + g - (kv_len - 1)), d * sm_scale) : -1e30f;
+            else
+                s[u] = valid[u] ? d * sm_scale : -1e30f;
         }
         float mnew = m;
 #pragma unroll

@@ -162,6 +162,18 @@ hipError_t launch_attn_decode_window(hipStream_t s, const uint16_t* qkv, const K
 int64_t window_shift(const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t nb, int cache_mode, int page_size,
                      int64_t window, int64_t* pos_out, int64_t* table_out, int32_t* skip_out, int64_t* max_kv_len_out);
 
+// ---- k_attn_alibi.hip: ALiBi attention (score + slopes[head] * (key position - query position), q and k not rotated) ----
+// multi-head (H == Hkv), head_dim 128, KV_FP16 / KV_I8G8, both cache modes; slopes: [H] fp32 on the device
+bool attn_alibi_supported(int kv_fmt, int H, int Hkv, int D);
+// requests [b0, B): causal attention of their new tokens under the bias (no workspace: the keys are never split)
+hipError_t launch_attn_prefill_alibi(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
+                                     const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t b0, int64_t B, int H,
+                                     int Hkv, int D, int64_t max_seq_len, const float* slopes, uint16_t* out);
+// decode rows [0, nb): the multi-head decode kernel in its ALIBI form; split > 1 ends in launch_attn_reduce
+hipError_t launch_attn_decode_alibi(hipStream_t s, const uint16_t* qkv, const KvAddr& kv, int kv_fmt, const int64_t* seq_starts,
+                                    const int64_t* start_pos, const int64_t* cache_indices, int64_t max_pages, int64_t nb, int H, int Hkv, int D,
+                                    int split, int threads, float* workspace, const float* slopes, uint16_t* out);
+
 // ---- k_attn_decode_shared.hip: shared-prefix decode attention -----------------------------------------
 // up to 16 query rows (request, head of one KV head's group) of ONE prefix group: requests row[0], row[grp], ... (n of them; column c
 // belongs to request c / grp, row[c] = -1 marks padding) over the group's shared keys [0, tokens), addressed through the page table of

@@ -1182,7 +1182,19 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
         if (int rc = window_attention_prefill(c, rank, lane, kv, k)) return rc;
         prof_end(R, lane, &ev);
     }
-    if (k.nd > 0 && !shared && !windowed) {
+    // ALiBi (rt_alibi.cc): every chunk's attention under the context's slopes; a window or shared-prefix detection cannot be on beside it
+    const bool alibi = c->alibi;
+    if (alibi && k.nd > 0) {
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_DECODE, &ev, /*in_light_mode=*/true);
+        if (int rc = alibi_attention_decode(c, rank, lane, kv, k, split, threads)) return rc;
+        prof_end(R, lane, &ev);
+    }
+    if (alibi && k.bn > k.nd) {
+        prof_begin(c, R, lane, PPLHIP_PROF_ATTN_PREFILL, &ev);
+        if (int rc = alibi_attention_prefill(c, rank, lane, kv, k)) return rc;
+        prof_end(R, lane, &ev);
+    }
+    if (k.nd > 0 && !shared && !windowed && !alibi) {
         // light profiling: the launch carries its own start / stop events (timestamps of the dispatch packet, no barrier
         // packets on the stream; with split-K the reduce kernel is not included)
         const bool light = c->o.enable_profiling == 2;
@@ -1199,7 +1211,7 @@ static int layer_attention_part(pplhip_ctx* c, int rank, Lane& lane, const StepP
         if (light) R.prof.push_back(ev);
         else prof_end(R, lane, &ev);
     }
-    if (k.bn > k.nd && !windowed) {
+    if (k.bn > k.nd && !windowed && !alibi) {
         prof_begin(c, R, lane, PPLHIP_PROF_ATTN_PREFILL, &ev);
         // (decode requests own one token row each, so the prefill requests' rows are [t0 + nd, t0 + tn): the split-KV form for short suffixes)
         HIPCK(c, rank, launch_attn_prefill(s, R.qkv, kv, c->kv_fmt, R.d_seq, R.d_sp, R.d_ci, R.max_pages, k.b0 + k.nd,

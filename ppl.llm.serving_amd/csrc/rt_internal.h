@@ -396,6 +396,9 @@ struct Rank {
     int st_win_cur = 0;
     int64_t win_nd = 0, win_width = 1, win_max_kv = 0;   // decode rows in the block (0: this step has none), table width, largest shifted kv length
 
+    // ALiBi attention (pplhip_alibi, rt_alibi.cc; k_attn_alibi.hip): the heads' slopes [H] fp32, null in a rotary context
+    float* alibi_slopes = nullptr;
+
     // mixture of experts (pplhip_moe, rt_moe.cc): the step's routing buffers and expert rows (k_moe.hip), null in a dense context
     void* moe_ws = nullptr;
     bool moe_counts_clean = false;                    // the workspace's expert counts are zero (every launch leaves them so)
@@ -457,6 +460,7 @@ struct pplhip_ctx {
     int H = 0, Hkv = 0, D = 0, inter = 0, vocab_local = 0;
     int moe_E = 0, moe_k = 0;        // pplhip_moe: experts and experts per token (0: a dense model)
     int32_t window = 0;              // pplhip_sliding_window: attention window in tokens (0: off)
+    bool alibi = false;              // pplhip_alibi was called: no rotation (an identity cos / sin table), every chunk's attention under the slopes
     bool weights_touched = false;    // a tensor was set, loaded or generated: pplhip_moe / pplhip_qkv_prologue come too late
     bool qkv_prologue = false;       // pplhip_qkv_prologue was called: the layers' Layer::pro are in use
     std::vector<Rank> ranks;
@@ -530,6 +534,10 @@ int window_attention_decode(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& k
 int window_attention_prefill(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const pplhip_chunk& k);
 void window_release(Rank& R);
 KvAddr view_kv_addr(const pplhip_kv_view* v);   // rt_ops.cc
+// rt_alibi.cc: the chunk's attention under the context's slopes -- its decode rows (k.nd > 0) and its prefill rows (k.bn > k.nd), two calls
+// so that the caller books them under their own profiling classes
+int alibi_attention_decode(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const pplhip_chunk& k, int split, int threads);
+int alibi_attention_prefill(pplhip_ctx* c, int rank, Lane& lane, const KvAddr& kv, const pplhip_chunk& k);
 // rt_moe.cc
 bool moe_find_tensor(pplhip_ctx* c, Rank& R, Layer& L, const char* rest, void** ptr, uint64_t* bytes, Linear** lin);
 int moe_ffn_part(pplhip_ctx* c, int rank, Lane& lane, const Layer& L, const uint16_t* xn, int64_t tn, uint16_t* out);

@@ -88,6 +88,7 @@ int pplhip_shared_prefix(pplhip_ctx* c, int32_t min_rows, int64_t min_tokens) {
     if (!c || min_rows < 0 || min_tokens < 0) return PPLHIP_INVALID_VALUE;
     if (min_rows > 0 && !attn_shared_supported(c->kv_fmt, c->d.cache_mode, c->d.page_size, c->H, c->Hkv, c->D)) return PPLHIP_UNSUPPORTED;
     if (min_rows > 0 && c->window > 0) return fail(c, -1, PPLHIP_UNSUPPORTED, "pplhip_shared_prefix: a sliding window is set in this context");
+    if (min_rows > 0 && c->alibi) return fail(c, -1, PPLHIP_UNSUPPORTED, "pplhip_shared_prefix: this context runs under ALiBi");
     for (int r = 0; r < (int)c->ranks.size(); ++r) {
         Rank& R = c->ranks[r];
         if (min_rows > 0 && !R.sp_ws) {   // everything whose size max_running_batch decides; the plan block follows the page-table width

@@ -135,6 +135,7 @@ int pplhip_sliding_window(pplhip_ctx* c, int32_t window) {
     if (window > 0) {
         const std::string why = window_refusal(c->d.cache_quant_bit, c->d.cache_quant_group, c->D);
         if (!why.empty()) return fail(c, -1, PPLHIP_UNSUPPORTED, "pplhip_sliding_window: " + why);
+        if (c->alibi) return fail(c, -1, PPLHIP_UNSUPPORTED, "pplhip_sliding_window: this context runs under ALiBi");
         for (const Rank& R : c->ranks)
             if (R.sp_min_rows > 0) return fail(c, -1, PPLHIP_UNSUPPORTED, "pplhip_sliding_window: shared-prefix detection is on in this context");
     }

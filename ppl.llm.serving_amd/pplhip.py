@@ -194,6 +194,7 @@ SYMBOLS = [
     "pplhip_moe", "pplhip_op_moe_route", "pplhip_op_moe_ffn", "pplhip_op_moe_ffn_workspace_bytes", "pplhip_op_moe_tile_rows",
     "pplhip_op_rmsnorm_form", "pplhip_op_rmsnorm_ex", "pplhip_op_gather_last_rows", "pplhip_op_rope_kv_write_ex", "pplhip_op_linear_defer",
     "pplhip_op_rope_kv_write_prologue", "pplhip_qkv_prologue",
+    "pplhip_op_alibi_slopes", "pplhip_op_attention_alibi", "pplhip_alibi",
 ]
 
 
@@ -342,6 +343,11 @@ def lib():
             L.pplhip_op_rope_kv_write_prologue.argtypes = [vp, vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i32, vp, i32, vp, i64,
                                                            vp, vp, vp, f32]
             L.pplhip_qkv_prologue.argtypes = [vp, i32, i32, f32]
+        if hasattr(L, "pplhip_alibi"):   # (PPLHIP_LIB may name a build from before ALiBi attention)
+            L.pplhip_op_alibi_slopes.argtypes = [i32, vp]
+            L.pplhip_op_attention_alibi.argtypes = [vp, vp, C.POINTER(KvView), vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, i32,
+                                                    vp, u64, vp, vp]
+            L.pplhip_alibi.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -724,6 +730,14 @@ class Context:
     def sliding_window(self, window):
         """sliding-window attention: position p attends keys max(0, p - window + 1) .. p (0: off)"""
         self._ck(lib().pplhip_sliding_window(self.h, window), -1, "sliding_window")
+
+    def alibi(self, slopes=None):
+        """ALiBi attention: no rotation, slopes[h] * (key position - query position) on every score; slopes [num_heads], None: the standard
+        ones.  Call it after init and before the first step (pplhip_alibi)"""
+        a = None if slopes is None else np.ascontiguousarray(slopes, dtype=np.float32)
+        if a is not None and a.shape != (self.desc.num_heads,):
+            raise PplHipError(f"alibi: {self.desc.num_heads} slopes expected, got shape {a.shape}")
+        self._ck(lib().pplhip_alibi(self.h, None if a is None else a.ctypes.data), -1, "alibi")
 
     def qkv_prologue(self, qkv_bias=False, qk_norm=False, eps=1e-6):
         """Qwen2's bias on wqkv and / or Qwen3's RMSNorm on the q and k head rows: call it before any weight is loaded (pplhip_qkv_prologue)"""

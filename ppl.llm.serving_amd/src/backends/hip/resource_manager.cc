@@ -392,6 +392,13 @@ RetCode HipResourceManager::Init(const ModelConfig& mc, const ResourceConfig& rc
             return FromPplHipStatus(ws);
         }
     }
+    if (mc.alibi) {   // an ALiBi model served with rotation gives wrong logits from the second token on: refuse what the kernels cannot serve
+        const int as = pplhip_alibi(ctx, NULL);
+        if (as) {
+            LOG(ERROR) << "pplhip_alibi failed: " << pplhip_last_error(ctx, -1);
+            return FromPplHipStatus(as);
+        }
+    }
     if (mc.qkv_bias || mc.qk_norm) {   // Qwen2 / Qwen3: the tensors must exist before the containers are read
         const int qs = pplhip_qkv_prologue(ctx, mc.qkv_bias, mc.qk_norm, mc.norm_eps);
         if (qs) {

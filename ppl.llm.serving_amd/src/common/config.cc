@@ -67,6 +67,7 @@ bool ParseModelConfigFromString(const std::string& text, ModelConfig* mc) {
     mc->experts_per_token = (int32_t)doc.GetInt("experts_per_token", mc->experts_per_token);
     mc->qkv_bias = doc.GetBool("qkv_bias", mc->qkv_bias);
     mc->qk_norm = doc.GetBool("qk_norm", mc->qk_norm);
+    mc->alibi = doc.GetInt("alibi", mc->alibi ? 1 : 0) != 0;   // (the exporter writes 1)
     if (const utils::JsonValue* v = doc.Find("sliding_window")) {   // (HF writes null where a checkpoint has no window)
         if (v->type == utils::JsonValue::NUMBER && v->AsInt() >= 0) mc->sliding_window = (int32_t)v->AsInt();
         else if (v->type != utils::JsonValue::NUL) {

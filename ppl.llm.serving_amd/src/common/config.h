@@ -97,7 +97,8 @@ struct ModelConfig final {
     int32_t weight_quant_group = 128;  // W4A16 group size along K
     int32_t num_experts = 0;           // mixture of experts (Mixtral): experts per layer, 0 = a dense model; intermediate_dim is one expert's
     int32_t experts_per_token = 0;     // ... and how many of them a token is routed to
-    int32_t sliding_window = 0;        // attention window in tokens (Mistral: position p attends keys p - W + 1 .. p); absent, null or 0 = off
+    bool alibi = false;                // ALiBi attention (Baichuan-13B): no rotation, the standard per-head slopes on the scores; absent or 0 = off
+    int32_t sliding_window = 0;       // attention window in tokens (Mistral: position p attends keys p - W + 1 .. p); absent, null or 0 = off
     bool qkv_bias = false;             // Qwen2: a bias on the q / k / v projections (layers.L.attention.wqkv.bias)
     bool qk_norm = false;              // Qwen3: an RMSNorm (norm_eps) over every q and k head row (layers.L.attention.q_norm / k_norm.weight)
 };

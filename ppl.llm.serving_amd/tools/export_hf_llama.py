@@ -106,7 +106,13 @@ def qwen_prologue(cfg):
     return mt == "qwen2" or (mt == "qwen3" and bool(cfg.get("attention_bias"))), mt == "qwen3"
 
 
-def convert(sd, cfg, tp, quant, group):
+def baichuan_head_is_normalised(cfg):
+    """Baichuan2 applies its lm_head with L2-normalised rows (NormHead); the config has no key for it.  Told from Baichuan (1) by the
+    vocabulary of the published Baichuan2 checkpoints, 125696 -- a rule from memory: --normalize-head / --no-normalize-head win"""
+    return cfg.get("model_type") == "baichuan" and cfg.get("vocab_size") == 125696
+
+
+def convert(sd, cfg, tp, quant, group, normalize_head=None):
     """-> list of per-rank {name: array} in container naming"""
     qkv_bias, qk_norm = qwen_prologue(cfg)
     if (qkv_bias or qk_norm) and cfg.get("head_dim", cfg["hidden_size"] // cfg["num_attention_heads"]) * cfg["num_attention_heads"] != cfg["hidden_size"]:
@@ -123,6 +129,9 @@ def convert(sd, cfg, tp, quant, group):
         raise ValueError("a mixture-of-experts model is exported at tensor-parallel size 1, fp16 or w8a16")
     f16 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float16)
     lm_head = sd.get("lm_head.weight", sd["model.embed_tokens.weight"])  # tied embeddings
+    if baichuan_head_is_normalised(cfg) if normalize_head is None else normalize_head:   # Baichuan2: the head the model applies, rows / their L2 norm
+        lm_head = np.asarray(lm_head, dtype=np.float32)
+        lm_head = lm_head / np.maximum(np.linalg.norm(lm_head, axis=1, keepdims=True), 1e-12)
     slices = []
     for r in range(tp):
         out = {"tok_embeddings.weight": f16(sd["model.embed_tokens.weight"]), "norm.weight": f16(sd["model.norm.weight"]),
@@ -140,7 +149,10 @@ def convert(sd, cfg, tp, quant, group):
             p = f"model.layers.{l}."
             out[f"layers.{l}.attention_norm.weight"] = f16(sd[p + "input_layernorm.weight"])
             out[f"layers.{l}.ffn_norm.weight"] = f16(sd[p + "post_attention_layernorm.weight"])
-            q, k, v = sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"]
+            if p + "self_attn.W_pack.weight" in sd:   # Baichuan: one packed projection, rows q | k | v
+                q, k, v = np.split(np.asarray(sd[p + "self_attn.W_pack.weight"]), [H * D, (H + Hkv) * D], axis=0)
+            else:
+                q, k, v = sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"]
             put(f"layers.{l}.attention.wqkv", np.concatenate([q[r * h * D:(r + 1) * h * D], k[r * hk * D:(r + 1) * hk * D],
                                                                v[r * hk * D:(r + 1) * hk * D]], 0))
             if qkv_bias:   # fused like wqkv's rows: the rank's q, k and v pieces
@@ -183,7 +195,7 @@ def params_json(cfg, args):
          "cache_quant_group": kv_group, "cache_layout": args.cache_layout, "cache_mode": args.cache_mode,
          "dynamic_batching": True, "auto_causal": True, "norm_eps": cfg.get("rms_norm_eps", 1e-5),
          "rope_theta": float(rope_theta if rope_theta is not None else 10000.0),
-         "max_position": cfg.get("max_position_embeddings", 4096),
+         "max_position": cfg.get("max_position_embeddings", cfg.get("model_max_length", 4096)),
          "weight_quant_bit": {"none": 0, "w8a16": 8, "w4a16": 4}[args.quant], "weight_quant_group": args.quant_group}
     if args.cache_mode == 1:
         p["page_size"] = args.page_size
@@ -192,6 +204,11 @@ def params_json(cfg, args):
     qwen = cfg.get("model_type") in ("qwen2", "qwen3")   # (their configs name a window that use_sliding_window switches, usually off)
     if cfg.get("sliding_window") is not None and (not qwen or cfg.get("use_sliding_window")):   # (Mistral, the first Mixtral checkpoints; absent or null: no key, the file as it always was)
         p["sliding_window"] = int(cfg["sliding_window"])
+    # ALiBi (Baichuan-13B / Baichuan2-13B): the flag, else a baichuan config without max_position_embeddings -- the 13B configs as
+    # published, from memory, which is why the flag wins.  Without the key the file is what it always was
+    alibi = getattr(args, "alibi", None)
+    if alibi if alibi is not None else (cfg.get("model_type") == "baichuan" and "max_position_embeddings" not in cfg):
+        p["alibi"] = 1
     qkv_bias, qk_norm = qwen_prologue(cfg)   # (keys only for such checkpoints)
     if qkv_bias:
         p["qkv_bias"] = True
@@ -214,12 +231,19 @@ def main(argv=None):
     ap.add_argument("--cache-layout", type=int, choices=[0, 1, 2, 3], default=3)
     ap.add_argument("--cache-mode", type=int, choices=[0, 1], default=0)
     ap.add_argument("--page-size", type=int, default=16)
+    ap.add_argument("--alibi", dest="alibi", action="store_true", default=None,
+                    help="ALiBi attention (no rotation): writes \"alibi\": 1 into params.json; default: a baichuan config without "
+                         "max_position_embeddings")
+    ap.add_argument("--no-alibi", dest="alibi", action="store_false")
+    ap.add_argument("--normalize-head", dest="normalize_head", action="store_true", default=None,
+                    help="export lm_head rows divided by their L2 norm (Baichuan2's NormHead); default: a baichuan config with Baichuan2's vocabulary")
+    ap.add_argument("--no-normalize-head", dest="normalize_head", action="store_false")
     args = ap.parse_args(argv)
     cfg = json.load(open(os.path.join(args.model_dir, "config.json")))
-    if cfg.get("model_type", "llama") not in ("llama", "mistral", "mixtral", "qwen2", "qwen3"):   # (Mistral: LLaMA's tensors plus a sliding window)
-        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA, Mistral, Mixtral, Qwen2 nor Qwen3")
+    if cfg.get("model_type", "llama") not in ("llama", "mistral", "mixtral", "qwen2", "qwen3", "baichuan"):   # (Mistral: LLaMA's tensors plus a sliding window)
+        sys.exit(f"model_type {cfg.get('model_type')} is neither LLaMA, Mistral, Mixtral, Qwen2, Qwen3 nor Baichuan")
     sd = load_state_dict(args.model_dir)
-    slices = convert(sd, cfg, args.tensor_parallel_size, args.quant, args.quant_group)
+    slices = convert(sd, cfg, args.tensor_parallel_size, args.quant, args.quant_group, args.normalize_head)
     os.makedirs(args.out, exist_ok=True)
     json.dump(params_json(cfg, args), open(os.path.join(args.out, "params.json"), "w"), indent=1)
     for r, tensors in enumerate(slices):
